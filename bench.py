@@ -4,9 +4,14 @@ synthetic EMOPIA-shaped batches: BASELINE.json configs[1] at N=1, configs[2] (DP
 
 One "step" = zero_grad + forward + CE loss + backward + grad all-reduce (N>1) + clip(0.5) + Adam +
 LR schedule + device-side accuracy counts, with dropout 0.1 active and omega redrawn every forward
-(reference-faithful).  Prints ONE JSON line on rank 0 (contract in the task statement) with
-`roofline` (dominant kernel, HIP-event timed on the launch stream) and `cpu_baseline` (the oracle's
-CPU training step timed on this box's host cores; N=1 only).
+(reference-faithful).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line; `--dump-outputs DIR` also writes
+what the last timed step handed its caller (see dump_outputs).  `--full` adds everything else the line
+can carry, each leg switched off again by its `--no-*` option: `roofline` (dominant kernel, HIP-event
+timed on the launch stream), package power over the timed steps, `step0_check` against the CPU oracle
+(before the timed steps), the generation, batch-4, fp32-parity, stage-1 and GPT-2 legs, and
+`cpu_baseline` (the oracle's CPU training step timed on the host's cores; N=1 only).
 """
 import argparse
 import json
@@ -177,7 +182,7 @@ def dominant_kernel_roofline(step_fn, B, T, n_steps=2):
     roof['timing'] = 'HIP events on the launch stream around every GEMM launch in %d real training steps (kernels serialized on one stream)' % n_steps
     import glob
     summaries = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'profiles', 'r*_bench_train_rocprof_stats.txt')))
-    roof['rocprof_summary'] = ('profiles/%s = rocprofv3 --kernel-trace --stats of `bench.py --steps 10 --warmup 3 --no-cpu-baseline '
+    roof['rocprof_summary'] = ('profiles/%s = rocprofv3 --kernel-trace --stats of `bench.py --full --steps 10 --warmup 3 --no-cpu-baseline '
                                % (os.path.basename(summaries[-1]) if summaries else '(none committed)') +
                                '--no-gen --no-stage1 --no-gpt2 --no-step0-check --no-b4 --no-fp32` (training kernels only); PMC (traffic, mfma_busy, effective clock): ' + pmc_note)
     roof['roofline_others'] = [entry(k) for k in order[1:]] + [attn_entry(k, v, n_steps, pmc_all if B * T == 131072 else {}) for k, v in sorted(extra.items())]
@@ -573,6 +578,32 @@ def fp32_parity_bench(tr, opt_cls, B, T, steps=5, warm=3):
                           'tests/test_gpu_model.py::test_performer_at_benchmark_shape_matches_oracle[fp32-*])'}
 
 
+DUMP_SAMPLE = 1 << 22          # elements per sampled array: 2 x 16 MB of fp32
+
+
+def dump_outputs(model, mean_loss, out_dir, seed=0):
+    """What the timed path (train.train_model) hands its caller after the last timed step, as DIR/<name>.npy:
+      mean_loss.npy  float64 [1]  the mean training loss train_model returns over the timed steps;
+      params.npy     float32 [n]  the parameters after the last step's Adam update;
+      grads.npy      float32 [n]  their gradients from the last step's backward (before the clip);
+    params / grads: the same fixed sample of n = 2^22 element positions (torch.randperm with a CPU generator seeded `seed`, sorted) of
+    all trainable parameters concatenated in registration order (the whole set: 38 M values, 153 MB per array).  The inputs (weights,
+    batches, omega and dropout draws) are seeded, so two runs with the same arguments see the same ones."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for p in model.parameters() if p.requires_grad]
+    total = sum(p.numel() for p in params)
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randperm(total, generator=g)[:DUMP_SAMPLE].sort().values.to(params[0].device)
+    with torch.no_grad():
+        flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+        flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in params])
+        arrays = {'params': flat_p[idx].cpu().numpy(), 'grads': flat_g[idx].cpu().numpy()}
+    arrays['mean_loss'] = np.array([mean_loss], dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N ranks (one per GPU) through torch.distributed.run and exit with its
     status.  Fails instead of shrinking the job when the node has fewer than N GPUs."""
@@ -597,6 +628,9 @@ def main():
     ap.add_argument('--batch', type=int, default=64, help='sequences per GPU (BASELINE.md: B=64)')
     ap.add_argument('--seq', type=int, default=CFG['seq'])
     ap.add_argument('--redraw', default='every_forward')
+    ap.add_argument('--dump-outputs', metavar='DIR', help="write the last timed step's outputs to DIR/<name>.npy (rank 0)")
+    ap.add_argument('--full', action='store_true', help='also run the legs below (roofline, power, step0 check, gen, b4, fp32, stage1, gpt2, '
+                                                        'CPU baselines); a plain run only times the training step')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-gen', action='store_true')
@@ -607,6 +641,8 @@ def main():
     ap.add_argument('--no-fp32', action='store_true', help='skip the fp32 parity-mode leg')
     ap.add_argument('--dp-selftest', action='store_true', help='N > 1: run only the gradient-exchange self-test and exit')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     want = max(args.gpus, 1)
     if 'WORLD_SIZE' not in os.environ and want > 1:
@@ -655,7 +691,7 @@ def main():
     batches = [synthetic_batch(CFG['n_token'], B, T, seed=dp.shard_seed(1234, rank) + 100 * i, device=dev) for i in range(2)]
     for b in batches:                                        # non-pad target count of the rank's batch (token-weighted DP mean)
         b['n_tok'] = (b['dec_target'] != CFG['n_token'] - 1).sum().to(torch.float32)
-    s0 = step0_check(model, batches[1]) if (world == 1 and not args.no_step0_check) else None     # batches[1] = the batch of step 1
+    s0 = step0_check(model, batches[1]) if (args.full and world == 1 and not args.no_step0_check) else None     # batches[1] = the batch of step 1
     # The timed step IS the product loop: train.train_model (zero_grad, forward with the omega redraw, loss, backward with the
     # overlapped gradient exchange at N > 1, clip(0.5) + Adam fused, LR schedule, loss bookkeeping on the device) over K synthetic
     # batches that are already resident in HBM, verbose off (= no per-step host sync; the reference's per-step print would add one).
@@ -694,7 +730,7 @@ def main():
         run_steps(args.warmup)
     torch.cuda.synchronize()
     dp.barrier()
-    sampler = PowerSampler() if rank == 0 else None
+    sampler = PowerSampler() if (args.full and rank == 0) else None
     if sampler is not None:
         sampler.start()
     t0 = time.perf_counter()
@@ -712,7 +748,7 @@ def main():
     value = tokens / elapsed
     out = {'metric': 'train tokens/sec (+ AR gen tokens/sec in "gen"), stage2 Performer d512 L12 seq%d' % T, 'value': round(value, 1), 'unit': 'tokens/s', 'n_gpus': world,
            'rccl_ranks': (ops.lib.emo_comm_world() if dp.data_plane() == 'rccl' else world if dp.data_plane() == 'nccl' else 0), 'comm': dp.data_plane() or 'none',
-           'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(1000 * elapsed / args.steps, 3), 'higher_is_better': True,
+           'steps': args.steps, 'steps_timed': len(per_step), 'warmup': args.warmup, 'ms_per_step': round(1000 * elapsed / args.steps, 3), 'higher_is_better': True,
            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'bf16', 'data': 'synthetic',
            'config': {'workload': 'BASELINE configs[%d]: stage2 Performer d_model=512 n_layer=12 n_head=8 favor_dims=128 seq=%d, B=%d/GPU, '
                                   'dropout 0.1, omega redraw %s, fwd+bwd+allreduce+clip+Adam' % (1 if world == 1 else 2, T, B, args.redraw),
@@ -721,7 +757,9 @@ def main():
            'timed_loop': 'emo_disentanger_amd.train.train_model (the product loop), verbose off',
            'median_ms_per_step': round(median_ms, 3), 'median_tokens_per_s': round(world * B * T / (median_ms / 1e3), 1) if median_ms == median_ms else None,
            'power': power}
-    if not args.no_roofline:                 # every rank runs the instrumented steps (they contain the all-reduce)
+    if args.dump_outputs and rank == 0:      # before the roofline's instrumented steps change the weights
+        dump_outputs(model, mean_loss, args.dump_outputs)
+    if args.full and not args.no_roofline:   # every rank runs the instrumented steps (they contain the all-reduce)
         roof = dominant_kernel_roofline(step, B, T)
         if rank == 0:
             out['roofline'] = roof
@@ -735,25 +773,26 @@ def main():
     if rank == 0:
         if s0 is not None:
             out['step0_check'] = s0
-        if world == 1 and not args.no_gen:
+        legs = args.full and world == 1
+        if legs and not args.no_gen:
             out['gen'] = generation_bench(model)
             if not args.no_cpu_baseline:
                 out['gen']['cpu_baseline'] = cpu_generation_baseline()
-        if world == 1 and not args.no_b4:
+        if legs and not args.no_b4:
             out['b4'] = b4_bench(model, FusedAdam, tr)
-        if world == 1 and not args.no_fp32:
+        if legs and not args.no_fp32:
             out['fp32_parity'] = fp32_parity_bench(tr, FusedAdam, B, T)
             torch.cuda.empty_cache()
-        if world == 1 and not args.no_stage1:
+        if legs and not args.no_stage1:
             out['stage1'] = stage1_bench()
-        if world == 1 and not args.no_gpt2:
+        if legs and not args.no_gpt2:
             del model, opt                                   # (the Performer's 21 GB of saved activations are not needed any more)
             torch.cuda.empty_cache()
             out['gpt2'] = gpt2_bench()
             if not args.no_gen:
                 torch.cuda.empty_cache()
                 out['gen_gpt2'] = gpt2_generation_bench()
-        if world == 1 and not args.no_cpu_baseline:
+        if legs and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(min(T, 2048))
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-box A/B of one environment setting on the reference-batch (B = 4) leg and the B = 64 leg: tools/ab_env_b4.sh NAME VALUE_A VALUE_B  ("-" = unset)
-F="--steps 6 --warmup 2 --no-cpu-baseline --no-gen --no-stage1 --no-gpt2 --no-step0-check"
+F="--full --steps 6 --warmup 2 --no-cpu-baseline --no-gen --no-stage1 --no-gpt2 --no-step0-check"
 N=$1; A=$2; B=$3
 for v in "$A" "$B" "$A" "$B"; do
   if [ "$v" = "-" ]; then unset $N; else export $N="$v"; fi
