@@ -456,6 +456,27 @@ class PlainTransformer(nn.Module):
             x = self._layer(l, x, attn)
         return self._logits(x)[0], mem
 
+    @torch.no_grad()
+    def decode_step(self, tok, mem, logits_out=None):
+        """The one-token branch of generate() for every row of `mem` at once: tok int64 [n] on the device -> logits fp32 [n, V] (into
+        `logits_out` when given).  Advances mem.lens on the device and keeps no host-side counter (mem.len is left alone), so the step can be
+        captured in a hipGraph; the caller keeps every row below mem.max_len.  Each row attends over its last dec_mem_len positions."""
+        if self.training:
+            raise NotImplementedError('decode_step() is an evaluation path: call .eval()')
+        ps = self._ensure_store()
+        D, H = self.dec_d_model, self.dec_n_head
+        x = self._embed(tok.view(-1, 1))
+        mem.lens.add_(1)
+        rw, rr = ps.f32('decoder.r_w_bias'), ps.f32('decoder.r_r_bias')
+        for l in range(self.dec_n_layer):
+            def attn(qkv, l=l):
+                return ops.relpos_attn_decode(qkv[:, :D], mem.kc[l], mem.vc[l], mem.lens, H, mem.r_dist[l], rw, rr, mem_len=self.dec_mem_len,
+                                              k_new=qkv[:, D:2 * D], v_new=qkv[:, 2 * D:])
+            x = self._layer(l, x, attn)
+        if logits_out is None:
+            return self._logits(x)
+        return ops.gemm(x, ps.w('dec_out_proj.weight'), bias=ps.f32('dec_out_proj.bias'), out=logits_out)
+
     def compute_loss(self, dec_logits, dec_tgt, reduction='mean'):
         """plain_transformer.py:82-93 (evaluation use: validation loss); the fused cross-entropy of the stage-2 path."""
         if reduction != 'mean':

@@ -6,12 +6,14 @@ representations is the key (temperature 1.1, p 0.97; under key_determine='rule' 
 contradicts the emotion is rejected), Beat positions never decrease inside a bar, 256 consecutive rejected samples abort, PAD is
 never appended, and a rejected sample makes the loop feed its previous input again — which appends that input to the model's
 memory a second time (a reference quirk the traces contain, kept on purpose)."""
+import os
 import time
 
 import numpy as np
 import torch
 
-from . import sampling
+from . import ops, sampling
+from ._lib import EmoError
 from .sampling import beat_position, nucleus  # noqa: F401  (`nucleus` is looked up at call time: tests wrap it)
 
 SHARP_NAMES = ('C', 'C#', 'D', 'D#', 'E', 'F', 'F#', 'G', 'G#', 'A', 'A#', 'B')     # pitch-class spelling of convert_key.py:14-15
@@ -98,3 +100,374 @@ def generate_plain_xl(model, event2idx, idx2event, max_bars=160, max_events=2048
             note('[stage1 gen] %s: %d bars, %d events' % (name, sheet.bars, len(sheet.tokens)))
     note('[stage1 gen] %d events in %.2f s' % (len(sheet.tokens), time.time() - t0))
     return sheet.tokens[:-1], time.time() - t0
+
+
+# ------------------------------------------------------------------------------------------------ lock-step batches
+# Mirrors of include/emo_hip.h (emo_txl_grammar_step): per-token event bits, per-stream parameter and state words, stream status.
+EV_BEAT, EV_BAR, EV_PAD, EV_EOS, EV_KEY, EV_MAJOR, EV_MINOR = 1, 2, 4, 8, 16, 32, 64
+P_MAX_BARS, P_MAX_EVENTS, P_PRIMER_LEN, P_KEYED, P_KEY_RULE, P_EMO_MODE = range(6)
+S_STATUS, S_LEN, S_ACCEPTED, S_BEAT, S_BARS, S_FAILED, S_FEED, S_DRAWS = range(8)
+RUNNING, DONE, STUCK, KEY_ERROR, OVERFLOW = range(5)
+KEY_TEMP, KEY_TOP_P = 1.1, 0.97                     # the key draw of generate_plain_xl (inference_utils.py:81-82)
+_KEY_ERROR = '[info] key generation failed'
+
+
+def event_tables(idx2event, V):
+    """-> (flags int32 [V], beat positions int32 [V]): the reference's own tests of an event name, per token id ('Beat' in e, 'Bar' in e,
+    e == 'PAD_None', e == 'EOS_None', e.split('_')[0] == 'Key'; beat_position for Beat events; the key's mode as match_emotion_key sees it).
+    Ids without an event get no bits."""
+    flags, beat = np.zeros(V, np.int32), np.zeros(V, np.int32)
+    for i in range(V):
+        e = idx2event.get(i) if isinstance(idx2event, dict) else (idx2event[i] if i < len(idx2event) else None)
+        if e is None:
+            continue
+        f = 0
+        if 'Beat' in e:
+            f |= EV_BEAT
+            beat[i] = beat_position(e)
+        if 'Bar' in e:
+            f |= EV_BAR
+        if e == 'PAD_None':
+            f |= EV_PAD
+        if e == 'EOS_None':
+            f |= EV_EOS
+        kind, _, tonic = e.partition('_')
+        if kind == 'Key':
+            f |= EV_KEY
+            if match_emotion_key('Positive', tonic):
+                f |= EV_MAJOR
+            if match_emotion_key('Negative', tonic):
+                f |= EV_MINOR
+        flags[i] = f
+    return flags, beat
+
+
+def emotion_mode(idx2event, first_token):
+    """0 / 1 (major: Q1, Q4, Positive) / 2 (minor: Q2, Q3, Negative) for a stream whose first token is `first_token` (the emotion tag)."""
+    parts = idx2event[first_token].split('_')
+    emo = parts[1] if len(parts) > 1 else ''
+    return 1 if emo in _MAJOR_MOODS else 2 if emo in _MINOR_MOODS else 0
+
+
+def _per_stream(n, **kw):
+    """Keyword values given once or as a list of n: -> n dicts."""
+    out = [{} for _ in range(n)]
+    for k, v in kw.items():
+        vals = list(v) if isinstance(v, (list, tuple)) else [v] * n
+        if len(vals) != n:
+            raise ValueError('%s: %d values for %d streams' % (k, len(vals), n))
+        for d, x in zip(out, vals):
+            d[k] = x
+    return out
+
+
+def _draw(sheet, logits, pick, idx2event, keyed, key_rule, temp, top_p):
+    """One draw and its grammar, as one iteration of generate_plain_xl (:81-93).  -> True if the word was appended; False if it was
+    rejected (a key that contradicts the emotion is rejected before the grammar runs).  Raises ValueError like the reference."""
+    if keyed and len(sheet.tokens) == 1:
+        word = pick(temperature(logits, KEY_TEMP), KEY_TOP_P)
+        name = idx2event[word]
+        if key_rule:
+            kind, _, tonic = name.partition('_')
+            if kind != 'Key':
+                raise ValueError(_KEY_ERROR)
+            if not match_emotion_key(idx2event[sheet.tokens[0]].split('_')[1], tonic):
+                return False
+    else:
+        word = pick(temperature(logits, temp), top_p)
+        name = idx2event[word]
+    return sheet.offer(word, name)
+
+
+def generate_plain_xl_batch(model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
+                            representation='functional', key_determine=None, samplers=None, seeds=None):
+    """n generate_plain_xl runs in lock-step on ONE TXLMemory, NumPy grammar and sampling per stream.  max_bars, max_events, prompt_bars,
+    representation and key_determine may be per-stream lists.  `samplers[i](probs)` defaults to nucleus(probs, p, rng=RandomState(seeds[i]))
+    (p = 0.97 on the key draw, top_p otherwise, as generate_plain_xl with its default sampler).  The common primer prefix is one prefill; the
+    longer primers' other tokens, and a primer fed again, go one token per step.
+    -> (results, seconds): results[i] is what generate_plain_xl(..., sampler=samplers[i]) returns for stream i alone (its id list, or None when
+    stuck) or, where that run raises, the exception instance (ValueError of the key rule, EmoError past max_gen_len)."""
+    n = len(primers)
+    assert n > 0
+    kw = _per_stream(n, max_bars=max_bars, max_events=max_events, prompt_bars=prompt_bars, representation=representation, key_determine=key_determine)
+    if samplers is None:
+        rss = [np.random.RandomState(seeds[i] if seeds is not None else i) for i in range(n)]
+        picks = [(lambda probs, p, rs=rs: nucleus(probs, p, rng=rs)) for rs in rss]
+    else:
+        picks = [(lambda probs, p, f=f: f(probs)) for f in samplers]
+    sheets = [_LeadSheet(event2idx, primers[i], kw[i]['prompt_bars'], kw[i]['max_bars'], kw[i]['max_events']) for i in range(n)]
+    keyed = [k['representation'] in ('functional', 'key') for k in kw]
+    results = [None if s.open() else s.tokens[:-1] for s in sheets]
+    live = [s.open() for s in sheets]
+    dev = next(model.parameters()).device
+    was_training = model.training
+    model.eval()
+    t0 = time.time()
+    try:
+        with torch.no_grad():
+            from .model.plain_transformer import TXLMemory
+            mem = TXLMemory(model, n, model._max_gen_len)
+            L0 = min(len(s.tokens) for s in sheets)
+            h, _, _ = model._prefill(torch.tensor([s.tokens[:L0] for s in sheets], dtype=torch.long, device=dev).t(), mem)
+            logits = model._logits(h.view(n, L0, -1)[:, -1].contiguous())
+            pending = [list(s.tokens[L0:]) for s in sheets]
+            glen = L0                                                     # positions in the memory (every row advances together)
+            while True:
+                nxt = [s.tokens[-1] for s in sheets]                      # (rows of finished streams idle)
+                logits_np = None
+                for i, s in enumerate(sheets):
+                    if not live[i]:
+                        continue
+                    if pending[i]:
+                        nxt[i] = pending[i].pop(0)
+                        continue
+                    if logits_np is None:
+                        logits_np = logits.cpu().numpy()
+                    try:
+                        _draw(s, logits_np[i], picks[i], idx2event, keyed[i], kw[i]['key_determine'] == 'rule', temp, top_p)
+                    except ValueError as e:
+                        results[i], live[i] = e, False
+                        continue
+                    if s.stuck or not s.open():
+                        results[i], live[i] = (None if s.stuck else s.tokens[:-1]), False
+                        continue
+                    feed = s.tokens if s.accepted == 0 else s.tokens[-1:]
+                    if len(feed) > 1 and model.dec_mem_len > 0 and glen + len(feed) > model.dec_mem_len + 1:
+                        results[i], live[i] = NotImplementedError('a multi-token segment that overflows mem_len while it is processed is not built'), False
+                        continue
+                    nxt[i], pending[i] = feed[0], list(feed[1:])
+                if not any(live):
+                    break
+                if glen >= mem.max_len:
+                    for i in range(n):
+                        if live[i]:
+                            results[i], live[i] = EmoError('generation longer than max_gen_len=%d: construct the model with a larger max_gen_len' % mem.max_len), False
+                    break
+                logits = model.decode_step(torch.tensor(nxt, dtype=torch.long, device=dev), mem)
+                glen += 1
+    finally:
+        model.train(was_training)
+    return results, time.time() - t0
+
+
+class LeadSheetLoop:
+    """Device state of generate_lead_sheets: a TXLMemory, the logits of the last step, the uniform table, the grammar tables and
+    per-stream parameters / state, the output sequences and the running count; one_step() = emo_txl_grammar_step + decode_step."""
+
+    def __init__(self, model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
+                 representation='functional', key_determine=None, seed=0):
+        from .model.plain_transformer import TXLMemory
+        n = self.n = len(primers)
+        assert n > 0
+        kw = _per_stream(n, max_bars=max_bars, max_events=max_events, prompt_bars=prompt_bars, representation=representation, key_determine=key_determine)
+        self.model, self.temp, self.top_p = model, float(temp), float(top_p)
+        dev = self.dev = next(model.parameters()).device
+        sheets = [_LeadSheet(event2idx, primers[i], kw[i]['prompt_bars'], kw[i]['max_bars'], kw[i]['max_events']) for i in range(n)]
+        V = model.vocab_size
+        if V > 1024:
+            raise EmoError('generate_lead_sheets: the device draw takes V <= 1024 (got %d)' % V)
+        flags, beat = event_tables(idx2event, V)
+        self.ev_flags, self.ev_beat = torch.from_numpy(flags).to(dev), torch.from_numpy(beat).to(dev)
+        self.mem = TXLMemory(model, n, model._max_gen_len)
+        self.max_len = self.mem.max_len
+        self.L0 = min(len(s.tokens) for s in sheets)
+        if self.L0 < 1:
+            raise ValueError('generate_lead_sheets: empty primer')
+        plens = [len(s.tokens) for s in sheets]
+        width = max(max(plens), max(k['max_events'] for k in kw)) + 1
+        seq = np.zeros((n, width), np.int64)
+        params = np.zeros((n, ops.TXL_PARAM_WORDS), np.int32)
+        state = np.zeros((n, ops.TXL_STATE_WORDS), np.int32)
+        for i, (s, k) in enumerate(zip(sheets, kw)):
+            seq[i, :plens[i]] = s.tokens
+            params[i, [P_MAX_BARS, P_MAX_EVENTS, P_PRIMER_LEN]] = k['max_bars'], k['max_events'], plens[i]
+            params[i, P_KEYED] = k['representation'] in ('functional', 'key')
+            params[i, P_KEY_RULE] = k['key_determine'] == 'rule'
+            params[i, P_EMO_MODE] = emotion_mode(idx2event, s.tokens[0])
+            state[i, [S_STATUS, S_LEN, S_BARS, S_FEED]] = (RUNNING if s.open() else DONE), plens[i], s.bars, self.L0
+        self.seq, self.params, self.state = (torch.from_numpy(a).to(dev) for a in (seq, params, state))
+        self.running = torch.tensor([int((state[:, S_STATUS] == RUNNING).sum())], dtype=torch.int32, device=dev)
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(seed)
+        self.U = torch.rand(self.max_len - self.L0 + 1, n, device=dev, generator=gen)      # at most one draw per step, one more at the end
+        self.tok = self.seq[:, self.L0 - 1].contiguous()      # (a valid id in every row before the first grammar step)
+        self.logits = torch.empty(n, V, dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            h, _, _ = model._prefill(self.seq[:, :self.L0].t(), self.mem)
+            self.logits.copy_(model._logits(h.view(n, self.L0, -1)[:, -1].contiguous()))
+        self.pos = self.L0                   # positions in the memory (host count: every row advances one per step)
+        self.graph = self.graph_k = self.stream = None
+
+    def grammar(self):
+        ops.txl_grammar_step(self.logits, self.temp, self.top_p, KEY_TEMP, KEY_TOP_P, self.U, self.ev_flags, self.ev_beat, self.params, self.state,
+                             self.seq, self.tok, self.running)
+
+    def one_step(self):
+        self.grammar()
+        self.model.decode_step(self.tok, self.mem, logits_out=self.logits)
+
+    def capture(self, steps):
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=self.dev)
+        g = torch.cuda.CUDAGraph()
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            with torch.cuda.graph(g, stream=self.stream):
+                for _ in range(steps):
+                    self.one_step()
+        return g
+
+    def run(self, use_graph=True, steps_per_graph=None):
+        """Steps until every stream is finished or the memory is full; the running count is read once per replay (per step without graphs).
+        At the memory's end one more grammar step runs alone: a stream that then still wants a model step would overflow max_gen_len."""
+        k = max(1, int(steps_per_graph or os.environ.get('EMO_GEN_GRAPH_STEPS', 16)))
+        with torch.no_grad():
+            if int(self.running.item()) > 0 and self.pos < self.max_len:
+                self.one_step()                  # eager first step (also warms every kernel / workspace cache before any capture)
+                self.pos += 1
+            if use_graph and int(self.running.item()) > 0 and self.pos < self.max_len:
+                torch.cuda.synchronize()
+                self.graph = self.capture(1)
+                self.graph_k = self.capture(k) if k > 1 and self.max_len - self.pos >= 2 * k else None
+                main = torch.cuda.current_stream()
+                with torch.cuda.stream(self.stream):
+                    while int(self.running.item()) > 0 and self.pos < self.max_len:
+                        many = self.graph_k is not None and self.max_len - self.pos >= k
+                        (self.graph_k if many else self.graph).replay()
+                        self.pos += k if many else 1
+                main.wait_stream(self.stream)
+            while int(self.running.item()) > 0 and self.pos < self.max_len:
+                self.one_step()
+                self.pos += 1
+            if int(self.running.item()) > 0:
+                self.grammar()
+            torch.cuda.synchronize()
+
+    def results(self, idx2event=None):
+        """-> per stream: the id list without the last id (DONE), None (STUCK), or the exception the reference loop raises."""
+        state, seq = self.state.cpu().numpy(), self.seq.cpu().numpy()
+        out = []
+        for i in range(self.n):
+            st, ln = int(state[i, S_STATUS]), int(state[i, S_LEN])
+            if st == DONE:
+                out.append([int(t) for t in seq[i, :ln - 1]])
+            elif st == STUCK:
+                out.append(None)
+            elif st == KEY_ERROR:
+                out.append(ValueError(_KEY_ERROR))
+            else:
+                out.append(EmoError('generation longer than max_gen_len=%d: construct the model with a larger max_gen_len' % self.max_len))
+        return out
+
+    def accepted_tokens(self):
+        st = self.state.cpu().numpy()
+        return int((st[:, S_LEN] - self.params.cpu().numpy()[:, P_PRIMER_LEN]).sum())
+
+
+def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
+                         representation='functional', key_determine=None, seed=0, use_graph=True):
+    """The throughput path of generate_plain_xl_batch: the same arguments and result shape, every draw and the grammar on the device
+    (emo_txl_grammar_step), each token step = grammar launch + decode_step, k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS,
+    default 16) and replayed until every stream has finished.  Draws come from a uniform table seeded with `seed` (like generate_streams),
+    so the ids are not NumPy-RNG-identical to the reference; they equal the host grammar driven by the same device draws.
+    -> (results, seconds)."""
+    was_training = model.training
+    model.eval()
+    t0 = time.time()
+    try:
+        loop = LeadSheetLoop(model, event2idx, idx2event, primers, max_bars=max_bars, max_events=max_events, temp=temp, top_p=top_p,
+                             prompt_bars=prompt_bars, representation=representation, key_determine=key_determine, seed=seed)
+        loop.run(use_graph=use_graph)
+        out = loop.results()
+    finally:
+        model.train(was_training)
+    return out, time.time() - t0
+
+
+# ------------------------------------------------------------------------------------------------ command line (reference stage1_compose/inference.py:86-298)
+MODES = {'lead_sheet': dict(temp=1.2, top_p=0.97, max_events=512, emotions=('Positive', 'Negative')),
+         'full_song': dict(temp=1.1, top_p=0.99, max_events=2400, emotions=('Q1', 'Q2', 'Q3', 'Q4'))}
+
+
+def read_vocab(vocab_file):
+    """stage1_compose/inference.py:22-29: dictionary.pkl = (event2idx, idx2event), PAD appended after it -> (event2idx, idx2event,
+    vocab_size).  idx2event[pad] = 'PAD_None' is added as well, so that a sampled PAD is rejected by the grammar instead of raising KeyError."""
+    import pickle
+    with open(vocab_file, 'rb') as f:
+        event2idx, idx2event = pickle.load(f)[:2]
+    idx2event = dict(idx2event) if isinstance(idx2event, dict) else dict(enumerate(idx2event))
+    pad = len(event2idx)
+    event2idx['PAD_None'] = pad
+    idx2event[pad] = 'PAD_None'
+    return event2idx, idx2event, pad + 1
+
+
+def main(argv=None):
+    """Same flags as the reference's stage-1 inference.py (-c -r -m -i -o -n): n_groups pieces for each emotion of the mode, key_determine
+    'rule', max_bars 128, written as samp_XX_<emotion>_roman.txt (functional) / samp_XX_<emotion>.txt (remi) without the emotion tag — the
+    files the stage-2 command line (inference.main) reads.  All jobs run --streams at a time through generate_lead_sheets (device draws and
+    grammar); --exact runs them through generate_plain_xl_batch (NumPy sampling, seeds 0, 1, ... in job order).  MIDI output (miditoolkit,
+    relative2absolute) is not part of this package."""
+    import argparse
+    import yaml
+    from .model.plain_transformer import PlainTransformer
+    ap = argparse.ArgumentParser(description='stage-1 lead-sheet generation on MI355X')
+    req = ap.add_argument_group('required arguments')
+    req.add_argument('-c', '--configuration', required=True, help='a stage-1 YAML (stage1_compose/config keys)')
+    req.add_argument('-r', '--representation', choices=['remi', 'functional'], required=True)
+    req.add_argument('-m', '--mode', choices=['lead_sheet', 'full_song'], required=True)
+    ap.add_argument('-i', '--inference_params', default='best_weight/Functional-two/emopia_lead_sheet_finetune/ep016_loss0.685_params.pt',
+                    help='checkpoint (.pt state dict)')
+    ap.add_argument('-o', '--output_dir', default='generation/emopia_functional_two')
+    ap.add_argument('-n', '--n_groups', type=int, default=20, help='pieces per emotion')
+    ap.add_argument('--streams', type=int, default=32, help='pieces generated in lock-step')
+    ap.add_argument('--dtype', default=None, choices=[None, 'bf16', 'fp32'])
+    ap.add_argument('--exact', action='store_true', help='NumPy sampling and grammar on the host (reference-exact per seed) instead of the device loop')
+    ap.add_argument('--seed', type=int, default=0, help='seed of the device uniform table (the group of streams j uses seed + j)')
+    args = ap.parse_args(argv)
+    conf = yaml.load(open(args.configuration), Loader=yaml.FullLoader)
+    mode = MODES[args.mode]
+    max_bars, key_determine = 128, 'rule'
+    print('representation: {}, key determine: {}'.format(args.representation, key_determine))
+    print('[nucleus parameters] t = {}, p = {}'.format(mode['temp'], mode['top_p']))
+    os.makedirs(args.output_dir, exist_ok=True)
+    event2idx, idx2event, vocab_size = read_vocab(conf['data']['vocab_path'].format(args.representation))
+    mc, dc = conf['model'], conf['model']['decoder']
+    model = PlainTransformer(mc['d_word_embed'], vocab_size, dc['n_layer'], dc['n_head'], dc['d_model'], dc['d_ff'], dc['tgt_len'], dc['tgt_len'],
+                             dec_dropout=dc['dropout'], pre_lnorm=mc['pre_lnorm'], compute_dtype=args.dtype,
+                             max_gen_len=2 * mode['max_events'] + 1024).cuda()
+    model.load_state_dict(torch.load(args.inference_params, map_location='cpu'))
+    model.eval()
+    suffix = '_roman.txt' if args.representation == 'functional' else '.txt'
+    jobs = []
+    for g in range(args.n_groups):
+        for emotion in mode['emotions']:
+            out = os.path.join(args.output_dir, 'samp_{:02d}_{}{}'.format(g, emotion, suffix))
+            if os.path.exists(out):
+                print('[info] {} exists, skipping ...'.format(out))
+                continue
+            jobs.append((out, emotion))
+    print('[# jobs]', len(jobs))
+    kw = dict(max_bars=max_bars, max_events=mode['max_events'], temp=mode['temp'], top_p=mode['top_p'], representation=args.representation,
+              key_determine=key_determine)
+    times = []
+    for j, i in enumerate(range(0, len(jobs), args.streams)):
+        group = jobs[i:i + args.streams]
+        primers = [['Emotion_{}'.format(e)] for _, e in group]
+        if args.exact:
+            res, sec = generate_plain_xl_batch(model, event2idx, idx2event, primers, seeds=list(range(i, i + len(group))), **kw)
+        else:
+            res, sec = generate_lead_sheets(model, event2idx, idx2event, primers, seed=args.seed + j, **kw)
+        times.append(sec)
+        for (out, _), ids in zip(group, res):
+            if ids is None or isinstance(ids, Exception):
+                print('[info] %s not written: %s' % (out, 'stuck after 256 rejected samples' if ids is None else ids))
+                continue
+            with open(out, 'w') as fh:
+                fh.write('\n'.join(idx2event[w] for w in ids[1:]) + '\n')
+            print('[info] wrote', out, len(ids) - 1, 'events')
+    print('[info] finished {} jobs in {:.2f} s'.format(len(jobs), sum(times)))
+
+
+if __name__ == '__main__':
+    main()

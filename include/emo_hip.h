@@ -412,6 +412,32 @@ int emo_sample_nucleus(const float* logits, int64_t rows, int64_t V, float tempe
 int emo_sample_nucleus_step(const float* logits, int64_t rows, int64_t V, float temperature,
                             float top_p, const float* u_steps, int64_t* step, int64_t* seq,
                             int64_t ld_seq, int64_t col0, int64_t* out, emo_stream_t stream);
+/* Stage-1 lead-sheet generation (stage1_compose/inference_utils.py generate_plain_xl :51-134, match_emotion_key :137-142): the draw and the
+ * grammar of one lock-step token step for n streams, one 512-thread workgroup per stream, all loop state in device memory (graph-capturable).
+ * A stream that is RUNNING and has fed its whole primer (state[FEED] >= params[PRIMER_LEN]) draws from logits[r] (fp32 [n, V], V <= 1024) with
+ * uniform u_steps[state[DRAWS] * n + r] (u_steps [n_u, n]) — the device code of emo_sample_nucleus, so the same id —, at key_temperature /
+ * key_top_p when params[KEYED] and the stream holds exactly one token (reference: 1.1 / 0.97), else at temperature / top_p.  Then, in the
+ * reference's order: the key rule (params[KEY_RULE], key draw only: a non-Key event -> KEY_ERROR; a key whose mode contradicts params[EMO_MODE]
+ * is rejected), Beat (a position below state[BEAT] is rejected and counted, 256 in a row -> STUCK; accepted: count reset), Bar (bars += 1,
+ * position 0), PAD (rejected, not counted), append to seq[r] (int64, pitch ld_seq; DONE when the length exceeds params[MAX_EVENTS] or the
+ * event is EOS), DONE when bars >= params[MAX_BARS].  tok_out[r] = the next input: the accepted word; after a rejection the previous input
+ * again; after a rejection with nothing accepted the primer (seq[r, 0 .. PRIMER_LEN)) again, one token per step with no draws.  A stream still
+ * feeding its primer writes tok_out[r] = seq[r, FEED] and advances FEED; a stream that finishes leaves its last token in tok_out[r] (its row
+ * idles).  *running is decremented once per stream that leaves RUNNING.
+ * ev_flags [V] (EMO_TXL_EV_* bits: 'Beat' in e, 'Bar' in e, e == 'PAD_None', e == 'EOS_None', e.split('_')[0] == 'Key', the key's tonic in
+ * MAJOR_KEY / MINOR_KEY) and ev_beat [V] (int(e.split('_')[-1]) of Beat events) are built on the host from idx2event.
+ * params int32 [n, EMO_TXL_PARAM_WORDS], state int32 [n, EMO_TXL_STATE_WORDS], laid out as the enums below. */
+enum { EMO_TXL_P_MAX_BARS = 0, EMO_TXL_P_MAX_EVENTS = 1, EMO_TXL_P_PRIMER_LEN = 2, EMO_TXL_P_KEYED = 3, EMO_TXL_P_KEY_RULE = 4,
+       EMO_TXL_P_EMO_MODE = 5 /* 0 none, 1 major (Q1 / Q4 / Positive), 2 minor (Q2 / Q3 / Negative) */, EMO_TXL_PARAM_WORDS = 8 };
+enum { EMO_TXL_S_STATUS = 0, EMO_TXL_S_LEN = 1 /* tokens in seq[r] */, EMO_TXL_S_ACCEPTED = 2, EMO_TXL_S_BEAT = 3, EMO_TXL_S_BARS = 4,
+       EMO_TXL_S_FAILED = 5 /* rejected Beats in a row */, EMO_TXL_S_FEED = 6 /* next primer token to feed */, EMO_TXL_S_DRAWS = 7, EMO_TXL_STATE_WORDS = 8 };
+enum { EMO_TXL_RUNNING = 0, EMO_TXL_DONE = 1, EMO_TXL_STUCK = 2, EMO_TXL_KEY_ERROR = 3, EMO_TXL_OVERFLOW = 4 /* seq or u_steps exhausted */ };
+enum { EMO_TXL_EV_BEAT = 1, EMO_TXL_EV_BAR = 2, EMO_TXL_EV_PAD = 4, EMO_TXL_EV_EOS = 8, EMO_TXL_EV_KEY = 16, EMO_TXL_EV_MAJOR = 32, EMO_TXL_EV_MINOR = 64 };
+int emo_txl_grammar_step(const float* logits, int64_t n, int64_t V, float temperature, float top_p,
+                         float key_temperature, float key_top_p, const float* u_steps, int64_t n_u,
+                         const int32_t* ev_flags, const int32_t* ev_beat, const int32_t* params,
+                         int32_t* state, int64_t* seq, int64_t ld_seq, int64_t* tok_out, int32_t* running,
+                         emo_stream_t stream);
 /* counts[0..5] += {nonpad, nonpad&correct, chord, chord&correct, melody, melody&correct} (train.py:184-193) */
 int emo_accuracy_counts(const float* logits, const int64_t* tgt, const int64_t* chord,
                         const int64_t* melody, int64_t M, int64_t V, int64_t pad, int64_t* counts,
