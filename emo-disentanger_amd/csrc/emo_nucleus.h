@@ -10,6 +10,46 @@
 constexpr int EMO_NUCLEUS_LDS = (3 * (1024 + 8)) * 4 + (1024 + 8) * 8 * 2 + 1024 * 4 + 64;      // bytes of LDS scratch (16-B aligned base)
 constexpr int EMO_NUCLEUS_BARRIERS = 9;                                                          // sync() calls of emo_nucleus_draw (every path)
 
+// The candidate cut and the draw of emo_nucleus_draw, from the sorted probabilities and prefixes it leaves in LDS: a second draw from the same
+// logits with another uniform costs only this part (3 barriers).  Same contract as emo_nucleus_draw: the id in thread 0.
+template <typename Sync>
+__device__ __forceinline__ int64_t emo_nucleus_pick(int64_t V, float top_p, float u, char* lds, int tid, Sync sync) {
+    float* sp = (float*)lds;
+    float* sq = sp + 1024 + 8;
+    float* cumf = sq + 1024 + 8;
+    double* cumd = (double*)(cumf + 1024 + 8);
+    unsigned long long* skey = (unsigned long long*)(cumd + 1024 + 8);
+    int* si = (int*)(skey + 1024 + 8);
+    float* red = (float*)(si + 1024);
+    int* cnt = (int*)(red + 8);
+    const int lane = tid & 63, wave = tid >> 6;
+    // first crossing i1 = #{i < V : cum_i <= top_p}; cum is non-decreasing, so the second crossing is i1 + 1
+    int c1 = 0;
+    for (int i = tid; i < V; i += 512) c1 += (cumf[i] <= top_p) ? 1 : 0;
+    c1 = (int)wave_sum((float)c1);
+    if (lane == 0) cnt[wave] = c1;
+    sync();
+    const int i1 = cnt[0] + cnt[1] + cnt[2] + cnt[3] + cnt[4] + cnt[5] + cnt[6] + cnt[7];
+    int last;
+    if (i1 >= V) last = V < 3 ? (int)V : 3;       // no crossing
+    else if (i1 + 1 >= V) last = (int)V;          // single crossing (reference: IndexError)
+    else last = i1 + 1;
+    const double target = (double)u * cumd[last - 1];
+    sync();
+    int c2 = 0;
+    for (int i = tid; i < last; i += 512) c2 += (cumd[i] <= target) ? 1 : 0;
+    c2 = (int)wave_sum((float)c2);
+    if (lane == 0) cnt[wave] = c2;
+    sync();
+    int64_t tok = 0;
+    if (tid == 0) {
+        int pick = cnt[0] + cnt[1] + cnt[2] + cnt[3] + cnt[4] + cnt[5] + cnt[6] + cnt[7];
+        if (pick >= last) pick = last - 1;
+        tok = (int64_t)si[pick];
+    }
+    return tok;
+}
+
 // tid in [0, 512); `sync` = a barrier over exactly the calling threads (+ any others that call it the same number of times).  Returns the picked
 // token id in thread 0 (other threads: undefined).  u = the uniform draw of this stream.
 template <typename Sync>
@@ -21,7 +61,6 @@ __device__ __forceinline__ int64_t emo_nucleus_draw(const float* __restrict__ l,
     unsigned long long* skey = (unsigned long long*)(cumd + 1024 + 8);
     int* si = (int*)(skey + 1024 + 8);
     float* red = (float*)(si + 1024);
-    int* cnt = (int*)(red + 8);
     const int Vp = ((int)V + 7) & ~7;
     const int lane = tid & 63, wave = tid >> 6;
     float mx = -INFINITY;
@@ -99,29 +138,5 @@ __device__ __forceinline__ int64_t emo_nucleus_draw(const float* __restrict__ l,
         }
     }
     sync();
-    // first crossing i1 = #{i < V : cum_i <= top_p}; cum is non-decreasing, so the second crossing is i1 + 1
-    int c1 = 0;
-    for (int i = tid; i < V; i += 512) c1 += (cumf[i] <= top_p) ? 1 : 0;
-    c1 = (int)wave_sum((float)c1);
-    if (lane == 0) cnt[wave] = c1;
-    sync();
-    const int i1 = cnt[0] + cnt[1] + cnt[2] + cnt[3] + cnt[4] + cnt[5] + cnt[6] + cnt[7];
-    int last;
-    if (i1 >= V) last = V < 3 ? (int)V : 3;       // no crossing
-    else if (i1 + 1 >= V) last = (int)V;          // single crossing (reference: IndexError)
-    else last = i1 + 1;
-    const double target = (double)u * cumd[last - 1];
-    sync();
-    int c2 = 0;
-    for (int i = tid; i < last; i += 512) c2 += (cumd[i] <= target) ? 1 : 0;
-    c2 = (int)wave_sum((float)c2);
-    if (lane == 0) cnt[wave] = c2;
-    sync();
-    int64_t tok = 0;
-    if (tid == 0) {
-        int pick = cnt[0] + cnt[1] + cnt[2] + cnt[3] + cnt[4] + cnt[5] + cnt[6] + cnt[7];
-        if (pick >= last) pick = last - 1;
-        tok = (int64_t)si[pick];
-    }
-    return tok;
+    return emo_nucleus_pick(V, top_p, u, lds, tid, sync);
 }

@@ -911,6 +911,246 @@ def generate_streams(model, prompt_tok, prompt_seg, n_new, temp=1.1, top_p=0.9, 
     return cs[0].out if chains == 1 else torch.cat([ch.out for ch in cs], 0)
 
 
+# ------------------------------------------------------------------------------------------------ device loop (stage 2, grammar on)
+# Mirrors of include/emo_hip.h (emo_acc_grammar_step): per-token event bits, per-stream parameter and state words, stream status.
+ACC_EV_BEAT, ACC_EV_TRACK_LS, ACC_EV_PAD, ACC_EV_EOS = 1, 2, 4, 8
+ACC_P_TARGET_BARS, ACC_P_MAX_EVENTS, ACC_P_SKIP_CHECK, ACC_P_BAR0, ACC_P_N_BARS = range(5)
+ACC_S_STATUS, ACC_S_LEN, ACC_S_CONSUMED, ACC_S_BARS, ACC_S_CUR_POS, ACC_S_FAILED, ACC_S_DRAWS, ACC_S_ACCEPTED = range(8)
+ACC_RUNNING, ACC_DONE, ACC_STUCK, ACC_WINDOW, ACC_OUT_OF_DRAWS, ACC_OVERFLOW = range(6)
+
+
+def acc_event_tables(idx2event, V):
+    """-> (flags int32 [V], beat positions int32 [V]): the tests _Stream.offer makes of an event name, per token id ('Beat' in e with
+    beat_position, e == 'Track_LeadSheet', e == 'PAD_None', e == 'EOS_None').  Ids without an event get no bits."""
+    flags, beat = np.zeros(V, np.int32), np.zeros(V, np.int32)
+    for i in range(V):
+        e = idx2event.get(i) if isinstance(idx2event, dict) else (idx2event[i] if i < len(idx2event) else None)
+        if e is None:
+            continue
+        f = 0
+        if 'Beat' in e:
+            f |= ACC_EV_BEAT
+            beat[i] = beat_position(e)
+        if e == 'Track_LeadSheet':
+            f |= ACC_EV_TRACK_LS
+        if e == 'PAD_None':
+            f |= ACC_EV_PAD
+        if e == 'EOS_None':
+            f |= ACC_EV_EOS
+        flags[i] = f
+    return flags, beat
+
+
+def pack_lead_sheets(lead_sheets):
+    """n lead sheets (lists of bars, each a list of ids) -> (tokens int64, offsets int32, first-bar index per stream, bar count per stream,
+    longest bar): bar j of stream i is tokens[offsets[bar0[i] + j] : offsets[bar0[i] + j + 1]] (emo_hip.h: emo_acc_grammar_step)."""
+    toks, offs, bar0, nbars = [], [], [], []
+    for lead in lead_sheets:
+        bar0.append(len(offs))
+        nbars.append(len(lead))
+        for b in lead:
+            offs.append(len(toks))
+            toks.extend(int(t) for t in b)
+        offs.append(len(toks))
+    longest = max([len(b) for lead in lead_sheets for b in lead] or [0])
+    return np.array(toks or [0], np.int64), np.array(offs, np.int32), bar0, nbars, longest
+
+
+def _refuse(model, inadmissibles):
+    if inadmissibles is not None:
+        raise ValueError('generate_accompaniments: `inadmissibles` is not supported by the device grammar')
+    if model.n_token > 1024:
+        raise EmoError('generate_accompaniments: the device draw takes V <= 1024 (got %d)' % model.n_token)
+
+
+class _GaveUp(Exception):
+    """The one-launch decode step gave up (emo_*_decode_step: its workgroups were not all resident in time)."""
+
+
+class AccompanimentLoop:
+    """Device state of generate_accompaniments: the decode engine (prefilled with the common prefix, positions on the device), the logits of
+    the last step, the uniform table, the grammar tables, the packed lead sheets, per-stream parameters / state and token / segment rows, and
+    the running count; one_step() = emo_acc_grammar_step + the engine step."""
+
+    def __init__(self, model, event2idx, idx2event, lead_sheets, primers, max_events=10000, skip_check=False, max_bars=None, temp=1.2, top_p=0.9,
+                 seed=0, n_u=None, persistent=True, redraw=True):
+        n = self.n = len(lead_sheets)
+        assert n == len(primers) and n > 0
+        _refuse(model, None)
+        self.model, self.temp, self.top_p = model, float(temp), float(top_p)
+        self.W = int(max_dec_inp_len)                 # read at call time (tests lower it)
+        dev = self.dev = next(model.parameters()).device
+        self.streams = [_Stream(event2idx, lead_sheets[i], primers[i], max_bars) for i in range(n)]
+        V = model.n_token
+        flags, beat = acc_event_tables(idx2event, V)
+        self.ev_flags, self.ev_beat = torch.from_numpy(flags).to(dev), torch.from_numpy(beat).to(dev)
+        toks, offs, bar0, nbars, longest = pack_lead_sheets(lead_sheets)
+        self.lead_tok, self.lead_off = torch.from_numpy(toks).to(dev), torch.from_numpy(offs).to(dev)
+        self.track_full, self.pad = event2idx['Track_Full'], event2idx.get('PAD_None', 0)
+        lens = [len(s.generated) for s in self.streams]
+        width = max(self.W, max(lens)) + longest + 2              # an injected bar + Track_Full always fit behind an accepted word
+        seq, segs = np.zeros((n, width), np.int64), np.zeros((n, width), np.int64)
+        params = np.zeros((n, ops.ACC_PARAM_WORDS), np.int32)
+        state = np.zeros((n, ops.ACC_STATE_WORDS), np.int32)
+        self.L0 = min(lens)
+        for i, s in enumerate(self.streams):
+            seq[i, :lens[i]], segs[i, :lens[i]] = s.generated, s.seg
+            params[i, [ACC_P_TARGET_BARS, ACC_P_MAX_EVENTS, ACC_P_SKIP_CHECK, ACC_P_BAR0, ACC_P_N_BARS]] = (s.target_bars, max_events, bool(skip_check),
+                                                                                                            bar0[i], nbars[i])
+            state[i, [ACC_S_STATUS, ACC_S_LEN, ACC_S_CONSUMED]] = (ACC_DONE if s.done else ACC_RUNNING), lens[i], self.L0
+        self.len0 = np.array(lens)
+        self.seq, self.segs, self.params, self.state = (torch.from_numpy(a).to(dev) for a in (seq, segs, params, state))
+        self.running = torch.tensor([int((state[:, ACC_S_STATUS] == ACC_RUNNING).sum())], dtype=torch.int32, device=dev)
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(seed)
+        self.U = torch.rand(int(n_u or 4 * self.W), n, device=dev, generator=gen)
+        self.tok = torch.zeros(n, dtype=torch.int64, device=dev)
+        self.segv = torch.ones(n, dtype=torch.int64, device=dev)
+        self.logits = torch.empty(n, V, dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            if model.kind == 'performer':
+                eng = PerformerDecodeEngine(model, n, redraw=redraw, persistent=persistent)
+                eng.max_len = self.W
+            else:
+                eng = GPT2DecodeEngine(model, n, max_len=self.W, persistent=persistent)
+            self.logits.copy_(eng.prefill(self.seq[:, :self.L0].contiguous(), self.segs[:, :self.L0].contiguous()))
+            eng.pos_dev.zero_()
+            eng.dev_pos0, eng.pos_auto = self.L0, True          # position = L0 + pos_dev[r], advanced by the engine
+        self.eng = eng
+        pe = model.pe.pe.shape[0] if model.use_pe else self.W
+        self.bound = min(self.W, pe)           # the engine never runs a step at a position >= bound (the one-launch GPT-2 step would clamp it)
+        self.pos = self.L0                     # host count of the engine position (every row advances one per step)
+        self.graph = self.graph_k = self.stream = None
+        self.replayed = (0, 0.0)
+
+    def grammar(self):
+        ops.acc_grammar_step(self.logits, self.temp, self.top_p, self.U, self.ev_flags, self.ev_beat, self.lead_tok, self.lead_off, self.params,
+                             self.state, self.seq, self.segs, self.W, self.track_full, self.pad, self.tok, self.segv, self.running)
+
+    def one_step(self):
+        self.grammar()
+        self.eng.step(self.tok, self.segv, dev_pos=True, logits_out=self.logits)
+
+    def capture(self, steps):
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=self.dev)
+        g = torch.cuda.CUDAGraph()
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            with torch.cuda.graph(g, stream=self.stream):
+                for _ in range(steps):
+                    self.one_step()
+        return g
+
+    def _live(self):
+        """Running count (synchronises); raises _GaveUp when the one-launch step gave up."""
+        if self.eng.persist is not None:
+            try:
+                self.eng.check_persistent()
+            except EmoError as e:
+                raise _GaveUp(str(e))
+        return int(self.running.item())
+
+    def run(self, use_graph=True, steps_per_graph=None):
+        """Steps until every stream has left RUNNING; the running count is read once per replay (per step without graphs).  A k-step replay
+        runs only while it keeps the position below `bound`; at the bound one more grammar step runs alone (a stream still running there
+        reaches the window in it)."""
+        k = max(1, int(steps_per_graph or os.environ.get('EMO_GEN_GRAPH_STEPS', 16)))
+        with torch.no_grad():
+            if self._live() > 0 and self.pos < self.bound:
+                self.one_step()                  # eager first step (also warms every kernel / workspace cache before any capture)
+                self.pos += 1
+            if use_graph and self._live() > 0 and self.pos < self.bound:
+                torch.cuda.synchronize()
+                self.graph = self.capture(1)
+                self.graph_k = self.capture(k) if k > 1 and self.bound - self.pos >= 2 * k else None
+                main = torch.cuda.current_stream()
+                t0, p0 = time.perf_counter(), self.pos
+                try:
+                    with torch.cuda.stream(self.stream):
+                        while self._live() > 0 and self.pos < self.bound:
+                            many = self.graph_k is not None and self.bound - self.pos >= k
+                            (self.graph_k if many else self.graph).replay()
+                            self.pos += k if many else 1
+                finally:
+                    main.wait_stream(self.stream)
+                self.replayed = (self.pos - p0, time.perf_counter() - t0)     # (steps, seconds) of the replays (the last poll synchronised)
+            while self._live() > 0 and self.pos < self.bound:
+                self.one_step()
+                self.pos += 1
+            if self._live() > 0:
+                self.grammar()
+            torch.cuda.synchronize()
+
+    def steps(self):
+        return self.pos - self.L0
+
+    def accepted_tokens(self):
+        return int(self.state[:, ACC_S_ACCEPTED].sum().item())
+
+    def counts(self):
+        st = self.state[:, ACC_S_STATUS].cpu().numpy()
+        return {'finished': int((st == ACC_DONE).sum()), 'stuck': int((st == ACC_STUCK).sum()), 'window': int((st == ACC_WINDOW).sum()),
+                'other': int(((st != ACC_DONE) & (st != ACC_STUCK) & (st != ACC_WINDOW)).sum())}
+
+    def results(self, event2idx, idx2event, max_events, skip_check, seed):
+        """Per stream what _Stream.result() gives: DONE -> generated[:-1], STUCK -> generated; WINDOW -> the stream rebuilt from the device
+        state and finished by _resume_windowed with nucleus(probs, top_p, rng=RandomState([seed, i])); an exhausted uniform table (or a
+        row / position limit) -> an EmoError in the stream's slot."""
+        state, seq, segs = self.state.cpu().numpy(), self.seq.cpu().numpy(), self.segs.cpu().numpy()
+        out = []
+        for i, s in enumerate(self.streams):
+            st, ln = int(state[i, ACC_S_STATUS]), int(state[i, ACC_S_LEN])
+            ids = [int(t) for t in seq[i, :ln]]
+            if st == ACC_DONE:
+                out.append(ids[:-1])
+            elif st == ACC_STUCK:
+                out.append(ids)
+            elif st == ACC_WINDOW:
+                s.generated, s.seg = ids, [int(t) for t in segs[i, :ln]]
+                s.generated_bars, s.cur_pos, s.failed_cnt = (int(state[i, w]) for w in (ACC_S_BARS, ACC_S_CUR_POS, ACC_S_FAILED))
+                s.consumed = int(state[i, ACC_S_CONSUMED])
+                rs = np.random.RandomState([seed, i])
+                out.append(_resume_windowed(self.model, event2idx, idx2event, s, max_events, skip_check, self.temp, None,
+                                            lambda probs, rs=rs: nucleus(probs, self.top_p, rng=rs)))
+            elif st == ACC_OUT_OF_DRAWS:
+                out.append(EmoError('generate_accompaniments: stream %d used all %d uniforms of its table' % (i, self.U.shape[0])))
+            elif st == ACC_OVERFLOW:
+                out.append(EmoError('generate_accompaniments: stream %d: token row or lead-sheet table too short' % i))
+            else:
+                out.append(EmoError('generate_accompaniments: stream %d still running at position %d (positional table / cache end)' % (i, self.pos)))
+        return out
+
+
+def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, max_events=10000, skip_check=False, max_bars=None, temp=1.2, top_p=0.9,
+                            inadmissibles=None, seed=0, use_graph=True):
+    """The throughput path of generate_conditional_batch: the same arguments (no per-stream samplers) and result per stream, every draw and
+    the grammar of _Stream.offer on the device (emo_acc_grammar_step), each token step = grammar launch + one engine step (the one-launch
+    persistent step where the engine has one), k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS, default 16) and replayed until
+    every stream has finished.  Draws come from a uniform table [4 * max_dec_inp_len, n] seeded with `seed` (like generate_streams), so ids
+    are not NumPy-RNG-identical to generate_conditional_batch; they equal the host grammar driven by the same device draws.  A stream that
+    reaches the max_dec_inp_len window is finished on the host by _resume_windowed, whose draws (NumPy, seeded with (seed, i)) do not come
+    from the device table.  If the one-launch step gives up, the batch is run again from the start on the chain of launches, with the same
+    table.  -> (results, seconds); a stream whose table runs out holds an EmoError."""
+    _refuse(model, inadmissibles)
+    was_training = model.training
+    model.eval()
+    t0 = time.time()
+    kw = dict(max_events=max_events, skip_check=skip_check, max_bars=max_bars, temp=temp, top_p=top_p, seed=seed)
+    try:
+        loop = AccompanimentLoop(model, event2idx, idx2event, lead_sheets, primers, **kw)
+        try:
+            loop.run(use_graph=use_graph)
+        except _GaveUp as e:
+            print('[gen] %s -> the batch again on the chain of launches' % e)
+            loop = AccompanimentLoop(model, event2idx, idx2event, lead_sheets, primers, persistent=False, redraw=False, **kw)
+            loop.run(use_graph=use_graph)
+        out = loop.results(event2idx, idx2event, max_events, skip_check, seed)
+    finally:
+        model.train(was_training)
+    return out, time.time() - t0
+
+
 # ------------------------------------------------------------------------------------------------ command line (reference inference.py:330-485)
 def read_lead_sheet(path, event2idx):
     """A stage-1 output file: one event per line, optionally a Key_* line first, bars opened by Bar_None.  -> (key event, [[ids of bar 0], ...])"""
@@ -929,7 +1169,9 @@ def emotions_of(file_name):
 
 def main(argv=None):
     """Same flags as the reference's stage-2 inference.py (-m / -c / -r / -i / -o): every lead sheet found in the output directory gets its
-    accompaniment, all jobs of a run in lock-step on ONE decode engine (--streams at a time).  The generated events are written as text
+    accompaniment, all jobs of a run in lock-step on ONE decode engine (--streams at a time): generate_conditional_batch (NumPy sampling and
+    grammar on the host, seeds 0, 1, ... in job order), or with --device generate_accompaniments (device draws and grammar).  The generated
+    events are written as text
     (`<piece>_<emotion>_full.txt`, one event per line); turning them into MIDI is the reference's convert2midi.py (needs miditoolkit) and
     is run on those files when that module is importable."""
     import argparse
@@ -946,6 +1188,8 @@ def main(argv=None):
     ap.add_argument('--streams', type=int, default=32, help='lead sheets generated in lock-step on one decode engine')
     ap.add_argument('--max_bars', type=int, default=128)
     ap.add_argument('--dtype', default=None, choices=[None, 'bf16', 'fp32'])
+    ap.add_argument('--device', action='store_true', help='draws and grammar on the device (generate_accompaniments) instead of the host loop')
+    ap.add_argument('--seed', type=int, default=0, help='--device: seed of the uniform table (the group of streams j uses seed + j)')
     args = ap.parse_args(argv)
     conf = yaml.load(open(args.configuration), Loader=yaml.FullLoader)
     torch.cuda.set_device(conf['training']['gpuid'])
@@ -969,11 +1213,18 @@ def main(argv=None):
             primer = [event2idx['Emotion_%s' % e]] + ([event2idx[key]] if args.representation == 'functional' else []) + [event2idx['Tempo_110']]
             jobs.append((out, key, bars, primer))
     print('[# jobs]', len(jobs))
-    for i in range(0, len(jobs), args.streams):
+    for j, i in enumerate(range(0, len(jobs), args.streams)):
         group = jobs[i:i + args.streams]
-        gen = generate_conditional_batch(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
-                                         temp=temp, top_p=top_p, seeds=list(range(i, i + len(group))))
+        if args.device:
+            gen, _ = generate_accompaniments(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
+                                             temp=temp, top_p=top_p, seed=args.seed + j)
+        else:
+            gen = generate_conditional_batch(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
+                                             temp=temp, top_p=top_p, seeds=list(range(i, i + len(group))))
         for (out, key, _, _), ids in zip(group, gen):
+            if isinstance(ids, Exception):
+                print('[info] %s not written: %s' % (out, ids))
+                continue
             with open(out, 'w') as fh:
                 fh.write('\n'.join([key] + [idx2event[w] for w in ids]) + '\n')
             print('[info] wrote', out, len(ids), 'events')

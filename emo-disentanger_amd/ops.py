@@ -15,7 +15,7 @@ from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, BF16, F32, MUL_BI
 
 __all__ = ['gemm', 'colsum', 'embed_fwd', 'embed_bwd', 'layernorm_fwd', 'layernorm_bwd', 'dropout_apply', 'favor_attn_fwd',
            'favor_attn_bwd', 'favor_decode_step', 'performer_decode_step', 'performer_decode_step_sampled', 'favor_draw_omega', 'softmax_attn_fwd', 'softmax_attn_bwd', 'softmax_attn_decode', 'relpos_attn_fwd', 'relpos_attn_bwd', 'relpos_attn_decode', 'xent_fwd',
-           'xent_bwd', 'argmax', 'sample_nucleus', 'sample_nucleus_step', 'txl_grammar_step', 'accuracy_counts', 'sumsq', 'clip_coef', 'adam_step', 'cast', 'add_bias2',
+           'xent_bwd', 'argmax', 'sample_nucleus', 'sample_nucleus_step', 'txl_grammar_step', 'acc_grammar_step', 'accuracy_counts', 'sumsq', 'clip_coef', 'adam_step', 'cast', 'add_bias2',
            'ACT_NONE', 'ACT_RELU', 'ACT_GELU_NEW', 'ACT_GELU', 'MUL_NONE', 'MUL_NONZERO', 'MUL_DGELU_NEW', 'MUL_DGELU', 'MUL_BITMASK', 'gemm_bitmask_ok', 'gemm_lna_ok', 'bitmask_rows', 'favor_bwd_dn_ok', 'ffn_fwd', 'ffn_fwd_ok']
 
 
@@ -582,6 +582,30 @@ def txl_grammar_step(logits, temperature, top_p, key_temperature, key_top_p, u_s
     assert params.shape == (n, TXL_PARAM_WORDS) and state.shape == (n, TXL_STATE_WORDS) and seq.dim() == 2 and seq.shape[0] == n
     check(lib.emo_txl_grammar_step(ptr(logits), n, V, temperature, top_p, key_temperature, key_top_p, ptr(u_steps), u_steps.shape[0], ptr(ev_flags),
                                    ptr(ev_beat), ptr(params), ptr(state), ptr(seq), seq.shape[1], ptr(tok_out), ptr(running), stream()))
+    return tok_out
+
+
+ACC_PARAM_WORDS = ACC_STATE_WORDS = 8     # emo_hip.h: EMO_ACC_PARAM_WORDS / EMO_ACC_STATE_WORDS
+
+
+def acc_grammar_step(logits, temperature, top_p, u_steps, ev_flags, ev_beat, lead_tok, lead_off, params, state, seq, segs, max_len, track_full, pad,
+                     tok_out, seg_out, running):
+    """One stage-2 sample-and-grammar step of n streams (include/emo_hip.h emo_acc_grammar_step): logits fp32 [n, V], u_steps fp32 [n_u, n],
+    ev_flags / ev_beat int32 [V], lead_tok int64 (flat), lead_off int32, params / state int32 [n, 8], seq / segs int64 [n, W], tok_out / seg_out
+    int64 [n], running int32 [1].  Allocation-free (hipGraph capture); state, seq, segs, tok_out, seg_out and running are updated in place."""
+    n, V = logits.shape
+    assert V <= 1024 and temperature > 0
+    assert logits.is_contiguous() and logits.dtype == torch.float32
+    assert u_steps.dtype == torch.float32 and u_steps.is_contiguous() and u_steps.dim() == 2 and u_steps.shape[1] == n
+    for t, dt in ((ev_flags, torch.int32), (ev_beat, torch.int32), (lead_off, torch.int32), (params, torch.int32), (state, torch.int32),
+                  (running, torch.int32), (lead_tok, torch.int64), (seq, torch.int64), (segs, torch.int64), (tok_out, torch.int64), (seg_out, torch.int64)):
+        assert t.dtype == dt and t.is_contiguous()
+    assert ev_flags.numel() >= V and ev_beat.numel() >= V and running.numel() >= 1 and tok_out.numel() == n and seg_out.numel() == n
+    assert params.shape == (n, ACC_PARAM_WORDS) and state.shape == (n, ACC_STATE_WORDS)
+    assert seq.dim() == 2 and seq.shape[0] == n and segs.shape == seq.shape and lead_tok.numel() >= 1 and lead_off.numel() >= 1
+    check(lib.emo_acc_grammar_step(ptr(logits), n, V, temperature, top_p, ptr(u_steps), u_steps.shape[0], ptr(ev_flags), ptr(ev_beat), ptr(lead_tok),
+                                   ptr(lead_off), ptr(params), ptr(state), ptr(seq), ptr(segs), seq.shape[1], max_len, track_full, pad, ptr(tok_out),
+                                   ptr(seg_out), ptr(running), stream()))
     return tok_out
 
 

@@ -438,6 +438,37 @@ int emo_txl_grammar_step(const float* logits, int64_t n, int64_t V, float temper
                          const int32_t* ev_flags, const int32_t* ev_beat, const int32_t* params,
                          int32_t* state, int64_t* seq, int64_t ld_seq, int64_t* tok_out, int32_t* running,
                          emo_stream_t stream);
+/* Stage-2 accompaniment generation (stage2_accompaniment/inference.py generate_conditional :231-327): the draw and the grammar of one lock-step
+ * token step for n streams, one 512-thread workgroup per stream, all loop state in device memory (graph-capturable).  seq / segs (int64, pitch
+ * ld_seq) hold each stream's `generated` / segment ids; state[LEN] of them are valid, state[CONSUMED] have been fed to the model.  Per stream r:
+ *   not RUNNING                 -> tok_out[r] = pad, seg_out[r] = 1;
+ *   state[LEN] >= max_len       -> WINDOW (the reference's window slides at max_dec_inp_len), then as above;
+ *   state[CONSUMED] < state[LEN] -> tok_out[r] / seg_out[r] = seq / segs[r, CONSUMED], CONSUMED += 1 (no draw);
+ *   otherwise draw from logits[r] (fp32 [n, V], V <= 1024) with u_steps[state[DRAWS] * n + r] (u_steps [n_u, n]; the device code of
+ *   emo_sample_nucleus, so the same id), DRAWS += 1, and run the grammar of the reference: with params[SKIP_CHECK] == 0 a Beat below
+ *   state[CUR_POS] is rejected and counted (256 in a row -> STUCK; accepted: CUR_POS = its position, count reset); Track_LeadSheet is appended
+ *   with segment 0 and BARS += 1, then below params[TARGET_BARS] the next lead-sheet bar (segment 0) and track_full (segment 1) are appended
+ *   and CUR_POS = 0, else DONE; PAD, and EOS before the last bar, are rejected (not counted); EOS at the last bar is appended and DONE; any
+ *   other event is appended with segment 1 (DONE when the length exceeds params[MAX_EVENTS]).  A rejected sample is drawn again from the same
+ *   logits with the next uniform INSIDE the launch (the reference's `continue`), until an acceptance, STUCK or the end of the table
+ *   (OUT_OF_DRAWS).  A stream still RUNNING then feeds seq[r, CONSUMED] as above; one that finished feeds pad.  *running is decremented once
+ *   per stream that leaves RUNNING.
+ * ev_flags [V] (EMO_ACC_EV_* bits: 'Beat' in e, e == 'Track_LeadSheet', e == 'PAD_None', e == 'EOS_None') and ev_beat [V] (beat_position of
+ * Beat events) are built on the host from idx2event.  Lead sheets: lead_tok int64 (all bars of all streams, flat) and lead_off int32: bar j of
+ * stream r is lead_tok[lead_off[params[BAR0] + j] .. lead_off[params[BAR0] + j + 1]), j < params[N_BARS].  Rows of width >= max_len + the
+ * longest bar + 2 always hold an injected bar; a row or a bar table too short for a step is a caller error (OVERFLOW).
+ * params int32 [n, EMO_ACC_PARAM_WORDS], state int32 [n, EMO_ACC_STATE_WORDS], laid out as the enums below. */
+enum { EMO_ACC_P_TARGET_BARS = 0, EMO_ACC_P_MAX_EVENTS = 1, EMO_ACC_P_SKIP_CHECK = 2, EMO_ACC_P_BAR0 = 3, EMO_ACC_P_N_BARS = 4, EMO_ACC_PARAM_WORDS = 8 };
+enum { EMO_ACC_S_STATUS = 0, EMO_ACC_S_LEN = 1 /* tokens in seq[r] */, EMO_ACC_S_CONSUMED = 2 /* tokens fed to the model */,
+       EMO_ACC_S_BARS = 3 /* generated_bars */, EMO_ACC_S_CUR_POS = 4, EMO_ACC_S_FAILED = 5 /* rejected Beats in a row */, EMO_ACC_S_DRAWS = 6,
+       EMO_ACC_S_ACCEPTED = 7 /* accepted draws */, EMO_ACC_STATE_WORDS = 8 };
+enum { EMO_ACC_RUNNING = 0, EMO_ACC_DONE = 1, EMO_ACC_STUCK = 2, EMO_ACC_WINDOW = 3, EMO_ACC_OUT_OF_DRAWS = 4, EMO_ACC_OVERFLOW = 5 };
+enum { EMO_ACC_EV_BEAT = 1, EMO_ACC_EV_TRACK_LS = 2, EMO_ACC_EV_PAD = 4, EMO_ACC_EV_EOS = 8 };
+int emo_acc_grammar_step(const float* logits, int64_t n, int64_t V, float temperature, float top_p,
+                         const float* u_steps, int64_t n_u, const int32_t* ev_flags, const int32_t* ev_beat,
+                         const int64_t* lead_tok, const int32_t* lead_off, const int32_t* params, int32_t* state,
+                         int64_t* seq, int64_t* segs, int64_t ld_seq, int64_t max_len, int64_t track_full,
+                         int64_t pad, int64_t* tok_out, int64_t* seg_out, int32_t* running, emo_stream_t stream);
 /* counts[0..5] += {nonpad, nonpad&correct, chord, chord&correct, melody, melody&correct} (train.py:184-193) */
 int emo_accuracy_counts(const float* logits, const int64_t* tgt, const int64_t* chord,
                         const int64_t* melody, int64_t M, int64_t V, int64_t pad, int64_t* counts,
