@@ -81,6 +81,8 @@ _SIG = {
     'emo_softmax_attn_decode_layout': (c_i, [c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_i, c_l, c_l, c_l, c_i, c_p]),
     'emo_xent_fwd': (c_i, [c_p, c_p, c_l, c_l, c_l, c_p, c_p, c_p]),
     'emo_xent_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_l, c_l, c_l, c_p]),
+    'emo_token_scores': (c_i, [c_p, c_l, c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_p, c_p]),
+    'emo_xent_bwd_rows': (c_i, [c_p, c_l, c_p, c_p, c_p, c_p, c_l, c_i, c_l, c_l, c_l, c_p]),
     'emo_argmax': (c_i, [c_p, c_l, c_l, c_p, c_p]),
     'emo_sample_nucleus': (c_i, [c_p, c_l, c_l, c_f, c_f, c_p, c_p, c_p]),
     'emo_sample_nucleus_step': (c_i, [c_p, c_l, c_l, c_f, c_f, c_p, c_p, c_p, c_l, c_l, c_p, c_p]),

@@ -733,6 +733,45 @@ class XentFn(torch.autograd.Function):
         return g, None, None
 
 
+class XentRowsFn(torch.autograd.Function):
+    """F.cross_entropy(ignore_index, reduction='none') on fp32 logits: the flat fp32 [M] vector of per-row losses (0 on ignored rows), with the
+    per-row upstream gradient carried back by emo_xent_bwd_rows.  reduction='sum' is its .sum(); 'mean' stays with XentFn."""
+
+    @staticmethod
+    def forward(ctx, logits, tgt, ignore_index):
+        V = logits.shape[-1]
+        l2 = padded_logits(logits)                                # read LogitsFn's padded buffer in place: only columns < V are touched
+        if l2 is None:
+            l2 = logits.reshape(-1, V)
+            if l2.stride(-1) != 1:
+                l2 = l2.contiguous()
+        t = tgt.reshape(-1)
+        check_ids(t, V, 'cross-entropy targets', also=ignore_index)
+        out = ops.token_scores(l2, t, ignore_index, V=V, want=('lse',))
+        ctx.save_for_backward(l2, t, out['lse'])
+        ctx.ignore, ctx.shape = ignore_index, logits.shape
+        return out['nll']
+
+    @staticmethod
+    def backward(ctx, gout):
+        l2, t, lse = ctx.saved_tensors
+        V = ctx.shape[-1]
+        ld_out = l2.shape[1] if l2.shape[1] != V else None        # a padded projection gets its gradient in the same padded layout (pad columns zero)
+        dl = ops.xent_bwd_rows(l2, t, lse, gout.float().reshape(-1), ctx.ignore, torch.float32, V=V, ld_out=ld_out)
+        g = dl.view(ctx.shape) if dl.shape[1] == V else _as_view(dl, V, ctx.shape)
+        return g, None, None
+
+
+def xent_rows(logits, tgt, ignore_index, reduction):
+    """compute_loss's cross-entropy for the reductions other than 'mean' (which is XentFn's): 'none' -> flat fp32 [M], 'sum' -> its sum;
+    any other string is refused the way F.cross_entropy refuses it."""
+    if reduction == 'none':
+        return XentRowsFn.apply(logits, tgt, ignore_index)
+    if reduction == 'sum':
+        return XentRowsFn.apply(logits, tgt, ignore_index).sum()
+    raise ValueError('%s is not a valid value for reduction' % reduction)
+
+
 _PADDED = {}                   # data_ptr -> weakref of a buffer LogitsFn.forward produced (pad columns = LOGIT_PAD_FILL)
 
 

@@ -1123,7 +1123,7 @@ class AccompanimentLoop:
 
 
 def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, max_events=10000, skip_check=False, max_bars=None, temp=1.2, top_p=0.9,
-                            inadmissibles=None, seed=0, use_graph=True):
+                            inadmissibles=None, seed=0, use_graph=True, best_of=1):
     """The throughput path of generate_conditional_batch: the same arguments (no per-stream samplers) and result per stream, every draw and
     the grammar of _Stream.offer on the device (emo_acc_grammar_step), each token step = grammar launch + one engine step (the one-launch
     persistent step where the engine has one), k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS, default 16) and replayed until
@@ -1131,8 +1131,21 @@ def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, m
     are not NumPy-RNG-identical to generate_conditional_batch; they equal the host grammar driven by the same device draws.  A stream that
     reaches the max_dec_inp_len window is finished on the host by _resume_windowed, whose draws (NumPy, seeded with (seed, i)) do not come
     from the device table.  If the one-launch step gives up, the batch is run again from the start on the chain of launches, with the same
-    table.  -> (results, seconds); a stream whose table runs out holds an EmoError."""
+    table.  -> (results, seconds); a stream whose table runs out holds an EmoError.
+
+    best_of = N > 1: every lead sheet runs as N streams of the same batch (stream i * N + c is candidate c of lead sheet i; each stream has its
+    own column of the uniform table, so the draws differ), every finished candidate is scored (scoring.targets_of + score_tokens: mean negative
+    log-probability over its Track_Full targets, on its first max_dec_inp_len tokens) and the candidate with the lowest one is returned; ties go
+    to the lowest candidate index, a candidate that failed never wins.  -> (results, seconds, picks), picks[i] = {'chosen': c, 'nll_mean': [N
+    floats, NaN for a failed candidate], 'candidates': [N results]}.  best_of = 1 is the path above, draw for draw."""
     _refuse(model, inadmissibles)
+    best_of = int(best_of)
+    if best_of < 1:
+        raise ValueError('best_of must be at least 1')
+    n_sheets = len(lead_sheets)
+    if best_of > 1:
+        lead_sheets = [ls for ls in lead_sheets for _ in range(best_of)]
+        primers = [p for p in primers for _ in range(best_of)]
     was_training = model.training
     model.eval()
     t0 = time.time()
@@ -1146,6 +1159,14 @@ def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, m
             loop = AccompanimentLoop(model, event2idx, idx2event, lead_sheets, primers, persistent=False, redraw=False, **kw)
             loop.run(use_graph=use_graph)
         out = loop.results(event2idx, idx2event, max_events, skip_check, seed)
+        if best_of > 1:
+            from . import scoring
+            nll = scoring.candidate_scores(model, event2idx, out, loop.bound)
+            picks = []
+            for i in range(n_sheets):
+                sl = slice(i * best_of, (i + 1) * best_of)
+                picks.append({'chosen': scoring.best_of(nll[sl]), 'nll_mean': nll[sl], 'candidates': out[sl]})
+            return [p['candidates'][p['chosen']] for p in picks], time.time() - t0, picks
     finally:
         model.train(was_training)
     return out, time.time() - t0
@@ -1190,7 +1211,11 @@ def main(argv=None):
     ap.add_argument('--dtype', default=None, choices=[None, 'bf16', 'fp32'])
     ap.add_argument('--device', action='store_true', help='draws and grammar on the device (generate_accompaniments) instead of the host loop')
     ap.add_argument('--seed', type=int, default=0, help='--device: seed of the uniform table (the group of streams j uses seed + j)')
+    ap.add_argument('--best-of', dest='best_of', type=int, default=1,
+                    help='--device: candidates generated per lead sheet; the one with the lowest mean negative log-probability is written')
     args = ap.parse_args(argv)
+    if args.best_of < 1 or (args.best_of > 1 and not args.device):
+        ap.error('--best-of needs --device and a count of at least 1')
     conf = yaml.load(open(args.configuration), Loader=yaml.FullLoader)
     torch.cuda.set_device(conf['training']['gpuid'])
     event2idx, idx2event, pad = load_vocab(conf['data_loader']['vocab_path'].format(args.representation))
@@ -1213,9 +1238,15 @@ def main(argv=None):
             primer = [event2idx['Emotion_%s' % e]] + ([event2idx[key]] if args.representation == 'functional' else []) + [event2idx['Tempo_110']]
             jobs.append((out, key, bars, primer))
     print('[# jobs]', len(jobs))
-    for j, i in enumerate(range(0, len(jobs), args.streams)):
-        group = jobs[i:i + args.streams]
-        if args.device:
+    per_group = max(1, args.streams // args.best_of)              # --streams counts engine streams: N of them per lead sheet with --best-of N
+    for j, i in enumerate(range(0, len(jobs), per_group)):
+        group = jobs[i:i + per_group]
+        if args.device and args.best_of > 1:
+            gen, _, picks = generate_accompaniments(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
+                                                    temp=temp, top_p=top_p, seed=args.seed + j, best_of=args.best_of)
+            for g, p in zip(group, picks):
+                print('[info] %s: candidate %d of %s' % (g[0], p['chosen'], ['%.4f' % x for x in p['nll_mean']]))
+        elif args.device:
             gen, _ = generate_accompaniments(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
                                              temp=temp, top_p=top_p, seed=args.seed + j)
         else:

@@ -93,8 +93,10 @@ class MusicLMBase(nn.Module):
         return engine.LogitsFn.apply(self, h)
 
     def compute_loss(self, dec_logits, dec_tgt, reduction='mean'):
-        """music_performer.py:72-81."""
+        """music_performer.py:72-81.  reduction: 'mean' (scalar), 'sum' (scalar) or 'none' (flat fp32 [B*T], 0 at pad targets), as
+        F.cross_entropy takes it; all three are differentiable."""
         if reduction != 'mean':
-            raise NotImplementedError("only reduction='mean' (the reference's only use) is built")
+            recons_loss = engine.xent_rows(dec_logits, dec_tgt.long(), self.n_token - 1, reduction)
+            return {'recons_loss': recons_loss, 'total_loss': recons_loss}
         recons_loss = engine.XentFn.apply(dec_logits, dec_tgt.long(), self.n_token - 1).float()
         return {'recons_loss': recons_loss, 'total_loss': recons_loss}

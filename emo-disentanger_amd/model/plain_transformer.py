@@ -479,8 +479,9 @@ class PlainTransformer(nn.Module):
 
     def compute_loss(self, dec_logits, dec_tgt, reduction='mean'):
         """plain_transformer.py:82-93 (evaluation use: validation loss); the fused cross-entropy of the stage-2 path."""
-        if reduction != 'mean':
-            raise NotImplementedError("only reduction='mean' (the reference's only use) is built")
         V = dec_logits.size(-1)
+        if reduction != 'mean':                                   # 'none' (flat fp32 [T*B]) / 'sum', as F.cross_entropy takes them
+            ce = engine.xent_rows(dec_logits.reshape(-1, V), dec_tgt.contiguous().view(-1).long(), self.pad_index, reduction)
+            return {'ce_loss': ce, 'total_loss': ce}
         ce = engine.XentFn.apply(dec_logits.reshape(-1, V).contiguous(), dec_tgt.contiguous().view(-1).long(), self.pad_index).float()
         return {'ce_loss': ce, 'total_loss': ce}

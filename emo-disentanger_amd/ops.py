@@ -15,7 +15,7 @@ from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, BF16, F32, MUL_BI
 
 __all__ = ['gemm', 'colsum', 'embed_fwd', 'embed_bwd', 'layernorm_fwd', 'layernorm_bwd', 'dropout_apply', 'favor_attn_fwd',
            'favor_attn_bwd', 'favor_decode_step', 'performer_decode_step', 'performer_decode_step_sampled', 'favor_draw_omega', 'softmax_attn_fwd', 'softmax_attn_bwd', 'softmax_attn_decode', 'relpos_attn_fwd', 'relpos_attn_bwd', 'relpos_attn_decode', 'xent_fwd',
-           'xent_bwd', 'argmax', 'sample_nucleus', 'sample_nucleus_step', 'txl_grammar_step', 'acc_grammar_step', 'accuracy_counts', 'sumsq', 'clip_coef', 'adam_step', 'cast', 'add_bias2',
+           'xent_bwd', 'token_scores', 'xent_bwd_rows', 'argmax', 'sample_nucleus', 'sample_nucleus_step', 'txl_grammar_step', 'acc_grammar_step', 'accuracy_counts', 'sumsq', 'clip_coef', 'adam_step', 'cast', 'add_bias2',
            'ACT_NONE', 'ACT_RELU', 'ACT_GELU_NEW', 'ACT_GELU', 'MUL_NONE', 'MUL_NONZERO', 'MUL_DGELU_NEW', 'MUL_DGELU', 'MUL_BITMASK', 'gemm_bitmask_ok', 'gemm_lna_ok', 'bitmask_rows', 'favor_bwd_dn_ok', 'ffn_fwd', 'ffn_fwd_ok']
 
 
@@ -532,6 +532,41 @@ def xent_bwd(logits, tgt, lse, gscale, ignore_index, out_dtype, ld_out=None):
     tgt = _c(tgt)
     check(lib.emo_xent_bwd(ptr(logits), ptr(tgt), ptr(lse), ptr(gscale), ptr(dl), ld_out, dtype_code(out_dtype), M, V,
                            ignore_index, stream()))
+    return dl
+
+
+def token_scores(logits, tgt, ignore_index, V=None, want=('lse', 'rank', 'entropy')):
+    """Per-row cross-entropy terms of fp32 logits [M, ld] (row-strided views allowed; only columns < V are read, V defaults to the width):
+    dict with 'nll' (0 on ignored rows) and whichever of 'lse', 'rank' (int32, -1 on ignored rows), 'entropy' `want` names."""
+    assert logits.dtype == torch.float32
+    M, ld = logits.shape[0], _rows(logits)
+    V = logits.shape[1] if V is None else V
+    assert 0 < V <= logits.shape[1] and tgt.numel() == M
+    unknown = set(want) - {'nll', 'lse', 'rank', 'entropy'}
+    if unknown:
+        raise ValueError('token_scores: unknown output(s) %s' % sorted(unknown))
+    tgt = _c(tgt.reshape(-1))
+    out = {'nll': torch.empty(M, device=logits.device, dtype=torch.float32)}
+    for name in ('lse', 'rank', 'entropy'):
+        if name in want:
+            out[name] = torch.empty(M, device=logits.device, dtype=torch.int32 if name == 'rank' else torch.float32)
+    check(lib.emo_token_scores(ptr(logits), ld, ptr(tgt), M, V, ignore_index, ptr(out['nll']), ptr(out.get('lse')), ptr(out.get('rank')),
+                               ptr(out.get('entropy')), stream()))
+    return out
+
+
+def xent_bwd_rows(logits, tgt, lse, grow, ignore_index, out_dtype, V=None, ld_out=None):
+    """xent_bwd with one upstream gradient per row (grow: fp32 [M]); logits as in token_scores."""
+    assert logits.dtype == torch.float32 and grow.dtype == torch.float32 and lse.dtype == torch.float32
+    M, ld = logits.shape[0], _rows(logits)
+    V = logits.shape[1] if V is None else V
+    assert 0 < V <= logits.shape[1] and tgt.numel() == M and grow.numel() == M and lse.numel() == M
+    ld_out = ld_out or ((V + 7) // 8) * 8
+    dl = torch.empty(M, ld_out, device=logits.device, dtype=out_dtype)
+    tgt = _c(tgt.reshape(-1))
+    grow = grow if grow.is_contiguous() else grow.contiguous()
+    check(lib.emo_xent_bwd_rows(ptr(logits), ld, ptr(tgt), ptr(lse), ptr(grow), ptr(dl), ld_out, dtype_code(out_dtype), M, V,
+                                ignore_index, stream()))
     return dl
 
 

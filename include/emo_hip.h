@@ -399,6 +399,23 @@ int emo_xent_bwd(const float* logits, const int64_t* tgt, const float* row_lse, 
                  void* dlogits, int64_t ld_out /* >= V; columns V..ld_out-1 are zero-filled */,
                  int dtype_out, int64_t M, int64_t V, int64_t ignore_index, emo_stream_t stream);
 
+/* ------------------------------------------------------------------ K9b: per-row cross-entropy terms (sequence scoring)
+ * What F.cross_entropy(..., reduction='none' / 'sum') computes — compute_loss hands `reduction` straight to it
+ * (model/music_performer.py:72-81, model/music_gpt2.py:94-103) — plus the per-token figures a scoring pass reports.
+ * logits: fp32 [M, ld], ld >= V; only columns < V are read (ld > V: LogitsFn's padded projection, no copy).
+ * Every output is [M]; all but nll may be NULL:
+ *   nll[m]     = lse[m] - logits[m, tgt[m]];  0 where tgt[m] == ignore_index (F.cross_entropy's value there)
+ *   lse[m]     = log sum_v exp(logits[m, v])  (bit-identical to the row_lse of the forward above on the same values)
+ *   rank[m]    = #{v : l[v] > l[tgt]} + #{v < tgt : l[v] == l[tgt]}: 0 exactly where the argmax below returns tgt[m]
+ *                ("first max wins");  -1 on ignored rows
+ *   entropy[m] = lse - sum_v softmax(l)_v l_v  in nats, ignored rows included
+ * bwd_rows: dlogits[m,v] = (exp(l - lse) - [v==tgt]) * (tgt!=ignore) * grow[m]   (grow: fp32 [M], the upstream gradient of nll) */
+int emo_token_scores(const float* logits, int64_t ld, const int64_t* tgt, int64_t M, int64_t V, int64_t ignore_index,
+                     float* nll, float* lse, int32_t* rank, float* entropy, emo_stream_t stream);
+int emo_xent_bwd_rows(const float* logits, int64_t ld, const int64_t* tgt, const float* row_lse, const float* grow,
+                      void* dlogits, int64_t ld_out /* >= V; columns V..ld_out-1 are zero-filled */,
+                      int dtype_out, int64_t M, int64_t V, int64_t ignore_index, emo_stream_t stream);
+
 /* ------------------------------------------------------------------ K10/K12: sampling + accuracy
  * argmax over V per row (greedy / parity mode; first max wins like np.argmax / torch.argmax).
  * nucleus: softmax(l/temp) -> sort desc -> keep through the token that crosses top_p
