@@ -88,6 +88,7 @@ _SIG = {
     'emo_sample_nucleus_step': (c_i, [c_p, c_l, c_l, c_f, c_f, c_p, c_p, c_p, c_l, c_l, c_p, c_p]),
     'emo_txl_grammar_step': (c_i, [c_p, c_l, c_l, c_f, c_f, c_f, c_f, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_p]),
     'emo_acc_grammar_step': (c_i, [c_p, c_l, c_l, c_f, c_f, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_p, c_p, c_p, c_p]),
+    'emo_acc_window_step': (c_i, [c_p, c_l, c_l, c_f, c_f, c_p, c_l, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_p]),
     'emo_accuracy_counts': (c_i, [c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_p, c_p]),
     'emo_sumsq': (c_i, [c_p, c_l, c_p, c_p]),
     'emo_clip_coef': (c_i, [c_p, c_f, c_f, c_p, c_p, c_p]),

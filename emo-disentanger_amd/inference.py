@@ -978,6 +978,7 @@ class AccompanimentLoop:
         assert n == len(primers) and n > 0
         _refuse(model, None)
         self.model, self.temp, self.top_p = model, float(temp), float(top_p)
+        self.max_events = int(max_events)
         self.W = int(max_dec_inp_len)                 # read at call time (tests lower it)
         dev = self.dev = next(model.parameters()).device
         self.streams = [_Stream(event2idx, lead_sheets[i], primers[i], max_bars) for i in range(n)]
@@ -987,6 +988,7 @@ class AccompanimentLoop:
         toks, offs, bar0, nbars, longest = pack_lead_sheets(lead_sheets)
         self.lead_tok, self.lead_off = torch.from_numpy(toks).to(dev), torch.from_numpy(offs).to(dev)
         self.track_full, self.pad = event2idx['Track_Full'], event2idx.get('PAD_None', 0)
+        self.longest_bar = longest
         lens = [len(s.generated) for s in self.streams]
         width = max(self.W, max(lens)) + longest + 2              # an injected bar + Track_Full always fit behind an accepted word
         seq, segs = np.zeros((n, width), np.int64), np.zeros((n, width), np.int64)
@@ -1093,11 +1095,28 @@ class AccompanimentLoop:
         return {'finished': int((st == ACC_DONE).sum()), 'stuck': int((st == ACC_STUCK).sum()), 'window': int((st == ACC_WINDOW).sum()),
                 'other': int(((st != ACC_DONE) & (st != ACC_STUCK) & (st != ACC_WINDOW)).sum())}
 
-    def results(self, event2idx, idx2event, max_events, skip_check, seed):
+    def handed_off(self, i, state=None, seq=None, segs=None):
+        """Stream i as the host grammar continues it: its _Stream rebuilt from the device state (host copies may be passed in)."""
+        state = self.state.cpu().numpy() if state is None else state
+        seq = self.seq[i].cpu().numpy() if seq is None else seq[i]
+        segs = self.segs[i].cpu().numpy() if segs is None else segs[i]
+        s, ln = self.streams[i], int(state[i, ACC_S_LEN])
+        s.generated, s.seg = [int(t) for t in seq[:ln]], [int(t) for t in segs[:ln]]
+        s.generated_bars, s.cur_pos, s.failed_cnt = (int(state[i, w]) for w in (ACC_S_BARS, ACC_S_CUR_POS, ACC_S_FAILED))
+        s.consumed = int(state[i, ACC_S_CONSUMED])
+        return s
+
+    def results(self, event2idx, idx2event, max_events, skip_check, seed, window='host'):
         """Per stream what _Stream.result() gives: DONE -> generated[:-1], STUCK -> generated; WINDOW -> the stream rebuilt from the device
-        state and finished by _resume_windowed with nucleus(probs, top_p, rng=RandomState([seed, i])); an exhausted uniform table (or a
-        row / position limit) -> an EmoError in the stream's slot."""
+        state and finished by _resume_windowed with nucleus(probs, top_p, rng=RandomState([seed, i])), or with window='device' finished
+        together with the other WINDOW streams by a WindowedLoop (kept in self.windowed); an exhausted uniform table (or a row / position
+        limit) -> an EmoError in the stream's slot."""
         state, seq, segs = self.state.cpu().numpy(), self.seq.cpu().numpy(), self.segs.cpu().numpy()
+        past = {}
+        if window == 'device' and (state[:, ACC_S_STATUS] == ACC_WINDOW).any():
+            self.windowed = WindowedLoop(self, seed)
+            self.windowed.run()
+            past = dict(zip(self.windowed.idx, self.windowed.results()))
         out = []
         for i, s in enumerate(self.streams):
             st, ln = int(state[i, ACC_S_STATUS]), int(state[i, ACC_S_LEN])
@@ -1106,10 +1125,10 @@ class AccompanimentLoop:
                 out.append(ids[:-1])
             elif st == ACC_STUCK:
                 out.append(ids)
+            elif st == ACC_WINDOW and i in past:
+                out.append(past[i])
             elif st == ACC_WINDOW:
-                s.generated, s.seg = ids, [int(t) for t in segs[i, :ln]]
-                s.generated_bars, s.cur_pos, s.failed_cnt = (int(state[i, w]) for w in (ACC_S_BARS, ACC_S_CUR_POS, ACC_S_FAILED))
-                s.consumed = int(state[i, ACC_S_CONSUMED])
+                s = self.handed_off(i, state, seq, segs)
                 rs = np.random.RandomState([seed, i])
                 out.append(_resume_windowed(self.model, event2idx, idx2event, s, max_events, skip_check, self.temp, None,
                                             lambda probs, rs=rs: nucleus(probs, self.top_p, rng=rs)))
@@ -1122,22 +1141,157 @@ class AccompanimentLoop:
         return out
 
 
+WINDOW_TAG = 0x57494E                  # the windowed phase's uniform table is seeded with (seed, this tag): never the in-window table's seed
+
+
+def window_compaction(live):
+    """The compaction rule of WindowedLoop.  live: one bool per row of the current batch, in batch order -> the positions the batch continues
+    on: the live ones, in order, once they are at most half of the rows; every position until then (a smaller batch means new GEMM shapes and a
+    fresh gather of the windows, so it has to pay: one long stream must not carry 31 finished rows through every forward)."""
+    keep = [p for p, x in enumerate(live) if x]
+    return keep if 2 * len(keep) <= len(live) else list(range(len(live)))
+
+
+class WindowedLoop:
+    """The ACC_WINDOW streams of a finished AccompanimentLoop, continued together on the device (the reference's sliding window, inference.py
+    :252-277, which _resume_windowed runs one stream and one host round trip at a time).  One step = one forward over the streams' last W tokens,
+    model(win_tok, seg_inp=win_seg, keep_last_only=True) on [m, W] — positions restart at 0, so nothing carries over between steps — and
+    emo_acc_window_step: the draw, the in-launch redraws, the grammar, and the next window of every stream still running.  Streams are indexed
+    by their place j among the WINDOW streams (self.idx[j] = the stream of the first loop): seq / segs [m0, width] (copies, wide enough for the
+    whole piece), params / state [m0, 8] (status RUNNING again, draw counter 0), the uniform table U [n_u, m0] of this phase alone, seeded with
+    (seed, WINDOW_TAG).  The host reads the running count once every `steps_per_poll` steps (EMO_GEN_GRAPH_STEPS, default 16; steps a stream
+    does not need are no-ops for it) and then applies window_compaction: self.rows (int32, stream j of each batch row) shrinks, nothing else
+    moves.  self.batch_rows: the row count of every step run.  The forward is the model's eager one (not captured in a hipGraph: DESIGN.md)."""
+
+    def __init__(self, loop, seed, n_u=None, steps_per_poll=None):
+        self.loop, self.model, self.dev = loop, loop.model, loop.dev
+        self.W, self.temp, self.top_p = loop.W, loop.temp, loop.top_p
+        dev, W = self.dev, self.W
+        state = loop.state.cpu().numpy()
+        self.idx = [i for i in range(loop.n) if state[i, ACC_S_STATUS] == ACC_WINDOW]
+        m0 = self.m0 = len(self.idx)
+        assert m0 > 0, 'no stream reached the window'
+        self.k = max(1, int(steps_per_poll or os.environ.get('EMO_GEN_GRAPH_STEPS', 16)))
+        sel = torch.tensor(self.idx, dtype=torch.long, device=dev)
+        len0 = state[self.idx, ACC_S_LEN].astype(np.int64)
+        self.len0 = len0
+        w0 = loop.seq.shape[1]
+        width = max(w0, int(len0.max()) + loop.max_events + loop.longest_bar + 2)     # the whole piece: max_events, the longest bar and 2 past the handoff
+        self.seq = torch.zeros(m0, width, dtype=torch.int64, device=dev)
+        self.segs = torch.zeros(m0, width, dtype=torch.int64, device=dev)
+        self.seq[:, :w0], self.segs[:, :w0] = loop.seq[sel], loop.segs[sel]
+        self.params = loop.params[sel].contiguous()
+        self.state = loop.state[sel].contiguous()
+        self.state[:, ACC_S_STATUS] = ACC_RUNNING
+        self.state[:, ACC_S_DRAWS] = 0
+        self.accepted0 = int(self.state[:, ACC_S_ACCEPTED].sum().item())
+        self.running = torch.tensor([m0], dtype=torch.int32, device=dev)
+        gen = torch.Generator(device=dev)
+        gen.manual_seed((int(seed) * 0x9E3779B1 + WINDOW_TAG) & 0x7FFFFFFFFFFFFFFF)
+        # max_events draws can be accepted at most; every rejected run before an acceptance is shorter than 256 Beats plus the PAD / early-EOS
+        # draws, which a trained model all but never makes: as many again, and one STUCK run
+        self.U = torch.rand(int(n_u or 2 * loop.max_events + 256), m0, device=dev, generator=gen)
+        self.win_tok = torch.zeros(m0, W, dtype=torch.int64, device=dev)
+        self.win_seg = torch.zeros(m0, W, dtype=torch.int64, device=dev)
+        self.logits = torch.zeros(m0, self.model.n_token, dtype=torch.float32, device=dev)
+        self.fwd_kw = {'attn_kwargs': {'omit_feature_map_draw': True}} if self.model.kind == 'performer' else {}
+        self.batch_rows, self.steps, self.seconds = [], 0, 0.0
+        self._set_rows(list(range(m0)))
+
+    def _set_rows(self, rows):
+        """The batch continues on these streams: rows [m] and their windows seq / segs[j, LEN - W .. LEN), gathered on the device."""
+        if not rows or len(set(rows)) != len(rows) or min(rows) < 0 or max(rows) >= self.m0:
+            raise EmoError('WindowedLoop: batch rows %r are not distinct streams of 0 .. %d' % (rows, self.m0 - 1))
+        self.m = len(rows)
+        self.rows_host = list(rows)
+        self.rows = torch.tensor(rows, dtype=torch.int32, device=self.dev)
+        r = self.rows.long()
+        col = (self.state[r, ACC_S_LEN].long() - self.W).view(-1, 1) + torch.arange(self.W, device=self.dev).view(1, -1)
+        self.win_tok[:self.m] = self.seq[r].gather(1, col)
+        self.win_seg[:self.m] = self.segs[r].gather(1, col)
+
+    def one_step(self):
+        m = self.m
+        self.logits[:m].copy_(self.model(self.win_tok[:m], seg_inp=self.win_seg[:m], keep_last_only=True, **self.fwd_kw))
+        lp = self.loop
+        ops.acc_window_step(self.logits[:m], self.temp, self.top_p, self.U, self.rows, lp.ev_flags, lp.ev_beat, lp.lead_tok, lp.lead_off, self.params,
+                            self.state, self.seq, self.segs, self.W, lp.track_full, self.win_tok[:m], self.win_seg[:m], self.running)
+        self.batch_rows.append(m)
+        self.steps += 1
+
+    def poll(self):
+        """Running count (synchronises), then the compaction rule (window_compaction alone decides).  -> streams still running."""
+        live = int(self.running.item())
+        if live > 0:
+            status = self.state[:, ACC_S_STATUS].cpu().numpy()
+            keep = window_compaction([status[j] == ACC_RUNNING for j in self.rows_host])
+            if len(keep) < self.m:
+                self._set_rows([self.rows_host[p] for p in keep])
+        return live
+
+    def run(self, max_steps=None):
+        """Steps until no stream is RUNNING (or `max_steps` steps have run: benchmarks), polling every k steps."""
+        was_training = self.model.training
+        self.model.eval()
+        t0 = time.perf_counter()
+        try:
+            with torch.no_grad():
+                while max_steps is None or self.steps < max_steps:
+                    for _ in range(self.k if max_steps is None else min(self.k, max_steps - self.steps)):
+                        self.one_step()
+                    if self.poll() == 0:
+                        break
+                torch.cuda.synchronize()
+        finally:
+            self.model.train(was_training)
+        self.seconds += time.perf_counter() - t0
+
+    def accepted_draws(self):
+        return int(self.state[:, ACC_S_ACCEPTED].sum().item()) - self.accepted0
+
+    def results(self):
+        """Per WINDOW stream, in the order of self.idx, what _Stream.result() gives (or an EmoError, as AccompanimentLoop.results)."""
+        state, seq = self.state.cpu().numpy(), self.seq.cpu().numpy()
+        out = []
+        for j, i in enumerate(self.idx):
+            st, ids = int(state[j, ACC_S_STATUS]), [int(t) for t in seq[j, :int(state[j, ACC_S_LEN])]]
+            if st == ACC_DONE:
+                out.append(ids[:-1])
+            elif st == ACC_STUCK:
+                out.append(ids)
+            elif st == ACC_OUT_OF_DRAWS:
+                out.append(EmoError('generate_accompaniments: stream %d used all %d uniforms of its windowed table' % (i, self.U.shape[0])))
+            elif st == ACC_OVERFLOW:
+                out.append(EmoError('generate_accompaniments: stream %d: token row or lead-sheet table too short past the window' % i))
+            else:
+                out.append(EmoError('generate_accompaniments: stream %d still running after %d windowed steps' % (i, self.steps)))
+        return out
+
+
 def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, max_events=10000, skip_check=False, max_bars=None, temp=1.2, top_p=0.9,
-                            inadmissibles=None, seed=0, use_graph=True, best_of=1):
+                            inadmissibles=None, seed=0, use_graph=True, best_of=1, window='host'):
     """The throughput path of generate_conditional_batch: the same arguments (no per-stream samplers) and result per stream, every draw and
     the grammar of _Stream.offer on the device (emo_acc_grammar_step), each token step = grammar launch + one engine step (the one-launch
     persistent step where the engine has one), k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS, default 16) and replayed until
     every stream has finished.  Draws come from a uniform table [4 * max_dec_inp_len, n] seeded with `seed` (like generate_streams), so ids
     are not NumPy-RNG-identical to generate_conditional_batch; they equal the host grammar driven by the same device draws.  A stream that
     reaches the max_dec_inp_len window is finished on the host by _resume_windowed, whose draws (NumPy, seeded with (seed, i)) do not come
-    from the device table.  If the one-launch step gives up, the batch is run again from the start on the chain of launches, with the same
-    table.  -> (results, seconds); a stream whose table runs out holds an EmoError.
+    from the device table (window = 'device' below finishes such streams on the device).  If the one-launch step gives up, the batch is run
+    again from the start on the chain of launches, with the same table.  -> (results, seconds); a stream whose table runs out holds an
+    EmoError.
 
     best_of = N > 1: every lead sheet runs as N streams of the same batch (stream i * N + c is candidate c of lead sheet i; each stream has its
     own column of the uniform table, so the draws differ), every finished candidate is scored (scoring.targets_of + score_tokens: mean negative
     log-probability over its Track_Full targets, on its first max_dec_inp_len tokens) and the candidate with the lowest one is returned; ties go
     to the lowest candidate index, a candidate that failed never wins.  -> (results, seconds, picks), picks[i] = {'chosen': c, 'nll_mean': [N
-    floats, NaN for a failed candidate], 'candidates': [N results]}.  best_of = 1 is the path above, draw for draw."""
+    floats, NaN for a failed candidate], 'candidates': [N results]}.  best_of = 1 is the path above, draw for draw.
+
+    window = 'device': the streams that reach the window are finished together on the device by a WindowedLoop (one batched full-window
+    forward and one emo_acc_window_step per draw, no host round trip per token) instead of one at a time by _resume_windowed.  Every id up to
+    a stream's handoff is the one window = 'host' gives; past it the draws come from the windowed phase's own uniform table (seeded with (seed,
+    WINDOW_TAG)), so the continuation equals the host grammar on those draws, not the NumPy draws of _resume_windowed."""
+    if window not in ('host', 'device'):
+        raise ValueError("window must be 'host' or 'device' (got %r)" % (window,))
     _refuse(model, inadmissibles)
     best_of = int(best_of)
     if best_of < 1:
@@ -1158,7 +1312,7 @@ def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, m
             print('[gen] %s -> the batch again on the chain of launches' % e)
             loop = AccompanimentLoop(model, event2idx, idx2event, lead_sheets, primers, persistent=False, redraw=False, **kw)
             loop.run(use_graph=use_graph)
-        out = loop.results(event2idx, idx2event, max_events, skip_check, seed)
+        out = loop.results(event2idx, idx2event, max_events, skip_check, seed, window=window)
         if best_of > 1:
             from . import scoring
             nll = scoring.candidate_scores(model, event2idx, out, loop.bound)
@@ -1213,9 +1367,13 @@ def main(argv=None):
     ap.add_argument('--seed', type=int, default=0, help='--device: seed of the uniform table (the group of streams j uses seed + j)')
     ap.add_argument('--best-of', dest='best_of', type=int, default=1,
                     help='--device: candidates generated per lead sheet; the one with the lowest mean negative log-probability is written')
+    ap.add_argument('--window', choices=['host', 'device'], default='host',
+                    help='--device: streams past the %d-token window are finished one at a time on the host, or together on the device' % max_dec_inp_len)
     args = ap.parse_args(argv)
     if args.best_of < 1 or (args.best_of > 1 and not args.device):
         ap.error('--best-of needs --device and a count of at least 1')
+    if args.window == 'device' and not args.device:
+        ap.error('--window device needs --device')
     conf = yaml.load(open(args.configuration), Loader=yaml.FullLoader)
     torch.cuda.set_device(conf['training']['gpuid'])
     event2idx, idx2event, pad = load_vocab(conf['data_loader']['vocab_path'].format(args.representation))
@@ -1243,12 +1401,12 @@ def main(argv=None):
         group = jobs[i:i + per_group]
         if args.device and args.best_of > 1:
             gen, _, picks = generate_accompaniments(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
-                                                    temp=temp, top_p=top_p, seed=args.seed + j, best_of=args.best_of)
+                                                    temp=temp, top_p=top_p, seed=args.seed + j, best_of=args.best_of, window=args.window)
             for g, p in zip(group, picks):
                 print('[info] %s: candidate %d of %s' % (g[0], p['chosen'], ['%.4f' % x for x in p['nll_mean']]))
         elif args.device:
             gen, _ = generate_accompaniments(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
-                                             temp=temp, top_p=top_p, seed=args.seed + j)
+                                             temp=temp, top_p=top_p, seed=args.seed + j, window=args.window)
         else:
             gen = generate_conditional_batch(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
                                              temp=temp, top_p=top_p, seeds=list(range(i, i + len(group))))

@@ -15,7 +15,7 @@ from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, BF16, F32, MUL_BI
 
 __all__ = ['gemm', 'colsum', 'embed_fwd', 'embed_bwd', 'layernorm_fwd', 'layernorm_bwd', 'dropout_apply', 'favor_attn_fwd',
            'favor_attn_bwd', 'favor_decode_step', 'performer_decode_step', 'performer_decode_step_sampled', 'favor_draw_omega', 'softmax_attn_fwd', 'softmax_attn_bwd', 'softmax_attn_decode', 'relpos_attn_fwd', 'relpos_attn_bwd', 'relpos_attn_decode', 'xent_fwd',
-           'xent_bwd', 'token_scores', 'xent_bwd_rows', 'argmax', 'sample_nucleus', 'sample_nucleus_step', 'txl_grammar_step', 'acc_grammar_step', 'accuracy_counts', 'sumsq', 'clip_coef', 'adam_step', 'cast', 'add_bias2',
+           'xent_bwd', 'token_scores', 'xent_bwd_rows', 'argmax', 'sample_nucleus', 'sample_nucleus_step', 'txl_grammar_step', 'acc_grammar_step', 'acc_window_step', 'accuracy_counts', 'sumsq', 'clip_coef', 'adam_step', 'cast', 'add_bias2',
            'ACT_NONE', 'ACT_RELU', 'ACT_GELU_NEW', 'ACT_GELU', 'MUL_NONE', 'MUL_NONZERO', 'MUL_DGELU_NEW', 'MUL_DGELU', 'MUL_BITMASK', 'gemm_bitmask_ok', 'gemm_lna_ok', 'bitmask_rows', 'favor_bwd_dn_ok', 'ffn_fwd', 'ffn_fwd_ok']
 
 
@@ -642,6 +642,34 @@ def acc_grammar_step(logits, temperature, top_p, u_steps, ev_flags, ev_beat, lea
                                    ptr(lead_off), ptr(params), ptr(state), ptr(seq), ptr(segs), seq.shape[1], max_len, track_full, pad, ptr(tok_out),
                                    ptr(seg_out), ptr(running), stream()))
     return tok_out
+
+
+def acc_window_step(logits, temperature, top_p, u_steps, rows, ev_flags, ev_beat, lead_tok, lead_off, params, state, seq, segs, window, track_full,
+                    win_tok, win_seg, running):
+    """One stage-2 draw-and-grammar step of m streams past the window (include/emo_hip.h emo_acc_window_step): logits fp32 [m, V], win_tok /
+    win_seg int64 [m, window]; rows int32 [m] (or None: row b is stream b) names each row's stream in u_steps fp32 [n_u, n], params / state
+    int32 [n, 8] and seq / segs int64 [n, width].  Allocation-free; state, seq, segs, win_tok, win_seg and running are updated in place."""
+    m, V = logits.shape
+    n = state.shape[0]
+    assert V <= 1024 and temperature > 0
+    assert logits.is_contiguous() and logits.dtype == torch.float32
+    assert u_steps.dtype == torch.float32 and u_steps.is_contiguous() and u_steps.dim() == 2 and u_steps.shape[1] == n
+    for t, dt in ((ev_flags, torch.int32), (ev_beat, torch.int32), (lead_off, torch.int32), (params, torch.int32), (state, torch.int32),
+                  (running, torch.int32), (lead_tok, torch.int64), (seq, torch.int64), (segs, torch.int64), (win_tok, torch.int64), (win_seg, torch.int64)):
+        assert t.dtype == dt and t.is_contiguous()
+    assert ev_flags.numel() >= V and ev_beat.numel() >= V and running.numel() >= 1
+    assert params.shape == (n, ACC_PARAM_WORDS) and state.shape == (n, ACC_STATE_WORDS)
+    assert seq.dim() == 2 and seq.shape[0] == n and segs.shape == seq.shape and seq.shape[1] >= window and lead_tok.numel() >= 1 and lead_off.numel() >= 1
+    assert win_tok.shape == (m, window) and win_seg.shape == (m, window)
+    if rows is None:
+        assert m <= n
+    else:
+        # (values in [0, n): checked by the caller on the host — WindowedLoop._set_rows; the kernel skips a row outside that range)
+        assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.numel() == m
+    check(lib.emo_acc_window_step(ptr(logits), m, V, temperature, top_p, ptr(u_steps), u_steps.shape[0], n, ptr(rows), ptr(ev_flags), ptr(ev_beat),
+                                  ptr(lead_tok), ptr(lead_off), ptr(params), ptr(state), ptr(seq), ptr(segs), seq.shape[1], window, track_full,
+                                  ptr(win_tok), ptr(win_seg), ptr(running), stream()))
+    return win_tok
 
 
 def accuracy_counts(logits, tgt, chord, melody, pad):

@@ -486,6 +486,23 @@ int emo_acc_grammar_step(const float* logits, int64_t n, int64_t V, float temper
                          const int64_t* lead_tok, const int32_t* lead_off, const int32_t* params, int32_t* state,
                          int64_t* seq, int64_t* segs, int64_t ld_seq, int64_t max_len, int64_t track_full,
                          int64_t pad, int64_t* tok_out, int64_t* seg_out, int32_t* running, emo_stream_t stream);
+/* The same draw and grammar for streams PAST the window (stage2_accompaniment/inference.py:252-277: the model input is the last max_dec_inp_len
+ * tokens of `generated`, positions restarting at 0 on every step, so nothing is fed token by token and an injected bar is simply part of the next
+ * input): one forward over [m, window] per draw, then this launch.  Row b of the batch (logits fp32 [m, V], win_tok / win_seg int64 [m, window])
+ * belongs to stream r = rows[b] (int32 [m]; NULL: r = b), which indexes params, state, seq, segs and the column of u_steps (fp32 [n_u, ld_u],
+ * ld_u = the number of streams; the uniform of draw d of stream r is u_steps[d * ld_u + r]), so a caller may drop finished rows from the batch
+ * without moving any state.  A row whose r is outside [0, ld_u) is skipped.
+ *   not RUNNING                 -> nothing is drawn, win_tok / win_seg[b] stay as they are;
+ *   state[LEN] < window         -> OVERFLOW (a caller error: there is no full window to read);
+ *   otherwise the draw, the in-launch redraws and the grammar of emo_acc_grammar_step (the same device code), state[CONSUMED] untouched; a
+ *   stream still RUNNING then gets its next model input, win_tok / win_seg[b, 0 .. window) = seq / segs[r, LEN - window .. LEN).
+ * OUT_OF_DRAWS, OVERFLOW (ld_seq too short for the accepted tokens) and *running behave as in emo_acc_grammar_step. */
+int emo_acc_window_step(const float* logits, int64_t m, int64_t V, float temperature, float top_p,
+                        const float* u_steps, int64_t n_u, int64_t ld_u, const int32_t* rows,
+                        const int32_t* ev_flags, const int32_t* ev_beat, const int64_t* lead_tok,
+                        const int32_t* lead_off, const int32_t* params, int32_t* state, int64_t* seq,
+                        int64_t* segs, int64_t ld_seq, int64_t window, int64_t track_full, int64_t* win_tok,
+                        int64_t* win_seg, int32_t* running, emo_stream_t stream);
 /* counts[0..5] += {nonpad, nonpad&correct, chord, chord&correct, melody, melody&correct} (train.py:184-193) */
 int emo_accuracy_counts(const float* logits, const int64_t* tgt, const int64_t* chord,
                         const int64_t* melody, int64_t M, int64_t V, int64_t pad, int64_t* counts,
