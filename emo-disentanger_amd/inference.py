@@ -19,12 +19,20 @@ import torch
 
 from . import engine, ops
 from ._lib import EmoError
+from .replay import StepReplayer, graph_steps
 
 max_dec_inp_len = 2048
 
 
 # ------------------------------------------------------------------------------------------------ sampling
-from .sampling import beat_position, nucleus, temperature  # noqa: E402,F401  (host path with the reference's NumPy semantics)
+from .sampling import beat_position, event_name, nucleus, temperature  # noqa: E402,F401  (host path with the reference's NumPy semantics)
+
+
+def uniform_table(rows, n, seed, device):
+    """fp32 [rows, n] uniforms of a device generator seeded with `seed`: the draws of the device loops (row = draw number, column = stream)."""
+    gen = torch.Generator(device=device)
+    gen.manual_seed(seed)
+    return torch.rand(rows, n, device=device, generator=gen)
 
 
 def sample_on_device(logits, temp, top_p, u=None, greedy=False):
@@ -47,15 +55,26 @@ class _EngineBase:
         self._tables = None
         self.dev_pos0, self.pos_auto = 0, True   # position = dev_pos0 + pos_dev[stream]; pos_auto: the engine advances pos_dev itself
 
+    def _inputs(self):
+        """-> (token table, segment table or None, positional table): the embedding tables are a snapshot, like the engine's omegas / folded weights."""
+        m = self.model
+        if self._tables is None:
+            self._tables = (engine.embedding_table(self.ps, 'token_emb.'), engine.embedding_table(self.ps, 'segemb.') if m.use_segment_emb else None)
+        return self._tables + (m.pe.pe if m.use_pe else m._zero_pe(self.max_len, m.d_model),)
+
     def _embed(self, tok, seg, pos0, dev_pos=False):
         m = self.model
-        if self._tables is None:                                  # snapshot, like the engine's omegas / folded weights
-            self._tables = (engine.embedding_table(self.ps, 'token_emb.'), engine.embedding_table(self.ps, 'segemb.') if m.use_segment_emb else None)
-        E, S = self._tables
+        E, S, pe = self._inputs()
         S = S if seg is not None else None
-        pe = m.pe.pe if m.use_pe else m._zero_pe(self.max_len, m.d_model)
         return ops.embed_fwd(tok, seg if S is not None else None, E, S, pe, self.dt, float(m.token_emb.emb_scale),
                              pos0=self.dev_pos0 if dev_pos else pos0, pos_ids=self.pos_dev if dev_pos else None).view(-1, m.d_model)
+
+    def _advance(self, dev_pos):
+        """One position further: the host count, or the device array unless the caller's own kernel advances it (pos_auto False)."""
+        if not dev_pos:
+            self.pos += 1
+        elif self.pos_auto:
+            self.pos_dev.add_(1)
 
     def _logits(self, h, out=None):
         return ops.gemm(h, self.ps.w('dec_out_proj.weight'), bias=self.ps.f32('dec_out_proj.bias'), out=out, out_dtype=torch.float32)
@@ -69,6 +88,100 @@ class _EngineBase:
         for i in range(tok.shape[1]):
             out = self.step(tok[:, i], seg[:, i])
         return out
+
+    # ------------------------------------------------------------------------------------------ one-launch step (what the two engines share)
+    # An engine with one supplies: step_entry (the C entry, for messages), _persist_layer(l, t_qkv, t_one, t_ffn) -> the 12 weight tensors of
+    # layer l, _persist_state(l) -> its last four table columns, _check_position(pe), _launch(...) and _launch_sampled(...).
+    _TABLE_COLS = ('wqkv', 'bqkv', 'wo', 'bo', 'g1', 'be1', 'w1', 'b1', 'w2', 'b2', 'g2', 'be2')
+
+    @staticmethod
+    def _pack_fragments(W, tile_idx, kpw):
+        """bf16 nn.Linear weight [N, K] -> [members][4 waves][tiles per member][kpw][64 lanes x 8]: the MFMA B fragment (16 output columns x 32 k)
+        of column tile t and k step ks holds, in lane l, W[16 t + l % 16][32 ks + 8 (l // 16) .. + 8]; wave w of the compute half that owns the
+        product holds the k steps [w kpw, (w + 1) kpw) of all of the member's tiles (emo_hip.h: emo_performer_decode_step)."""
+        N, K = W.shape
+        assert N % 16 == 0 and K == 32 * 4 * kpw
+        frags = W.reshape(N // 16, 16, K // 32, 4, 8).permute(0, 2, 3, 1, 4).reshape(N // 16, K // 32, 512)      # [tile][k step][lane * 8 + j]
+        sel = frags[tile_idx]                                                                                  # [members, tiles per member, k steps, 512]
+        members, tpm = tile_idx.shape
+        return sel.reshape(members, tpm, 4, kpw, 512).permute(0, 2, 1, 3, 4).contiguous()
+
+    def _prepare_persist(self):
+        m, ps, dev = self.model, self.ps, self.dev
+        mem = torch.arange(32, device=dev)
+        t_qkv = torch.stack([mem, 32 + mem, 64 + mem], 1)            # member (h, j) = 4 h + j: rows 64 h + 16 j .. of q, of k (+ 512), of v (+ 1024)
+        t_one = mem.view(32, 1)                                      # member m: output columns 16 m ..
+        t_ffn = (4 * mem).view(32, 1) + torch.arange(4, device=dev).view(1, 4)
+        self.persist = {'w': [self._persist_layer(l, t_qkv, t_one, t_ffn) for l in range(m.n_layer)], 'table': None}
+        V = m.n_token
+        Vp = (V + 15) // 16 * 16
+        wout = torch.zeros(Vp, m.d_model, device=dev, dtype=torch.bfloat16)
+        wout[:V] = ps.w('dec_out_proj.weight')
+        self.persist['wout'] = self._pack_fragments(wout, torch.arange(Vp // 16, device=dev).view(-1, 1), 4)
+        self.persist['bout'] = ps.f32('dec_out_proj.bias')
+        self.persist['sync'] = torch.zeros(ops.lib.emo_performer_decode_step_workspace_bytes() // 8, device=dev, dtype=torch.int64)   # zeroed ONCE
+        self.persist['logits'] = torch.zeros(self.n_pad, V, device=dev, dtype=torch.float32)
+        if self.n_pad != self.n:                                     # padded inputs of the idle streams: token 0, segment 0, position 0
+            self.persist['tok'] = torch.zeros(self.n_pad, dtype=torch.int64, device=dev)
+            self.persist['seg'] = torch.zeros(self.n_pad, dtype=torch.int64, device=dev)
+            self.persist['pos'] = torch.zeros(self.n_pad, dtype=torch.int64, device=dev)
+
+    def _persist_table(self):
+        """[L][16] device pointers (emo_hip.h); built at the first step after the state tensors exist (prefill voids it)."""
+        pp = self.persist
+        if pp['table'] is None:
+            rows = [[w[c].data_ptr() for c in self._TABLE_COLS] + self._persist_state(l) for l, w in enumerate(pp['w'])]
+            pp['table'] = torch.tensor(rows, dtype=torch.int64, device=self.dev)
+        return pp['table']
+
+    def _step_persistent(self, tok, seg, dev_pos, logits_out):
+        """Returns `logits_out` when given, else the engine's STATIC logits buffer (or a view of its first n rows): the next step overwrites it —
+        callers that keep logits across steps clone them (the chain of launches returns a fresh tensor; hipGraph capture needs the static one)."""
+        pp = self.persist
+        E, Sg, pe = self._inputs()
+        seg = seg if (Sg is not None and seg is not None) else None
+        if not dev_pos:
+            self._check_position(pe)                                 # (ops.embed_fwd makes the same check on the launch-chain path)
+        pos_ids = self.pos_dev if dev_pos else None
+        padded = self.n_pad != self.n
+        if padded:
+            pp['tok'][:self.n].copy_(tok)
+            tok = pp['tok']
+            if seg is not None:
+                pp['seg'][:self.n].copy_(seg)
+                seg = pp['seg']
+            if pos_ids is not None:
+                pp['pos'][:self.n].copy_(pos_ids)
+                pos_ids = pp['pos']
+        out = logits_out if (logits_out is not None and not padded) else pp['logits']
+        self._launch(tok, seg, E, Sg if seg is not None else None, pe, self.dev_pos0 if dev_pos else self.pos, pos_ids, out)
+        if padded:
+            if logits_out is not None:
+                logits_out.copy_(out[:self.n])
+                return logits_out
+            return out[:self.n]
+        return out
+
+    def step_sampled(self, seg_padded, temp, top_p, U, step_ctr, seq, col0, tok_out, pos0):
+        """One token step with the nucleus draw INSIDE the launch (emo_*_decode_step_sampled): draws from the logits the previous step (or the
+        prefill: see load_logits) left in the engine's buffer, writes token / sequence / step counter like emo_sample_nucleus_step, then runs
+        the step on the drawn tokens.  seg_padded: int64 [n_pad] (or None)."""
+        E, Sg, pe = self._inputs()
+        seg = seg_padded if Sg is not None else None
+        self._launch_sampled(seg, E, Sg if seg is not None else None, pe, pos0, temp, top_p, U, step_ctr, seq, col0, tok_out)
+        return self.persist['logits'][:self.n]
+
+    def load_logits(self, logits):
+        """Put externally produced logits (the prefill's) where step_sampled draws from."""
+        self.persist['logits'][:self.n].copy_(logits)
+
+    def check_persistent(self):
+        """Raises if a one-launch step gave up (synchronises; call it where the caller reads results anyway)."""
+        if self.persist is not None:
+            code = int(self.persist['sync'][-8].item())
+            if code != 0:
+                raise EmoError('%s gave up (code 0x%x): a workgroup of the persistent launch did not get a compute unit next to the others within '
+                               '50 ms (is another process using the GPU?); set EMO_DECODE_PERSISTENT=0 for the chain of launches' % (self.step_entry, code))
 
 
 class PerformerDecodeEngine(_EngineBase):
@@ -105,123 +218,39 @@ class PerformerDecodeEngine(_EngineBase):
             self._prepare_persist()
 
     # ------------------------------------------------------------------------------------------ one-launch step
-    @staticmethod
-    def _pack_fragments(W, tile_idx, kpw):
-        """bf16 nn.Linear weight [N, K] -> [members][4 waves][tiles per member][kpw][64 lanes x 8]: the MFMA B fragment (16 output columns x 32 k)
-        of column tile t and k step ks holds, in lane l, W[16 t + l % 16][32 ks + 8 (l // 16) .. + 8]; wave w of the compute half that owns the
-        product holds the k steps [w kpw, (w + 1) kpw) of all of the member's tiles (emo_hip.h: emo_performer_decode_step)."""
-        N, K = W.shape
-        assert N % 16 == 0 and K == 32 * 4 * kpw
-        frags = W.reshape(N // 16, 16, K // 32, 4, 8).permute(0, 2, 3, 1, 4).reshape(N // 16, K // 32, 512)      # [tile][k step][lane * 8 + j]
-        sel = frags[tile_idx]                                                                                  # [members, tiles per member, k steps, 512]
-        members, tpm = tile_idx.shape
-        return sel.reshape(members, tpm, 4, kpw, 512).permute(0, 2, 1, 3, 4).contiguous()
+    step_entry = 'emo_performer_decode_step'
 
-    def _prepare_persist(self):
-        m, ps, dev = self.model, self.ps, self.dev
-        D, L = m.d_model, m.n_layer
-        mem = torch.arange(32, device=dev)
-        t_qkv = torch.stack([mem, 32 + mem, 64 + mem], 1)            # member (h, j) = 4 h + j: rows 64 h + 16 j .. of q, of k (+ 512), of v (+ 1024)
-        t_one = mem.view(32, 1)                                      # member m: output columns 16 m ..
-        t_ffn = (4 * mem).view(32, 1) + torch.arange(4, device=dev).view(1, 4)
-        pk = self._pack_fragments
-        self.persist = {'w': [], 'table': None}
-        for l in range(L):
-            pfx = m._layer_prefix(l)
-            q = pfx + 'attention.query_projection.'
-            self.persist['w'].append(dict(
-                wqkv=pk(ps.w(q + 'weight', 3 * D), t_qkv, 4), bqkv=ps.f32(q + 'bias', 3 * D),
-                wo=pk(ps.w(pfx + 'attention.out_projection.weight'), t_one, 4), bo=ps.f32(pfx + 'attention.out_projection.bias'),
-                g1=ps.f32(pfx + 'norm1.weight'), be1=ps.f32(pfx + 'norm1.bias'),
-                w1=pk(ps.w(pfx + 'linear1.weight'), t_ffn, 4), b1=ps.f32(pfx + 'linear1.bias'),
-                w2=pk(ps.w(pfx + 'linear2.weight'), t_one, 16), b2=ps.f32(pfx + 'linear2.bias'),
-                g2=ps.f32(pfx + 'norm2.weight'), be2=ps.f32(pfx + 'norm2.bias')))
-        V = m.n_token
-        Vp = (V + 15) // 16 * 16
-        wout = torch.zeros(Vp, D, device=dev, dtype=torch.bfloat16)
-        wout[:V] = ps.w('dec_out_proj.weight')
-        self.persist['wout'] = pk(wout, torch.arange(Vp // 16, device=dev).view(-1, 1), 4)
-        self.persist['bout'] = ps.f32('dec_out_proj.bias')
-        self.persist['sync'] = torch.zeros(ops.lib.emo_performer_decode_step_workspace_bytes() // 8, device=dev, dtype=torch.int64)   # zeroed ONCE
-        self.persist['logits'] = torch.zeros(self.n_pad, V, device=dev, dtype=torch.float32)
-        if self.n_pad != self.n:                                     # padded inputs of the idle streams: token 0, segment 0, position 0
-            self.persist['tok'] = torch.zeros(self.n_pad, dtype=torch.int64, device=dev)
-            self.persist['seg'] = torch.zeros(self.n_pad, dtype=torch.int64, device=dev)
-            self.persist['pos'] = torch.zeros(self.n_pad, dtype=torch.int64, device=dev)
+    def _persist_layer(self, l, t_qkv, t_one, t_ffn):
+        m, ps, pk = self.model, self.ps, self._pack_fragments
+        D = m.d_model
+        pfx = m._layer_prefix(l)
+        q = pfx + 'attention.query_projection.'
+        return dict(wqkv=pk(ps.w(q + 'weight', 3 * D), t_qkv, 4), bqkv=ps.f32(q + 'bias', 3 * D),
+                    wo=pk(ps.w(pfx + 'attention.out_projection.weight'), t_one, 4), bo=ps.f32(pfx + 'attention.out_projection.bias'),
+                    g1=ps.f32(pfx + 'norm1.weight'), be1=ps.f32(pfx + 'norm1.bias'),
+                    w1=pk(ps.w(pfx + 'linear1.weight'), t_ffn, 4), b1=ps.f32(pfx + 'linear1.bias'),
+                    w2=pk(ps.w(pfx + 'linear2.weight'), t_one, 16), b2=ps.f32(pfx + 'linear2.bias'),
+                    g2=ps.f32(pfx + 'norm2.weight'), be2=ps.f32(pfx + 'norm2.bias'))
 
-    def _persist_table(self):
-        """[L][16] device pointers (emo_hip.h); built once the recurrent state exists (prefill)."""
-        pp = self.persist
-        if pp['table'] is None:
-            rows = []
-            for l, w in enumerate(pp['w']):
-                assert self.S[l].is_contiguous() and self.z[l].is_contiguous() and self.omegas[l].is_contiguous()
-                rows.append([w['wqkv'].data_ptr(), w['bqkv'].data_ptr(), w['wo'].data_ptr(), w['bo'].data_ptr(), w['g1'].data_ptr(), w['be1'].data_ptr(),
-                             w['w1'].data_ptr(), w['b1'].data_ptr(), w['w2'].data_ptr(), w['b2'].data_ptr(), w['g2'].data_ptr(), w['be2'].data_ptr(),
-                             self.omegas[l].data_ptr(), self.S[l].data_ptr(), self.z[l].data_ptr(), 0])
-            pp['table'] = torch.tensor(rows, dtype=torch.int64, device=self.dev)
-        return pp['table']
+    def _persist_state(self, l):
+        assert self.S[l].is_contiguous() and self.z[l].is_contiguous() and self.omegas[l].is_contiguous()
+        return [self.omegas[l].data_ptr(), self.S[l].data_ptr(), self.z[l].data_ptr(), 0]
 
-    def _step_persistent(self, tok, seg, dev_pos, logits_out):
-        """Returns `logits_out` when given, else the engine's STATIC logits buffer (or a view of its first n rows): the next step overwrites it —
-        callers that keep logits across steps clone them (the chain of launches returns a fresh tensor; hipGraph capture needs the static one)."""
-        m, pp = self.model, self.persist
-        if self._tables is None:
-            self._tables = (engine.embedding_table(self.ps, 'token_emb.'), engine.embedding_table(self.ps, 'segemb.') if m.use_segment_emb else None)
-        E, Sg = self._tables
-        seg = seg if (Sg is not None and seg is not None) else None
-        pe = m.pe.pe if m.use_pe else m._zero_pe(self.max_len, m.d_model)
-        if not dev_pos and self.pos >= pe.shape[0]:                  # (ops.embed_fwd makes the same check on the launch-chain path)
+    def _check_position(self, pe):
+        if self.pos >= pe.shape[0]:
             raise EmoError('decode position %d is past the positional-encoding table (%d rows)' % (self.pos, pe.shape[0]))
-        nf = 2 * self.omegas[0].shape[1]
-        pos_ids = self.pos_dev if dev_pos else None
-        padded = self.n_pad != self.n
-        if padded:
-            pp['tok'][:self.n].copy_(tok)
-            tok = pp['tok']
-            if seg is not None:
-                pp['seg'][:self.n].copy_(seg)
-                seg = pp['seg']
-            if pos_ids is not None:
-                pp['pos'][:self.n].copy_(pos_ids)
-                pos_ids = pp['pos']
-        out = logits_out if (logits_out is not None and not padded) else pp['logits']
-        ops.performer_decode_step(self._persist_table(), m.n_layer, tok, seg, E, Sg if seg is not None else None, pe, float(m.token_emb.emb_scale),
-                                  self.dev_pos0 if dev_pos else self.pos, pos_ids, pp['wout'], pp['bout'], m.n_token, out,
-                                  self.n_pad, m.d_model, m.n_head, nf, 2048, pp['sync'], diag=pp.get('diag'))
-        if padded:
-            if logits_out is not None:
-                logits_out.copy_(out[:self.n])
-                return logits_out
-            return out[:self.n]
-        return out
 
-    def step_sampled(self, seg_padded, temp, top_p, U, step_ctr, seq, col0, tok_out, pos0):
-        """One token step with the nucleus draw INSIDE the launch (emo_performer_decode_step_sampled): draws from the logits the previous step (or
-        the prefill: see load_logits) left in the engine's buffer, writes token / sequence / step counter like emo_sample_nucleus_step, then runs
-        the step on the drawn tokens.  seg_padded: int64 [n_pad] (or None)."""
+    def _launch(self, tok, seg, E, Sg, pe, pos0, pos_ids, out):
         m, pp = self.model, self.persist
-        if self._tables is None:
-            self._tables = (engine.embedding_table(self.ps, 'token_emb.'), engine.embedding_table(self.ps, 'segemb.') if m.use_segment_emb else None)
-        E, Sg = self._tables
-        seg = seg_padded if Sg is not None else None
-        pe = m.pe.pe if m.use_pe else m._zero_pe(self.max_len, m.d_model)
-        ops.performer_decode_step_sampled(self._persist_table(), m.n_layer, seg, E, Sg if seg is not None else None, pe, float(m.token_emb.emb_scale), pos0,
-                                          pp['wout'], pp['bout'], m.n_token, pp['logits'], self.n_pad, self.n, m.d_model, m.n_head,
-                                          2 * self.omegas[0].shape[1], 2048, pp['sync'], temp, top_p, U, step_ctr, seq, col0, tok_out)
-        return pp['logits'][:self.n]
+        ops.performer_decode_step(self._persist_table(), m.n_layer, tok, seg, E, Sg, pe, float(m.token_emb.emb_scale), pos0, pos_ids, pp['wout'],
+                                  pp['bout'], m.n_token, out, self.n_pad, m.d_model, m.n_head, 2 * self.omegas[0].shape[1], 2048, pp['sync'],
+                                  diag=pp.get('diag'))
 
-    def load_logits(self, logits):
-        """Put externally produced logits (the prefill's) where step_sampled draws from."""
-        self.persist['logits'][:self.n].copy_(logits)
-
-    def check_persistent(self):
-        """Raises if a one-launch step gave up (synchronises; call it where the caller reads results anyway)."""
-        if self.persist is not None:
-            code = int(self.persist['sync'][-8].item())
-            if code != 0:
-                raise EmoError('emo_performer_decode_step gave up (code 0x%x): a workgroup of the persistent launch did not get a compute unit next to the '
-                               'others within 50 ms (is another process using the GPU?); set EMO_DECODE_PERSISTENT=0 for the chain of launches' % code)
+    def _launch_sampled(self, seg, E, Sg, pe, pos0, temp, top_p, U, step_ctr, seq, col0, tok_out):
+        m, pp = self.model, self.persist
+        ops.performer_decode_step_sampled(self._persist_table(), m.n_layer, seg, E, Sg, pe, float(m.token_emb.emb_scale), pos0, pp['wout'], pp['bout'],
+                                          m.n_token, pp['logits'], self.n_pad, self.n, m.d_model, m.n_head, 2 * self.omegas[0].shape[1], 2048,
+                                          pp['sync'], temp, top_p, U, step_ctr, seq, col0, tok_out)
 
     def _prepare_folds(self):
         """gamma-scaled weights, c1[n] = sum_k gamma_k W[n,k] (of the ROUNDED bf16 product, the one the MFMA sees) and bias + W.beta for every
@@ -311,20 +340,12 @@ class PerformerDecodeEngine(_EngineBase):
         D, H = m.d_model, m.n_head
         if self.persist is not None:
             out = self._step_persistent(tok.reshape(-1), None if seg is None else seg.reshape(-1), dev_pos, logits_out)
-            if dev_pos:
-                if self.pos_auto:
-                    self.pos_dev.add_(1)
-            else:
-                self.pos += 1
+            self._advance(dev_pos)
             return out
         x = self._embed(tok.view(-1, 1), None if seg is None else seg.view(-1, 1), self.pos, dev_pos)
         if self.fold is not None:
             out = self._step_folded(x, logits_out)
-            if dev_pos:
-                if self.pos_auto:
-                    self.pos_dev.add_(1)
-            else:
-                self.pos += 1
+            self._advance(dev_pos)
             return out
         for l in range(m.n_layer):
             pfx = m._layer_prefix(l)
@@ -332,11 +353,7 @@ class PerformerDecodeEngine(_EngineBase):
             qkv = ops.gemm(x, ps.w(q + 'weight', 3 * D), bias=ps.f32(q + 'bias', 3 * D))
             attn = ops.favor_decode_step(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], self.omegas[l], self.S[l], self.z[l], H)
             x = self._tail(pfx, x, attn)
-        if dev_pos:
-            if self.pos_auto:
-                self.pos_dev.add_(1)
-        else:
-            self.pos += 1
+        self._advance(dev_pos)
         return self._logits(x, logits_out)
 
 
@@ -376,113 +393,46 @@ class GPT2DecodeEngine(_EngineBase):
             self._prepare_persist()
 
     # ------------------------------------------------------------------------------------------ one-launch step
+    step_entry = 'emo_gpt2_decode_step'
+
     def _prepare_persist(self):
-        m, ps, dev = self.model, self.ps, self.dev
-        L = m.n_layer
-        mem = torch.arange(32, device=dev)
-        t_qkv = torch.stack([mem, 32 + mem, 64 + mem], 1)            # member (h, j) = 4 h + j: columns 64 h + 16 j .. of q, of k (+ 512), of v (+ 1024)
-        t_one = mem.view(32, 1)
-        t_ffn = (4 * mem).view(32, 1) + torch.arange(4, device=dev).view(1, 4)
-        pk = PerformerDecodeEngine._pack_fragments
+        super()._prepare_persist()
+        ps, p0 = self.ps, self.model._layer_prefix(0)
+        self.persist['ln0'] = torch.cat([ps.f32(p0 + 'ln_1.weight'), ps.f32(p0 + 'ln_1.bias')]).contiguous()
+
+    def _persist_layer(self, l, t_qkv, t_one, t_ffn):
+        m, ps, pk = self.model, self.ps, self._pack_fragments
 
         def lin(name):                                               # Conv1D [in, out] -> nn.Linear layout [out, in]
             return ps.w(name).t().contiguous()
 
-        pf = [m._layer_prefix(l) for l in range(L)]
-        self.persist = {'w': [], 'table': None}
-        for l in range(L):
-            nx = pf[l + 1] if l + 1 < L else pf[0]                   # (the last block's slot is loaded and never applied: this GPT-2 has no ln_f)
-            self.persist['w'].append(dict(
-                wqkv=pk(lin(pf[l] + 'attn.c_attn.weight'), t_qkv, 4), bqkv=ps.f32(pf[l] + 'attn.c_attn.bias'),
-                wo=pk(lin(pf[l] + 'attn.c_proj.weight'), t_one, 4), bo=ps.f32(pf[l] + 'attn.c_proj.bias'),
-                g1=ps.f32(pf[l] + 'ln_2.weight'), be1=ps.f32(pf[l] + 'ln_2.bias'),
-                w1=pk(lin(pf[l] + 'mlp.c_fc.weight'), t_ffn, 4), b1=ps.f32(pf[l] + 'mlp.c_fc.bias'),
-                w2=pk(lin(pf[l] + 'mlp.c_proj.weight'), t_one, 16), b2=ps.f32(pf[l] + 'mlp.c_proj.bias'),
-                g2=ps.f32(nx + 'ln_1.weight'), be2=ps.f32(nx + 'ln_1.bias')))
-        self.persist['ln0'] = torch.cat([ps.f32(pf[0] + 'ln_1.weight'), ps.f32(pf[0] + 'ln_1.bias')]).contiguous()
-        V = m.n_token
-        Vp = (V + 15) // 16 * 16
-        wout = torch.zeros(Vp, m.d_model, device=dev, dtype=torch.bfloat16)
-        wout[:V] = ps.w('dec_out_proj.weight')
-        self.persist['wout'] = pk(wout, torch.arange(Vp // 16, device=dev).view(-1, 1), 4)
-        self.persist['bout'] = ps.f32('dec_out_proj.bias')
-        self.persist['sync'] = torch.zeros(ops.lib.emo_performer_decode_step_workspace_bytes() // 8, device=dev, dtype=torch.int64)   # zeroed ONCE
-        self.persist['logits'] = torch.zeros(self.n_pad, V, device=dev, dtype=torch.float32)
-        if self.n_pad != self.n:                                     # padded inputs of the idle streams: token 0, segment 0, position 0
-            self.persist['tok'] = torch.zeros(self.n_pad, dtype=torch.int64, device=dev)
-            self.persist['seg'] = torch.zeros(self.n_pad, dtype=torch.int64, device=dev)
-            self.persist['pos'] = torch.zeros(self.n_pad, dtype=torch.int64, device=dev)
+        pfx = m._layer_prefix(l)
+        nx = m._layer_prefix(l + 1 if l + 1 < m.n_layer else 0)      # (the last block's slot is loaded and never applied: this GPT-2 has no ln_f)
+        return dict(wqkv=pk(lin(pfx + 'attn.c_attn.weight'), t_qkv, 4), bqkv=ps.f32(pfx + 'attn.c_attn.bias'),
+                    wo=pk(lin(pfx + 'attn.c_proj.weight'), t_one, 4), bo=ps.f32(pfx + 'attn.c_proj.bias'),
+                    g1=ps.f32(pfx + 'ln_2.weight'), be1=ps.f32(pfx + 'ln_2.bias'),
+                    w1=pk(lin(pfx + 'mlp.c_fc.weight'), t_ffn, 4), b1=ps.f32(pfx + 'mlp.c_fc.bias'),
+                    w2=pk(lin(pfx + 'mlp.c_proj.weight'), t_one, 16), b2=ps.f32(pfx + 'mlp.c_proj.bias'),
+                    g2=ps.f32(nx + 'ln_1.weight'), be2=ps.f32(nx + 'ln_1.bias'))
 
-    def _persist_table(self):
-        """[L][16] device pointers (emo_hip.h: emo_gpt2_decode_step); the caches live as long as the engine."""
-        pp = self.persist
-        if pp['table'] is None:
-            rows = []
-            for l, w in enumerate(pp['w']):
-                rows.append([w['wqkv'].data_ptr(), w['bqkv'].data_ptr(), w['wo'].data_ptr(), w['bo'].data_ptr(), w['g1'].data_ptr(), w['be1'].data_ptr(),
-                             w['w1'].data_ptr(), w['b1'].data_ptr(), w['w2'].data_ptr(), w['b2'].data_ptr(), w['g2'].data_ptr(), w['be2'].data_ptr(),
-                             0, self.kc_all[l].data_ptr(), self.vc_all[l].data_ptr(), 0])
-            pp['table'] = torch.tensor(rows, dtype=torch.int64, device=self.dev)
-        return pp['table']
+    def _persist_state(self, l):
+        return [0, self.kc_all[l].data_ptr(), self.vc_all[l].data_ptr(), 0]       # (the caches live as long as the engine)
 
-    def _persist_inputs(self):
-        m = self.model
-        if self._tables is None:
-            self._tables = (engine.embedding_table(self.ps, 'token_emb.'), engine.embedding_table(self.ps, 'segemb.') if m.use_segment_emb else None)
-        E, Sg = self._tables
-        pe = m.pe.pe if m.use_pe else m._zero_pe(self.max_len, m.d_model)
-        return E, Sg, pe
+    def _check_position(self, pe):
+        rows = min(pe.shape[0], self.max_len)
+        if self.pos >= rows:
+            raise EmoError('decode position %d is past the positional-encoding table / the KV cache (%d rows)' % (self.pos, rows))
 
-    def _step_persistent(self, tok, seg, dev_pos, logits_out):
-        """Returns `logits_out` when given, else the engine's STATIC logits buffer (or a view of its first n rows), like the Performer engine's."""
+    def _launch(self, tok, seg, E, Sg, pe, pos0, pos_ids, out):
         m, pp = self.model, self.persist
-        E, Sg, pe = self._persist_inputs()
-        seg = seg if (Sg is not None and seg is not None) else None
-        if not dev_pos and self.pos >= min(pe.shape[0], self.max_len):
-            raise EmoError('decode position %d is past the positional-encoding table / the KV cache (%d rows)' % (self.pos, min(pe.shape[0], self.max_len)))
-        pos_ids = self.pos_dev if dev_pos else None
-        padded = self.n_pad != self.n
-        if padded:
-            pp['tok'][:self.n].copy_(tok)
-            tok = pp['tok']
-            if seg is not None:
-                pp['seg'][:self.n].copy_(seg)
-                seg = pp['seg']
-            if pos_ids is not None:
-                pp['pos'][:self.n].copy_(pos_ids)
-                pos_ids = pp['pos']
-        out = logits_out if (logits_out is not None and not padded) else pp['logits']
-        ops.gpt2_decode_step(self._persist_table(), m.n_layer, tok, seg, E, Sg if seg is not None else None, pe, float(m.token_emb.emb_scale),
-                             self.dev_pos0 if dev_pos else self.pos, pos_ids, pp['ln0'], self.max_len, pp['wout'], pp['bout'], m.n_token, out,
-                             self.n_pad, m.d_model, m.n_head, 2048, pp['sync'], diag=pp.get('diag'))
-        if padded:
-            if logits_out is not None:
-                logits_out.copy_(out[:self.n])
-                return logits_out
-            return out[:self.n]
-        return out
+        ops.gpt2_decode_step(self._persist_table(), m.n_layer, tok, seg, E, Sg, pe, float(m.token_emb.emb_scale), pos0, pos_ids, pp['ln0'], self.max_len,
+                             pp['wout'], pp['bout'], m.n_token, out, self.n_pad, m.d_model, m.n_head, 2048, pp['sync'], diag=pp.get('diag'))
 
-    def step_sampled(self, seg_padded, temp, top_p, U, step_ctr, seq, col0, tok_out, pos0):
-        """One token step with the nucleus draw INSIDE the launch (emo_gpt2_decode_step_sampled); see PerformerDecodeEngine.step_sampled."""
+    def _launch_sampled(self, seg, E, Sg, pe, pos0, temp, top_p, U, step_ctr, seq, col0, tok_out):
         m, pp = self.model, self.persist
-        E, Sg, pe = self._persist_inputs()
-        seg = seg_padded if Sg is not None else None
-        ops.gpt2_decode_step_sampled(self._persist_table(), m.n_layer, seg, E, Sg if seg is not None else None, pe, float(m.token_emb.emb_scale), pos0,
-                                     pp['ln0'], self.max_len, pp['wout'], pp['bout'], m.n_token, pp['logits'], self.n_pad, self.n, m.d_model, m.n_head,
-                                     2048, pp['sync'], temp, top_p, U, step_ctr, seq, col0, tok_out)
-        return pp['logits'][:self.n]
-
-    def load_logits(self, logits):
-        """Put externally produced logits (the prefill's) where step_sampled draws from."""
-        self.persist['logits'][:self.n].copy_(logits)
-
-    def check_persistent(self):
-        """Raises if a one-launch step gave up (synchronises; call it where the caller reads results anyway)."""
-        if self.persist is not None:
-            code = int(self.persist['sync'][-8].item())
-            if code != 0:
-                raise EmoError('emo_gpt2_decode_step gave up (code 0x%x): a workgroup of the persistent launch did not get a compute unit next to the '
-                               'others within 50 ms (is another process using the GPU?); set EMO_DECODE_PERSISTENT=0 for the chain of launches' % code)
+        ops.gpt2_decode_step_sampled(self._persist_table(), m.n_layer, seg, E, Sg, pe, float(m.token_emb.emb_scale), pos0, pp['ln0'], self.max_len,
+                                     pp['wout'], pp['bout'], m.n_token, pp['logits'], self.n_pad, self.n, m.d_model, m.n_head, 2048, pp['sync'],
+                                     temp, top_p, U, step_ctr, seq, col0, tok_out)
 
     def _prepare_folds(self):
         m, ps = self.model, self.ps
@@ -555,11 +505,7 @@ class GPT2DecodeEngine(_EngineBase):
         if self.persist is not None:
             out = self._step_persistent(tok.reshape(-1), None if seg is None else seg.reshape(-1), dev_pos, logits_out)
             self.lens.add_(1)
-            if dev_pos:
-                if self.pos_auto:
-                    self.pos_dev.add_(1)
-            else:
-                self.pos += 1
+            self._advance(dev_pos)
             return out
         x = self._embed(tok.view(-1, 1), None if seg is None else seg.view(-1, 1), self.pos, dev_pos)
         if self.fold is not None:
@@ -567,10 +513,7 @@ class GPT2DecodeEngine(_EngineBase):
                 return self._step_folded(x, self.pos_dev, self.dev_pos0 + 1, logits_out)
             self.lens.add_(1)
             out = self._step_folded(x, self.lens, 0, logits_out)
-            if dev_pos:
-                self.pos_dev.add_(1)
-            else:
-                self.pos += 1
+            self._advance(dev_pos)
             return out
         self.lens.add_(1)
         ext = dev_pos and not self.pos_auto                       # positions AND key counts come from the sampler's step counter (as in the folded path)
@@ -582,10 +525,7 @@ class GPT2DecodeEngine(_EngineBase):
             a = ops.softmax_attn_decode(qkv[:, :D], self.kc[l], self.vc[l], self.pos_dev if ext else self.lens, H, lens_off=self.dev_pos0 + 1 if ext else 0,
                                         k_new=qkv[:, D:2 * D], v_new=qkv[:, 2 * D:])
             x = self._block_tail(pfx, x, a)
-        if dev_pos:
-            self.pos_dev.add_(1)
-        else:
-            self.pos += 1
+        self._advance(dev_pos)
         return self._logits(x, logits_out)
 
 
@@ -791,124 +731,62 @@ def _resume_windowed(model, event2idx, idx2event, s, max_events, skip_check, tem
     return s.result()
 
 
-class _Chain:
-    """One lock-step group of streams: engine + device-side loop state + (optionally) the captured step graph on its own HIP stream."""
-
-    def __init__(self, model, ptok, pseg, n_new, U, temp, top_p, greedy, seg_value, redraw, persistent=True):
-        self.n, self.T0 = ptok.shape
-        n, T0, dev = self.n, self.T0, ptok.device
-        self.eng = make_engine(model, n, redraw=redraw, persistent=persistent) if model.kind == 'performer' else make_engine(model, n, persistent=persistent)
-        eng = self.eng
-        self.out = torch.empty(n, T0 + n_new, dtype=torch.long, device=dev)
-        self.out[:, :T0] = ptok
-        out = self.out
-        seg_col = torch.full((n,), seg_value, dtype=torch.long, device=dev)
-        logits_buf = eng.prefill(ptok, pseg).clone()
-        if not greedy:
-            # all loop state on the device inside OUR kernels: the sampler reads u[step[r], r], writes the token into out[r, T0 + step[r]] and
-            # advances step[r]; the embedding takes position (T0 - 1) + step[r]; the logits GEMM writes straight into logits_buf
-            # (5 fewer launches per token than the torch index_select / scatter_ / add_ / copy_ version below).
-            step_ctr = torch.zeros(n, dtype=torch.long, device=dev)
-            eng.pos_dev, eng.dev_pos0, eng.pos_auto = step_ctr, T0 - 1, False
-            nxt_buf = torch.empty(n, dtype=torch.long, device=dev)
-
-            if getattr(eng, 'persist', None) is not None and os.environ.get('EMO_PD_SAMPLER', '1') != '0':
-                # one launch per token: the draw runs inside the persistent step (the same device code as emo_sample_nucleus_step)
-                eng.load_logits(logits_buf)
-                seg_p = torch.zeros(eng.n_pad, dtype=torch.long, device=dev)
-                seg_p[:n] = seg_col
-                Uc = U.contiguous()
-
-                def one_step():
-                    eng.step_sampled(seg_p, temp, top_p, Uc, step_ctr, out, T0, nxt_buf, T0 - 1)
-            else:
-                def one_step():
-                    ops.sample_nucleus_step(logits_buf, temp, top_p, U, step_ctr, seq=out, col0=T0, out=nxt_buf)
-                    eng.step(nxt_buf, seg_col, dev_pos=True, logits_out=logits_buf)
-        else:
-            step_idx = torch.zeros(1, dtype=torch.long, device=dev)
-
-            def one_step():
-                u = U.index_select(0, step_idx).view(n)
-                nxt = sample_on_device(logits_buf, temp, top_p, u, greedy)
-                out.scatter_(1, (step_idx + T0).expand(n, 1), nxt.view(n, 1))
-                logits_buf.copy_(eng.step(nxt, seg_col, dev_pos=True))
-                step_idx.add_(1)
-        self.one_step = one_step
-        self.graph, self.stream = None, None
-
-    def capture(self, steps=1):
-        """One graph of `steps` consecutive token steps (all loop state lives on the device, so a replay continues wherever the streams are):
-        a replay costs the device a fixed ~10 us of idle time whatever it holds, so several token steps per replay amortise it (r04:
-        EMO_GEN_GRAPH_STEPS, default 16; the single-step graph serves the remainder)."""
-        dev = self.out.device
-        if self.stream is None:
-            self.stream = torch.cuda.Stream(device=dev)
-        g = torch.cuda.CUDAGraph()
-        self.stream.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(self.stream):
-            with torch.cuda.graph(g, stream=self.stream):
-                for _ in range(steps):
-                    self.one_step()
-        return g
-
-
 @torch.no_grad()
 def generate_streams(model, prompt_tok, prompt_seg, n_new, temp=1.1, top_p=0.9, greedy=False, seed=0, seg_value=1, use_graph=True, chains=None):
     """BASELINE configs[3]: n parallel streams in lock-step (grammar checks off => fixed token count).  Everything stays
-    on the GPU: recurrent/KV state, positions, sampling, token buffer.  One decode step is ~64 small DEPENDENT launches, so the
-    step (sample -> append -> embed -> 12 layers -> logits) is captured ONCE in a hipGraph and replayed per token.  `chains` > 1 splits the
-    streams into independent groups whose graphs replay on separate HIP streams (same tokens as one group: every stream keeps its own
-    uniform draws); measured r01: SLOWER (0.52 / 0.89 / 0.60 / 1.11 ms per step for 1 / 2 / 4 / 8 chains) — the replays are issued by one
-    host thread and do not overlap — so the default is one chain.
+    on the GPU: recurrent/KV state, positions, sampling, token buffer.  One decode step is ~64 small DEPENDENT launches (one where the engine
+    has the one-launch step), so the step (sample -> append -> embed -> 12 layers -> logits) is captured ONCE in a hipGraph and replayed per
+    token (replay.StepReplayer with a fixed step count: every replay is enqueued without reading anything back).  `chains`: None or 1; the
+    mode that split the streams over several graphs on several HIP streams is gone (slower at every split).
     Returns int64 [n, T0 + n_new]."""
+    if chains not in (None, 1):
+        raise ValueError('generate_streams: chains=%r: the multi-chain mode (streams split over several graphs / HIP streams) was removed' % (chains,))
     n, T0 = prompt_tok.shape
     dev = prompt_tok.device
-    gen = torch.Generator(device=dev)
-    gen.manual_seed(seed)
-    U = torch.rand(max(n_new, 1), n, device=dev, generator=gen)
-    if chains is None:
-        chains = int(os.environ.get('EMO_GEN_CHAINS', 1))
-    if not use_graph or n_new <= 2 or chains < 1 or n % chains != 0 or n // chains < 1:
-        chains = 1
-    m = n // chains
-    cs = []
-    for c in range(chains):
-        rows = slice(c * m, (c + 1) * m)
-        cs.append(_Chain(model, prompt_tok[rows].contiguous(), prompt_seg[rows].contiguous(), n_new, U[:, rows].contiguous(), temp, top_p, greedy,
-                         seg_value, redraw=(c == 0), persistent=(chains == 1)))      # (two persistent launches on two streams can each be
-                                                                                      # partially resident and starve each other: one chain only)
-    if n_new > 0:
-        for ch in cs:
-            ch.one_step()                        # eager first step (also warms every kernel / attribute cache)
-        if not use_graph:
-            for _ in range(n_new - 1):
-                cs[0].one_step()
-        elif n_new > 1:
-            torch.cuda.synchronize()
-            left = n_new - 1
-            k = max(1, int(os.environ.get('EMO_GEN_GRAPH_STEPS', 16)))
-            for ch in cs:
-                ch.graph = ch.capture(1)
-                ch.graph_k = ch.capture(k) if (k > 1 and left >= 2 * k) else None
-            main = torch.cuda.current_stream()
-            t_host = time.perf_counter()
-            while left > 0:
-                many = cs[0].graph_k is not None and left >= k
-                for ch in cs:
-                    with torch.cuda.stream(ch.stream):
-                        (ch.graph_k if many else ch.graph).replay()
-                left -= k if many else 1
-            if os.environ.get('EMO_GEN_TIMING'):            # diagnostics: host time to ENQUEUE the replays vs time until the GPU is done
-                t_enq = time.perf_counter() - t_host
-                torch.cuda.synchronize()
-                print('[gen timing] enqueue %.3f ms/step, total %.3f ms/step' % (1e3 * t_enq / (n_new - 1), 1e3 * (time.perf_counter() - t_host) / (n_new - 1)))
-            for ch in cs:
-                main.wait_stream(ch.stream)
-    for ch in cs:
-        if getattr(ch.eng, 'persist', None) is not None:
-            ch.eng.check_persistent()
-    return cs[0].out if chains == 1 else torch.cat([ch.out for ch in cs], 0)
+    U = uniform_table(max(n_new, 1), n, seed, dev)
+    eng = make_engine(model, n)
+    out = torch.empty(n, T0 + n_new, dtype=torch.long, device=dev)
+    out[:, :T0] = prompt_tok
+    seg_col = torch.full((n,), seg_value, dtype=torch.long, device=dev)
+    logits_buf = eng.prefill(prompt_tok.contiguous(), prompt_seg.contiguous()).clone()
+    if not greedy:
+        # all loop state on the device inside OUR kernels: the sampler reads u[step[r], r], writes the token into out[r, T0 + step[r]] and
+        # advances step[r]; the embedding takes position (T0 - 1) + step[r]; the logits GEMM writes straight into logits_buf
+        # (5 fewer launches per token than the torch index_select / scatter_ / add_ / copy_ version below).
+        step_ctr = torch.zeros(n, dtype=torch.long, device=dev)
+        eng.pos_dev, eng.dev_pos0, eng.pos_auto = step_ctr, T0 - 1, False
+        nxt_buf = torch.empty(n, dtype=torch.long, device=dev)
+
+        if eng.persist is not None and os.environ.get('EMO_PD_SAMPLER', '1') != '0':
+            # one launch per token: the draw runs inside the persistent step (the same device code as emo_sample_nucleus_step)
+            eng.load_logits(logits_buf)
+            seg_p = torch.zeros(eng.n_pad, dtype=torch.long, device=dev)
+            seg_p[:n] = seg_col
+
+            def one_step():
+                eng.step_sampled(seg_p, temp, top_p, U, step_ctr, out, T0, nxt_buf, T0 - 1)
+        else:
+            def one_step():
+                ops.sample_nucleus_step(logits_buf, temp, top_p, U, step_ctr, seq=out, col0=T0, out=nxt_buf)
+                eng.step(nxt_buf, seg_col, dev_pos=True, logits_out=logits_buf)
+    else:
+        step_idx = torch.zeros(1, dtype=torch.long, device=dev)
+
+        def one_step():
+            u = U.index_select(0, step_idx).view(n)
+            nxt = sample_on_device(logits_buf, temp, top_p, u, greedy)
+            out.scatter_(1, (step_idx + T0).expand(n, 1), nxt.view(n, 1))
+            logits_buf.copy_(eng.step(nxt, seg_col, dev_pos=True))
+            step_idx.add_(1)
+    rp = StepReplayer(one_step, dev)
+    rp.run(0, n_new, use_graph=use_graph)
+    if os.environ.get('EMO_GEN_TIMING') and rp.replayed[0]:      # diagnostics: host time to ENQUEUE the replays vs time until the GPU is done
+        steps, t_enq = rp.replayed
+        t1 = time.perf_counter()
+        torch.cuda.synchronize()
+        print('[gen timing] enqueue %.3f ms/step, total %.3f ms/step' % (1e3 * t_enq / steps, 1e3 * (t_enq + time.perf_counter() - t1) / steps))
+    eng.check_persistent()
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ device loop (stage 2, grammar on)
@@ -924,7 +802,7 @@ def acc_event_tables(idx2event, V):
     beat_position, e == 'Track_LeadSheet', e == 'PAD_None', e == 'EOS_None').  Ids without an event get no bits."""
     flags, beat = np.zeros(V, np.int32), np.zeros(V, np.int32)
     for i in range(V):
-        e = idx2event.get(i) if isinstance(idx2event, dict) else (idx2event[i] if i < len(idx2event) else None)
+        e = event_name(idx2event, i)
         if e is None:
             continue
         f = 0
@@ -967,6 +845,16 @@ class _GaveUp(Exception):
     """The one-launch decode step gave up (emo_*_decode_step: its workgroups were not all resident in time)."""
 
 
+def _stream_result(status, ids, out_of_draws, overflow, still_running):
+    """Status word and ids so far of a stream that is not at the window -> what _Stream.result() gives (DONE: generated[:-1], STUCK:
+    generated), or an EmoError with the caller's text for an exhausted uniform table, a row / table limit, or a stream still running."""
+    if status == ACC_DONE:
+        return ids[:-1]
+    if status == ACC_STUCK:
+        return ids
+    return EmoError('generate_accompaniments: ' + (out_of_draws if status == ACC_OUT_OF_DRAWS else overflow if status == ACC_OVERFLOW else still_running))
+
+
 class AccompanimentLoop:
     """Device state of generate_accompaniments: the decode engine (prefilled with the common prefix, positions on the device), the logits of
     the last step, the uniform table, the grammar tables, the packed lead sheets, per-stream parameters / state and token / segment rows, and
@@ -1003,9 +891,7 @@ class AccompanimentLoop:
         self.len0 = np.array(lens)
         self.seq, self.segs, self.params, self.state = (torch.from_numpy(a).to(dev) for a in (seq, segs, params, state))
         self.running = torch.tensor([int((state[:, ACC_S_STATUS] == ACC_RUNNING).sum())], dtype=torch.int32, device=dev)
-        gen = torch.Generator(device=dev)
-        gen.manual_seed(seed)
-        self.U = torch.rand(int(n_u or 4 * self.W), n, device=dev, generator=gen)
+        self.U = uniform_table(int(n_u or 4 * self.W), n, seed, dev)
         self.tok = torch.zeros(n, dtype=torch.int64, device=dev)
         self.segv = torch.ones(n, dtype=torch.int64, device=dev)
         self.logits = torch.empty(n, V, dtype=torch.float32, device=dev)
@@ -1022,7 +908,6 @@ class AccompanimentLoop:
         pe = model.pe.pe.shape[0] if model.use_pe else self.W
         self.bound = min(self.W, pe)           # the engine never runs a step at a position >= bound (the one-launch GPT-2 step would clamp it)
         self.pos = self.L0                     # host count of the engine position (every row advances one per step)
-        self.graph = self.graph_k = self.stream = None
         self.replayed = (0, 0.0)
 
     def grammar(self):
@@ -1032,17 +917,6 @@ class AccompanimentLoop:
     def one_step(self):
         self.grammar()
         self.eng.step(self.tok, self.segv, dev_pos=True, logits_out=self.logits)
-
-    def capture(self, steps):
-        if self.stream is None:
-            self.stream = torch.cuda.Stream(device=self.dev)
-        g = torch.cuda.CUDAGraph()
-        self.stream.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(self.stream):
-            with torch.cuda.graph(g, stream=self.stream):
-                for _ in range(steps):
-                    self.one_step()
-        return g
 
     def _live(self):
         """Running count (synchronises); raises _GaveUp when the one-launch step gave up."""
@@ -1057,29 +931,12 @@ class AccompanimentLoop:
         """Steps until every stream has left RUNNING; the running count is read once per replay (per step without graphs).  A k-step replay
         runs only while it keeps the position below `bound`; at the bound one more grammar step runs alone (a stream still running there
         reaches the window in it)."""
-        k = max(1, int(steps_per_graph or os.environ.get('EMO_GEN_GRAPH_STEPS', 16)))
+        # (the replayer holds graph / graph_k / stream of this run and goes with it: kept on the loop it would close a reference cycle through
+        # one_step, and graphs freed by the cycle collector can be freed in the middle of a later capture)
+        rp = StepReplayer(self.one_step, self.dev, steps_per_graph)
         with torch.no_grad():
-            if self._live() > 0 and self.pos < self.bound:
-                self.one_step()                  # eager first step (also warms every kernel / workspace cache before any capture)
-                self.pos += 1
-            if use_graph and self._live() > 0 and self.pos < self.bound:
-                torch.cuda.synchronize()
-                self.graph = self.capture(1)
-                self.graph_k = self.capture(k) if k > 1 and self.bound - self.pos >= 2 * k else None
-                main = torch.cuda.current_stream()
-                t0, p0 = time.perf_counter(), self.pos
-                try:
-                    with torch.cuda.stream(self.stream):
-                        while self._live() > 0 and self.pos < self.bound:
-                            many = self.graph_k is not None and self.bound - self.pos >= k
-                            (self.graph_k if many else self.graph).replay()
-                            self.pos += k if many else 1
-                finally:
-                    main.wait_stream(self.stream)
-                self.replayed = (self.pos - p0, time.perf_counter() - t0)     # (steps, seconds) of the replays (the last poll synchronised)
-            while self._live() > 0 and self.pos < self.bound:
-                self.one_step()
-                self.pos += 1
+            self.pos = rp.run(self.pos, self.bound, live=self._live, use_graph=use_graph)
+            self.replayed = rp.replayed      # (steps, seconds) of the replays (the last poll synchronised)
             if self._live() > 0:
                 self.grammar()
             torch.cuda.synchronize()
@@ -1120,24 +977,17 @@ class AccompanimentLoop:
         out = []
         for i, s in enumerate(self.streams):
             st, ln = int(state[i, ACC_S_STATUS]), int(state[i, ACC_S_LEN])
-            ids = [int(t) for t in seq[i, :ln]]
-            if st == ACC_DONE:
-                out.append(ids[:-1])
-            elif st == ACC_STUCK:
-                out.append(ids)
-            elif st == ACC_WINDOW and i in past:
+            if st == ACC_WINDOW and i in past:
                 out.append(past[i])
             elif st == ACC_WINDOW:
                 s = self.handed_off(i, state, seq, segs)
                 rs = np.random.RandomState([seed, i])
                 out.append(_resume_windowed(self.model, event2idx, idx2event, s, max_events, skip_check, self.temp, None,
                                             lambda probs, rs=rs: nucleus(probs, self.top_p, rng=rs)))
-            elif st == ACC_OUT_OF_DRAWS:
-                out.append(EmoError('generate_accompaniments: stream %d used all %d uniforms of its table' % (i, self.U.shape[0])))
-            elif st == ACC_OVERFLOW:
-                out.append(EmoError('generate_accompaniments: stream %d: token row or lead-sheet table too short' % i))
             else:
-                out.append(EmoError('generate_accompaniments: stream %d still running at position %d (positional table / cache end)' % (i, self.pos)))
+                out.append(_stream_result(st, [int(t) for t in seq[i, :ln]], 'stream %d used all %d uniforms of its table' % (i, self.U.shape[0]),
+                                          'stream %d: token row or lead-sheet table too short' % i,
+                                          'stream %d still running at position %d (positional table / cache end)' % (i, self.pos)))
         return out
 
 
@@ -1171,7 +1021,7 @@ class WindowedLoop:
         self.idx = [i for i in range(loop.n) if state[i, ACC_S_STATUS] == ACC_WINDOW]
         m0 = self.m0 = len(self.idx)
         assert m0 > 0, 'no stream reached the window'
-        self.k = max(1, int(steps_per_poll or os.environ.get('EMO_GEN_GRAPH_STEPS', 16)))
+        self.k = graph_steps(steps_per_poll)
         sel = torch.tensor(self.idx, dtype=torch.long, device=dev)
         len0 = state[self.idx, ACC_S_LEN].astype(np.int64)
         self.len0 = len0
@@ -1186,11 +1036,9 @@ class WindowedLoop:
         self.state[:, ACC_S_DRAWS] = 0
         self.accepted0 = int(self.state[:, ACC_S_ACCEPTED].sum().item())
         self.running = torch.tensor([m0], dtype=torch.int32, device=dev)
-        gen = torch.Generator(device=dev)
-        gen.manual_seed((int(seed) * 0x9E3779B1 + WINDOW_TAG) & 0x7FFFFFFFFFFFFFFF)
         # max_events draws can be accepted at most; every rejected run before an acceptance is shorter than 256 Beats plus the PAD / early-EOS
         # draws, which a trained model all but never makes: as many again, and one STUCK run
-        self.U = torch.rand(int(n_u or 2 * loop.max_events + 256), m0, device=dev, generator=gen)
+        self.U = uniform_table(int(n_u or 2 * loop.max_events + 256), m0, (int(seed) * 0x9E3779B1 + WINDOW_TAG) & 0x7FFFFFFFFFFFFFFF, dev)
         self.win_tok = torch.zeros(m0, W, dtype=torch.int64, device=dev)
         self.win_seg = torch.zeros(m0, W, dtype=torch.int64, device=dev)
         self.logits = torch.zeros(m0, self.model.n_token, dtype=torch.float32, device=dev)
@@ -1255,16 +1103,9 @@ class WindowedLoop:
         out = []
         for j, i in enumerate(self.idx):
             st, ids = int(state[j, ACC_S_STATUS]), [int(t) for t in seq[j, :int(state[j, ACC_S_LEN])]]
-            if st == ACC_DONE:
-                out.append(ids[:-1])
-            elif st == ACC_STUCK:
-                out.append(ids)
-            elif st == ACC_OUT_OF_DRAWS:
-                out.append(EmoError('generate_accompaniments: stream %d used all %d uniforms of its windowed table' % (i, self.U.shape[0])))
-            elif st == ACC_OVERFLOW:
-                out.append(EmoError('generate_accompaniments: stream %d: token row or lead-sheet table too short past the window' % i))
-            else:
-                out.append(EmoError('generate_accompaniments: stream %d still running after %d windowed steps' % (i, self.steps)))
+            out.append(_stream_result(st, ids, 'stream %d used all %d uniforms of its windowed table' % (i, self.U.shape[0]),
+                                      'stream %d: token row or lead-sheet table too short past the window' % i,
+                                      'stream %d still running after %d windowed steps' % (i, self.steps)))
         return out
 
 

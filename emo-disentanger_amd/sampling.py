@@ -57,3 +57,11 @@ def nucleus(probs, p, rng=None):
 def beat_position(event):
     """'Beat_7' -> 7"""
     return int(event.rsplit('_', 1)[1])
+
+
+def event_name(idx2event, i):
+    """The event of token id i in a dict or list vocabulary, None where it has none."""
+    if isinstance(idx2event, dict):
+        return idx2event.get(i)
+    return idx2event[i] if i < len(idx2event) else None
+

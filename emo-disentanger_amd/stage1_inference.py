@@ -14,7 +14,9 @@ import torch
 
 from . import ops, sampling
 from ._lib import EmoError
-from .sampling import beat_position, nucleus  # noqa: F401  (`nucleus` is looked up at call time: tests wrap it)
+from .inference import uniform_table
+from .replay import StepReplayer
+from .sampling import beat_position, event_name, nucleus  # noqa: F401  (`nucleus` is looked up at call time: tests wrap it)
 
 SHARP_NAMES = ('C', 'C#', 'D', 'D#', 'E', 'F', 'F#', 'G', 'G#', 'A', 'A#', 'B')     # pitch-class spelling of convert_key.py:14-15
 MAJOR_KEY = np.array(SHARP_NAMES)
@@ -118,7 +120,7 @@ def event_tables(idx2event, V):
     Ids without an event get no bits."""
     flags, beat = np.zeros(V, np.int32), np.zeros(V, np.int32)
     for i in range(V):
-        e = idx2event.get(i) if isinstance(idx2event, dict) else (idx2event[i] if i < len(idx2event) else None)
+        e = event_name(idx2event, i)
         if e is None:
             continue
         f = 0
@@ -287,16 +289,14 @@ class LeadSheetLoop:
             state[i, [S_STATUS, S_LEN, S_BARS, S_FEED]] = (RUNNING if s.open() else DONE), plens[i], s.bars, self.L0
         self.seq, self.params, self.state = (torch.from_numpy(a).to(dev) for a in (seq, params, state))
         self.running = torch.tensor([int((state[:, S_STATUS] == RUNNING).sum())], dtype=torch.int32, device=dev)
-        gen = torch.Generator(device=dev)
-        gen.manual_seed(seed)
-        self.U = torch.rand(self.max_len - self.L0 + 1, n, device=dev, generator=gen)      # at most one draw per step, one more at the end
+        self.U = uniform_table(self.max_len - self.L0 + 1, n, seed, dev)      # at most one draw per step, one more at the end
         self.tok = self.seq[:, self.L0 - 1].contiguous()      # (a valid id in every row before the first grammar step)
         self.logits = torch.empty(n, V, dtype=torch.float32, device=dev)
         with torch.no_grad():
             h, _, _ = model._prefill(self.seq[:, :self.L0].t(), self.mem)
             self.logits.copy_(model._logits(h.view(n, self.L0, -1)[:, -1].contiguous()))
         self.pos = self.L0                   # positions in the memory (host count: every row advances one per step)
-        self.graph = self.graph_k = self.stream = None
+        self.replayed = (0, 0.0)
 
     def grammar(self):
         ops.txl_grammar_step(self.logits, self.temp, self.top_p, KEY_TEMP, KEY_TOP_P, self.U, self.ev_flags, self.ev_beat, self.params, self.state,
@@ -306,40 +306,20 @@ class LeadSheetLoop:
         self.grammar()
         self.model.decode_step(self.tok, self.mem, logits_out=self.logits)
 
-    def capture(self, steps):
-        if self.stream is None:
-            self.stream = torch.cuda.Stream(device=self.dev)
-        g = torch.cuda.CUDAGraph()
-        self.stream.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(self.stream):
-            with torch.cuda.graph(g, stream=self.stream):
-                for _ in range(steps):
-                    self.one_step()
-        return g
+    def _live(self):
+        """Running count (synchronises)."""
+        return int(self.running.item())
 
     def run(self, use_graph=True, steps_per_graph=None):
         """Steps until every stream is finished or the memory is full; the running count is read once per replay (per step without graphs).
         At the memory's end one more grammar step runs alone: a stream that then still wants a model step would overflow max_gen_len."""
-        k = max(1, int(steps_per_graph or os.environ.get('EMO_GEN_GRAPH_STEPS', 16)))
+        # (the replayer holds graph / graph_k / stream of this run and goes with it: kept on the loop it would close a reference cycle through
+        # one_step, and graphs freed by the cycle collector can be freed in the middle of a later capture)
+        rp = StepReplayer(self.one_step, self.dev, steps_per_graph)
         with torch.no_grad():
-            if int(self.running.item()) > 0 and self.pos < self.max_len:
-                self.one_step()                  # eager first step (also warms every kernel / workspace cache before any capture)
-                self.pos += 1
-            if use_graph and int(self.running.item()) > 0 and self.pos < self.max_len:
-                torch.cuda.synchronize()
-                self.graph = self.capture(1)
-                self.graph_k = self.capture(k) if k > 1 and self.max_len - self.pos >= 2 * k else None
-                main = torch.cuda.current_stream()
-                with torch.cuda.stream(self.stream):
-                    while int(self.running.item()) > 0 and self.pos < self.max_len:
-                        many = self.graph_k is not None and self.max_len - self.pos >= k
-                        (self.graph_k if many else self.graph).replay()
-                        self.pos += k if many else 1
-                main.wait_stream(self.stream)
-            while int(self.running.item()) > 0 and self.pos < self.max_len:
-                self.one_step()
-                self.pos += 1
-            if int(self.running.item()) > 0:
+            self.pos = rp.run(self.pos, self.max_len, live=self._live, use_graph=use_graph)
+            self.replayed = rp.replayed
+            if self._live() > 0:
                 self.grammar()
             torch.cuda.synchronize()
 

@@ -156,6 +156,33 @@ def test_generate_streams_gpt2_kv_cache_graph():
     assert torch.equal(a[:, 9:][safe], full[:, 8:-1].argmax(-1)[safe])
 
 
+def test_generate_streams_gpt2_fp32_nucleus_graph_eager_and_host_draws():
+    # the general-shape GPT-2 step (fp32: no LayerNorm fold, no one-launch step) under the nucleus path, where the sampler kernel owns the
+    # position counter and the engine must not advance it: replay == eager == a host loop drawing from the same uniform table, row per step
+    from emo_disentanger_amd import inference as inf, ops
+    g = json.load(open(os.path.join(G, 'generate.json')))
+    m = _tiny_gpt2(g['model'])
+    n, T0, Tn, temp, top_p, seed = 3, 9, 20, 1.1, 0.9, 3
+    gen = torch.Generator().manual_seed(2)
+    ptok = torch.randint(0, g['model']['V'] - 1, (n, T0), generator=gen).cuda()
+    pseg = torch.ones(n, T0, dtype=torch.long).cuda()
+    a = inf.generate_streams(m, ptok, pseg, Tn, temp=temp, top_p=top_p, seed=seed)
+    b = inf.generate_streams(m, ptok, pseg, Tn, temp=temp, top_p=top_p, seed=seed, use_graph=False)
+    assert a.shape == (n, T0 + Tn) and torch.equal(a, b)
+    assert torch.equal(a[:, :T0], ptok) and int(a.min()) >= 0 and int(a.max()) < g['model']['V']
+    U = inf.uniform_table(Tn, n, seed, ptok.device)
+    with torch.no_grad():
+        eng = inf.make_engine(m, n)
+        assert eng.persist is None and eng.fold is None
+        logits = eng.prefill(ptok, pseg)
+        want = [ptok]
+        for s in range(Tn):
+            nxt = ops.sample_nucleus(logits.contiguous(), temp, top_p, U[s].contiguous())
+            want.append(nxt.view(n, 1))
+            logits = eng.step(nxt, pseg[:, 0])
+    assert torch.equal(a, torch.cat(want, 1))
+
+
 @pytest.mark.parametrize('accum', [1, 2])
 def test_train_loop_matches_reference_trace(accum):
     from emo_disentanger_amd import train as tr

@@ -121,27 +121,20 @@ def bare_step(inf, m, e2i, i2e, leads, primers, steps, k=16):
 
     def one():
         eng.step(loop.tok, loop.segv, dev_pos=True, logits_out=loop.logits)
+    from emo_disentanger_amd.replay import StepReplayer, replay_plan
+    rp = StepReplayer(one, loop.dev, k)
     with torch.no_grad():
         one()
         torch.cuda.synchronize()
-        s = torch.cuda.Stream()
-        graphs = {}
-        for n_ in (1, k):
-            g = torch.cuda.CUDAGraph()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                with torch.cuda.graph(g, stream=s):
-                    for _ in range(n_):
-                        one()
-            graphs[n_] = g
-        main = torch.cuda.current_stream()
-        left = steps
+        counts, many = replay_plan(0, steps, k)
+        graphs = {1: rp.capture(1)}
+        if many:
+            graphs[k] = rp.capture(k)
+        main, s = torch.cuda.current_stream(), rp.stream
         t0 = time.perf_counter()
         with torch.cuda.stream(s):
-            while left > 0:
-                many = left >= k
-                graphs[k if many else 1].replay()
-                left -= k if many else 1
+            for c in counts:
+                graphs[c].replay()
                 eng.check_persistent() if eng.persist is not None else None
                 int(loop.running.item())
         main.wait_stream(s)
