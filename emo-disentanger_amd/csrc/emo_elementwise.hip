@@ -836,6 +836,8 @@ extern "C" int emo_accuracy_counts(const float* logits, const int64_t* tgt, cons
 // ascending index) of <= 1024 entries in LDS; inclusive cumsum in np.cumsum's sequential fp32 order; last_index = SECOND position
 // whose cumsum exceeds top_p (reference inference.py:93-94 keeps the crossing token — SURVEY F12); where the reference would raise
 // IndexError (single crossing) all sorted tokens are kept.  Draw: cdf over the renormalised (f64) candidates, searchsorted(u, right).
+// Ascending index among equal probabilities is this project's rule; the reference's order among exact ties is an accident of NumPy's
+// unstable argsort (emo_nucleus.h).
 // Serial work is two tight prefix scans (fp32 by wave 0, f64 by wave 1, concurrently); because both prefixes are monotone the
 // crossing positions are COUNTS (#{cum <= top_p}, #{run <= target}) taken by all threads.  r01: 62 us (bitonic network + three
 // branchy single-thread loops) -> see profiles.

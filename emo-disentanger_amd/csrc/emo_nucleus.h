@@ -2,8 +2,12 @@
 // (emo_decode_persist.hip), which must pick the same token from the same logits bit for bit.  Reference: stage2_accompaniment/inference.py:71-100.
 // probs = softmax(l/temp) (fp32, as NumPy on fp32 logits); rank sort (descending, ties by ascending index) of <= 1024 entries in LDS; inclusive
 // cumsum in np.cumsum's sequential fp32 order; last_index = SECOND position whose cumsum exceeds top_p (the reference keeps the crossing token —
-// SURVEY F12); where the reference would raise IndexError (single crossing) all sorted tokens are kept.  Draw: cdf over the renormalised (f64)
-// candidates, searchsorted(u, right).
+// SURVEY F12); where the reference would raise IndexError (single crossing) all sorted tokens are kept; no crossing keeps the top min(V, 3).  Draw:
+// cdf over the renormalised (f64) candidates, searchsorted(u, right).
+// Ascending index among EQUAL probabilities is THIS PROJECT's rule, not the reference's: the reference's order among exact ties is whatever NumPy's
+// unstable argsort produces (on tests/golden/sampling.json neither ascending nor descending index), so a tie group that straddles the cut keeps
+// its lowest indices here and an arbitrary subset of the same size there.  tests/test_gpu_sampling.py pins the rule and holds this header to a
+// float64 restatement (tests/nucleus_ref.py) with derived rounding bounds.
 #pragma once
 #include "emo_common.h"
 
@@ -81,7 +85,7 @@ __device__ __forceinline__ int64_t emo_nucleus_draw(const float* __restrict__ l,
     sync();
     const float tot = red[0] + red[1] + red[2] + red[3] + red[4] + red[5] + red[6] + red[7];
     // rank sort on 64-bit keys {probability bits, ~index}: key_j > key_c  <=>  p_j > p_c, or p_j == p_c and j < c (probabilities are >= 0, so their
-    // bit patterns order like their values) - the stable descending order of the reference's argsort in ONE compare + ONE add-with-carry per pair
+    // bit patterns order like their values) - a total order (the tie rule above) in ONE compare + ONE add-with-carry per pair
     // (r04: the float version spent ~7 VALU instructions per pair, 336 x 336 pairs on 6 waves = half of the kernel's 20 us).  Pad keys are 0.
     for (int c = tid; c < V; c += 512) {
         const float pc = sp[c] / tot;

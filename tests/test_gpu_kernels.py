@@ -1002,6 +1002,7 @@ def test_softmax_attention_dropout_consistency():
 def test_nucleus_sampling_matches_host_reference():
     ops = _ops()
     from oracle import host_ref
+    from nucleus_ref import DELTA
     rng = np.random.default_rng(3)
     for V, scale, temp, p in ((327, 4.0, 1.1, 0.9), (327, 1.0, 1.2, 0.97), (40, 2.0, 1.1, 0.99), (370, 3.0, 1.0, 0.5)):
         logits = (rng.standard_normal((16, V)) * scale).astype(np.float32)
@@ -1013,11 +1014,12 @@ def test_nucleus_sampling_matches_host_reference():
             cdf = np.cumsum(pr)
             cdf /= cdf[-1]
             exp = cand[np.searchsorted(cdf, u[r], side='right')]
-            # ties/rounding at a cdf boundary may move the pick by one rank: accept a neighbour within 1e-5 of the boundary
+            # rounding at a cdf boundary may move the pick by one rank: accept a neighbour within DELTA = 32 * 2^-24 of the boundary, the bound
+            # derived in tests/nucleus_ref.py (tests/test_gpu_sampling.py probes both sides of every boundary at 2 DELTA)
             if got[r] != exp:
                 i = int(np.searchsorted(cdf, u[r], side='right'))
                 near = min(abs(cdf[i] - u[r]), abs(cdf[i - 1] - u[r]) if i > 0 else 1.0)
-                assert near < 1e-5 and got[r] in cand, (V, r, got[r], exp)
+                assert near <= DELTA and got[r] in cand, (V, r, got[r], exp)
 
 
 def test_nucleus_step_keeps_loop_state_on_device():
