@@ -54,6 +54,9 @@
 // half A (first granule pair polled alone), no slice between a publish and the barrier behind the next gather: kernel 197.6 -> 164 us per token step;
 // with the weight stream ablated 130 us.  The same kernel as a template also runs the GPT-2 block (KV-cache attention in P2): see the end of the file.
 //
+// Third form (stage 1): the Transformer-XL evaluation block on the GPT-2 form's skeleton — relative-position attention over a sliding window of the
+// head-major KV cache in P2; see the Transformer-XL notes before its entry points at the end of the file.
+//
 // Arithmetic mirrors the launch path's bf16 mode (emo_gemm skinny kernel, favor_decode_fast_kernel, layernorm_fwd_bf16_d512_kernel): bf16
 // activations between products, fp32 accumulation, fp32 FAVOR+ state, LayerNorm statistics in fp32 from the bf16 row.
 #include "emo_common.h"
@@ -91,8 +94,11 @@ struct PdArgs {
     // logits) exactly as emo_sample_nucleus_step does, writes it to tok_out / seq and hands it to the group through 4 granules; tok is ignored
     int samp_mode; float temp, top_p; const float* u_steps; int64_t* step; int64_t* seq; int64_t ld_seq, col0; int64_t* tok_out; const float* logits_in; int n_real;
     int flags;      // bit 0: non-temporal weight loads
-    // GPT-2 form (pd_step_kernel<true>): [gamma | beta] of layer 0's ln_1, rows per (stream, head) of the head-major KV caches the table's S / z slots point to
+    // GPT-2 form (pd_step_kernel<1>): [gamma | beta] of layer 0's ln_1, rows per (stream, head) of the head-major KV caches the table's S / z slots point to
     const float* ln0; int64_t kv_tmax;
+    // Transformer-XL form (pd_step_kernel<2>): per-stream lengths INCLUDING this token (read from the device: the token's cache row is lens - 1), the
+    // attention window (keys lens - 1 - mem_len .. lens - 1), the two bias rows [8][64] of the relative-position score; the table's omega slot holds R_l
+    const int64_t* lens; int mem_len; const float* rwb; const float* rrb;
     u64* diag;      // optional [32 members][16 layers][8 phases][4]: {t_start, t_gathered, t_published, failed poll passes} of GROUP 0, 10-ns ticks (tools/pd_diag.py)
 };
 // t = thread index INSIDE the role (0..255), hw = wave inside the role (0..3)
@@ -393,9 +399,11 @@ __device__ __noinline__ int64_t pd_draw(const float* l, int n_token, float temp,
     return emo_nucleus_draw(l, n_token, temp, top_p, u, pd_smem + LDS_SAMP, tid, [] { PD_BARRIER(); });
 }
 
-// G2 = false: the Performer layer described above.  G2 = true: the GPT-2 block on the same skeleton (see the GPT-2 notes before the entry points).
-template <bool G2>
+// FORM 0: the Performer layer described above.  FORM 1 (G2): the GPT-2 block on the same skeleton (see the GPT-2 notes before the entry points).
+// FORM 2 (G2 and TX): the Transformer-XL block = the GPT-2 form with relative-position scores over a window, ReLU, no positional table.
+template <int FORM>
 __global__ __launch_bounds__(PD_NT, 3) void pd_step_kernel(PdArgs a) {
+    constexpr bool G2 = FORM != 0, TX = FORM == 2;
     bf16_t* xin = (bf16_t*)(pd_smem + LDS_XIN);        // layer input (post-LN2 / embedding), kept for the out-projection's residual
     bf16_t* xa = (bf16_t*)(pd_smem + LDS_XA);          // attention output rows
     bf16_t* x1 = (bf16_t*)(pd_smem + LDS_X1);          // post-LN1 rows, kept for the FFN2 residual
@@ -484,7 +492,10 @@ __global__ __launch_bounds__(PD_NT, 3) void pd_step_kernel(PdArgs a) {
             const int s = c.hw, c8 = c.lane * 8;
             const int64_t stream = (int64_t)g * PD_GS + s;
             int64_t tk, pos;
-            if (sampling) {                                           // position = pos0 + (step counter AFTER the draw); the counter is bumped at the kernel's end
+            if constexpr (TX) {                                       // no position enters the embedding; pos = the cache row of this token (idle streams: length 0)
+                tk = a.tok[stream];
+                pos = max(a.lens[stream] - 1, (int64_t)0);
+            } else if (sampling) {                                    // position = pos0 + (step counter AFTER the draw); the counter is bumped at the kernel's end
                 tk = s_misc[4 + s];
                 pos = stream < a.n_real ? a.pos0 + a.step[stream] + 1 : 0;
             } else {
@@ -498,12 +509,15 @@ __global__ __launch_bounds__(PD_NT, 3) void pd_step_kernel(PdArgs a) {
                 const f32x4 e = *(const f32x4*)(a.E + tk * PD_D + c8 + 4 * h2);
                 f32x4 sv = {0.f, 0.f, 0.f, 0.f};
                 if (a.seg) sv = *(const f32x4*)(a.Sg + sg * PD_D + c8 + 4 * h2);
-                const f32x4 p = *(const f32x4*)(a.pe + pos * PD_D + c8 + 4 * h2);
+                f32x4 p = {0.f, 0.f, 0.f, 0.f};
+                if constexpr (!TX) p = *(const f32x4*)(a.pe + pos * PD_D + c8 + 4 * h2);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     float v = e[i] * a.emb_scale;                     // reference order: emb.mul_(scale); emb += seg.mul_(scale); + pe
-                    v += sv[i] * a.emb_scale;
-                    v += p[i];
+                    if constexpr (!TX) {
+                        v += sv[i] * a.emb_scale;
+                        v += p[i];
+                    }
                     o[4 * h2 + i] = (bf16_t)v;
                 }
             }
@@ -702,7 +716,7 @@ __global__ __launch_bounds__(PD_NT, 3) void pd_step_kernel(PdArgs a) {
             {
                 const int t = cc.t >> 6, s = (cc.t >> 4) & 3, col = cc.t & 15;      // hidden column m * 64 + t * 16 + col
                 const float hv = pd_part_sum<4>(part, t, s, col);
-                pd_publish_triple(gs + OFF_E5 + ((s * PD_GM + m) * 4 + t) * PD_E5_GPT, ep + 4u, G2 ? gelu_new_fast(hv) : fmaxf(hv, 0.f), col, cc);
+                pd_publish_triple(gs + OFF_E5 + ((s * PD_GM + m) * 4 + t) * PD_E5_GPT, ep + 4u, (G2 && !TX) ? gelu_new_fast(hv) : fmaxf(hv, 0.f), col, cc);
             }
             PD_DIAG(l, 4, 2, PD_NOW());
             PD_SCHED_FENCE();
@@ -806,17 +820,40 @@ __global__ __launch_bounds__(PD_NT, 3) void pd_step_kernel(PdArgs a) {
             // in flight.  The first two key sweeps are requested BEFORE the q row arrives (they do not depend on it), the first two value sweeps before the
             // softmax's two barriers.
             const int kprev = G2 ? min(s_misc[8 + jm], (int)a.kv_tmax - 1) : 0;      // cached rows; this token's row gets index kprev
-            const int last_c = kprev > 0 ? kprev - 1 : 0;             // rows past the cache: any valid address, the value is replaced / masked
+            // The sweeps index the rows of the attention WINDOW: row i = cache row jb + i, nk cached rows, this token's row = window row nk.  GPT-2: the
+            // window is the whole cache (jb = 0, nk = kprev) and the token's row is part of the sweeps (nin = nk + 1 rows).  Transformer-XL: the last
+            // mem_len cached rows, and the token's row is scored on its own — in the steady state (nk = mem_len = 512) the sweeps are then exactly one
+            // 512-row round and not a round plus one row, which would cost a second exposed load latency for the keys and for the values.
+            const int jb = TX ? max(kprev - a.mem_len, 0) : 0;
+            const int nk = kprev - jb, nin = TX ? nk : nk + 1;
+            const int last_c = nk > 0 ? nk - 1 : 0;                   // rows past the window: any valid address, the value is replaced / masked
             const int rl = cc.t >> 3, c8 = (cc.t & 7) * 8;
-            gbf16_t* Kc = (gbf16_t*)L.S + (sh * a.kv_tmax) * PD_DH + c8;
-            gbf16_t* Vc = (gbf16_t*)L.z + (sh * a.kv_tmax) * PD_DH + c8;
+            gbf16_t* Kc = (gbf16_t*)L.S + (sh * a.kv_tmax + jb) * PD_DH + c8;
+            gbf16_t* Vc = (gbf16_t*)L.z + (sh * a.kv_tmax + jb) * PD_DH + c8;
             bf16x8 kA[8], kB[8];
 #define PD_KV_LOAD(dst, base, J0)                                                                          \
     _Pragma("unroll") for (int u = 0; u < 8; ++u) {                                                        \
         const int j_ = (J0) + u * 32 + rl;                                                                 \
-        dst[u] = *(const gbf16x8*)((base) + (int64_t)(j_ < kprev ? j_ : last_c) * PD_DH);                  \
+        dst[u] = *(const gbf16x8*)((base) + (int64_t)(j_ < nk ? j_ : last_c) * PD_DH);                     \
     }
-            if constexpr (G2) {
+            // Transformer-XL: window row i lies at distance nk - i, whose R row (of this head) is swept like a key row; rows past the window read row 0
+            const gbf16_t* Rp = (const gbf16_t*)L.omega + hm * PD_DH + c8;
+#define PD_R_LOAD(dst, J0)                                                                                 \
+    _Pragma("unroll") for (int u = 0; u < 8; ++u) {                                                        \
+        const int j_ = (J0) + u * 32 + rl;                                                                 \
+        dst[u] = *(const gbf16x8*)(Rp + (int64_t)(j_ < nk ? nk - j_ : 0) * PD_D);                          \
+    }
+            bf16x8 r0 = {};
+            f32x4 bw[2] = {}, br[2] = {};
+            if constexpr (TX) {
+                PD_R_LOAD(kA, 0);
+                PD_R_LOAD(kB, 256);
+                r0 = *(const gbf16x8*)Rp;                             // distance 0: the token's own row
+                const gfloat* bwp = (const gfloat*)a.rwb + hm * PD_DH + c8;
+                const gfloat* brp = (const gfloat*)a.rrb + hm * PD_DH + c8;
+                bw[0] = *(const gf32x4*)bwp; bw[1] = *(const gf32x4*)(bwp + 4);
+                br[0] = *(const gf32x4*)brp; br[1] = *(const gf32x4*)(brp + 4);
+            } else if constexpr (G2) {
                 PD_KV_LOAD(kA, Kc, 0);
                 PD_KV_LOAD(kB, Kc, 256);      // (unconditional: rows past the cache read one hot row — a conditionally defined array stays live across the layer loop)
             }
@@ -827,35 +864,81 @@ __global__ __launch_bounds__(PD_NT, 3) void pd_step_kernel(PdArgs a) {
                 float* sc = oml;
                 float* vp = oml + 2048;
                 bf16x8 kn, vn;
-                float qv[8];
+                float qv[8], qr[8];                                   // Transformer-XL: qv = q + r_w_bias (content term), qr = q + r_r_bias (position term)
 #pragma unroll
-                for (int e = 0; e < 8; ++e) { qv[e] = xq[c8 + e]; kn[e] = (bf16_t)xk[c8 + e]; vn[e] = (bf16_t)xv[c8 + e]; }
-                if (cc.t < 8) {
-                    *(gbf16x8*)(Kc + (int64_t)kprev * PD_DH) = kn;
-                    *(gbf16x8*)(Vc + (int64_t)kprev * PD_DH) = vn;
+                for (int e = 0; e < 8; ++e) {
+                    qv[e] = xq[c8 + e];
+                    qr[e] = 0.f;
+                    if constexpr (TX) { qr[e] = qv[e] + br[e >> 2][e & 3]; qv[e] += bw[e >> 2][e & 3]; }
+                    kn[e] = (bf16_t)xk[c8 + e];
+                    vn[e] = (bf16_t)xv[c8 + e];
+                }
+                if (cc.t < 8) {                                       // window row nk = cache row kprev <= kv_tmax - 1
+                    *(gbf16x8*)(Kc + (int64_t)nk * PD_DH) = kn;
+                    *(gbf16x8*)(Vc + (int64_t)nk * PD_DH) = vn;
                 }
                 float mx = -3.0e38f;
 #define PD_KV_SCORE(src, J0)                                                                               \
     _Pragma("unroll") for (int u = 0; u < 8; ++u) {                                                        \
         const int j_ = (J0) + u * 32 + rl;                                                                 \
-        const bf16x8 kk = j_ == kprev ? kn : src[u];                                                       \
+        const bf16x8 kk = (!TX && j_ == nk) ? kn : src[u];                                                 \
         float d = 0.f;                                                                                     \
         _Pragma("unroll") for (int e = 0; e < 8; ++e) d += qv[e] * (float)kk[e];                           \
         d = pd_dpp_add(d, 0);                                                                              \
         d = pd_dpp_add(d, 1);                                                                              \
         d = pd_dpp_add(d, 2);                                                                              \
+        if (TX && j_ < nin) d += sc[j_];                          /* the row's position term (PD_R_SCORE) */ \
         d *= 0.125f;                                                                                       \
-        if (j_ <= kprev) {                                                                                 \
+        if (j_ < nin) {                                                                                    \
             mx = fmaxf(mx, d);                                                                             \
             if ((cc.t & 7) == 0) sc[j_] = d;                                                               \
         }                                                                                                  \
     }
-                for (int j0 = 0; j0 <= kprev; j0 += 512) {
-                    PD_KV_SCORE(kA, j0);
-                    if (j0 + 512 <= kprev) { PD_KV_LOAD(kA, Kc, j0 + 512); }
-                    if (j0 + 256 <= kprev) {
-                        PD_KV_SCORE(kB, j0 + 256);
-                        if (j0 + 768 <= kprev) { PD_KV_LOAD(kB, Kc, j0 + 768); }
+                // position term of window row j_: (q + r_r_bias) . R[nk - j_], left in sc[j_] by the thread that adds the content term to it
+#define PD_R_SCORE(src, J0)                                                                                \
+    _Pragma("unroll") for (int u = 0; u < 8; ++u) {                                                        \
+        const int j_ = (J0) + u * 32 + rl;                                                                 \
+        float d = 0.f;                                                                                     \
+        _Pragma("unroll") for (int e = 0; e < 8; ++e) d += qr[e] * (float)src[u][e];                       \
+        d = pd_dpp_add(d, 0);                                                                              \
+        d = pd_dpp_add(d, 1);                                                                              \
+        d = pd_dpp_add(d, 2);                                                                              \
+        if (j_ < nin && (cc.t & 7) == 0) sc[j_] = d;                                                       \
+    }
+                if constexpr (TX) {
+                    // a round = 512 window rows: their R rows are in the registers (requested before the q row arrived, or at the end of the round before);
+                    // each half's key rows are requested into the registers its position terms have just left
+                    for (int j0 = 0; j0 < nin; j0 += 512) {
+                        PD_R_SCORE(kA, j0);
+                        PD_SCHED_FENCE();
+                        PD_KV_LOAD(kA, Kc, j0);
+                        PD_R_SCORE(kB, j0 + 256);
+                        PD_SCHED_FENCE();
+                        PD_KV_LOAD(kB, Kc, j0 + 256);
+                        PD_KV_SCORE(kA, j0);
+                        PD_SCHED_FENCE();
+                        if (j0 + 512 < nin) { PD_R_LOAD(kA, j0 + 512); }
+                        if (j0 + 256 < nin) { PD_KV_SCORE(kB, j0 + 256); }
+                        PD_SCHED_FENCE();
+                        if (j0 + 512 < nin) { PD_R_LOAD(kB, j0 + 768); }
+                    }
+                    float d = 0.f;                                    // the token's own row: distance 0 (every thread; the 8 lanes of a row hold the 64 dims)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) d += qv[e] * (float)kn[e] + qr[e] * (float)r0[e];
+                    d = pd_dpp_add(d, 0);
+                    d = pd_dpp_add(d, 1);
+                    d = pd_dpp_add(d, 2);
+                    d *= 0.125f;
+                    mx = fmaxf(mx, d);
+                    if (cc.t == 0) sc[nk] = d;
+                } else {
+                    for (int j0 = 0; j0 < nin; j0 += 512) {
+                        PD_KV_SCORE(kA, j0);
+                        if (j0 + 512 < nin) { PD_KV_LOAD(kA, Kc, j0 + 512); }
+                        if (j0 + 256 < nin) {
+                            PD_KV_SCORE(kB, j0 + 256);
+                            if (j0 + 768 < nin) { PD_KV_LOAD(kB, Kc, j0 + 768); }
+                        }
                     }
                 }
                 PD_SCHED_FENCE();
@@ -868,7 +951,7 @@ __global__ __launch_bounds__(PD_NT, 3) void pd_step_kernel(PdArgs a) {
                 PD_BARRIER();                                         // 2b
                 mx = fmaxf(fmaxf(dpart[0], dpart[1]), fmaxf(dpart[2], dpart[3]));
                 float sum = 0.f;
-                for (int j = cc.t; j <= kprev; j += PD_HT) {
+                for (int j = cc.t; j <= nk; j += PD_HT) {
                     const float pj = __expf(sc[j] - mx);
                     sc[j] = pj;
                     sum += pj;
@@ -882,16 +965,23 @@ __global__ __launch_bounds__(PD_NT, 3) void pd_step_kernel(PdArgs a) {
 #define PD_KV_ACC(src, J0)                                                                                 \
     _Pragma("unroll") for (int u = 0; u < 8; ++u) {                                                        \
         const int j_ = (J0) + u * 32 + rl;                                                                 \
-        const bf16x8 vv = j_ == kprev ? vn : src[u];                                                       \
-        const float pj = j_ <= kprev ? sc[j_] : 0.f;                                                       \
+        const bf16x8 vv = (!TX && j_ == nk) ? vn : src[u];                                                 \
+        const float pj = j_ < nin ? sc[j_] : 0.f;                                                          \
         _Pragma("unroll") for (int e = 0; e < 8; ++e) acc[e] += pj * (float)vv[e];                         \
     }
-                for (int j0 = 0; j0 <= kprev; j0 += 512) {
+                for (int j0 = 0; j0 < nin; j0 += 512) {
                     PD_KV_ACC(vA, j0);
-                    if (j0 + 512 <= kprev) { PD_KV_LOAD(vA, Vc, j0 + 512); }
-                    if (j0 + 256 <= kprev) {
+                    if (j0 + 512 < nin) { PD_KV_LOAD(vA, Vc, j0 + 512); }
+                    if (j0 + 256 < nin) {
                         PD_KV_ACC(vB, j0 + 256);
-                        if (j0 + 768 <= kprev) { PD_KV_LOAD(vB, Vc, j0 + 768); }
+                        if (j0 + 768 < nin) { PD_KV_LOAD(vB, Vc, j0 + 768); }
+                    }
+                }
+                if constexpr (TX) {                                   // the token's own row
+                    if (rl == 0) {
+                        const float pj = sc[nk];
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) acc[e] += pj * (float)vn[e];
                     }
                 }
                 *(f32x4*)(vp + rl * PD_DH + c8) = (f32x4){acc[0], acc[1], acc[2], acc[3]};
@@ -1021,10 +1111,12 @@ static int pd_supported() {
     const size_t lds = 96 * 1024;
     int dev = 0, cus = 0, per_cu = 0;
     bool ok = hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus >= PD_NG * PD_GM;
-    ok = ok && hipFuncSetAttribute((const void*)pd_step_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-    ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)pd_step_kernel<false>, PD_NT, lds) == hipSuccess && per_cu >= 1;
-    ok = ok && hipFuncSetAttribute((const void*)pd_step_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-    ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)pd_step_kernel<true>, PD_NT, lds) == hipSuccess && per_cu >= 1;
+    ok = ok && hipFuncSetAttribute((const void*)pd_step_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+    ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)pd_step_kernel<0>, PD_NT, lds) == hipSuccess && per_cu >= 1;
+    ok = ok && hipFuncSetAttribute((const void*)pd_step_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+    ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)pd_step_kernel<1>, PD_NT, lds) == hipSuccess && per_cu >= 1;
+    ok = ok && hipFuncSetAttribute((const void*)pd_step_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+    ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)pd_step_kernel<2>, PD_NT, lds) == hipSuccess && per_cu >= 1;
     (void)hipGetLastError();
     cached = ok ? 1 : 0;
     return cached;
@@ -1035,10 +1127,20 @@ static int pd_launch(const void* layer_table, int64_t n_layers, const int64_t* t
                      float emb_scale, int64_t pos0, const int64_t* pos_ids, const void* wout_packed, const float* bout, int64_t n_token, float* logits,
                      int64_t n_streams, int64_t d_model, int64_t n_head, int64_t n_feat, int64_t d_ff, void* sync_ws, int64_t sync_ws_bytes, float eps,
                      float ln_eps, int64_t* diag, int samp_mode, float temperature, float top_p, const float* u_steps, int64_t* step, int64_t* seq,
-                     int64_t ld_seq, int64_t col0, int64_t* tok_out, const float* logits_in, int64_t n_real, emo_stream_t stream, bool g2 = false,
-                     const float* ln0 = nullptr, int64_t kv_tmax = 0) {
-    EMO_CHECK(layer_table && E && pe && wout_packed && bout && logits && sync_ws, "emo_performer_decode_step: null pointer");
-    if (g2) EMO_CHECK(ln0 && kv_tmax >= 1 && kv_tmax <= 2048, "emo_gpt2_decode_step: needs layer 0's ln_1 parameters and a KV cache of <= 2048 rows per (stream, head)");
+                     int64_t ld_seq, int64_t col0, int64_t* tok_out, const float* logits_in, int64_t n_real, emo_stream_t stream, int form = 0,
+                     const float* ln0 = nullptr, int64_t kv_tmax = 0, const int64_t* lens = nullptr, int64_t mem_len = 0, int64_t n_dist = 0,
+                     const float* rwb = nullptr, const float* rrb = nullptr) {
+    EMO_CHECK(layer_table && E && (pe || form == 2) && wout_packed && bout && logits && sync_ws, "emo_performer_decode_step: null pointer");
+    if (form == 1) EMO_CHECK(ln0 && kv_tmax >= 1 && kv_tmax <= 2048, "emo_gpt2_decode_step: needs layer 0's ln_1 parameters and a KV cache of <= 2048 rows per (stream, head)");
+    if (form == 2) {
+        // the score buffer holds the window's mem_len cached rows + the token's own: mem_len + 1 <= 2048; the CACHE may be longer (row = position)
+        EMO_CHECK(ln0 && lens && rwb && rrb, "emo_txl_decode_step: null pointer");
+        EMO_CHECK(mem_len >= 1 && mem_len + 1 <= 2048, "emo_txl_decode_step: 1 <= mem_len and mem_len + 1 <= 2048 (got mem_len %lld)", (long long)mem_len);
+        EMO_CHECK(kv_tmax >= 1 && kv_tmax <= ((int64_t)1 << 24), "emo_txl_decode_step: bad kv_tmax %lld", (long long)kv_tmax);
+        EMO_CHECK(n_dist >= (mem_len < kv_tmax - 1 ? mem_len : kv_tmax - 1) + 1,
+                  "emo_txl_decode_step: the R tables have %lld rows, the window reaches distance %lld", (long long)n_dist,
+                  (long long)(mem_len < kv_tmax - 1 ? mem_len : kv_tmax - 1));
+    }
     EMO_CHECK(d_model == PD_D && n_head == PD_H && n_feat == PD_F && d_ff == PD_FF,
               "emo_performer_decode_step: built for d_model 512 / 8 heads / 128 features / d_ff 2048 (got %lld / %lld / %lld / %lld)", (long long)d_model,
               (long long)n_head, (long long)n_feat, (long long)d_ff);
@@ -1061,13 +1163,15 @@ static int pd_launch(const void* layer_table, int64_t n_layers, const int64_t* t
     a.samp_mode = samp_mode; a.temp = temperature; a.top_p = top_p; a.u_steps = u_steps; a.step = step; a.seq = seq; a.ld_seq = ld_seq; a.col0 = col0;
     a.tok_out = tok_out; a.logits_in = logits_in; a.n_real = (int)n_real;
     a.ln0 = ln0; a.kv_tmax = kv_tmax;
+    a.lens = lens; a.mem_len = (int)mem_len; a.rwb = rwb; a.rrb = rrb;
     { const char* e = getenv("EMO_PD_NT"); a.flags = e ? (atoi(e) & 3) : 0; }
     static_assert(LDS_TOTAL <= 96 * 1024, "LDS carve");
     const size_t lds = 96 * 1024;                                         // > half of the CU's LDS: one workgroup per CU
     EMO_CHECK(pd_supported(), "emo_performer_decode_step: this device / partition cannot hold the launch's %d workgroups at once (needs >= %d CUs with 96 KB "
               "of LDS each): use the chain of launches", PD_NG * PD_GM, PD_NG * PD_GM);
-    if (g2) hipLaunchKernelGGL(pd_step_kernel<true>, dim3(PD_NG * PD_GM), dim3(PD_NT), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(pd_step_kernel<false>, dim3(PD_NG * PD_GM), dim3(PD_NT), lds, (hipStream_t)stream, a);
+    if (form == 2) hipLaunchKernelGGL(pd_step_kernel<2>, dim3(PD_NG * PD_GM), dim3(PD_NT), lds, (hipStream_t)stream, a);
+    else if (form == 1) hipLaunchKernelGGL(pd_step_kernel<1>, dim3(PD_NG * PD_GM), dim3(PD_NT), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(pd_step_kernel<0>, dim3(PD_NG * PD_GM), dim3(PD_NT), lds, (hipStream_t)stream, a);
     EMO_LAUNCH_CHECK();
     return EMO_OK;
 }
@@ -1094,7 +1198,7 @@ extern "C" int emo_performer_decode_step_sampled(const void* layer_table, int64_
 
 // ---------------------------------------------------------------------------------------------------------------- GPT-2 form (r06)
 // The same launch for the GPT-2 backbone of BASELINE configs[3] (reference: stage2_accompaniment/model/music_gpt2.py -> HF GPT2Block, pre-LN,
-// gelu_new, no ln_f; the loop of stage2_accompaniment/inference.py:250-277): pd_step_kernel<true>.  Differences to the Performer layer, all inside the
+// gelu_new, no ln_f; the loop of stage2_accompaniment/inference.py:250-277): pd_step_kernel<1>.  Differences to the Performer layer, all inside the
 // same five edges and the same barrier sequence:
 //   * the gathered rows are the RAW residual stream; the pollers normalise them out of place (E1 -> ln_1 of the next block, E4 -> ln_2), half B adds
 //     the raw rows as residuals; layer 0's ln_1 parameters come from `ln0`, and the logits take the last block's output as it is;
@@ -1109,7 +1213,7 @@ extern "C" int emo_gpt2_decode_step(const void* layer_table, int64_t n_layers, c
                                     const void* wout_packed, const float* bout, int64_t n_token, float* logits, int64_t n_streams, int64_t d_model,
                                     int64_t n_head, int64_t d_ff, void* sync_ws, int64_t sync_ws_bytes, float ln_eps, int64_t* diag, emo_stream_t stream) {
     return pd_launch(layer_table, n_layers, tok, seg, E, Sg, pe, emb_scale, pos0, pos_ids, wout_packed, bout, n_token, logits, n_streams, d_model, n_head,
-                     PD_F, d_ff, sync_ws, sync_ws_bytes, 0.f, ln_eps, diag, 0, 1.f, 1.f, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0, stream, true, ln0,
+                     PD_F, d_ff, sync_ws, sync_ws_bytes, 0.f, ln_eps, diag, 0, 1.f, 1.f, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0, stream, 1, ln0,
                      kv_tmax);
 }
 
@@ -1120,5 +1224,37 @@ extern "C" int emo_gpt2_decode_step_sampled(const void* layer_table, int64_t n_l
                                             int64_t* step, int64_t* seq, int64_t ld_seq, int64_t col0, int64_t* tok_out, emo_stream_t stream) {
     return pd_launch(layer_table, n_layers, nullptr, seg, E, Sg, pe, emb_scale, pos0, nullptr, wout_packed, bout, n_token, logits, n_streams, d_model, n_head,
                      PD_F, d_ff, sync_ws, sync_ws_bytes, 0.f, ln_eps, nullptr, 1, temperature, top_p, u_steps, step, seq, ld_seq, col0, tok_out, logits, n_real,
-                     stream, true, ln0, kv_tmax);
+                     stream, 1, ln0, kv_tmax);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- Transformer-XL form (stage 1)
+// The same launch for the stage-1 lead-sheet model (reference: stage1_compose/model/optimus_txl_decoder.py — RelPartialLearnableDecoderLayer :526-557 =
+// RelPartialLearnableMultiHeadAttn :301-391 with pre_lnorm + PositionwiseFF :28-66, evaluation mode — stepped one token at a time by
+// PlainTransformer.generate, plain_transformer.py:52-59, in the loop of inference_utils.py:51-134): pd_step_kernel<2>, the chain of ~88 launches of
+// PlainTransformer.decode_step in one.  It is the GPT-2 form — pre-LN block, raw residual rows, head-major KV cache, no final LayerNorm — except:
+//   * embedding = word embedding x emb_scale: no positional table, no segment table;
+//   * qkv_net and o_net have no bias: the caller's table points their bias slots to zeros (fp32 accumulators start at 0.f either way);  FFN activation ReLU;
+//   * the cache row of the token is lens[s] - 1 (lens = the stream's length INCLUDING this token, read from the device, so a captured graph continues
+//     wherever the streams are; the caller advances it in front of the launch, as PlainTransformer.decode_step does), clamped to kv_tmax - 1;
+//   * P2 of (stream, head) attends over the WINDOW of cache rows max(0, lens - 1 - mem_len) .. lens - 1 with the score of relattn_decode_kernel
+//     (emo_softmax_attn.hip): ((q + r_w_bias[h]) . k_j + (q + r_r_bias[h]) . R_l[lens - 1 - j, h]) / 8; softmax and value sum as in the GPT-2 form.  The cache
+//     may be longer than the 2048 scores the LDS holds: only the window (mem_len + 1 <= 2048 rows) is scored.  R_l (bf16 [n_dist][512], row = distance)
+//     sits in the table's omega slot; rows 0 .. mem_len are read.
+// The position term is computed FIRST, as a vector of one value per window row, and the key sweep adds its content term to it; it is not folded into the
+// key sweep.  From the ISA of the GPT-2 form: the kernel allocates 162 of the 168 VGPRs that 3 waves per SIMD leave (half B's two 8-fragment sweeps are 64 of
+// them, its FFN2 fragments another 64), so a sweep that held the R rows beside the key rows (+ 32 to + 64) would either spill (each spill a vmcnt(0) in the middle of the
+// sweeps, as the note on P3's operand set says) or halve the rows in flight.  Taken first, the R rows go through the SAME registers: they are requested
+// before the q row arrives (they depend on the lengths only, and come from L2 — every stream of a head reads the same rows), each half's keys are
+// requested the moment its position terms have left the registers, and the value sum runs unchanged.  The term passes from one sweep to the other through
+// the score buffer, written and read by the same thread (window row -> thread is the same map in both sweeps), so no barrier is added.  This form
+// allocates 159 VGPRs and spills none; the instruction streams of the other two forms are those of the two-form build.
+extern "C" int emo_txl_decode_step_supported(void) { return pd_supported(); }
+
+extern "C" int emo_txl_decode_step(const void* layer_table, int64_t n_layers, const int64_t* tok, const float* E, float emb_scale, const int64_t* lens,
+                                   int64_t mem_len, int64_t n_dist, const float* r_w_bias, const float* r_r_bias, const float* ln0, int64_t kv_tmax,
+                                   const void* wout_packed, const float* bout, int64_t n_token, float* logits, int64_t n_streams, int64_t d_model,
+                                   int64_t n_head, int64_t d_ff, void* sync_ws, int64_t sync_ws_bytes, float ln_eps, int64_t* diag, emo_stream_t stream) {
+    return pd_launch(layer_table, n_layers, tok, nullptr, E, nullptr, nullptr, emb_scale, 0, nullptr, wout_packed, bout, n_token, logits, n_streams, d_model,
+                     n_head, PD_F, d_ff, sync_ws, sync_ws_bytes, 0.f, ln_eps, diag, 0, 1.f, 1.f, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0, stream, 2, ln0,
+                     kv_tmax, lens, mem_len, n_dist, r_w_bias, r_r_bias);
 }

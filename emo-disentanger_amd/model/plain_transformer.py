@@ -264,6 +264,47 @@ class TXLMemory:
         return len(self.kc) + 1
 
 
+def head_major(x, n_head):
+    """Token-major rows [n, T, H * dh] -> the head-major view [n, H, T, dh] of the same storage (no copy)."""
+    n, T, D = x.shape
+    return x.view(n, T, n_head, D // n_head).permute(0, 2, 1, 3)
+
+
+class TXLMemoryHeadMajor:
+    """TXLMemory for the one-launch token step (emo_txl_decode_step): caches [rows, H, max_len, dh], row = position, so that the keys of a
+    (stream, head) are one contiguous run.  `rows` >= n_streams: the launch works on groups of 4 streams, rows n_streams .. are its idle padding
+    (length 0, never read back); kc / vc / lens are the views of the real streams."""
+
+    def __init__(self, model, n_streams, max_len, rows=None, r_dist=None):
+        """r_dist: the R tables of a TXLMemory of the same max_len (they are the same tables: not computed twice)."""
+        ps = model._ensure_store()
+        rows = n_streams if rows is None else rows
+        assert rows >= n_streams
+        self.n, self.max_len, self.len = n_streams, max_len, 0
+        D, H, L = model.dec_d_model, model.dec_n_head, model.dec_n_layer
+        self.n_head = H
+        self.kc_all = [torch.zeros(rows, H, max_len, D // H, device=ps.device, dtype=ps.compute_dtype) for _ in range(L)]
+        self.vc_all = [torch.zeros(rows, H, max_len, D // H, device=ps.device, dtype=ps.compute_dtype) for _ in range(L)]
+        self.kc = [t[:n_streams] for t in self.kc_all]
+        self.vc = [t[:n_streams] for t in self.vc_all]
+        self.lens = torch.zeros(n_streams, device=ps.device, dtype=torch.int64)
+        self.r_dist = r_dist if r_dist is not None else model._r_by_distance(max_len)
+        assert self.r_dist[0].shape[0] >= max_len
+
+    def __len__(self):
+        return len(self.kc) + 1
+
+    def take_over(self, mem, T):
+        """The one-time hand-off from a prefill: the first T positions of the token-major TXLMemory `mem`, transposed; and its lengths."""
+        assert mem.n == self.n and T <= min(mem.max_len, self.max_len)
+        for l in range(len(self.kc)):
+            self.kc[l][:, :, :T].copy_(head_major(mem.kc[l][:, :T], self.n_head))
+            self.vc[l][:, :, :T].copy_(head_major(mem.vc[l][:, :T], self.n_head))
+        self.lens.copy_(mem.lens)
+        self.len = mem.len
+        return self
+
+
 class PlainTransformer(nn.Module):
     def __init__(self, d_word_embed, vocab_size, dec_n_layer, dec_n_head, dec_d_model, dec_d_ff, dec_mem_len, dec_tgt_len,
                  dec_dropout=0.1, dec_activation='relu', pad_index=None, pre_lnorm=False, compute_dtype=None, max_gen_len=4096):
@@ -283,6 +324,12 @@ class PlainTransformer(nn.Module):
         self._fwd_counter, self._seed = 0, int(torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF
 
     # ------------------------------------------------------------------ engine plumbing
+    # (the names the one-launch-step adapter of the decode engines, inference._EngineBase, reads from its model)
+    n_layer = property(lambda self: self.dec_n_layer)
+    n_head = property(lambda self: self.dec_n_head)
+    d_model = property(lambda self: self.dec_d_model)
+    n_token = property(lambda self: self.vocab_size)
+
     def _ensure_store(self):
         if self._store is None or not self._store.intact() or self._store.compute_dtype != self._compute_dtype:
             # (the r_net weights of all layers sit back to back: R of every layer is ONE [n_dist, L*D] product of the shared position embedding,

@@ -390,6 +390,20 @@ def gpt2_decode_step_sampled(layer_table, n_layers, seg, E, Sg, pe, emb_scale, p
     return logits
 
 
+def txl_decode_step(layer_table, n_layers, tok, E, emb_scale, lens, mem_len, n_dist, r_w_bias, r_r_bias, ln0, kv_tmax, wout_packed, bout, n_token, logits,
+                    n_streams, d_model, n_head, d_ff, sync_ws, ln_eps=1e-5, diag=None):
+    """One Transformer-XL token step of every stream in ONE persistent launch (emo_hip.h: emo_txl_decode_step)."""
+    tok, lens = _c(tok), _c(lens)
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.shape == (n_streams, n_token)
+    assert ln0.dtype == torch.float32 and ln0.is_contiguous() and ln0.numel() == 2 * d_model
+    assert lens.dtype == torch.int64 and lens.numel() == n_streams and tok.dtype == torch.int64
+    assert r_w_bias.dtype == torch.float32 and r_r_bias.dtype == torch.float32 and r_w_bias.is_contiguous() and r_r_bias.is_contiguous()
+    check(lib.emo_txl_decode_step(ptr(layer_table), n_layers, ptr(tok), ptr(E), emb_scale, ptr(lens), mem_len, n_dist, ptr(r_w_bias), ptr(r_r_bias), ptr(ln0),
+                                  kv_tmax, ptr(wout_packed), ptr(bout), n_token, ptr(logits), n_streams, d_model, n_head, d_ff,
+                                  ptr(sync_ws), sync_ws.numel() * sync_ws.element_size(), ln_eps, ptr(diag), stream()))
+    return logits
+
+
 def favor_draw_omega(gauss, omega):
     """gauss [L, nb, dh, dh] ~ N(0,1) -> omega [L, dh, n_feat/2] (orthogonal blocks scaled by row norms)."""
     L, nb, dh, _ = gauss.shape

@@ -14,7 +14,7 @@ import torch
 
 from . import ops, sampling
 from ._lib import EmoError
-from .inference import uniform_table
+from .inference import _EngineBase, uniform_table
 from .replay import StepReplayer
 from .sampling import beat_position, event_name, nucleus  # noqa: F401  (`nucleus` is looked up at call time: tests wrap it)
 
@@ -252,15 +252,115 @@ def generate_plain_xl_batch(model, event2idx, idx2event, primers, max_bars=160, 
     return results, time.time() - t0
 
 
+# ------------------------------------------------------------------------------------------------ one-launch token step
+STEPS = ('chain', 'one_launch')                     # PlainTransformer.decode_step (a chain of ~88 launches) / emo_txl_decode_step (one persistent launch)
+
+
+def one_launch_conditions(model, n_streams, device_ok=None):
+    """What emo_txl_decode_step was built for, in the order it is reported: [(description, holds)].  device_ok: the answer of
+    emo_txl_decode_step_supported() (asked here when None)."""
+    dec = model.decoder
+    if device_ok is None:
+        device_ok = ops.lib.emo_txl_decode_step_supported() == 1
+    return [('compute dtype bf16 (got %s)' % str(model._compute_dtype).replace('torch.', ''), model._compute_dtype == torch.bfloat16),
+            ('d_model 512 (got %d)' % model.dec_d_model, model.dec_d_model == 512),
+            ('8 heads (got %d)' % model.dec_n_head, model.dec_n_head == 8),
+            ('d_ff 2048 (got %d)' % model.dec_d_ff, model.dec_d_ff == 2048),
+            ('pre_lnorm', bool(dec.pre_lnorm)),
+            ('ReLU feed-forward (got %s)' % model.dec_activation, model.dec_activation == 'relu'),
+            ('at most 15 layers (got %d)' % model.dec_n_layer, model.dec_n_layer <= 15),
+            ('a vocabulary of at most 512 (got %d)' % model.vocab_size, model.vocab_size <= 512),
+            ('1 to 32 streams (got %d)' % n_streams, 1 <= n_streams <= 32),
+            ('1 <= mem_len and mem_len + 1 <= 2048 (got mem_len %d)' % model.dec_mem_len, 1 <= model.dec_mem_len <= 2047),
+            ('d_word_embed == d_model (got %d)' % model.d_word_embed, model.d_word_embed == model.dec_d_model),
+            ('a device that holds the launch: 256 compute units with 96 KB of LDS each (emo_txl_decode_step_supported)', bool(device_ok))]
+
+
+def one_launch_unsupported(model, n_streams, device_ok=None):
+    """None, or the first condition of emo_txl_decode_step this model / stream count does not meet."""
+    for what, holds in one_launch_conditions(model, n_streams, device_ok):
+        if not holds:
+            return what
+    return None
+
+
+class OneLaunchStep(_EngineBase):
+    """decode_step of n lock-step streams as ONE persistent launch (emo_txl_decode_step): the packed weights, the pointer table and the workspace
+    of the decode engines' one-launch adapter, on a head-major TXLMemory (`mem`).  take_over(prefill memory, T) is the one-time hand-off."""
+    step_entry = 'emo_txl_decode_step'
+
+    def __init__(self, model, n_streams, max_len=None, r_dist=None):
+        from .model.plain_transformer import TXLMemoryHeadMajor
+        why = one_launch_unsupported(model, n_streams)
+        if why is not None:
+            raise EmoError("step='one_launch' (emo_txl_decode_step) needs %s; use step='chain'" % why)
+        super().__init__(model, n_streams, model._max_gen_len if max_len is None else max_len)
+        ps = self.ps
+        self.n_pad = (n_streams + 3) // 4 * 4
+        self.mem = TXLMemoryHeadMajor(model, n_streams, self.max_len, rows=self.n_pad, r_dist=r_dist)
+        self.pos_dev = self.mem.lens                                 # the adapter's device positions ARE the memory's lengths
+        self.zeros = torch.zeros(3 * model.dec_d_model, device=self.dev, dtype=torch.float32)      # qkv_net / o_net have no bias
+        self._prepare_persist()
+        a0 = 'decoder.layers.0.dec_attn.layer_norm.'
+        self.persist['ln0'] = torch.cat([ps.f32(a0 + 'weight'), ps.f32(a0 + 'bias')]).contiguous()
+        self.rw, self.rr = ps.f32('decoder.r_w_bias').contiguous(), ps.f32('decoder.r_r_bias').contiguous()
+
+    def _inputs(self):
+        return self.ps.f32('word_emb.emb_lookup.weight'), None, None      # what PlainTransformer._embed passes: no segment and no positional table
+
+    def _persist_layer(self, l, t_qkv, t_one, t_ffn):
+        m, ps, pk = self.model, self.ps, self._pack_fragments
+        a, f = 'decoder.layers.%d.dec_attn.' % l, 'decoder.layers.%d.pos_ff.' % l
+        nx = 'decoder.layers.%d.dec_attn.' % (l + 1 if l + 1 < m.dec_n_layer else 0)     # (the last layer's slot is loaded and never applied)
+        return dict(wqkv=pk(ps.w(a + 'qkv_net.weight'), t_qkv, 4), bqkv=self.zeros,
+                    wo=pk(ps.w(a + 'o_net.weight'), t_one, 4), bo=self.zeros,
+                    g1=ps.f32(f + 'layer_norm.weight'), be1=ps.f32(f + 'layer_norm.bias'),
+                    w1=pk(ps.w(f + 'CoreNet.0.weight'), t_ffn, 4), b1=ps.f32(f + 'CoreNet.0.bias'),
+                    w2=pk(ps.w(f + 'CoreNet.3.weight'), t_one, 16), b2=ps.f32(f + 'CoreNet.3.bias'),
+                    g2=ps.f32(nx + 'layer_norm.weight'), be2=ps.f32(nx + 'layer_norm.bias'))
+
+    def _persist_state(self, l):
+        mem = self.mem
+        assert mem.r_dist[l].is_contiguous() and mem.r_dist[l].dtype == torch.bfloat16
+        return [mem.r_dist[l].data_ptr(), mem.kc_all[l].data_ptr(), mem.vc_all[l].data_ptr(), 0]      # (the caches live as long as the step object)
+
+    def _check_position(self, pe):
+        pass                                                         # (positions are the memory's device lengths; the cache row is clamped in the launch)
+
+    def _launch(self, tok, seg, E, Sg, pe, pos0, pos_ids, out):
+        m, pp = self.model, self.persist
+        ops.txl_decode_step(self._persist_table(), m.dec_n_layer, tok, E, float(m.word_emb.emb_scale), pos_ids, m.dec_mem_len, self.mem.r_dist[0].shape[0],
+                            self.rw, self.rr, pp['ln0'], self.max_len, pp['wout'], pp['bout'], m.vocab_size, out, self.n_pad, m.dec_d_model,
+                            m.dec_n_head, m.dec_d_ff, pp['sync'], diag=pp.get('diag'))
+
+    def take_over(self, mem, T):
+        self.mem.take_over(mem, T)
+        return self
+
+    @torch.no_grad()
+    def step(self, tok, logits_out=None):
+        """PlainTransformer.decode_step(tok, self.mem, logits_out): the lengths advance on the device in front of the launch, no host counter takes part
+        (capturable); the caller keeps every row below mem.max_len."""
+        self.mem.lens.add_(1)
+        return self._step_persistent(tok.reshape(-1), None, True, logits_out)
+
+
 class LeadSheetLoop:
     """Device state of generate_lead_sheets: a TXLMemory, the logits of the last step, the uniform table, the grammar tables and
-    per-stream parameters / state, the output sequences and the running count; one_step() = emo_txl_grammar_step + decode_step."""
+    per-stream parameters / state, the output sequences and the running count; one_step() = emo_txl_grammar_step + decode_step
+    (step='chain') or + emo_txl_decode_step (step='one_launch': OneLaunchStep on the head-major copy of the prefill's memory)."""
 
     def __init__(self, model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
-                 representation='functional', key_determine=None, seed=0):
+                 representation='functional', key_determine=None, seed=0, step='chain'):
         from .model.plain_transformer import TXLMemory
         n = self.n = len(primers)
         assert n > 0
+        if step not in STEPS:
+            raise ValueError("step must be one of %s (got %r)" % (', '.join(repr(s) for s in STEPS), step))
+        if step == 'one_launch':                                     # refused before anything is allocated; never a silent fall-back to the chain
+            why = one_launch_unsupported(model, n)
+            if why is not None:
+                raise EmoError("step='one_launch' (emo_txl_decode_step) needs %s; use step='chain'" % why)
         kw = _per_stream(n, max_bars=max_bars, max_events=max_events, prompt_bars=prompt_bars, representation=representation, key_determine=key_determine)
         self.model, self.temp, self.top_p = model, float(temp), float(top_p)
         dev = self.dev = next(model.parameters()).device
@@ -295,6 +395,10 @@ class LeadSheetLoop:
         with torch.no_grad():
             h, _, _ = model._prefill(self.seq[:, :self.L0].t(), self.mem)
             self.logits.copy_(model._logits(h.view(n, self.L0, -1)[:, -1].contiguous()))
+        self.stepper = None
+        if step == 'one_launch':
+            self.stepper = OneLaunchStep(model, n, self.max_len, r_dist=self.mem.r_dist).take_over(self.mem, self.L0)
+            self.mem = self.stepper.mem                              # (the token-major prefill memory goes)
         self.pos = self.L0                   # positions in the memory (host count: every row advances one per step)
         self.replayed = (0, 0.0)
 
@@ -304,7 +408,10 @@ class LeadSheetLoop:
 
     def one_step(self):
         self.grammar()
-        self.model.decode_step(self.tok, self.mem, logits_out=self.logits)
+        if self.stepper is not None:
+            self.stepper.step(self.tok, logits_out=self.logits)
+        else:
+            self.model.decode_step(self.tok, self.mem, logits_out=self.logits)
 
     def _live(self):
         """Running count (synchronises)."""
@@ -322,6 +429,8 @@ class LeadSheetLoop:
             if self._live() > 0:
                 self.grammar()
             torch.cuda.synchronize()
+        if self.stepper is not None:
+            self.stepper.check_persistent()                          # a launch that gave up must not pass for a result
 
     def results(self, idx2event=None):
         """-> per stream: the id list without the last id (DONE), None (STUCK), or the exception the reference loop raises."""
@@ -345,18 +454,19 @@ class LeadSheetLoop:
 
 
 def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
-                         representation='functional', key_determine=None, seed=0, use_graph=True):
+                         representation='functional', key_determine=None, seed=0, use_graph=True, step='chain'):
     """The throughput path of generate_plain_xl_batch: the same arguments and result shape, every draw and the grammar on the device
     (emo_txl_grammar_step), each token step = grammar launch + decode_step, k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS,
     default 16) and replayed until every stream has finished.  Draws come from a uniform table seeded with `seed` (like generate_streams),
     so the ids are not NumPy-RNG-identical to the reference; they equal the host grammar driven by the same device draws.
+    step='one_launch' runs the model step as one persistent launch (emo_txl_decode_step) and raises EmoError where it was not built for the model.
     -> (results, seconds)."""
     was_training = model.training
     model.eval()
     t0 = time.time()
     try:
         loop = LeadSheetLoop(model, event2idx, idx2event, primers, max_bars=max_bars, max_events=max_events, temp=temp, top_p=top_p,
-                             prompt_bars=prompt_bars, representation=representation, key_determine=key_determine, seed=seed)
+                             prompt_bars=prompt_bars, representation=representation, key_determine=key_determine, seed=seed, step=step)
         loop.run(use_graph=use_graph)
         out = loop.results()
     finally:
@@ -382,15 +492,9 @@ def read_vocab(vocab_file):
     return event2idx, idx2event, pad + 1
 
 
-def main(argv=None):
-    """Same flags as the reference's stage-1 inference.py (-c -r -m -i -o -n): n_groups pieces for each emotion of the mode, key_determine
-    'rule', max_bars 128, written as samp_XX_<emotion>_roman.txt (functional) / samp_XX_<emotion>.txt (remi) without the emotion tag — the
-    files the stage-2 command line (inference.main) reads.  All jobs run --streams at a time through generate_lead_sheets (device draws and
-    grammar); --exact runs them through generate_plain_xl_batch (NumPy sampling, seeds 0, 1, ... in job order).  MIDI output (miditoolkit,
-    relative2absolute) is not part of this package."""
+def parse_args(argv=None):
+    """The command line of main()."""
     import argparse
-    import yaml
-    from .model.plain_transformer import PlainTransformer
     ap = argparse.ArgumentParser(description='stage-1 lead-sheet generation on MI355X')
     req = ap.add_argument_group('required arguments')
     req.add_argument('-c', '--configuration', required=True, help='a stage-1 YAML (stage1_compose/config keys)')
@@ -404,7 +508,20 @@ def main(argv=None):
     ap.add_argument('--dtype', default=None, choices=[None, 'bf16', 'fp32'])
     ap.add_argument('--exact', action='store_true', help='NumPy sampling and grammar on the host (reference-exact per seed) instead of the device loop')
     ap.add_argument('--seed', type=int, default=0, help='seed of the device uniform table (the group of streams j uses seed + j)')
-    args = ap.parse_args(argv)
+    ap.add_argument('--step', default='chain', choices=['chain', 'one-launch'],
+                    help='the model step of the device loop: the chain of launches of decode_step, or one persistent launch (emo_txl_decode_step)')
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    """Same flags as the reference's stage-1 inference.py (-c -r -m -i -o -n): n_groups pieces for each emotion of the mode, key_determine
+    'rule', max_bars 128, written as samp_XX_<emotion>_roman.txt (functional) / samp_XX_<emotion>.txt (remi) without the emotion tag — the
+    files the stage-2 command line (inference.main) reads.  All jobs run --streams at a time through generate_lead_sheets (device draws and
+    grammar; --step one-launch: the model step as one persistent launch); --exact runs them through generate_plain_xl_batch (NumPy sampling, seeds 0, 1, ... in job order).  MIDI output (miditoolkit,
+    relative2absolute) is not part of this package."""
+    import yaml
+    from .model.plain_transformer import PlainTransformer
+    args = parse_args(argv)
     conf = yaml.load(open(args.configuration), Loader=yaml.FullLoader)
     mode = MODES[args.mode]
     max_bars, key_determine = 128, 'rule'
@@ -437,7 +554,7 @@ def main(argv=None):
         if args.exact:
             res, sec = generate_plain_xl_batch(model, event2idx, idx2event, primers, seeds=list(range(i, i + len(group))), **kw)
         else:
-            res, sec = generate_lead_sheets(model, event2idx, idx2event, primers, seed=args.seed + j, **kw)
+            res, sec = generate_lead_sheets(model, event2idx, idx2event, primers, seed=args.seed + j, step=args.step.replace('-', '_'), **kw)
         times.append(sec)
         for (out, _), ids in zip(group, res):
             if ids is None or isinstance(ids, Exception):

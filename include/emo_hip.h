@@ -290,6 +290,28 @@ int emo_gpt2_decode_step_sampled(const void* layer_table, int64_t n_layers, cons
                                  void* sync_ws, int64_t sync_ws_bytes, float ln_eps, float temperature, float top_p, const float* u_steps,
                                  int64_t* step, int64_t* seq, int64_t ld_seq, int64_t col0, int64_t* tok_out, emo_stream_t stream);
 
+/* ONE-LAUNCH Transformer-XL decode step (stage 1): the same persistent launch for the lead-sheet model — one token of every stream through
+ * stage1_compose/model/plain_transformer.py:52-59 (PlainTransformer.generate, one-token call) -> optimus_txl_decoder.py:750-925 with attn_type 0:
+ * word embedding x emb_scale (:788), n_layers RelPartialLearnableDecoderLayer (:526-557: relative-position attention :301-391 with pre_lnorm over the
+ * last mem_len cached positions, PositionwiseFF :28-66, evaluation mode) -> dec_out_proj; the token step of the sampling loop of
+ * stage1_compose/inference_utils.py:51-134.  d_model 512 / 8 heads / d_ff 2048, n_layers <= 15, n_token <= 512, n_streams <= 32 (a multiple of 4), bf16.
+ * Arguments as emo_gpt2_decode_step, except:
+ *   layer_table : [n_layers][16] pointers: qkv_net packed, ZEROS (f32 [3 d]: qkv_net has no bias), o_net packed, ZEROS (f32 [d]), pos_ff.layer_norm
+ *                 gamma, beta, CoreNet.0 packed, bias, CoreNet.3 packed, bias, dec_attn.layer_norm gamma, beta OF THE NEXT LAYER (any valid pointer
+ *                 for the last one), R_l = r_net_l(pos_emb) (bf16 [n_dist][512], row = distance), K cache, V cache, unused.
+ *                 K / V cache: bf16 [n_streams][8][kv_tmax][64], row = position; kv_tmax is NOT bounded by the 2048-entry score buffer.
+ *   tok, E      : int64 [n_streams], f32 [n_token][512]; there is no positional and no segment table
+ *   lens        : int64 [n_streams] ON THE DEVICE: the length of each stream INCLUDING this token (the caller advances it in front of the launch);
+ *                 the step appends the token's key / value row at index min(lens[s] - 1, kv_tmax - 1) and attends over rows
+ *                 max(0, lens[s] - 1 - mem_len) .. lens[s] - 1 with the score ((q + r_w_bias[h]) . k_j + (q + r_r_bias[h]) . R_l[lens[s] - 1 - j, h]) / 8
+ *   mem_len     : 1 <= mem_len, mem_len + 1 <= 2048;  n_dist >= min(mem_len, kv_tmax - 1) + 1
+ *   r_w_bias, r_r_bias : f32 [8][64];  ln0 : f32 [2][512]: gamma | beta of layer 0's dec_attn.layer_norm. */
+int emo_txl_decode_step_supported(void);
+int emo_txl_decode_step(const void* layer_table, int64_t n_layers, const int64_t* tok, const float* E, float emb_scale, const int64_t* lens,
+                        int64_t mem_len, int64_t n_dist, const float* r_w_bias, const float* r_r_bias, const float* ln0, int64_t kv_tmax,
+                        const void* wout_packed, const float* bout, int64_t n_token, float* logits, int64_t n_streams, int64_t d_model,
+                        int64_t n_head, int64_t d_ff, void* sync_ws, int64_t sync_ws_bytes, float ln_eps, int64_t* diag, emo_stream_t stream);
+
 /* FAVOR+ omega draw (fast-transformers orthogonal_random_matrix_, called from new_feature_map() on every
  * forward — SURVEY F8): gauss [n_layers, ceil((n_feat/2)/dh), dh, dh] ~ N(0,1) from the caller's RNG ->
  * omega [n_layers, dh, n_feat/2] with orthogonal columns per block scaled by the row norms of the block. */
