@@ -30,6 +30,17 @@ class Epilogue(ctypes.Structure):
                 ('lna_gamma', c_p), ('lna_beta', c_p), ('lna_out', c_p), ('lna_mean', c_p), ('lna_rstd', c_p), ('hdiv', c_p), ('hdiv_T', c_l)]
 
 
+class DecodeStep(ctypes.Structure):
+    """emo_decode_step_t (emo_hip.h), field for field: the argument block of the one-launch token step.  Pointer fields hold raw device addresses."""
+    _fields_ = [('form', ctypes.c_int32), ('sampled', ctypes.c_int32), ('layer_table', c_p), ('n_layers', c_l),
+                ('tok', c_p), ('seg', c_p), ('E', c_p), ('Sg', c_p), ('pe', c_p), ('emb_scale', c_f), ('pos0', c_l), ('pos_ids', c_p),
+                ('wout_packed', c_p), ('bout', c_p), ('n_token', c_l), ('logits', c_p),
+                ('n_streams', c_l), ('n_real', c_l), ('d_model', c_l), ('n_head', c_l), ('n_feat', c_l), ('d_ff', c_l),
+                ('sync_ws', c_p), ('sync_ws_bytes', c_l), ('eps', c_f), ('ln_eps', c_f), ('diag', c_p),
+                ('temperature', c_f), ('top_p', c_f), ('u_steps', c_p), ('step', c_p), ('seq', c_p), ('ld_seq', c_l), ('col0', c_l), ('tok_out', c_p),
+                ('ln0', c_p), ('kv_tmax', c_l), ('lens', c_p), ('mem_len', c_l), ('n_dist', c_l), ('r_w_bias', c_p), ('r_r_bias', c_p)]
+
+
 _SIG = {
     'emo_version': (c_i, []),
     'emo_build_flags': (c_i, []),
@@ -56,17 +67,10 @@ _SIG = {
     'emo_favor_attn_bwd_dn_supported': (c_i, [c_i, c_l, c_l, c_l, c_l, c_l]),
     'emo_favor_attn_bwd_dn': (c_i, [c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_l, c_i, c_l, c_l, c_l, c_l, c_l, c_f, c_p]),
     'emo_favor_decode_step': (c_i, [c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_l, c_i, c_l, c_l, c_l, c_l, c_f, c_p]),
-    'emo_performer_decode_step_workspace_bytes': (c_l, []),
-    'emo_performer_decode_step_supported': (c_i, []),
-    'emo_performer_decode_step': (c_i, [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_f, c_l, c_p, c_p, c_p, c_l, c_p, c_l, c_l, c_l, c_l, c_l, c_p, c_l, c_f, c_f, c_p, c_p]),
-    'emo_performer_decode_step_sampled': (c_i, [c_p, c_l, c_p, c_p, c_p, c_p, c_f, c_l, c_p, c_p, c_l, c_p, c_l, c_l, c_l, c_l, c_l, c_l, c_p, c_l, c_f, c_f,
-                                                c_f, c_f, c_p, c_p, c_p, c_l, c_l, c_p, c_p]),
-    'emo_gpt2_decode_step_supported': (c_i, []),
-    'emo_gpt2_decode_step': (c_i, [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_f, c_l, c_p, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_l, c_l, c_l, c_p, c_l, c_f, c_p, c_p]),
-    'emo_gpt2_decode_step_sampled': (c_i, [c_p, c_l, c_p, c_p, c_p, c_p, c_f, c_l, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_l, c_l, c_l, c_l, c_p, c_l, c_f,
-                                           c_f, c_f, c_p, c_p, c_p, c_l, c_l, c_p, c_p]),
-    'emo_txl_decode_step_supported': (c_i, []),
-    'emo_txl_decode_step': (c_i, [c_p, c_l, c_p, c_p, c_f, c_p, c_l, c_l, c_p, c_p, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_l, c_l, c_l, c_p, c_l, c_f, c_p, c_p]),
+    'emo_decode_step_size': (c_i, []),
+    'emo_decode_step_workspace_bytes': (c_l, []),
+    'emo_decode_step_supported': (c_i, []),
+    'emo_decode_step': (c_i, [ctypes.POINTER(DecodeStep), c_p]),
     'emo_favor_draw_omega': (c_i, [c_p, c_p, c_l, c_l, c_l, c_p]),
     'emo_softmax_attn_fwd': (c_i, [c_p, c_p, c_p, c_l, c_p, c_l, c_p, c_i, c_l, c_l, c_l, c_l, c_f, c_u64, c_u64, c_p]),
     'emo_softmax_attn_bwd': (c_i, [c_p, c_p, c_p, c_l, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_l, c_l, c_l, c_l, c_f, c_u64, c_u64, c_p]),
@@ -114,6 +118,9 @@ for _name, (_res, _args) in _SIG.items():
 if lib.emo_epilogue_size() != ctypes.sizeof(Epilogue):      # a stale libemo_hip.so (or a stale mirror above) would read garbage pointers
     raise ImportError('libemo_hip.so was built with an emo_epilogue_t of %d bytes, this binding has %d: rebuild (python -c "import __graft_entry__ as g; g.build()")'
                       % (lib.emo_epilogue_size(), ctypes.sizeof(Epilogue)))
+if lib.emo_decode_step_size() != ctypes.sizeof(DecodeStep):
+    raise ImportError('libemo_hip.so was built with an emo_decode_step_t of %d bytes, this binding has %d: rebuild (python -c "import __graft_entry__ as g; g.build()")'
+                      % (lib.emo_decode_step_size(), ctypes.sizeof(DecodeStep)))
 
 
 class EmoError(RuntimeError):

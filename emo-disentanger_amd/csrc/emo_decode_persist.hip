@@ -1099,106 +1099,13 @@ __global__ __launch_bounds__(PD_NT, 3) void pd_step_kernel(PdArgs a) {
 }
 }  // namespace
 
-extern "C" int64_t emo_performer_decode_step_workspace_bytes(void) { return (int64_t)PD_WS_WORDS * 8; }
+extern "C" int64_t emo_decode_step_workspace_bytes(void) { return (int64_t)PD_WS_WORDS * 8; }
+extern "C" int emo_decode_step_size(void) { return (int)sizeof(emo_decode_step_t); }
 
-// The launch is PD_NG * PD_GM = 256 workgroups that spin-wait on each other: all of them must be resident at once, one per CU.  Checked once per
-// process: the 96-KB dynamic LDS attribute could be set, the device has at least 256 CUs (partition modes / CU masks have fewer), and the
-// occupancy query grants the kernel a workgroup per CU.  (Another process holding CUs cannot be seen from here: that case is the 50-ms give-up
-// code in the workspace, emo_performer_decode_step's documented failure mode.)
-static int pd_supported() {
-    static int cached = -1;
-    if (cached >= 0) return cached;
-    const size_t lds = 96 * 1024;
-    int dev = 0, cus = 0, per_cu = 0;
-    bool ok = hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus >= PD_NG * PD_GM;
-    ok = ok && hipFuncSetAttribute((const void*)pd_step_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-    ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)pd_step_kernel<0>, PD_NT, lds) == hipSuccess && per_cu >= 1;
-    ok = ok && hipFuncSetAttribute((const void*)pd_step_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-    ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)pd_step_kernel<1>, PD_NT, lds) == hipSuccess && per_cu >= 1;
-    ok = ok && hipFuncSetAttribute((const void*)pd_step_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-    ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)pd_step_kernel<2>, PD_NT, lds) == hipSuccess && per_cu >= 1;
-    (void)hipGetLastError();
-    cached = ok ? 1 : 0;
-    return cached;
-}
-extern "C" int emo_performer_decode_step_supported(void) { return pd_supported(); }
-
-static int pd_launch(const void* layer_table, int64_t n_layers, const int64_t* tok, const int64_t* seg, const float* E, const float* Sg, const float* pe,
-                     float emb_scale, int64_t pos0, const int64_t* pos_ids, const void* wout_packed, const float* bout, int64_t n_token, float* logits,
-                     int64_t n_streams, int64_t d_model, int64_t n_head, int64_t n_feat, int64_t d_ff, void* sync_ws, int64_t sync_ws_bytes, float eps,
-                     float ln_eps, int64_t* diag, int samp_mode, float temperature, float top_p, const float* u_steps, int64_t* step, int64_t* seq,
-                     int64_t ld_seq, int64_t col0, int64_t* tok_out, const float* logits_in, int64_t n_real, emo_stream_t stream, int form = 0,
-                     const float* ln0 = nullptr, int64_t kv_tmax = 0, const int64_t* lens = nullptr, int64_t mem_len = 0, int64_t n_dist = 0,
-                     const float* rwb = nullptr, const float* rrb = nullptr) {
-    EMO_CHECK(layer_table && E && (pe || form == 2) && wout_packed && bout && logits && sync_ws, "emo_performer_decode_step: null pointer");
-    if (form == 1) EMO_CHECK(ln0 && kv_tmax >= 1 && kv_tmax <= 2048, "emo_gpt2_decode_step: needs layer 0's ln_1 parameters and a KV cache of <= 2048 rows per (stream, head)");
-    if (form == 2) {
-        // the score buffer holds the window's mem_len cached rows + the token's own: mem_len + 1 <= 2048; the CACHE may be longer (row = position)
-        EMO_CHECK(ln0 && lens && rwb && rrb, "emo_txl_decode_step: null pointer");
-        EMO_CHECK(mem_len >= 1 && mem_len + 1 <= 2048, "emo_txl_decode_step: 1 <= mem_len and mem_len + 1 <= 2048 (got mem_len %lld)", (long long)mem_len);
-        EMO_CHECK(kv_tmax >= 1 && kv_tmax <= ((int64_t)1 << 24), "emo_txl_decode_step: bad kv_tmax %lld", (long long)kv_tmax);
-        EMO_CHECK(n_dist >= (mem_len < kv_tmax - 1 ? mem_len : kv_tmax - 1) + 1,
-                  "emo_txl_decode_step: the R tables have %lld rows, the window reaches distance %lld", (long long)n_dist,
-                  (long long)(mem_len < kv_tmax - 1 ? mem_len : kv_tmax - 1));
-    }
-    EMO_CHECK(d_model == PD_D && n_head == PD_H && n_feat == PD_F && d_ff == PD_FF,
-              "emo_performer_decode_step: built for d_model 512 / 8 heads / 128 features / d_ff 2048 (got %lld / %lld / %lld / %lld)", (long long)d_model,
-              (long long)n_head, (long long)n_feat, (long long)d_ff);
-    EMO_CHECK(n_layers >= 1 && n_layers <= PD_MAX_LAYERS, "emo_performer_decode_step: 1 <= n_layers <= %d", PD_MAX_LAYERS);
-    EMO_CHECK(n_streams >= PD_GS && n_streams <= PD_GS * PD_NG && n_streams % PD_GS == 0, "emo_performer_decode_step: n_streams must be a multiple of 4, <= 32");
-    EMO_CHECK(n_token >= 1 && n_token <= 16 * PD_GM, "emo_performer_decode_step: n_token <= 512");
-    EMO_CHECK(!(seg && !Sg), "emo_performer_decode_step: seg ids without a segment table");
-    EMO_CHECK(sync_ws_bytes >= (int64_t)PD_WS_WORDS * 8 && ((uintptr_t)sync_ws & 15) == 0, "emo_performer_decode_step: workspace too small / unaligned");
-    if (samp_mode) {
-        EMO_CHECK(u_steps && step && tok_out && logits_in && n_real >= 1 && n_real <= n_streams && temperature > 0.f && n_token <= 1024,
-                  "emo_performer_decode_step_sampled: bad sampling arguments");
-    } else {
-        EMO_CHECK(tok, "emo_performer_decode_step: null token pointer");
-    }
-    PdArgs a;
-    a.layers = (const PdLayer*)layer_table; a.n_layers = (int)n_layers;
-    a.tok = tok; a.seg = seg; a.E = E; a.Sg = Sg; a.pe = pe; a.emb_scale = emb_scale; a.pos0 = pos0; a.pos_ids = pos_ids;
-    a.wout = (const bf16_t*)wout_packed; a.bout = bout; a.n_token = (int)n_token; a.logits = logits; a.n_streams = (int)n_streams;
-    a.sync = (u64*)sync_ws; a.eps = eps; a.ln_eps = ln_eps; a.diag = (u64*)diag;
-    a.samp_mode = samp_mode; a.temp = temperature; a.top_p = top_p; a.u_steps = u_steps; a.step = step; a.seq = seq; a.ld_seq = ld_seq; a.col0 = col0;
-    a.tok_out = tok_out; a.logits_in = logits_in; a.n_real = (int)n_real;
-    a.ln0 = ln0; a.kv_tmax = kv_tmax;
-    a.lens = lens; a.mem_len = (int)mem_len; a.rwb = rwb; a.rrb = rrb;
-    { const char* e = getenv("EMO_PD_NT"); a.flags = e ? (atoi(e) & 3) : 0; }
-    static_assert(LDS_TOTAL <= 96 * 1024, "LDS carve");
-    const size_t lds = 96 * 1024;                                         // > half of the CU's LDS: one workgroup per CU
-    EMO_CHECK(pd_supported(), "emo_performer_decode_step: this device / partition cannot hold the launch's %d workgroups at once (needs >= %d CUs with 96 KB "
-              "of LDS each): use the chain of launches", PD_NG * PD_GM, PD_NG * PD_GM);
-    if (form == 2) hipLaunchKernelGGL(pd_step_kernel<2>, dim3(PD_NG * PD_GM), dim3(PD_NT), lds, (hipStream_t)stream, a);
-    else if (form == 1) hipLaunchKernelGGL(pd_step_kernel<1>, dim3(PD_NG * PD_GM), dim3(PD_NT), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(pd_step_kernel<0>, dim3(PD_NG * PD_GM), dim3(PD_NT), lds, (hipStream_t)stream, a);
-    EMO_LAUNCH_CHECK();
-    return EMO_OK;
-}
-
-extern "C" int emo_performer_decode_step(const void* layer_table, int64_t n_layers, const int64_t* tok, const int64_t* seg, const float* E, const float* Sg,
-                                         const float* pe, float emb_scale, int64_t pos0, const int64_t* pos_ids, const void* wout_packed,
-                                         const float* bout, int64_t n_token, float* logits, int64_t n_streams, int64_t d_model, int64_t n_head,
-                                         int64_t n_feat, int64_t d_ff, void* sync_ws, int64_t sync_ws_bytes, float eps, float ln_eps,
-                                         int64_t* diag, emo_stream_t stream) {
-    return pd_launch(layer_table, n_layers, tok, seg, E, Sg, pe, emb_scale, pos0, pos_ids, wout_packed, bout, n_token, logits, n_streams, d_model, n_head,
-                     n_feat, d_ff, sync_ws, sync_ws_bytes, eps, ln_eps, diag, 0, 1.f, 1.f, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0, stream);
-}
-
-extern "C" int emo_performer_decode_step_sampled(const void* layer_table, int64_t n_layers, const int64_t* seg, const float* E, const float* Sg,
-                                                 const float* pe, float emb_scale, int64_t pos0, const void* wout_packed, const float* bout,
-                                                 int64_t n_token, float* logits, int64_t n_streams, int64_t n_real, int64_t d_model, int64_t n_head,
-                                                 int64_t n_feat, int64_t d_ff, void* sync_ws, int64_t sync_ws_bytes, float eps, float ln_eps,
-                                                 float temperature, float top_p, const float* u_steps, int64_t* step, int64_t* seq, int64_t ld_seq,
-                                                 int64_t col0, int64_t* tok_out, emo_stream_t stream) {
-    return pd_launch(layer_table, n_layers, nullptr, seg, E, Sg, pe, emb_scale, pos0, nullptr, wout_packed, bout, n_token, logits, n_streams, d_model, n_head,
-                     n_feat, d_ff, sync_ws, sync_ws_bytes, eps, ln_eps, nullptr, 1, temperature, top_p, u_steps, step, seq, ld_seq, col0, tok_out, logits,
-                     n_real, stream);
-}
-
-// ---------------------------------------------------------------------------------------------------------------- GPT-2 form (r06)
-// The same launch for the GPT-2 backbone of BASELINE configs[3] (reference: stage2_accompaniment/model/music_gpt2.py -> HF GPT2Block, pre-LN,
-// gelu_new, no ln_f; the loop of stage2_accompaniment/inference.py:250-277): pd_step_kernel<1>.  Differences to the Performer layer, all inside the
+// The three forms of the launch (emo_decode_step_t.form), their names in messages, and the notes on the two that were added to the first:
+//
+// GPT-2 form (r06) — the same launch for the GPT-2 backbone of BASELINE configs[3] (reference: stage2_accompaniment/model/music_gpt2.py -> HF GPT2Block,
+// pre-LN, gelu_new, no ln_f; the loop of stage2_accompaniment/inference.py:250-277): pd_step_kernel<1>.  Differences to the Performer layer, all inside the
 // same five edges and the same barrier sequence:
 //   * the gathered rows are the RAW residual stream; the pollers normalise them out of place (E1 -> ln_1 of the next block, E4 -> ln_2), half B adds
 //     the raw rows as residuals; layer 0's ln_1 parameters come from `ln0`, and the logits take the last block's output as it is;
@@ -1206,32 +1113,11 @@ extern "C" int emo_performer_decode_step_sampled(const void* layer_table, int64_
 //     value row at index pos (= keys already cached; pos = pos0 + pos_ids[stream], or the sampler's counter) and reads the rows before it — the
 //     table's S / z slots hold the K / V cache of the layer, the omega slot is unused;
 //   * the table's g1 / be1 are ln_2 of the block, g2 / be2 are ln_1 of the NEXT block (any valid pointer for the last one); FFN activation gelu_new.
-extern "C" int emo_gpt2_decode_step_supported(void) { return pd_supported(); }
-
-extern "C" int emo_gpt2_decode_step(const void* layer_table, int64_t n_layers, const int64_t* tok, const int64_t* seg, const float* E, const float* Sg,
-                                    const float* pe, float emb_scale, int64_t pos0, const int64_t* pos_ids, const float* ln0, int64_t kv_tmax,
-                                    const void* wout_packed, const float* bout, int64_t n_token, float* logits, int64_t n_streams, int64_t d_model,
-                                    int64_t n_head, int64_t d_ff, void* sync_ws, int64_t sync_ws_bytes, float ln_eps, int64_t* diag, emo_stream_t stream) {
-    return pd_launch(layer_table, n_layers, tok, seg, E, Sg, pe, emb_scale, pos0, pos_ids, wout_packed, bout, n_token, logits, n_streams, d_model, n_head,
-                     PD_F, d_ff, sync_ws, sync_ws_bytes, 0.f, ln_eps, diag, 0, 1.f, 1.f, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0, stream, 1, ln0,
-                     kv_tmax);
-}
-
-extern "C" int emo_gpt2_decode_step_sampled(const void* layer_table, int64_t n_layers, const int64_t* seg, const float* E, const float* Sg, const float* pe,
-                                            float emb_scale, int64_t pos0, const float* ln0, int64_t kv_tmax, const void* wout_packed, const float* bout,
-                                            int64_t n_token, float* logits, int64_t n_streams, int64_t n_real, int64_t d_model, int64_t n_head, int64_t d_ff,
-                                            void* sync_ws, int64_t sync_ws_bytes, float ln_eps, float temperature, float top_p, const float* u_steps,
-                                            int64_t* step, int64_t* seq, int64_t ld_seq, int64_t col0, int64_t* tok_out, emo_stream_t stream) {
-    return pd_launch(layer_table, n_layers, nullptr, seg, E, Sg, pe, emb_scale, pos0, nullptr, wout_packed, bout, n_token, logits, n_streams, d_model, n_head,
-                     PD_F, d_ff, sync_ws, sync_ws_bytes, 0.f, ln_eps, nullptr, 1, temperature, top_p, u_steps, step, seq, ld_seq, col0, tok_out, logits, n_real,
-                     stream, 1, ln0, kv_tmax);
-}
-
-// ---------------------------------------------------------------------------------------------------------------- Transformer-XL form (stage 1)
-// The same launch for the stage-1 lead-sheet model (reference: stage1_compose/model/optimus_txl_decoder.py — RelPartialLearnableDecoderLayer :526-557 =
-// RelPartialLearnableMultiHeadAttn :301-391 with pre_lnorm + PositionwiseFF :28-66, evaluation mode — stepped one token at a time by
-// PlainTransformer.generate, plain_transformer.py:52-59, in the loop of inference_utils.py:51-134): pd_step_kernel<2>, the chain of ~88 launches of
-// PlainTransformer.decode_step in one.  It is the GPT-2 form — pre-LN block, raw residual rows, head-major KV cache, no final LayerNorm — except:
+//
+// Transformer-XL form (stage 1) — the same launch for the stage-1 lead-sheet model (reference: stage1_compose/model/optimus_txl_decoder.py —
+// RelPartialLearnableDecoderLayer :526-557 = RelPartialLearnableMultiHeadAttn :301-391 with pre_lnorm + PositionwiseFF :28-66, evaluation mode — stepped one
+// token at a time by PlainTransformer.generate, plain_transformer.py:52-59, in the loop of inference_utils.py:51-134): pd_step_kernel<2>, the chain of ~88
+// launches of PlainTransformer.decode_step in one.  It is the GPT-2 form — pre-LN block, raw residual rows, head-major KV cache, no final LayerNorm — except:
 //   * embedding = word embedding x emb_scale: no positional table, no segment table;
 //   * qkv_net and o_net have no bias: the caller's table points their bias slots to zeros (fp32 accumulators start at 0.f either way);  FFN activation ReLU;
 //   * the cache row of the token is lens[s] - 1 (lens = the stream's length INCLUDING this token, read from the device, so a captured graph continues
@@ -1248,13 +1134,92 @@ extern "C" int emo_gpt2_decode_step_sampled(const void* layer_table, int64_t n_l
 // requested the moment its position terms have left the registers, and the value sum runs unchanged.  The term passes from one sweep to the other through
 // the score buffer, written and read by the same thread (window row -> thread is the same map in both sweeps), so no barrier is added.  This form
 // allocates 159 VGPRs and spills none; the instruction streams of the other two forms are those of the two-form build.
-extern "C" int emo_txl_decode_step_supported(void) { return pd_supported(); }
+typedef void (*pd_kernel_t)(PdArgs);
+static const struct { pd_kernel_t kernel; const char* name; const char* name_sampled; } pd_forms[3] = {
+    {pd_step_kernel<0>, "emo_decode_step[performer]", "emo_decode_step[performer, sampled]"},
+    {pd_step_kernel<1>, "emo_decode_step[gpt2]", "emo_decode_step[gpt2, sampled]"},
+    {pd_step_kernel<2>, "emo_decode_step[txl]", "emo_decode_step[txl, sampled]"}};
+static const size_t PD_LDS_BYTES = 96 * 1024;                             // > half of the CU's LDS: one workgroup per CU
 
-extern "C" int emo_txl_decode_step(const void* layer_table, int64_t n_layers, const int64_t* tok, const float* E, float emb_scale, const int64_t* lens,
-                                   int64_t mem_len, int64_t n_dist, const float* r_w_bias, const float* r_r_bias, const float* ln0, int64_t kv_tmax,
-                                   const void* wout_packed, const float* bout, int64_t n_token, float* logits, int64_t n_streams, int64_t d_model,
-                                   int64_t n_head, int64_t d_ff, void* sync_ws, int64_t sync_ws_bytes, float ln_eps, int64_t* diag, emo_stream_t stream) {
-    return pd_launch(layer_table, n_layers, tok, nullptr, E, nullptr, nullptr, emb_scale, 0, nullptr, wout_packed, bout, n_token, logits, n_streams, d_model,
-                     n_head, PD_F, d_ff, sync_ws, sync_ws_bytes, 0.f, ln_eps, diag, 0, 1.f, 1.f, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0, stream, 2, ln0,
-                     kv_tmax, lens, mem_len, n_dist, r_w_bias, r_r_bias);
+// The launch is PD_NG * PD_GM = 256 workgroups that spin-wait on each other: all of them must be resident at once, one per CU.  Checked once per
+// process: the 96-KB dynamic LDS attribute could be set, the device has at least 256 CUs (partition modes / CU masks have fewer), and the
+// occupancy query grants every form's kernel a workgroup per CU.  (Another process holding CUs cannot be seen from here: that case is the 50-ms give-up
+// code in the workspace, emo_decode_step's documented failure mode.)
+static int pd_supported() {
+    static int cached = -1;
+    if (cached >= 0) return cached;
+    int dev = 0, cus = 0, per_cu = 0;
+    bool ok = hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus >= PD_NG * PD_GM;
+    for (const auto& f : pd_forms) {
+        ok = ok && hipFuncSetAttribute((const void*)f.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PD_LDS_BYTES) == hipSuccess;
+        ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)f.kernel, PD_NT, PD_LDS_BYTES) == hipSuccess && per_cu >= 1;
+    }
+    (void)hipGetLastError();
+    cached = ok ? 1 : 0;
+    return cached;
+}
+extern "C" int emo_decode_step_supported(void) { return pd_supported(); }
+
+static int pd_launch(const emo_decode_step_t& s, emo_stream_t stream) {
+    EMO_CHECK(s.form >= 0 && s.form <= 2, "emo_decode_step: form %d is none of 0 (Performer), 1 (GPT-2), 2 (Transformer-XL)", (int)s.form);
+    const int form = s.form;
+    const bool sampled = s.sampled != 0;
+    const char* const name = sampled ? pd_forms[form].name_sampled : pd_forms[form].name;
+    // what each form / mode takes from the block, in one place: everything below reads these, never the fields themselves
+    const bool tx = form == 2;
+    const int64_t* tok = sampled ? nullptr : s.tok;                       // sampled: the launch draws the tokens from `logits` and counts positions in `step`
+    const int64_t* pos_ids = sampled || tx ? nullptr : s.pos_ids;
+    const float* logits_in = sampled ? s.logits : nullptr;
+    const int64_t* seg = tx ? nullptr : s.seg;                            // Transformer-XL: word embedding only, positions are `lens`
+    const float *Sg = tx ? nullptr : s.Sg, *pe = tx ? nullptr : s.pe;
+    const int64_t pos0 = tx ? 0 : s.pos0;
+    const int64_t n_feat = form == 0 ? s.n_feat : PD_F;                   // the FAVOR+ fields are the Performer's
+    const float eps = form == 0 ? s.eps : 0.f;
+    EMO_CHECK(s.layer_table && s.E && (pe || tx) && s.wout_packed && s.bout && s.logits && s.sync_ws, "%s: null pointer", name);
+    if (form == 1)
+        EMO_CHECK(s.ln0 && s.kv_tmax >= 1 && s.kv_tmax <= 2048, "%s: needs layer 0's ln_1 parameters and a KV cache of <= 2048 rows per (stream, head)", name);
+    if (tx) {
+        // the score buffer holds the window's mem_len cached rows + the token's own: mem_len + 1 <= 2048; the CACHE may be longer (row = position)
+        EMO_CHECK(!sampled, "%s: this form has no sampled step", name);
+        EMO_CHECK(s.ln0 && s.lens && s.r_w_bias && s.r_r_bias, "%s: null pointer", name);
+        EMO_CHECK(s.mem_len >= 1 && s.mem_len + 1 <= 2048, "%s: 1 <= mem_len and mem_len + 1 <= 2048 (got mem_len %lld)", name, (long long)s.mem_len);
+        EMO_CHECK(s.kv_tmax >= 1 && s.kv_tmax <= ((int64_t)1 << 24), "%s: bad kv_tmax %lld", name, (long long)s.kv_tmax);
+        const int64_t reach = s.mem_len < s.kv_tmax - 1 ? s.mem_len : s.kv_tmax - 1;
+        EMO_CHECK(s.n_dist >= reach + 1, "%s: the R tables have %lld rows, the window reaches distance %lld", name, (long long)s.n_dist, (long long)reach);
+    }
+    EMO_CHECK(s.d_model == PD_D && s.n_head == PD_H && n_feat == PD_F && s.d_ff == PD_FF,
+              "%s: built for d_model 512 / 8 heads / 128 features / d_ff 2048 (got %lld / %lld / %lld / %lld)", name, (long long)s.d_model,
+              (long long)s.n_head, (long long)n_feat, (long long)s.d_ff);
+    EMO_CHECK(s.n_layers >= 1 && s.n_layers <= PD_MAX_LAYERS, "%s: 1 <= n_layers <= %d", name, PD_MAX_LAYERS);
+    EMO_CHECK(s.n_streams >= PD_GS && s.n_streams <= PD_GS * PD_NG && s.n_streams % PD_GS == 0, "%s: n_streams must be a multiple of 4, <= 32", name);
+    EMO_CHECK(s.n_token >= 1 && s.n_token <= 16 * PD_GM, "%s: n_token <= 512", name);
+    EMO_CHECK(!(seg && !Sg), "%s: seg ids without a segment table", name);
+    EMO_CHECK(s.sync_ws_bytes >= (int64_t)PD_WS_WORDS * 8 && ((uintptr_t)s.sync_ws & 15) == 0, "%s: workspace too small / unaligned", name);
+    if (sampled) {
+        EMO_CHECK(s.u_steps && s.step && s.tok_out && s.n_real >= 1 && s.n_real <= s.n_streams && s.temperature > 0.f && s.n_token <= 1024,
+                  "%s: bad sampling arguments", name);
+    } else {
+        EMO_CHECK(tok, "%s: null token pointer", name);
+    }
+    PdArgs a;
+    a.layers = (const PdLayer*)s.layer_table; a.n_layers = (int)s.n_layers;
+    a.tok = tok; a.seg = seg; a.E = s.E; a.Sg = Sg; a.pe = pe; a.emb_scale = s.emb_scale; a.pos0 = pos0; a.pos_ids = pos_ids;
+    a.wout = (const bf16_t*)s.wout_packed; a.bout = s.bout; a.n_token = (int)s.n_token; a.logits = s.logits; a.n_streams = (int)s.n_streams;
+    a.sync = (u64*)s.sync_ws; a.eps = eps; a.ln_eps = s.ln_eps; a.diag = (u64*)s.diag;
+    a.samp_mode = sampled ? 1 : 0; a.temp = s.temperature; a.top_p = s.top_p; a.u_steps = s.u_steps; a.step = s.step; a.seq = s.seq; a.ld_seq = s.ld_seq;
+    a.col0 = s.col0; a.tok_out = s.tok_out; a.logits_in = logits_in; a.n_real = (int)s.n_real;
+    a.ln0 = s.ln0; a.kv_tmax = s.kv_tmax;
+    a.lens = s.lens; a.mem_len = (int)s.mem_len; a.rwb = s.r_w_bias; a.rrb = s.r_r_bias;
+    { const char* e = getenv("EMO_PD_NT"); a.flags = e ? (atoi(e) & 3) : 0; }
+    static_assert(LDS_TOTAL <= PD_LDS_BYTES, "LDS carve");
+    EMO_CHECK(pd_supported(), "%s: this device / partition cannot hold the launch's %d workgroups at once (needs >= %d CUs with 96 KB "
+              "of LDS each): use the chain of launches", name, PD_NG * PD_GM, PD_NG * PD_GM);
+    hipLaunchKernelGGL(pd_forms[form].kernel, dim3(PD_NG * PD_GM), dim3(PD_NT), PD_LDS_BYTES, (hipStream_t)stream, a);
+    EMO_LAUNCH_CHECK();
+    return EMO_OK;
+}
+
+extern "C" int emo_decode_step(const emo_decode_step_t* args, emo_stream_t stream) {
+    EMO_CHECK(args, "emo_decode_step: null argument block");
+    return pd_launch(*args, stream);
 }

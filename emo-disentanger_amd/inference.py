@@ -90,15 +90,17 @@ class _EngineBase:
         return out
 
     # ------------------------------------------------------------------------------------------ one-launch step (what the two engines share)
-    # An engine with one supplies: step_entry (the C entry, for messages), _persist_layer(l, t_qkv, t_one, t_ffn) -> the 12 weight tensors of
-    # layer l, _persist_state(l) -> its last four table columns, _check_position(pe), _launch(...) and _launch_sampled(...).
+    # An engine with one supplies: step_entry (the form's name in emo_decode_step's messages), _persist_layer(l, t_qkv, t_one, t_ffn) -> the 12
+    # weight tensors of layer l, _persist_state(l) -> its last four table columns, _check_position(pe) and _persist_form() -> the fields of the
+    # argument block that are the form's own.  The base class owns the block (persist['args'], one per engine) and both launches.
+    _pos_field = 'pos_ids'                                           # the field that takes the device positions of a step
     _TABLE_COLS = ('wqkv', 'bqkv', 'wo', 'bo', 'g1', 'be1', 'w1', 'b1', 'w2', 'b2', 'g2', 'be2')
 
     @staticmethod
     def _pack_fragments(W, tile_idx, kpw):
         """bf16 nn.Linear weight [N, K] -> [members][4 waves][tiles per member][kpw][64 lanes x 8]: the MFMA B fragment (16 output columns x 32 k)
         of column tile t and k step ks holds, in lane l, W[16 t + l % 16][32 ks + 8 (l // 16) .. + 8]; wave w of the compute half that owns the
-        product holds the k steps [w kpw, (w + 1) kpw) of all of the member's tiles (emo_hip.h: emo_performer_decode_step)."""
+        product holds the k steps [w kpw, (w + 1) kpw) of all of the member's tiles (emo_hip.h: emo_decode_step_t.layer_table)."""
         N, K = W.shape
         assert N % 16 == 0 and K == 32 * 4 * kpw
         frags = W.reshape(N // 16, 16, K // 32, 4, 8).permute(0, 2, 3, 1, 4).reshape(N // 16, K // 32, 512)      # [tile][k step][lane * 8 + j]
@@ -119,29 +121,44 @@ class _EngineBase:
         wout[:V] = ps.w('dec_out_proj.weight')
         self.persist['wout'] = self._pack_fragments(wout, torch.arange(Vp // 16, device=dev).view(-1, 1), 4)
         self.persist['bout'] = ps.f32('dec_out_proj.bias')
-        self.persist['sync'] = torch.zeros(ops.lib.emo_performer_decode_step_workspace_bytes() // 8, device=dev, dtype=torch.int64)   # zeroed ONCE
+        self.persist['sync'] = torch.zeros(ops.lib.emo_decode_step_workspace_bytes() // 8, device=dev, dtype=torch.int64)   # zeroed ONCE
         self.persist['logits'] = torch.zeros(self.n_pad, V, device=dev, dtype=torch.float32)
         if self.n_pad != self.n:                                     # padded inputs of the idle streams: token 0, segment 0, position 0
             self.persist['tok'] = torch.zeros(self.n_pad, dtype=torch.int64, device=dev)
             self.persist['seg'] = torch.zeros(self.n_pad, dtype=torch.int64, device=dev)
             self.persist['pos'] = torch.zeros(self.n_pad, dtype=torch.int64, device=dev)
+        # the argument block of the launch (emo_hip.h: emo_decode_step_t): what never changes is written here, once; persist['held'] keeps the
+        # tensors behind its addresses alive.  A step writes only its inputs, its output and — sampled — the sampler's fields.
+        E, Sg, pe = self._inputs()
+        pp = self.persist
+        pp['args'], pp['held'], pp['pe'] = ops.DecodeStep(), {}, pe
+        ops.decode_step_set(pp['args'], pp['held'], n_layers=m.n_layer, E=E, Sg=Sg, pe=pe, wout_packed=pp['wout'], bout=pp['bout'], n_token=V,
+                            n_streams=self.n_pad, n_real=self.n, d_model=m.d_model, n_head=m.n_head, d_ff=2048, sync_ws=pp['sync'], ln_eps=1e-5,
+                            **self._persist_form())
 
-    def _persist_table(self):
-        """[L][16] device pointers (emo_hip.h); built at the first step after the state tensors exist (prefill voids it)."""
+    def _void_table(self):
+        """New state tensors (a prefill): the pointer table is rebuilt at the next step, and the block must not keep the address of the old one."""
+        self.persist['table'] = None
+        ops.decode_step_set(self.persist['args'], self.persist['held'], layer_table=None)
+
+    def _launch(self, sampled, **fields):
+        """The one-launch step on the engine's argument block.  The [L][16] pointer table (emo_hip.h) is built at the first step after the state
+        tensors exist."""
         pp = self.persist
         if pp['table'] is None:
             rows = [[w[c].data_ptr() for c in self._TABLE_COLS] + self._persist_state(l) for l, w in enumerate(pp['w'])]
             pp['table'] = torch.tensor(rows, dtype=torch.int64, device=self.dev)
-        return pp['table']
+            fields['layer_table'] = pp['table']
+        ops.decode_step_set(pp['args'], pp['held'], sampled=sampled, **fields)
+        ops.decode_step(pp['args'])
 
     def _step_persistent(self, tok, seg, dev_pos, logits_out):
         """Returns `logits_out` when given, else the engine's STATIC logits buffer (or a view of its first n rows): the next step overwrites it —
         callers that keep logits across steps clone them (the chain of launches returns a fresh tensor; hipGraph capture needs the static one)."""
         pp = self.persist
-        E, Sg, pe = self._inputs()
-        seg = seg if (Sg is not None and seg is not None) else None
+        seg = seg if (pp['held']['Sg'] is not None and seg is not None) else None
         if not dev_pos:
-            self._check_position(pe)                                 # (ops.embed_fwd makes the same check on the launch-chain path)
+            self._check_position(pp['pe'])                           # (ops.embed_fwd makes the same check on the launch-chain path)
         pos_ids = self.pos_dev if dev_pos else None
         padded = self.n_pad != self.n
         if padded:
@@ -154,7 +171,7 @@ class _EngineBase:
                 pp['pos'][:self.n].copy_(pos_ids)
                 pos_ids = pp['pos']
         out = logits_out if (logits_out is not None and not padded) else pp['logits']
-        self._launch(tok, seg, E, Sg if seg is not None else None, pe, self.dev_pos0 if dev_pos else self.pos, pos_ids, out)
+        self._launch(0, tok=tok, seg=seg, pos0=self.dev_pos0 if dev_pos else self.pos, logits=out, diag=pp.get('diag'), **{self._pos_field: pos_ids})
         if padded:
             if logits_out is not None:
                 logits_out.copy_(out[:self.n])
@@ -163,13 +180,13 @@ class _EngineBase:
         return out
 
     def step_sampled(self, seg_padded, temp, top_p, U, step_ctr, seq, col0, tok_out, pos0):
-        """One token step with the nucleus draw INSIDE the launch (emo_*_decode_step_sampled): draws from the logits the previous step (or the
+        """One token step with the nucleus draw INSIDE the launch (emo_decode_step_t.sampled): draws from the logits the previous step (or the
         prefill: see load_logits) left in the engine's buffer, writes token / sequence / step counter like emo_sample_nucleus_step, then runs
         the step on the drawn tokens.  seg_padded: int64 [n_pad] (or None)."""
-        E, Sg, pe = self._inputs()
-        seg = seg_padded if Sg is not None else None
-        self._launch_sampled(seg, E, Sg if seg is not None else None, pe, pos0, temp, top_p, U, step_ctr, seq, col0, tok_out)
-        return self.persist['logits'][:self.n]
+        pp = self.persist
+        self._launch(1, seg=seg_padded if pp['held']['Sg'] is not None else None, pos0=pos0, logits=pp['logits'], diag=None, temperature=temp, top_p=top_p,
+                     u_steps=U, step=step_ctr, seq=seq, col0=col0, tok_out=tok_out)
+        return pp['logits'][:self.n]
 
     def load_logits(self, logits):
         """Put externally produced logits (the prefill's) where step_sampled draws from."""
@@ -201,7 +218,7 @@ class PerformerDecodeEngine(_EngineBase):
         self.fold = None
         if self.dt == torch.bfloat16 and n_streams <= 32 and os.environ.get('EMO_DECODE_LN_FOLD', '1') != '0':
             self._prepare_folds()
-        # the whole token step as ONE persistent launch (emo_performer_decode_step) for the benchmark architecture: bf16, d_model 512, 8 heads,
+        # the whole token step as ONE persistent launch (emo_decode_step, form 0) for the benchmark architecture: bf16, d_model 512, 8 heads,
         # 128 features, d_ff 2048, up to 32 streams (the kernel's groups own 4 streams each: other counts — the reference's own one-piece-at-a-time
         # loop is n = 1 — are padded with idle streams whose state is zero and whose logits nobody reads).  EMO_DECODE_PERSISTENT=0 keeps the chain
         # of launches (tests compare the two).
@@ -212,13 +229,13 @@ class PerformerDecodeEngine(_EngineBase):
         if (self.dt == torch.bfloat16 and 1 <= n_streams <= 32 and model.d_model == 512 and model.n_head == 8 and nf == 128
                 and ff == 2048 and model.n_layer <= 15 and model.n_token <= 512 and persistent and self.act == ops.ACT_RELU
                 and os.environ.get('EMO_DECODE_PERSISTENT', '1') != '0'
-                and ops.lib.emo_performer_decode_step_supported() == 1):
-            # (emo_performer_decode_step_supported: the launch's 256 workgroups spin-wait on each other and must all be resident — >= 256 CUs,
+                and ops.lib.emo_decode_step_supported() == 1):
+            # (emo_decode_step_supported: the launch's 256 workgroups spin-wait on each other and must all be resident — >= 256 CUs,
             # 96 KB LDS each, one per CU by the occupancy query; partitions / CU masks with fewer keep the chain of launches)
             self._prepare_persist()
 
     # ------------------------------------------------------------------------------------------ one-launch step
-    step_entry = 'emo_performer_decode_step'
+    step_entry = 'emo_decode_step[performer]'
 
     def _persist_layer(self, l, t_qkv, t_one, t_ffn):
         m, ps, pk = self.model, self.ps, self._pack_fragments
@@ -240,17 +257,8 @@ class PerformerDecodeEngine(_EngineBase):
         if self.pos >= pe.shape[0]:
             raise EmoError('decode position %d is past the positional-encoding table (%d rows)' % (self.pos, pe.shape[0]))
 
-    def _launch(self, tok, seg, E, Sg, pe, pos0, pos_ids, out):
-        m, pp = self.model, self.persist
-        ops.performer_decode_step(self._persist_table(), m.n_layer, tok, seg, E, Sg, pe, float(m.token_emb.emb_scale), pos0, pos_ids, pp['wout'],
-                                  pp['bout'], m.n_token, out, self.n_pad, m.d_model, m.n_head, 2 * self.omegas[0].shape[1], 2048, pp['sync'],
-                                  diag=pp.get('diag'))
-
-    def _launch_sampled(self, seg, E, Sg, pe, pos0, temp, top_p, U, step_ctr, seq, col0, tok_out):
-        m, pp = self.model, self.persist
-        ops.performer_decode_step_sampled(self._persist_table(), m.n_layer, seg, E, Sg, pe, float(m.token_emb.emb_scale), pos0, pp['wout'], pp['bout'],
-                                          m.n_token, pp['logits'], self.n_pad, self.n, m.d_model, m.n_head, 2 * self.omegas[0].shape[1], 2048,
-                                          pp['sync'], temp, top_p, U, step_ctr, seq, col0, tok_out)
+    def _persist_form(self):
+        return dict(form=0, emb_scale=float(self.model.token_emb.emb_scale), n_feat=2 * self.omegas[0].shape[1], eps=1e-6)
 
     def _prepare_folds(self):
         """gamma-scaled weights, c1[n] = sum_k gamma_k W[n,k] (of the ROUNDED bf16 product, the one the MFMA sees) and bias + W.beta for every
@@ -311,7 +319,7 @@ class PerformerDecodeEngine(_EngineBase):
             attn, _, self.S[l], self.z[l] = ops.favor_attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], self.omegas[l], B, T, H, want_state=True)
             x = self._tail(pfx, x, attn)
         if self.persist is not None:
-            self.persist['table'] = None                         # new state tensors: the pointer table is rebuilt at the next step
+            self._void_table()
             if self.n_pad != B:                                  # state of the padded (idle) streams: zero; S[l] / z[l] stay the views of the real ones
                 for l in range(m.n_layer):
                     Sp = torch.zeros((self.n_pad,) + tuple(self.S[l].shape[1:]), device=self.dev, dtype=self.S[l].dtype)
@@ -367,14 +375,14 @@ class GPT2DecodeEngine(_EngineBase):
         # head-major cache [n, H, max_len, dh] (r06; HF's own past_key_values layout): the decode attention gives one workgroup to a (stream, head),
         # whose keys are then one contiguous run instead of 128-byte pieces 1 KB apart.  EMO_KV_HEAD_MAJOR=0: [n, max_len, D] (r05, same-box A/B)
         self.head_major = os.environ.get('EMO_KV_HEAD_MAJOR', '1') != '0'
-        # the whole token step as ONE persistent launch (emo_gpt2_decode_step; r06), under the conditions of the Performer engine's: bf16, d_model 512,
+        # the whole token step as ONE persistent launch (emo_decode_step, form 1; r06), under the conditions of the Performer engine's: bf16, d_model 512,
         # 8 heads, d_ff 2048, <= 32 streams (padded to a multiple of 4 with idle streams), head-major cache of <= 2048 rows.  EMO_DECODE_PERSISTENT=0 /
         # EMO_GPT2_PERSISTENT=0 keep the chain of launches (tests compare the two).
         ff = self.ps.f32(model._layer_prefix(0) + 'mlp.c_fc.bias').numel()
         want_persist = (self.dt == torch.bfloat16 and 1 <= n_streams <= 32 and D == 512 and model.n_head == 8 and ff == 2048 and model.n_layer <= 15
                         and model.n_token <= 512 and max_len <= 2048 and self.head_major and persistent
                         and os.environ.get('EMO_DECODE_PERSISTENT', '1') != '0' and os.environ.get('EMO_GPT2_PERSISTENT', '1') != '0'
-                        and ops.lib.emo_gpt2_decode_step_supported() == 1)
+                        and ops.lib.emo_decode_step_supported() == 1)
         rows = self.n_pad if want_persist else n_streams
         shp = (rows, model.n_head, max_len, D // model.n_head) if self.head_major else (rows, max_len, D)
         self.kc_all = [torch.zeros(*shp, device=self.dev, dtype=self.dt) for _ in range(model.n_layer)]
@@ -393,12 +401,12 @@ class GPT2DecodeEngine(_EngineBase):
             self._prepare_persist()
 
     # ------------------------------------------------------------------------------------------ one-launch step
-    step_entry = 'emo_gpt2_decode_step'
+    step_entry = 'emo_decode_step[gpt2]'
 
-    def _prepare_persist(self):
-        super()._prepare_persist()
+    def _persist_form(self):
         ps, p0 = self.ps, self.model._layer_prefix(0)
-        self.persist['ln0'] = torch.cat([ps.f32(p0 + 'ln_1.weight'), ps.f32(p0 + 'ln_1.bias')]).contiguous()
+        return dict(form=1, emb_scale=float(self.model.token_emb.emb_scale), kv_tmax=self.max_len,
+                    ln0=torch.cat([ps.f32(p0 + 'ln_1.weight'), ps.f32(p0 + 'ln_1.bias')]).contiguous())
 
     def _persist_layer(self, l, t_qkv, t_one, t_ffn):
         m, ps, pk = self.model, self.ps, self._pack_fragments
@@ -422,17 +430,6 @@ class GPT2DecodeEngine(_EngineBase):
         rows = min(pe.shape[0], self.max_len)
         if self.pos >= rows:
             raise EmoError('decode position %d is past the positional-encoding table / the KV cache (%d rows)' % (self.pos, rows))
-
-    def _launch(self, tok, seg, E, Sg, pe, pos0, pos_ids, out):
-        m, pp = self.model, self.persist
-        ops.gpt2_decode_step(self._persist_table(), m.n_layer, tok, seg, E, Sg, pe, float(m.token_emb.emb_scale), pos0, pos_ids, pp['ln0'], self.max_len,
-                             pp['wout'], pp['bout'], m.n_token, out, self.n_pad, m.d_model, m.n_head, 2048, pp['sync'], diag=pp.get('diag'))
-
-    def _launch_sampled(self, seg, E, Sg, pe, pos0, temp, top_p, U, step_ctr, seq, col0, tok_out):
-        m, pp = self.model, self.persist
-        ops.gpt2_decode_step_sampled(self._persist_table(), m.n_layer, seg, E, Sg, pe, float(m.token_emb.emb_scale), pos0, pp['ln0'], self.max_len,
-                                     pp['wout'], pp['bout'], m.n_token, pp['logits'], self.n_pad, self.n, m.d_model, m.n_head, 2048, pp['sync'],
-                                     temp, top_p, U, step_ctr, seq, col0, tok_out)
 
     def _prepare_folds(self):
         m, ps = self.model, self.ps

@@ -271,7 +271,7 @@ def head_major(x, n_head):
 
 
 class TXLMemoryHeadMajor:
-    """TXLMemory for the one-launch token step (emo_txl_decode_step): caches [rows, H, max_len, dh], row = position, so that the keys of a
+    """TXLMemory for the one-launch token step (emo_decode_step, form 2): caches [rows, H, max_len, dh], row = position, so that the keys of a
     (stream, head) are one contiguous run.  `rows` >= n_streams: the launch works on groups of 4 streams, rows n_streams .. are its idle padding
     (length 0, never read back); kc / vc / lens are the views of the real streams."""
 

@@ -10,11 +10,11 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, BF16, F32, MUL_BITMASK, MUL_DGELU, MUL_DGELU_NEW, MUL_NONE, MUL_NONZERO, Epilogue, check,
+from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, BF16, F32, MUL_BITMASK, MUL_DGELU, MUL_DGELU_NEW, MUL_NONE, MUL_NONZERO, DecodeStep, Epilogue, check,
                    dtype_code, lib, ptr, stream)
 
 __all__ = ['gemm', 'colsum', 'embed_fwd', 'embed_bwd', 'layernorm_fwd', 'layernorm_bwd', 'dropout_apply', 'favor_attn_fwd',
-           'favor_attn_bwd', 'favor_decode_step', 'performer_decode_step', 'performer_decode_step_sampled', 'favor_draw_omega', 'softmax_attn_fwd', 'softmax_attn_bwd', 'softmax_attn_decode', 'relpos_attn_fwd', 'relpos_attn_bwd', 'relpos_attn_decode', 'xent_fwd',
+           'favor_attn_bwd', 'favor_decode_step', 'decode_step', 'decode_step_set', 'DecodeStep', 'favor_draw_omega', 'softmax_attn_fwd', 'softmax_attn_bwd', 'softmax_attn_decode', 'relpos_attn_fwd', 'relpos_attn_bwd', 'relpos_attn_decode', 'xent_fwd',
            'xent_bwd', 'token_scores', 'xent_bwd_rows', 'argmax', 'sample_nucleus', 'sample_nucleus_step', 'txl_grammar_step', 'acc_grammar_step', 'acc_window_step', 'accuracy_counts', 'sumsq', 'clip_coef', 'adam_step', 'cast', 'add_bias2',
            'ACT_NONE', 'ACT_RELU', 'ACT_GELU_NEW', 'ACT_GELU', 'MUL_NONE', 'MUL_NONZERO', 'MUL_DGELU_NEW', 'MUL_DGELU', 'MUL_BITMASK', 'gemm_bitmask_ok', 'gemm_lna_ok', 'bitmask_rows', 'favor_bwd_dn_ok', 'ffn_fwd', 'ffn_fwd_ok']
 
@@ -338,70 +338,54 @@ def favor_decode_step(q, k, v, omega, state_S, state_z, H, eps=1e-6):
     return out
 
 
-def performer_decode_step(layer_table, n_layers, tok, seg, E, Sg, pe, emb_scale, pos0, pos_ids, wout_packed, bout, n_token, logits, n_streams,
-                          d_model, n_head, n_feat, d_ff, sync_ws, eps=1e-6, ln_eps=1e-5, diag=None):
-    """One token step of every stream in ONE persistent launch (emo_hip.h: emo_performer_decode_step)."""
-    tok, seg, pos_ids = _c(tok), _c(seg), _c(pos_ids)
-    assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.shape == (n_streams, n_token)
-    check(lib.emo_performer_decode_step(ptr(layer_table), n_layers, ptr(tok), ptr(seg), ptr(E), ptr(Sg), ptr(pe), emb_scale, pos0, ptr(pos_ids),
-                                        ptr(wout_packed), ptr(bout), n_token, ptr(logits), n_streams, d_model, n_head, n_feat, d_ff,
-                                        ptr(sync_ws), sync_ws.numel() * sync_ws.element_size(), eps, ln_eps, ptr(diag), stream()))
-    return logits
+_F32 = torch.float32
+# layout a tensor must have before its address goes into a DecodeStep field: field -> check(args, tensor)
+_DECODE_STEP_LAYOUT = {
+    'logits': lambda a, t: t.dtype == _F32 and t.is_contiguous() and t.shape == (a.n_streams, a.n_token),
+    'ln0': lambda a, t: t.dtype == _F32 and t.is_contiguous() and t.numel() == 2 * a.d_model,
+    'u_steps': lambda a, t: t.dtype == _F32 and t.is_contiguous() and t.shape[1] == a.n_real,
+    'step': lambda a, t: t.dtype == torch.int64,
+    'tok_out': lambda a, t: t.dtype == torch.int64,
+    'seq': lambda a, t: t.dtype == torch.int64 and t.stride(1) == 1,
+    'lens': lambda a, t: t.numel() == a.n_streams,
+    'r_w_bias': lambda a, t: t.dtype == _F32 and t.is_contiguous(),
+    'r_r_bias': lambda a, t: t.dtype == _F32 and t.is_contiguous(),
+}
+_DECODE_STEP_I64 = ('tok', 'seg', 'pos_ids', 'lens')          # int64 vectors, made contiguous (_c)
 
 
-def performer_decode_step_sampled(layer_table, n_layers, seg, E, Sg, pe, emb_scale, pos0, wout_packed, bout, n_token, logits, n_streams, n_real,
-                                  d_model, n_head, n_feat, d_ff, sync_ws, temperature, top_p, u_steps, step, seq, col0, tok_out, eps=1e-6, ln_eps=1e-5):
-    """emo_performer_decode_step with the next token drawn inside the launch (emo_hip.h)."""
-    seg = _c(seg)
-    assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.shape == (n_streams, n_token)
-    assert u_steps.dtype == torch.float32 and u_steps.is_contiguous() and u_steps.shape[1] == n_real and step.dtype == torch.int64 and tok_out.dtype == torch.int64
-    assert seq is None or (seq.dtype == torch.int64 and seq.stride(1) == 1)
-    check(lib.emo_performer_decode_step_sampled(ptr(layer_table), n_layers, ptr(seg), ptr(E), ptr(Sg), ptr(pe), emb_scale, pos0, ptr(wout_packed), ptr(bout),
-                                                n_token, ptr(logits), n_streams, n_real, d_model, n_head, n_feat, d_ff, ptr(sync_ws),
-                                                sync_ws.numel() * sync_ws.element_size(), eps, ln_eps, temperature, top_p, ptr(u_steps), ptr(step), ptr(seq),
-                                                0 if seq is None else seq.stride(0), col0, ptr(tok_out), stream()))
-    return logits
+def decode_step_set(args, held, **fields):
+    """Write fields of a DecodeStep (emo_hip.h: emo_decode_step_t): numbers as they are, tensors (or None) as device addresses after the layout
+    check of the field; `seq` also sets ld_seq, `sync_ws` also sets sync_ws_bytes.  The struct holds raw addresses, so the rule of _c() applies to
+    its owner: `held` (field -> tensor) is the owner's dict that keeps every tensor whose address is in the struct alive, the contiguous copies
+    made here included.  A tensor that `held` already has for the field is the one the struct points to, checked when it went in: it is not
+    looked at again (a token loop hands over the same buffers step after step).  Numbers are written first: a tensor may be checked against a
+    size given in the same call."""
+    tensors = None
+    for k, v in fields.items():
+        if v is None or isinstance(v, torch.Tensor):
+            if k not in held or held[k] is not v:
+                tensors = tensors or []
+                tensors.append((k, v))
+        else:
+            setattr(args, k, v)
+    for k, t in tensors or ():
+        if t is not None:
+            if k in _DECODE_STEP_I64:
+                t = _c(t)                                         # (a copy is held in the caller's place, so the next call makes a new one)
+            ok = _DECODE_STEP_LAYOUT.get(k)
+            assert ok is None or ok(args, t), 'decode step: bad dtype / layout of %s' % k
+        held[k] = t
+        setattr(args, k, ptr(t))
+        if k == 'seq':
+            args.ld_seq = 0 if t is None else t.stride(0)
+        elif k == 'sync_ws':
+            args.sync_ws_bytes = 0 if t is None else t.numel() * t.element_size()
 
 
-def gpt2_decode_step(layer_table, n_layers, tok, seg, E, Sg, pe, emb_scale, pos0, pos_ids, ln0, kv_tmax, wout_packed, bout, n_token, logits, n_streams,
-                     d_model, n_head, d_ff, sync_ws, ln_eps=1e-5, diag=None):
-    """One GPT-2 token step of every stream in ONE persistent launch (emo_hip.h: emo_gpt2_decode_step)."""
-    tok, seg, pos_ids = _c(tok), _c(seg), _c(pos_ids)
-    assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.shape == (n_streams, n_token)
-    assert ln0.dtype == torch.float32 and ln0.is_contiguous() and ln0.numel() == 2 * d_model
-    check(lib.emo_gpt2_decode_step(ptr(layer_table), n_layers, ptr(tok), ptr(seg), ptr(E), ptr(Sg), ptr(pe), emb_scale, pos0, ptr(pos_ids), ptr(ln0), kv_tmax,
-                                   ptr(wout_packed), ptr(bout), n_token, ptr(logits), n_streams, d_model, n_head, d_ff,
-                                   ptr(sync_ws), sync_ws.numel() * sync_ws.element_size(), ln_eps, ptr(diag), stream()))
-    return logits
-
-
-def gpt2_decode_step_sampled(layer_table, n_layers, seg, E, Sg, pe, emb_scale, pos0, ln0, kv_tmax, wout_packed, bout, n_token, logits, n_streams, n_real,
-                             d_model, n_head, d_ff, sync_ws, temperature, top_p, u_steps, step, seq, col0, tok_out, ln_eps=1e-5):
-    """emo_gpt2_decode_step with the next token drawn inside the launch (emo_hip.h)."""
-    seg = _c(seg)
-    assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.shape == (n_streams, n_token)
-    assert ln0.dtype == torch.float32 and ln0.is_contiguous() and ln0.numel() == 2 * d_model
-    assert u_steps.dtype == torch.float32 and u_steps.is_contiguous() and u_steps.shape[1] == n_real and step.dtype == torch.int64 and tok_out.dtype == torch.int64
-    assert seq is None or (seq.dtype == torch.int64 and seq.stride(1) == 1)
-    check(lib.emo_gpt2_decode_step_sampled(ptr(layer_table), n_layers, ptr(seg), ptr(E), ptr(Sg), ptr(pe), emb_scale, pos0, ptr(ln0), kv_tmax, ptr(wout_packed),
-                                           ptr(bout), n_token, ptr(logits), n_streams, n_real, d_model, n_head, d_ff, ptr(sync_ws),
-                                           sync_ws.numel() * sync_ws.element_size(), ln_eps, temperature, top_p, ptr(u_steps), ptr(step), ptr(seq),
-                                           0 if seq is None else seq.stride(0), col0, ptr(tok_out), stream()))
-    return logits
-
-
-def txl_decode_step(layer_table, n_layers, tok, E, emb_scale, lens, mem_len, n_dist, r_w_bias, r_r_bias, ln0, kv_tmax, wout_packed, bout, n_token, logits,
-                    n_streams, d_model, n_head, d_ff, sync_ws, ln_eps=1e-5, diag=None):
-    """One Transformer-XL token step of every stream in ONE persistent launch (emo_hip.h: emo_txl_decode_step)."""
-    tok, lens = _c(tok), _c(lens)
-    assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.shape == (n_streams, n_token)
-    assert ln0.dtype == torch.float32 and ln0.is_contiguous() and ln0.numel() == 2 * d_model
-    assert lens.dtype == torch.int64 and lens.numel() == n_streams and tok.dtype == torch.int64
-    assert r_w_bias.dtype == torch.float32 and r_r_bias.dtype == torch.float32 and r_w_bias.is_contiguous() and r_r_bias.is_contiguous()
-    check(lib.emo_txl_decode_step(ptr(layer_table), n_layers, ptr(tok), ptr(E), emb_scale, ptr(lens), mem_len, n_dist, ptr(r_w_bias), ptr(r_r_bias), ptr(ln0),
-                                  kv_tmax, ptr(wout_packed), ptr(bout), n_token, ptr(logits), n_streams, d_model, n_head, d_ff,
-                                  ptr(sync_ws), sync_ws.numel() * sync_ws.element_size(), ln_eps, ptr(diag), stream()))
-    return logits
+def decode_step(args):
+    """One token step of every stream in ONE persistent launch (emo_hip.h: emo_decode_step) from a prepared DecodeStep; its logits field is the output."""
+    check(lib.emo_decode_step(ctypes.byref(args), stream()))
 
 
 def favor_draw_omega(gauss, omega):

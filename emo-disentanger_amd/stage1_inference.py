@@ -253,15 +253,15 @@ def generate_plain_xl_batch(model, event2idx, idx2event, primers, max_bars=160, 
 
 
 # ------------------------------------------------------------------------------------------------ one-launch token step
-STEPS = ('chain', 'one_launch')                     # PlainTransformer.decode_step (a chain of ~88 launches) / emo_txl_decode_step (one persistent launch)
+STEPS = ('chain', 'one_launch')                     # PlainTransformer.decode_step (a chain of ~88 launches) / emo_decode_step, form 2 (one persistent launch)
 
 
 def one_launch_conditions(model, n_streams, device_ok=None):
-    """What emo_txl_decode_step was built for, in the order it is reported: [(description, holds)].  device_ok: the answer of
-    emo_txl_decode_step_supported() (asked here when None)."""
+    """What the Transformer-XL form of emo_decode_step was built for, in the order it is reported: [(description, holds)].  device_ok: the answer of
+    emo_decode_step_supported() (asked here when None)."""
     dec = model.decoder
     if device_ok is None:
-        device_ok = ops.lib.emo_txl_decode_step_supported() == 1
+        device_ok = ops.lib.emo_decode_step_supported() == 1
     return [('compute dtype bf16 (got %s)' % str(model._compute_dtype).replace('torch.', ''), model._compute_dtype == torch.bfloat16),
             ('d_model 512 (got %d)' % model.dec_d_model, model.dec_d_model == 512),
             ('8 heads (got %d)' % model.dec_n_head, model.dec_n_head == 8),
@@ -273,11 +273,11 @@ def one_launch_conditions(model, n_streams, device_ok=None):
             ('1 to 32 streams (got %d)' % n_streams, 1 <= n_streams <= 32),
             ('1 <= mem_len and mem_len + 1 <= 2048 (got mem_len %d)' % model.dec_mem_len, 1 <= model.dec_mem_len <= 2047),
             ('d_word_embed == d_model (got %d)' % model.d_word_embed, model.d_word_embed == model.dec_d_model),
-            ('a device that holds the launch: 256 compute units with 96 KB of LDS each (emo_txl_decode_step_supported)', bool(device_ok))]
+            ('a device that holds the launch: 256 compute units with 96 KB of LDS each (emo_decode_step_supported)', bool(device_ok))]
 
 
 def one_launch_unsupported(model, n_streams, device_ok=None):
-    """None, or the first condition of emo_txl_decode_step this model / stream count does not meet."""
+    """None, or the first condition of emo_decode_step's Transformer-XL form this model / stream count does not meet."""
     for what, holds in one_launch_conditions(model, n_streams, device_ok):
         if not holds:
             return what
@@ -285,25 +285,22 @@ def one_launch_unsupported(model, n_streams, device_ok=None):
 
 
 class OneLaunchStep(_EngineBase):
-    """decode_step of n lock-step streams as ONE persistent launch (emo_txl_decode_step): the packed weights, the pointer table and the workspace
+    """decode_step of n lock-step streams as ONE persistent launch (emo_decode_step, form 2): the packed weights, the pointer table and the workspace
     of the decode engines' one-launch adapter, on a head-major TXLMemory (`mem`).  take_over(prefill memory, T) is the one-time hand-off."""
-    step_entry = 'emo_txl_decode_step'
+    step_entry = 'emo_decode_step[txl]'
+    _pos_field = 'lens'                                              # the device positions of a step are the streams' lengths
 
     def __init__(self, model, n_streams, max_len=None, r_dist=None):
         from .model.plain_transformer import TXLMemoryHeadMajor
         why = one_launch_unsupported(model, n_streams)
         if why is not None:
-            raise EmoError("step='one_launch' (emo_txl_decode_step) needs %s; use step='chain'" % why)
+            raise EmoError("step='one_launch' (emo_decode_step[txl]) needs %s; use step='chain'" % why)
         super().__init__(model, n_streams, model._max_gen_len if max_len is None else max_len)
-        ps = self.ps
         self.n_pad = (n_streams + 3) // 4 * 4
         self.mem = TXLMemoryHeadMajor(model, n_streams, self.max_len, rows=self.n_pad, r_dist=r_dist)
         self.pos_dev = self.mem.lens                                 # the adapter's device positions ARE the memory's lengths
         self.zeros = torch.zeros(3 * model.dec_d_model, device=self.dev, dtype=torch.float32)      # qkv_net / o_net have no bias
         self._prepare_persist()
-        a0 = 'decoder.layers.0.dec_attn.layer_norm.'
-        self.persist['ln0'] = torch.cat([ps.f32(a0 + 'weight'), ps.f32(a0 + 'bias')]).contiguous()
-        self.rw, self.rr = ps.f32('decoder.r_w_bias').contiguous(), ps.f32('decoder.r_r_bias').contiguous()
 
     def _inputs(self):
         return self.ps.f32('word_emb.emb_lookup.weight'), None, None      # what PlainTransformer._embed passes: no segment and no positional table
@@ -327,11 +324,11 @@ class OneLaunchStep(_EngineBase):
     def _check_position(self, pe):
         pass                                                         # (positions are the memory's device lengths; the cache row is clamped in the launch)
 
-    def _launch(self, tok, seg, E, Sg, pe, pos0, pos_ids, out):
-        m, pp = self.model, self.persist
-        ops.txl_decode_step(self._persist_table(), m.dec_n_layer, tok, E, float(m.word_emb.emb_scale), pos_ids, m.dec_mem_len, self.mem.r_dist[0].shape[0],
-                            self.rw, self.rr, pp['ln0'], self.max_len, pp['wout'], pp['bout'], m.vocab_size, out, self.n_pad, m.dec_d_model,
-                            m.dec_n_head, m.dec_d_ff, pp['sync'], diag=pp.get('diag'))
+    def _persist_form(self):
+        m, ps, a0 = self.model, self.ps, 'decoder.layers.0.dec_attn.layer_norm.'
+        return dict(form=2, emb_scale=float(m.word_emb.emb_scale), kv_tmax=self.max_len, mem_len=m.dec_mem_len, n_dist=self.mem.r_dist[0].shape[0],
+                    ln0=torch.cat([ps.f32(a0 + 'weight'), ps.f32(a0 + 'bias')]).contiguous(),
+                    r_w_bias=ps.f32('decoder.r_w_bias').contiguous(), r_r_bias=ps.f32('decoder.r_r_bias').contiguous())
 
     def take_over(self, mem, T):
         self.mem.take_over(mem, T)
@@ -348,7 +345,7 @@ class OneLaunchStep(_EngineBase):
 class LeadSheetLoop:
     """Device state of generate_lead_sheets: a TXLMemory, the logits of the last step, the uniform table, the grammar tables and
     per-stream parameters / state, the output sequences and the running count; one_step() = emo_txl_grammar_step + decode_step
-    (step='chain') or + emo_txl_decode_step (step='one_launch': OneLaunchStep on the head-major copy of the prefill's memory)."""
+    (step='chain') or + emo_decode_step, form 2 (step='one_launch': OneLaunchStep on the head-major copy of the prefill's memory)."""
 
     def __init__(self, model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
                  representation='functional', key_determine=None, seed=0, step='chain'):
@@ -360,7 +357,7 @@ class LeadSheetLoop:
         if step == 'one_launch':                                     # refused before anything is allocated; never a silent fall-back to the chain
             why = one_launch_unsupported(model, n)
             if why is not None:
-                raise EmoError("step='one_launch' (emo_txl_decode_step) needs %s; use step='chain'" % why)
+                raise EmoError("step='one_launch' (emo_decode_step[txl]) needs %s; use step='chain'" % why)
         kw = _per_stream(n, max_bars=max_bars, max_events=max_events, prompt_bars=prompt_bars, representation=representation, key_determine=key_determine)
         self.model, self.temp, self.top_p = model, float(temp), float(top_p)
         dev = self.dev = next(model.parameters()).device
@@ -459,7 +456,7 @@ def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max
     (emo_txl_grammar_step), each token step = grammar launch + decode_step, k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS,
     default 16) and replayed until every stream has finished.  Draws come from a uniform table seeded with `seed` (like generate_streams),
     so the ids are not NumPy-RNG-identical to the reference; they equal the host grammar driven by the same device draws.
-    step='one_launch' runs the model step as one persistent launch (emo_txl_decode_step) and raises EmoError where it was not built for the model.
+    step='one_launch' runs the model step as one persistent launch (emo_decode_step, form 2) and raises EmoError where it was not built for the model.
     -> (results, seconds)."""
     was_training = model.training
     model.eval()
@@ -509,7 +506,7 @@ def parse_args(argv=None):
     ap.add_argument('--exact', action='store_true', help='NumPy sampling and grammar on the host (reference-exact per seed) instead of the device loop')
     ap.add_argument('--seed', type=int, default=0, help='seed of the device uniform table (the group of streams j uses seed + j)')
     ap.add_argument('--step', default='chain', choices=['chain', 'one-launch'],
-                    help='the model step of the device loop: the chain of launches of decode_step, or one persistent launch (emo_txl_decode_step)')
+                    help='the model step of the device loop: the chain of launches of decode_step, or one persistent launch (emo_decode_step, form 2)')
     return ap.parse_args(argv)
 
 

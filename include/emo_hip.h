@@ -233,84 +233,99 @@ int emo_favor_decode_step(const void* q, const void* k, const void* v, int64_t l
                           float* state_S, float* state_z, void* out, int64_t ld_out, int dtype,
                           int64_t n_streams, int64_t H, int64_t dh, int64_t n_feat, float eps,
                           emo_stream_t stream);
-/* ONE-LAUNCH Performer decode step (the token loop of inference.py:250-277 -> MusicPerformer.forward(keep_last_only), music_performer.py:50-70):
- * embedding (transformer_helpers.py:81-87 + PE) -> n_layers post-LN FAVOR+ encoder layers (fast_transformer_decoder.py:54-74: fused q/k/v projection,
- * FAVOR+ recurrent step on the fp32 state, out-projection + residual + LayerNorm, ReLU FFN + residual + LayerNorm) -> dec_out_proj logits, for
- * n_streams <= 32 streams (a multiple of 4), bf16 weights, in a single persistent kernel: 8 groups x 32 workgroups of 12 waves (4 poller + 2 x 4 compute), a group owns 4 streams and
- * exchanges the activations of the 5 dependent products of a layer through tagged 8-byte granules (csrc/emo_decode_persist.hip).
- * Built for d_model 512 / 8 heads / 128 features / d_ff 2048, n_layers <= 15, n_token <= 512.
- *   layer_table : device array [n_layers][16] of pointers: wqkv_packed, bqkv (f32 [3 d], q|k|v), wo_packed, bo, norm1 gamma, beta, w1_packed, b1,
- *                 w2_packed, b2, norm2 gamma, beta, omega (f32 [64][64]), state_S (f32 [n][8][128][64]), state_z (f32 [n][8][128]), unused.
- *                 *_packed = the bf16 nn.Linear weight [N][K] re-ordered per (member, wave 0..3 of the compute half, column tile, k step) into 1-KB MFMA B fragments
- *                 (element (lane, j) = W[16 tile + lane % 16][32 kstep + 8 (lane / 16) + j]); the host mirror builds them (inference.py).
- *   tok, seg    : int64 [n_streams] (seg may be NULL); position of stream s = pos0 + (pos_ids ? pos_ids[s] : 0)
- *   logits      : f32 [n_streams][n_token]
- *   sync_ws     : emo_performer_decode_step_workspace_bytes() bytes, ZEROED ONCE by the caller before the first step and then left alone
- *                 (it carries the launch counter the granule tags are derived from); its last 8 words: [0] != 0 after a step that gave up
- *                 (a workgroup could not be scheduled next to the others within 50 ms) - the caller must check it before trusting the logits.
- *   diag        : NULL, or int64 [32][16][8][4] device words that receive group 0's per-phase time stamps (tools/pd_diag.py). */
-int64_t emo_performer_decode_step_workspace_bytes(void);
+/* ONE-LAUNCH decode step: one token of every stream through a whole model in a single persistent kernel (csrc/emo_decode_persist.hip), for
+ * n_streams <= 32 streams (a multiple of 4), bf16 weights: 8 groups x 32 workgroups of 12 waves (4 poller + 2 x 4 compute), a group owns 4 streams and
+ * exchanges the activations of the 5 dependent products of a layer through tagged 8-byte granules.  Built for d_model 512 / 8 heads / d_ff 2048,
+ * n_layers <= 15, n_token <= 512.  One argument block, emo_decode_step_t, selects the model (`form`) and whether the launch draws its own token (`sampled`):
+ *   form 0, Performer: the token loop of stage2_accompaniment/inference.py:250-277 -> MusicPerformer.forward(keep_last_only), music_performer.py:50-70:
+ *     embedding (transformer_helpers.py:81-87 + PE) -> n_layers post-LN FAVOR+ encoder layers (fast_transformer_decoder.py:54-74: fused q/k/v projection,
+ *     FAVOR+ recurrent step on the fp32 state, out-projection + residual + LayerNorm, ReLU FFN + residual + LayerNorm) -> dec_out_proj logits; 128 features.
+ *   form 1, GPT-2 (r06): the same loop on the GPT-2 backbone (stage2_accompaniment/model/music_gpt2.py -> HF GPT2Block: pre-LN, gelu_new, no ln_f) with
+ *     the KV cache BASELINE configs[3] names.
+ *   form 2, Transformer-XL (stage 1): the lead-sheet model — one token of every stream through stage1_compose/model/plain_transformer.py:52-59
+ *     (PlainTransformer.generate, one-token call) -> optimus_txl_decoder.py:750-925 with attn_type 0: word embedding x emb_scale (:788), n_layers
+ *     RelPartialLearnableDecoderLayer (:526-557: relative-position attention :301-391 with pre_lnorm over the last mem_len cached positions,
+ *     PositionwiseFF :28-66, evaluation mode) -> dec_out_proj; the token step of the sampling loop of stage1_compose/inference_utils.py:51-134.
+ *   sampled = 1 (forms 0 and 1): the NEXT token is drawn inside the launch (the sampling half of the loop of inference.py:252-277, arithmetic of
+ *     emo_sample_nucleus_step: same device code): member s < 4 of a group draws stream 4 g + s from `logits` AS THE PREVIOUS STEP LEFT IT (temperature,
+ *     nucleus top_p, uniform u_steps[step[r] * n_real + r]), writes the token to tok_out[r] and seq[r * ld_seq + col0 + step[r]], and the step then
+ *     embeds it at position pos0 + step[r] + 1 (form 1: = the row index of the appended key); step[r] is incremented when the launch is done.
+ *     Streams r >= n_real are idle padding (n_streams = n_real rounded up to 4).
+ * A field that a form does not read is ignored, whatever it holds.  The struct holds raw device addresses: its owner keeps the memory alive. */
+typedef struct {
+    int32_t form;              /* 0 Performer, 1 GPT-2, 2 Transformer-XL */
+    int32_t sampled;           /* 1: draw the token inside the launch (forms 0, 1) */
+    /* --- table and shape (all forms) */
+    const void* layer_table;   /* device array [n_layers][16] of pointers.
+                                *   form 0: wqkv_packed, bqkv (f32 [3 d], q|k|v), wo_packed, bo, norm1 gamma, beta, w1_packed, b1, w2_packed, b2, norm2 gamma,
+                                *           beta, omega (f32 [64][64]), state_S (f32 [n][8][128][64]), state_z (f32 [n][8][128]), unused.
+                                *           *_packed = the bf16 nn.Linear weight [N][K] re-ordered per (member, wave 0..3 of the compute half, column tile,
+                                *           k step) into 1-KB MFMA B fragments (element (lane, j) = W[16 tile + lane % 16][32 kstep + 8 (lane / 16) + j]);
+                                *           the host mirror builds them (inference.py).
+                                *   form 1: c_attn packed, bias (f32 [3 d]), attn.c_proj packed, bias, ln_2 gamma, beta, c_fc packed, bias, mlp.c_proj
+                                *           packed, bias, ln_1 gamma, beta OF THE NEXT BLOCK (any valid pointer for the last block), unused, K cache, V cache,
+                                *           unused.  Packed = the TRANSPOSED Conv1D weight ([out][in]) in the fragment order of form 0.
+                                *           K / V cache: bf16 [n_streams][8][kv_tmax][64] (head-major, kv_tmax <= 2048); the step appends the token's key /
+                                *           value row at index pos = pos0 + pos_ids[s] (= the number of rows already cached) and attends over rows 0 .. pos.
+                                *   form 2: qkv_net packed, ZEROS (f32 [3 d]: qkv_net has no bias), o_net packed, ZEROS (f32 [d]), pos_ff.layer_norm gamma,
+                                *           beta, CoreNet.0 packed, bias, CoreNet.3 packed, bias, dec_attn.layer_norm gamma, beta OF THE NEXT LAYER (any valid
+                                *           pointer for the last one), R_l = r_net_l(pos_emb) (bf16 [n_dist][512], row = distance), K cache, V cache, unused.
+                                *           K / V cache: bf16 [n_streams][8][kv_tmax][64], row = position; kv_tmax is NOT bounded by the 2048-entry score buffer. */
+    int64_t n_layers;          /* 1 .. 15 */
+    /* --- input */
+    const int64_t* tok;        /* int64 [n_streams]; ignored when sampled */
+    const int64_t* seg;        /* forms 0, 1: int64 [n_streams] or NULL (then Sg is not read) */
+    const float* E;            /* token embedding table, f32 [n_token][512] */
+    const float* Sg;           /* forms 0, 1: segment embedding table (needed when seg is given) */
+    const float* pe;           /* forms 0, 1: positional table, f32 [rows][512]; form 2 has no positional and no segment table */
+    float emb_scale;
+    int64_t pos0;              /* forms 0, 1: position of stream s = pos0 + (pos_ids ? pos_ids[s] : 0) */
+    const int64_t* pos_ids;    /* forms 0, 1: int64 [n_streams] or NULL; ignored when sampled */
+    /* --- output layer (all forms) */
+    const void* wout_packed;   /* dec_out_proj weight, packed as above */
+    const float* bout;
+    int64_t n_token;           /* <= 512 */
+    float* logits;             /* f32 [n_streams][n_token]; sampled: also the logits the token is drawn from */
+    /* --- sizes (all forms) */
+    int64_t n_streams;         /* a multiple of 4, <= 32 */
+    int64_t n_real;            /* sampled: 1 .. n_streams, the streams that draw */
+    int64_t d_model, n_head;   /* 512, 8 */
+    int64_t n_feat;            /* form 0: 128 */
+    int64_t d_ff;              /* 2048 */
+    /* --- workspace and numerics */
+    void* sync_ws;             /* emo_decode_step_workspace_bytes() bytes, 16-byte aligned, ZEROED ONCE by the caller before the first step and then left
+                                * alone (it carries the launch counter the granule tags are derived from); its last 8 words: [0] != 0 after a step that gave
+                                * up (a workgroup could not be scheduled next to the others within 50 ms) - the caller must check it before trusting the logits. */
+    int64_t sync_ws_bytes;
+    float eps;                 /* form 0: the FAVOR+ normaliser's epsilon */
+    float ln_eps;
+    int64_t* diag;             /* NULL, or int64 [32][16][8][4] device words that receive group 0's per-phase time stamps (tools/pd_diag.py) */
+    /* --- sampling (read when sampled) */
+    float temperature, top_p;  /* temperature > 0 */
+    const float* u_steps;      /* f32 [draws][n_real] uniforms */
+    int64_t* step;             /* int64 [n_real] draw counters, advanced by the launch */
+    int64_t* seq;              /* NULL, or int64 rows of ld_seq words that receive the drawn tokens at column col0 + step[r] */
+    int64_t ld_seq, col0;
+    int64_t* tok_out;          /* int64 [n_real] */
+    /* --- form-specific */
+    const float* ln0;          /* forms 1, 2: f32 [2][512]: gamma | beta of block 0's ln_1 / layer 0's dec_attn.layer_norm */
+    int64_t kv_tmax;           /* forms 1, 2: rows per (stream, head) of the K / V caches; form 1: <= 2048 */
+    const int64_t* lens;       /* form 2: int64 [n_streams] ON THE DEVICE: the length of each stream INCLUDING this token (the caller advances it in front
+                                * of the launch); the step appends the token's key / value row at index min(lens[s] - 1, kv_tmax - 1) and attends over rows
+                                * max(0, lens[s] - 1 - mem_len) .. lens[s] - 1 with the score
+                                * ((q + r_w_bias[h]) . k_j + (q + r_r_bias[h]) . R_l[lens[s] - 1 - j, h]) / 8 */
+    int64_t mem_len;           /* form 2: 1 <= mem_len, mem_len + 1 <= 2048 */
+    int64_t n_dist;            /* form 2: rows of the R tables, >= min(mem_len, kv_tmax - 1) + 1 */
+    const float* r_w_bias;     /* form 2: f32 [8][64] */
+    const float* r_r_bias;     /* form 2: f32 [8][64] */
+} emo_decode_step_t;
+/* sizeof(emo_decode_step_t) as the library was built (a binding checks its mirror against it, as with emo_epilogue_size) */
+int emo_decode_step_size(void);
+int64_t emo_decode_step_workspace_bytes(void);
 /* 1 when this device can hold the launch (>= 256 CUs, 96 KB of LDS per workgroup granted, one workgroup per CU by the occupancy query), else 0:
  * callers keep the chain of launches (emo_gemm + emo_favor_decode_step ...) of stage2_accompaniment/inference.py:250-277 then */
-int emo_performer_decode_step_supported(void);
-int emo_performer_decode_step(const void* layer_table, int64_t n_layers, const int64_t* tok, const int64_t* seg, const float* E,
-                              const float* Sg, const float* pe, float emb_scale, int64_t pos0, const int64_t* pos_ids,
-                              const void* wout_packed, const float* bout, int64_t n_token, float* logits, int64_t n_streams,
-                              int64_t d_model, int64_t n_head, int64_t n_feat, int64_t d_ff, void* sync_ws, int64_t sync_ws_bytes,
-                              float eps, float ln_eps, int64_t* diag, emo_stream_t stream);
-/* The same launch with the NEXT token drawn inside it (the sampling half of the loop of inference.py:252-277, arithmetic of emo_sample_nucleus_step:
- * same device code): member s < 4 of a group draws stream 4 g + s from `logits` AS THE PREVIOUS STEP LEFT IT (temperature, nucleus top_p, uniform
- * u_steps[step[r] * n_real + r]), writes the token to tok_out[r] and seq[r * ld_seq + col0 + step[r]], and the step then embeds it at position
- * pos0 + step[r] + 1; step[r] is incremented when the launch is done.  Streams r >= n_real are idle padding (n_streams = n_real rounded up to 4). */
-int emo_performer_decode_step_sampled(const void* layer_table, int64_t n_layers, const int64_t* seg, const float* E, const float* Sg,
-                                      const float* pe, float emb_scale, int64_t pos0, const void* wout_packed, const float* bout,
-                                      int64_t n_token, float* logits, int64_t n_streams, int64_t n_real, int64_t d_model, int64_t n_head,
-                                      int64_t n_feat, int64_t d_ff, void* sync_ws, int64_t sync_ws_bytes, float eps, float ln_eps,
-                                      float temperature, float top_p, const float* u_steps, int64_t* step, int64_t* seq, int64_t ld_seq,
-                                      int64_t col0, int64_t* tok_out, emo_stream_t stream);
-
-/* ONE-LAUNCH GPT-2 decode step (r06): the same persistent launch for the GPT-2 backbone (stage2_accompaniment/model/music_gpt2.py -> HF GPT2Block:
- * pre-LN, gelu_new, no ln_f; token loop of inference.py:250-277 with the KV cache BASELINE configs[3] names).  d_model 512 / 8 heads / d_ff 2048,
- * n_layers <= 15, n_token <= 512, n_streams <= 32 (a multiple of 4), bf16.  Arguments as emo_performer_decode_step, except:
- *   layer_table : [n_layers][16] pointers: c_attn packed, bias (f32 [3 d]), attn.c_proj packed, bias, ln_2 gamma, beta, c_fc packed, bias, mlp.c_proj
- *                 packed, bias, ln_1 gamma, beta OF THE NEXT BLOCK (any valid pointer for the last block), unused, K cache, V cache, unused.
- *                 Packed = the TRANSPOSED Conv1D weight ([out][in]) in the fragment order of emo_performer_decode_step.
- *                 K / V cache: bf16 [n_streams][8][kv_tmax][64] (head-major, kv_tmax <= 2048); the step appends the token's key / value row at index
- *                 pos = pos0 + pos_ids[s] (= the number of rows already cached) and attends over rows 0 .. pos.
- *   ln0         : f32 [2][512]: gamma | beta of block 0's ln_1. */
-int emo_gpt2_decode_step_supported(void);
-int emo_gpt2_decode_step(const void* layer_table, int64_t n_layers, const int64_t* tok, const int64_t* seg, const float* E, const float* Sg,
-                         const float* pe, float emb_scale, int64_t pos0, const int64_t* pos_ids, const float* ln0, int64_t kv_tmax,
-                         const void* wout_packed, const float* bout, int64_t n_token, float* logits, int64_t n_streams, int64_t d_model,
-                         int64_t n_head, int64_t d_ff, void* sync_ws, int64_t sync_ws_bytes, float ln_eps, int64_t* diag, emo_stream_t stream);
-/* with the next token drawn inside the launch, as emo_performer_decode_step_sampled (row index of the appended key = pos0 + step[r] + 1) */
-int emo_gpt2_decode_step_sampled(const void* layer_table, int64_t n_layers, const int64_t* seg, const float* E, const float* Sg, const float* pe,
-                                 float emb_scale, int64_t pos0, const float* ln0, int64_t kv_tmax, const void* wout_packed, const float* bout,
-                                 int64_t n_token, float* logits, int64_t n_streams, int64_t n_real, int64_t d_model, int64_t n_head, int64_t d_ff,
-                                 void* sync_ws, int64_t sync_ws_bytes, float ln_eps, float temperature, float top_p, const float* u_steps,
-                                 int64_t* step, int64_t* seq, int64_t ld_seq, int64_t col0, int64_t* tok_out, emo_stream_t stream);
-
-/* ONE-LAUNCH Transformer-XL decode step (stage 1): the same persistent launch for the lead-sheet model — one token of every stream through
- * stage1_compose/model/plain_transformer.py:52-59 (PlainTransformer.generate, one-token call) -> optimus_txl_decoder.py:750-925 with attn_type 0:
- * word embedding x emb_scale (:788), n_layers RelPartialLearnableDecoderLayer (:526-557: relative-position attention :301-391 with pre_lnorm over the
- * last mem_len cached positions, PositionwiseFF :28-66, evaluation mode) -> dec_out_proj; the token step of the sampling loop of
- * stage1_compose/inference_utils.py:51-134.  d_model 512 / 8 heads / d_ff 2048, n_layers <= 15, n_token <= 512, n_streams <= 32 (a multiple of 4), bf16.
- * Arguments as emo_gpt2_decode_step, except:
- *   layer_table : [n_layers][16] pointers: qkv_net packed, ZEROS (f32 [3 d]: qkv_net has no bias), o_net packed, ZEROS (f32 [d]), pos_ff.layer_norm
- *                 gamma, beta, CoreNet.0 packed, bias, CoreNet.3 packed, bias, dec_attn.layer_norm gamma, beta OF THE NEXT LAYER (any valid pointer
- *                 for the last one), R_l = r_net_l(pos_emb) (bf16 [n_dist][512], row = distance), K cache, V cache, unused.
- *                 K / V cache: bf16 [n_streams][8][kv_tmax][64], row = position; kv_tmax is NOT bounded by the 2048-entry score buffer.
- *   tok, E      : int64 [n_streams], f32 [n_token][512]; there is no positional and no segment table
- *   lens        : int64 [n_streams] ON THE DEVICE: the length of each stream INCLUDING this token (the caller advances it in front of the launch);
- *                 the step appends the token's key / value row at index min(lens[s] - 1, kv_tmax - 1) and attends over rows
- *                 max(0, lens[s] - 1 - mem_len) .. lens[s] - 1 with the score ((q + r_w_bias[h]) . k_j + (q + r_r_bias[h]) . R_l[lens[s] - 1 - j, h]) / 8
- *   mem_len     : 1 <= mem_len, mem_len + 1 <= 2048;  n_dist >= min(mem_len, kv_tmax - 1) + 1
- *   r_w_bias, r_r_bias : f32 [8][64];  ln0 : f32 [2][512]: gamma | beta of layer 0's dec_attn.layer_norm. */
-int emo_txl_decode_step_supported(void);
-int emo_txl_decode_step(const void* layer_table, int64_t n_layers, const int64_t* tok, const float* E, float emb_scale, const int64_t* lens,
-                        int64_t mem_len, int64_t n_dist, const float* r_w_bias, const float* r_r_bias, const float* ln0, int64_t kv_tmax,
-                        const void* wout_packed, const float* bout, int64_t n_token, float* logits, int64_t n_streams, int64_t d_model,
-                        int64_t n_head, int64_t d_ff, void* sync_ws, int64_t sync_ws_bytes, float ln_eps, int64_t* diag, emo_stream_t stream);
+int emo_decode_step_supported(void);
+int emo_decode_step(const emo_decode_step_t* args, emo_stream_t stream);
 
 /* FAVOR+ omega draw (fast-transformers orthogonal_random_matrix_, called from new_feature_map() on every
  * forward — SURVEY F8): gauss [n_layers, ceil((n_feat/2)/dh), dh, dh] ~ N(0,1) from the caller's RNG ->

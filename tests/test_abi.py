@@ -45,3 +45,57 @@ def test_epilogue_struct_mirror_has_the_library_size():
     from emo_disentanger_amd import _lib
     assert _lib.lib.emo_epilogue_size() == ctypes.sizeof(_lib.Epilogue)
 
+
+def test_decode_step_struct_mirror_has_the_library_size():
+    # the ctypes mirror of emo_decode_step_t, as for emo_epilogue_t above: a stale mirror would hand the launch garbage addresses
+    from emo_disentanger_amd import _lib
+    assert _lib.lib.emo_decode_step_size() == ctypes.sizeof(_lib.DecodeStep)
+
+
+_FORM_NAME = {0: 'performer', 1: 'gpt2', 2: 'txl'}
+
+
+def _decode_step_args(form, **kw):
+    """A block that passes every host check of `form` (pointer fields: small fake addresses, 16-byte aligned — validation never dereferences them,
+    and no refusal below gets as far as the device query or the launch), with the fields of `kw` changed."""
+    from emo_disentanger_amd import _lib
+    a = _lib.DecodeStep()
+    for name, ctype in _lib.DecodeStep._fields_:
+        if ctype is _lib.c_p:
+            setattr(a, name, 0x1000)
+    a.form, a.sampled, a.n_layers, a.n_token, a.n_streams, a.n_real = form, 0, 2, 327, 4, 4
+    a.d_model, a.n_head, a.n_feat, a.d_ff = 512, 8, 128, 2048
+    a.sync_ws_bytes = _lib.lib.emo_decode_step_workspace_bytes()
+    a.temperature, a.top_p, a.emb_scale, a.eps, a.ln_eps = 1.0, 0.9, 1.0, 1e-6, 1e-5
+    a.kv_tmax, a.mem_len, a.n_dist = 2048, 64, 65
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+@pytest.mark.parametrize('form, sampled, kw, what', [
+    (0, 0, dict(d_model=256), 'built for d_model 512'), (1, 0, dict(d_model=256), 'built for d_model 512'), (2, 0, dict(d_model=256), 'built for d_model 512'),
+    (0, 0, dict(n_streams=6), 'multiple of 4'), (1, 0, dict(n_streams=6), 'multiple of 4'), (2, 0, dict(n_streams=6), 'multiple of 4'),
+    (1, 0, dict(kv_tmax=4096), 'KV cache of <= 2048 rows'),
+    (2, 0, dict(mem_len=2048), '1 <= mem_len and mem_len + 1 <= 2048 (got mem_len 2048)'),
+    (2, 0, dict(mem_len=64, n_dist=64), 'the R tables have 64 rows, the window reaches distance 64'),
+    (0, 1, dict(temperature=0.0), 'bad sampling arguments'), (1, 1, dict(temperature=0.0), 'bad sampling arguments'),
+])
+def test_decode_step_refuses_bad_arguments_without_a_gpu_and_names_its_form(form, sampled, kw, what):
+    from emo_disentanger_amd import _lib
+    a = _decode_step_args(form, sampled=sampled, **kw)
+    assert _lib.lib.emo_decode_step(ctypes.byref(a), None) == -1
+    msg = _lib.lib.emo_last_error().decode()
+    assert what in msg
+    assert msg.startswith('emo_decode_step[%s%s]: ' % (_FORM_NAME[form], ', sampled' if sampled else ''))
+    with pytest.raises(_lib.EmoError):
+        _lib.check(-1)
+
+
+def test_decode_step_refuses_an_all_zero_block_without_a_gpu():
+    from emo_disentanger_amd import _lib
+    a = _lib.DecodeStep()
+    assert _lib.lib.emo_decode_step(ctypes.byref(a), None) == -1
+    msg = _lib.lib.emo_last_error().decode()
+    assert msg.startswith('emo_decode_step[performer]: ') and 'null pointer' in msg
+    assert _lib.lib.emo_decode_step(None, None) == -1 and b'null argument block' in _lib.lib.emo_last_error()

@@ -1,4 +1,4 @@
-"""GPU: the one-launch Performer decode step (emo_performer_decode_step, csrc/emo_decode_persist.hip) against (a) the chain of launches it
+"""GPU: the one-launch decode step (emo_decode_step, csrc/emo_decode_persist.hip), Performer form first, against (a) the chain of launches it
 replaces (same bf16 arithmetic up to the LayerNorm fold and the reduction order: logits within 2 % of the logit range, recurrent state within
 1e-3 relative) and (b) the fp32 parity-mode engine, which is itself tied to the oracle's recurrent form (tests/test_gpu_generate.py) — bf16
 tolerance 5 % of the logit range.  Reference: the token loop of stage2_accompaniment/inference.py:250-277."""
@@ -10,10 +10,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-def _model(L, dtype, seed=0, scale=2.5):
+def _model(L, dtype, seed=0, scale=2.5, V=327):
     from emo_disentanger_amd.model.music_performer import MusicPerformer
     from oracle.weights import make_state_dict
-    V, H, d, dff, nf = 327, 8, 512, 2048, 128
+    H, d, dff, nf = 8, 512, 2048, 128
     sd = make_state_dict('performer', V, L, H, d, dff, favor_feature_dims=nf, seed=seed, scale=scale)
     m = MusicPerformer(V, L, H, d, dff, d, favor_feature_dims=nf, use_segment_emb=True, n_segment_types=2, compute_dtype=dtype, redraw='fixed')
     m.load_state_dict(sd)
@@ -71,7 +71,7 @@ def test_one_launch_step_matches_launch_chain_and_fp32(n, L, monkeypatch):
 @pytest.mark.parametrize('n', [4, 32])
 def test_one_launch_step_matches_oracle_recurrent_form(n, monkeypatch):
     """The launch `gen` times, directly against the ORACLE: teacher-force 64 tokens on 4 / 32 streams at d512 / L12 / H8 / F128 and compare
-    every step's logits of emo_performer_decode_step with oracle.model_ref.performer_forward(form='recurrent') — the token recurrence
+    every step's logits of emo_decode_step (form 0) with oracle.model_ref.performer_forward(form='recurrent') — the token recurrence
     S += phi(k) v^T, z += phi(k), out = phi(q) S / (phi(q) z + eps) that the cached loop of stage2_accompaniment/inference.py:250-277 runs —
     on the same tokens.  bf16 bound: 5 % of the logit range (the bound of the bf16 training-parity tests); greedy ids must agree wherever the
     oracle's top-2 margin exceeds twice that bound's measured counterpart."""
@@ -112,25 +112,33 @@ def test_one_launch_step_matches_oracle_recurrent_form(n, monkeypatch):
     assert torch.equal(got.argmax(-1)[safe], ref.argmax(-1)[safe])
 
 
-def test_one_launch_step_refuses_what_it_was_not_built_for():
+def _refused(match, **fields):
+    """ops.decode_step on a block filled by ops.decode_step_set from `fields` (over the common ones) must raise an EmoError matching `match`."""
     from emo_disentanger_amd import ops
     from emo_disentanger_amd._lib import EmoError
-    z = torch.zeros(16, device='cuda')
+    z = torch.zeros(1024, device='cuda')
     zi = torch.zeros(16, dtype=torch.int64, device='cuda')
-    ws = torch.zeros(ops.lib.emo_performer_decode_step_workspace_bytes() // 8, dtype=torch.int64, device='cuda')
-    lg = torch.zeros(4, 327, device='cuda')
-    with pytest.raises(EmoError, match='built for d_model 512'):
-        ops.performer_decode_step(zi, 1, zi, None, z, None, z, 1.0, 0, None, z, z, 327, lg, 4, 256, 8, 128, 2048, ws)
-    lg6 = torch.zeros(6, 327, device='cuda')
-    with pytest.raises(EmoError, match='multiple of 4'):
-        ops.performer_decode_step(zi, 1, zi, None, z, None, z, 1.0, 0, None, z, z, 327, lg6, 6, 512, 8, 128, 2048, ws)
+    ws = torch.zeros(ops.lib.emo_decode_step_workspace_bytes() // 8, dtype=torch.int64, device='cuda')
+    common = dict(layer_table=zi, n_layers=1, tok=zi, E=z, pe=z, emb_scale=1.0, pos0=0, wout_packed=z, bout=z, n_token=327, n_streams=4, d_model=512,
+                  n_head=8, n_feat=128, d_ff=2048, sync_ws=ws, eps=1e-6, ln_eps=1e-5)
+    common.update(fields)
+    common.setdefault('logits', torch.zeros(common['n_streams'], 327, device='cuda'))
+    args, held = ops.DecodeStep(), {}
+    ops.decode_step_set(args, held, **common)
+    with pytest.raises(EmoError, match=match):
+        ops.decode_step(args)
 
 
-# ------------------------------------------------------------------------------------------------ GPT-2 form (emo_gpt2_decode_step, r06)
-def _gpt2(L, dtype, seed=0, scale=2.5):
+def test_one_launch_step_refuses_what_it_was_not_built_for():
+    _refused('built for d_model 512', form=0, d_model=256)
+    _refused('multiple of 4', form=0, n_streams=6)
+
+
+# ------------------------------------------------------------------------------------------------ GPT-2 form (emo_decode_step form 1, r06)
+def _gpt2(L, dtype, seed=0, scale=2.5, V=327):
     from emo_disentanger_amd.model.music_gpt2 import MusicGPT2
     from oracle.weights import make_state_dict
-    V, H, d, dff = 327, 8, 512, 2048
+    H, d, dff = 8, 512, 2048
     sd = make_state_dict('gpt2', V, L, H, d, dff, seed=seed, scale=scale)
     m = MusicGPT2(V, L, H, d, dff, d, use_segment_emb=True, n_segment_types=2, compute_dtype=dtype)
     m.load_state_dict(sd)
@@ -153,7 +161,7 @@ def _run_gpt2(model, ptok, pseg, toks, segs, persistent, monkeypatch):
 
 @pytest.mark.parametrize('n,L,T0', [(4, 1, 24), (8, 3, 2), (32, 12, 300), (1, 2, 33), (5, 2, 257)])      # (1, 5: padded to groups of 4 streams)
 def test_gpt2_one_launch_step_matches_launch_chain_and_fp32(n, L, T0, monkeypatch):
-    """emo_gpt2_decode_step against the chain of launches it replaces (skinny GEMMs with folded LayerNorms + sattn_decode: the same bf16 arithmetic up
+    """The GPT-2 form of emo_decode_step against the chain of launches it replaces (skinny GEMMs with folded LayerNorms + sattn_decode: the same bf16 arithmetic up
     to the fold and the reduction order) and the fp32 parity-mode engine; the appended key / value rows must equal the chain's up to the bf16 rounding
     of their inputs.  Context lengths cover one row, a partial 256-row sweep, and several sweeps.  Reference loop: stage2_accompaniment/inference.py:250-277."""
     g = torch.Generator().manual_seed(15 + n)
@@ -250,16 +258,51 @@ def test_gpt2_one_launch_step_fills_the_cache_to_its_last_row(monkeypatch):
 
 
 def test_gpt2_one_launch_step_refuses_what_it_was_not_built_for():
-    from emo_disentanger_amd import ops
-    from emo_disentanger_amd._lib import EmoError
     z = torch.zeros(1024, device='cuda')
-    zi = torch.zeros(16, dtype=torch.int64, device='cuda')
-    ws = torch.zeros(ops.lib.emo_performer_decode_step_workspace_bytes() // 8, dtype=torch.int64, device='cuda')
-    lg = torch.zeros(4, 327, device='cuda')
-    with pytest.raises(EmoError, match='built for d_model 512'):
-        ops.gpt2_decode_step(zi, 1, zi, None, z, None, z, 1.0, 0, None, z[:512], 2048, z, z, 327, lg, 4, 256, 8, 2048, ws)
-    with pytest.raises(EmoError, match='KV cache of <= 2048 rows'):
-        ops.gpt2_decode_step(zi, 1, zi, None, z, None, z, 1.0, 0, None, z, 4096, z, z, 327, lg, 4, 512, 8, 2048, ws)
-    lg6 = torch.zeros(6, 327, device='cuda')
-    with pytest.raises(EmoError, match='multiple of 4'):
-        ops.gpt2_decode_step(zi, 1, zi, None, z, None, z, 1.0, 0, None, z, 2048, z, z, 327, lg6, 6, 512, 8, 2048, ws)
+    _refused('built for d_model 512', form=1, d_model=256, ln0=z[:512], kv_tmax=2048)
+    _refused('KV cache of <= 2048 rows', form=1, ln0=z, kv_tmax=4096)
+    _refused('multiple of 4', form=1, n_streams=6, ln0=z, kv_tmax=2048)
+
+
+# ------------------------------------------------------------------------------------------------ one argument block per engine
+def _phases(eng, prompts, toks, segs):
+    """Generator over the logits of: prefill, 3 steps, a SECOND prefill (new state tensors: the pointer table is rebuilt), one more step."""
+    (p0, s0), (p1, s1) = prompts
+    yield eng.prefill(p0, s0).float().clone()
+    for t in range(3):
+        yield eng.step(toks[:, t], segs[:, t]).float().clone()
+    yield eng.prefill(p1, s1).float().clone()
+    yield eng.step(toks[:, 3], segs[:, 3]).float().clone()
+
+
+def test_engines_alive_together_step_as_they_do_alone(monkeypatch):
+    """Every engine owns ONE long-lived argument block and rewrites a few of its fields per step.  Two Performer engines (4 streams, and 5 padded
+    to 8) and a GPT-2 engine, alive at once and stepped in turn, must produce the logits of fresh engines of the same models stepped alone, bit
+    for bit (same kernel, same inputs): a block shared between engines, or one that kept the address of the pointer table of before a prefill,
+    does not.  The step after the second prefill is compared with an engine that only ever saw that prefill."""
+    from emo_disentanger_amd import inference as inf
+    monkeypatch.setenv('EMO_DECODE_PERSISTENT', '1')
+    V, T0 = 40, 24
+    mp, (mg, _) = _model(1, 'bf16', V=V), _gpt2(1, 'bf16', V=V)
+    g = torch.Generator().manual_seed(77)
+
+    def inputs(n):
+        prompts = [(torch.randint(0, V - 1, (n, T0 + 3 * i), generator=g).cuda(), torch.randint(0, 2, (n, T0 + 3 * i), generator=g).cuda()) for i in range(2)]
+        return prompts, torch.randint(0, V - 1, (n, 4), generator=g).cuda(), torch.randint(0, 2, (n, 4), generator=g).cuda()
+
+    cases = [(lambda: inf.make_engine(mp, 4, redraw=False), inputs(4)), (lambda: inf.make_engine(mp, 5, redraw=False), inputs(5)),
+             (lambda: inf.make_engine(mg, 4), inputs(4))]
+    engines = [make() for make, _ in cases]
+    assert all(e.persist is not None for e in engines) and len({id(e.persist['args']) for e in engines}) == 3
+    together = list(zip(*[_phases(e, *inp) for e, (_, inp) in zip(engines, cases)]))          # phase by phase, the three engines in turn
+    for e in engines:
+        e.check_persistent()
+    for i, (make, (prompts, toks, segs)) in enumerate(cases):
+        first = make()
+        alone = list(_phases(first, prompts, toks, segs))
+        first.check_persistent()
+        fresh = make()                                               # the second prefill and its step, on an engine with no history
+        alone2 = [fresh.prefill(*prompts[1]).float().clone(), fresh.step(toks[:, 3], segs[:, 3]).float().clone()]
+        fresh.check_persistent()
+        for ph, lg in enumerate(alone + alone2):
+            assert torch.equal(lg, together[ph if ph < 6 else ph - 2][i]), (i, ph)

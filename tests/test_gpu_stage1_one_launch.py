@@ -1,4 +1,4 @@
-"""GPU: the stage-1 Transformer-XL token step as one persistent launch (emo_txl_decode_step, pd_step_kernel<2> of csrc/emo_decode_persist.hip)
+"""GPU: the stage-1 Transformer-XL token step as one persistent launch (emo_decode_step form 2, pd_step_kernel<2> of csrc/emo_decode_persist.hip)
 against (a) the chain of launches it replaces (PlainTransformer.decode_step: the same bf16 arithmetic up to the reduction order — logits within
 2 % of the logit range, appended key / value rows within 1e-2 relative norm), (b) the fp32 model's chain (5 %), (c) the oracle fed one token at a
 time with its mems (5 %), and through generate_lead_sheets(step='one_launch'): host grammar on the same device draws, graph replay = eager

@@ -1,4 +1,4 @@
-"""CPU: the host side of the stage-1 one-launch token step (emo_txl_decode_step): the head-major hand-off helper, the support predicate
+"""CPU: the host side of the stage-1 one-launch token step (emo_decode_step, form 2): the head-major hand-off helper, the support predicate
 condition by condition, the --step argument and the step= switch."""
 from types import SimpleNamespace
 
@@ -43,7 +43,7 @@ def test_support_predicate_names_the_first_failed_condition():
     for kw, n, what in cases:
         why = s1.one_launch_unsupported(_fake(**kw), n, device_ok=True)
         assert why is not None and what in why, (kw, n, why)
-    assert 'emo_txl_decode_step_supported' in s1.one_launch_unsupported(_fake(), 32, device_ok=False)
+    assert 'emo_decode_step_supported' in s1.one_launch_unsupported(_fake(), 32, device_ok=False)
     # the FIRST failed condition, in the documented order
     assert 'bf16' in s1.one_launch_unsupported(_fake(_compute_dtype=torch.float32, dec_n_head=4), 40, device_ok=False)
     assert len(s1.one_launch_conditions(_fake(), 32, device_ok=True)) == 12

@@ -4,7 +4,7 @@ against the device loop generate_lead_sheets at 1 and 32 streams (grammar launch
 Prints one JSON line.  Roofline figure: the weight bytes one token step streams (from the shapes) over the step time.
 Arguments: --events N (max_events per piece, default 512), --single-events N (default 256), --loop-only (the 32-stream device loop alone:
 the run a kernel-trace profile is taken of), --step chain | one-launch | both (the model step of the device loop: decode_step's chain of
-launches, the one persistent launch emo_txl_decode_step, or both timed in this process on the same seeds: keys streams_N_one_launch and
+launches, the one persistent launch emo_decode_step (form 2), or both timed in this process on the same seeds: keys streams_N_one_launch and
 one_launch_vs_chain_32_streams = chain ms per step / one-launch ms per step)."""
 import argparse
 import json

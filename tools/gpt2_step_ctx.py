@@ -1,4 +1,4 @@
-"""GPT-2 one-launch decode step (emo_gpt2_decode_step) timed at fixed context lengths: 32 streams, prefill CTX tokens, then K teacher-forced steps
+"""GPT-2 one-launch decode step (emo_decode_step, form 1) timed at fixed context lengths: 32 streams, prefill CTX tokens, then K teacher-forced steps
 between two events.  ms per step vs context = the latency floor of the 60 phases + the KV-cache stream (12 layers x 2 x ctx x 1 KB per stream)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
