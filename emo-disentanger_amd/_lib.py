@@ -41,6 +41,17 @@ class DecodeStep(ctypes.Structure):
                 ('ln0', c_p), ('kv_tmax', c_l), ('lens', c_p), ('mem_len', c_l), ('n_dist', c_l), ('r_w_bias', c_p), ('r_r_bias', c_p)]
 
 
+class GrammarStep(ctypes.Structure):
+    """emo_grammar_step_t (emo_hip.h), field for field: the argument block of the three device grammar steps.  Pointer fields hold raw device addresses."""
+    _fields_ = [('kind', ctypes.c_int32), ('n_rows', c_l), ('logits', c_p), ('n_token', c_l), ('temperature', c_f), ('top_p', c_f),
+                ('u_steps', c_p), ('n_u', c_l), ('ld_u', c_l), ('ev_flags', c_p), ('ev_beat', c_p), ('params', c_p), ('state', c_p),
+                ('seq', c_p), ('ld_seq', c_l), ('running', c_p),
+                ('key_temperature', c_f), ('key_top_p', c_f), ('tok_out', c_p), ('seg_out', c_p), ('max_len', c_l), ('pad', c_l),
+                ('segs', c_p), ('lead_tok', c_p), ('lead_off', c_p), ('track_full', c_l), ('window', c_l), ('rows', c_p), ('win_tok', c_p), ('win_seg', c_p)]
+
+
+GRAMMAR_TXL, GRAMMAR_ACC, GRAMMAR_ACC_WINDOW = 0, 1, 2      # emo_hip.h: EMO_GRAMMAR_*
+
 _SIG = {
     'emo_version': (c_i, []),
     'emo_build_flags': (c_i, []),
@@ -92,9 +103,8 @@ _SIG = {
     'emo_argmax': (c_i, [c_p, c_l, c_l, c_p, c_p]),
     'emo_sample_nucleus': (c_i, [c_p, c_l, c_l, c_f, c_f, c_p, c_p, c_p]),
     'emo_sample_nucleus_step': (c_i, [c_p, c_l, c_l, c_f, c_f, c_p, c_p, c_p, c_l, c_l, c_p, c_p]),
-    'emo_txl_grammar_step': (c_i, [c_p, c_l, c_l, c_f, c_f, c_f, c_f, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_p]),
-    'emo_acc_grammar_step': (c_i, [c_p, c_l, c_l, c_f, c_f, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_p, c_p, c_p, c_p]),
-    'emo_acc_window_step': (c_i, [c_p, c_l, c_l, c_f, c_f, c_p, c_l, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_p]),
+    'emo_grammar_step_size': (c_i, []),
+    'emo_grammar_step': (c_i, [ctypes.POINTER(GrammarStep), c_p]),
     'emo_accuracy_counts': (c_i, [c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_p, c_p]),
     'emo_sumsq': (c_i, [c_p, c_l, c_p, c_p]),
     'emo_clip_coef': (c_i, [c_p, c_f, c_f, c_p, c_p, c_p]),
@@ -115,12 +125,11 @@ _SIG = {
 for _name, (_res, _args) in _SIG.items():
     _fn = getattr(lib, _name)          # AttributeError here = header/library mismatch
     _fn.restype, _fn.argtypes = _res, _args
-if lib.emo_epilogue_size() != ctypes.sizeof(Epilogue):      # a stale libemo_hip.so (or a stale mirror above) would read garbage pointers
-    raise ImportError('libemo_hip.so was built with an emo_epilogue_t of %d bytes, this binding has %d: rebuild (python -c "import __graft_entry__ as g; g.build()")'
-                      % (lib.emo_epilogue_size(), ctypes.sizeof(Epilogue)))
-if lib.emo_decode_step_size() != ctypes.sizeof(DecodeStep):
-    raise ImportError('libemo_hip.so was built with an emo_decode_step_t of %d bytes, this binding has %d: rebuild (python -c "import __graft_entry__ as g; g.build()")'
-                      % (lib.emo_decode_step_size(), ctypes.sizeof(DecodeStep)))
+for _cname, _size, _mirror in (('emo_epilogue_t', lib.emo_epilogue_size, Epilogue), ('emo_decode_step_t', lib.emo_decode_step_size, DecodeStep),
+                               ('emo_grammar_step_t', lib.emo_grammar_step_size, GrammarStep)):
+    if _size() != ctypes.sizeof(_mirror):                   # a stale libemo_hip.so (or a stale mirror above) would read garbage pointers
+        raise ImportError('libemo_hip.so was built with an %s of %d bytes, this binding has %d: rebuild (python -c "import __graft_entry__ as g; g.build()")'
+                          % (_cname, _size(), ctypes.sizeof(_mirror)))
 
 
 class EmoError(RuntimeError):

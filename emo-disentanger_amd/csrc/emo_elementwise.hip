@@ -16,7 +16,7 @@ void emo_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* emo_last_error(void) { return g_err; }
-extern "C" int emo_version(void) { return 101; }
+extern "C" int emo_version(void) { return 102; }
 extern "C" int emo_build_flags(void) {
 #ifdef EMO_EXPERIMENTAL
     return 1;

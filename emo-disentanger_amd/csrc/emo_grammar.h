@@ -1,0 +1,17 @@
+// What the three kinds of emo_grammar_step (emo_stage1_gen.hip: TXL; emo_stage2_gen.hip: ACC, ACC_WINDOW and the entry) share besides the draw.
+// Each kernel takes the caller's emo_grammar_step_t by value as its one parameter (a field is fetched from the kernel arguments where it is used,
+// so the fields of the other kinds cost nothing) and runs as one 512-thread workgroup per row.
+#pragma once
+#include "emo_nucleus.h"
+
+// The opening of every kind: the stream's state and params words (n_st / n_pr of them) into LDS, one barrier.  Thread 0 alone touches the
+// stream's state in memory afterwards: the other threads decide from this copy, so a write of thread 0 can never change the path (and the
+// barrier count) of a thread that has not read yet.
+__device__ __forceinline__ void emo_grammar_open(const int32_t* st, int n_st, const int32_t* pr, int n_pr, int32_t* sst, int32_t* spr, int tid) {
+    if (tid < n_st) sst[tid] = st[tid];
+    if (tid < n_pr) spr[tid] = pr[tid];
+    __syncthreads();
+}
+
+// The launch of the TXL kind (emo_stage1_gen.hip), for emo_grammar_step, which has checked the block.
+int emo_txl_grammar_launch(const emo_grammar_step_t& a, emo_stream_t stream);

@@ -787,7 +787,7 @@ def generate_streams(model, prompt_tok, prompt_seg, n_new, temp=1.1, top_p=0.9, 
 
 
 # ------------------------------------------------------------------------------------------------ device loop (stage 2, grammar on)
-# Mirrors of include/emo_hip.h (emo_acc_grammar_step): per-token event bits, per-stream parameter and state words, stream status.
+# Mirrors of include/emo_hip.h (emo_grammar_step, kinds ACC / ACC_WINDOW): per-token event bits, per-stream parameter and state words, stream status.
 ACC_EV_BEAT, ACC_EV_TRACK_LS, ACC_EV_PAD, ACC_EV_EOS = 1, 2, 4, 8
 ACC_P_TARGET_BARS, ACC_P_MAX_EVENTS, ACC_P_SKIP_CHECK, ACC_P_BAR0, ACC_P_N_BARS = range(5)
 ACC_S_STATUS, ACC_S_LEN, ACC_S_CONSUMED, ACC_S_BARS, ACC_S_CUR_POS, ACC_S_FAILED, ACC_S_DRAWS, ACC_S_ACCEPTED = range(8)
@@ -818,7 +818,7 @@ def acc_event_tables(idx2event, V):
 
 def pack_lead_sheets(lead_sheets):
     """n lead sheets (lists of bars, each a list of ids) -> (tokens int64, offsets int32, first-bar index per stream, bar count per stream,
-    longest bar): bar j of stream i is tokens[offsets[bar0[i] + j] : offsets[bar0[i] + j + 1]] (emo_hip.h: emo_acc_grammar_step)."""
+    longest bar): bar j of stream i is tokens[offsets[bar0[i] + j] : offsets[bar0[i] + j + 1]] (emo_hip.h: EMO_GRAMMAR_ACC)."""
     toks, offs, bar0, nbars = [], [], [], []
     for lead in lead_sheets:
         bar0.append(len(offs))
@@ -855,7 +855,7 @@ def _stream_result(status, ids, out_of_draws, overflow, still_running):
 class AccompanimentLoop:
     """Device state of generate_accompaniments: the decode engine (prefilled with the common prefix, positions on the device), the logits of
     the last step, the uniform table, the grammar tables, the packed lead sheets, per-stream parameters / state and token / segment rows, and
-    the running count; one_step() = emo_acc_grammar_step + the engine step."""
+    the running count; one_step() = emo_grammar_step (kind ACC) + the engine step."""
 
     def __init__(self, model, event2idx, idx2event, lead_sheets, primers, max_events=10000, skip_check=False, max_bars=None, temp=1.2, top_p=0.9,
                  seed=0, n_u=None, persistent=True, redraw=True):
@@ -892,6 +892,12 @@ class AccompanimentLoop:
         self.tok = torch.zeros(n, dtype=torch.int64, device=dev)
         self.segv = torch.ones(n, dtype=torch.int64, device=dev)
         self.logits = torch.empty(n, V, dtype=torch.float32, device=dev)
+        # the grammar launch's argument block (emo_hip.h: emo_grammar_step_t), written once: _gheld keeps what its addresses point to alive
+        self._gargs, self._gheld = ops.GrammarStep(kind=ops.GRAMMAR_ACC), {}
+        ops.block_set(self._gargs, self._gheld, n_rows=n, n_token=V, ld_u=n, temperature=self.temp, top_p=self.top_p, max_len=self.W,
+                      track_full=self.track_full, pad=self.pad, logits=self.logits, u_steps=self.U, ev_flags=self.ev_flags, ev_beat=self.ev_beat,
+                      lead_tok=self.lead_tok, lead_off=self.lead_off, params=self.params, state=self.state, seq=self.seq, segs=self.segs,
+                      tok_out=self.tok, seg_out=self.segv, running=self.running)
         with torch.no_grad():
             if model.kind == 'performer':
                 eng = PerformerDecodeEngine(model, n, redraw=redraw, persistent=persistent)
@@ -908,8 +914,7 @@ class AccompanimentLoop:
         self.replayed = (0, 0.0)
 
     def grammar(self):
-        ops.acc_grammar_step(self.logits, self.temp, self.top_p, self.U, self.ev_flags, self.ev_beat, self.lead_tok, self.lead_off, self.params,
-                             self.state, self.seq, self.segs, self.W, self.track_full, self.pad, self.tok, self.segv, self.running)
+        ops.grammar_step(self._gargs)
 
     def one_step(self):
         self.grammar()
@@ -1003,7 +1008,7 @@ class WindowedLoop:
     """The ACC_WINDOW streams of a finished AccompanimentLoop, continued together on the device (the reference's sliding window, inference.py
     :252-277, which _resume_windowed runs one stream and one host round trip at a time).  One step = one forward over the streams' last W tokens,
     model(win_tok, seg_inp=win_seg, keep_last_only=True) on [m, W] — positions restart at 0, so nothing carries over between steps — and
-    emo_acc_window_step: the draw, the in-launch redraws, the grammar, and the next window of every stream still running.  Streams are indexed
+    emo_grammar_step (kind ACC_WINDOW): the draw, the in-launch redraws, the grammar, and the next window of every stream still running.  Streams are indexed
     by their place j among the WINDOW streams (self.idx[j] = the stream of the first loop): seq / segs [m0, width] (copies, wide enough for the
     whole piece), params / state [m0, 8] (status RUNNING again, draw counter 0), the uniform table U [n_u, m0] of this phase alone, seeded with
     (seed, WINDOW_TAG).  The host reads the running count once every `steps_per_poll` steps (EMO_GEN_GRAPH_STEPS, default 16; steps a stream
@@ -1041,6 +1046,12 @@ class WindowedLoop:
         self.logits = torch.zeros(m0, self.model.n_token, dtype=torch.float32, device=dev)
         self.fwd_kw = {'attn_kwargs': {'omit_feature_map_draw': True}} if self.model.kind == 'performer' else {}
         self.batch_rows, self.steps, self.seconds = [], 0, 0.0
+        # the windowed step's argument block (emo_hip.h: emo_grammar_step_t), written once for the full batch; _set_rows keeps n_rows / rows current
+        self._gargs, self._gheld = ops.GrammarStep(kind=ops.GRAMMAR_ACC_WINDOW), {}
+        ops.block_set(self._gargs, self._gheld, n_rows=m0, n_token=self.model.n_token, ld_u=m0, temperature=self.temp, top_p=self.top_p, window=W,
+                      track_full=loop.track_full, logits=self.logits, u_steps=self.U, ev_flags=loop.ev_flags, ev_beat=loop.ev_beat,
+                      lead_tok=loop.lead_tok, lead_off=loop.lead_off, params=self.params, state=self.state, seq=self.seq, segs=self.segs, win_tok=self.win_tok,
+                      win_seg=self.win_seg, running=self.running)
         self._set_rows(list(range(m0)))
 
     def _set_rows(self, rows):
@@ -1050,6 +1061,9 @@ class WindowedLoop:
         self.m = len(rows)
         self.rows_host = list(rows)
         self.rows = torch.tensor(rows, dtype=torch.int32, device=self.dev)
+        # the only fields that change: logits[:m], win_tok[:m] and win_seg[:m] keep their base addresses.  The block is read at call time and this
+        # loop is eager (no captured launch holds the old values), so the next one_step runs on the new rows.
+        ops.block_set(self._gargs, self._gheld, n_rows=self.m, rows=self.rows)
         r = self.rows.long()
         col = (self.state[r, ACC_S_LEN].long() - self.W).view(-1, 1) + torch.arange(self.W, device=self.dev).view(1, -1)
         self.win_tok[:self.m] = self.seq[r].gather(1, col)
@@ -1058,9 +1072,7 @@ class WindowedLoop:
     def one_step(self):
         m = self.m
         self.logits[:m].copy_(self.model(self.win_tok[:m], seg_inp=self.win_seg[:m], keep_last_only=True, **self.fwd_kw))
-        lp = self.loop
-        ops.acc_window_step(self.logits[:m], self.temp, self.top_p, self.U, self.rows, lp.ev_flags, lp.ev_beat, lp.lead_tok, lp.lead_off, self.params,
-                            self.state, self.seq, self.segs, self.W, lp.track_full, self.win_tok[:m], self.win_seg[:m], self.running)
+        ops.grammar_step(self._gargs)
         self.batch_rows.append(m)
         self.steps += 1
 
@@ -1109,7 +1121,7 @@ class WindowedLoop:
 def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, max_events=10000, skip_check=False, max_bars=None, temp=1.2, top_p=0.9,
                             inadmissibles=None, seed=0, use_graph=True, best_of=1, window='host'):
     """The throughput path of generate_conditional_batch: the same arguments (no per-stream samplers) and result per stream, every draw and
-    the grammar of _Stream.offer on the device (emo_acc_grammar_step), each token step = grammar launch + one engine step (the one-launch
+    the grammar of _Stream.offer on the device (emo_grammar_step), each token step = grammar launch + one engine step (the one-launch
     persistent step where the engine has one), k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS, default 16) and replayed until
     every stream has finished.  Draws come from a uniform table [4 * max_dec_inp_len, n] seeded with `seed` (like generate_streams), so ids
     are not NumPy-RNG-identical to generate_conditional_batch; they equal the host grammar driven by the same device draws.  A stream that
@@ -1125,7 +1137,7 @@ def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, m
     floats, NaN for a failed candidate], 'candidates': [N results]}.  best_of = 1 is the path above, draw for draw.
 
     window = 'device': the streams that reach the window are finished together on the device by a WindowedLoop (one batched full-window
-    forward and one emo_acc_window_step per draw, no host round trip per token) instead of one at a time by _resume_windowed.  Every id up to
+    forward and one windowed emo_grammar_step per draw, no host round trip per token) instead of one at a time by _resume_windowed.  Every id up to
     a stream's handoff is the one window = 'host' gives; past it the draws come from the windowed phase's own uniform table (seeded with (seed,
     WINDOW_TAG)), so the continuation equals the host grammar on those draws, not the NumPy draws of _resume_windowed."""
     if window not in ('host', 'device'):

@@ -10,11 +10,11 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, BF16, F32, MUL_BITMASK, MUL_DGELU, MUL_DGELU_NEW, MUL_NONE, MUL_NONZERO, DecodeStep, Epilogue, check,
+from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, BF16, F32, MUL_BITMASK, MUL_DGELU, MUL_DGELU_NEW, MUL_NONE, MUL_NONZERO, GRAMMAR_ACC, GRAMMAR_ACC_WINDOW, GRAMMAR_TXL, DecodeStep, Epilogue, GrammarStep, check,
                    dtype_code, lib, ptr, stream)
 
 __all__ = ['gemm', 'colsum', 'embed_fwd', 'embed_bwd', 'layernorm_fwd', 'layernorm_bwd', 'dropout_apply', 'favor_attn_fwd',
-           'favor_attn_bwd', 'favor_decode_step', 'decode_step', 'decode_step_set', 'DecodeStep', 'favor_draw_omega', 'softmax_attn_fwd', 'softmax_attn_bwd', 'softmax_attn_decode', 'relpos_attn_fwd', 'relpos_attn_bwd', 'relpos_attn_decode', 'xent_fwd',
+           'favor_attn_bwd', 'favor_decode_step', 'decode_step', 'decode_step_set', 'block_set', 'DecodeStep', 'GrammarStep', 'grammar_step', 'favor_draw_omega', 'softmax_attn_fwd', 'softmax_attn_bwd', 'softmax_attn_decode', 'relpos_attn_fwd', 'relpos_attn_bwd', 'relpos_attn_decode', 'xent_fwd',
            'xent_bwd', 'token_scores', 'xent_bwd_rows', 'argmax', 'sample_nucleus', 'sample_nucleus_step', 'txl_grammar_step', 'acc_grammar_step', 'acc_window_step', 'accuracy_counts', 'sumsq', 'clip_coef', 'adam_step', 'cast', 'add_bias2',
            'ACT_NONE', 'ACT_RELU', 'ACT_GELU_NEW', 'ACT_GELU', 'MUL_NONE', 'MUL_NONZERO', 'MUL_DGELU_NEW', 'MUL_DGELU', 'MUL_BITMASK', 'gemm_bitmask_ok', 'gemm_lna_ok', 'bitmask_rows', 'favor_bwd_dn_ok', 'ffn_fwd', 'ffn_fwd_ok']
 
@@ -338,29 +338,66 @@ def favor_decode_step(q, k, v, omega, state_S, state_z, H, eps=1e-6):
     return out
 
 
-_F32 = torch.float32
+TXL_PARAM_WORDS = TXL_STATE_WORDS = ACC_PARAM_WORDS = ACC_STATE_WORDS = 8     # emo_hip.h: EMO_TXL_* / EMO_ACC_*_WORDS
+_F32, _I32, _I64 = torch.float32, torch.int32, torch.int64
+
+
+def _is(t, dtype):
+    return t.dtype == dtype and t.is_contiguous()
+
+
 # layout a tensor must have before its address goes into a DecodeStep field: field -> check(args, tensor)
 _DECODE_STEP_LAYOUT = {
-    'logits': lambda a, t: t.dtype == _F32 and t.is_contiguous() and t.shape == (a.n_streams, a.n_token),
-    'ln0': lambda a, t: t.dtype == _F32 and t.is_contiguous() and t.numel() == 2 * a.d_model,
-    'u_steps': lambda a, t: t.dtype == _F32 and t.is_contiguous() and t.shape[1] == a.n_real,
-    'step': lambda a, t: t.dtype == torch.int64,
-    'tok_out': lambda a, t: t.dtype == torch.int64,
-    'seq': lambda a, t: t.dtype == torch.int64 and t.stride(1) == 1,
+    'logits': lambda a, t: _is(t, _F32) and t.shape == (a.n_streams, a.n_token),
+    'ln0': lambda a, t: _is(t, _F32) and t.numel() == 2 * a.d_model,
+    'u_steps': lambda a, t: _is(t, _F32) and t.shape[1] == a.n_real,
+    'step': lambda a, t: t.dtype == _I64,
+    'tok_out': lambda a, t: t.dtype == _I64,
+    'seq': lambda a, t: t.dtype == _I64 and t.stride(1) == 1,
     'lens': lambda a, t: t.numel() == a.n_streams,
-    'r_w_bias': lambda a, t: t.dtype == _F32 and t.is_contiguous(),
-    'r_r_bias': lambda a, t: t.dtype == _F32 and t.is_contiguous(),
+    'r_w_bias': lambda a, t: _is(t, _F32),
+    'r_r_bias': lambda a, t: _is(t, _F32),
 }
 _DECODE_STEP_I64 = ('tok', 'seg', 'pos_ids', 'lens')          # int64 vectors, made contiguous (_c)
+# the same for a GrammarStep, against the numbers of the block: n_rows (n, or the m rows of the windowed batch), n_token, ld_u = the number of
+# streams, window (0 outside the windowed kind), and ld_seq, which `seq` sets: hand over seq before segs
+_GRAMMAR_STEP_LAYOUT = {
+    'logits': lambda a, t: _is(t, _F32) and t.shape == (a.n_rows, a.n_token),
+    'u_steps': lambda a, t: _is(t, _F32) and t.dim() == 2 and t.shape[1] == a.ld_u,
+    'ev_flags': lambda a, t: _is(t, _I32) and t.numel() >= a.n_token,
+    'ev_beat': lambda a, t: _is(t, _I32) and t.numel() >= a.n_token,
+    'params': lambda a, t: _is(t, _I32) and t.shape == (a.ld_u, ACC_PARAM_WORDS),
+    'state': lambda a, t: _is(t, _I32) and t.shape == (a.ld_u, ACC_STATE_WORDS),
+    'running': lambda a, t: _is(t, _I32) and t.numel() >= 1,
+    'seq': lambda a, t: _is(t, _I64) and t.dim() == 2 and t.shape[0] == a.ld_u and t.shape[1] >= a.window,
+    'segs': lambda a, t: _is(t, _I64) and t.shape == (a.ld_u, a.ld_seq),
+    'lead_tok': lambda a, t: _is(t, _I64) and t.numel() >= 1,
+    'lead_off': lambda a, t: _is(t, _I32) and t.numel() >= 1,
+    'tok_out': lambda a, t: _is(t, _I64) and t.numel() == a.n_rows,
+    'seg_out': lambda a, t: _is(t, _I64) and t.numel() == a.n_rows,
+    # (values in [0, ld_u): checked by the caller on the host — WindowedLoop._set_rows; the kernel skips a row outside that range)
+    'rows': lambda a, t: _is(t, _I32) and t.numel() == a.n_rows,
+    'win_tok': lambda a, t: _is(t, _I64) and t.shape == (a.n_rows, a.window),
+    'win_seg': lambda a, t: _is(t, _I64) and t.shape == (a.n_rows, a.window),
+}
+# per struct: its name in messages, the layout table, the int64 vectors, and the numbers a tensor brings with it (field -> (number, of tensor))
+_BLOCKS = {
+    DecodeStep: ('decode step', _DECODE_STEP_LAYOUT, _DECODE_STEP_I64,
+                 {'seq': ('ld_seq', lambda t: t.stride(0)), 'sync_ws': ('sync_ws_bytes', lambda t: t.numel() * t.element_size())}),
+    GrammarStep: ('grammar step', _GRAMMAR_STEP_LAYOUT, (),
+                  {'seq': ('ld_seq', lambda t: t.shape[1]), 'u_steps': ('n_u', lambda t: t.shape[0])}),
+}
 
 
-def decode_step_set(args, held, **fields):
-    """Write fields of a DecodeStep (emo_hip.h: emo_decode_step_t): numbers as they are, tensors (or None) as device addresses after the layout
-    check of the field; `seq` also sets ld_seq, `sync_ws` also sets sync_ws_bytes.  The struct holds raw addresses, so the rule of _c() applies to
-    its owner: `held` (field -> tensor) is the owner's dict that keeps every tensor whose address is in the struct alive, the contiguous copies
-    made here included.  A tensor that `held` already has for the field is the one the struct points to, checked when it went in: it is not
-    looked at again (a token loop hands over the same buffers step after step).  Numbers are written first: a tensor may be checked against a
-    size given in the same call."""
+def block_set(args, held, **fields):
+    """Write fields of an argument block, a DecodeStep or a GrammarStep (emo_hip.h: emo_decode_step_t, emo_grammar_step_t): numbers as they are,
+    tensors (or None) as device addresses after the layout check of the field in the struct's table; a tensor that brings a number with it sets
+    that too (`seq` ld_seq; DecodeStep `sync_ws` sync_ws_bytes; GrammarStep `u_steps` n_u).  The struct holds raw addresses, so the rule of _c()
+    applies to its owner: `held` (field -> tensor) is the owner's dict that keeps every tensor whose address is in the struct alive, the
+    contiguous copies made here included.  A tensor that `held` already has for the field is the one the struct points to, checked when it went
+    in: it is not looked at again (a token loop hands over the same buffers step after step).  Numbers are written first: a tensor may be
+    checked against a size given in the same call."""
+    what, layout, i64, brings = _BLOCKS[type(args)]
     tensors = None
     for k, v in fields.items():
         if v is None or isinstance(v, torch.Tensor):
@@ -371,16 +408,18 @@ def decode_step_set(args, held, **fields):
             setattr(args, k, v)
     for k, t in tensors or ():
         if t is not None:
-            if k in _DECODE_STEP_I64:
+            if k in i64:
                 t = _c(t)                                         # (a copy is held in the caller's place, so the next call makes a new one)
-            ok = _DECODE_STEP_LAYOUT.get(k)
-            assert ok is None or ok(args, t), 'decode step: bad dtype / layout of %s' % k
+            ok = layout.get(k)
+            assert ok is None or ok(args, t), '%s: bad dtype / layout of %s' % (what, k)
         held[k] = t
         setattr(args, k, ptr(t))
-        if k == 'seq':
-            args.ld_seq = 0 if t is None else t.stride(0)
-        elif k == 'sync_ws':
-            args.sync_ws_bytes = 0 if t is None else t.numel() * t.element_size()
+        if k in brings:
+            number, of = brings[k]
+            setattr(args, number, 0 if t is None else of(t))
+
+
+decode_step_set = block_set
 
 
 def decode_step(args):
@@ -598,75 +637,53 @@ def sample_nucleus_step(logits, temperature, top_p, u_steps, step, seq=None, col
     return out
 
 
-TXL_PARAM_WORDS = TXL_STATE_WORDS = 8     # emo_hip.h: EMO_TXL_PARAM_WORDS / EMO_TXL_STATE_WORDS
+def grammar_step(args):
+    """One device grammar step (emo_hip.h: emo_grammar_step) from a prepared GrammarStep.  Allocation-free (hipGraph capture); the state, token
+    and output tensors of the block are updated in place."""
+    check(lib.emo_grammar_step(ctypes.byref(args), stream()))
+
+
+def _grammar_once(kind, **fields):
+    """The one-shot form: a fresh block through block_set (every layout check), one call."""
+    args = GrammarStep(kind=kind)
+    block_set(args, {}, **fields)
+    grammar_step(args)
 
 
 def txl_grammar_step(logits, temperature, top_p, key_temperature, key_top_p, u_steps, ev_flags, ev_beat, params, state, seq, tok_out, running):
-    """One stage-1 sample-and-grammar step of n streams (include/emo_hip.h emo_txl_grammar_step): logits fp32 [n, V], u_steps fp32 [n_u, n],
-    ev_flags / ev_beat int32 [V], params / state int32 [n, 8], seq int64 [n, W], tok_out int64 [n], running int32 [1].  Allocation-free
-    (hipGraph capture); state, seq, tok_out and running are updated in place."""
+    """One stage-1 sample-and-grammar step of n streams (include/emo_hip.h, EMO_GRAMMAR_TXL): logits fp32 [n, V], u_steps fp32 [n_u, n],
+    ev_flags / ev_beat int32 [V], params / state int32 [n, 8], seq int64 [n, W], tok_out int64 [n], running int32 [1].  state, seq, tok_out
+    and running are updated in place."""
     n, V = logits.shape
-    assert logits.is_contiguous() and logits.dtype == torch.float32
-    assert u_steps.dtype == torch.float32 and u_steps.is_contiguous() and u_steps.dim() == 2 and u_steps.shape[1] == n
-    for t, dt in ((ev_flags, torch.int32), (ev_beat, torch.int32), (params, torch.int32), (state, torch.int32), (running, torch.int32),
-                  (seq, torch.int64), (tok_out, torch.int64)):
-        assert t.dtype == dt and t.is_contiguous()
-    assert ev_flags.numel() >= V and ev_beat.numel() >= V and running.numel() >= 1 and tok_out.numel() == n
-    assert params.shape == (n, TXL_PARAM_WORDS) and state.shape == (n, TXL_STATE_WORDS) and seq.dim() == 2 and seq.shape[0] == n
-    check(lib.emo_txl_grammar_step(ptr(logits), n, V, temperature, top_p, key_temperature, key_top_p, ptr(u_steps), u_steps.shape[0], ptr(ev_flags),
-                                   ptr(ev_beat), ptr(params), ptr(state), ptr(seq), seq.shape[1], ptr(tok_out), ptr(running), stream()))
+    _grammar_once(GRAMMAR_TXL, n_rows=n, n_token=V, ld_u=n, temperature=temperature, top_p=top_p, key_temperature=key_temperature,
+                  key_top_p=key_top_p, logits=logits, u_steps=u_steps, ev_flags=ev_flags, ev_beat=ev_beat, params=params, state=state, seq=seq,
+                  tok_out=tok_out, running=running)
     return tok_out
-
-
-ACC_PARAM_WORDS = ACC_STATE_WORDS = 8     # emo_hip.h: EMO_ACC_PARAM_WORDS / EMO_ACC_STATE_WORDS
 
 
 def acc_grammar_step(logits, temperature, top_p, u_steps, ev_flags, ev_beat, lead_tok, lead_off, params, state, seq, segs, max_len, track_full, pad,
                      tok_out, seg_out, running):
-    """One stage-2 sample-and-grammar step of n streams (include/emo_hip.h emo_acc_grammar_step): logits fp32 [n, V], u_steps fp32 [n_u, n],
+    """One stage-2 sample-and-grammar step of n streams (include/emo_hip.h, EMO_GRAMMAR_ACC): logits fp32 [n, V], u_steps fp32 [n_u, n],
     ev_flags / ev_beat int32 [V], lead_tok int64 (flat), lead_off int32, params / state int32 [n, 8], seq / segs int64 [n, W], tok_out / seg_out
-    int64 [n], running int32 [1].  Allocation-free (hipGraph capture); state, seq, segs, tok_out, seg_out and running are updated in place."""
+    int64 [n], running int32 [1].  state, seq, segs, tok_out, seg_out and running are updated in place."""
     n, V = logits.shape
-    assert V <= 1024 and temperature > 0
-    assert logits.is_contiguous() and logits.dtype == torch.float32
-    assert u_steps.dtype == torch.float32 and u_steps.is_contiguous() and u_steps.dim() == 2 and u_steps.shape[1] == n
-    for t, dt in ((ev_flags, torch.int32), (ev_beat, torch.int32), (lead_off, torch.int32), (params, torch.int32), (state, torch.int32),
-                  (running, torch.int32), (lead_tok, torch.int64), (seq, torch.int64), (segs, torch.int64), (tok_out, torch.int64), (seg_out, torch.int64)):
-        assert t.dtype == dt and t.is_contiguous()
-    assert ev_flags.numel() >= V and ev_beat.numel() >= V and running.numel() >= 1 and tok_out.numel() == n and seg_out.numel() == n
-    assert params.shape == (n, ACC_PARAM_WORDS) and state.shape == (n, ACC_STATE_WORDS)
-    assert seq.dim() == 2 and seq.shape[0] == n and segs.shape == seq.shape and lead_tok.numel() >= 1 and lead_off.numel() >= 1
-    check(lib.emo_acc_grammar_step(ptr(logits), n, V, temperature, top_p, ptr(u_steps), u_steps.shape[0], ptr(ev_flags), ptr(ev_beat), ptr(lead_tok),
-                                   ptr(lead_off), ptr(params), ptr(state), ptr(seq), ptr(segs), seq.shape[1], max_len, track_full, pad, ptr(tok_out),
-                                   ptr(seg_out), ptr(running), stream()))
+    _grammar_once(GRAMMAR_ACC, n_rows=n, n_token=V, ld_u=n, temperature=temperature, top_p=top_p, max_len=max_len, track_full=track_full, pad=pad,
+                  logits=logits, u_steps=u_steps, ev_flags=ev_flags, ev_beat=ev_beat, lead_tok=lead_tok, lead_off=lead_off, params=params, state=state,
+                  seq=seq, segs=segs, tok_out=tok_out, seg_out=seg_out, running=running)
     return tok_out
 
 
 def acc_window_step(logits, temperature, top_p, u_steps, rows, ev_flags, ev_beat, lead_tok, lead_off, params, state, seq, segs, window, track_full,
                     win_tok, win_seg, running):
-    """One stage-2 draw-and-grammar step of m streams past the window (include/emo_hip.h emo_acc_window_step): logits fp32 [m, V], win_tok /
+    """One stage-2 draw-and-grammar step of m streams past the window (include/emo_hip.h, EMO_GRAMMAR_ACC_WINDOW): logits fp32 [m, V], win_tok /
     win_seg int64 [m, window]; rows int32 [m] (or None: row b is stream b) names each row's stream in u_steps fp32 [n_u, n], params / state
-    int32 [n, 8] and seq / segs int64 [n, width].  Allocation-free; state, seq, segs, win_tok, win_seg and running are updated in place."""
+    int32 [n, 8] and seq / segs int64 [n, width].  state, seq, segs, win_tok, win_seg and running are updated in place."""
     m, V = logits.shape
     n = state.shape[0]
-    assert V <= 1024 and temperature > 0
-    assert logits.is_contiguous() and logits.dtype == torch.float32
-    assert u_steps.dtype == torch.float32 and u_steps.is_contiguous() and u_steps.dim() == 2 and u_steps.shape[1] == n
-    for t, dt in ((ev_flags, torch.int32), (ev_beat, torch.int32), (lead_off, torch.int32), (params, torch.int32), (state, torch.int32),
-                  (running, torch.int32), (lead_tok, torch.int64), (seq, torch.int64), (segs, torch.int64), (win_tok, torch.int64), (win_seg, torch.int64)):
-        assert t.dtype == dt and t.is_contiguous()
-    assert ev_flags.numel() >= V and ev_beat.numel() >= V and running.numel() >= 1
-    assert params.shape == (n, ACC_PARAM_WORDS) and state.shape == (n, ACC_STATE_WORDS)
-    assert seq.dim() == 2 and seq.shape[0] == n and segs.shape == seq.shape and seq.shape[1] >= window and lead_tok.numel() >= 1 and lead_off.numel() >= 1
-    assert win_tok.shape == (m, window) and win_seg.shape == (m, window)
-    if rows is None:
-        assert m <= n
-    else:
-        # (values in [0, n): checked by the caller on the host — WindowedLoop._set_rows; the kernel skips a row outside that range)
-        assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.numel() == m
-    check(lib.emo_acc_window_step(ptr(logits), m, V, temperature, top_p, ptr(u_steps), u_steps.shape[0], n, ptr(rows), ptr(ev_flags), ptr(ev_beat),
-                                  ptr(lead_tok), ptr(lead_off), ptr(params), ptr(state), ptr(seq), ptr(segs), seq.shape[1], window, track_full,
-                                  ptr(win_tok), ptr(win_seg), ptr(running), stream()))
+    assert rows is not None or m <= n
+    _grammar_once(GRAMMAR_ACC_WINDOW, n_rows=m, n_token=V, ld_u=n, temperature=temperature, top_p=top_p, window=window, track_full=track_full,
+                  logits=logits, u_steps=u_steps, rows=rows, ev_flags=ev_flags, ev_beat=ev_beat, lead_tok=lead_tok, lead_off=lead_off, params=params,
+                  state=state, seq=seq, segs=segs, win_tok=win_tok, win_seg=win_seg, running=running)
     return win_tok
 
 

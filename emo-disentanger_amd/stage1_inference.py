@@ -105,7 +105,7 @@ def generate_plain_xl(model, event2idx, idx2event, max_bars=160, max_events=2048
 
 
 # ------------------------------------------------------------------------------------------------ lock-step batches
-# Mirrors of include/emo_hip.h (emo_txl_grammar_step): per-token event bits, per-stream parameter and state words, stream status.
+# Mirrors of include/emo_hip.h (emo_grammar_step, kind TXL): per-token event bits, per-stream parameter and state words, stream status.
 EV_BEAT, EV_BAR, EV_PAD, EV_EOS, EV_KEY, EV_MAJOR, EV_MINOR = 1, 2, 4, 8, 16, 32, 64
 P_MAX_BARS, P_MAX_EVENTS, P_PRIMER_LEN, P_KEYED, P_KEY_RULE, P_EMO_MODE = range(6)
 S_STATUS, S_LEN, S_ACCEPTED, S_BEAT, S_BARS, S_FAILED, S_FEED, S_DRAWS = range(8)
@@ -344,7 +344,7 @@ class OneLaunchStep(_EngineBase):
 
 class LeadSheetLoop:
     """Device state of generate_lead_sheets: a TXLMemory, the logits of the last step, the uniform table, the grammar tables and
-    per-stream parameters / state, the output sequences and the running count; one_step() = emo_txl_grammar_step + decode_step
+    per-stream parameters / state, the output sequences and the running count; one_step() = emo_grammar_step (kind TXL) + decode_step
     (step='chain') or + emo_decode_step, form 2 (step='one_launch': OneLaunchStep on the head-major copy of the prefill's memory)."""
 
     def __init__(self, model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
@@ -389,6 +389,11 @@ class LeadSheetLoop:
         self.U = uniform_table(self.max_len - self.L0 + 1, n, seed, dev)      # at most one draw per step, one more at the end
         self.tok = self.seq[:, self.L0 - 1].contiguous()      # (a valid id in every row before the first grammar step)
         self.logits = torch.empty(n, V, dtype=torch.float32, device=dev)
+        # the grammar launch's argument block (emo_hip.h: emo_grammar_step_t), written once: _gheld keeps what its addresses point to alive
+        self._gargs, self._gheld = ops.GrammarStep(kind=ops.GRAMMAR_TXL), {}
+        ops.block_set(self._gargs, self._gheld, n_rows=n, n_token=V, ld_u=n, temperature=self.temp, top_p=self.top_p, key_temperature=KEY_TEMP,
+                      key_top_p=KEY_TOP_P, logits=self.logits, u_steps=self.U, ev_flags=self.ev_flags, ev_beat=self.ev_beat, params=self.params,
+                      state=self.state, seq=self.seq, tok_out=self.tok, running=self.running)
         with torch.no_grad():
             h, _, _ = model._prefill(self.seq[:, :self.L0].t(), self.mem)
             self.logits.copy_(model._logits(h.view(n, self.L0, -1)[:, -1].contiguous()))
@@ -400,8 +405,7 @@ class LeadSheetLoop:
         self.replayed = (0, 0.0)
 
     def grammar(self):
-        ops.txl_grammar_step(self.logits, self.temp, self.top_p, KEY_TEMP, KEY_TOP_P, self.U, self.ev_flags, self.ev_beat, self.params, self.state,
-                             self.seq, self.tok, self.running)
+        ops.grammar_step(self._gargs)
 
     def one_step(self):
         self.grammar()
@@ -453,7 +457,7 @@ class LeadSheetLoop:
 def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
                          representation='functional', key_determine=None, seed=0, use_graph=True, step='chain'):
     """The throughput path of generate_plain_xl_batch: the same arguments and result shape, every draw and the grammar on the device
-    (emo_txl_grammar_step), each token step = grammar launch + decode_step, k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS,
+    (emo_grammar_step), each token step = grammar launch + decode_step, k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS,
     default 16) and replayed until every stream has finished.  Draws come from a uniform table seeded with `seed` (like generate_streams),
     so the ids are not NumPy-RNG-identical to the reference; they equal the host grammar driven by the same device draws.
     step='one_launch' runs the model step as one persistent launch (emo_decode_step, form 2) and raises EmoError where it was not built for the model.

@@ -466,7 +466,7 @@ int emo_sample_nucleus(const float* logits, int64_t rows, int64_t V, float tempe
 int emo_sample_nucleus_step(const float* logits, int64_t rows, int64_t V, float temperature,
                             float top_p, const float* u_steps, int64_t* step, int64_t* seq,
                             int64_t ld_seq, int64_t col0, int64_t* out, emo_stream_t stream);
-/* Stage-1 lead-sheet generation (stage1_compose/inference_utils.py generate_plain_xl :51-134, match_emotion_key :137-142): the draw and the
+/* EMO_GRAMMAR_TXL.  Stage-1 lead-sheet generation (stage1_compose/inference_utils.py generate_plain_xl :51-134, match_emotion_key :137-142): the draw and the
  * grammar of one lock-step token step for n streams, one 512-thread workgroup per stream, all loop state in device memory (graph-capturable).
  * A stream that is RUNNING and has fed its whole primer (state[FEED] >= params[PRIMER_LEN]) draws from logits[r] (fp32 [n, V], V <= 1024) with
  * uniform u_steps[state[DRAWS] * n + r] (u_steps [n_u, n]) — the device code of emo_sample_nucleus, so the same id —, at key_temperature /
@@ -487,12 +487,7 @@ enum { EMO_TXL_S_STATUS = 0, EMO_TXL_S_LEN = 1 /* tokens in seq[r] */, EMO_TXL_S
        EMO_TXL_S_FAILED = 5 /* rejected Beats in a row */, EMO_TXL_S_FEED = 6 /* next primer token to feed */, EMO_TXL_S_DRAWS = 7, EMO_TXL_STATE_WORDS = 8 };
 enum { EMO_TXL_RUNNING = 0, EMO_TXL_DONE = 1, EMO_TXL_STUCK = 2, EMO_TXL_KEY_ERROR = 3, EMO_TXL_OVERFLOW = 4 /* seq or u_steps exhausted */ };
 enum { EMO_TXL_EV_BEAT = 1, EMO_TXL_EV_BAR = 2, EMO_TXL_EV_PAD = 4, EMO_TXL_EV_EOS = 8, EMO_TXL_EV_KEY = 16, EMO_TXL_EV_MAJOR = 32, EMO_TXL_EV_MINOR = 64 };
-int emo_txl_grammar_step(const float* logits, int64_t n, int64_t V, float temperature, float top_p,
-                         float key_temperature, float key_top_p, const float* u_steps, int64_t n_u,
-                         const int32_t* ev_flags, const int32_t* ev_beat, const int32_t* params,
-                         int32_t* state, int64_t* seq, int64_t ld_seq, int64_t* tok_out, int32_t* running,
-                         emo_stream_t stream);
-/* Stage-2 accompaniment generation (stage2_accompaniment/inference.py generate_conditional :231-327): the draw and the grammar of one lock-step
+/* EMO_GRAMMAR_ACC.  Stage-2 accompaniment generation (stage2_accompaniment/inference.py generate_conditional :231-327): the draw and the grammar of one lock-step
  * token step for n streams, one 512-thread workgroup per stream, all loop state in device memory (graph-capturable).  seq / segs (int64, pitch
  * ld_seq) hold each stream's `generated` / segment ids; state[LEN] of them are valid, state[CONSUMED] have been fed to the model.  Per stream r:
  *   not RUNNING                 -> tok_out[r] = pad, seg_out[r] = 1;
@@ -518,12 +513,7 @@ enum { EMO_ACC_S_STATUS = 0, EMO_ACC_S_LEN = 1 /* tokens in seq[r] */, EMO_ACC_S
        EMO_ACC_S_ACCEPTED = 7 /* accepted draws */, EMO_ACC_STATE_WORDS = 8 };
 enum { EMO_ACC_RUNNING = 0, EMO_ACC_DONE = 1, EMO_ACC_STUCK = 2, EMO_ACC_WINDOW = 3, EMO_ACC_OUT_OF_DRAWS = 4, EMO_ACC_OVERFLOW = 5 };
 enum { EMO_ACC_EV_BEAT = 1, EMO_ACC_EV_TRACK_LS = 2, EMO_ACC_EV_PAD = 4, EMO_ACC_EV_EOS = 8 };
-int emo_acc_grammar_step(const float* logits, int64_t n, int64_t V, float temperature, float top_p,
-                         const float* u_steps, int64_t n_u, const int32_t* ev_flags, const int32_t* ev_beat,
-                         const int64_t* lead_tok, const int32_t* lead_off, const int32_t* params, int32_t* state,
-                         int64_t* seq, int64_t* segs, int64_t ld_seq, int64_t max_len, int64_t track_full,
-                         int64_t pad, int64_t* tok_out, int64_t* seg_out, int32_t* running, emo_stream_t stream);
-/* The same draw and grammar for streams PAST the window (stage2_accompaniment/inference.py:252-277: the model input is the last max_dec_inp_len
+/* EMO_GRAMMAR_ACC_WINDOW.  The same draw and grammar for streams PAST the window (stage2_accompaniment/inference.py:252-277: the model input is the last max_dec_inp_len
  * tokens of `generated`, positions restarting at 0 on every step, so nothing is fed token by token and an injected bar is simply part of the next
  * input): one forward over [m, window] per draw, then this launch.  Row b of the batch (logits fp32 [m, V], win_tok / win_seg int64 [m, window])
  * belongs to stream r = rows[b] (int32 [m]; NULL: r = b), which indexes params, state, seq, segs and the column of u_steps (fp32 [n_u, ld_u],
@@ -531,15 +521,50 @@ int emo_acc_grammar_step(const float* logits, int64_t n, int64_t V, float temper
  * without moving any state.  A row whose r is outside [0, ld_u) is skipped.
  *   not RUNNING                 -> nothing is drawn, win_tok / win_seg[b] stay as they are;
  *   state[LEN] < window         -> OVERFLOW (a caller error: there is no full window to read);
- *   otherwise the draw, the in-launch redraws and the grammar of emo_acc_grammar_step (the same device code), state[CONSUMED] untouched; a
+ *   otherwise the draw, the in-launch redraws and the grammar of the ACC kind (the same device code), state[CONSUMED] untouched; a
  *   stream still RUNNING then gets its next model input, win_tok / win_seg[b, 0 .. window) = seq / segs[r, LEN - window .. LEN).
- * OUT_OF_DRAWS, OVERFLOW (ld_seq too short for the accepted tokens) and *running behave as in emo_acc_grammar_step. */
-int emo_acc_window_step(const float* logits, int64_t m, int64_t V, float temperature, float top_p,
-                        const float* u_steps, int64_t n_u, int64_t ld_u, const int32_t* rows,
-                        const int32_t* ev_flags, const int32_t* ev_beat, const int64_t* lead_tok,
-                        const int32_t* lead_off, const int32_t* params, int32_t* state, int64_t* seq,
-                        int64_t* segs, int64_t ld_seq, int64_t window, int64_t track_full, int64_t* win_tok,
-                        int64_t* win_seg, int32_t* running, emo_stream_t stream);
+ * OUT_OF_DRAWS, OVERFLOW (ld_seq too short for the accepted tokens) and *running behave as in the ACC kind. */
+/* The three grammar steps above are the kinds of ONE entry with ONE argument block, as emo_decode_step_t is for the model step beside them in
+ * every generation loop.  `kind` selects the kernel; a field that a kind does not read is ignored by it, whatever it holds (the comment of each
+ * field names its readers; none = all three).  The block is read AT CALL TIME: its values travel as the launch's arguments, so under hipGraph
+ * capture they are baked into the captured launch, exactly as positional arguments would be, and a later change of the block reaches only later
+ * calls (and later captures).  The struct holds raw device addresses: its owner keeps the memory alive. */
+enum { EMO_GRAMMAR_TXL = 0, EMO_GRAMMAR_ACC = 1, EMO_GRAMMAR_ACC_WINDOW = 2 };   /* what each does: the three comments above (n = n_rows, V = n_token) */
+typedef struct {
+    int32_t kind;              /* EMO_GRAMMAR_* */
+    /* --- all kinds */
+    int64_t n_rows;            /* workgroups launched: TXL, ACC the n streams; ACC_WINDOW the m rows of the batch */
+    const float* logits;       /* f32 [n_rows, n_token] */
+    int64_t n_token;           /* V <= 1024 */
+    float temperature, top_p;  /* temperature > 0 */
+    const float* u_steps;      /* f32 [n_u, ld_u] uniforms: draw d of stream r takes u_steps[d * ld_u + r] */
+    int64_t n_u, ld_u;         /* ld_u = the number of streams (TXL, ACC: >= n_rows) */
+    const int32_t* ev_flags;   /* int32 [n_token]: EMO_TXL_EV_* / EMO_ACC_EV_* bits */
+    const int32_t* ev_beat;    /* int32 [n_token] */
+    const int32_t* params;     /* int32 [streams, 8] */
+    int32_t* state;            /* int32 [streams, 8] */
+    int64_t* seq;              /* int64 [streams, ld_seq] */
+    int64_t ld_seq;
+    int32_t* running;          /* int32 [1] */
+    /* --- kind-specific (ordered so that the fields one kind reads lie together: a kernel fetches its arguments in runs) */
+    float key_temperature, key_top_p;   /* TXL: the key draw; key_temperature > 0 */
+    int64_t* tok_out;          /* TXL, ACC: int64 [n_rows] */
+    int64_t* seg_out;          /* ACC: int64 [n_rows] */
+    int64_t max_len;           /* ACC: > 0 */
+    int64_t pad;               /* ACC */
+    int64_t* segs;             /* ACC, ACC_WINDOW: int64 [streams, ld_seq] */
+    const int64_t* lead_tok;   /* ACC, ACC_WINDOW */
+    const int32_t* lead_off;   /* ACC, ACC_WINDOW */
+    int64_t track_full;        /* ACC, ACC_WINDOW */
+    int64_t window;            /* ACC_WINDOW: 0 < window <= ld_seq */
+    const int32_t* rows;       /* ACC_WINDOW: int32 [n_rows] or NULL */
+    int64_t* win_tok;          /* ACC_WINDOW: int64 [n_rows, window] */
+    int64_t* win_seg;          /* ACC_WINDOW: int64 [n_rows, window] */
+} emo_grammar_step_t;
+/* sizeof(emo_grammar_step_t) as the library was built (a binding checks its mirror against it, as with emo_epilogue_size) */
+int emo_grammar_step_size(void);
+/* Messages name the kind: "emo_grammar_step[txl]: ", "emo_grammar_step[acc]: ", "emo_grammar_step[acc_window]: ". */
+int emo_grammar_step(const emo_grammar_step_t* args, emo_stream_t stream);
 /* counts[0..5] += {nonpad, nonpad&correct, chord, chord&correct, melody, melody&correct} (train.py:184-193) */
 int emo_accuracy_counts(const float* logits, const int64_t* tgt, const int64_t* chord,
                         const int64_t* melody, int64_t M, int64_t V, int64_t pad, int64_t* counts,

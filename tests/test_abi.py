@@ -99,3 +99,72 @@ def test_decode_step_refuses_an_all_zero_block_without_a_gpu():
     msg = _lib.lib.emo_last_error().decode()
     assert msg.startswith('emo_decode_step[performer]: ') and 'null pointer' in msg
     assert _lib.lib.emo_decode_step(None, None) == -1 and b'null argument block' in _lib.lib.emo_last_error()
+
+
+def test_grammar_step_struct_mirror_has_the_library_size():
+    # the ctypes mirror of emo_grammar_step_t, as for the two structs above
+    from emo_disentanger_amd import _lib
+    assert _lib.lib.emo_grammar_step_size() == ctypes.sizeof(_lib.GrammarStep)
+
+
+_KIND_NAME = {0: 'txl', 1: 'acc', 2: 'acc_window'}
+
+
+def _grammar_step_args(kind, **kw):
+    """A block that passes every host check of `kind` (pointer fields: small fake addresses, 16-byte aligned — validation never dereferences
+    them, and no refusal below gets as far as the launch), with the fields of `kw` changed."""
+    from emo_disentanger_amd import _lib
+    a = _lib.GrammarStep()
+    for name, ctype in _lib.GrammarStep._fields_:
+        if ctype is _lib.c_p:
+            setattr(a, name, 0x1000)
+    a.kind, a.n_rows, a.n_token, a.n_u, a.ld_u, a.ld_seq, a.max_len, a.window = kind, 3, 327, 8, 3, 64, 32, 32
+    a.temperature, a.top_p, a.key_temperature, a.key_top_p = 1.2, 0.9, 1.1, 0.97
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+@pytest.mark.parametrize('kind, kw, what', [
+    (0, dict(n_token=2000), 'V must be <= 1024 (got 2000)'), (1, dict(n_token=2000), 'V must be <= 1024 (got 2000)'),
+    (2, dict(n_token=2000), 'V must be <= 1024 (got 2000)'),
+    (0, dict(temperature=0.0), 'temperatures must be > 0'), (1, dict(temperature=0.0), 'temperature must be > 0'),
+    (2, dict(temperature=0.0), 'temperature must be > 0'),
+    (0, dict(key_temperature=0.0), 'temperatures must be > 0'),
+    (2, dict(window=65), 'bad sizes'),
+    (0, dict(tok_out=None), 'null pointer'), (1, dict(seg_out=None), 'null pointer'), (2, dict(win_seg=None), 'null pointer'),
+    (1, dict(max_len=0), 'bad sizes'), (0, dict(ld_u=2), 'bad sizes'),
+])
+def test_grammar_step_refuses_bad_arguments_without_a_gpu_and_names_its_kind(kind, kw, what):
+    from emo_disentanger_amd import _lib
+    a = _grammar_step_args(kind, **kw)
+    assert _lib.lib.emo_grammar_step(ctypes.byref(a), None) == -1
+    msg = _lib.lib.emo_last_error().decode()
+    assert what in msg
+    assert msg.startswith('emo_grammar_step[%s]: ' % _KIND_NAME[kind])
+    with pytest.raises(_lib.EmoError):
+        _lib.check(-1)
+
+
+def test_grammar_step_refuses_an_empty_a_missing_and_an_unknown_block_without_a_gpu():
+    from emo_disentanger_amd import _lib
+    a = _lib.GrammarStep()
+    assert _lib.lib.emo_grammar_step(ctypes.byref(a), None) == -1
+    msg = _lib.lib.emo_last_error().decode()
+    assert msg.startswith('emo_grammar_step[txl]: ') and 'null pointer' in msg
+    assert _lib.lib.emo_grammar_step(None, None) == -1 and b'null argument block' in _lib.lib.emo_last_error()
+    assert _lib.lib.emo_grammar_step(ctypes.byref(_grammar_step_args(7)), None) == -1
+    msg = _lib.lib.emo_last_error().decode()
+    assert msg.startswith('emo_grammar_step: ') and 'kind 7' in msg
+
+
+def test_a_kind_ignores_the_fields_of_the_other_kinds():
+    # a block is refused for its own kind's fields only: the windowed kind's NULL win_tok does not stop TXL or ACC getting past the pointer
+    # check (each goes on to its next refusal, a size of its own)
+    from emo_disentanger_amd import _lib
+    for kind, kw in ((0, dict(segs=None, lead_tok=None, seg_out=None, rows=None, win_tok=None, win_seg=None, max_len=0, window=0)),
+                     (1, dict(rows=None, win_tok=None, win_seg=None, window=0, key_temperature=0.0)),
+                     (2, dict(rows=None, tok_out=None, seg_out=None, max_len=0, key_temperature=0.0))):
+        a = _grammar_step_args(kind, n_u=0, **kw)
+        assert _lib.lib.emo_grammar_step(ctypes.byref(a), None) == -1
+        assert _lib.lib.emo_last_error().decode() == 'emo_grammar_step[%s]: bad sizes' % _KIND_NAME[kind]

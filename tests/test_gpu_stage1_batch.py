@@ -207,6 +207,45 @@ def test_grammar_kernel_matches_the_host_grammar_step_by_step():
     assert [h.draws for h in hosts] == [len(s) for s in scripts]          # every scripted word was drawn, nothing more
 
 
+def test_a_prepared_grammar_block_reused_over_steps_equals_the_one_shot_wrapper():
+    # three streams: 0 finished before the first step, 1 still feeding its primer (4 steps, then draws), 2 drawing from the first step with its draw
+    # counter at 4 of a uniform table of 8 rows: its fifth step finds the table used up -> OVERFLOW.  A GrammarStep filled once and launched six
+    # times leaves, word for word, what ops.txl_grammar_step (a fresh block per call) leaves on its own copies of the same tensors.
+    from emo_disentanger_amd import ops, stage1_inference as s1
+    g, _, e2i, i2e = _fixture()
+    V, n, W, dev = len(i2e), 3, 16, 'cuda'
+    primers = [['Emotion_Q2'], ['Emotion_Positive', 'Key_C', 'Bar_None', 'Beat_0', 'Chord_I_M'], ['Emotion_Q1']]
+    flags, beat = s1.event_tables(i2e, V)
+    seq, params, state = np.zeros((n, W), np.int64), np.zeros((n, 8), np.int32), np.zeros((n, 8), np.int32)
+    for i, p in enumerate(primers):
+        ids = [e2i[e] for e in p]
+        seq[i, :len(ids)] = ids
+        params[i, :6] = 8, 100, len(ids), 1, 0, s1.emotion_mode(i2e, ids[0])
+        state[i, [s1.S_STATUS, s1.S_LEN, s1.S_FEED]] = s1.RUNNING, len(ids), 1
+    state[0, s1.S_STATUS], state[2, s1.S_DRAWS] = s1.DONE, 4
+    T = lambda a: torch.from_numpy(a).to(dev)      # noqa: E731
+    shared = dict(u_steps=torch.rand(8, n, device=dev, generator=torch.Generator(device=dev).manual_seed(5)), ev_flags=T(flags), ev_beat=T(beat),
+                  params=T(params))
+    fresh = lambda: dict(state=T(state), seq=T(seq), tok_out=torch.full((n,), -1, dtype=torch.long, device=dev),      # noqa: E731
+                         running=torch.tensor([2], dtype=torch.int32, device=dev))
+    one, blk = fresh(), fresh()
+    logits = torch.randn(6, n, V, device=dev, generator=torch.Generator(device=dev).manual_seed(6)) * 2.0
+    logits[:, :, [e2i['EOS_None'], e2i['Bar_None']]] = -60.0          # no stream ends on its own within the six steps
+    lg = torch.empty(n, V, device=dev)
+    args, held = ops.GrammarStep(kind=ops.GRAMMAR_TXL), {}
+    ops.block_set(args, held, n_rows=n, n_token=V, ld_u=n, temperature=1.2, top_p=0.9, key_temperature=1.1, key_top_p=0.97, logits=lg, **shared, **blk)
+    for t in range(6):
+        lg.copy_(logits[t])
+        ops.txl_grammar_step(lg, 1.2, 0.9, 1.1, 0.97, shared['u_steps'], shared['ev_flags'], shared['ev_beat'], shared['params'], one['state'],
+                             one['seq'], one['tok_out'], one['running'])
+        ops.grammar_step(args)
+        for k in one:
+            assert torch.equal(one[k], blk[k]), (t, k, one[k].tolist(), blk[k].tolist())
+    st = blk['state'].cpu().numpy()
+    assert st[:, s1.S_STATUS].tolist() == [s1.DONE, s1.RUNNING, s1.OVERFLOW] and int(blk['running'].item()) == 1
+    assert st[:, s1.S_DRAWS].tolist() == [0, 2, 8] and st[1, s1.S_FEED] >= 1 and (blk['tok_out'].cpu().numpy()[1:] >= 0).all()
+
+
 STREAMS16 = [  # primer, representation, key_determine, max_bars, max_events, prompt_bars
     (['Emotion_%s' % e], 'functional', kd, mb, me, None) for e, kd, mb, me in
     [('Q1', None, 3, 60), ('Q2', 'rule', 4, 50), ('Positive', None, 2, 40), ('Negative', 'rule', 3, 70), ('Q1', 'rule', 3, 60),

@@ -180,6 +180,84 @@ def test_grammar_kernel_matches_the_host_grammar_step_by_step():
     assert len(hosts[3].s.generated) == 15 and len(hosts[7].s.generated) == W_UNIT
 
 
+def _three_streams(inf, g, e2i, i2e, dev, n_u=8):
+    """Three streams of UNIT on the device, for the argument-block tests: 0 finished before the first launch, 1 still feeding a primer two tokens
+    longer than the common prefix, 2 drawing from the first launch; a uniform table of n_u rows.  -> (what the launches only read, a maker of
+    fresh copies of what they write), both keyed by the fields of emo_grammar_step_t."""
+    pick = [UNIT[0], UNIT[5], UNIT[6]]
+    V, n = len(i2e), len(pick)
+    leads = [[list(g['lead'][j]) for j in u[0]] for u in pick]
+    st = [inf._Stream(e2i, ld, u[1], u[2]) for u, ld in zip(pick, leads)]
+    L0 = min(len(s.generated) for s in st)
+    flags, beat = inf.acc_event_tables(i2e, V)
+    toks, offs, bar0, nbars, longest = inf.pack_lead_sheets(leads)
+    width = W_UNIT + longest + 2
+    seq, segs = np.zeros((n, width), np.int64), np.zeros((n, width), np.int64)
+    params, state = np.zeros((n, 8), np.int32), np.zeros((n, 8), np.int32)
+    for i, (s, u) in enumerate(zip(st, pick)):
+        k = len(s.generated)
+        seq[i, :k], segs[i, :k] = s.generated, s.seg
+        params[i, :5] = s.target_bars, u[3], u[4], bar0[i], nbars[i]
+        state[i, [inf.ACC_S_STATUS, inf.ACC_S_LEN, inf.ACC_S_CONSUMED]] = inf.ACC_RUNNING, k, L0
+    state[0, inf.ACC_S_STATUS] = inf.ACC_DONE
+    T = lambda a: torch.from_numpy(a).to(dev)      # noqa: E731
+    shared = dict(u_steps=torch.rand(n_u, n, device=dev, generator=torch.Generator(device=dev).manual_seed(5)), ev_flags=T(flags), ev_beat=T(beat),
+                  lead_tok=T(toks), lead_off=T(offs), params=T(params))
+    fresh = lambda: dict(state=T(state), seq=T(seq), segs=T(segs), tok_out=torch.full((n,), -1, dtype=torch.long, device=dev),      # noqa: E731
+                         seg_out=torch.full((n,), -1, dtype=torch.long, device=dev), running=torch.tensor([2], dtype=torch.int32, device=dev))
+    return shared, fresh
+
+
+def test_a_prepared_grammar_block_reused_over_steps_equals_the_one_shot_wrapper():
+    # stream 2 accepts one word, then draws PAD until its table of 8 uniforms is used up (OUT_OF_DRAWS inside the second launch); stream 1 feeds
+    # two primer tokens, then draws from random logits.  A GrammarStep filled once and launched six times leaves, word for word, what
+    # ops.acc_grammar_step (a fresh block per call) leaves on its own copies of the same tensors.
+    from emo_disentanger_amd import inference as inf, ops
+    g, e2i, i2e = _vocab()
+    V, n, dev = len(i2e), 3, 'cuda'
+    shared, fresh = _three_streams(inf, g, e2i, i2e, dev)
+    one, blk = fresh(), fresh()
+    logits = torch.randn(6, n, V, device=dev, generator=torch.Generator(device=dev).manual_seed(6)) * 2.0
+    logits[0, 2, e2i['Note_Octave_4']] = 60.0
+    logits[1:, 2, e2i['PAD_None']] = 60.0
+    lg = torch.empty(n, V, device=dev)
+    tf, pad = e2i['Track_Full'], e2i['PAD_None']
+    args, held = ops.GrammarStep(kind=ops.GRAMMAR_ACC), {}
+    ops.block_set(args, held, n_rows=n, n_token=V, ld_u=n, temperature=1.2, top_p=0.9, max_len=W_UNIT, track_full=tf, pad=pad, logits=lg, **shared, **blk)
+    for t in range(6):
+        lg.copy_(logits[t])
+        ops.acc_grammar_step(lg, 1.2, 0.9, shared['u_steps'], shared['ev_flags'], shared['ev_beat'], shared['lead_tok'], shared['lead_off'],
+                             shared['params'], one['state'], one['seq'], one['segs'], W_UNIT, tf, pad, one['tok_out'], one['seg_out'], one['running'])
+        ops.grammar_step(args)
+        for k in one:
+            assert torch.equal(one[k], blk[k]), (t, k, one[k].tolist(), blk[k].tolist())
+    st = blk['state'].cpu().numpy()
+    assert st[0, inf.ACC_S_STATUS] == inf.ACC_DONE and st[2, inf.ACC_S_STATUS] == inf.ACC_OUT_OF_DRAWS and st[2, inf.ACC_S_DRAWS] == 8
+    assert st[2, inf.ACC_S_ACCEPTED] == 1 and st[1, inf.ACC_S_DRAWS] >= 1 and st[0, inf.ACC_S_DRAWS] == 0
+    assert blk['tok_out'].cpu().tolist()[0::2] == [pad, pad] and blk['seg_out'].cpu().tolist()[0::2] == [1, 1]
+
+
+def test_the_block_setter_refuses_a_bad_layout_when_the_tensor_enters_the_block():
+    # the asserts of the former per-call wrappers, now made once: a tensor of the wrong shape, stride or dtype never gets its address into a
+    # GrammarStep (no launch is made here)
+    from emo_disentanger_amd import inference as inf, ops
+    g, e2i, i2e = _vocab()
+    V, n, dev = len(i2e), 3, 'cuda'
+    shared, fresh = _three_streams(inf, g, e2i, i2e, dev)
+    good = dict(shared, logits=torch.zeros(n, V, device=dev), **fresh())
+    numbers = dict(n_rows=n, n_token=V, ld_u=n, temperature=1.2, top_p=0.9, max_len=W_UNIT, track_full=e2i['Track_Full'], pad=e2i['PAD_None'])
+    wide = torch.zeros(n, 2 * good['seq'].shape[1], dtype=torch.int64, device=dev)
+    for field, bad in (('state', good['state'][:, :7].contiguous()), ('seq', wide[:, ::2]), ('ev_flags', good['ev_flags'].long()),
+                       ('u_steps', torch.zeros(8, n + 1, device=dev))):
+        args, held = ops.GrammarStep(kind=ops.GRAMMAR_ACC), {}
+        with pytest.raises(AssertionError, match='grammar step: bad dtype / layout of %s' % field):
+            ops.block_set(args, held, **numbers, **dict(good, **{field: bad}))
+        assert field not in held and getattr(args, field) is None                  # (a c_void_p field reads as None while it is NULL)
+    args, held = ops.GrammarStep(kind=ops.GRAMMAR_ACC), {}
+    ops.block_set(args, held, **numbers, **good)
+    assert args.state == good['state'].data_ptr() and args.ld_seq == good['seq'].shape[1] and args.n_u == 8 and held['segs'] is good['segs']
+
+
 # ------------------------------------------------------------------------------------------------ the device loop against the host grammar
 def _host_grammar_loop(inf, model, e2i, i2e, leads, primers, U, max_events, skip_check, temp, top_p, max_bars=None):
     """The same engine, ops.sample_nucleus on each stream's own column of U at its own draw counter, _Stream.offer on the host."""

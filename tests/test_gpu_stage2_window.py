@@ -205,6 +205,59 @@ def test_window_kernel_matches_the_host_grammar_launch_by_launch():
     assert hosts[7].accepted >= 3 and hosts[8].accepted >= 3
 
 
+def test_a_prepared_window_block_reused_and_compacted_equals_the_one_shot_wrapper():
+    # three streams at the handoff: 0 finished before the first launch, 1 drawing from random logits, 2 accepting four words and then drawing PAD
+    # until its table of 8 uniforms is used up (OUT_OF_DRAWS inside its fifth launch).  The batch is m = 2 rows, rows = [2, 0]; after three
+    # steps it is compacted to rows = [2] through the setter, which rewrites n_rows and rows in place (what WindowedLoop._set_rows does).  A
+    # GrammarStep filled once leaves, word for word, what ops.acc_window_step (a fresh block per call) leaves on its own copies of the tensors.
+    from emo_disentanger_amd import inference as inf, ops
+    g, e2i, i2e = _vocab()
+    pick = [WIN_UNIT[3], WIN_UNIT[7], WIN_UNIT[4]]
+    V, n, dev = len(i2e), len(pick), 'cuda'
+    leads = [[list(g['lead'][j]) for j in u[0]] for u in pick]
+    flags, beat = inf.acc_event_tables(i2e, V)
+    toks, offs, bar0, nbars, longest = inf.pack_lead_sheets(leads)
+    hosts = [HostWin(inf, e2i, i2e, ld, u[1], u[2], u[3], u[4], W_WIN, WIDTH_WIN, e2i[FILL], done=u[5]) for u, ld in zip(pick, leads)]
+    seq, segs = np.zeros((n, WIDTH_WIN), np.int64), np.zeros((n, WIDTH_WIN), np.int64)
+    params, state = np.zeros((n, 8), np.int32), np.zeros((n, 8), np.int32)
+    for i, (h, u) in enumerate(zip(hosts, pick)):
+        k = len(h.s.generated)
+        seq[i, :k], segs[i, :k] = h.s.generated, h.s.seg
+        params[i, :5] = h.s.target_bars, u[3], u[4], bar0[i], nbars[i]
+        for w, v in h.state().items():
+            state[i, w] = v
+    T = lambda a: torch.from_numpy(a).to(dev)      # noqa: E731
+    shared = dict(u_steps=torch.rand(8, n, device=dev, generator=torch.Generator(device=dev).manual_seed(5)), ev_flags=T(flags), ev_beat=T(beat),
+                  lead_tok=T(toks), lead_off=T(offs), params=T(params))
+    fresh = lambda: dict(state=T(state), seq=T(seq), segs=T(segs), win_tok=torch.full((2, W_WIN), -7, dtype=torch.long, device=dev),      # noqa: E731
+                         win_seg=torch.full((2, W_WIN), -7, dtype=torch.long, device=dev), running=torch.tensor([2], dtype=torch.int32, device=dev))
+    one, blk = fresh(), fresh()
+    logits = torch.randn(6, 2, V, device=dev, generator=torch.Generator(device=dev).manual_seed(6)) * 2.0
+    logits[:3, 0, e2i['Note_Velocity_60']] = 60.0
+    logits[3, 0, e2i['Chord_I_M']] = 60.0
+    logits[4:, 0, e2i['PAD_None']] = 60.0
+    lg = torch.empty(2, V, device=dev)
+    tf = e2i['Track_Full']
+    rows2, rows1 = (torch.tensor(r, dtype=torch.int32, device=dev) for r in ([2, 0], [2]))
+    args, held = ops.GrammarStep(kind=ops.GRAMMAR_ACC_WINDOW), {}
+    ops.block_set(args, held, n_rows=2, n_token=V, ld_u=n, temperature=1.2, top_p=0.9, window=W_WIN, track_full=tf, logits=lg, rows=rows2, **shared, **blk)
+    for t in range(6):
+        m, rows = (2, rows2) if t < 3 else (1, rows1)
+        if t == 3:
+            ops.block_set(args, held, n_rows=1, rows=rows1)
+            assert args.n_rows == 1 and args.rows == rows1.data_ptr() and args.logits == lg.data_ptr() and args.win_tok == blk['win_tok'].data_ptr()
+        lg.copy_(logits[t])
+        ops.acc_window_step(lg[:m], 1.2, 0.9, shared['u_steps'], rows, shared['ev_flags'], shared['ev_beat'], shared['lead_tok'], shared['lead_off'],
+                            shared['params'], one['state'], one['seq'], one['segs'], W_WIN, tf, one['win_tok'][:m], one['win_seg'][:m], one['running'])
+        ops.grammar_step(args)
+        for k in one:
+            assert torch.equal(one[k], blk[k]), (t, k, one[k].tolist(), blk[k].tolist())
+    st = blk['state'].cpu().numpy()
+    assert st[:, inf.ACC_S_STATUS].tolist() == [inf.ACC_DONE, inf.ACC_RUNNING, inf.ACC_OUT_OF_DRAWS] and int(blk['running'].item()) == 1
+    assert st[:, inf.ACC_S_DRAWS].tolist() == [0, 0, 8] and st[2, inf.ACC_S_ACCEPTED] == 4
+    assert (blk['win_tok'][1] == -7).all() and (blk['win_tok'][0] >= 0).all()        # the finished stream's row was never written
+
+
 # ------------------------------------------------------------------------------------------------ the loop against the host grammar
 def _host_window_loop(inf, model, e2i, i2e, loop, wl, max_events, skip_check):
     """The windowed phase restated on the host: the SAME batched forward on the same rows, ops.sample_nucleus on each stream's own column of

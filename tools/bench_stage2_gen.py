@@ -1,7 +1,7 @@
 """Stage-2 accompaniment generation at the benchmark shape (d 512, 12 layers, 8 heads, d_ff 2048, V = 327, bf16, seeded random weights, a
 synthetic stage-2 vocabulary, synthetic lead sheets of 8 bars, output-bias nudges so that Track_LeadSheet and Beats occur and pieces
 finish), Performer (128 features) and GPT-2, 32 streams: the host loop generate_conditional_batch (NumPy draws and grammar, a host sync per
-step) against the device loop generate_accompaniments (emo_acc_grammar_step + the one-launch engine step, hipGraph replays), and the bare
+step) against the device loop generate_accompaniments (emo_grammar_step, kind ACC, + the one-launch engine step, hipGraph replays), and the bare
 engine step replayed the same way over the same positions.  Prints one JSON line.
 `ms_per_step` of the device loop is run() as a caller sees it (eager first step and graph capture included); `replay_ms_per_step` is the
 replay phase alone, the figure compared with the bare step (`device_over_bare`).

@@ -1,7 +1,7 @@
 """Stage-2 generation PAST the 2048-token window at the benchmark shape (d 512, 12 layers, 8 heads, d_ff 2048, V = 327, bf16, seeded random
 weights, the synthetic vocabulary / model / lead sheets of bench_stage2_gen.py, lead sheets long enough that every stream reaches the
 window), Performer (128 features) and GPT-2, 32 streams.  After the in-window device loop has handed the streams off, in ONE process:
-  device   WindowedLoop (one batched [m, 2048] forward + emo_acc_window_step per draw, a poll every 16 steps): ms per step, accepted draws / s
+  device   WindowedLoop (one batched [m, 2048] forward + emo_grammar_step (kind ACC_WINDOW) per draw, a poll every 16 steps): ms per step, accepted draws / s
   host     _resume_windowed on the SAME handed-off streams, one after the other, each capped at --host-draws accepted draws, repeated
            --host-repeats times (same draws every repeat): accepted draws / s per repeat, best and spread
   forward  the bare [32, 2048] eval forward, keep_last_only (what a windowed step cannot go below)
