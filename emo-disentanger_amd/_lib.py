@@ -52,6 +52,22 @@ class GrammarStep(ctypes.Structure):
 
 GRAMMAR_TXL, GRAMMAR_ACC, GRAMMAR_ACC_WINDOW = 0, 1, 2      # emo_hip.h: EMO_GRAMMAR_*
 
+
+class Attn(ctypes.Structure):
+    """emo_attn_t (emo_hip.h), field for field: the argument block of the training-side attention kernels.  Pointer fields hold raw device addresses."""
+    _fields_ = [('kind', ctypes.c_int32), ('pass_', ctypes.c_int32),
+                ('q', c_p), ('k', c_p), ('v', c_p), ('ld', c_l), ('out', c_p), ('dout', c_p), ('ld_out', c_l), ('dq', c_p), ('dk', c_p), ('dv', c_p), ('ld_d', c_l),
+                ('dtype', ctypes.c_int32), ('B', c_l), ('T', c_l), ('H', c_l), ('dh', c_l), ('p_drop', c_f), ('seed', c_u64), ('offset', c_u64),
+                ('workspace', c_p), ('workspace_bytes', c_l),
+                ('omega', c_p), ('den', c_p), ('state_S', c_p), ('state_z', c_p), ('n_feat', c_l), ('eps', c_f), ('kstate_valid', ctypes.c_int32), ('dout_is_dn', ctypes.c_int32),
+                ('lse', c_p), ('delta_ws', c_p), ('keep', c_p), ('keep_bytes', c_l),
+                ('r_dist', c_p), ('ld_r', c_l), ('n_dist', c_l), ('r_w_bias', c_p), ('r_r_bias', c_p), ('zden', c_p), ('dq_rel', c_p), ('ld_rel', c_l), ('delta', c_p),
+                ('qu', c_p), ('qv', c_p), ('ld_q', c_l), ('dR', c_p), ('ld_dr', c_l)]
+
+
+ATTN_FAVOR, ATTN_SOFTMAX, ATTN_RELPOS = 0, 1, 2             # emo_hip.h: EMO_ATTN_* kinds
+ATTN_FWD, ATTN_BWD, ATTN_BWD_KV, ATTN_BWD_R = 0, 1, 2, 3    # ... and passes (`pass` is a Python keyword: the mirror's field is pass_)
+
 _SIG = {
     'emo_version': (c_i, []),
     'emo_build_flags': (c_i, []),
@@ -67,35 +83,23 @@ _SIG = {
     'emo_embed_fwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_l, c_l, c_l, c_l, c_p, c_f, c_f, c_u64, c_u64, c_p]),
     'emo_embed_bwd': (c_i, [c_p, c_p, c_p, c_i, c_p, c_p, c_l, c_l, c_l, c_l, c_l, c_f, c_f, c_u64, c_u64, c_p]),
     'emo_layernorm_fwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_f, c_p]),
-    'emo_layernorm_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_f, c_u64, c_u64, c_p]),
+    'emo_layernorm_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_f, c_u64, c_u64, c_p, c_l, c_p]),
     'emo_layernorm_bwd_workspace_bytes': (c_l, [c_i, c_l, c_l]),
-    'emo_layernorm_bwd_ws': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_f, c_u64, c_u64, c_p, c_l, c_p]),
     'emo_dropout_apply': (c_i, [c_p, c_p, c_i, c_l, c_f, c_u64, c_u64, c_p]),
+    'emo_attn_size': (c_i, []),
+    'emo_attn': (c_i, [ctypes.POINTER(Attn), c_p]),
     'emo_favor_attn_workspace_bytes': (c_l, [c_l, c_l, c_l, c_l, c_l]),
-    'emo_favor_attn_fwd': (c_i, [c_p, c_p, c_p, c_l, c_p, c_p, c_l, c_p, c_p, c_p, c_i, c_l, c_l, c_l, c_l, c_l, c_f, c_p, c_l, c_p]),
-    'emo_favor_attn_bwd': (c_i, [c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_l, c_i, c_l, c_l, c_l, c_l, c_l, c_f, c_p, c_l, c_p]),
-    'emo_favor_attn_bwd_kstate': (c_i, [c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_l, c_i, c_l, c_l, c_l, c_l, c_l, c_f, c_p, c_l, c_i, c_p]),
     'emo_favor_attn_bwd_dn_supported': (c_i, [c_i, c_l, c_l, c_l, c_l, c_l]),
-    'emo_favor_attn_bwd_dn': (c_i, [c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_l, c_i, c_l, c_l, c_l, c_l, c_l, c_f, c_p]),
     'emo_favor_decode_step': (c_i, [c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_l, c_i, c_l, c_l, c_l, c_l, c_f, c_p]),
     'emo_decode_step_size': (c_i, []),
     'emo_decode_step_workspace_bytes': (c_l, []),
     'emo_decode_step_supported': (c_i, []),
     'emo_decode_step': (c_i, [ctypes.POINTER(DecodeStep), c_p]),
     'emo_favor_draw_omega': (c_i, [c_p, c_p, c_l, c_l, c_l, c_p]),
-    'emo_softmax_attn_fwd': (c_i, [c_p, c_p, c_p, c_l, c_p, c_l, c_p, c_i, c_l, c_l, c_l, c_l, c_f, c_u64, c_u64, c_p]),
-    'emo_softmax_attn_bwd': (c_i, [c_p, c_p, c_p, c_l, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_l, c_l, c_l, c_l, c_f, c_u64, c_u64, c_p]),
     'emo_softmax_attn_keep_bytes': (c_l, [c_i, c_l, c_l, c_l, c_l, c_f]),
-    'emo_softmax_attn_fwd_keep': (c_i, [c_p, c_p, c_p, c_l, c_p, c_l, c_p, c_i, c_l, c_l, c_l, c_l, c_f, c_u64, c_u64, c_p, c_l, c_p]),
-    'emo_softmax_attn_bwd_keep': (c_i, [c_p, c_p, c_p, c_l, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_l, c_l, c_l, c_l, c_f, c_u64, c_u64, c_p, c_l, c_p]),
-    'emo_relpos_attn_fwd': (c_i, [c_p, c_p, c_p, c_l, c_p, c_l, c_l, c_p, c_p, c_p, c_l, c_p, c_p, c_i, c_l, c_l, c_l, c_l, c_f, c_u64, c_u64, c_p]),
-    'emo_relpos_attn_bwd_kv': (c_i, [c_p, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_l, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_l, c_l, c_l, c_l, c_f, c_u64, c_u64, c_p]),
-    'emo_relpos_attn_bwd': (c_i, [c_p, c_p, c_p, c_l, c_p, c_l, c_l, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_l, c_p, c_l, c_p, c_i, c_l, c_l, c_l, c_l, c_f, c_u64, c_u64, c_p]),
-    'emo_relpos_attn_bwd_r': (c_i, [c_p, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_l, c_p, c_l, c_p, c_p, c_p, c_p, c_l, c_p, c_l, c_i, c_l, c_l, c_l, c_l, c_f, c_u64, c_u64, c_p]),
     'emo_relpos_attn_bwd_r_workspace_bytes': (c_l, [c_l, c_l, c_l, c_l]),
     'emo_relpos_attn_decode': (c_i, [c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_l, c_p, c_p, c_l, c_p, c_l, c_l, c_p, c_p, c_p, c_l, c_i, c_l, c_l, c_l, c_p]),
-    'emo_softmax_attn_decode': (c_i, [c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_i, c_l, c_l, c_l, c_p]),
-    'emo_softmax_attn_decode_layout': (c_i, [c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_i, c_l, c_l, c_l, c_i, c_p]),
+    'emo_softmax_attn_decode': (c_i, [c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_i, c_l, c_l, c_l, c_i, c_p]),
     'emo_xent_fwd': (c_i, [c_p, c_p, c_l, c_l, c_l, c_p, c_p, c_p]),
     'emo_xent_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_l, c_l, c_l, c_p]),
     'emo_token_scores': (c_i, [c_p, c_l, c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_p, c_p]),
@@ -126,7 +130,7 @@ for _name, (_res, _args) in _SIG.items():
     _fn = getattr(lib, _name)          # AttributeError here = header/library mismatch
     _fn.restype, _fn.argtypes = _res, _args
 for _cname, _size, _mirror in (('emo_epilogue_t', lib.emo_epilogue_size, Epilogue), ('emo_decode_step_t', lib.emo_decode_step_size, DecodeStep),
-                               ('emo_grammar_step_t', lib.emo_grammar_step_size, GrammarStep)):
+                               ('emo_grammar_step_t', lib.emo_grammar_step_size, GrammarStep), ('emo_attn_t', lib.emo_attn_size, Attn)):
     if _size() != ctypes.sizeof(_mirror):                   # a stale libemo_hip.so (or a stale mirror above) would read garbage pointers
         raise ImportError('libemo_hip.so was built with an %s of %d bytes, this binding has %d: rebuild (python -c "import __graft_entry__ as g; g.build()")'
                           % (_cname, _size(), ctypes.sizeof(_mirror)))

@@ -16,7 +16,7 @@ void emo_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* emo_last_error(void) { return g_err; }
-extern "C" int emo_version(void) { return 102; }
+extern "C" int emo_version(void) { return 103; }
 extern "C" int emo_build_flags(void) {
 #ifdef EMO_EXPERIMENTAL
     return 1;
@@ -518,10 +518,10 @@ extern "C" int64_t emo_layernorm_bwd_workspace_bytes(int dtype, int64_t M, int64
     return ln_bwd_blocks(M) * 3 * 512 * (int64_t)sizeof(float);
 }
 
-extern "C" int emo_layernorm_bwd_ws(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
-                                    const void* dres, void* dx, void* dx_drop, float* dgamma, float* dbeta, float* dcol, int dtype,
-                                    int64_t M, int64_t D, float p_drop, uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes,
-                                    emo_stream_t stream) {
+extern "C" int emo_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
+                                 const void* dres, void* dx, void* dx_drop, float* dgamma, float* dbeta, float* dcol, int dtype,
+                                 int64_t M, int64_t D, float p_drop, uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes,
+                                 emo_stream_t stream) {
     EMO_CHECK(dy && x && gamma && mean && rstd && dx && dgamma && dbeta, "emo_layernorm_bwd: null pointer");
     EMO_CHECK((D & 3) == 0 && D <= 1024, "emo_layernorm_bwd: D must be a multiple of 4 and <= 1024 (got %lld)", (long long)D);
     hipStream_t st = (hipStream_t)stream;
@@ -554,12 +554,6 @@ extern "C" int emo_layernorm_bwd_ws(const void* dy, const void* x, const float* 
 #undef LN_BWD
     EMO_LAUNCH_CHECK();
     return EMO_OK;
-}
-
-extern "C" int emo_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
-                                 const void* dres, void* dx, void* dx_drop, float* dgamma, float* dbeta, float* dcol, int dtype,
-                                 int64_t M, int64_t D, float p_drop, uint64_t seed, uint64_t offset, emo_stream_t stream) {
-    return emo_layernorm_bwd_ws(dy, x, gamma, mean, rstd, dres, dx, dx_drop, dgamma, dbeta, dcol, dtype, M, D, p_drop, seed, offset, nullptr, 0, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ dropout re-apply

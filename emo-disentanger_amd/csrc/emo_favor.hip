@@ -1285,15 +1285,14 @@ extern "C" int64_t emo_favor_attn_workspace_bytes(int64_t B, int64_t T, int64_t 
 template <typename CT, int DH, int MF, int CF, int CQ, int CK>
 static int run_favor(int which, const void* q, const void* k, const void* v, int64_t ld, const float* omega, void* out, int64_t ld_out, float* den,
                      float* sS, float* sz, const void* dout, void* dq, void* dk, void* dv, int64_t ld_d, int64_t B, int64_t T, int64_t H, float eps,
-                     void* workspace, int64_t workspace_bytes, hipStream_t st, bool kstate_valid = false) {
+                     void* workspace, int64_t workspace_bytes, hipStream_t st, bool kstate_valid, bool dn) {
     constexpr int F = 2 * MF;
     int P = 1; int64_t Ts = T > 0 ? T : 1;
     if (workspace) {
         favor_segments(B, T, H, &P, &Ts);
         const int64_t need = P > 1 ? B * H * P * (int64_t)(F * DH + F) * (int64_t)sizeof(float) : 0;
-        EMO_CHECK(workspace_bytes >= need, "favor attention: workspace %lld B < %lld B (emo_favor_attn_workspace_bytes)", (long long)workspace_bytes,
-                  (long long)need);
-        EMO_CHECK(((uintptr_t)workspace & 15) == 0, "favor attention: workspace must be 16-B aligned");
+        EMO_CHECK(workspace_bytes >= need, "workspace %lld B < %lld B (emo_favor_attn_workspace_bytes)", (long long)workspace_bytes, (long long)need);
+        EMO_CHECK(((uintptr_t)workspace & 15) == 0, "workspace must be 16-B aligned");
     }
     if (P <= 1) { P = 1; Ts = T > 0 ? T : 1; }
     float* wsS = (float*)workspace;
@@ -1309,13 +1308,13 @@ static int run_favor(int which, const void* q, const void* k, const void* v, int
                 return true;
         }
         const char* e = getenv("EMO_FAVOR_FS");
-        if (e && atoi(e) == 2) emo_set_error("favor attention: EMO_FAVOR_FS=2 but the slice kernels do not cover this call");
+        if (e && atoi(e) == 2) emo_set_error("EMO_FAVOR_FS=2 but the slice kernels do not cover this call");
         return false;
     };
     auto fs_required_failed = [&]() { const char* e = getenv("EMO_FAVOR_FS"); return e && atoi(e) == 2; };
     if (which == 0) {
         const size_t lds = fwd_lds<CT, DH, MF, CF>();
-        EMO_CHECK(lds <= EMO_MAX_LDS, "favor fwd: LDS %zu too large", lds);
+        EMO_CHECK(lds <= EMO_MAX_LDS, "LDS %zu too large", lds);
         auto kf = favor_fwd_kernel<CT, DH, MF, CF, false>;
         auto ks = favor_fwd_kernel<CT, DH, MF, CF, true>;
         static bool attr = false;
@@ -1335,7 +1334,7 @@ static int run_favor(int which, const void* q, const void* k, const void* v, int
         }
     } else {
         const size_t l0 = fwd_lds<CT, DH, MF, CF>(), l1 = dq_lds<CT, DH, MF, CQ>(), l2 = dkv_lds<CT, DH, MF, CK>();
-        EMO_CHECK(l0 <= EMO_MAX_LDS && l1 <= EMO_MAX_LDS && l2 <= EMO_MAX_LDS, "favor bwd: LDS %zu / %zu / %zu too large", l0, l1, l2);
+        EMO_CHECK(l0 <= EMO_MAX_LDS && l1 <= EMO_MAX_LDS && l2 <= EMO_MAX_LDS, "LDS %zu / %zu / %zu too large", l0, l1, l2);
         auto k0 = favor_fwd_kernel<CT, DH, MF, CF, true>;
         auto k1 = favor_bwd_dq_kernel<CT, DH, MF, CQ>;
         auto k2 = favor_bwd_dkv_kernel<CT, DH, MF, CK, false>;
@@ -1348,18 +1347,18 @@ static int run_favor(int which, const void* q, const void* k, const void* v, int
             (void)hipFuncSetAttribute((const void*)k2s, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
             attr = true;
         }
-        if (den == nullptr) {
-            // emo_favor_attn_bwd_dn: `dout` is dN = dout / den already — only the slice kernels' single-segment instances take that form
-            EMO_CHECK(FS && P == 1, "emo_favor_attn_bwd_dn: needs bf16, d_head 64, 128 features and a single-segment scan (B * H >= 256): emo_favor_attn_bwd_dn_supported()");
+        if (dn) {
+            // dout_is_dn: `dout` is dN = dout / den already (den = NULL down here) — only the slice kernels' single-segment instances take that form
+            EMO_CHECK(FS && P == 1, "dout_is_dn needs bf16, d_head 64, 128 features and a single-segment scan (B * H >= 256): emo_favor_attn_bwd_dn_supported()");
             if (!fs_try(1) || !fs_try(2)) {
-                emo_set_error("emo_favor_attn_bwd_dn: the slice kernels refused this call (T %% 32, 16-B alignment, EMO_FAVOR_FS / EMO_FAVOR_FS_BWD = 0)");
+                emo_set_error("the slice kernels refused this call (T %% 32, 16-B alignment, EMO_FAVOR_FS / EMO_FAVOR_FS_BWD = 0)");
                 return EMO_ERR_UNSUPPORTED;
             }
             EMO_LAUNCH_CHECK();
             return EMO_OK;
         }
         // P > 1: the K-state increments are recomputed (state-only forward pass), then the workspace is reused for the R-state increments
-        // (kstate_valid: the caller kept the forward's workspace — the same increments — for this call: emo_favor_attn_bwd_kstate)
+        // (kstate_valid: the caller kept the forward's workspace — the same increments — for this call)
         if (P > 1 && !kstate_valid)
             hipLaunchKernelGGL(k0, grid, dim3(FT), l0, st, (const CT*)q, (const CT*)k, (const CT*)v, ld, omega, (CT*)nullptr, ld_out, (float*)nullptr,
                                (float*)nullptr, (float*)nullptr, T, H, eps, wsS, wsz, P, Ts);
@@ -1383,14 +1382,14 @@ static int run_favor(int which, const void* q, const void* k, const void* v, int
 
 static int dispatch_favor(int which, int dtype, int64_t dh, int64_t mf, const void* q, const void* k, const void* v, int64_t ld, const float* omega,
                           void* out, int64_t ld_out, float* den, float* sS, float* sz, const void* dout, void* dq, void* dk, void* dv, int64_t ld_d,
-                          int64_t B, int64_t T, int64_t H, float eps, void* ws, int64_t ws_bytes, hipStream_t st, bool kstate_valid = false) {
+                          int64_t B, int64_t T, int64_t H, float eps, void* ws, int64_t ws_bytes, hipStream_t st, bool kstate_valid, bool dn) {
 #define FAVOR_CASE(DHv, MFv, CFb, CQb, CKb, CFf, CQf, CKf)                                                                                   \
     if (dh == DHv && mf == MFv) {                                                                                                            \
         if (dtype == EMO_BF16)                                                                                                               \
             return run_favor<bf16_t, DHv, MFv, CFb, CQb, CKb>(which, q, k, v, ld, omega, out, ld_out, den, sS, sz, dout, dq, dk, dv, ld_d, B, T, H, eps, ws, \
-                                                              ws_bytes, st, kstate_valid);                                                   \
+                                                              ws_bytes, st, kstate_valid, dn);                                               \
         return run_favor<float, DHv, MFv, CFf, CQf, CKf>(which, q, k, v, ld, omega, out, ld_out, den, sS, sz, dout, dq, dk, dv, ld_d, B, T, H, eps, ws,      \
-                                                         ws_bytes, st, kstate_valid);                                                        \
+                                                         ws_bytes, st, kstate_valid, dn);                                                    \
     }
     FAVOR_CASE(64, 64, FAVOR_CFB, FAVOR_CQB, FAVOR_CKB, 32, 32, 16)
     FAVOR_CASE(32, 64, 64, 64, 64, 32, 32, 32)
@@ -1398,45 +1397,12 @@ static int dispatch_favor(int which, int dtype, int64_t dh, int64_t mf, const vo
     FAVOR_CASE(16, 16, 64, 64, 64, 32, 32, 32)
     FAVOR_CASE(16, 32, 64, 64, 64, 32, 32, 32)
 #undef FAVOR_CASE
-    emo_set_error("favor attention: unsupported (d_head=%lld, n_feat=%lld); built: (64,128) (32,128) (32,64) (16,32) (16,64)", (long long)dh,
+    emo_set_error("unsupported (d_head=%lld, n_feat=%lld); built: (64,128) (32,128) (32,64) (16,32) (16,64)", (long long)dh,
                   (long long)(2 * mf));
     return EMO_ERR_UNSUPPORTED;
 }
 
-static int favor_check(const void* q, const void* k, const void* v, int64_t ld, int64_t ld_out, int dtype, int64_t dh, int64_t n_feat) {
-    EMO_CHECK(q && k && v, "favor attention: null pointer");
-    EMO_CHECK(dtype == EMO_F32 || dtype == EMO_BF16, "favor attention: bad dtype");
-    const int64_t ve = dtype == EMO_BF16 ? 8 : 4;
-    EMO_CHECK(ld % ve == 0 && ld_out % 4 == 0 && dh % ve == 0, "favor attention: ld/dh must keep rows 16-B aligned");
-    EMO_CHECK(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0, "favor attention: q/k/v must be 16-B aligned");
-    EMO_CHECK(n_feat % 2 == 0, "favor attention: n_feat must be even");
-    return EMO_OK;
-}
-
-extern "C" int emo_favor_attn_fwd(const void* q, const void* k, const void* v, int64_t ld, const float* omega, void* out, int64_t ld_out, float* den,
-                                  float* state_S, float* state_z, int dtype, int64_t B, int64_t T, int64_t H, int64_t dh, int64_t n_feat, float eps,
-                                  void* workspace, int64_t workspace_bytes, emo_stream_t stream) {
-    int rc = favor_check(q, k, v, ld, ld_out, dtype, dh, n_feat);
-    if (rc) return rc;
-    EMO_CHECK(omega && out && den, "emo_favor_attn_fwd: null pointer");
-    EMO_CHECK(((uintptr_t)out & 15) == 0, "emo_favor_attn_fwd: out must be 16-B aligned");
-    EMO_CHECK(!(state_S && !state_z), "emo_favor_attn_fwd: state_S without state_z");
-    return dispatch_favor(0, dtype, dh, n_feat / 2, q, k, v, ld, omega, out, ld_out, den, state_S, state_z, nullptr, nullptr, nullptr, nullptr, 0, B, T, H,
-                          eps, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-extern "C" int emo_favor_attn_bwd_kstate(const void* q, const void* k, const void* v, int64_t ld, const float* omega, const void* out, const void* dout,
-                                         int64_t ld_out, const float* den, void* dq, void* dk, void* dv, int64_t ld_d, int dtype, int64_t B, int64_t T, int64_t H,
-                                         int64_t dh, int64_t n_feat, float eps, void* workspace, int64_t workspace_bytes, int kstate_valid, emo_stream_t stream) {
-    int rc = favor_check(q, k, v, ld, ld_out, dtype, dh, n_feat);
-    if (rc) return rc;
-    EMO_CHECK(omega && out && dout && den && dq && dk && dv, "emo_favor_attn_bwd: null pointer");
-    EMO_CHECK(ld_d % 4 == 0, "emo_favor_attn_bwd: ld_d must be a multiple of 4");
-    EMO_CHECK((((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)out | (uintptr_t)dout) & 15) == 0, "emo_favor_attn_bwd: pointers must be 16-B aligned");
-    return dispatch_favor(1, dtype, dh, n_feat / 2, q, k, v, ld, omega, (void*)out, ld_out, (float*)den, nullptr, nullptr, dout, dq, dk, dv, ld_d, B, T, H,
-                          eps, workspace, workspace_bytes, (hipStream_t)stream, kstate_valid != 0 && workspace != nullptr);
-}
-// 1 when emo_favor_attn_bwd_dn serves this problem (the single-segment slice kernels), else 0
+// 1 when the dout_is_dn form of the backward serves this problem (the single-segment slice kernels), else 0
 extern "C" int emo_favor_attn_bwd_dn_supported(int dtype, int64_t B, int64_t T, int64_t H, int64_t dh, int64_t n_feat) {
     if (dtype != EMO_BF16 || dh != 64 || n_feat != 128 || T < 32 || (T % 32) != 0 || B * H <= 0) return 0;
     const char* e = getenv("EMO_FAVOR_FS");
@@ -1446,22 +1412,26 @@ extern "C" int emo_favor_attn_bwd_dn_supported(int dtype, int64_t B, int64_t T, 
     favor_segments(B, T, H, &P, &Ts);
     return P <= 1 ? 1 : 0;
 }
-extern "C" int emo_favor_attn_bwd_dn(const void* q, const void* k, const void* v, int64_t ld, const float* omega, const void* out, const void* dn,
-                                     int64_t ld_out, void* dq, void* dk, void* dv, int64_t ld_d, int dtype, int64_t B, int64_t T, int64_t H,
-                                     int64_t dh, int64_t n_feat, float eps, emo_stream_t stream) {
-    int rc = favor_check(q, k, v, ld, ld_out, dtype, dh, n_feat);
-    if (rc) return rc;
-    EMO_CHECK(omega && out && dn && dq && dk && dv, "emo_favor_attn_bwd_dn: null pointer");
-    EMO_CHECK(emo_favor_attn_bwd_dn_supported(dtype, B, T, H, dh, n_feat), "emo_favor_attn_bwd_dn: problem not in the supported class (emo_favor_attn_bwd_dn_supported)");
-    EMO_CHECK(ld_d % 4 == 0, "emo_favor_attn_bwd_dn: ld_d must be a multiple of 4");
-    EMO_CHECK((((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)out | (uintptr_t)dn) & 15) == 0, "emo_favor_attn_bwd_dn: pointers must be 16-B aligned");
-    return dispatch_favor(1, dtype, dh, n_feat / 2, q, k, v, ld, omega, (void*)out, ld_out, (float*)nullptr, nullptr, nullptr, dn, dq, dk, dv, ld_d, B, T, H,
-                          eps, nullptr, 0, (hipStream_t)stream, false);
-}
-extern "C" int emo_favor_attn_bwd(const void* q, const void* k, const void* v, int64_t ld, const float* omega, const void* out, const void* dout,
-                                  int64_t ld_out, const float* den, void* dq, void* dk, void* dv, int64_t ld_d, int dtype, int64_t B, int64_t T, int64_t H,
-                                  int64_t dh, int64_t n_feat, float eps, void* workspace, int64_t workspace_bytes, emo_stream_t stream) {
-    return emo_favor_attn_bwd_kstate(q, k, v, ld, omega, out, dout, ld_out, den, dq, dk, dv, ld_d, dtype, B, T, H, dh, n_feat, eps, workspace, workspace_bytes, 0, stream);
+
+// The FAVOR kind of emo_attn (emo_softmax_attn.hip: the entry, the checks every kind shares and the prefix of the messages)
+int emo_attn_favor(const emo_attn_t& a, hipStream_t st) {
+    EMO_CHECK(a.n_feat % 2 == 0, "n_feat must be even");
+    if (a.pass == EMO_ATTN_FWD) {
+        EMO_CHECK(a.omega && a.out && a.den, "null pointer");
+        EMO_CHECK(((uintptr_t)a.out & 15) == 0, "out must be 16-B aligned");
+        EMO_CHECK(!(a.state_S && !a.state_z), "state_S without state_z");
+        return dispatch_favor(0, a.dtype, a.dh, a.n_feat / 2, a.q, a.k, a.v, a.ld, a.omega, a.out, a.ld_out, a.den, a.state_S, a.state_z, nullptr, nullptr, nullptr,
+                              nullptr, 0, a.B, a.T, a.H, a.eps, a.workspace, a.workspace_bytes, st, false, false);
+    }
+    // dout_is_dn: neither the normaliser nor a workspace is read (single-segment scan)
+    const bool dn = a.dout_is_dn != 0;
+    EMO_CHECK(a.omega && a.out && a.dout && (a.den || dn) && a.dq && a.dk && a.dv, "null pointer");
+    EMO_CHECK(!dn || emo_favor_attn_bwd_dn_supported(a.dtype, a.B, a.T, a.H, a.dh, a.n_feat), "dout_is_dn outside its class (emo_favor_attn_bwd_dn_supported)");
+    EMO_CHECK(a.ld_d % 4 == 0, "ld_d must be a multiple of 4");
+    EMO_CHECK((((uintptr_t)a.dq | (uintptr_t)a.dk | (uintptr_t)a.dv | (uintptr_t)a.out | (uintptr_t)a.dout) & 15) == 0, "pointers must be 16-B aligned");
+    void* const ws = dn ? nullptr : a.workspace;
+    return dispatch_favor(1, a.dtype, a.dh, a.n_feat / 2, a.q, a.k, a.v, a.ld, a.omega, a.out, a.ld_out, dn ? nullptr : a.den, nullptr, nullptr, a.dout, a.dq, a.dk,
+                          a.dv, a.ld_d, a.B, a.T, a.H, a.eps, ws, dn ? 0 : a.workspace_bytes, st, a.kstate_valid != 0 && ws != nullptr, dn);
 }
 
 extern "C" int emo_favor_decode_step(const void* q, const void* k, const void* v, int64_t ld, const float* omega, float* state_S, float* state_z, void* out,

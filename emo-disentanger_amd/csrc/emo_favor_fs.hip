@@ -502,7 +502,7 @@ __device__ __forceinline__ bf16x8 fs_scale8(const bf16x8& x, float a) {
     return r;
 }
 
-// PRE (r06): `dout` already holds dN = dout / den (the out-projection dgrad divided it in its epilogue, emo_hip.h: hdiv / emo_favor_attn_bwd_dn): no
+// PRE (r06): `dout` already holds dN = dout / den (the out-projection dgrad divided it in its epilogue, emo_hip.h: hdiv / emo_attn_t.dout_is_dn): no
 // normaliser stream (5 DMA instructions per chunk instead of 6), no reciprocal, no rescaled operand copies — dD = -(dN . out) comes straight from
 // the Gram diagonal.  r05 measured the same arithmetic removal with a timing-only build: -10 % / -17 % VALU in dq / dk-dv, -4.4 % time.
 template <bool PRE>
@@ -1177,7 +1177,7 @@ __global__ __launch_bounds__(FS_NT, 2) void favor_fs_dkv_kernel(const bf16_t* __
 // which: 0 forward, 1 backward main passes (P > 1: the caller has run the generic state-only pass into S_ws / z_ws — for the backward the
 // K-state increments before `stage` 1 (dq) and the R-state increments before `stage` 2 (dk, dv)).  stage: 0 = whole call (P == 1 only),
 // 1 = dq, 2 = dk / dv.  Returns 0 when the shape / mode is not covered (the caller then runs the generic kernels), 1 when it was served.
-// den == nullptr in a backward call: `dout` is dN = dout / den (emo_favor_attn_bwd_dn) — the PRE instances.
+// den == nullptr in a backward call: `dout` is dN = dout / den (emo_attn_t.dout_is_dn) — the PRE instances.
 int emo_favor_fs_try(int which, int stage, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld, const float* omega, bf16_t* out, int64_t ld_out,
                      float* den, float* sS, float* sz, const bf16_t* dout, bf16_t* dq, bf16_t* dk, bf16_t* dv, int64_t ld_d, int64_t B, int64_t T, int64_t H,
                      float eps, const float* ws_S, const float* ws_z, int P, int64_t Ts, hipStream_t st) {

@@ -516,7 +516,7 @@ static int run_sattn(int which, const void* q, const void* k, const void* v, int
         }
     }
     // keep words exist only in the 32 x 32 kernels' layout: a forward that cannot write them must not pretend to, a backward must not half-use them
-    EMO_CHECK(!(which == 0 && keep), "softmax attention: keep words requested but the call is not served by the 32 x 32 kernels (bf16, d_head 64, T %% 128 == 0, 16-B aligned views)");
+    EMO_CHECK(!(which == 0 && keep), "keep words requested but the call is not served by the 32 x 32 kernels (bf16, d_head 64, T %% 128 == 0, 16-B aligned views)");
     dim3 grid((unsigned)(B * H), (unsigned)((T + 63) / 64));
     static bool attr = false;
     const size_t lfwd = sa_fwd_lds<CT, DH>(), ldq = sa_dq_lds<CT, DH>(), ldkv = sa_dkv_lds<CT, DH>();
@@ -544,7 +544,7 @@ static int run_sattn(int which, const void* q, const void* k, const void* v, int
         if constexpr (sizeof(CT) == 2 && DH == 64)
             dkv32 = emo_sattn32_dkv_try((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ld, (const bf16_t*)dout, ld_out, lse, delta, (bf16_t*)dk, (bf16_t*)dv, ld_d,
                                         B, T, H, drop, keep, st);
-        EMO_CHECK(dkv32 || !keep, "softmax attention backward: keep words given but the 32 x 32 dK/dV kernel does not serve the call");
+        EMO_CHECK(dkv32 || !keep, "keep words given but the 32 x 32 dK/dV kernel does not serve the call");
         if (!dkv32)
             hipLaunchKernelGGL(kdkv, grid, dim3(256), ldkv, st, (const CT*)q, (const CT*)k, (const CT*)v, ld, (const CT*)dout, ld_out, lse, delta, (CT*)dk,
                                (CT*)dv, ld_d, T, H, drop);
@@ -565,74 +565,40 @@ static int dispatch_sattn(int which, int dtype, int64_t dh, const void* q, const
     SA_CASE(32)
     SA_CASE(16)
 #undef SA_CASE
-    emo_set_error("softmax attention: unsupported d_head=%lld (built: 16, 32, 64)", (long long)dh);
+    emo_set_error("unsupported d_head=%lld (built: 16, 32, 64)", (long long)dh);
     return EMO_ERR_UNSUPPORTED;
-}
-
-static int sattn_check(const void* q, const void* k, const void* v, int64_t ld, int64_t ld_out, int dtype, int64_t dh) {
-    EMO_CHECK(q && k && v, "softmax attention: null pointer");
-    EMO_CHECK(dtype == EMO_F32 || dtype == EMO_BF16, "softmax attention: bad dtype");
-    const int64_t ve = dtype == EMO_BF16 ? 8 : 4;
-    EMO_CHECK(ld % ve == 0 && ld_out % ve == 0 && dh % ve == 0, "softmax attention: ld/dh must keep rows 16-B aligned");
-    EMO_CHECK((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) == 0, "softmax attention: q/k/v must be 16-B aligned");
-    return EMO_OK;
 }
 
 extern "C" int64_t emo_softmax_attn_keep_bytes(int dtype, int64_t B, int64_t T, int64_t H, int64_t dh, float p_drop) {
     return dtype == EMO_BF16 ? emo_sattn32_keep_bytes(B, T, H, dh, p_drop) : 0;
 }
 
-extern "C" int emo_softmax_attn_fwd_keep(const void* q, const void* k, const void* v, int64_t ld, void* out, int64_t ld_out, float* lse, int dtype, int64_t B,
-                                         int64_t T, int64_t H, int64_t dh, float p_drop, uint64_t seed, uint64_t offset, void* keep, int64_t keep_bytes,
-                                         emo_stream_t stream) {
-    int rc = sattn_check(q, k, v, ld, ld_out, dtype, dh);
-    if (rc) return rc;
-    EMO_CHECK(out && lse && ((uintptr_t)out & 15) == 0, "emo_softmax_attn_fwd: bad out/lse");
-    if (keep) {
-        const int64_t need = emo_softmax_attn_keep_bytes(dtype, B, T, H, dh, p_drop);
-        EMO_CHECK(need > 0 && keep_bytes >= need && ((uintptr_t)keep & 15) == 0, "emo_softmax_attn_fwd_keep: keep buffer of %lld bytes, need %lld (emo_softmax_attn_keep_bytes; 0 = not available for this call)",
-                  (long long)keep_bytes, (long long)need);
+// The SOFTMAX kind of emo_attn (the entry, with the checks every kind shares, is at the end of this file)
+static int attn_softmax(const emo_attn_t& a, hipStream_t st) {
+    const bool fwd = a.pass == EMO_ATTN_FWD;
+    if (fwd) {
+        EMO_CHECK(a.out && a.lse && ((uintptr_t)a.out & 15) == 0, "bad out/lse");
+    } else {
+        EMO_CHECK(a.out && a.dout && a.lse && a.delta_ws && a.dq && a.dk && a.dv, "null pointer");
+        EMO_CHECK(a.ld_d % 4 == 0 && (((uintptr_t)a.dq | (uintptr_t)a.dk | (uintptr_t)a.dv | (uintptr_t)a.out | (uintptr_t)a.dout) & 15) == 0,
+                  "gradients must be 16-B aligned with ld_d %% 4 == 0");
     }
-    return dispatch_sattn(0, dtype, dh, q, k, v, ld, out, nullptr, ld_out, lse, nullptr, nullptr, nullptr, nullptr, 0, B, T, H, make_drop(p_drop, seed, offset),
-                          (uint32_t*)keep, (hipStream_t)stream);
-}
-extern "C" int emo_softmax_attn_fwd(const void* q, const void* k, const void* v, int64_t ld, void* out, int64_t ld_out, float* lse, int dtype, int64_t B,
-                                    int64_t T, int64_t H, int64_t dh, float p_drop, uint64_t seed, uint64_t offset, emo_stream_t stream) {
-    return emo_softmax_attn_fwd_keep(q, k, v, ld, out, ld_out, lse, dtype, B, T, H, dh, p_drop, seed, offset, nullptr, 0, stream);
+    if (a.keep) {
+        const int64_t need = emo_softmax_attn_keep_bytes(a.dtype, a.B, a.T, a.H, a.dh, a.p_drop);
+        EMO_CHECK(need > 0 && a.keep_bytes >= need && ((uintptr_t)a.keep & 15) == 0,
+                  "keep buffer of %lld bytes, need %lld (emo_softmax_attn_keep_bytes; 0 = not available for this call)", (long long)a.keep_bytes, (long long)need);
+    }
+    const DropCtx drop = make_drop(a.p_drop, a.seed, a.offset);
+    if (fwd)
+        return dispatch_sattn(0, a.dtype, a.dh, a.q, a.k, a.v, a.ld, a.out, nullptr, a.ld_out, a.lse, nullptr, nullptr, nullptr, nullptr, 0, a.B, a.T, a.H, drop,
+                              (uint32_t*)a.keep, st);
+    return dispatch_sattn(1, a.dtype, a.dh, a.q, a.k, a.v, a.ld, a.out, a.dout, a.ld_out, a.lse, a.delta_ws, a.dq, a.dk, a.dv, a.ld_d, a.B, a.T, a.H, drop,
+                          (uint32_t*)a.keep, st);
 }
 
-extern "C" int emo_softmax_attn_bwd_keep(const void* q, const void* k, const void* v, int64_t ld, const void* out, const void* dout, int64_t ld_out,
-                                         const float* lse, float* delta_ws, void* dq, void* dk, void* dv, int64_t ld_d, int dtype, int64_t B, int64_t T, int64_t H,
-                                         int64_t dh, float p_drop, uint64_t seed, uint64_t offset, const void* keep, int64_t keep_bytes, emo_stream_t stream) {
-    int rc = sattn_check(q, k, v, ld, ld_out, dtype, dh);
-    if (rc) return rc;
-    EMO_CHECK(out && dout && lse && delta_ws && dq && dk && dv, "emo_softmax_attn_bwd: null pointer");
-    EMO_CHECK(ld_d % 4 == 0 && (((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)out | (uintptr_t)dout) & 15) == 0,
-              "emo_softmax_attn_bwd: gradients must be 16-B aligned with ld_d %% 4 == 0");
-    if (keep) {
-        const int64_t need = emo_softmax_attn_keep_bytes(dtype, B, T, H, dh, p_drop);
-        EMO_CHECK(need > 0 && keep_bytes >= need && ((uintptr_t)keep & 15) == 0, "emo_softmax_attn_bwd_keep: keep buffer of %lld bytes, need %lld", (long long)keep_bytes, (long long)need);
-    }
-    return dispatch_sattn(1, dtype, dh, q, k, v, ld, out, dout, ld_out, (float*)lse, delta_ws, dq, dk, dv, ld_d, B, T, H, make_drop(p_drop, seed, offset),
-                          (uint32_t*)keep, (hipStream_t)stream);
-}
-extern "C" int emo_softmax_attn_bwd(const void* q, const void* k, const void* v, int64_t ld, const void* out, const void* dout, int64_t ld_out,
-                                    const float* lse, float* delta_ws, void* dq, void* dk, void* dv, int64_t ld_d, int dtype, int64_t B, int64_t T, int64_t H,
-                                    int64_t dh, float p_drop, uint64_t seed, uint64_t offset, emo_stream_t stream) {
-    return emo_softmax_attn_bwd_keep(q, k, v, ld, out, dout, ld_out, lse, delta_ws, dq, dk, dv, ld_d, dtype, B, T, H, dh, p_drop, seed, offset, nullptr, 0, stream);
-}
-
-extern "C" int emo_softmax_attn_decode_layout(const void* q, int64_t ld_q, void* kcache, void* vcache, int64_t T_max, const int64_t* lens, int64_t lens_off,
-                                              const void* k_new, const void* v_new, int64_t ld_new, void* out, int64_t ld_out, int dtype, int64_t n_streams,
-                                              int64_t H, int64_t dh, int head_major, emo_stream_t stream);
 extern "C" int emo_softmax_attn_decode(const void* q, int64_t ld_q, void* kcache, void* vcache, int64_t T_max, const int64_t* lens, int64_t lens_off,
                                        const void* k_new, const void* v_new, int64_t ld_new, void* out, int64_t ld_out, int dtype, int64_t n_streams,
-                                       int64_t H, int64_t dh, emo_stream_t stream) {
-    return emo_softmax_attn_decode_layout(q, ld_q, kcache, vcache, T_max, lens, lens_off, k_new, v_new, ld_new, out, ld_out, dtype, n_streams, H, dh, 0, stream);
-}
-extern "C" int emo_softmax_attn_decode_layout(const void* q, int64_t ld_q, void* kcache, void* vcache, int64_t T_max, const int64_t* lens, int64_t lens_off,
-                                              const void* k_new, const void* v_new, int64_t ld_new, void* out, int64_t ld_out, int dtype, int64_t n_streams,
-                                              int64_t H, int64_t dh, int head_major, emo_stream_t stream) {
+                                       int64_t H, int64_t dh, int head_major, emo_stream_t stream) {
     EMO_CHECK(q && kcache && vcache && lens && out, "emo_softmax_attn_decode: null pointer");
     EMO_CHECK(dh == 16 || dh == 32 || dh == 64 || dh == 128, "emo_softmax_attn_decode: d_head must be 16, 32, 64 or 128");
     EMO_CHECK(!k_new == !v_new, "emo_softmax_attn_decode: k_new and v_new go together");
@@ -1562,30 +1528,6 @@ static int run_relattn(const void* q, const void* k, const void* v, int64_t ld, 
     return EMO_OK;
 }
 
-extern "C" int emo_relpos_attn_fwd(const void* q, const void* k, const void* v, int64_t ld, const void* r_dist, int64_t ld_r, int64_t n_dist,
-                                   const float* r_w_bias, const float* r_r_bias, void* out, int64_t ld_out, float* lse, float* zden, int dtype, int64_t B,
-                                   int64_t T, int64_t H, int64_t dh, float p_drop, uint64_t seed, uint64_t offset, emo_stream_t stream) {
-    int rc = sattn_check(q, k, v, ld, ld_out, dtype, dh);
-    if (rc) return rc;
-    EMO_CHECK(r_dist && r_w_bias && r_r_bias && out && lse, "emo_relpos_attn_fwd: null pointer");
-    const int64_t ve = dtype == EMO_BF16 ? 8 : 4;
-    EMO_CHECK(ld_r % ve == 0 && ((uintptr_t)r_dist & 15) == 0 && ((uintptr_t)out & 15) == 0, "emo_relpos_attn_fwd: r_dist / out must keep rows 16-B aligned");
-    EMO_CHECK(n_dist >= T, "emo_relpos_attn_fwd: r_dist needs a row for every distance 0 .. T-1");
-    const DropCtx drop = make_drop(p_drop, seed, offset);
-    hipStream_t st = (hipStream_t)stream;
-#define RA_CASE(DHv)                                                                                                                                   \
-    if (dh == DHv) {                                                                                                                                   \
-        if (dtype == EMO_BF16) return run_relattn<bf16_t, DHv>(q, k, v, ld, r_dist, ld_r, n_dist, r_w_bias, r_r_bias, out, ld_out, lse, zden, B, T, H, drop, st); \
-        return run_relattn<float, DHv>(q, k, v, ld, r_dist, ld_r, n_dist, r_w_bias, r_r_bias, out, ld_out, lse, zden, B, T, H, drop, st);               \
-    }
-    RA_CASE(64)
-    RA_CASE(32)
-    RA_CASE(16)
-#undef RA_CASE
-    emo_set_error("emo_relpos_attn_fwd: unsupported d_head=%lld (built: 16, 32, 64)", (long long)dh);
-    return EMO_ERR_UNSUPPORTED;
-}
-
 template <typename CT, int DH> static size_t ra_bwd_lds() {
     typedef SaDims<CT, DH> D;
     return sizeof(CT) * (size_t)(3 * 64 * D::LDX + (sizeof(CT) == 2 ? 0 : DH * D::LDC) + 128 * D::LDX) + sizeof(float) * (4 * 16 * 84 + 64);
@@ -1603,35 +1545,6 @@ static int run_relattn_bwd(const void* q, const void* k, const void* v, int64_t 
                        (const CT*)dout, ld_out, lse, zden, (CT*)dq, ld_d, (CT*)dq_rel, ld_rel, delta, T, H, drop);
     EMO_LAUNCH_CHECK();
     return EMO_OK;
-}
-
-extern "C" int emo_relpos_attn_bwd(const void* q, const void* k, const void* v, int64_t ld, const void* r_dist, int64_t ld_r, int64_t n_dist,
-                                   const float* r_w_bias, const float* r_r_bias, const void* out, const void* dout, int64_t ld_out, const float* lse,
-                                   const float* zden, void* dq, int64_t ld_d, void* dq_rel, int64_t ld_rel, float* delta, int dtype,
-                                   int64_t B, int64_t T, int64_t H, int64_t dh, float p_drop, uint64_t seed, uint64_t offset, emo_stream_t stream) {
-    int rc = sattn_check(q, k, v, ld, ld_out, dtype, dh);
-    if (rc) return rc;
-    EMO_CHECK(r_dist && r_w_bias && r_r_bias && out && dout && lse && zden && dq && dq_rel, "emo_relpos_attn_bwd: null pointer");
-    const int64_t ve = dtype == EMO_BF16 ? 8 : 4;
-    EMO_CHECK(ld_r % ve == 0 && ld_d % 4 == 0 && ld_rel % 4 == 0 && (((uintptr_t)r_dist | (uintptr_t)dq | (uintptr_t)dq_rel | (uintptr_t)out | (uintptr_t)dout) & 15) == 0,
-              "emo_relpos_attn_bwd: pointers must be 16-B aligned");
-    EMO_CHECK(n_dist >= T, "emo_relpos_attn_bwd: r_dist needs a row for every distance 0 .. T-1");
-    const DropCtx drop = make_drop(p_drop, seed, offset);
-    hipStream_t st = (hipStream_t)stream;
-#define RAB_CASE(DHv)                                                                                                                                  \
-    if (dh == DHv) {                                                                                                                                   \
-        if (dtype == EMO_BF16)                                                                                                                         \
-            return run_relattn_bwd<bf16_t, DHv>(q, k, v, ld, r_dist, ld_r, n_dist, r_w_bias, r_r_bias, out, dout, ld_out, lse, zden, dq, ld_d, dq_rel, ld_rel,  \
-                                                delta, B, T, H, drop, st);                                                          \
-        return run_relattn_bwd<float, DHv>(q, k, v, ld, r_dist, ld_r, n_dist, r_w_bias, r_r_bias, out, dout, ld_out, lse, zden, dq, ld_d, dq_rel, ld_rel,       \
-                                           delta, B, T, H, drop, st);                                                               \
-    }
-    RAB_CASE(64)
-    RAB_CASE(32)
-    RAB_CASE(16)
-#undef RAB_CASE
-    emo_set_error("emo_relpos_attn_bwd: unsupported d_head=%lld (built: 16, 32, 64)", (long long)dh);
-    return EMO_ERR_UNSUPPORTED;
 }
 
 template <typename CT, int DH> static size_t ra_dr_lds() {
@@ -1660,36 +1573,6 @@ extern "C" int64_t emo_relpos_attn_bwd_r_workspace_bytes(int64_t B, int64_t T, i
     return B * H * ((T + 63) / 64) * 128 * dh * (int64_t)sizeof(float);
 }
 
-extern "C" int emo_relpos_attn_bwd_r(const void* qu, const void* qv, int64_t ld_q, const void* k, const void* v, int64_t ld, const void* r_dist, int64_t ld_r,
-                                     int64_t n_dist, const void* dout, int64_t ld_out, const float* lse, const float* zden, const float* delta, float* dR,
-                                     int64_t ld_dr, void* workspace, int64_t workspace_bytes, int dtype, int64_t B, int64_t T, int64_t H, int64_t dh,
-                                     float p_drop, uint64_t seed, uint64_t offset, emo_stream_t stream) {
-    int rc = sattn_check(qu, k, v, ld, ld_out, dtype, dh);
-    if (rc) return rc;
-    EMO_CHECK(qv && r_dist && dout && lse && zden && delta && dR && workspace, "emo_relpos_attn_bwd_r: null pointer");
-    const int64_t ve = dtype == EMO_BF16 ? 8 : 4;
-    EMO_CHECK(ld_r % ve == 0 && ld_q % ve == 0 && (((uintptr_t)r_dist | (uintptr_t)qu | (uintptr_t)qv | (uintptr_t)dout | (uintptr_t)workspace) & 15) == 0,
-              "emo_relpos_attn_bwd_r: pointers must be 16-B aligned");
-    EMO_CHECK(n_dist >= T && ld_dr >= H * dh, "emo_relpos_attn_bwd_r: r_dist needs a row for every distance 0 .. T-1, dR a column for every (h, d)");
-    EMO_CHECK(workspace_bytes >= emo_relpos_attn_bwd_r_workspace_bytes(B, T, H, dh), "emo_relpos_attn_bwd_r: workspace too small (emo_relpos_attn_bwd_r_workspace_bytes)");
-    const DropCtx drop = make_drop(p_drop, seed, offset);
-    hipStream_t st = (hipStream_t)stream;
-#define RAR_CASE(DHv)                                                                                                                                  \
-    if (dh == DHv) {                                                                                                                                   \
-        if (dtype == EMO_BF16)                                                                                                                         \
-            return run_relattn_dr<bf16_t, DHv>(qu, qv, ld_q, k, v, ld, r_dist, ld_r, n_dist, dout, ld_out, lse, zden, delta, dR, ld_dr, (float*)workspace, B, T, \
-                                               H, drop, st);                                                                                           \
-        return run_relattn_dr<float, DHv>(qu, qv, ld_q, k, v, ld, r_dist, ld_r, n_dist, dout, ld_out, lse, zden, delta, dR, ld_dr, (float*)workspace, B, T, H,  \
-                                          drop, st);                                                                                                   \
-    }
-    RAR_CASE(64)
-    RAR_CASE(32)
-    RAR_CASE(16)
-#undef RAR_CASE
-    emo_set_error("emo_relpos_attn_bwd_r: unsupported d_head=%lld (built: 16, 32, 64)", (long long)dh);
-    return EMO_ERR_UNSUPPORTED;
-}
-
 template <typename CT, int DH> static size_t ra_dkv_lds() {
     typedef SaDims<CT, DH> D;
     return sizeof(CT) * (size_t)(5 * 64 * D::LDX + 128 * D::LDX + (sizeof(CT) == 2 ? 0 : 2 * DH * D::LDC)) + sizeof(float) * (4 * 16 * 36 + 3 * 64);
@@ -1709,32 +1592,85 @@ static int run_relattn_dkv(const void* qu, const void* qv, int64_t ld_q, const v
     return EMO_OK;
 }
 
-extern "C" int emo_relpos_attn_bwd_kv(const void* qu, const void* qv, int64_t ld_q, const void* k, const void* v, int64_t ld, const void* r_dist, int64_t ld_r,
-                                      int64_t n_dist, const void* dout, int64_t ld_out, const float* lse, const float* zden, const float* delta, void* dk,
-                                      void* dv, int64_t ld_d, int dtype, int64_t B, int64_t T, int64_t H, int64_t dh, float p_drop, uint64_t seed,
-                                      uint64_t offset, emo_stream_t stream) {
-    int rc = sattn_check(qu, k, v, ld, ld_out, dtype, dh);
-    if (rc) return rc;
-    EMO_CHECK(qv && r_dist && dout && lse && zden && delta && dk && dv, "emo_relpos_attn_bwd_kv: null pointer");
-    const int64_t ve = dtype == EMO_BF16 ? 8 : 4;
-    EMO_CHECK(ld_r % ve == 0 && ld_q % ve == 0 && ld_d % 4 == 0 &&
-              (((uintptr_t)r_dist | (uintptr_t)qu | (uintptr_t)qv | (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)dout) & 15) == 0,
-              "emo_relpos_attn_bwd_kv: pointers must be 16-B aligned");
-    EMO_CHECK(n_dist >= T, "emo_relpos_attn_bwd_kv: r_dist needs a row for every distance 0 .. T-1");
-    const DropCtx drop = make_drop(p_drop, seed, offset);
-    hipStream_t st = (hipStream_t)stream;
-#define RAK_CASE(DHv)                                                                                                                                  \
-    if (dh == DHv) {                                                                                                                                   \
-        if (dtype == EMO_BF16)                                                                                                                         \
-            return run_relattn_dkv<bf16_t, DHv>(qu, qv, ld_q, k, v, ld, r_dist, ld_r, n_dist, dout, ld_out, lse, zden, delta, dk, dv, ld_d, B, T, H, drop, st); \
-        return run_relattn_dkv<float, DHv>(qu, qv, ld_q, k, v, ld, r_dist, ld_r, n_dist, dout, ld_out, lse, zden, delta, dk, dv, ld_d, B, T, H, drop, st);      \
+// The RELPOS kind of emo_attn: its four passes, in the order of the kernels above
+static int attn_relpos(const emo_attn_t& a, hipStream_t st) {
+    const bool bf = a.dtype == EMO_BF16;
+    const int64_t ve = bf ? 8 : 4;
+    const DropCtx drop = make_drop(a.p_drop, a.seed, a.offset);
+#define RA_RUN(run, ...)                                                                                  \
+    do {                                                                                                  \
+        if (a.dh == 64) return bf ? run<bf16_t, 64>(__VA_ARGS__, a.B, a.T, a.H, drop, st) : run<float, 64>(__VA_ARGS__, a.B, a.T, a.H, drop, st); \
+        if (a.dh == 32) return bf ? run<bf16_t, 32>(__VA_ARGS__, a.B, a.T, a.H, drop, st) : run<float, 32>(__VA_ARGS__, a.B, a.T, a.H, drop, st); \
+        if (a.dh == 16) return bf ? run<bf16_t, 16>(__VA_ARGS__, a.B, a.T, a.H, drop, st) : run<float, 16>(__VA_ARGS__, a.B, a.T, a.H, drop, st); \
+        emo_set_error("unsupported d_head=%lld (built: 16, 32, 64)", (long long)a.dh);                    \
+        return EMO_ERR_UNSUPPORTED;                                                                       \
+    } while (0)
+    EMO_CHECK(a.r_dist && a.lse, "null pointer");
+    EMO_CHECK(a.ld_r % ve == 0 && ((uintptr_t)a.r_dist & 15) == 0, "r_dist must keep rows 16-B aligned");
+    EMO_CHECK(a.n_dist >= a.T, "r_dist needs a row for every distance 0 .. T-1");
+    if (a.pass == EMO_ATTN_FWD) {
+        EMO_CHECK(a.r_w_bias && a.r_r_bias && a.out, "null pointer");
+        EMO_CHECK(((uintptr_t)a.out & 15) == 0, "out must be 16-B aligned");
+        RA_RUN(run_relattn, a.q, a.k, a.v, a.ld, a.r_dist, a.ld_r, a.n_dist, a.r_w_bias, a.r_r_bias, a.out, a.ld_out, a.lse, a.zden);
     }
-    RAK_CASE(64)
-    RAK_CASE(32)
-    RAK_CASE(16)
-#undef RAK_CASE
-    emo_set_error("emo_relpos_attn_bwd_kv: unsupported d_head=%lld (built: 16, 32, 64)", (long long)dh);
-    return EMO_ERR_UNSUPPORTED;
+    if (a.pass == EMO_ATTN_BWD) {
+        EMO_CHECK(a.r_w_bias && a.r_r_bias && a.out && a.dout && a.zden && a.dq && a.dq_rel, "null pointer");
+        EMO_CHECK(a.ld_d % 4 == 0 && a.ld_rel % 4 == 0 && (((uintptr_t)a.dq | (uintptr_t)a.dq_rel | (uintptr_t)a.out | (uintptr_t)a.dout) & 15) == 0,
+                  "pointers must be 16-B aligned with ld_d %% 4 == 0 and ld_rel %% 4 == 0");
+        RA_RUN(run_relattn_bwd, a.q, a.k, a.v, a.ld, a.r_dist, a.ld_r, a.n_dist, a.r_w_bias, a.r_r_bias, a.out, a.dout, a.ld_out, a.lse, a.zden, a.dq, a.ld_d,
+               a.dq_rel, a.ld_rel, a.delta);
+    }
+    // the distance-window and the key-tile pass: the biased query copies in the place of q
+    EMO_CHECK(a.qv && a.dout && a.zden && a.delta, "null pointer");
+    EMO_CHECK(a.ld_q % ve == 0 && (((uintptr_t)a.qu | (uintptr_t)a.qv | (uintptr_t)a.dout) & 15) == 0, "qu / qv / dout must keep rows 16-B aligned");
+    if (a.pass == EMO_ATTN_BWD_R) {
+        EMO_CHECK(a.dR && a.workspace && ((uintptr_t)a.workspace & 15) == 0, "dR / workspace: null pointer or not 16-B aligned");
+        EMO_CHECK(a.ld_dr >= a.H * a.dh, "dR needs a column for every (h, d)");
+        EMO_CHECK(a.workspace_bytes >= emo_relpos_attn_bwd_r_workspace_bytes(a.B, a.T, a.H, a.dh), "workspace too small (emo_relpos_attn_bwd_r_workspace_bytes)");
+        RA_RUN(run_relattn_dr, a.qu, a.qv, a.ld_q, a.k, a.v, a.ld, a.r_dist, a.ld_r, a.n_dist, a.dout, a.ld_out, a.lse, a.zden, a.delta, a.dR, a.ld_dr,
+               (float*)a.workspace);
+    }
+    EMO_CHECK(a.dk && a.dv, "null pointer");
+    EMO_CHECK(a.ld_d % 4 == 0 && (((uintptr_t)a.dk | (uintptr_t)a.dv) & 15) == 0, "dk / dv must be 16-B aligned with ld_d %% 4 == 0");
+    RA_RUN(run_relattn_dkv, a.qu, a.qv, a.ld_q, a.k, a.v, a.ld, a.r_dist, a.ld_r, a.n_dist, a.dout, a.ld_out, a.lse, a.zden, a.delta, a.dk, a.dv, a.ld_d);
+#undef RA_RUN
+}
+
+// ----------------------------------------------------------------------------------------------- emo_attn: one entry for the three attention kinds
+int emo_attn_favor(const emo_attn_t& a, hipStream_t st);   // emo_favor.hip
+
+extern "C" int emo_attn_size(void) { return (int)sizeof(emo_attn_t); }
+
+// the checks every (kind, pass) shares, then its own
+static int attn_run(const emo_attn_t& a, hipStream_t st) {
+    // (the key-tile and distance-window passes of RELPOS take qu where the others take q)
+    const void* q = a.kind == EMO_ATTN_RELPOS && a.pass >= EMO_ATTN_BWD_KV ? a.qu : a.q;
+    EMO_CHECK(q && a.k && a.v, "null pointer");
+    EMO_CHECK(a.dtype == EMO_F32 || a.dtype == EMO_BF16, "bad dtype");
+    const int64_t ve = a.dtype == EMO_BF16 ? 8 : 4;
+    EMO_CHECK(a.ld % ve == 0 && a.ld_out % (a.kind == EMO_ATTN_FAVOR ? 4 : ve) == 0 && a.dh % ve == 0, "ld/dh must keep rows 16-B aligned");
+    EMO_CHECK((((uintptr_t)q | (uintptr_t)a.k | (uintptr_t)a.v) & 15) == 0, "q/k/v must be 16-B aligned");
+    switch (a.kind) {
+        case EMO_ATTN_FAVOR: return emo_attn_favor(a, (hipStream_t)st);
+        case EMO_ATTN_SOFTMAX: return attn_softmax(a, (hipStream_t)st);
+        default: return attn_relpos(a, (hipStream_t)st);
+    }
+}
+
+extern "C" int emo_attn(const emo_attn_t* args, emo_stream_t stream) {
+    static const char* const kinds[3] = {"favor", "softmax", "relpos"};
+    static const char* const passes[4] = {"fwd", "bwd", "bwd_kv", "bwd_r"};
+    EMO_CHECK(args, "emo_attn: null argument block");
+    const emo_attn_t& a = *args;
+    EMO_CHECK(a.kind >= 0 && a.kind <= 2, "emo_attn: kind %d is none of EMO_ATTN_FAVOR, EMO_ATTN_SOFTMAX, EMO_ATTN_RELPOS", (int)a.kind);
+    EMO_CHECK(a.pass >= 0 && a.pass <= (a.kind == EMO_ATTN_RELPOS ? EMO_ATTN_BWD_R : EMO_ATTN_BWD), "emo_attn: kind %s has no pass %d", kinds[a.kind], (int)a.pass);
+    const int rc = attn_run(a, (hipStream_t)stream);
+    if (rc != EMO_OK) {                                        // every message names the (kind, pass) it comes from
+        char msg[512];
+        snprintf(msg, sizeof(msg), "%s", emo_last_error());
+        emo_set_error("emo_attn[%s, %s%s]: %s", kinds[a.kind], passes[a.pass], a.kind == EMO_ATTN_FAVOR && a.pass == EMO_ATTN_BWD && a.dout_is_dn ? ", dn" : "", msg);
+    }
+    return rc;
 }
 
 extern "C" int emo_relpos_attn_decode(const void* q, int64_t ld_q, void* kcache, void* vcache, int64_t T_max, const int64_t* lens, int64_t lens_off,

@@ -10,7 +10,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, BF16, F32, MUL_BITMASK, MUL_DGELU, MUL_DGELU_NEW, MUL_NONE, MUL_NONZERO, GRAMMAR_ACC, GRAMMAR_ACC_WINDOW, GRAMMAR_TXL, DecodeStep, Epilogue, GrammarStep, check,
+from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, ATTN_BWD, ATTN_BWD_KV, ATTN_BWD_R, ATTN_FAVOR, ATTN_FWD, ATTN_RELPOS, ATTN_SOFTMAX, BF16, F32, MUL_BITMASK, MUL_DGELU, MUL_DGELU_NEW, MUL_NONE, MUL_NONZERO, GRAMMAR_ACC, GRAMMAR_ACC_WINDOW, GRAMMAR_TXL, Attn, DecodeStep, Epilogue, GrammarStep, check,
                    dtype_code, lib, ptr, stream)
 
 __all__ = ['gemm', 'colsum', 'embed_fwd', 'embed_bwd', 'layernorm_fwd', 'layernorm_bwd', 'dropout_apply', 'favor_attn_fwd',
@@ -252,8 +252,8 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dgamma, dbeta, dres=None, want_drop=
     dx = torch.empty_like(x)
     dxd = torch.empty_like(x) if want_drop else None
     ws, ws_bytes = _workspace('ln_bwd', x.device, lib.emo_layernorm_bwd_workspace_bytes(dtype_code(x.dtype), M, D))
-    check(lib.emo_layernorm_bwd_ws(ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), ptr(dx), ptr(dxd), ptr(dgamma), ptr(dbeta),
-                                   ptr(dcol), dtype_code(x.dtype), M, D, p_drop, seed, offset, ptr(ws), ws_bytes, stream()))
+    check(lib.emo_layernorm_bwd(ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), ptr(dx), ptr(dxd), ptr(dgamma), ptr(dbeta),
+                                ptr(dcol), dtype_code(x.dtype), M, D, p_drop, seed, offset, ptr(ws), ws_bytes, stream()))
     return dx, dxd
 
 
@@ -264,6 +264,16 @@ def dropout_apply(x, p_drop, seed, offset):
     return out
 
 
+def _attn(kind, pass_, q, k, v, B, T, H, **fields):
+    """One emo_attn call (emo_hip.h) from a fresh emo_attn_t: the kind, the pass, the q / k / v views ([B*T, H*dh], one row stride; the RELPOS
+    BWD_KV / BWD_R passes take their biased query copies as `qu`, `qv` fields and read no q) and the shape; every other field by its name in the
+    struct, tensors as ptr(t).  The block lives for this call only: the library reads it at call time."""
+    ld = _rows(k)
+    assert q.shape[0] == B * T and _rows(v) == ld and (pass_ >= ATTN_BWD_KV or _rows(q) == ld)
+    a = Attn(kind=kind, pass_=pass_, q=ptr(q), k=ptr(k), v=ptr(v), ld=ld, dtype=dtype_code(q.dtype), B=B, T=T, H=H, dh=q.shape[1] // H, **fields)
+    check(lib.emo_attn(ctypes.byref(a), stream()))
+
+
 def _favor_workspace(device, B, T, H, dh, n_feat):
     """Scratch for the segment-parallel scan (see include/emo_hip.h)."""
     return _workspace('favor', device, lib.emo_favor_attn_workspace_bytes(B, T, H, dh, n_feat))
@@ -272,12 +282,11 @@ def _favor_workspace(device, B, T, H, dh, n_feat):
 def favor_attn_fwd(q, k, v, omega, B, T, H, eps=1e-6, want_state=False, keep_ws=False):
     """q,k,v: [B*T, H*dh] (row-strided views allowed). Returns out [B*T, H*dh], den [B,H,T] (, S, z).
     keep_ws: the call gets a PRIVATE workspace, returned as a third value (None when the scan is not segmented) for favor_attn_bwd(ws_saved=):
-    the backward then skips recomputing the K-state increments (include/emo_hip.h, emo_favor_attn_bwd_kstate)."""
+    the backward then skips recomputing the K-state increments (include/emo_hip.h, emo_attn_t.kstate_valid)."""
     M, HD = q.shape
     dh = HD // H
     n_feat = 2 * omega.shape[1]
-    assert M == B * T and omega.shape[0] == dh and omega.dtype == torch.float32 and omega.is_contiguous()
-    assert _rows(q) == _rows(k) == _rows(v)
+    assert omega.shape[0] == dh and omega.dtype == torch.float32 and omega.is_contiguous()
     out = torch.empty(M, HD, device=q.device, dtype=q.dtype)
     den = torch.empty(B, H, T, device=q.device, dtype=torch.float32)
     S = torch.empty(B, H, n_feat, dh, device=q.device, dtype=torch.float32) if want_state else None
@@ -289,8 +298,8 @@ def favor_attn_fwd(q, k, v, omega, B, T, H, eps=1e-6, want_state=False, keep_ws=
         ws, ws_bytes = _favor_workspace(q.device, B, T, H, dh, n_feat)
     # algorithmic HBM bytes: read q, k, v + write out = 4 * H*dh * e per token
     with _timed('favor_fwd', 0.0, 4.0 * M * HD * q.element_size()):
-        check(lib.emo_favor_attn_fwd(ptr(q), ptr(k), ptr(v), _rows(q), ptr(omega), ptr(out), HD, ptr(den), ptr(S), ptr(z), dtype_code(q.dtype),
-                                     B, T, H, dh, n_feat, eps, ptr(ws), ws_bytes, stream()))
+        _attn(ATTN_FAVOR, ATTN_FWD, q, k, v, B, T, H, omega=ptr(omega), out=ptr(out), ld_out=HD, den=ptr(den), state_S=ptr(S), state_z=ptr(z),
+              n_feat=n_feat, eps=eps, workspace=ptr(ws), workspace_bytes=ws_bytes)
     if keep_ws:
         assert not want_state
         return out, den, ws
@@ -298,7 +307,7 @@ def favor_attn_fwd(q, k, v, omega, B, T, H, eps=1e-6, want_state=False, keep_ws=
 
 
 def favor_bwd_dn_ok(dtype, B, T, H, dh, n_feat):
-    """True when favor_attn_bwd(dn=True) serves the problem (emo_hip.h: emo_favor_attn_bwd_dn — the single-segment slice kernels)."""
+    """True when favor_attn_bwd(dn=True) serves the problem (emo_hip.h: emo_attn_t.dout_is_dn — the single-segment slice kernels)."""
     return dtype == torch.bfloat16 and bool(lib.emo_favor_attn_bwd_dn_supported(dtype_code(dtype), B, T, H, dh, n_feat))
 
 
@@ -312,20 +321,18 @@ def favor_attn_bwd(q, k, v, omega, out, dout, den, B, T, H, dqkv=None, eps=1e-6,
     if dqkv is None:
         dqkv = torch.empty(M, 3 * HD, device=q.device, dtype=q.dtype)
     dq, dk, dv = dqkv[:, :HD], dqkv[:, HD:2 * HD], dqkv[:, 2 * HD:]
-    if dn:
-        with _timed('favor_bwd', 0.0, 7.0 * M * HD * q.element_size()):
-            check(lib.emo_favor_attn_bwd_dn(ptr(q), ptr(k), ptr(v), _rows(q), ptr(omega), ptr(out), ptr(dout), HD, ptr(dq), ptr(dk), ptr(dv), 3 * HD,
-                                            dtype_code(q.dtype), B, T, H, dh, n_feat, eps, stream()))
-        return dq, dk, dv
-    if ws_saved is not None:                                      # the forward's private workspace: its K-state increments are still there
+    if dn:                                                        # single-segment scan: no workspace either
+        ws, ws_bytes, kvalid = None, 0, 0
+    elif ws_saved is not None:                                    # the forward's private workspace: its K-state increments are still there
         ws, ws_bytes, kvalid = ws_saved, ws_saved.numel(), 1
         assert ws_bytes == lib.emo_favor_attn_workspace_bytes(B, T, H, dh, n_feat)
     else:
         (ws, ws_bytes), kvalid = _favor_workspace(q.device, B, T, H, dh, n_feat), 0
     # read q, k, v, dout (+ out) + write dq, dk, dv = 7 * H*dh * e per token
     with _timed('favor_bwd', 0.0, 7.0 * M * HD * q.element_size()):
-        check(lib.emo_favor_attn_bwd_kstate(ptr(q), ptr(k), ptr(v), _rows(q), ptr(omega), ptr(out), ptr(dout), HD, ptr(den), ptr(dq), ptr(dk), ptr(dv),
-                                            3 * HD, dtype_code(q.dtype), B, T, H, dh, n_feat, eps, ptr(ws), ws_bytes, kvalid, stream()))
+        _attn(ATTN_FAVOR, ATTN_BWD, q, k, v, B, T, H, omega=ptr(omega), out=ptr(out), dout=ptr(dout), ld_out=HD, den=ptr(den),
+              dq=ptr(dq), dk=ptr(dk), dv=ptr(dv), ld_d=3 * HD, n_feat=n_feat, eps=eps, workspace=ptr(ws), workspace_bytes=ws_bytes,
+              kstate_valid=kvalid, dout_is_dn=int(dn))
     return dq, dk, dv
 
 
@@ -439,7 +446,6 @@ def softmax_attn_fwd(q, k, v, B, T, H, p_drop=0.0, seed=0, offset=0, want_keep=F
     """want_keep: also return the dropout keep words for softmax_attn_bwd (None when the call has none: include/emo_hip.h)."""
     M, HD = q.shape
     dh = HD // H
-    assert M == B * T and _rows(q) == _rows(k) == _rows(v)
     out = torch.empty(M, HD, device=q.device, dtype=q.dtype)
     lse = torch.empty(B, H, T, device=q.device, dtype=torch.float32)
     keep, kbytes = None, 0
@@ -449,8 +455,8 @@ def softmax_attn_fwd(q, k, v, B, T, H, p_drop=0.0, seed=0, offset=0, want_keep=F
             keep = torch.empty(kbytes // 4, device=q.device, dtype=torch.int32)
     # 2 matmuls (Q K^T, P V) of 2*T*T*dh FLOP per (b, h), half of the tiles skipped by the causal mask
     with _timed('sattn_fwd', 0.5 * 2 * 2.0 * B * H * T * T * dh, 4.0 * M * HD * q.element_size()):
-        check(lib.emo_softmax_attn_fwd_keep(ptr(q), ptr(k), ptr(v), _rows(q), ptr(out), HD, ptr(lse), dtype_code(q.dtype), B, T, H, dh, p_drop,
-                                            seed, offset, ptr(keep), kbytes, stream()))
+        _attn(ATTN_SOFTMAX, ATTN_FWD, q, k, v, B, T, H, out=ptr(out), ld_out=HD, lse=ptr(lse), p_drop=p_drop, seed=seed, offset=offset,
+              keep=ptr(keep), keep_bytes=kbytes)
     return (out, lse, keep) if want_keep else (out, lse)
 
 
@@ -464,8 +470,9 @@ def softmax_attn_bwd(q, k, v, out, dout, lse, B, T, H, p_drop=0.0, seed=0, offse
     delta = torch.empty(B, H, T, device=q.device, dtype=torch.float32)          # dO.O per query row, handed from the dQ to the dK/dV pass
     # dQ pass: S, dP, dQ; dK/dV pass: S, dP, dV, dK = 7 matmuls, causal half
     with _timed('sattn_bwd', 0.5 * 7 * 2.0 * B * H * T * T * dh, 8.0 * M * HD * q.element_size()):
-        check(lib.emo_softmax_attn_bwd_keep(ptr(q), ptr(k), ptr(v), _rows(q), ptr(out), ptr(dout), HD, ptr(lse), ptr(delta), ptr(dq), ptr(dk), ptr(dv), 3 * HD,
-                                            dtype_code(q.dtype), B, T, H, dh, p_drop, seed, offset, ptr(keep), 0 if keep is None else keep.numel() * 4, stream()))
+        _attn(ATTN_SOFTMAX, ATTN_BWD, q, k, v, B, T, H, out=ptr(out), dout=ptr(dout), ld_out=HD, lse=ptr(lse), delta_ws=ptr(delta), dq=ptr(dq),
+              dk=ptr(dk), dv=ptr(dv), ld_d=3 * HD, p_drop=p_drop, seed=seed, offset=offset, keep=ptr(keep),
+              keep_bytes=0 if keep is None else keep.numel() * 4)
     return dq, dk, dv
 
 
@@ -479,22 +486,21 @@ def softmax_attn_decode(q, kcache, vcache, lens, H, lens_off=0, k_new=None, v_ne
     assert not head_major or (kcache.shape[1] == H and kcache.shape[3] == HD // H)
     assert (k_new is None) == (v_new is None) and (k_new is None or _rows(k_new) == _rows(v_new))
     out = torch.empty(n, HD, device=q.device, dtype=q.dtype)
-    check(lib.emo_softmax_attn_decode_layout(ptr(q), _rows(q), ptr(kcache), ptr(vcache), T_max, ptr(lens), lens_off, ptr(k_new), ptr(v_new),
-                                             0 if k_new is None else _rows(k_new), ptr(out), HD, dtype_code(q.dtype), n, H, HD // H, int(head_major), stream()))
+    check(lib.emo_softmax_attn_decode(ptr(q), _rows(q), ptr(kcache), ptr(vcache), T_max, ptr(lens), lens_off, ptr(k_new), ptr(v_new),
+                                      0 if k_new is None else _rows(k_new), ptr(out), HD, dtype_code(q.dtype), n, H, HD // H, int(head_major), stream()))
     return out
 
 
 def relpos_attn_fwd(q, k, v, r_dist, r_w_bias, r_r_bias, B, T, H, p_drop=0.0, seed=0, offset=0):
     """Transformer-XL relative-position causal attention (stage 1).  q,k,v [B*T, H*dh] views; r_dist [>=T, H*dh] indexed by distance."""
     M, HD = q.shape
-    dh = HD // H
-    assert M == B * T and _rows(q) == _rows(k) == _rows(v) and r_dist.shape[0] >= T and r_dist.dtype == q.dtype
+    assert r_dist.shape[0] >= T and r_dist.dtype == q.dtype
     assert r_w_bias.dtype == torch.float32 and r_r_bias.dtype == torch.float32 and r_w_bias.is_contiguous() and r_r_bias.is_contiguous()
     out = torch.empty(M, HD, device=q.device, dtype=q.dtype)
     lse = torch.empty(B, H, T, device=q.device, dtype=torch.float32)
     zden = torch.empty(B, H, T, device=q.device, dtype=torch.float32)
-    check(lib.emo_relpos_attn_fwd(ptr(q), ptr(k), ptr(v), _rows(q), ptr(r_dist), _rows(r_dist), r_dist.shape[0], ptr(r_w_bias), ptr(r_r_bias), ptr(out), HD,
-                                  ptr(lse), ptr(zden), dtype_code(q.dtype), B, T, H, dh, p_drop, seed, offset, stream()))
+    _attn(ATTN_RELPOS, ATTN_FWD, q, k, v, B, T, H, r_dist=ptr(r_dist), ld_r=_rows(r_dist), n_dist=r_dist.shape[0], r_w_bias=ptr(r_w_bias),
+          r_r_bias=ptr(r_r_bias), out=ptr(out), ld_out=HD, lse=ptr(lse), zden=ptr(zden), p_drop=p_drop, seed=seed, offset=offset)
     return out, lse, zden
 
 
@@ -513,9 +519,11 @@ def relpos_attn_bwd(qkv, r_dist, r_w_bias, r_r_bias, out, dout, lse, zden, B, T,
     assert dq_rel.shape == (M, D) and dq_rel.dtype == dt and dq_rel.is_contiguous()
     delta = torch.empty(B, H, T, device=dev, dtype=torch.float32)
     q, k, v = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
-    check(lib.emo_relpos_attn_bwd(ptr(q), ptr(k), ptr(v), D3, ptr(r_dist), _rows(r_dist), r_dist.shape[0], ptr(r_w_bias), ptr(r_r_bias), ptr(out),
-                                  ptr(dout), D, ptr(lse), ptr(zden), ptr(dqkv), D3, ptr(dq_rel), D, ptr(delta), dtype_code(dt), B, T, H, dh, p_drop,
-                                  seed, offset, stream()))
+    # what the three passes share: r_dist, the incoming gradient, the saved statistics and the dropout stream
+    common = dict(r_dist=ptr(r_dist), ld_r=_rows(r_dist), n_dist=r_dist.shape[0], dout=ptr(dout), ld_out=D, lse=ptr(lse), zden=ptr(zden), delta=ptr(delta),
+                  ld_d=D3, p_drop=p_drop, seed=seed, offset=offset)
+    _attn(ATTN_RELPOS, ATTN_BWD, q, k, v, B, T, H, r_w_bias=ptr(r_w_bias), r_r_bias=ptr(r_r_bias), out=ptr(out), dq=ptr(dqkv), dq_rel=ptr(dq_rel), ld_rel=D,
+          **common)
     if acc_rr is not None:                                      # training stack: column sums accumulated over the layers, no per-layer ATen ops —
         if acc_dq is not None:                                  # acc_dq += colsum(dq) (None: the caller takes it from the qkv_net weight-gradient
             colsum(dqkv[:, :D], out=acc_dq, accumulate=True)    # GEMM's a_rowsum, one launch fewer), acc_rr += colsum(dq_rel); the caller forms
@@ -527,17 +535,15 @@ def relpos_attn_bwd(qkv, r_dist, r_w_bias, r_r_bias, out, dout, lse, zden, B, T,
         d_rw = (colsum(dqkv[:, :D]) - d_rr).view(H, dh)         # ... of the content part = d r_w_bias
         d_rr = d_rr.view(H, dh)
     qu, qv = add_bias2(q, r_w_bias, r_r_bias)                   # q + r_w_bias, q + r_r_bias
-    check(lib.emo_relpos_attn_bwd_kv(ptr(qu), ptr(qv), D, ptr(k), ptr(v), D3, ptr(r_dist), _rows(r_dist), r_dist.shape[0], ptr(dout), D, ptr(lse),
-                                     ptr(zden), ptr(delta), ptr(dqkv[:, D:2 * D]), ptr(dqkv[:, 2 * D:]), D3, dtype_code(dt), B, T, H, dh, p_drop, seed,
-                                     offset, stream()))
+    common.update(qu=ptr(qu), qv=ptr(qv), ld_q=D)
+    _attn(ATTN_RELPOS, ATTN_BWD_KV, qu, k, v, B, T, H, dk=ptr(dqkv[:, D:2 * D]), dv=ptr(dqkv[:, 2 * D:]), **common)
     if dR_out is not None:                                      # caller's fp32 [>= T, D] view (row-strided: one column block of a buffer shared by all layers)
         assert dR_out.dtype == torch.float32 and dR_out.shape[1] == D and dR_out.shape[0] >= T and dR_out.stride(1) == 1
         dR = dR_out
     else:
         dR = torch.empty(T, D, device=dev, dtype=torch.float32)
     ws, ws_bytes = _workspace('relpos_dr', dev, lib.emo_relpos_attn_bwd_r_workspace_bytes(B, T, H, dh))
-    check(lib.emo_relpos_attn_bwd_r(ptr(qu), ptr(qv), D, ptr(k), ptr(v), D3, ptr(r_dist), _rows(r_dist), r_dist.shape[0], ptr(dout), D, ptr(lse),
-                                    ptr(zden), ptr(delta), ptr(dR), _rows(dR), ptr(ws), ws_bytes, dtype_code(dt), B, T, H, dh, p_drop, seed, offset, stream()))
+    _attn(ATTN_RELPOS, ATTN_BWD_R, qu, k, v, B, T, H, dR=ptr(dR), ld_dr=_rows(dR), workspace=ptr(ws), workspace_bytes=ws_bytes, **common)
     return dqkv, dR, d_rw, d_rr
 
 

@@ -102,9 +102,9 @@ typedef struct {
     float* lna_mean;
     float* lna_rstd;
     /* Per-row, per-64-column-block divisor (r06): C[m][n] /= hdiv[((m / hdiv_T) * (N / 64) + n / 64) * hdiv_T + m % hdiv_T] — with hdiv = the FAVOR+
-     * normaliser den [B, H, T] (emo_favor_attn_fwd) and C = d(attention output) = the out-projection's dgrad, the product leaves as dN = dout / den
+     * normaliser den [B, H, T] (emo_attn_t.den) and C = d(attention output) = the out-projection's dgrad, the product leaves as dN = dout / den
      * (the first thing both backward sweeps of causal_product form), in ONE rounding from the fp32 accumulators, and
-     * emo_favor_attn_bwd_dn takes it without the normaliser.  Replaces the d(out)/den scalings inside the causal_product backward reached from
+     * the FAVOR backward takes it without the normaliser (emo_attn_t.dout_is_dn).  Replaces the d(out)/den scalings inside the causal_product backward reached from
      * fast_transformer_decoder.py:33-40.  Only with a plain epilogue in the A-stationary class (bf16 in / out, NT, K = 512, M % 128 == 0, M >= 4096,
      * N % 64 == 0) and hdiv_T % 32 == 0, M % hdiv_T == 0; refused elsewhere. */
     const float* hdiv;
@@ -167,67 +167,127 @@ int emo_layernorm_fwd(const void* x, const float* gamma, const float* beta, void
                       float* rstd, int dtype, int64_t M, int64_t D, float eps, emo_stream_t stream);
 /* dx = LN'(dy) (+ dres);  dx_drop (optional) = dx * dropmask(p,seed,offset);  dgamma/dbeta += (atomic);
  * dcol (optional, fp32 [D]) += column sums of dx_drop (of dx when dx_drop is NULL) — the bias gradient of the Linear
- * whose output fed this LayerNorm's residual branch, fused here to save one pass over the tensor. */
-int emo_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean,
-                      const float* rstd, const void* dres, void* dx, void* dx_drop, float* dgamma,
-                      float* dbeta, float* dcol, int dtype, int64_t M, int64_t D, float p_drop,
-                      uint64_t seed, uint64_t offset, emo_stream_t stream);
-/* The same with a caller-owned scratch for the three column sums (dgamma, dbeta, dcol): every block writes its partial sums to the workspace
+ * whose output fed this LayerNorm's residual branch, fused here to save one pass over the tensor.
+ * workspace: a caller-owned scratch for the three column sums (dgamma, dbeta, dcol): every block writes its partial sums to the workspace
  * and a second small kernel adds them in block order — no atomics, so these gradients are bit-reproducible and the 3 x D atomics per block
  * (a third of the kernel's time at 8192 rows) are gone.  emo_layernorm_bwd_workspace_bytes() = 0 means the shape takes the generic
  * kernel (atomics); workspace = NULL or too small falls back to the atomic accumulation as well.  Contents need not survive the call. */
 int64_t emo_layernorm_bwd_workspace_bytes(int dtype, int64_t M, int64_t D);
-int emo_layernorm_bwd_ws(const void* dy, const void* x, const float* gamma, const float* mean,
-                         const float* rstd, const void* dres, void* dx, void* dx_drop, float* dgamma,
-                         float* dbeta, float* dcol, int dtype, int64_t M, int64_t D, float p_drop,
-                         uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes,
-                         emo_stream_t stream);
+int emo_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean,
+                      const float* rstd, const void* dres, void* dx, void* dx_drop, float* dgamma,
+                      float* dbeta, float* dcol, int dtype, int64_t M, int64_t D, float p_drop,
+                      uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes,
+                      emo_stream_t stream);
 /* out = x * dropmask  (backward of a dropout whose forward was fused in a GEMM epilogue) */
 int emo_dropout_apply(const void* x, void* out, int dtype, int64_t n, float p_drop, uint64_t seed,
                       uint64_t offset, emo_stream_t stream);
 
-/* ------------------------------------------------------------------ K3+K4: FAVOR+ causal linear attention
- * q,k,v: [B*T, H*dh] views with row stride ld (a fused [B*T,3*H*dh] projection works);
- * omega [dh, n_feat/2] fp32; out [B*T, H*dh] (ld_out); den [B,H,T] fp32 (saved for backward).
+/* ------------------------------------------------------------------ K3+K4, K5, K5r: the attention kernels of the training step
+ * ONE entry, emo_attn, with ONE argument block, emo_attn_t: `kind` selects the attention, `pass` the forward or a backward pass of it.  q, k, v:
+ * [B*T, H*dh] views with row stride ld (a fused [B*T, 3*H*dh] projection works; batch-major); out [B*T, H*dh] (ld_out).
+ *
+ * EMO_ATTN_FAVOR — FAVOR+ causal linear attention (K3+K4).  omega [dh, n_feat/2] fp32; den [B,H,T] fp32 (saved for backward).
  * state_S [B,H,n_feat,dh] / state_z [B,H,n_feat] fp32: optional final scan state (decode prefill).
  * Replaces fast-transformers Favor.forward + CausalLinearAttention.forward + native
  * causal_product (called via model/fast_transformer_decoder.py:28-40) and their backward.
+ *   workspace: when B*H workgroups cannot fill the GPU (the reference's default batch_size 4 x 8 heads
+ *   = 32), the scan is cut into P time segments that run in parallel: a state-only pass writes each
+ *   segment's state increment to the workspace and the main pass starts every segment from the sum
+ *   of the increments before it (behind it, for the reverse sweep of dk/dv).  The caller owns the
+ *   scratch: emo_favor_attn_workspace_bytes() gives its size (0 = single segment; same value for
+ *   fwd and bwd, contents need not survive between calls).  workspace = NULL forces P = 1.
+ *   kstate_valid (BWD): when the segment-parallel scan is in use (emo_favor_attn_workspace_bytes() > 0) the backward first recomputes the per-segment
+ *   K-state increments that the forward call left in ITS workspace.  A caller that kept that buffer untouched for the matching backward passes
+ *   it here with kstate_valid = 1 and saves the state-only pass (one launch per layer); the buffer is then reused for the R-state increments as usual.
+ *   dout_is_dn (BWD, r06): the incoming gradient is already divided by the normaliser: `dout` = dN = dout / den, as the out-projection's dgrad leaves
+ *   it when its epilogue carries emo_epilogue_t.hdiv = den (one rounding from the fp32 accumulators instead of bf16(dout) then bf16(dout / den)); the
+ *   kernels then need neither den nor the rescaled operand copies (dD_t = -(dN_t . out_t)), and no workspace.  Same reference lines (the native
+ *   causal_product backward reached from fast_transformer_decoder.py:33-40).  Served by the single-segment slice kernels only — bf16, d_head 64,
+ *   128 features, T % 32 == 0, B * H >= 256 (emo_favor_attn_bwd_dn_supported() = 1); refused elsewhere, the caller then keeps the plain form.
  *
- * workspace: when B*H workgroups cannot fill the GPU (the reference's default batch_size 4 x 8 heads
- * = 32), the scan is cut into P time segments that run in parallel: a state-only pass writes each
- * segment's state increment to the workspace and the main pass starts every segment from the sum
- * of the increments before it (behind it, for the reverse sweep of dk/dv).  The caller owns the
- * scratch: emo_favor_attn_workspace_bytes() gives its size (0 = single segment; same value for
- * fwd and bwd, contents need not survive between calls).  workspace = NULL forces P = 1. */
+ * EMO_ATTN_SOFTMAX — causal softmax attention (K5, GPT-2).  Replaces HF GPT2Attention._attn (model/music_gpt2.py:86):
+ * softmax(q k^T/sqrt(dh) + causal) [dropout] v.  lse [B,H,T] fp32 saved for backward.  Dropout index = ((b*H+h)*T + i)*T + j.
+ *   delta_ws (BWD): caller scratch [B,H,T] fp32 (dO.O per query row: written by the dQ pass, read by the dK/dV pass).
+ *   keep: the attention-dropout keep decisions handed from the forward to the backward: the forward writes one bit per score at or below the
+ *   diagonal (32-bit words [B*H][T/64 key tiles][2][T rows], emo_softmax_attn_keep_bytes() bytes — 0 when the call is not served by the 32 x 32
+ *   MFMA kernels: then pass keep = NULL), the dK/dV pass reads the bits instead of re-evaluating the keyed hash per score.  Results are
+ *   bit-identical to the calls without the buffer (same hash, evaluated once).
+ *
+ * EMO_ATTN_RELPOS — relative-position causal attention (K5r, stage-1 Transformer-XL).  SURVEY §8 f-1.  Replaces
+ * RelPartialLearnableMultiHeadAttn's score / softmax / value product (stage1_compose/model/optimus_txl_decoder.py:331-366) including
+ * `_rel_shift` (:280-293):
+ *   score[i][j] = ((q_i + r_w_bias).k_j + (q_i + r_r_bias).R[i-j]) / sqrt(dh),  j <= i
+ *   prob = softmax -> dropout -> p / (sum_j p + 1e-8);  out = prob v
+ * r_dist [n_dist >= T, H*dh] (ld_r) = r_net(pos_emb) indexed BY DISTANCE (row d = the reference's r_head_k[klen-1-d]).  r_w_bias / r_r_bias
+ * [H, dh] fp32.  lse [B,H,T], zden [B,H,T] (may be NULL in FWD: the renormalisation denominator E/l + 1e-8) are saved for the backward passes.
+ *   BWD, the query-tile pass: recomputes the probabilities per query tile and returns dq = dq_content + dq_relative (dq_content = ds.K/sqrt(dh),
+ *   dq_relative[i] = sum_j ds_ij R[i-j]/sqrt(dh), both accumulated in-kernel) plus dq_rel = the relative part alone ([B*T, H*dh], pitch ld_rel,
+ *   dtype of q): d r_r_bias = colsum(dq_rel), d r_w_bias = colsum(dq) - colsum(dq_rel).  delta (may be NULL) [B,H,T] fp32: dO.O per query row,
+ *   for the two passes below.
+ *   BWD_KV, the key-tile pass: dk, dv in one kernel.  qu = q + r_w_bias, qv = q + r_r_bias [B*T, H*dh] (pitch ld_q) materialised by the
+ *   caller (emo_add_bias2); delta as exported by BWD.
+ *   BWD_R, the distance-window pass: dR [T, ld_dr] fp32 (overwritten) = gradient of r_dist rows 0..T-1,
+ *   dR[dist][h*dh + d] = sum_{b,i} ds[b,h,i,i-dist] (q_i + r_r_bias)[d] / sqrt(dh).  One workgroup per (b, h, tile diagonal); the partial windows
+ *   go through `workspace` (emo_relpos_attn_bwd_r_workspace_bytes) and are summed in a fixed order (deterministic).  qu, qv, delta as for BWD_KV.
+ *   Replaces the reference's autograd through _rel_shift (optimus_txl_decoder.py:280-293, 331-366).
+ *
+ * A field that a kind/pass does not read is ignored, whatever it holds (the comment of each field names its readers).  The block is read at
+ * call time and holds raw device addresses: its owner keeps the memory alive until the launches are queued. */
+enum { EMO_ATTN_FAVOR = 0, EMO_ATTN_SOFTMAX = 1, EMO_ATTN_RELPOS = 2 };
+enum { EMO_ATTN_FWD = 0, EMO_ATTN_BWD = 1, EMO_ATTN_BWD_KV = 2 /* RELPOS */, EMO_ATTN_BWD_R = 3 /* RELPOS */ };
+typedef struct {
+    int32_t kind;              /* EMO_ATTN_FAVOR / SOFTMAX / RELPOS */
+    int32_t pass;              /* EMO_ATTN_FWD / BWD; RELPOS also BWD_KV, BWD_R */
+    /* --- all kinds */
+    const void *q, *k, *v;     /* 16-B aligned; q: not RELPOS BWD_KV / BWD_R (they take qu, qv) */
+    int64_t ld;                /* row stride of q, k, v: a multiple of 16 B */
+    void* out;                 /* FWD: written; BWD (all kinds): read.  16-B aligned */
+    const void* dout;          /* every backward pass: [B*T, H*dh] (ld_out), 16-B aligned */
+    int64_t ld_out;            /* row stride of out and dout */
+    void *dq, *dk, *dv;        /* BWD of FAVOR, SOFTMAX: all three; RELPOS BWD: dq, RELPOS BWD_KV: dk, dv.  16-B aligned */
+    int64_t ld_d;              /* row stride of dq, dk, dv: a multiple of 4 */
+    int32_t dtype;             /* EMO_F32 / EMO_BF16 of q, k, v, out and the gradients */
+    int64_t B, T, H, dh;
+    float p_drop;              /* SOFTMAX, RELPOS: dropout on the probabilities, regenerated in every pass from (seed, offset) */
+    uint64_t seed, offset;
+    void* workspace;           /* FAVOR (not with dout_is_dn): segment states or NULL; RELPOS BWD_R: the partial windows.  16-B aligned */
+    int64_t workspace_bytes;
+    /* --- FAVOR */
+    const float* omega;
+    float* den;                /* FWD: written; BWD: read (not with dout_is_dn) */
+    float *state_S, *state_z;  /* FWD: NULL or both */
+    int64_t n_feat;            /* even */
+    float eps;                 /* the normaliser's epsilon */
+    int32_t kstate_valid;      /* BWD: `workspace` still holds the forward's K-state increments */
+    int32_t dout_is_dn;        /* BWD: dout is dN = dout / den */
+    /* --- SOFTMAX, RELPOS */
+    float* lse;                /* FWD: written; every backward pass: read */
+    /* --- SOFTMAX */
+    float* delta_ws;           /* BWD */
+    void* keep;                /* NULL or the keep words: FWD writes, BWD reads */
+    int64_t keep_bytes;
+    /* --- RELPOS */
+    const void* r_dist;        /* 16-B aligned */
+    int64_t ld_r, n_dist;      /* ld_r: a multiple of 16 B; n_dist >= T */
+    const float *r_w_bias, *r_r_bias;   /* FWD, BWD */
+    float* zden;               /* FWD: written (or NULL); every backward pass: read */
+    void* dq_rel;              /* BWD.  16-B aligned */
+    int64_t ld_rel;            /* BWD: a multiple of 4 */
+    float* delta;              /* BWD: written (or NULL); BWD_KV, BWD_R: read */
+    const void *qu, *qv;       /* BWD_KV, BWD_R.  16-B aligned */
+    int64_t ld_q;              /* row stride of qu, qv */
+    float* dR;                 /* BWD_R */
+    int64_t ld_dr;             /* BWD_R: >= H * dh */
+} emo_attn_t;
+/* sizeof(emo_attn_t) as the library was built (a binding checks its mirror against it, as with emo_epilogue_size) */
+int emo_attn_size(void);
+/* Messages name the kind and the pass: "emo_attn[favor, fwd]: ", "emo_attn[favor, bwd, dn]: " (dout_is_dn), "emo_attn[relpos, bwd_kv]: " ... */
+int emo_attn(const emo_attn_t* args, emo_stream_t stream);
+/* the sizes and classes named above: pure functions of the problem (and of the EMO_FAVOR_* switches) */
 int64_t emo_favor_attn_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t dh, int64_t n_feat);
-int emo_favor_attn_fwd(const void* q, const void* k, const void* v, int64_t ld, const float* omega,
-                       void* out, int64_t ld_out, float* den, float* state_S, float* state_z,
-                       int dtype, int64_t B, int64_t T, int64_t H, int64_t dh, int64_t n_feat,
-                       float eps, void* workspace, int64_t workspace_bytes, emo_stream_t stream);
-int emo_favor_attn_bwd(const void* q, const void* k, const void* v, int64_t ld, const float* omega,
-                       const void* out, const void* dout, int64_t ld_out, const float* den,
-                       void* dq, void* dk, void* dv, int64_t ld_d, int dtype, int64_t B, int64_t T,
-                       int64_t H, int64_t dh, int64_t n_feat, float eps, void* workspace,
-                       int64_t workspace_bytes, emo_stream_t stream);
-/* The same with the forward's workspace handed over: when the segment-parallel scan is in use (emo_favor_attn_workspace_bytes() > 0) the
- * backward first recomputes the per-segment K-state increments that the forward call left in ITS workspace.  A caller that kept that buffer
- * untouched for the matching backward passes it here with kstate_valid = 1 and saves the state-only pass (one launch per layer); the buffer is
- * then reused for the R-state increments as usual.  kstate_valid = 0: exactly emo_favor_attn_bwd. */
-int emo_favor_attn_bwd_kstate(const void* q, const void* k, const void* v, int64_t ld, const float* omega,
-                              const void* out, const void* dout, int64_t ld_out, const float* den, void* dq,
-                              void* dk, void* dv, int64_t ld_d, int dtype, int64_t B, int64_t T, int64_t H,
-                              int64_t dh, int64_t n_feat, float eps, void* workspace, int64_t workspace_bytes,
-                              int kstate_valid, emo_stream_t stream);
-/* The backward with the incoming gradient already divided by the normaliser (r06): `dn` = dN = dout / den, as the out-projection's dgrad leaves it
- * when its epilogue carries emo_epilogue_t.hdiv = den (one rounding from the fp32 accumulators instead of bf16(dout) then bf16(dout / den)); the kernels
- * then need neither den nor the rescaled operand copies (dD_t = -(dN_t . out_t)).  Same reference lines as emo_favor_attn_bwd (the native
- * causal_product backward reached from fast_transformer_decoder.py:33-40).  Served by the single-segment slice kernels only — bf16, d_head 64,
- * 128 features, T % 32 == 0, B * H >= 256 (emo_favor_attn_bwd_dn_supported() = 1); EMO_ERR_UNSUPPORTED elsewhere, the caller then keeps the plain form. */
 int emo_favor_attn_bwd_dn_supported(int dtype, int64_t B, int64_t T, int64_t H, int64_t dh, int64_t n_feat);
-int emo_favor_attn_bwd_dn(const void* q, const void* k, const void* v, int64_t ld, const float* omega,
-                          const void* out, const void* dn, int64_t ld_out, void* dq, void* dk, void* dv,
-                          int64_t ld_d, int dtype, int64_t B, int64_t T, int64_t H, int64_t dh, int64_t n_feat,
-                          float eps, emo_stream_t stream);
+int64_t emo_softmax_attn_keep_bytes(int dtype, int64_t B, int64_t T, int64_t H, int64_t dh, float p_drop);
+int64_t emo_relpos_attn_bwd_r_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t dh);
 /* one recurrent step per stream: state += phi(k) (x) v ; out = phi(q)^T S / (phi(q).z + eps) */
 int emo_favor_decode_step(const void* q, const void* k, const void* v, int64_t ld, const float* omega,
                           float* state_S, float* state_z, void* out, int64_t ld_out, int dtype,
@@ -333,89 +393,20 @@ int emo_decode_step(const emo_decode_step_t* args, emo_stream_t stream);
 int emo_favor_draw_omega(const float* gauss, float* omega, int64_t n_layers, int64_t dh, int64_t n_feat,
                          emo_stream_t stream);
 
-/* ------------------------------------------------------------------ K5: causal softmax attention (GPT-2)
- * Replaces HF GPT2Attention._attn (model/music_gpt2.py:86): softmax(q k^T/sqrt(dh) + causal) [dropout] v.
- * lse [B,H,T] fp32 saved for backward.  Dropout index = ((b*H+h)*T + i)*T + j. */
-int emo_softmax_attn_fwd(const void* q, const void* k, const void* v, int64_t ld, void* out,
-                         int64_t ld_out, float* lse, int dtype, int64_t B, int64_t T, int64_t H,
-                         int64_t dh, float p_drop, uint64_t seed, uint64_t offset, emo_stream_t stream);
-/* delta_ws: caller scratch [B,H,T] fp32 (dO.O per query row: written by the dQ pass, read by the dK/dV pass). */
-int emo_softmax_attn_bwd(const void* q, const void* k, const void* v, int64_t ld, const void* out,
-                         const void* dout, int64_t ld_out, const float* lse, float* delta_ws,
-                         void* dq, void* dk, void* dv, int64_t ld_d, int dtype, int64_t B, int64_t T,
-                         int64_t H, int64_t dh, float p_drop, uint64_t seed, uint64_t offset,
-                         emo_stream_t stream);
-/* The same two calls with the attention-dropout keep decisions handed from the forward to the backward: the forward writes one bit per
- * score at or below the diagonal (32-bit words [B*H][T/64 key tiles][2][T rows], emo_softmax_attn_keep_bytes() bytes — 0 when the call is
- * not served by the 32 x 32 MFMA kernels: then pass keep = NULL), the dK/dV pass reads the bits instead of re-evaluating the keyed hash per
- * score.  Results are bit-identical to the calls without the buffer (same hash, evaluated once).  keep = NULL: exactly the calls above. */
-int64_t emo_softmax_attn_keep_bytes(int dtype, int64_t B, int64_t T, int64_t H, int64_t dh, float p_drop);
-int emo_softmax_attn_fwd_keep(const void* q, const void* k, const void* v, int64_t ld, void* out,
-                              int64_t ld_out, float* lse, int dtype, int64_t B, int64_t T, int64_t H,
-                              int64_t dh, float p_drop, uint64_t seed, uint64_t offset, void* keep,
-                              int64_t keep_bytes, emo_stream_t stream);
-int emo_softmax_attn_bwd_keep(const void* q, const void* k, const void* v, int64_t ld, const void* out,
-                              const void* dout, int64_t ld_out, const float* lse, float* delta_ws,
-                              void* dq, void* dk, void* dv, int64_t ld_d, int dtype, int64_t B,
-                              int64_t T, int64_t H, int64_t dh, float p_drop, uint64_t seed,
-                              uint64_t offset, const void* keep, int64_t keep_bytes, emo_stream_t stream);
-/* decode: one query row per stream against a KV cache [n_streams, T_max, H*dh]; lens[s] + lens_off = valid keys INCLUDING the new
+/* ------------------------------------------------------------------ K5 decode: causal softmax attention, one query row per stream (GPT-2)
+ * (the HF `past_key_values` path of GPT2Attention, model/music_gpt2.py:86) against a KV cache; lens[s] + lens_off = valid keys INCLUDING the new
  * token.  k_new / v_new [n_streams, H*dh] (ld_new; both or neither NULL): the new token's key / value rows, appended to the caches
- * at position len-1 by the kernel itself (the HF `past_key_values` concat of GPT2Attention). */
+ * at position len-1 by the kernel itself (the HF `past_key_values` concat of GPT2Attention).
+ * Cache layout (r06): head_major = 0: [n_streams, T_max, H*dh]; head_major = 1: [n_streams, H, T_max, dh] — the keys / values of one
+ * (stream, head) are one contiguous run, which is what the one workgroup per (stream, head) streams (the layout HF's `past_key_values` itself
+ * uses: [batch, head, seq, head_dim]). */
 int emo_softmax_attn_decode(const void* q, int64_t ld_q, void* kcache, void* vcache, int64_t T_max,
                             const int64_t* lens, int64_t lens_off, const void* k_new, const void* v_new,
                             int64_t ld_new, void* out, int64_t ld_out, int dtype, int64_t n_streams,
-                            int64_t H, int64_t dh, emo_stream_t stream);
-/* The same with the cache layout chosen by the caller (r06): head_major = 0: [n_streams, T_max, H*dh] as above; head_major = 1:
- * [n_streams, H, T_max, dh] — the keys / values of one (stream, head) are one contiguous run, which is what the one workgroup per (stream, head)
- * streams (the layout HF's `past_key_values` itself uses: [batch, head, seq, head_dim]). */
-int emo_softmax_attn_decode_layout(const void* q, int64_t ld_q, void* kcache, void* vcache, int64_t T_max,
-                                   const int64_t* lens, int64_t lens_off, const void* k_new, const void* v_new,
-                                   int64_t ld_new, void* out, int64_t ld_out, int dtype, int64_t n_streams,
-                                   int64_t H, int64_t dh, int head_major, emo_stream_t stream);
+                            int64_t H, int64_t dh, int head_major, emo_stream_t stream);
 
-/* ------------------------------------------------------------------ K5r: relative-position causal attention (stage-1 Transformer-XL)
- * SURVEY §8 f-1.  Replaces RelPartialLearnableMultiHeadAttn's score / softmax / value product
- * (stage1_compose/model/optimus_txl_decoder.py:331-366) including `_rel_shift` (:280-293):
- *   score[i][j] = ((q_i + r_w_bias).k_j + (q_i + r_r_bias).R[i-j]) / sqrt(dh),  j <= i
- *   prob = softmax -> dropout -> p / (sum_j p + 1e-8);  out = prob v
- * q,k,v: [B*T, H*dh] views (row stride ld; batch-major).  r_dist [n_dist >= T, H*dh] (ld_r) = r_net(pos_emb) indexed BY DISTANCE
- * (row d = the reference's r_head_k[klen-1-d]).  r_w_bias / r_r_bias [H, dh] fp32.  lse [B,H,T], zden [B,H,T] (may be NULL:
- * the renormalisation denominator E/l + 1e-8) are saved for the backward pass. */
-int emo_relpos_attn_fwd(const void* q, const void* k, const void* v, int64_t ld, const void* r_dist,
-                        int64_t ld_r, int64_t n_dist, const float* r_w_bias, const float* r_r_bias,
-                        void* out, int64_t ld_out, float* lse, float* zden, int dtype, int64_t B,
-                        int64_t T, int64_t H, int64_t dh, float p_drop, uint64_t seed,
-                        uint64_t offset, emo_stream_t stream);
-/* Backward, query-tile pass: recomputes the probabilities per query tile and returns dq = dq_content + dq_relative
- * (dq_content = ds.K/sqrt(dh), dq_relative[i] = sum_j ds_ij R[i-j]/sqrt(dh), both accumulated in-kernel) plus dq_rel = the relative part
- * alone ([B*T, H*dh], pitch ld_rel, dtype of q): d r_r_bias = colsum(dq_rel), d r_w_bias = colsum(dq) - colsum(dq_rel).
- * delta (may be NULL) [B,H,T] fp32: dO.O per query row, for emo_relpos_attn_bwd_kv / emo_relpos_attn_bwd_r. */
-int emo_relpos_attn_bwd(const void* q, const void* k, const void* v, int64_t ld, const void* r_dist,
-                        int64_t ld_r, int64_t n_dist, const float* r_w_bias, const float* r_r_bias,
-                        const void* out, const void* dout, int64_t ld_out, const float* lse,
-                        const float* zden, void* dq, int64_t ld_d, void* dq_rel, int64_t ld_rel,
-                        float* delta, int dtype, int64_t B, int64_t T, int64_t H, int64_t dh,
-                        float p_drop, uint64_t seed, uint64_t offset, emo_stream_t stream);
-/* Distance-window pass of the backward: dR [T, ld_dr] fp32 (overwritten) = gradient of r_dist rows 0..T-1,
- * dR[dist][h*dh + d] = sum_{b,i} ds[b,h,i,i-dist] (q_i + r_r_bias)[d] / sqrt(dh).  One workgroup per (b, h, tile diagonal); the partial
- * windows go through `workspace` (emo_relpos_attn_bwd_r_workspace_bytes) and are summed in a fixed order (deterministic).  qu, qv, delta as
- * for emo_relpos_attn_bwd_kv.  Replaces the reference's autograd through _rel_shift (optimus_txl_decoder.py:280-293, 331-366). */
-int64_t emo_relpos_attn_bwd_r_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t dh);
-int emo_relpos_attn_bwd_r(const void* qu, const void* qv, int64_t ld_q, const void* k, const void* v,
-                          int64_t ld, const void* r_dist, int64_t ld_r, int64_t n_dist, const void* dout,
-                          int64_t ld_out, const float* lse, const float* zden, const float* delta,
-                          float* dR, int64_t ld_dr, void* workspace, int64_t workspace_bytes, int dtype,
-                          int64_t B, int64_t T, int64_t H, int64_t dh, float p_drop, uint64_t seed,
-                          uint64_t offset, emo_stream_t stream);
-/* Key-tile pass of the backward: dk, dv in one kernel.  qu = q + r_w_bias, qv = q + r_r_bias
- * [B*T, H*dh] (pitch ld_q) materialised by the caller; delta [B,H,T] = dO.O per query row as exported by emo_relpos_attn_bwd. */
-int emo_relpos_attn_bwd_kv(const void* qu, const void* qv, int64_t ld_q, const void* k, const void* v,
-                           int64_t ld, const void* r_dist, int64_t ld_r, int64_t n_dist, const void* dout,
-                           int64_t ld_out, const float* lse, const float* zden, const float* delta,
-                           void* dk, void* dv, int64_t ld_d, int dtype, int64_t B, int64_t T, int64_t H,
-                           int64_t dh, float p_drop, uint64_t seed, uint64_t offset, emo_stream_t stream);
-/* one query row per stream against a KV cache (the reference re-projects its cached hidden states `mems` every step,
+/* ------------------------------------------------------------------ K5r decode: relative-position attention (stage-1 Transformer-XL, EMO_ATTN_RELPOS's score),
+ * one query row per stream against a KV cache (the reference re-projects its cached hidden states `mems` every step,
  * plain_transformer.py:52-59; k / v of a position do not change, so they are cached instead).  Keys j in
  * [max(0, len-1-mem_len), len) with len = lens[s] + lens_off; the distance of key j is len-1-j.  k_new / v_new as in
  * emo_softmax_attn_decode.  Eval semantics (no dropout). */
@@ -587,7 +578,7 @@ int emo_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, in
 int emo_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, emo_stream_t stream);
 /* o1 = x + b1, o2 = x + b2 with per-column fp32 biases [D]; x [M, D] (row pitch ld), o1 / o2 contiguous [M, D], same dtype.  The biased
  * query copies qu = q + r_w_bias, qv = q + r_r_bias of the relative-position attention (stage1_compose/model/optimus_txl_decoder.py:331-341:
- * rw_head_q / rr_head_q) for emo_relpos_attn_bwd_kv / _r, in one launch. */
+ * rw_head_q / rr_head_q) for the BWD_KV / BWD_R passes of EMO_ATTN_RELPOS, in one launch. */
 int emo_add_bias2(const void* x, int64_t ld, const float* b1, const float* b2, void* o1, void* o2, int dtype,
                   int64_t M, int64_t D, emo_stream_t stream);
 /* n bf16 transposes in one launch (no reference counterpart: the transposed weight mirrors that let every dgrad run as a k-contiguous NT

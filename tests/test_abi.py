@@ -168,3 +168,104 @@ def test_a_kind_ignores_the_fields_of_the_other_kinds():
         a = _grammar_step_args(kind, n_u=0, **kw)
         assert _lib.lib.emo_grammar_step(ctypes.byref(a), None) == -1
         assert _lib.lib.emo_last_error().decode() == 'emo_grammar_step[%s]: bad sizes' % _KIND_NAME[kind]
+
+
+def test_attn_struct_mirror_has_the_library_size():
+    # the ctypes mirror of emo_attn_t, as for the three structs above
+    from emo_disentanger_amd import _lib
+    assert _lib.lib.emo_attn_size() == ctypes.sizeof(_lib.Attn)
+
+
+_ATTN_KIND = {0: 'favor', 1: 'softmax', 2: 'relpos'}
+_ATTN_PASS = {0: 'fwd', 1: 'bwd', 2: 'bwd_kv', 3: 'bwd_r'}
+_ATTN_PASSES = [(0, 0), (0, 1), (1, 0), (1, 1), (2, 0), (2, 1), (2, 2), (2, 3)]          # every (kind, pass) the entry has
+
+
+def _attn_args(kind, pass_, **kw):
+    """A block that passes every host check of its (kind, pass) (pointer fields: small fake addresses, 16-byte aligned — validation never
+    dereferences them; such a block would go on to the launch, so every caller breaks one field), with the fields of `kw` changed.
+    bf16, B * H = 256 single-segment FAVOR scans (the dout_is_dn class), T = 128 with dropout (the class that has keep words)."""
+    from emo_disentanger_amd import _lib
+    a = _lib.Attn()
+    for name, ctype in _lib.Attn._fields_:
+        if ctype is _lib.c_p:
+            setattr(a, name, 0x1000)
+    a.kind, a.pass_, a.dtype, a.B, a.T, a.H, a.dh, a.n_feat = kind, pass_, _lib.BF16, 32, 128, 8, 64, 128
+    a.ld, a.ld_out, a.ld_d, a.ld_r, a.n_dist, a.ld_rel, a.ld_q, a.ld_dr = 1536, 512, 1536, 512, 128, 512, 512, 512
+    a.p_drop, a.seed, a.offset, a.eps = 0.1, 7, 3, 1e-6
+    a.keep_bytes = _lib.lib.emo_softmax_attn_keep_bytes(_lib.BF16, 32, 128, 8, 64, 0.1)
+    a.workspace_bytes = _lib.lib.emo_relpos_attn_bwd_r_workspace_bytes(32, 128, 8, 64)
+    assert a.keep_bytes > 0 and a.workspace_bytes > 0
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+@pytest.mark.parametrize('kind, pass_, kw, what', [
+    (0, 0, dict(omega=None), 'null pointer'), (0, 0, dict(n_feat=127), 'n_feat must be even'), (0, 0, dict(workspace=0x1008), 'workspace must be 16-B aligned'),
+    (0, 1, dict(den=None), 'null pointer'), (0, 1, dict(ld_d=1538), 'ld_d must be a multiple of 4'), (0, 1, dict(ld=1540), 'ld/dh must keep rows 16-B aligned'),
+    (0, 1, dict(dout_is_dn=1, dq=None), 'null pointer'), (0, 1, dict(dout_is_dn=1, B=4, T=1024), 'dout_is_dn outside its class'),      # B * H = 32: a segmented scan
+    (0, 1, dict(dout_is_dn=1, dtype=0), 'dout_is_dn outside its class'),
+    (1, 0, dict(lse=None), 'bad out/lse'), (1, 0, dict(ld=1540), 'ld/dh must keep rows 16-B aligned'), (1, 0, dict(keep_bytes=1024), 'keep buffer of 1024 bytes'),
+    (1, 1, dict(delta_ws=None), 'null pointer'), (1, 1, dict(ld_d=1538), 'ld_d % 4 == 0'), (1, 1, dict(keep_bytes=1024), 'keep buffer of 1024 bytes'),
+    (1, 1, dict(dtype=3), 'bad dtype'),
+    (2, 0, dict(r_dist=None), 'null pointer'), (2, 0, dict(n_dist=127), 'a row for every distance'), (2, 0, dict(ld_r=516), 'r_dist must keep rows 16-B aligned'),
+    (2, 1, dict(dq_rel=None), 'null pointer'), (2, 1, dict(ld_rel=510), 'ld_rel % 4 == 0'), (2, 1, dict(q=None), 'null pointer'),
+    (2, 2, dict(qv=None), 'null pointer'), (2, 2, dict(ld_d=1538), 'ld_d % 4 == 0'), (2, 2, dict(qu=None), 'null pointer'), (2, 2, dict(ld_q=516), 'qu / qv / dout'),
+    (2, 3, dict(dR=None), 'dR / workspace'), (2, 3, dict(workspace_bytes=1024), 'workspace too small'), (2, 3, dict(ld_dr=256), 'a column for every (h, d)'),
+])
+def test_attn_refuses_bad_arguments_without_a_gpu_and_names_its_kind_and_pass(kind, pass_, kw, what):
+    from emo_disentanger_amd import _lib
+    a = _attn_args(kind, pass_, **kw)
+    assert _lib.lib.emo_attn(ctypes.byref(a), None) == -1          # (-1: a host refusal; a HIP call on this machine would come back as -2)
+    msg = _lib.lib.emo_last_error().decode()
+    assert what in msg
+    assert msg.startswith('emo_attn[%s, %s%s]: ' % (_ATTN_KIND[kind], _ATTN_PASS[pass_], ', dn' if a.dout_is_dn else ''))
+    with pytest.raises(_lib.EmoError):
+        _lib.check(-1)
+
+
+def test_attn_refusal_cases_cover_every_kind_and_pass():
+    cases = test_attn_refuses_bad_arguments_without_a_gpu_and_names_its_kind_and_pass.pytestmark[0].args[1]
+    assert {(c[0], c[1]) for c in cases} == set(_ATTN_PASSES)
+
+
+def test_attn_refuses_an_empty_a_missing_and_an_unknown_block_without_a_gpu():
+    from emo_disentanger_amd import _lib
+    a = _lib.Attn()
+    assert _lib.lib.emo_attn(ctypes.byref(a), None) == -1
+    assert _lib.lib.emo_last_error().decode() == 'emo_attn[favor, fwd]: null pointer'
+    assert _lib.lib.emo_attn(None, None) == -1 and b'emo_attn: null argument block' in _lib.lib.emo_last_error()
+    assert _lib.lib.emo_attn(ctypes.byref(_attn_args(3, 0)), None) == -1
+    msg = _lib.lib.emo_last_error().decode()
+    assert msg.startswith('emo_attn: ') and 'kind 3' in msg
+    for kind, pass_ in ((0, 2), (1, 3), (2, 4), (0, -1)):           # BWD_KV / BWD_R are passes of RELPOS only
+        assert _lib.lib.emo_attn(ctypes.byref(_attn_args(kind, pass_)), None) == -1
+        msg = _lib.lib.emo_last_error().decode()
+        assert msg == 'emo_attn: kind %s has no pass %d' % (_ATTN_KIND[kind], pass_)
+
+
+def test_an_attention_kind_ignores_the_fields_of_the_other_kinds_and_passes():
+    # a block is refused for the fields of its own (kind, pass) only: with every other kind's and pass's fields NULL / zero it gets as far as the
+    # LAST host check of its own, which one broken field of its own then fails
+    favor = dict(omega=None, den=None, state_S=None, state_z=None, n_feat=1, eps=0.0, kstate_valid=1, dout_is_dn=0)
+    softmax = dict(delta_ws=None, keep=None, keep_bytes=0)
+    relpos = dict(r_dist=None, ld_r=1, n_dist=0, r_w_bias=None, r_r_bias=None, zden=None, dq_rel=None, ld_rel=1, delta=None, qu=None, qv=None, ld_q=1, dR=None,
+                  ld_dr=0)
+    bwd = dict(dout=None, dq=None, dk=None, dv=None, ld_d=1)
+    for kind, pass_, others, broken, what in (
+            (0, 0, dict(softmax, lse=None, **relpos, **bwd), dict(state_z=None), 'state_S without state_z'),
+            (0, 1, dict(softmax, lse=None, **relpos), dict(dout_is_dn=1, den=None, workspace=None, dv=0x1008), 'pointers must be 16-B aligned'),
+            (1, 0, dict(favor, workspace=None, **relpos, **bwd), dict(keep_bytes=16), 'keep buffer of 16 bytes'),
+            (1, 1, dict(favor, workspace=None, **relpos), dict(keep_bytes=16), 'keep buffer of 16 bytes'),
+            (2, 0, dict(favor, workspace=None, **softmax, **bwd, qu=None, qv=None, dq_rel=None, dR=None, delta=None, zden=None), dict(out=0x1008), 'out must be 16-B aligned'),
+            (2, 1, dict(favor, workspace=None, **softmax, dk=None, dv=None, qu=None, qv=None, dR=None, delta=None), dict(ld_rel=510), 'ld_rel % 4 == 0'),
+            (2, 2, dict(favor, workspace=None, **softmax, q=None, out=None, dq=None, dq_rel=None, dR=None, r_w_bias=None, r_r_bias=None), dict(ld_d=1538),
+             'ld_d % 4 == 0'),
+            (2, 3, dict(favor, **softmax, q=None, out=None, dq=None, dk=None, dv=None, ld_d=1, dq_rel=None, r_w_bias=None, r_r_bias=None),
+             dict(workspace_bytes=16), 'workspace too small')):
+        from emo_disentanger_amd import _lib
+        a = _attn_args(kind, pass_, **dict(others, **broken))
+        assert _lib.lib.emo_attn(ctypes.byref(a), None) == -1
+        msg = _lib.lib.emo_last_error().decode()
+        assert msg.startswith('emo_attn[%s, %s%s]: ' % (_ATTN_KIND[kind], _ATTN_PASS[pass_], ', dn' if a.dout_is_dn else '')) and what in msg, msg

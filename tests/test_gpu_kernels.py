@@ -723,7 +723,7 @@ def test_favor_slice_kernels_vs_oracle_and_generic(B, T, H, segs, monkeypatch):
         assert float((a - b_).abs().max()) <= 3e-2 * max(float(b_.abs().max()), 1e-6)
 
 
-# r06: the backward from a gradient that is already dN = dout / den (emo_favor_attn_bwd_dn; the out-projection dgrad divides in its epilogue:
+# r06: the backward from a gradient that is already dN = dout / den (emo_attn_t.dout_is_dn; the out-projection dgrad divides in its epilogue:
 # emo_epilogue_t.hdiv) against the fp64 quadratic form and against the plain form of the same kernels
 @pytest.mark.parametrize('B,T,H', [(2, 256, 2), (1, 32, 1), (3, 96, 3), (2, 2048, 1), (32, 512, 8)])
 def test_favor_backward_from_the_predivided_gradient(B, T, H, monkeypatch):
@@ -762,7 +762,7 @@ def test_favor_backward_from_the_predivided_gradient(B, T, H, monkeypatch):
 
 @pytest.mark.parametrize('M,T,N', [(4096, 512, 512), (32768, 2048, 512), (8192, 1024, 256)])
 def test_gemm_row_block_divisor_epilogue(M, T, N):
-    """emo_epilogue_t.hdiv: C[m][n] /= hdiv[m / T][n / 64][m % T] — the out-projection dgrad leaving dN = dout / den for emo_favor_attn_bwd_dn."""
+    """emo_epilogue_t.hdiv: C[m][n] /= hdiv[m / T][n / 64][m % T] — the out-projection dgrad leaving dN = dout / den for the FAVOR backward's dout_is_dn form."""
     ops = _ops()
     A, W = _r(M, 512, seed=1).to(torch.bfloat16).cuda(), _r(N, 512, seed=2, scale=0.1).to(torch.bfloat16).cuda()
     den = (torch.rand(M // T, N // 64, T, generator=torch.Generator().manual_seed(3)) * 4 + 0.25).cuda()
@@ -818,7 +818,8 @@ def test_favor_attention_segmented_scan(dt, B, T, H, dh, nf, segs, monkeypatch):
 
 def test_favor_workspace_contract():
     ops = _ops()
-    from emo_disentanger_amd._lib import lib, ptr, EmoError, check
+    import ctypes
+    from emo_disentanger_amd._lib import lib, ptr, EmoError, check, Attn, ATTN_FAVOR, ATTN_FWD
     from oracle.weights import orthogonal_omega
     B, T, H, dh, nf = 1, 512, 2, 32, 64
     need = lib.emo_favor_attn_workspace_bytes(B, T, H, dh, nf)
@@ -831,12 +832,13 @@ def test_favor_workspace_contract():
     out = torch.empty(B * T, HD, device='cuda')
     den = torch.empty(B, H, T, device='cuda')
     small = torch.empty(need - 16, dtype=torch.uint8, device='cuda')
+    a = Attn(kind=ATTN_FAVOR, pass_=ATTN_FWD, q=ptr(qkv[:, :HD]), k=ptr(qkv[:, HD:2 * HD]), v=ptr(qkv[:, 2 * HD:]), ld=3 * HD, omega=ptr(om), out=ptr(out),
+             ld_out=HD, den=ptr(den), dtype=0, B=B, T=T, H=H, dh=dh, n_feat=nf, eps=1e-6, workspace=ptr(small), workspace_bytes=small.numel())
     with pytest.raises(EmoError, match='workspace'):
-        check(lib.emo_favor_attn_fwd(ptr(qkv[:, :HD]), ptr(qkv[:, HD:2 * HD]), ptr(qkv[:, 2 * HD:]), 3 * HD, ptr(om), ptr(out), HD, ptr(den), None, None,
-                                     0, B, T, H, dh, nf, 1e-6, ptr(small), small.numel(), torch.cuda.current_stream().cuda_stream))
+        check(lib.emo_attn(ctypes.byref(a), torch.cuda.current_stream().cuda_stream))
     # NULL workspace = single-segment scan, same result as the wrapper's segmented call
-    check(lib.emo_favor_attn_fwd(ptr(qkv[:, :HD]), ptr(qkv[:, HD:2 * HD]), ptr(qkv[:, 2 * HD:]), 3 * HD, ptr(om), ptr(out), HD, ptr(den), None, None,
-                                 0, B, T, H, dh, nf, 1e-6, None, 0, torch.cuda.current_stream().cuda_stream))
+    a.workspace, a.workspace_bytes = None, 0
+    check(lib.emo_attn(ctypes.byref(a), torch.cuda.current_stream().cuda_stream))
     out2, den2 = ops.favor_attn_fwd(qkv[:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:], om, B, T, H)
     _close(out2, out, torch.float32, mult=3)
 
@@ -887,7 +889,7 @@ def test_softmax_attention_fwd_bwd(dt, B, T, H, dh):
     ql = qc[:, :HD].reshape(B, T, HD)[:, -1].contiguous()
     od = ops.softmax_attn_decode(ql, kc, vc, torch.full((B,), T, dtype=torch.int64, device='cuda'), H)
     _close(od, ref.view(B, T, HD)[:, -1], dt)
-    # head-major cache [B, H, T_max, dh] (r06, emo_softmax_attn_decode_layout) with the last key / value row appended by the kernel itself
+    # head-major cache [B, H, T_max, dh] (r06, emo_softmax_attn_decode's head_major) with the last key / value row appended by the kernel itself
     T_max = T + 5
     kh = torch.zeros(B, H, T_max, dh, device='cuda', dtype=dt)
     vh = torch.zeros(B, H, T_max, dh, device='cuda', dtype=dt)

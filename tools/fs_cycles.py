@@ -13,9 +13,13 @@ import emo_disentanger_amd.ops as O
 # call through ops with want_state: the DIAG kernel writes counters into the state buffer
 out, den, S, z = ops.favor_attn_fwd(q, k, v, om, B, T, H, want_state=True)
 S.zero_()
-from emo_disentanger_amd._lib import lib, ptr, check, dtype_code
+import ctypes
+from emo_disentanger_amd._lib import lib, ptr, check, dtype_code, Attn, ATTN_FAVOR, ATTN_FWD
 from emo_disentanger_amd.ops import stream
-check(lib.emo_favor_attn_fwd(ptr(q), ptr(k), ptr(v), 3 * HD, ptr(om), ptr(out), HD, ptr(den), ptr(S), ptr(z), dtype_code(q.dtype), B, T, H, dh, F, 1e-6, None, 0, stream()))
+# (the raw entry with NULL workspace: the single-segment scan whatever B * H is)
+a = Attn(kind=ATTN_FAVOR, pass_=ATTN_FWD, q=ptr(q), k=ptr(k), v=ptr(v), ld=3 * HD, omega=ptr(om), out=ptr(out), ld_out=HD, den=ptr(den), state_S=ptr(S),
+         state_z=ptr(z), dtype=dtype_code(q.dtype), B=B, T=T, H=H, dh=dh, n_feat=F, eps=1e-6)
+check(lib.emo_attn(ctypes.byref(a), stream()))
 torch.cuda.synchronize()
 d = S.view(-1)[:20].view(torch.int64).tolist()
 waves, nch = d[9], T // 32
