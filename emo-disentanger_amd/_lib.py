@@ -62,7 +62,7 @@ class Attn(ctypes.Structure):
                 ('omega', c_p), ('den', c_p), ('state_S', c_p), ('state_z', c_p), ('n_feat', c_l), ('eps', c_f), ('kstate_valid', ctypes.c_int32), ('dout_is_dn', ctypes.c_int32),
                 ('lse', c_p), ('delta_ws', c_p), ('keep', c_p), ('keep_bytes', c_l),
                 ('r_dist', c_p), ('ld_r', c_l), ('n_dist', c_l), ('r_w_bias', c_p), ('r_r_bias', c_p), ('zden', c_p), ('dq_rel', c_p), ('ld_rel', c_l), ('delta', c_p),
-                ('qu', c_p), ('qv', c_p), ('ld_q', c_l), ('dR', c_p), ('ld_dr', c_l)]
+                ('qu', c_p), ('qv', c_p), ('ld_q', c_l), ('dR', c_p), ('ld_dr', c_l), ('window', c_l)]
 
 
 ATTN_FAVOR, ATTN_SOFTMAX, ATTN_RELPOS = 0, 1, 2             # emo_hip.h: EMO_ATTN_* kinds

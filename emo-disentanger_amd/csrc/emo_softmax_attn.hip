@@ -642,11 +642,16 @@ extern "C" int emo_softmax_attn_decode(const void* q, int64_t ld_q, void* kcache
 // forward above plus, per key tile, one more product P2[c][t] = Rwin[c].(q_t + v) over the 80 distances c a wave's 16 rows can see; the
 // skew c = t - j + 63 moves P2 between lanes through a small wave-private LDS buffer.  Probabilities: softmax -> dropout -> p / (sum p + 1e-8)
 // (:361-363); the kernel tracks l = sum e and E = sum drop(e) online, out = sum drop(e) v / (E + 1e-8 l); zden = E / l + 1e-8 saved with lse.
-template <typename CT, int DH>
+// BAND (evaluation only, no dropout): the sliding window of the one-token steps, score[i][j] for max(0, i - W) <= j <= i with W = the one trailing
+// argument `window` (the causal instance takes none, so its argument block and code are what they were).  Query tile qt starts at the key tile that
+// holds key 64 qt - W; the lower edge i - W moves through 64 consecutive keys over the tile's rows, so it is masked per element on the first two
+// tiles of the sweep, as the causal edge is on the last one.  Distances past W only meet masked scores: R rows 0 .. min(T - 1, W) are all it reads.
+template <typename CT, int DH, bool BAND, typename... WIN>
 __global__ __launch_bounds__(256) void relattn_fwd_kernel(const CT* __restrict__ q, const CT* __restrict__ k, const CT* __restrict__ v, int64_t ld,
                                                           const CT* __restrict__ rd, int64_t ld_r, int64_t n_dist, const float* __restrict__ ub,
                                                           const float* __restrict__ vb_, CT* __restrict__ out, int64_t ld_out, float* __restrict__ lse_g,
-                                                          float* __restrict__ zden_g, int64_t T, int64_t H, DropCtx drop) {
+                                                          float* __restrict__ zden_g, int64_t T, int64_t H, DropCtx drop, WIN... window) {
+    static_assert(sizeof...(WIN) == (BAND ? 1 : 0), "the banded instance takes the window, the causal one nothing");
     typedef SaDims<CT, DH> D;
     constexpr int LDX = D::LDX, LDC = D::LDC, DHP = D::DHP, ND = DH / 16, NQ = DHP / Img<CT>::KSTEP, SKW = 84;
     constexpr bool TR = sizeof(CT) == 2;
@@ -700,11 +705,17 @@ __global__ __launch_bounds__(256) void relattn_fwd_kernel(const CT* __restrict__
             for (int it = tid; it < 128 * (DHP - DH); it += 256) Rw[(it / (DHP - DH)) * LDX + DH + it % (DHP - DH)] = from_f32<CT>(0.f);
         }
     };
+    int64_t W = 0, kt0 = 0;                   // band width and first key tile of the sweep (causal instance: tile 0)
+    if constexpr (BAND) {
+        W = (window, ...);
+        kt0 = q0 > W ? (q0 - W) / 64 : 0;
+    }
     {
-        const int kv0 = (int)(T < 64 ? T : 64);
-        pk.load(kb, ld, kv0, tid);
-        pv.load(vb, ld, kv0, tid);
-        fetch_r(q0 - 63);
+        const int64_t kf0 = kt0 * 64;
+        const int kv0 = (int)((T - kf0) < 64 ? (T - kf0) : 64);
+        pk.load(kb + kf0 * ld, ld, kv0, tid);
+        pv.load(vb + kf0 * ld, ld, kv0, tid);
+        fetch_r(q0 - kf0 - 63);
     }
     // fragments of (q + u) and (q + v) for this wave's 16 query rows
     typename Img<CT>::V quf[NQ], qvf[NQ];
@@ -733,7 +744,7 @@ __global__ __launch_bounds__(256) void relattn_fwd_kernel(const CT* __restrict__
     for (int i = 0; i < ND; ++i) oacc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float* skw = sk + (wave * 16 + (lane & 15)) * SKW;       // this lane's query row of the wave-private skew buffer
 
-    for (int64_t kt = 0; kt <= qt; ++kt) {
+    for (int64_t kt = kt0; kt <= qt; ++kt) {
         const int64_t k0 = kt * 64;
         __syncthreads();
         pk.store_rows(Ki, LDX, tid);
@@ -759,6 +770,7 @@ __global__ __launch_bounds__(256) void relattn_fwd_kernel(const CT* __restrict__
         float s[4][4];
         float mx = -INFINITY;
         const bool diag = kt == qt;
+        const bool low = BAND && kt <= kt0 + 1;               // the only tiles the lower band edge crosses
 #pragma unroll
         for (int jt = 0; jt < 4; ++jt) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -772,6 +784,7 @@ __global__ __launch_bounds__(256) void relattn_fwd_kernel(const CT* __restrict__
                 const float bd = skw[(lane & 15) + 63 - jl];               // c - 16w = (16w + (l&15)) - jl + 63 - 16w
                 float val = sizeof(CT) == 2 ? (acc[r] + bd) * c2 : (acc[r] + bd) / sqrt_dh;
                 if (diag && (jl > tl || k0 + jl >= T)) val = -INFINITY;
+                if constexpr (BAND) { if (low && k0 + jl < tg - W) val = -INFINITY; }
                 s[jt][r] = val;
                 mx = fmaxf(mx, val);
             }
@@ -779,13 +792,14 @@ __global__ __launch_bounds__(256) void relattn_fwd_kernel(const CT* __restrict__
         __builtin_amdgcn_wave_barrier();
         mx = rows4_max(mx);
         float m_new = fmaxf(m_run, mx);
+        const bool none = BAND && m_new == -INFINITY;         // a row with no key in the band yet keeps m = -inf, not the 0 it is shifted by
         if (m_new == -INFINITY) m_new = 0.f;
         const float alpha = sizeof(CT) == 2 ? __builtin_amdgcn_exp2f(m_run - m_new) : __expf(m_run - m_new);
         float psum = 0.f, esum = 0.f;
 #pragma unroll
         for (int jt = 0; jt < 4; ++jt) {
             float dm[4] = {1.f, 1.f, 1.f, 1.f};
-            if (drop.thr16) drop_mult4(drop, (uint64_t)((bh * T + tg) * T + k0 + jt * 16 + (lane >> 4) * 4), dm);
+            if (!BAND && drop.thr16) drop_mult4(drop, (uint64_t)((bh * T + tg) * T + k0 + jt * 16 + (lane >> 4) * 4), dm);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float p = sizeof(CT) == 2 ? __builtin_amdgcn_exp2f(s[jt][r] - m_new) : Img<CT>::ex(s[jt][r] - m_new);
@@ -797,6 +811,7 @@ __global__ __launch_bounds__(256) void relattn_fwd_kernel(const CT* __restrict__
         l_run = l_run * alpha + psum;              // per-lane partial sums: the four row groups are added once, after the sweep
         e_run = e_run * alpha + esum;
         m_run = m_new;
+        if constexpr (BAND) { if (none) m_run = -INFINITY; }
 #pragma unroll
         for (int i = 0; i < ND; ++i) oacc[i] *= alpha;
 #pragma unroll
@@ -1516,10 +1531,19 @@ template <typename CT, int DH> static size_t ra_fwd_lds() {
 }
 template <typename CT, int DH>
 static int run_relattn(const void* q, const void* k, const void* v, int64_t ld, const void* rd, int64_t ld_r, int64_t n_dist, const float* ub, const float* vb,
-                       void* out, int64_t ld_out, float* lse, float* zden, int64_t B, int64_t T, int64_t H, DropCtx drop, hipStream_t st) {
+                       void* out, int64_t ld_out, float* lse, float* zden, int64_t window, int64_t B, int64_t T, int64_t H, DropCtx drop, hipStream_t st) {
     dim3 grid((unsigned)(B * H), (unsigned)((T + 63) / 64));
     const size_t lds = ra_fwd_lds<CT, DH>();
-    auto kf = relattn_fwd_kernel<CT, DH>;
+    if (window > 0 && window + 1 < T) {                        // (a band that holds every key j <= i is the causal kernel)
+        auto kb = relattn_fwd_kernel<CT, DH, true, int64_t>;
+        static bool attr_b = false;
+        if (!attr_b) { (void)hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_b = true; }
+        hipLaunchKernelGGL(kb, grid, dim3(256), lds, st, (const CT*)q, (const CT*)k, (const CT*)v, ld, (const CT*)rd, ld_r, n_dist, ub, vb, (CT*)out, ld_out,
+                           lse, zden, T, H, drop, window);
+        EMO_LAUNCH_CHECK();
+        return EMO_OK;
+    }
+    auto kf = relattn_fwd_kernel<CT, DH, false>;
     static bool attr = false;
     if (!attr) { (void)hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
     hipLaunchKernelGGL(kf, grid, dim3(256), lds, st, (const CT*)q, (const CT*)k, (const CT*)v, ld, (const CT*)rd, ld_r, n_dist, ub, vb, (CT*)out, ld_out, lse,
@@ -1607,11 +1631,16 @@ static int attn_relpos(const emo_attn_t& a, hipStream_t st) {
     } while (0)
     EMO_CHECK(a.r_dist && a.lse, "null pointer");
     EMO_CHECK(a.ld_r % ve == 0 && ((uintptr_t)a.r_dist & 15) == 0, "r_dist must keep rows 16-B aligned");
-    EMO_CHECK(a.n_dist >= a.T, "r_dist needs a row for every distance 0 .. T-1");
+    if (a.pass == EMO_ATTN_FWD && a.window > 0) {              // a query sees distances 0 .. window only
+        EMO_CHECK(a.p_drop <= 0.f, "window > 0 is an evaluation pass: p_drop must be 0");
+        EMO_CHECK(a.n_dist >= (a.window + 1 < a.T ? a.window + 1 : a.T), "r_dist needs a row for every distance 0 .. min(T-1, window)");
+    } else {
+        EMO_CHECK(a.n_dist >= a.T, "r_dist needs a row for every distance 0 .. T-1");
+    }
     if (a.pass == EMO_ATTN_FWD) {
         EMO_CHECK(a.r_w_bias && a.r_r_bias && a.out, "null pointer");
         EMO_CHECK(((uintptr_t)a.out & 15) == 0, "out must be 16-B aligned");
-        RA_RUN(run_relattn, a.q, a.k, a.v, a.ld, a.r_dist, a.ld_r, a.n_dist, a.r_w_bias, a.r_r_bias, a.out, a.ld_out, a.lse, a.zden);
+        RA_RUN(run_relattn, a.q, a.k, a.v, a.ld, a.r_dist, a.ld_r, a.n_dist, a.r_w_bias, a.r_r_bias, a.out, a.ld_out, a.lse, a.zden, a.window);
     }
     if (a.pass == EMO_ATTN_BWD) {
         EMO_CHECK(a.r_w_bias && a.r_r_bias && a.out && a.dout && a.zden && a.dq && a.dq_rel, "null pointer");
@@ -1650,6 +1679,7 @@ static int attn_run(const emo_attn_t& a, hipStream_t st) {
     const int64_t ve = a.dtype == EMO_BF16 ? 8 : 4;
     EMO_CHECK(a.ld % ve == 0 && a.ld_out % (a.kind == EMO_ATTN_FAVOR ? 4 : ve) == 0 && a.dh % ve == 0, "ld/dh must keep rows 16-B aligned");
     EMO_CHECK((((uintptr_t)q | (uintptr_t)a.k | (uintptr_t)a.v) & 15) == 0, "q/k/v must be 16-B aligned");
+    EMO_CHECK(a.window <= 0 || (a.kind == EMO_ATTN_RELPOS && a.pass == EMO_ATTN_FWD), "window > 0 is served by [relpos, fwd] only (the backward passes are not windowed)");
     switch (a.kind) {
         case EMO_ATTN_FAVOR: return emo_attn_favor(a, (hipStream_t)st);
         case EMO_ATTN_SOFTMAX: return attn_softmax(a, (hipStream_t)st);

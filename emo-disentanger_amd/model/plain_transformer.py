@@ -408,6 +408,30 @@ class PlainTransformer(nn.Module):
             mem.lens.fill_(T)
         return x, B, T
 
+    @torch.no_grad()
+    def forward_windowed(self, dec_input, window=None):
+        """The logits the one-token steps give, in one pass: dec_input int64 [T, B] -> logits fp32 [T, B, V], the evaluation forward with every
+        layer's attention restricted to the band max(0, i - window) <= j <= i (relpos_attn_fwd(window=)), which is what position i sees in
+        generate() / decode_step() with dec_mem_len = window.  No mems in or out.  window defaults to dec_mem_len."""
+        if self.training:
+            raise NotImplementedError('forward_windowed() is an evaluation path: call .eval()')
+        window = self.dec_mem_len if window is None else int(window)
+        if window < 1:
+            raise ValueError('forward_windowed: window must be at least 1 (got %d)' % window)
+        if not dec_input.is_cuda:
+            raise EmoError('inputs must be GPU tensors (the HIP path has no CPU fallback)')
+        ps = self._ensure_store()
+        tok = dec_input.t().contiguous().long()
+        B, T = tok.shape
+        D, H = self.dec_d_model, self.dec_n_head
+        r_dist = self._r_by_distance(min(T, window + 1))
+        x = self._embed(tok)
+        rw, rr = ps.f32('decoder.r_w_bias'), ps.f32('decoder.r_r_bias')
+        for l in range(self.dec_n_layer):
+            x = self._layer(l, x, lambda qkv, l=l: ops.relpos_attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], r_dist[l], rw, rr, B, T, H,
+                                                                       window=window)[0])
+        return self._logits(x).view(B, T, self.vocab_size).permute(1, 0, 2)
+
     def forward(self, dec_input, dec_mems, dec_seg_len=None, return_avg_attn=False):
         """plain_transformer.py:62-80.  dec_input int64 [T, B]; returns (logits fp32 [T, B, V], new_mems).  mem_len = 0 (every training / validation
         YAML): new_mems is the empty list, as in the reference."""

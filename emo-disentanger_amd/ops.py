@@ -491,16 +491,18 @@ def softmax_attn_decode(q, kcache, vcache, lens, H, lens_off=0, k_new=None, v_ne
     return out
 
 
-def relpos_attn_fwd(q, k, v, r_dist, r_w_bias, r_r_bias, B, T, H, p_drop=0.0, seed=0, offset=0):
-    """Transformer-XL relative-position causal attention (stage 1).  q,k,v [B*T, H*dh] views; r_dist [>=T, H*dh] indexed by distance."""
+def relpos_attn_fwd(q, k, v, r_dist, r_w_bias, r_r_bias, B, T, H, p_drop=0.0, seed=0, offset=0, window=0):
+    """Transformer-XL relative-position causal attention (stage 1).  q,k,v [B*T, H*dh] views; r_dist [>=T, H*dh] indexed by distance.
+    window = W > 0 (evaluation, p_drop = 0): query i sees keys max(0, i - W) .. i, the window of relpos_attn_decode with mem_len = W; r_dist
+    then needs min(T, W + 1) rows (the library checks it)."""
     M, HD = q.shape
-    assert r_dist.shape[0] >= T and r_dist.dtype == q.dtype
+    assert r_dist.dtype == q.dtype and (window > 0 or r_dist.shape[0] >= T)
     assert r_w_bias.dtype == torch.float32 and r_r_bias.dtype == torch.float32 and r_w_bias.is_contiguous() and r_r_bias.is_contiguous()
     out = torch.empty(M, HD, device=q.device, dtype=q.dtype)
     lse = torch.empty(B, H, T, device=q.device, dtype=torch.float32)
     zden = torch.empty(B, H, T, device=q.device, dtype=torch.float32)
     _attn(ATTN_RELPOS, ATTN_FWD, q, k, v, B, T, H, r_dist=ptr(r_dist), ld_r=_rows(r_dist), n_dist=r_dist.shape[0], r_w_bias=ptr(r_w_bias),
-          r_r_bias=ptr(r_r_bias), out=ptr(out), ld_out=HD, lse=ptr(lse), zden=ptr(zden), p_drop=p_drop, seed=seed, offset=offset)
+          r_r_bias=ptr(r_r_bias), out=ptr(out), ld_out=HD, lse=ptr(lse), zden=ptr(zden), p_drop=p_drop, seed=seed, offset=offset, window=int(window))
     return out, lse, zden
 
 

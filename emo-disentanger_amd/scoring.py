@@ -1,5 +1,6 @@
 """Scoring of token sequences under a stage-2 checkpoint: per-token log-probability, rank and predictive entropy (one model forward and one
 emo_token_scores launch per batch), per-piece perplexity / top-k accuracy records, and the command line that writes them as scores.json.
+Stage-1 lead sheets (the Transformer-XL model) are scored by score_lead_sheet_tokens / score_lead_sheets / --stage 1, below the stage-2 part.
 
 The reference has no scoring tool; what is scored is exactly what its training loss sees — the targets `EventPieceDataset._targets`
 builds (stage2_accompaniment/dataloader.py:127-143: only the tokens inside Track_Full spans are predicted, everything else is pad)."""
@@ -182,6 +183,113 @@ def best_of(scores):
     return arg
 
 
+# ------------------------------------------------------------------------------------------------ stage 1: lead sheets
+def lead_sheet_targets(tokens, lengths, primer_len, pad):
+    """Next-token targets of lead sheets: tokens int64 [B, T] (rows padded to T with anything), lengths [B], primer_len an int or [B].
+    Position i of row b predicts tokens[b, i + 1] when primer_len - 1 <= i and i + 1 < lengths[b]; every other target is `pad` (the ignore index):
+    the positions inside the primer (their next token was given, not generated), the row's last token and everything past it, and a target that
+    is `pad` itself.  Works on whatever device `tokens` is on."""
+    tokens = torch.as_tensor(tokens).long()
+    B, T = tokens.shape
+    dev = tokens.device
+    lengths = torch.as_tensor(lengths, device=dev).long().reshape(B)
+    primer = torch.as_tensor(primer_len, device=dev).long().reshape(-1).expand(B)
+    pos = torch.arange(T, device=dev)
+    nxt = torch.cat([tokens[:, 1:], tokens.new_full((B, 1), pad)], 1)
+    keep = (pos[None, :] >= primer[:, None] - 1) & (pos[None, :] + 1 < lengths[:, None])
+    return torch.where(keep, nxt, torch.full_like(nxt, pad))
+
+
+def score_lead_sheet_tokens(model, tokens, lengths, primer_len, window=None):
+    """Per-token scores of lead sheets under a stage-1 model (PlainTransformer): one forward_windowed (eval mode, no_grad; the model's mode is
+    restored) and one emo_token_scores launch.  tokens int64 [B, T] on the GPU, rows padded with the model's PAD (n_token - 1, the ignore index);
+    targets and mask by lead_sheet_targets.  -> TokenScores [B, T]: entry (b, i) scores token i + 1 of row b.
+
+    What the scores mean: the probabilities a token-by-token pass over the sequence assigns — position i attends to positions
+    max(0, i - window) .. i, as generate() / decode_step() do with mem_len = window (default: the model's dec_mem_len) — with no rejected
+    draws: the generation loop feeds a rejected draw's predecessor again, which is not part of the piece and not scored.  The generator's first
+    call attends fully inside the primer; that is the same band whenever the primer has at most window + 1 tokens (score_lead_sheets reports a
+    longer one as primer_outside_window)."""
+    pad = model.n_token - 1
+    tokens = tokens.long()
+    tgt = lead_sheet_targets(tokens, lengths, primer_len, pad)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            engine.check_ids(tokens, model.n_token, 'lead-sheet tokens')
+            logits = model.forward_windowed(tokens.t(), window)           # [T, B, V]: the permuted view of the projection's [B * T, V] rows
+            V = logits.shape[-1]
+            out = ops.token_scores(logits.permute(1, 0, 2).reshape(-1, V), tgt.reshape(-1), pad, V=V, want=('rank', 'entropy'))
+    finally:
+        model.train(was_training)
+    shape = tgt.shape
+    return TokenScores(out['nll'].neg().view(shape), out['rank'].view(shape), out['entropy'].view(shape), tgt != pad)
+
+
+def lead_sheet_batches(token_lists, primer_lens, batch, pad, ids=None):
+    """Groups of `batch` lead sheets, each padded with `pad` to the longest of its group: dicts with 'piece_id', 'tokens' [b, T] int64,
+    'length', 'primer_len' (lists)."""
+    assert len(primer_lens) == len(token_lists)
+    for i in range(0, len(token_lists), batch):
+        group = token_lists[i:i + batch]
+        T = max(1, max(len(t) for t in group))
+        tok = np.full((len(group), T), pad, np.int64)
+        for r, t in enumerate(group):
+            tok[r, :len(t)] = t
+        yield {'piece_id': list(ids[i:i + batch]) if ids is not None else list(range(i, i + len(group))), 'tokens': torch.from_numpy(tok),
+               'length': [len(t) for t in group], 'primer_len': [int(p) for p in primer_lens[i:i + batch]]}
+
+
+def score_lead_sheets(model, token_lists, primer_lens, batch=16, window=None, ids=None, scorer=score_lead_sheet_tokens, per_token=None):
+    """One record per lead sheet (the keys of piece_record, and 'primer_outside_window': the primer has more than window + 1 tokens, so the
+    generator's first call saw more inside it than the band does — see score_lead_sheet_tokens), in the order given.  token_lists: id lists, primer
+    included; primer_lens: how many leading tokens of each were given.  One scorer call and one host transfer per group of `batch`."""
+    dev = next(model.parameters()).device
+    pad = model.n_token - 1
+    window = int(model.dec_mem_len if window is None else window)
+    records = []
+    for b in lead_sheet_batches(token_lists, primer_lens, batch, pad, ids):
+        sc = scorer(model, b['tokens'].to(dev), b['length'], b['primer_len'], window=window)
+        m = sc.mask
+        sums = torch.stack([m.sum(1).double(), -(sc.logprob.double() * m).sum(1), ((sc.rank == 0) & m).sum(1).double(),
+                            ((sc.rank >= 0) & (sc.rank < 5) & m).sum(1).double(), (sc.entropy.double() * m).sum(1)], 1).cpu().numpy()
+        if per_token is not None:
+            lp, rk, en = sc.logprob.cpu().numpy(), sc.rank.cpu().numpy(), sc.entropy.cpu().numpy()
+        for r, pid in enumerate(b['piece_id']):
+            if per_token is not None:
+                per_token(pid, lp[r], rk[r], en[r])
+            rec = piece_record(pid, b['length'][r], *sums[r])
+            rec['primer_outside_window'] = b['primer_len'][r] > window + 1
+            records.append(rec)
+    return records
+
+
+def lead_sheet_candidate_scores(model, candidates, primer_lens, batch=16, window=None, scorer=score_lead_sheet_tokens):
+    """nll_mean over the generated tokens of every candidate lead sheet (None or an Exception in the list keeps its place and scores NaN)."""
+    real = [i for i, c in enumerate(candidates) if c is not None and not isinstance(c, Exception)]
+    out = [float('nan')] * len(candidates)
+    if real:
+        for r in score_lead_sheets(model, [candidates[i] for i in real], [primer_lens[i] for i in real], batch, window, ids=real, scorer=scorer):
+            out[r['id']] = r['nll_mean']
+    return out
+
+
+def read_lead_sheet_file(path, event2idx):
+    """A samp_XX_<emotion>[_roman].txt file as stage1_inference.main writes it: one event per line, WITHOUT the Emotion_<emotion> tag that was
+    its one-token primer — the tag comes back from the file name.  (A file that does start with an Emotion_* line is taken as it is.)
+    -> (ids, primer_len = 1)."""
+    events = [e for e in open(path).read().splitlines() if e]
+    if not events or not events[0].startswith('Emotion_'):
+        stem = os.path.basename(path).split('.')[0]
+        stem = stem[:-len('_roman')] if stem.endswith('_roman') else stem
+        tag = 'Emotion_' + stem.split('_')[-1]
+        if tag not in event2idx:
+            raise ValueError('%s: no Emotion_* line and no emotion in the file name (samp_XX_<emotion>[_roman].txt)' % path)
+        events = [tag] + events
+    return [event2idx[e] for e in events], 1
+
+
 # ------------------------------------------------------------------------------------------------ command line
 def read_token_file(path, event2idx):
     """A token file as inference.main writes it and read_lead_sheet reads it: one event per line, optionally a Key_* line first (not a token
@@ -194,9 +302,12 @@ def read_token_file(path, event2idx):
 
 def _parser():
     import argparse
-    ap = argparse.ArgumentParser(description='score token sequences under a stage-2 checkpoint on MI355X')
+    ap = argparse.ArgumentParser(description='score token sequences under a stage-2 (or, --stage 1, a stage-1) checkpoint on MI355X')
+    ap.add_argument('--stage', type=int, choices=[1, 2], default=2,
+                    help='1: lead sheets under the stage-1 Transformer-XL model (-c a stage-1 YAML, --files the samp_*.txt of stage1_inference; no -m, no --split)')
+    ap.add_argument('--window', type=int, default=None, help="--stage 1: the attention window (default: the configuration's mem_len)")
     req = ap.add_argument_group('required arguments')
-    req.add_argument('-m', '--model_type', choices=['performer', 'gpt2'], required=True)
+    req.add_argument('-m', '--model_type', choices=['performer', 'gpt2'], help='required with --stage 2')
     req.add_argument('-c', '--configuration', required=True)
     req.add_argument('-r', '--representation', choices=['remi', 'functional'], required=True)
     req.add_argument('--params', required=True, help='checkpoint (.pt state dict)')
@@ -218,14 +329,68 @@ def _load_model(args, conf, n_token):
     return model.eval()
 
 
-def main(argv=None, scorer=score_tokens, load_model=_load_model):
-    """-m / -c / -r as inference.main; --params checkpoint; --split {train,val} (through EventPieceDataset, start bar 0) or --files token
-    files; writes scores.json ({'pieces': [...], 'corpus': {...}}) and with --per-token DIR three .npy rows per piece."""
+def _load_stage1_model(args, conf, n_token):
+    from .model.plain_transformer import PlainTransformer
+    mc, dc = conf['model'], conf['model']['decoder']
+    model = PlainTransformer(mc['d_word_embed'], n_token, dc['n_layer'], dc['n_head'], dc['d_model'], dc['d_ff'], dc['tgt_len'], dc['tgt_len'],
+                             dec_dropout=dc['dropout'], pre_lnorm=mc['pre_lnorm'], compute_dtype=args.dtype).cuda()
+    model.load_state_dict(torch.load(args.params, map_location='cpu'))
+    return model.eval()
+
+
+def _per_token_dump(directory):
+    if not directory:
+        return None
+    os.makedirs(directory, exist_ok=True)
+
+    def dump(pid, lp, rk, en):
+        for name, a in (('logprob', lp), ('rank', rk), ('entropy', en)):
+            np.save(os.path.join(directory, '%s.%s.npy' % (pid, name)), a)
+    return dump
+
+
+def _main_stage1(args, scorer, load_model):
+    """--stage 1: the vocabulary and model of stage1_inference.main (the generator's memory = the configuration's tgt_len, which is the default
+    window), the files it writes."""
     import yaml
-    from .data import EventPieceDataset, load_split, load_vocab
+    from .stage1_inference import read_vocab
+    if args.split or not args.files:
+        raise SystemExit('--stage 1 scores --files (the samp_*.txt of stage1_inference), not a dataset split')
+    conf = yaml.load(open(args.configuration), Loader=yaml.FullLoader)
+    event2idx, _, n_token = read_vocab(conf['data']['vocab_path'].format(args.representation))
+    window = conf['model']['decoder']['tgt_len'] if args.window is None else args.window
+    if window < 1:
+        raise SystemExit('--window must be at least 1')
+    model = load_model(args, conf, n_token)
+    ids = [os.path.splitext(os.path.basename(f))[0] for f in args.files]
+    read = [read_lead_sheet_file(f, event2idx) for f in args.files]
+    kw = {} if scorer is None else {'scorer': scorer}
+    records = score_lead_sheets(model, [r[0] for r in read], [r[1] for r in read], batch=args.batch, window=window, ids=ids,
+                                per_token=_per_token_dump(args.per_token), **kw)
+    result = {'pieces': records, 'corpus': corpus_summary(records),
+              'model': {'type': 'stage1_txl', 'params': args.params, 'dtype': args.dtype, 'window': window}}
+    return result
+
+
+def main(argv=None, scorer=None, load_model=None):
+    """-m / -c / -r as inference.main; --params checkpoint; --split {train,val} (through EventPieceDataset, start bar 0) or --files token
+    files; writes scores.json ({'pieces': [...], 'corpus': {...}}) and with --per-token DIR three .npy rows per piece.
+    --stage 1: -c a stage-1 YAML, -r, --params a stage-1 checkpoint, --files the samp_*.txt files of stage1_inference.main (score_lead_sheets;
+    every record also carries primer_outside_window).  scorer / load_model: stand-ins for score_tokens (stage 1: score_lead_sheet_tokens) and
+    the model loader."""
+    import yaml
     args = _parser().parse_args(argv)
     if args.batch < 1:
         raise SystemExit('--batch must be at least 1')
+    if args.stage == 1:
+        result = _main_stage1(args, scorer, load_model or _load_stage1_model)
+        return _write(args, result)
+    if args.model_type is None:
+        raise SystemExit('-m/--model_type is required with --stage 2')
+    if args.window is not None:
+        raise SystemExit('--window goes with --stage 1')
+    from .data import EventPieceDataset, load_split, load_vocab
+    scorer, load_model = scorer or score_tokens, load_model or _load_model
     conf = yaml.load(open(args.configuration), Loader=yaml.FullLoader)
     dl = conf['data_loader']
     vocab_path = dl['vocab_path'].format(args.representation)
@@ -241,15 +406,12 @@ def main(argv=None, scorer=score_tokens, load_model=_load_model):
                                pieces=load_split(dl[args.split + '_split']), pad_to_same=True, appoint_st_bar=0, predict_key=False)
         ds.piece_admissible_stbars = [[0] for _ in ds.pieces]            # score every piece from its first bar (a long one: its first max_len tokens)
         batches = DataLoader(ds, batch_size=args.batch, shuffle=False)
-    dump = None
-    if args.per_token:
-        os.makedirs(args.per_token, exist_ok=True)
-
-        def dump(pid, lp, rk, en):
-            for name, a in (('logprob', lp), ('rank', rk), ('entropy', en)):
-                np.save(os.path.join(args.per_token, '%s.%s.npy' % (pid, name)), a)
-    result = score_pieces(model, batches, pad, scorer=scorer, per_token=dump)
+    result = score_pieces(model, batches, pad, scorer=scorer, per_token=_per_token_dump(args.per_token))
     result['model'] = {'type': args.model_type, 'params': args.params, 'dtype': args.dtype,'max_len': max_len}
+    return _write(args, result)
+
+
+def _write(args, result):
     with open(args.output, 'w') as fh:
         json.dump(result, fh, indent=1)
     c = result['corpus']

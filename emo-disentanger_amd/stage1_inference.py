@@ -455,13 +455,29 @@ class LeadSheetLoop:
 
 
 def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
-                         representation='functional', key_determine=None, seed=0, use_graph=True, step='chain'):
+                         representation='functional', key_determine=None, seed=0, use_graph=True, step='chain', best_of=1):
     """The throughput path of generate_plain_xl_batch: the same arguments and result shape, every draw and the grammar on the device
     (emo_grammar_step), each token step = grammar launch + decode_step, k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS,
     default 16) and replayed until every stream has finished.  Draws come from a uniform table seeded with `seed` (like generate_streams),
     so the ids are not NumPy-RNG-identical to the reference; they equal the host grammar driven by the same device draws.
     step='one_launch' runs the model step as one persistent launch (emo_decode_step, form 2) and raises EmoError where it was not built for the model.
-    -> (results, seconds)."""
+    -> (results, seconds).
+
+    best_of = N > 1: every primer runs as N streams of the same batch (stream i * N + c is candidate c of primer i; each stream has its own
+    column of the uniform table, so the draws differ; per-primer lists among the arguments are repeated alike), every finished candidate is
+    scored (scoring.score_lead_sheets: mean negative log-probability of its generated tokens in one windowed forward, window = the model's
+    dec_mem_len) and the candidate with the lowest one is returned; ties go to the lowest candidate index, a candidate that failed (stuck, key
+    error, out of memory) never wins.  -> (results, seconds, picks), picks[i] = {'chosen': c, 'nll_mean': [N floats, NaN for a failed
+    candidate], 'candidates': [N results]}.  best_of = 1 is the path above, draw for draw."""
+    best_of = int(best_of)
+    if best_of < 1:
+        raise ValueError('best_of must be at least 1')
+    n_primers = len(primers)
+    if best_of > 1:
+        rep = lambda v: [x for x in v for _ in range(best_of)] if isinstance(v, (list, tuple)) and len(v) == n_primers else v
+        max_bars, max_events, prompt_bars, representation, key_determine = (rep(v) for v in (max_bars, max_events, prompt_bars, representation,
+                                                                                               key_determine))
+        primers = [p for p in primers for _ in range(best_of)]
     was_training = model.training
     model.eval()
     t0 = time.time()
@@ -470,9 +486,24 @@ def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max
                              prompt_bars=prompt_bars, representation=representation, key_determine=key_determine, seed=seed, step=step)
         loop.run(use_graph=use_graph)
         out = loop.results()
+        if best_of > 1:
+            picks = pick_best(model, out, loop.params.cpu().numpy()[:, P_PRIMER_LEN].tolist(), best_of)
+            return [p['candidates'][p['chosen']] for p in picks], time.time() - t0, picks
     finally:
         model.train(was_training)
     return out, time.time() - t0
+
+
+def pick_best(model, candidates, primer_lens, best_of, scorer=None):
+    """The picks of generate_lead_sheets(best_of=N): candidates i * N .. i * N + N - 1 belong to primer i.  scorer: a stand-in for
+    scoring.lead_sheet_candidate_scores (model, candidates, primer_lens) -> nll_mean per candidate."""
+    from . import scoring
+    nll = (scorer or scoring.lead_sheet_candidate_scores)(model, candidates, primer_lens)
+    picks = []
+    for i in range(len(candidates) // best_of):
+        sl = slice(i * best_of, (i + 1) * best_of)
+        picks.append({'chosen': scoring.best_of(nll[sl]), 'nll_mean': nll[sl], 'candidates': candidates[sl]})
+    return picks
 
 
 # ------------------------------------------------------------------------------------------------ command line (reference stage1_compose/inference.py:86-298)
@@ -511,7 +542,12 @@ def parse_args(argv=None):
     ap.add_argument('--seed', type=int, default=0, help='seed of the device uniform table (the group of streams j uses seed + j)')
     ap.add_argument('--step', default='chain', choices=['chain', 'one-launch'],
                     help='the model step of the device loop: the chain of launches of decode_step, or one persistent launch (emo_decode_step, form 2)')
-    return ap.parse_args(argv)
+    ap.add_argument('--best-of', dest='best_of', type=int, default=1,
+                    help='generate N candidates per piece in the same batch (N engine streams each) and keep the likeliest (device loop only)')
+    args = ap.parse_args(argv)
+    if args.best_of < 1 or (args.best_of > 1 and args.exact):
+        ap.error('--best-of must be at least 1 and goes with the device loop (not --exact)')
+    return args
 
 
 def main(argv=None):
@@ -549,11 +585,17 @@ def main(argv=None):
     kw = dict(max_bars=max_bars, max_events=mode['max_events'], temp=mode['temp'], top_p=mode['top_p'], representation=args.representation,
               key_determine=key_determine)
     times = []
-    for j, i in enumerate(range(0, len(jobs), args.streams)):
-        group = jobs[i:i + args.streams]
+    per_group = max(1, args.streams // args.best_of)               # --streams counts engine streams: N of them per piece with --best-of N
+    for j, i in enumerate(range(0, len(jobs), per_group)):
+        group = jobs[i:i + per_group]
         primers = [['Emotion_{}'.format(e)] for _, e in group]
         if args.exact:
             res, sec = generate_plain_xl_batch(model, event2idx, idx2event, primers, seeds=list(range(i, i + len(group))), **kw)
+        elif args.best_of > 1:
+            res, sec, picks = generate_lead_sheets(model, event2idx, idx2event, primers, seed=args.seed + j, step=args.step.replace('-', '_'),
+                                                   best_of=args.best_of, **kw)
+            for (out, _), p in zip(group, picks):
+                print('[info] %s: candidate %d of %d (nll_mean %s)' % (out, p['chosen'], args.best_of, ' '.join('%.4f' % x for x in p['nll_mean'])))
         else:
             res, sec = generate_lead_sheets(model, event2idx, idx2event, primers, seed=args.seed + j, step=args.step.replace('-', '_'), **kw)
         times.append(sec)

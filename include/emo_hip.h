@@ -220,6 +220,10 @@ int emo_dropout_apply(const void* x, void* out, int dtype, int64_t n, float p_dr
  *   prob = softmax -> dropout -> p / (sum_j p + 1e-8);  out = prob v
  * r_dist [n_dist >= T, H*dh] (ld_r) = r_net(pos_emb) indexed BY DISTANCE (row d = the reference's r_head_k[klen-1-d]).  r_w_bias / r_r_bias
  * [H, dh] fp32.  lse [B,H,T], zden [B,H,T] (may be NULL in FWD: the renormalisation denominator E/l + 1e-8) are saved for the backward passes.
+ *   window (FWD only): 0 = every key j <= i.  W > 0 = the sliding window of the one-token steps (emo_relpos_attn_decode with mem_len = W, form 2
+ *   of emo_decode_step): score[i][j] for max(0, i - W) <= j <= i only, same score, softmax, zden and lse over those keys — what T decode steps
+ *   over a K/V cache compute, in one pass and O(T W) work (key tiles outside the band are never loaded).  r_dist then needs rows
+ *   0 .. min(T - 1, W) only.  An evaluation feature: refused with p_drop > 0, and on every other kind or pass (the backward passes are not windowed).
  *   BWD, the query-tile pass: recomputes the probabilities per query tile and returns dq = dq_content + dq_relative (dq_content = ds.K/sqrt(dh),
  *   dq_relative[i] = sum_j ds_ij R[i-j]/sqrt(dh), both accumulated in-kernel) plus dq_rel = the relative part alone ([B*T, H*dh], pitch ld_rel,
  *   dtype of q): d r_r_bias = colsum(dq_rel), d r_w_bias = colsum(dq) - colsum(dq_rel).  delta (may be NULL) [B,H,T] fp32: dO.O per query row,
@@ -268,7 +272,7 @@ typedef struct {
     int64_t keep_bytes;
     /* --- RELPOS */
     const void* r_dist;        /* 16-B aligned */
-    int64_t ld_r, n_dist;      /* ld_r: a multiple of 16 B; n_dist >= T */
+    int64_t ld_r, n_dist;      /* ld_r: a multiple of 16 B; n_dist >= T (FWD with window = W > 0: >= min(T, W + 1)) */
     const float *r_w_bias, *r_r_bias;   /* FWD, BWD */
     float* zden;               /* FWD: written (or NULL); every backward pass: read */
     void* dq_rel;              /* BWD.  16-B aligned */
@@ -278,6 +282,7 @@ typedef struct {
     int64_t ld_q;              /* row stride of qu, qv */
     float* dR;                 /* BWD_R */
     int64_t ld_dr;             /* BWD_R: >= H * dh */
+    int64_t window;            /* RELPOS FWD: 0 or the band width W (keys i - W .. i); must be 0 everywhere else */
 } emo_attn_t;
 /* sizeof(emo_attn_t) as the library was built (a binding checks its mirror against it, as with emo_epilogue_size) */
 int emo_attn_size(void);
