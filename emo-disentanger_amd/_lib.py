@@ -54,7 +54,8 @@ GRAMMAR_TXL, GRAMMAR_ACC, GRAMMAR_ACC_WINDOW = 0, 1, 2      # emo_hip.h: EMO_GRA
 
 
 class Attn(ctypes.Structure):
-    """emo_attn_t (emo_hip.h), field for field: the argument block of the training-side attention kernels.  Pointer fields hold raw device addresses."""
+    """emo_attn_t (emo_hip.h), field for field: the argument block of the attention kernels (training passes and the one-token DECODE pass).
+    Pointer fields hold raw device addresses."""
     _fields_ = [('kind', ctypes.c_int32), ('pass_', ctypes.c_int32),
                 ('q', c_p), ('k', c_p), ('v', c_p), ('ld', c_l), ('out', c_p), ('dout', c_p), ('ld_out', c_l), ('dq', c_p), ('dk', c_p), ('dv', c_p), ('ld_d', c_l),
                 ('dtype', ctypes.c_int32), ('B', c_l), ('T', c_l), ('H', c_l), ('dh', c_l), ('p_drop', c_f), ('seed', c_u64), ('offset', c_u64),
@@ -62,11 +63,12 @@ class Attn(ctypes.Structure):
                 ('omega', c_p), ('den', c_p), ('state_S', c_p), ('state_z', c_p), ('n_feat', c_l), ('eps', c_f), ('kstate_valid', ctypes.c_int32), ('dout_is_dn', ctypes.c_int32),
                 ('lse', c_p), ('delta_ws', c_p), ('keep', c_p), ('keep_bytes', c_l),
                 ('r_dist', c_p), ('ld_r', c_l), ('n_dist', c_l), ('r_w_bias', c_p), ('r_r_bias', c_p), ('zden', c_p), ('dq_rel', c_p), ('ld_rel', c_l), ('delta', c_p),
-                ('qu', c_p), ('qv', c_p), ('ld_q', c_l), ('dR', c_p), ('ld_dr', c_l), ('window', c_l)]
+                ('qu', c_p), ('qv', c_p), ('ld_q', c_l), ('dR', c_p), ('ld_dr', c_l), ('window', c_l),
+                ('kcache', c_p), ('vcache', c_p), ('T_max', c_l), ('lens', c_p), ('lens_off', c_l), ('head_major', ctypes.c_int32)]
 
 
 ATTN_FAVOR, ATTN_SOFTMAX, ATTN_RELPOS = 0, 1, 2             # emo_hip.h: EMO_ATTN_* kinds
-ATTN_FWD, ATTN_BWD, ATTN_BWD_KV, ATTN_BWD_R = 0, 1, 2, 3    # ... and passes (`pass` is a Python keyword: the mirror's field is pass_)
+ATTN_FWD, ATTN_BWD, ATTN_BWD_KV, ATTN_BWD_R, ATTN_DECODE = 0, 1, 2, 3, 4    # ... and passes (`pass` is a Python keyword: the mirror's field is pass_)
 
 _SIG = {
     'emo_version': (c_i, []),
@@ -90,7 +92,6 @@ _SIG = {
     'emo_attn': (c_i, [ctypes.POINTER(Attn), c_p]),
     'emo_favor_attn_workspace_bytes': (c_l, [c_l, c_l, c_l, c_l, c_l]),
     'emo_favor_attn_bwd_dn_supported': (c_i, [c_i, c_l, c_l, c_l, c_l, c_l]),
-    'emo_favor_decode_step': (c_i, [c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_l, c_i, c_l, c_l, c_l, c_l, c_f, c_p]),
     'emo_decode_step_size': (c_i, []),
     'emo_decode_step_workspace_bytes': (c_l, []),
     'emo_decode_step_supported': (c_i, []),
@@ -98,8 +99,6 @@ _SIG = {
     'emo_favor_draw_omega': (c_i, [c_p, c_p, c_l, c_l, c_l, c_p]),
     'emo_softmax_attn_keep_bytes': (c_l, [c_i, c_l, c_l, c_l, c_l, c_f]),
     'emo_relpos_attn_bwd_r_workspace_bytes': (c_l, [c_l, c_l, c_l, c_l]),
-    'emo_relpos_attn_decode': (c_i, [c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_l, c_p, c_p, c_l, c_p, c_l, c_l, c_p, c_p, c_p, c_l, c_i, c_l, c_l, c_l, c_p]),
-    'emo_softmax_attn_decode': (c_i, [c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_i, c_l, c_l, c_l, c_i, c_p]),
     'emo_xent_fwd': (c_i, [c_p, c_p, c_l, c_l, c_l, c_p, c_p, c_p]),
     'emo_xent_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_l, c_l, c_l, c_p]),
     'emo_token_scores': (c_i, [c_p, c_l, c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_p, c_p]),

@@ -16,7 +16,7 @@ void emo_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* emo_last_error(void) { return g_err; }
-extern "C" int emo_version(void) { return 103; }
+extern "C" int emo_version(void) { return 104; }
 extern "C" int emo_build_flags(void) {
 #ifdef EMO_EXPERIMENTAL
     return 1;

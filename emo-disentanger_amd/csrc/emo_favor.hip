@@ -1413,9 +1413,43 @@ extern "C" int emo_favor_attn_bwd_dn_supported(int dtype, int64_t B, int64_t T, 
     return P <= 1 ? 1 : 0;
 }
 
+// The DECODE pass of the FAVOR kind: one recurrent step per stream
+static int favor_decode(const emo_attn_t& a, hipStream_t st) {
+    EMO_CHECK(a.q && a.k && a.v && a.omega && a.state_S && a.state_z && a.out, "null pointer");
+    EMO_CHECK(a.dh <= 64 && a.dh >= 16 && 256 % a.dh == 0 && a.n_feat <= 128, "needs 16<=d_head<=64 dividing 256, n_feat<=128");
+    dim3 grid((unsigned)(a.B * a.H));
+#define DECODE_LAUNCH(CTv, DHv, MFv)                                                                                                            \
+    hipLaunchKernelGGL((favor_decode_fast_kernel<CTv, DHv, MFv>), grid, dim3(256), 0, st, (const CTv*)a.q, (const CTv*)a.k, (const CTv*)a.v, a.ld, a.omega, \
+                       a.state_S, a.state_z, (CTv*)a.out, a.ld_out, a.H, a.eps)
+#define DECODE_CASE(DHv, MFv)                                                                                                                   \
+    if (a.dh == DHv && a.n_feat == 2 * MFv) {                                                                                                   \
+        if (a.dtype == EMO_F32) DECODE_LAUNCH(float, DHv, MFv); else DECODE_LAUNCH(bf16_t, DHv, MFv);                                           \
+        EMO_LAUNCH_CHECK();                                                                                                                     \
+        return EMO_OK;                                                                                                                          \
+    }
+    if (getenv("EMO_FAVOR_DECODE_GENERIC") == nullptr && (((uintptr_t)a.state_S) & 15) == 0) {
+        DECODE_CASE(64, 64)
+        DECODE_CASE(32, 64)
+        DECODE_CASE(32, 32)
+        DECODE_CASE(16, 16)
+        DECODE_CASE(16, 32)
+    }
+#undef DECODE_CASE
+#undef DECODE_LAUNCH
+    if (a.dtype == EMO_F32)
+        hipLaunchKernelGGL(favor_decode_kernel<float>, grid, dim3(256), 0, st, (const float*)a.q, (const float*)a.k, (const float*)a.v, a.ld, a.omega, a.state_S,
+                           a.state_z, (float*)a.out, a.ld_out, a.H, (int)a.dh, (int)(a.n_feat / 2), a.eps);
+    else
+        hipLaunchKernelGGL(favor_decode_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)a.q, (const bf16_t*)a.k, (const bf16_t*)a.v, a.ld, a.omega, a.state_S,
+                           a.state_z, (bf16_t*)a.out, a.ld_out, a.H, (int)a.dh, (int)(a.n_feat / 2), a.eps);
+    EMO_LAUNCH_CHECK();
+    return EMO_OK;
+}
+
 // The FAVOR kind of emo_attn (emo_softmax_attn.hip: the entry, the checks every kind shares and the prefix of the messages)
 int emo_attn_favor(const emo_attn_t& a, hipStream_t st) {
     EMO_CHECK(a.n_feat % 2 == 0, "n_feat must be even");
+    if (a.pass == EMO_ATTN_DECODE) return favor_decode(a, st);
     if (a.pass == EMO_ATTN_FWD) {
         EMO_CHECK(a.omega && a.out && a.den, "null pointer");
         EMO_CHECK(((uintptr_t)a.out & 15) == 0, "out must be 16-B aligned");
@@ -1432,38 +1466,4 @@ int emo_attn_favor(const emo_attn_t& a, hipStream_t st) {
     void* const ws = dn ? nullptr : a.workspace;
     return dispatch_favor(1, a.dtype, a.dh, a.n_feat / 2, a.q, a.k, a.v, a.ld, a.omega, a.out, a.ld_out, dn ? nullptr : a.den, nullptr, nullptr, a.dout, a.dq, a.dk,
                           a.dv, a.ld_d, a.B, a.T, a.H, a.eps, ws, dn ? 0 : a.workspace_bytes, st, a.kstate_valid != 0 && ws != nullptr, dn);
-}
-
-extern "C" int emo_favor_decode_step(const void* q, const void* k, const void* v, int64_t ld, const float* omega, float* state_S, float* state_z, void* out,
-                                     int64_t ld_out, int dtype, int64_t n_streams, int64_t H, int64_t dh, int64_t n_feat, float eps, emo_stream_t stream) {
-    EMO_CHECK(q && k && v && omega && state_S && state_z && out, "emo_favor_decode_step: null pointer");
-    EMO_CHECK(dh <= 64 && dh >= 16 && 256 % dh == 0 && n_feat <= 128 && n_feat % 2 == 0, "emo_favor_decode_step: needs 16<=d_head<=64 dividing 256, n_feat<=128");
-    dim3 grid((unsigned)(n_streams * H));
-    hipStream_t st = (hipStream_t)stream;
-#define DECODE_LAUNCH(CTv, DHv, MFv)                                                                                                            \
-    hipLaunchKernelGGL((favor_decode_fast_kernel<CTv, DHv, MFv>), grid, dim3(256), 0, st, (const CTv*)q, (const CTv*)k, (const CTv*)v, ld, omega,             \
-                       state_S, state_z, (CTv*)out, ld_out, H, eps)
-#define DECODE_CASE(DHv, MFv)                                                                                                                   \
-    if (dh == DHv && n_feat == 2 * MFv) {                                                                                                       \
-        if (dtype == EMO_F32) DECODE_LAUNCH(float, DHv, MFv); else DECODE_LAUNCH(bf16_t, DHv, MFv);                                             \
-        EMO_LAUNCH_CHECK();                                                                                                                     \
-        return EMO_OK;                                                                                                                          \
-    }
-    if (getenv("EMO_FAVOR_DECODE_GENERIC") == nullptr && (((uintptr_t)state_S) & 15) == 0) {
-        DECODE_CASE(64, 64)
-        DECODE_CASE(32, 64)
-        DECODE_CASE(32, 32)
-        DECODE_CASE(16, 16)
-        DECODE_CASE(16, 32)
-    }
-#undef DECODE_CASE
-#undef DECODE_LAUNCH
-    if (dtype == EMO_F32)
-        hipLaunchKernelGGL(favor_decode_kernel<float>, grid, dim3(256), 0, st, (const float*)q, (const float*)k, (const float*)v, ld, omega, state_S, state_z,
-                           (float*)out, ld_out, H, (int)dh, (int)(n_feat / 2), eps);
-    else
-        hipLaunchKernelGGL(favor_decode_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ld, omega, state_S,
-                           state_z, (bf16_t*)out, ld_out, H, (int)dh, (int)(n_feat / 2), eps);
-    EMO_LAUNCH_CHECK();
-    return EMO_OK;
 }

@@ -573,8 +573,45 @@ extern "C" int64_t emo_softmax_attn_keep_bytes(int dtype, int64_t B, int64_t T, 
     return dtype == EMO_BF16 ? emo_sattn32_keep_bytes(B, T, H, dh, p_drop) : 0;
 }
 
+// The DECODE pass of the SOFTMAX kind: one query row per stream against the KV caches
+static int softmax_decode(const emo_attn_t& a, hipStream_t st) {
+    EMO_CHECK(a.q && a.kcache && a.vcache && a.lens && a.out, "null pointer");
+    EMO_CHECK(a.dh == 16 || a.dh == 32 || a.dh == 64 || a.dh == 128, "d_head must be 16, 32, 64 or 128");
+    EMO_CHECK(!a.k == !a.v, "k and v (the new token's rows) go together");
+    const int64_t ve = a.dtype == EMO_BF16 ? 8 : 4;
+    EMO_CHECK((((uintptr_t)a.kcache | (uintptr_t)a.vcache) & 15) == 0 && (a.H * a.dh) % ve == 0, "caches must be 16-B aligned");
+    EMO_CHECK(a.T_max * 4 <= 128 * 1024, "T_max too large for the LDS score buffer");
+    dim3 grid((unsigned)(a.B * a.H));
+    const size_t lds = (size_t)a.T_max * sizeof(float);
+    // one workgroup per (stream, head) = at most one per CU at 32 streams x 8 heads: 16 waves instead of 4 give the CU's memory pipe four
+    // times the requests in flight (r05; EMO_SATTN_DECODE_NT=256 keeps the 4-wave instance).  GPT-2 generation, 32 streams x 2048: 25 us per
+    // layer with 8 rows per thread in flight, 20 us with 16 waves (the CU's own ~10 B/clk HBM rate gives 12 us for its 270 KB at the mean
+    // context); a single-sweep online-softmax variant (K and V rows in flight together, no score buffer) measured the same 20 us and was dropped.
+    // (r06: a single-sweep form — lens, q, the new rows and the first 1024 key AND value rows requested speculatively in the first round trip,
+    // thread-local online softmax, one merge at the end — measured 0.675 against 0.558 ms per token step of the 32 x 2048 generation: it moves
+    // 1.5 x the bytes (every step fetches 1024 rows per (stream, head) whatever its context) and the kernel is bound by the CU's fetch rate, not
+    // by its chain of round trips; removed, tools/ab_gen_gpt2.sh kept.  Requesting the next iteration's rows before the current ones are used
+    // (software-pipelined sweeps) measured 0.585 against 0.566: more requests in flight per CU do not help either)
+    int nt = 1024;
+    { const char* e = getenv("EMO_SATTN_DECODE_NT"); if (e && atoi(e) == 256) nt = 256; }
+    if (a.T_max * 4 > 96 * 1024) nt = 256;                            // (two-pass kernel: score buffer + the 1024-thread instance's partial sums must fit the LDS)
+#define SD_LAUNCH(CTv, NTv)                                                                                                                \
+    do {                                                                                                                                   \
+        static bool set = false;                                                                                                           \
+        if (!set) { (void)hipFuncSetAttribute((const void*)sattn_decode_kernel<CTv, NTv>, hipFuncAttributeMaxDynamicSharedMemorySize, (NTv == 1024 ? 96 : 128) * 1024); set = true; } \
+        hipLaunchKernelGGL((sattn_decode_kernel<CTv, NTv>), grid, dim3(NTv), lds, st, (const CTv*)a.q, a.ld, (CTv*)a.kcache, (CTv*)a.vcache, a.T_max, a.lens, \
+                           a.lens_off, (const CTv*)a.k, (const CTv*)a.v, a.ld, (CTv*)a.out, a.ld_out, a.H, (int)a.dh, (int)a.head_major);          \
+    } while (0)
+    if (a.dtype == EMO_F32) { if (nt == 1024) SD_LAUNCH(float, 1024); else SD_LAUNCH(float, 256); }
+    else { if (nt == 1024) SD_LAUNCH(bf16_t, 1024); else SD_LAUNCH(bf16_t, 256); }
+#undef SD_LAUNCH
+    EMO_LAUNCH_CHECK();
+    return EMO_OK;
+}
+
 // The SOFTMAX kind of emo_attn (the entry, with the checks every kind shares, is at the end of this file)
 static int attn_softmax(const emo_attn_t& a, hipStream_t st) {
+    if (a.pass == EMO_ATTN_DECODE) return softmax_decode(a, st);
     const bool fwd = a.pass == EMO_ATTN_FWD;
     if (fwd) {
         EMO_CHECK(a.out && a.lse && ((uintptr_t)a.out & 15) == 0, "bad out/lse");
@@ -594,44 +631,6 @@ static int attn_softmax(const emo_attn_t& a, hipStream_t st) {
                               (uint32_t*)a.keep, st);
     return dispatch_sattn(1, a.dtype, a.dh, a.q, a.k, a.v, a.ld, a.out, a.dout, a.ld_out, a.lse, a.delta_ws, a.dq, a.dk, a.dv, a.ld_d, a.B, a.T, a.H, drop,
                           (uint32_t*)a.keep, st);
-}
-
-extern "C" int emo_softmax_attn_decode(const void* q, int64_t ld_q, void* kcache, void* vcache, int64_t T_max, const int64_t* lens, int64_t lens_off,
-                                       const void* k_new, const void* v_new, int64_t ld_new, void* out, int64_t ld_out, int dtype, int64_t n_streams,
-                                       int64_t H, int64_t dh, int head_major, emo_stream_t stream) {
-    EMO_CHECK(q && kcache && vcache && lens && out, "emo_softmax_attn_decode: null pointer");
-    EMO_CHECK(dh == 16 || dh == 32 || dh == 64 || dh == 128, "emo_softmax_attn_decode: d_head must be 16, 32, 64 or 128");
-    EMO_CHECK(!k_new == !v_new, "emo_softmax_attn_decode: k_new and v_new go together");
-    const int64_t ve = dtype == EMO_BF16 ? 8 : 4;
-    EMO_CHECK((((uintptr_t)kcache | (uintptr_t)vcache) & 15) == 0 && (H * dh) % ve == 0, "emo_softmax_attn_decode: caches must be 16-B aligned");
-    EMO_CHECK(T_max * 4 <= 128 * 1024, "emo_softmax_attn_decode: T_max too large for the LDS score buffer");
-    dim3 grid((unsigned)(n_streams * H));
-    const size_t lds = (size_t)T_max * sizeof(float);
-    hipStream_t st = (hipStream_t)stream;
-    // one workgroup per (stream, head) = at most one per CU at 32 streams x 8 heads: 16 waves instead of 4 give the CU's memory pipe four
-    // times the requests in flight (r05; EMO_SATTN_DECODE_NT=256 keeps the 4-wave instance).  GPT-2 generation, 32 streams x 2048: 25 us per
-    // layer with 8 rows per thread in flight, 20 us with 16 waves (the CU's own ~10 B/clk HBM rate gives 12 us for its 270 KB at the mean
-    // context); a single-sweep online-softmax variant (K and V rows in flight together, no score buffer) measured the same 20 us and was dropped.
-    // (r06: a single-sweep form — lens, q, the new rows and the first 1024 key AND value rows requested speculatively in the first round trip,
-    // thread-local online softmax, one merge at the end — measured 0.675 against 0.558 ms per token step of the 32 x 2048 generation: it moves
-    // 1.5 x the bytes (every step fetches 1024 rows per (stream, head) whatever its context) and the kernel is bound by the CU's fetch rate, not
-    // by its chain of round trips; removed, tools/ab_gen_gpt2.sh kept.  Requesting the next iteration's rows before the current ones are used
-    // (software-pipelined sweeps) measured 0.585 against 0.566: more requests in flight per CU do not help either)
-    int nt = 1024;
-    { const char* e = getenv("EMO_SATTN_DECODE_NT"); if (e && atoi(e) == 256) nt = 256; }
-    if (T_max * 4 > 96 * 1024) nt = 256;                             // (two-pass kernel: score buffer + the 1024-thread instance's partial sums must fit the LDS)
-#define SD_LAUNCH(CTv, NTv)                                                                                                                \
-    do {                                                                                                                                   \
-        static bool a = false;                                                                                                             \
-        if (!a) { (void)hipFuncSetAttribute((const void*)sattn_decode_kernel<CTv, NTv>, hipFuncAttributeMaxDynamicSharedMemorySize, (NTv == 1024 ? 96 : 128) * 1024); a = true; } \
-        hipLaunchKernelGGL((sattn_decode_kernel<CTv, NTv>), grid, dim3(NTv), lds, st, (const CTv*)q, ld_q, (CTv*)kcache, (CTv*)vcache, T_max, lens, lens_off, \
-                           (const CTv*)k_new, (const CTv*)v_new, ld_new, (CTv*)out, ld_out, H, (int)dh, head_major);                      \
-    } while (0)
-    if (dtype == EMO_F32) { if (nt == 1024) SD_LAUNCH(float, 1024); else SD_LAUNCH(float, 256); }
-    else { if (nt == 1024) SD_LAUNCH(bf16_t, 1024); else SD_LAUNCH(bf16_t, 256); }
-#undef SD_LAUNCH
-    EMO_LAUNCH_CHECK();
-    return EMO_OK;
 }
 
 // =============================================================================================== relative-position attention (stage-1 Transformer-XL)
@@ -1616,8 +1615,11 @@ static int run_relattn_dkv(const void* qu, const void* qv, int64_t ld_q, const v
     return EMO_OK;
 }
 
-// The RELPOS kind of emo_attn: its four passes, in the order of the kernels above
+static int relpos_decode(const emo_attn_t& a, hipStream_t st);   // (at the end of this file, where its kernel instances have always been named)
+
+// The RELPOS kind of emo_attn: its four training passes, in the order of the kernels above
 static int attn_relpos(const emo_attn_t& a, hipStream_t st) {
+    if (a.pass == EMO_ATTN_DECODE) return relpos_decode(a, st);
     const bool bf = a.dtype == EMO_BF16;
     const int64_t ve = bf ? 8 : 4;
     const DropCtx drop = make_drop(a.p_drop, a.seed, a.offset);
@@ -1673,13 +1675,16 @@ extern "C" int emo_attn_size(void) { return (int)sizeof(emo_attn_t); }
 // the checks every (kind, pass) shares, then its own
 static int attn_run(const emo_attn_t& a, hipStream_t st) {
     // (the key-tile and distance-window passes of RELPOS take qu where the others take q)
-    const void* q = a.kind == EMO_ATTN_RELPOS && a.pass >= EMO_ATTN_BWD_KV ? a.qu : a.q;
-    EMO_CHECK(q && a.k && a.v, "null pointer");
+    const void* q = a.kind == EMO_ATTN_RELPOS && (a.pass == EMO_ATTN_BWD_KV || a.pass == EMO_ATTN_BWD_R) ? a.qu : a.q;
+    const bool decode = a.pass == EMO_ATTN_DECODE;             // its kernels read q, k, v element-wise and k, v may be NULL: the kind checks what it needs
+    EMO_CHECK(decode || (q && a.k && a.v), "null pointer");
     EMO_CHECK(a.dtype == EMO_F32 || a.dtype == EMO_BF16, "bad dtype");
     const int64_t ve = a.dtype == EMO_BF16 ? 8 : 4;
-    EMO_CHECK(a.ld % ve == 0 && a.ld_out % (a.kind == EMO_ATTN_FAVOR ? 4 : ve) == 0 && a.dh % ve == 0, "ld/dh must keep rows 16-B aligned");
-    EMO_CHECK((((uintptr_t)q | (uintptr_t)a.k | (uintptr_t)a.v) & 15) == 0, "q/k/v must be 16-B aligned");
-    EMO_CHECK(a.window <= 0 || (a.kind == EMO_ATTN_RELPOS && a.pass == EMO_ATTN_FWD), "window > 0 is served by [relpos, fwd] only (the backward passes are not windowed)");
+    EMO_CHECK(decode || (a.ld % ve == 0 && a.ld_out % (a.kind == EMO_ATTN_FAVOR ? 4 : ve) == 0 && a.dh % ve == 0), "ld/dh must keep rows 16-B aligned");
+    EMO_CHECK(decode || (((uintptr_t)q | (uintptr_t)a.k | (uintptr_t)a.v) & 15) == 0, "q/k/v must be 16-B aligned");
+    EMO_CHECK(!decode || a.T == 1, "T must be 1 (one query row per stream; B = the number of streams)");
+    EMO_CHECK(a.window <= 0 || (a.kind == EMO_ATTN_RELPOS && (a.pass == EMO_ATTN_FWD || decode)),
+              "window > 0 is served by [relpos, fwd] and [relpos, decode] only (the backward passes are not windowed)");
     switch (a.kind) {
         case EMO_ATTN_FAVOR: return emo_attn_favor(a, (hipStream_t)st);
         case EMO_ATTN_SOFTMAX: return attn_softmax(a, (hipStream_t)st);
@@ -1689,11 +1694,12 @@ static int attn_run(const emo_attn_t& a, hipStream_t st) {
 
 extern "C" int emo_attn(const emo_attn_t* args, emo_stream_t stream) {
     static const char* const kinds[3] = {"favor", "softmax", "relpos"};
-    static const char* const passes[4] = {"fwd", "bwd", "bwd_kv", "bwd_r"};
+    static const char* const passes[5] = {"fwd", "bwd", "bwd_kv", "bwd_r", "decode"};
     EMO_CHECK(args, "emo_attn: null argument block");
     const emo_attn_t& a = *args;
     EMO_CHECK(a.kind >= 0 && a.kind <= 2, "emo_attn: kind %d is none of EMO_ATTN_FAVOR, EMO_ATTN_SOFTMAX, EMO_ATTN_RELPOS", (int)a.kind);
-    EMO_CHECK(a.pass >= 0 && a.pass <= (a.kind == EMO_ATTN_RELPOS ? EMO_ATTN_BWD_R : EMO_ATTN_BWD), "emo_attn: kind %s has no pass %d", kinds[a.kind], (int)a.pass);
+    EMO_CHECK(a.pass >= 0 && a.pass <= EMO_ATTN_DECODE && (a.kind == EMO_ATTN_RELPOS || (a.pass != EMO_ATTN_BWD_KV && a.pass != EMO_ATTN_BWD_R)),
+              "emo_attn: kind %s has no pass %d", kinds[a.kind], (int)a.pass);
     const int rc = attn_run(a, (hipStream_t)stream);
     if (rc != EMO_OK) {                                        // every message names the (kind, pass) it comes from
         char msg[512];
@@ -1703,34 +1709,30 @@ extern "C" int emo_attn(const emo_attn_t* args, emo_stream_t stream) {
     return rc;
 }
 
-extern "C" int emo_relpos_attn_decode(const void* q, int64_t ld_q, void* kcache, void* vcache, int64_t T_max, const int64_t* lens, int64_t lens_off,
-                                      int64_t mem_len, const void* k_new, const void* v_new, int64_t ld_new, const void* r_dist, int64_t ld_r, int64_t n_dist,
-                                      const float* r_w_bias, const float* r_r_bias, void* out, int64_t ld_out, int dtype, int64_t n_streams, int64_t H,
-                                      int64_t dh, emo_stream_t stream) {
-    EMO_CHECK(q && kcache && vcache && lens && out && r_dist && r_w_bias && r_r_bias, "emo_relpos_attn_decode: null pointer");
-    EMO_CHECK(dh == 16 || dh == 32 || dh == 64 || dh == 128, "emo_relpos_attn_decode: d_head must be 16, 32, 64 or 128");
-    EMO_CHECK(T_max * 4 <= 128 * 1024, "emo_relpos_attn_decode: T_max too large for the LDS score buffer");
-    EMO_CHECK(!k_new == !v_new, "emo_relpos_attn_decode: k_new and v_new go together");
-    EMO_CHECK(n_dist >= T_max, "emo_relpos_attn_decode: r_dist needs a row for every distance 0 .. T_max-1");
-    const int64_t ve = dtype == EMO_BF16 ? 8 : 4;
-    EMO_CHECK((((uintptr_t)kcache | (uintptr_t)vcache | (uintptr_t)r_dist) & 15) == 0 && (H * dh) % ve == 0 && ld_r % ve == 0,
-              "emo_relpos_attn_decode: caches / r_dist must be 16-B aligned");
-    EMO_CHECK(T_max * 4 <= 128 * 1024, "emo_softmax_attn_decode: T_max too large for the LDS score buffer");
-    dim3 grid((unsigned)(n_streams * H));
-    const size_t lds = (size_t)T_max * sizeof(float);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == EMO_F32) {
-        static bool a = false;
-        if (!a) { (void)hipFuncSetAttribute((const void*)relattn_decode_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); a = true; }
-        hipLaunchKernelGGL(relattn_decode_kernel<float>, grid, dim3(256), lds, st, (const float*)q, ld_q, (float*)kcache, (float*)vcache, T_max, lens, lens_off,
-                           mem_len, (const float*)k_new, (const float*)v_new, ld_new, (const float*)r_dist, ld_r, r_w_bias, r_r_bias, (float*)out, ld_out, H,
-                           (int)dh);
+// The DECODE pass of the RELPOS kind: one query row per stream against the KV caches, keys len-1-window .. len-1
+static int relpos_decode(const emo_attn_t& a, hipStream_t st) {
+    EMO_CHECK(a.q && a.kcache && a.vcache && a.lens && a.out && a.r_dist && a.r_w_bias && a.r_r_bias, "null pointer");
+    EMO_CHECK(a.dh == 16 || a.dh == 32 || a.dh == 64 || a.dh == 128, "d_head must be 16, 32, 64 or 128");
+    EMO_CHECK(a.T_max * 4 <= 128 * 1024, "T_max too large for the LDS score buffer");
+    EMO_CHECK(!a.k == !a.v, "k and v (the new token's rows) go together");
+    EMO_CHECK(a.n_dist >= a.T_max, "r_dist needs a row for every distance 0 .. T_max-1");
+    const int64_t ve = a.dtype == EMO_BF16 ? 8 : 4;
+    EMO_CHECK((((uintptr_t)a.kcache | (uintptr_t)a.vcache | (uintptr_t)a.r_dist) & 15) == 0 && (a.H * a.dh) % ve == 0 && a.ld_r % ve == 0,
+              "caches / r_dist must be 16-B aligned");
+    dim3 grid((unsigned)(a.B * a.H));
+    const size_t lds = (size_t)a.T_max * sizeof(float);
+    if (a.dtype == EMO_F32) {
+        static bool set = false;
+        if (!set) { (void)hipFuncSetAttribute((const void*)relattn_decode_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); set = true; }
+        hipLaunchKernelGGL(relattn_decode_kernel<float>, grid, dim3(256), lds, st, (const float*)a.q, a.ld, (float*)a.kcache, (float*)a.vcache, a.T_max, a.lens,
+                           a.lens_off, a.window, (const float*)a.k, (const float*)a.v, a.ld, (const float*)a.r_dist, a.ld_r, a.r_w_bias, a.r_r_bias,
+                           (float*)a.out, a.ld_out, a.H, (int)a.dh);
     } else {
-        static bool a = false;
-        if (!a) { (void)hipFuncSetAttribute((const void*)relattn_decode_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); a = true; }
-        hipLaunchKernelGGL(relattn_decode_kernel<bf16_t>, grid, dim3(256), lds, st, (const bf16_t*)q, ld_q, (bf16_t*)kcache, (bf16_t*)vcache, T_max, lens,
-                           lens_off, mem_len, (const bf16_t*)k_new, (const bf16_t*)v_new, ld_new, (const bf16_t*)r_dist, ld_r, r_w_bias, r_r_bias,
-                           (bf16_t*)out, ld_out, H, (int)dh);
+        static bool set = false;
+        if (!set) { (void)hipFuncSetAttribute((const void*)relattn_decode_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); set = true; }
+        hipLaunchKernelGGL(relattn_decode_kernel<bf16_t>, grid, dim3(256), lds, st, (const bf16_t*)a.q, a.ld, (bf16_t*)a.kcache, (bf16_t*)a.vcache, a.T_max, a.lens,
+                           a.lens_off, a.window, (const bf16_t*)a.k, (const bf16_t*)a.v, a.ld, (const bf16_t*)a.r_dist, a.ld_r, a.r_w_bias, a.r_r_bias,
+                           (bf16_t*)a.out, a.ld_out, a.H, (int)a.dh);
     }
     EMO_LAUNCH_CHECK();
     return EMO_OK;

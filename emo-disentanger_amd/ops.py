@@ -10,7 +10,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, ATTN_BWD, ATTN_BWD_KV, ATTN_BWD_R, ATTN_FAVOR, ATTN_FWD, ATTN_RELPOS, ATTN_SOFTMAX, BF16, F32, MUL_BITMASK, MUL_DGELU, MUL_DGELU_NEW, MUL_NONE, MUL_NONZERO, GRAMMAR_ACC, GRAMMAR_ACC_WINDOW, GRAMMAR_TXL, Attn, DecodeStep, Epilogue, GrammarStep, check,
+from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, ATTN_BWD, ATTN_BWD_KV, ATTN_BWD_R, ATTN_DECODE, ATTN_FAVOR, ATTN_FWD, ATTN_RELPOS, ATTN_SOFTMAX, BF16, F32, MUL_BITMASK, MUL_DGELU, MUL_DGELU_NEW, MUL_NONE, MUL_NONZERO, GRAMMAR_ACC, GRAMMAR_ACC_WINDOW, GRAMMAR_TXL, Attn, DecodeStep, Epilogue, GrammarStep, check,
                    dtype_code, lib, ptr, stream)
 
 __all__ = ['gemm', 'colsum', 'embed_fwd', 'embed_bwd', 'layernorm_fwd', 'layernorm_bwd', 'dropout_apply', 'favor_attn_fwd',
@@ -266,10 +266,13 @@ def dropout_apply(x, p_drop, seed, offset):
 
 def _attn(kind, pass_, q, k, v, B, T, H, **fields):
     """One emo_attn call (emo_hip.h) from a fresh emo_attn_t: the kind, the pass, the q / k / v views ([B*T, H*dh], one row stride; the RELPOS
-    BWD_KV / BWD_R passes take their biased query copies as `qu`, `qv` fields and read no q) and the shape; every other field by its name in the
-    struct, tensors as ptr(t).  The block lives for this call only: the library reads it at call time."""
-    ld = _rows(k)
-    assert q.shape[0] == B * T and _rows(v) == ld and (pass_ >= ATTN_BWD_KV or _rows(q) == ld)
+    BWD_KV / BWD_R passes take their biased query copies as `qu`, `qv` fields and read no q; the DECODE passes of SOFTMAX and RELPOS take
+    k = v = None when nothing is appended to the caches) and the shape; every other field by its name in the struct, tensors as ptr(t).  The block
+    lives for this call only: the library reads it at call time."""
+    assert (k is None) == (v is None)
+    ld = _rows(q if k is None else k)
+    same_ld = lambda t: _rows(t) == ld or t.shape[0] == 1        # (the stride of a single row is whatever the view left there)
+    assert q.shape[0] == B * T and (k is None or same_ld(v)) and (pass_ in (ATTN_BWD_KV, ATTN_BWD_R) or same_ld(q))
     a = Attn(kind=kind, pass_=pass_, q=ptr(q), k=ptr(k), v=ptr(v), ld=ld, dtype=dtype_code(q.dtype), B=B, T=T, H=H, dh=q.shape[1] // H, **fields)
     check(lib.emo_attn(ctypes.byref(a), stream()))
 
@@ -338,10 +341,9 @@ def favor_attn_bwd(q, k, v, omega, out, dout, den, B, T, H, dqkv=None, eps=1e-6,
 
 def favor_decode_step(q, k, v, omega, state_S, state_z, H, eps=1e-6):
     n, HD = q.shape
-    dh = HD // H
     out = torch.empty(n, HD, device=q.device, dtype=q.dtype)
-    check(lib.emo_favor_decode_step(ptr(q), ptr(k), ptr(v), _rows(q), ptr(omega), ptr(state_S), ptr(state_z), ptr(out), HD,
-                                    dtype_code(q.dtype), n, H, dh, 2 * omega.shape[1], eps, stream()))
+    _attn(ATTN_FAVOR, ATTN_DECODE, q, k, v, n, 1, H, omega=ptr(omega), state_S=ptr(state_S), state_z=ptr(state_z), out=ptr(out), ld_out=HD,
+          n_feat=2 * omega.shape[1], eps=eps)
     return out
 
 
@@ -484,10 +486,9 @@ def softmax_attn_decode(q, kcache, vcache, lens, H, lens_off=0, k_new=None, v_ne
     T_max = kcache.shape[2] if head_major else kcache.shape[1]
     assert kcache.is_contiguous() and vcache.is_contiguous() and lens.dtype == torch.int64 and kcache.shape == vcache.shape
     assert not head_major or (kcache.shape[1] == H and kcache.shape[3] == HD // H)
-    assert (k_new is None) == (v_new is None) and (k_new is None or _rows(k_new) == _rows(v_new))
     out = torch.empty(n, HD, device=q.device, dtype=q.dtype)
-    check(lib.emo_softmax_attn_decode(ptr(q), _rows(q), ptr(kcache), ptr(vcache), T_max, ptr(lens), lens_off, ptr(k_new), ptr(v_new),
-                                      0 if k_new is None else _rows(k_new), ptr(out), HD, dtype_code(q.dtype), n, H, HD // H, int(head_major), stream()))
+    _attn(ATTN_SOFTMAX, ATTN_DECODE, q, k_new, v_new, n, 1, H, kcache=ptr(kcache), vcache=ptr(vcache), T_max=T_max, lens=ptr(lens), lens_off=lens_off,
+          head_major=int(head_major), out=ptr(out), ld_out=HD)
     return out
 
 
@@ -554,9 +555,9 @@ def relpos_attn_decode(q, kcache, vcache, lens, H, r_dist, r_w_bias, r_r_bias, m
     T_max = kcache.shape[1]
     assert kcache.is_contiguous() and vcache.is_contiguous() and lens.dtype == torch.int64 and r_dist.shape[0] >= T_max
     out = torch.empty(n, HD, device=q.device, dtype=q.dtype)
-    check(lib.emo_relpos_attn_decode(ptr(q), _rows(q), ptr(kcache), ptr(vcache), T_max, ptr(lens), lens_off, mem_len, ptr(k_new), ptr(v_new),
-                                     0 if k_new is None else _rows(k_new), ptr(r_dist), _rows(r_dist), r_dist.shape[0], ptr(r_w_bias), ptr(r_r_bias),
-                                     ptr(out), HD, dtype_code(q.dtype), n, H, HD // H, stream()))
+    _attn(ATTN_RELPOS, ATTN_DECODE, q, k_new, v_new, n, 1, H, kcache=ptr(kcache), vcache=ptr(vcache), T_max=T_max, lens=ptr(lens), lens_off=lens_off,
+          window=mem_len, r_dist=ptr(r_dist), ld_r=_rows(r_dist), n_dist=r_dist.shape[0], r_w_bias=ptr(r_w_bias), r_r_bias=ptr(r_r_bias), out=ptr(out),
+          ld_out=HD)
     return out
 
 

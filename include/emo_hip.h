@@ -182,9 +182,11 @@ int emo_layernorm_bwd(const void* dy, const void* x, const float* gamma, const f
 int emo_dropout_apply(const void* x, void* out, int dtype, int64_t n, float p_drop, uint64_t seed,
                       uint64_t offset, emo_stream_t stream);
 
-/* ------------------------------------------------------------------ K3+K4, K5, K5r: the attention kernels of the training step
- * ONE entry, emo_attn, with ONE argument block, emo_attn_t: `kind` selects the attention, `pass` the forward or a backward pass of it.  q, k, v:
- * [B*T, H*dh] views with row stride ld (a fused [B*T, 3*H*dh] projection works; batch-major); out [B*T, H*dh] (ld_out).
+/* ------------------------------------------------------------------ K3+K4, K5, K5r: the attention kernels of the training step and of the chain-of-launches token step
+ * ONE entry, emo_attn, with ONE argument block, emo_attn_t: `kind` selects the attention, `pass` the forward, a backward pass or the one-token
+ * DECODE pass of it.  q, k, v: [B*T, H*dh] views with row stride ld (a fused [B*T, 3*H*dh] projection works; batch-major); out [B*T, H*dh] (ld_out).
+ * DECODE (every kind): one query row per stream, T = 1 and B = the number of streams; q, k, v are the new token's rows [B, H*dh] (read element-wise:
+ * no alignment or stride rule beyond one shared ld).
  *
  * EMO_ATTN_FAVOR — FAVOR+ causal linear attention (K3+K4).  omega [dh, n_feat/2] fp32; den [B,H,T] fp32 (saved for backward).
  * state_S [B,H,n_feat,dh] / state_z [B,H,n_feat] fp32: optional final scan state (decode prefill).
@@ -204,6 +206,8 @@ int emo_dropout_apply(const void* x, void* out, int dtype, int64_t n, float p_dr
  *   kernels then need neither den nor the rescaled operand copies (dD_t = -(dN_t . out_t)), and no workspace.  Same reference lines (the native
  *   causal_product backward reached from fast_transformer_decoder.py:33-40).  Served by the single-segment slice kernels only — bf16, d_head 64,
  *   128 features, T % 32 == 0, B * H >= 256 (emo_favor_attn_bwd_dn_supported() = 1); refused elsewhere, the caller then keeps the plain form.
+ *   DECODE: one recurrent step per stream on state_S / state_z (both required, read and written): state += phi(k) (x) v ;
+ *   out = phi(q)^T S / (phi(q).z + eps).  16 <= dh <= 64 dividing 256, n_feat <= 128.
  *
  * EMO_ATTN_SOFTMAX — causal softmax attention (K5, GPT-2).  Replaces HF GPT2Attention._attn (model/music_gpt2.py:86):
  * softmax(q k^T/sqrt(dh) + causal) [dropout] v.  lse [B,H,T] fp32 saved for backward.  Dropout index = ((b*H+h)*T + i)*T + j.
@@ -212,6 +216,11 @@ int emo_dropout_apply(const void* x, void* out, int dtype, int64_t n, float p_dr
  *   diagonal (32-bit words [B*H][T/64 key tiles][2][T rows], emo_softmax_attn_keep_bytes() bytes — 0 when the call is not served by the 32 x 32
  *   MFMA kernels: then pass keep = NULL), the dK/dV pass reads the bits instead of re-evaluating the keyed hash per score.  Results are
  *   bit-identical to the calls without the buffer (same hash, evaluated once).
+ *   DECODE (K5 decode): one query row per stream (the HF `past_key_values` path of GPT2Attention, model/music_gpt2.py:86) against a KV cache;
+ *   lens[s] + lens_off = valid keys INCLUDING the new token.  k, v (both or neither NULL): the new token's key / value rows, appended to the caches
+ *   at position len-1 by the kernel itself (the HF `past_key_values` concat of GPT2Attention).  Cache layout (r06): head_major = 0:
+ *   [B, T_max, H*dh]; head_major = 1: [B, H, T_max, dh] — the keys / values of one (stream, head) are one contiguous run, which is what the one
+ *   workgroup per (stream, head) streams (the layout HF's `past_key_values` itself uses: [batch, head, seq, head_dim]).  No dropout, no window.
  *
  * EMO_ATTN_RELPOS — relative-position causal attention (K5r, stage-1 Transformer-XL).  SURVEY §8 f-1.  Replaces
  * RelPartialLearnableMultiHeadAttn's score / softmax / value product (stage1_compose/model/optimus_txl_decoder.py:331-366) including
@@ -220,10 +229,10 @@ int emo_dropout_apply(const void* x, void* out, int dtype, int64_t n, float p_dr
  *   prob = softmax -> dropout -> p / (sum_j p + 1e-8);  out = prob v
  * r_dist [n_dist >= T, H*dh] (ld_r) = r_net(pos_emb) indexed BY DISTANCE (row d = the reference's r_head_k[klen-1-d]).  r_w_bias / r_r_bias
  * [H, dh] fp32.  lse [B,H,T], zden [B,H,T] (may be NULL in FWD: the renormalisation denominator E/l + 1e-8) are saved for the backward passes.
- *   window (FWD only): 0 = every key j <= i.  W > 0 = the sliding window of the one-token steps (emo_relpos_attn_decode with mem_len = W, form 2
- *   of emo_decode_step): score[i][j] for max(0, i - W) <= j <= i only, same score, softmax, zden and lse over those keys — what T decode steps
+ *   window (FWD): 0 = every key j <= i.  W > 0 = the sliding window of the one-token steps (the DECODE pass with the same window, mem_len = W
+ *   of emo_decode_step's form 2): score[i][j] for max(0, i - W) <= j <= i only, same score, softmax, zden and lse over those keys — what T decode steps
  *   over a K/V cache compute, in one pass and O(T W) work (key tiles outside the band are never loaded).  r_dist then needs rows
- *   0 .. min(T - 1, W) only.  An evaluation feature: refused with p_drop > 0, and on every other kind or pass (the backward passes are not windowed).
+ *   0 .. min(T - 1, W) only.  An evaluation feature: refused with p_drop > 0, and on every other kind or pass but DECODE (the backward passes are not windowed).
  *   BWD, the query-tile pass: recomputes the probabilities per query tile and returns dq = dq_content + dq_relative (dq_content = ds.K/sqrt(dh),
  *   dq_relative[i] = sum_j ds_ij R[i-j]/sqrt(dh), both accumulated in-kernel) plus dq_rel = the relative part alone ([B*T, H*dh], pitch ld_rel,
  *   dtype of q): d r_r_bias = colsum(dq_rel), d r_w_bias = colsum(dq) - colsum(dq_rel).  delta (may be NULL) [B,H,T] fp32: dO.O per query row,
@@ -234,24 +243,28 @@ int emo_dropout_apply(const void* x, void* out, int dtype, int64_t n, float p_dr
  *   dR[dist][h*dh + d] = sum_{b,i} ds[b,h,i,i-dist] (q_i + r_r_bias)[d] / sqrt(dh).  One workgroup per (b, h, tile diagonal); the partial windows
  *   go through `workspace` (emo_relpos_attn_bwd_r_workspace_bytes) and are summed in a fixed order (deterministic).  qu, qv, delta as for BWD_KV.
  *   Replaces the reference's autograd through _rel_shift (optimus_txl_decoder.py:280-293, 331-366).
+ *   DECODE (K5r decode): one query row per stream against a KV cache [B, T_max, H*dh] (the reference re-projects its cached hidden states `mems`
+ *   every step, plain_transformer.py:52-59; k / v of a position do not change, so they are cached instead).  Keys j in [max(0, len-1-window), len)
+ *   with len = lens[s] + lens_off and window = 0 for every cached key; the distance of key j is len-1-j, so r_dist needs n_dist >= T_max rows.
+ *   k, v as in the SOFTMAX DECODE pass.  Eval semantics (no dropout).
  *
  * A field that a kind/pass does not read is ignored, whatever it holds (the comment of each field names its readers).  The block is read at
  * call time and holds raw device addresses: its owner keeps the memory alive until the launches are queued. */
 enum { EMO_ATTN_FAVOR = 0, EMO_ATTN_SOFTMAX = 1, EMO_ATTN_RELPOS = 2 };
-enum { EMO_ATTN_FWD = 0, EMO_ATTN_BWD = 1, EMO_ATTN_BWD_KV = 2 /* RELPOS */, EMO_ATTN_BWD_R = 3 /* RELPOS */ };
+enum { EMO_ATTN_FWD = 0, EMO_ATTN_BWD = 1, EMO_ATTN_BWD_KV = 2 /* RELPOS */, EMO_ATTN_BWD_R = 3 /* RELPOS */, EMO_ATTN_DECODE = 4 };
 typedef struct {
     int32_t kind;              /* EMO_ATTN_FAVOR / SOFTMAX / RELPOS */
-    int32_t pass;              /* EMO_ATTN_FWD / BWD; RELPOS also BWD_KV, BWD_R */
+    int32_t pass;              /* EMO_ATTN_FWD / BWD / DECODE; RELPOS also BWD_KV, BWD_R */
     /* --- all kinds */
-    const void *q, *k, *v;     /* 16-B aligned; q: not RELPOS BWD_KV / BWD_R (they take qu, qv) */
-    int64_t ld;                /* row stride of q, k, v: a multiple of 16 B */
-    void* out;                 /* FWD: written; BWD (all kinds): read.  16-B aligned */
+    const void *q, *k, *v;     /* 16-B aligned; q: not RELPOS BWD_KV / BWD_R (they take qu, qv).  DECODE: any alignment; SOFTMAX, RELPOS: k, v both or both NULL */
+    int64_t ld;                /* row stride of q, k, v: a multiple of 16 B (DECODE: any) */
+    void* out;                 /* FWD, DECODE: written; BWD (all kinds): read.  16-B aligned (DECODE: any alignment) */
     const void* dout;          /* every backward pass: [B*T, H*dh] (ld_out), 16-B aligned */
     int64_t ld_out;            /* row stride of out and dout */
     void *dq, *dk, *dv;        /* BWD of FAVOR, SOFTMAX: all three; RELPOS BWD: dq, RELPOS BWD_KV: dk, dv.  16-B aligned */
     int64_t ld_d;              /* row stride of dq, dk, dv: a multiple of 4 */
     int32_t dtype;             /* EMO_F32 / EMO_BF16 of q, k, v, out and the gradients */
-    int64_t B, T, H, dh;
+    int64_t B, T, H, dh;       /* DECODE: B streams, T = 1 */
     float p_drop;              /* SOFTMAX, RELPOS: dropout on the probabilities, regenerated in every pass from (seed, offset) */
     uint64_t seed, offset;
     void* workspace;           /* FAVOR (not with dout_is_dn): segment states or NULL; RELPOS BWD_R: the partial windows.  16-B aligned */
@@ -259,8 +272,8 @@ typedef struct {
     /* --- FAVOR */
     const float* omega;
     float* den;                /* FWD: written; BWD: read (not with dout_is_dn) */
-    float *state_S, *state_z;  /* FWD: NULL or both */
-    int64_t n_feat;            /* even */
+    float *state_S, *state_z;  /* FWD: NULL or both, written; DECODE: both, read and written */
+    int64_t n_feat;            /* even; DECODE: <= 128 */
     float eps;                 /* the normaliser's epsilon */
     int32_t kstate_valid;      /* BWD: `workspace` still holds the forward's K-state increments */
     int32_t dout_is_dn;        /* BWD: dout is dN = dout / den */
@@ -272,8 +285,8 @@ typedef struct {
     int64_t keep_bytes;
     /* --- RELPOS */
     const void* r_dist;        /* 16-B aligned */
-    int64_t ld_r, n_dist;      /* ld_r: a multiple of 16 B; n_dist >= T (FWD with window = W > 0: >= min(T, W + 1)) */
-    const float *r_w_bias, *r_r_bias;   /* FWD, BWD */
+    int64_t ld_r, n_dist;      /* ld_r: a multiple of 16 B; n_dist >= T (FWD with window = W > 0: >= min(T, W + 1); DECODE: >= T_max) */
+    const float *r_w_bias, *r_r_bias;   /* FWD, BWD, DECODE */
     float* zden;               /* FWD: written (or NULL); every backward pass: read */
     void* dq_rel;              /* BWD.  16-B aligned */
     int64_t ld_rel;            /* BWD: a multiple of 4 */
@@ -282,22 +295,23 @@ typedef struct {
     int64_t ld_q;              /* row stride of qu, qv */
     float* dR;                 /* BWD_R */
     int64_t ld_dr;             /* BWD_R: >= H * dh */
-    int64_t window;            /* RELPOS FWD: 0 or the band width W (keys i - W .. i); must be 0 everywhere else */
+    int64_t window;            /* RELPOS FWD, DECODE: 0 or the band width W (keys i - W .. i; DECODE: len-1-W .. len-1); must be 0 everywhere else */
+    /* --- DECODE of SOFTMAX, RELPOS */
+    void *kcache, *vcache;     /* the K / V caches, read and (with k, v) appended to.  16-B aligned, H*dh a multiple of 16 B */
+    int64_t T_max;             /* rows per stream (head_major: per (stream, head)) of the caches; T_max * 4 bytes of scores must fit 128 KB of LDS */
+    const int64_t* lens;       /* int64 [B] on the device: lens[s] + lens_off = the valid keys of stream s, the new token included */
+    int64_t lens_off;
+    int32_t head_major;        /* SOFTMAX DECODE: the caches are [B, H, T_max, dh] instead of [B, T_max, H*dh] */
 } emo_attn_t;
 /* sizeof(emo_attn_t) as the library was built (a binding checks its mirror against it, as with emo_epilogue_size) */
 int emo_attn_size(void);
-/* Messages name the kind and the pass: "emo_attn[favor, fwd]: ", "emo_attn[favor, bwd, dn]: " (dout_is_dn), "emo_attn[relpos, bwd_kv]: " ... */
+/* Messages name the kind and the pass: "emo_attn[favor, fwd]: ", "emo_attn[favor, bwd, dn]: " (dout_is_dn), "emo_attn[relpos, bwd_kv]: ", "emo_attn[softmax, decode]: " ... */
 int emo_attn(const emo_attn_t* args, emo_stream_t stream);
 /* the sizes and classes named above: pure functions of the problem (and of the EMO_FAVOR_* switches) */
 int64_t emo_favor_attn_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t dh, int64_t n_feat);
 int emo_favor_attn_bwd_dn_supported(int dtype, int64_t B, int64_t T, int64_t H, int64_t dh, int64_t n_feat);
 int64_t emo_softmax_attn_keep_bytes(int dtype, int64_t B, int64_t T, int64_t H, int64_t dh, float p_drop);
 int64_t emo_relpos_attn_bwd_r_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t dh);
-/* one recurrent step per stream: state += phi(k) (x) v ; out = phi(q)^T S / (phi(q).z + eps) */
-int emo_favor_decode_step(const void* q, const void* k, const void* v, int64_t ld, const float* omega,
-                          float* state_S, float* state_z, void* out, int64_t ld_out, int dtype,
-                          int64_t n_streams, int64_t H, int64_t dh, int64_t n_feat, float eps,
-                          emo_stream_t stream);
 /* ONE-LAUNCH decode step: one token of every stream through a whole model in a single persistent kernel (csrc/emo_decode_persist.hip), for
  * n_streams <= 32 streams (a multiple of 4), bf16 weights: 8 groups x 32 workgroups of 12 waves (4 poller + 2 x 4 compute), a group owns 4 streams and
  * exchanges the activations of the 5 dependent products of a layer through tagged 8-byte granules.  Built for d_model 512 / 8 heads / d_ff 2048,
@@ -388,7 +402,7 @@ typedef struct {
 int emo_decode_step_size(void);
 int64_t emo_decode_step_workspace_bytes(void);
 /* 1 when this device can hold the launch (>= 256 CUs, 96 KB of LDS per workgroup granted, one workgroup per CU by the occupancy query), else 0:
- * callers keep the chain of launches (emo_gemm + emo_favor_decode_step ...) of stage2_accompaniment/inference.py:250-277 then */
+ * callers keep the chain of launches (emo_gemm + the DECODE pass of emo_attn ...) of stage2_accompaniment/inference.py:250-277 then */
 int emo_decode_step_supported(void);
 int emo_decode_step(const emo_decode_step_t* args, emo_stream_t stream);
 
@@ -397,30 +411,6 @@ int emo_decode_step(const emo_decode_step_t* args, emo_stream_t stream);
  * omega [n_layers, dh, n_feat/2] with orthogonal columns per block scaled by the row norms of the block. */
 int emo_favor_draw_omega(const float* gauss, float* omega, int64_t n_layers, int64_t dh, int64_t n_feat,
                          emo_stream_t stream);
-
-/* ------------------------------------------------------------------ K5 decode: causal softmax attention, one query row per stream (GPT-2)
- * (the HF `past_key_values` path of GPT2Attention, model/music_gpt2.py:86) against a KV cache; lens[s] + lens_off = valid keys INCLUDING the new
- * token.  k_new / v_new [n_streams, H*dh] (ld_new; both or neither NULL): the new token's key / value rows, appended to the caches
- * at position len-1 by the kernel itself (the HF `past_key_values` concat of GPT2Attention).
- * Cache layout (r06): head_major = 0: [n_streams, T_max, H*dh]; head_major = 1: [n_streams, H, T_max, dh] — the keys / values of one
- * (stream, head) are one contiguous run, which is what the one workgroup per (stream, head) streams (the layout HF's `past_key_values` itself
- * uses: [batch, head, seq, head_dim]). */
-int emo_softmax_attn_decode(const void* q, int64_t ld_q, void* kcache, void* vcache, int64_t T_max,
-                            const int64_t* lens, int64_t lens_off, const void* k_new, const void* v_new,
-                            int64_t ld_new, void* out, int64_t ld_out, int dtype, int64_t n_streams,
-                            int64_t H, int64_t dh, int head_major, emo_stream_t stream);
-
-/* ------------------------------------------------------------------ K5r decode: relative-position attention (stage-1 Transformer-XL, EMO_ATTN_RELPOS's score),
- * one query row per stream against a KV cache (the reference re-projects its cached hidden states `mems` every step,
- * plain_transformer.py:52-59; k / v of a position do not change, so they are cached instead).  Keys j in
- * [max(0, len-1-mem_len), len) with len = lens[s] + lens_off; the distance of key j is len-1-j.  k_new / v_new as in
- * emo_softmax_attn_decode.  Eval semantics (no dropout). */
-int emo_relpos_attn_decode(const void* q, int64_t ld_q, void* kcache, void* vcache, int64_t T_max,
-                           const int64_t* lens, int64_t lens_off, int64_t mem_len, const void* k_new,
-                           const void* v_new, int64_t ld_new, const void* r_dist, int64_t ld_r,
-                           int64_t n_dist, const float* r_w_bias, const float* r_r_bias, void* out,
-                           int64_t ld_out, int dtype, int64_t n_streams, int64_t H, int64_t dh,
-                           emo_stream_t stream);
 
 /* ------------------------------------------------------------------ K9: cross-entropy with ignore_index
  * Replaces F.cross_entropy in compute_loss (model/music_performer.py:72-81).

@@ -177,14 +177,15 @@ def test_attn_struct_mirror_has_the_library_size():
 
 
 _ATTN_KIND = {0: 'favor', 1: 'softmax', 2: 'relpos'}
-_ATTN_PASS = {0: 'fwd', 1: 'bwd', 2: 'bwd_kv', 3: 'bwd_r'}
-_ATTN_PASSES = [(0, 0), (0, 1), (1, 0), (1, 1), (2, 0), (2, 1), (2, 2), (2, 3)]          # every (kind, pass) the entry has
+_ATTN_PASS = {0: 'fwd', 1: 'bwd', 2: 'bwd_kv', 3: 'bwd_r', 4: 'decode'}
+_ATTN_PASSES = [(0, 0), (0, 1), (1, 0), (1, 1), (2, 0), (2, 1), (2, 2), (2, 3), (0, 4), (1, 4), (2, 4)]          # every (kind, pass) the entry has
 
 
 def _attn_args(kind, pass_, **kw):
     """A block that passes every host check of its (kind, pass) (pointer fields: small fake addresses, 16-byte aligned — validation never
     dereferences them; such a block would go on to the launch, so every caller breaks one field), with the fields of `kw` changed.
-    bf16, B * H = 256 single-segment FAVOR scans (the dout_is_dn class), T = 128 with dropout (the class that has keep words)."""
+    bf16, B * H = 256 single-segment FAVOR scans (the dout_is_dn class), T = 128 with dropout (the class that has keep words); the DECODE pass:
+    T = 1 against caches of T_max = 128 rows, no window."""
     from emo_disentanger_amd import _lib
     a = _lib.Attn()
     for name, ctype in _lib.Attn._fields_:
@@ -196,6 +197,8 @@ def _attn_args(kind, pass_, **kw):
     a.keep_bytes = _lib.lib.emo_softmax_attn_keep_bytes(_lib.BF16, 32, 128, 8, 64, 0.1)
     a.workspace_bytes = _lib.lib.emo_relpos_attn_bwd_r_workspace_bytes(32, 128, 8, 64)
     assert a.keep_bytes > 0 and a.workspace_bytes > 0
+    if pass_ == 4:
+        a.T, a.T_max, a.lens_off, a.window = 1, 128, 0, 0
     for k, v in kw.items():
         setattr(a, k, v)
     return a
@@ -213,6 +216,13 @@ def _attn_args(kind, pass_, **kw):
     (2, 1, dict(dq_rel=None), 'null pointer'), (2, 1, dict(ld_rel=510), 'ld_rel % 4 == 0'), (2, 1, dict(q=None), 'null pointer'),
     (2, 2, dict(qv=None), 'null pointer'), (2, 2, dict(ld_d=1538), 'ld_d % 4 == 0'), (2, 2, dict(qu=None), 'null pointer'), (2, 2, dict(ld_q=516), 'qu / qv / dout'),
     (2, 3, dict(dR=None), 'dR / workspace'), (2, 3, dict(workspace_bytes=1024), 'workspace too small'), (2, 3, dict(ld_dr=256), 'a column for every (h, d)'),
+    (0, 4, dict(state_z=None), 'null pointer'), (0, 4, dict(k=None), 'null pointer'), (0, 4, dict(dh=48), 'd_head<=64 dividing 256'),
+    (0, 4, dict(n_feat=256), 'n_feat<=128'), (0, 4, dict(T=2), 'T must be 1'), (0, 4, dict(window=8), 'window > 0 is served by [relpos, fwd] and [relpos, decode] only'),
+    (1, 4, dict(kcache=None), 'null pointer'), (1, 4, dict(v=None), 'go together'), (1, 4, dict(T_max=40000), 'T_max too large for the LDS score buffer'),
+    (1, 4, dict(kcache=0x1008), 'caches must be 16-B aligned'), (1, 4, dict(dh=48), 'd_head must be 16, 32, 64 or 128'), (1, 4, dict(T=128), 'T must be 1'),
+    (1, 4, dict(window=8), 'window > 0 is served by [relpos, fwd] and [relpos, decode] only'),
+    (2, 4, dict(r_w_bias=None), 'null pointer'), (2, 4, dict(n_dist=127), 'a row for every distance 0 .. T_max-1'), (2, 4, dict(ld_r=516), 'caches / r_dist must be 16-B aligned'),
+    (2, 4, dict(k=None), 'go together'), (2, 4, dict(T_max=40000, n_dist=40000), 'T_max too large for the LDS score buffer'), (2, 4, dict(dtype=3), 'bad dtype'),
 ])
 def test_attn_refuses_bad_arguments_without_a_gpu_and_names_its_kind_and_pass(kind, pass_, kw, what):
     from emo_disentanger_amd import _lib
@@ -239,7 +249,7 @@ def test_attn_refuses_an_empty_a_missing_and_an_unknown_block_without_a_gpu():
     assert _lib.lib.emo_attn(ctypes.byref(_attn_args(3, 0)), None) == -1
     msg = _lib.lib.emo_last_error().decode()
     assert msg.startswith('emo_attn: ') and 'kind 3' in msg
-    for kind, pass_ in ((0, 2), (1, 3), (2, 4), (0, -1)):           # BWD_KV / BWD_R are passes of RELPOS only
+    for kind, pass_ in ((0, 2), (1, 3), (2, 5), (0, 5), (0, -1)):   # BWD_KV / BWD_R are passes of RELPOS only; DECODE (4) is the last pass of every kind
         assert _lib.lib.emo_attn(ctypes.byref(_attn_args(kind, pass_)), None) == -1
         msg = _lib.lib.emo_last_error().decode()
         assert msg == 'emo_attn: kind %s has no pass %d' % (_ATTN_KIND[kind], pass_)
@@ -253,17 +263,26 @@ def test_an_attention_kind_ignores_the_fields_of_the_other_kinds_and_passes():
     relpos = dict(r_dist=None, ld_r=1, n_dist=0, r_w_bias=None, r_r_bias=None, zden=None, dq_rel=None, ld_rel=1, delta=None, qu=None, qv=None, ld_q=1, dR=None,
                   ld_dr=0)
     bwd = dict(dout=None, dq=None, dk=None, dv=None, ld_d=1)
+    cache = dict(kcache=None, vcache=None, T_max=0, lens=None, lens_off=0, head_major=0)      # the DECODE passes' own: FWD and the backward passes ignore them
+    # what no DECODE pass reads: the gradients, the statistics, dropout, the scratch buffers, the biased query copies
+    train = dict(bwd, workspace=None, workspace_bytes=0, den=None, kstate_valid=0, dout_is_dn=0, lse=None, zden=None, dq_rel=None, ld_rel=1, delta=None, qu=None,
+                 qv=None, ld_q=1, dR=None, ld_dr=0, p_drop=0.0, seed=0, offset=0, **softmax)
+    relpos_in = dict(r_dist=None, ld_r=1, n_dist=0, r_w_bias=None, r_r_bias=None)
     for kind, pass_, others, broken, what in (
-            (0, 0, dict(softmax, lse=None, **relpos, **bwd), dict(state_z=None), 'state_S without state_z'),
-            (0, 1, dict(softmax, lse=None, **relpos), dict(dout_is_dn=1, den=None, workspace=None, dv=0x1008), 'pointers must be 16-B aligned'),
-            (1, 0, dict(favor, workspace=None, **relpos, **bwd), dict(keep_bytes=16), 'keep buffer of 16 bytes'),
-            (1, 1, dict(favor, workspace=None, **relpos), dict(keep_bytes=16), 'keep buffer of 16 bytes'),
-            (2, 0, dict(favor, workspace=None, **softmax, **bwd, qu=None, qv=None, dq_rel=None, dR=None, delta=None, zden=None), dict(out=0x1008), 'out must be 16-B aligned'),
-            (2, 1, dict(favor, workspace=None, **softmax, dk=None, dv=None, qu=None, qv=None, dR=None, delta=None), dict(ld_rel=510), 'ld_rel % 4 == 0'),
-            (2, 2, dict(favor, workspace=None, **softmax, q=None, out=None, dq=None, dq_rel=None, dR=None, r_w_bias=None, r_r_bias=None), dict(ld_d=1538),
+            (0, 0, dict(softmax, lse=None, **relpos, **bwd, **cache), dict(state_z=None), 'state_S without state_z'),
+            (0, 1, dict(softmax, lse=None, **relpos, **cache), dict(dout_is_dn=1, den=None, workspace=None, dv=0x1008), 'pointers must be 16-B aligned'),
+            (1, 0, dict(favor, workspace=None, **relpos, **bwd, **cache), dict(keep_bytes=16), 'keep buffer of 16 bytes'),
+            (1, 1, dict(favor, workspace=None, **relpos, **cache), dict(keep_bytes=16), 'keep buffer of 16 bytes'),
+            (2, 0, dict(favor, workspace=None, **softmax, **bwd, **cache, qu=None, qv=None, dq_rel=None, dR=None, delta=None, zden=None), dict(out=0x1008),
+             'out must be 16-B aligned'),
+            (2, 1, dict(favor, workspace=None, **softmax, **cache, dk=None, dv=None, qu=None, qv=None, dR=None, delta=None), dict(ld_rel=510), 'ld_rel % 4 == 0'),
+            (2, 2, dict(favor, workspace=None, **softmax, **cache, q=None, out=None, dq=None, dq_rel=None, dR=None, r_w_bias=None, r_r_bias=None), dict(ld_d=1538),
              'ld_d % 4 == 0'),
-            (2, 3, dict(favor, **softmax, q=None, out=None, dq=None, dk=None, dv=None, ld_d=1, dq_rel=None, r_w_bias=None, r_r_bias=None),
-             dict(workspace_bytes=16), 'workspace too small')):
+            (2, 3, dict(favor, **softmax, **cache, q=None, out=None, dq=None, dk=None, dv=None, ld_d=1, dq_rel=None, r_w_bias=None, r_r_bias=None),
+             dict(workspace_bytes=16), 'workspace too small'),
+            (0, 4, dict(train, **relpos_in, **cache), dict(dh=48), 'needs 16<=d_head<=64 dividing 256'),
+            (1, 4, dict(train, **relpos_in, omega=None, state_S=None, state_z=None, n_feat=1, eps=0.0), dict(T_max=40000), 'T_max too large for the LDS score buffer'),
+            (2, 4, dict(train, omega=None, state_S=None, state_z=None, n_feat=1, eps=0.0, head_major=1), dict(ld_r=516), 'caches / r_dist must be 16-B aligned')):
         from emo_disentanger_amd import _lib
         a = _attn_args(kind, pass_, **dict(others, **broken))
         assert _lib.lib.emo_attn(ctypes.byref(a), None) == -1

@@ -889,7 +889,7 @@ def test_softmax_attention_fwd_bwd(dt, B, T, H, dh):
     ql = qc[:, :HD].reshape(B, T, HD)[:, -1].contiguous()
     od = ops.softmax_attn_decode(ql, kc, vc, torch.full((B,), T, dtype=torch.int64, device='cuda'), H)
     _close(od, ref.view(B, T, HD)[:, -1], dt)
-    # head-major cache [B, H, T_max, dh] (r06, emo_softmax_attn_decode's head_major) with the last key / value row appended by the kernel itself
+    # head-major cache [B, H, T_max, dh] (r06, emo_attn_t.head_major) with the last key / value row appended by the kernel itself
     T_max = T + 5
     kh = torch.zeros(B, H, T_max, dh, device='cuda', dtype=dt)
     vh = torch.zeros(B, H, T_max, dh, device='cuda', dtype=dt)
@@ -899,6 +899,60 @@ def test_softmax_attention_fwd_bwd(dt, B, T, H, dh):
                                  k_new=kc[:, -1].contiguous(), v_new=vc[:, -1].contiguous())
     assert torch.equal(oh, od)
     assert torch.equal(kh[:, :, T - 1], kc.view(B, T, H, dh)[:, -1]) and torch.equal(vh[:, :, T - 1], vc.view(B, T, H, dh)[:, -1])
+
+
+# the fields of emo_attn_t (emo_hip.h) that the DECODE pass of each kind reads; `window` counts for every kind: the entry refuses W > 0 outside RELPOS
+_DECODE_SHARED = {'kind', 'pass_', 'q', 'k', 'v', 'ld', 'out', 'ld_out', 'dtype', 'B', 'T', 'H', 'dh', 'window'}
+_DECODE_CACHE = {'kcache', 'vcache', 'T_max', 'lens', 'lens_off'}
+_DECODE_OWN = {'favor': _DECODE_SHARED | {'omega', 'state_S', 'state_z', 'n_feat', 'eps'},
+               'softmax': _DECODE_SHARED | _DECODE_CACHE | {'head_major'},
+               'relpos': _DECODE_SHARED | _DECODE_CACHE | {'r_dist', 'ld_r', 'n_dist', 'r_w_bias', 'r_r_bias'}}
+
+
+@pytest.mark.parametrize('dt', DT)
+@pytest.mark.parametrize('kind,dh,opt', [('favor', 32, None), ('softmax', 32, False), ('softmax', 32, True), ('softmax', 64, False), ('softmax', 64, True),
+                                         ('relpos', 32, 0), ('relpos', 32, 8), ('relpos', 64, 0), ('relpos', 64, 8)])
+def test_decode_pass_ignores_foreign_fields(dt, kind, dh, opt, monkeypatch):
+    """The DECODE pass of every kind of emo_attn, run twice on the same inputs: on the block ops builds, and on that block with every field the pass
+    does not read set to a non-NULL address (a NaN-filled scratch tensor) or a non-zero value.  Output and the updated caches / state must be
+    bit-identical and the scratch untouched.  opt: SOFTMAX head-major caches, RELPOS window.  3 streams x 2 heads; lens (1, 17, 45) of T_max 45 =
+    a one-key row, a partial sweep and a full cache."""
+    ops = _ops()
+    from emo_disentanger_amd import _lib
+    from oracle.weights import orthogonal_omega
+    n, H, T_max, nf = 3, 2, 45, 64
+    HD = H * dh
+    qkv = _r(n, 3 * HD, seed=11, dt=dt, scale=0.7).cuda()
+    q, k, v = qkv[:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:]
+    lens = torch.tensor([1, 17, 45], dtype=torch.int64, device='cuda')
+    scratch = torch.full((1024,), float('nan'), device='cuda')
+
+    def run():                                                   # fresh state / caches every time: the pass updates them
+        if kind == 'favor':
+            om = orthogonal_omega(dh, nf, np.random.default_rng(6)).cuda()
+            S, z = _r(n, H, nf, dh, seed=12).cuda(), (_r(n, H, nf, seed=13).abs() + 1.0).cuda()
+            return ops.favor_decode_step(q, k, v, om, S, z, H), S, z
+        shape = (n, H, T_max, dh) if kind == 'softmax' and opt else (n, T_max, HD)
+        kc, vc = _r(*shape, seed=14, dt=dt).cuda(), _r(*shape, seed=15, dt=dt).cuda()
+        if kind == 'softmax':
+            return ops.softmax_attn_decode(q, kc, vc, lens, H, k_new=k, v_new=v), kc, vc
+        R, u, vb = _r(T_max, HD, seed=16, dt=dt, scale=0.7).cuda(), _r(H, dh, seed=17, scale=0.3).cuda(), _r(H, dh, seed=18, scale=0.3).cuda()
+        return ops.relpos_attn_decode(q, kc, vc, lens, H, R, u, vb, mem_len=opt, k_new=k, v_new=v), kc, vc
+
+    def block_with_foreign_fields(**fields):
+        a = _lib.Attn(**fields)
+        for name, ctype in _lib.Attn._fields_:
+            if name not in _DECODE_OWN[kind]:
+                setattr(a, name, scratch.data_ptr() if ctype is _lib.c_p else 3)
+        return a
+
+    plain = run()
+    monkeypatch.setattr(ops, 'Attn', block_with_foreign_fields)
+    loaded = run()
+    assert all(torch.isfinite(t).all() for t in plain)
+    for a, b in zip(plain, loaded):
+        assert torch.equal(a, b)
+    assert torch.isnan(scratch).all()
 
 
 @pytest.mark.parametrize('B,T,H,p', [(2, 256, 2, 0.0), (1, 128, 1, 0.0), (1, 640, 3, 0.0), (2, 384, 2, 0.2)])
