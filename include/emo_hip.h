@@ -299,7 +299,9 @@ typedef struct {
     /* --- DECODE of SOFTMAX, RELPOS */
     void *kcache, *vcache;     /* the K / V caches, read and (with k, v) appended to.  16-B aligned, H*dh a multiple of 16 B */
     int64_t T_max;             /* rows per stream (head_major: per (stream, head)) of the caches; T_max * 4 bytes of scores must fit 128 KB of LDS */
-    const int64_t* lens;       /* int64 [B] on the device: lens[s] + lens_off = the valid keys of stream s, the new token included */
+    const int64_t* lens;       /* int64 [B] on the device: lens[s] + lens_off = the valid keys of stream s, the new token included.  DECODE requires
+                                * 1 <= lens[s] + lens_off <= T_max for every stream: both cache kernels index row len-1 unconditionally (they read it, and
+                                * with k, v write it) and the values live on the device, where the entry cannot check them */
     int64_t lens_off;
     int32_t head_major;        /* SOFTMAX DECODE: the caches are [B, H, T_max, dh] instead of [B, T_max, H*dh] */
 } emo_attn_t;

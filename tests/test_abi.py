@@ -223,6 +223,7 @@ def _attn_args(kind, pass_, **kw):
     (1, 4, dict(window=8), 'window > 0 is served by [relpos, fwd] and [relpos, decode] only'),
     (2, 4, dict(r_w_bias=None), 'null pointer'), (2, 4, dict(n_dist=127), 'a row for every distance 0 .. T_max-1'), (2, 4, dict(ld_r=516), 'caches / r_dist must be 16-B aligned'),
     (2, 4, dict(k=None), 'go together'), (2, 4, dict(T_max=40000, n_dist=40000), 'T_max too large for the LDS score buffer'), (2, 4, dict(dtype=3), 'bad dtype'),
+    (0, 4, dict(n_feat=127), 'n_feat must be even'),             # (the shared FAVOR check runs in front of the DECODE pass too)
 ])
 def test_attn_refuses_bad_arguments_without_a_gpu_and_names_its_kind_and_pass(kind, pass_, kw, what):
     from emo_disentanger_amd import _lib
