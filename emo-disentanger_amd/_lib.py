@@ -47,7 +47,8 @@ class GrammarStep(ctypes.Structure):
                 ('u_steps', c_p), ('n_u', c_l), ('ld_u', c_l), ('ev_flags', c_p), ('ev_beat', c_p), ('params', c_p), ('state', c_p),
                 ('seq', c_p), ('ld_seq', c_l), ('running', c_p),
                 ('key_temperature', c_f), ('key_top_p', c_f), ('tok_out', c_p), ('seg_out', c_p), ('max_len', c_l), ('pad', c_l),
-                ('segs', c_p), ('lead_tok', c_p), ('lead_off', c_p), ('track_full', c_l), ('window', c_l), ('rows', c_p), ('win_tok', c_p), ('win_seg', c_p)]
+                ('segs', c_p), ('lead_tok', c_p), ('lead_off', c_p), ('track_full', c_l), ('window', c_l), ('rows', c_p), ('win_tok', c_p), ('win_seg', c_p),
+                ('tok_logp', c_p), ('tok_rank', c_p), ('tok_entropy', c_p)]
 
 
 GRAMMAR_TXL, GRAMMAR_ACC, GRAMMAR_ACC_WINDOW = 0, 1, 2      # emo_hip.h: EMO_GRAMMAR_*

@@ -7,40 +7,17 @@
 //   otherwise           -> draw with u_steps[draws, r], run the grammar in the reference's order (key rule, Beat, Bar, PAD, append, end tests)
 //                          and choose the next input: the accepted word, the previous input again after a rejection, or — when nothing has
 //                          been accepted yet — the whole primer again from its first token (the reference re-submits `generated`).
+// When the caller wants them (tok_logp / tok_rank / tok_entropy), an accepted draw's figures go to the cell of the token it appended: from the
+// same logits row at temperature 1 — the key draw too, which draws at key_temperature — by the whole workgroup (emo_draw_scores.h), so thread 0
+// publishes the accepted column and word through LDS.  A rejection records nothing.
 #include "emo_grammar.h"
 
 namespace {
 
-__global__ __launch_bounds__(512) void txl_grammar_kernel(const emo_grammar_step_t a) {
-    __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
-    __shared__ int32_t sst[EMO_TXL_STATE_WORDS], spr[EMO_TXL_PARAM_WORDS];
-    const int tid = (int)threadIdx.x;
-    const int64_t r = blockIdx.x;
-    int32_t* st = a.state + r * EMO_TXL_STATE_WORDS;
-    int64_t* row = a.seq + r * a.ld_seq;
-    emo_grammar_open(st, EMO_TXL_STATE_WORDS, a.params + r * EMO_TXL_PARAM_WORDS, EMO_TXL_PARAM_WORDS, sst, spr, tid);
-    if (sst[EMO_TXL_S_STATUS] != EMO_TXL_RUNNING) return;
-    const int32_t plen = spr[EMO_TXL_P_PRIMER_LEN];
-    if (sst[EMO_TXL_S_FEED] < plen) {
-        if (tid == 0) {
-            a.tok_out[r] = row[sst[EMO_TXL_S_FEED]];
-            st[EMO_TXL_S_FEED] = sst[EMO_TXL_S_FEED] + 1;
-        }
-        return;
-    }
-    const int32_t draws = sst[EMO_TXL_S_DRAWS];
-    if (draws >= a.n_u) {                                    // the caller's uniform table is exhausted: the stream stops with an error status
-        if (tid == 0) {
-            st[EMO_TXL_S_STATUS] = EMO_TXL_OVERFLOW;
-            atomicSub(a.running, 1);
-        }
-        return;
-    }
-    int32_t len = sst[EMO_TXL_S_LEN];
-    const bool key_step = spr[EMO_TXL_P_KEYED] != 0 && len == 1;          // the event after the emotion tag is the key (:81-89)
-    const int64_t word = emo_nucleus_draw(a.logits + r * a.n_token, a.n_token, key_step ? a.key_temperature : a.temperature,
-                                          key_step ? a.key_top_p : a.top_p, a.u_steps[(int64_t)draws * a.ld_u + r], lds, tid, [] { __syncthreads(); });
-    if (tid != 0) return;
+// Thread 0's part of a drawing step: the grammar on `word`, the next input, the state.  -> the column of seq[r] the word was appended at, or -1.
+__device__ __forceinline__ int32_t txl_grammar(const emo_grammar_step_t& a, int64_t r, int64_t* row, int32_t* st,
+                                               const int32_t* sst, const int32_t* spr, int64_t word, int32_t draws, bool key_step, int32_t len) {
+    const int32_t len0 = len;
     const int32_t fl = a.ev_flags[word];
     int32_t status = EMO_TXL_RUNNING, accepted = sst[EMO_TXL_S_ACCEPTED], beat = sst[EMO_TXL_S_BEAT], bars = sst[EMO_TXL_S_BARS];
     int32_t failed = sst[EMO_TXL_S_FAILED], feed = sst[EMO_TXL_S_FEED];
@@ -96,6 +73,50 @@ __global__ __launch_bounds__(512) void txl_grammar_kernel(const emo_grammar_step
     st[EMO_TXL_S_FEED] = feed;
     st[EMO_TXL_S_DRAWS] = draws + 1;
     if (status != EMO_TXL_RUNNING) atomicSub(a.running, 1);
+    return len > len0 ? len0 : -1;
+}
+
+__global__ __launch_bounds__(512) void txl_grammar_kernel(const emo_grammar_step_t a) {
+    __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
+    __shared__ int32_t sst[EMO_TXL_STATE_WORDS], spr[EMO_TXL_PARAM_WORDS];
+    __shared__ int32_t sacc[2];
+    __shared__ float sred[EMO_DRAW_SCORES_WORDS];
+    const int tid = (int)threadIdx.x;
+    const int64_t r = blockIdx.x;
+    int32_t* st = a.state + r * EMO_TXL_STATE_WORDS;
+    int64_t* row = a.seq + r * a.ld_seq;
+    emo_grammar_open(st, EMO_TXL_STATE_WORDS, a.params + r * EMO_TXL_PARAM_WORDS, EMO_TXL_PARAM_WORDS, sst, spr, tid);
+    if (sst[EMO_TXL_S_STATUS] != EMO_TXL_RUNNING) return;
+    const int32_t plen = spr[EMO_TXL_P_PRIMER_LEN];
+    if (sst[EMO_TXL_S_FEED] < plen) {
+        if (tid == 0) {
+            a.tok_out[r] = row[sst[EMO_TXL_S_FEED]];
+            st[EMO_TXL_S_FEED] = sst[EMO_TXL_S_FEED] + 1;
+        }
+        return;
+    }
+    const int32_t draws = sst[EMO_TXL_S_DRAWS];
+    if (draws >= a.n_u) {                                    // the caller's uniform table is exhausted: the stream stops with an error status
+        if (tid == 0) {
+            st[EMO_TXL_S_STATUS] = EMO_TXL_OVERFLOW;
+            atomicSub(a.running, 1);
+        }
+        return;
+    }
+    const int32_t len = sst[EMO_TXL_S_LEN];
+    const bool key_step = spr[EMO_TXL_P_KEYED] != 0 && len == 1;          // the event after the emotion tag is the key (:81-89)
+    const int64_t word = emo_nucleus_draw(a.logits + r * a.n_token, a.n_token, key_step ? a.key_temperature : a.temperature,
+                                          key_step ? a.key_top_p : a.top_p, a.u_steps[(int64_t)draws * a.ld_u + r], lds, tid, [] { __syncthreads(); });
+    if (!emo_grammar_wants_scores(a)) {
+        if (tid == 0) txl_grammar(a, r, row, st, sst, spr, word, draws, key_step, len);
+        return;
+    }
+    if (tid == 0) {
+        sacc[0] = txl_grammar(a, r, row, st, sst, spr, word, draws, key_step, len);
+        sacc[1] = (int32_t)word;
+    }
+    __syncthreads();
+    if (sacc[0] >= 0) emo_grammar_score(a, a.logits + r * a.n_token, r, sacc[0], sacc[1], sred, tid);
 }
 
 }  // namespace

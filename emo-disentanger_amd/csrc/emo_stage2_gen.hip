@@ -12,6 +12,10 @@
 // The ACC_WINDOW kind is the same draw and grammar (acc_draw below, shared) for streams past the window (reference :252-277: the model input is
 // the last max_dec_inp_len tokens, positions restarting at 0): nothing is fed token by token; after an acceptance the stream's next model input
 // win_tok / win_seg[b, 0..W) = seq / segs[r, LEN - W .. LEN) is written, an injected bar included.
+// Both kinds, when the caller wants them (tok_logp / tok_rank / tok_entropy): the figures of the ACCEPTED draw, from the same logits row at
+// temperature 1, go to the cell of the token it appended (emo_draw_scores.h) — after the draw loop has ended, since the redraws read the sorted
+// state, and by the whole workgroup: whether and where a draw was accepted is read from the LDS state words thread 0 wrote before the loop's
+// last barrier.
 #include "emo_grammar.h"
 
 namespace {
@@ -101,6 +105,7 @@ __device__ __forceinline__ int32_t acc_draw(const emo_grammar_step_t& a, const f
 __global__ __launch_bounds__(512) void acc_grammar_kernel(const emo_grammar_step_t a) {
     __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
     __shared__ int32_t sst[EMO_ACC_STATE_WORDS], spr[EMO_ACC_PARAM_WORDS], sagain;
+    __shared__ float sred[EMO_DRAW_SCORES_WORDS];
     const int tid = (int)threadIdx.x;
     const int64_t r = blockIdx.x;
     int32_t* st = a.state + r * EMO_ACC_STATE_WORDS;
@@ -133,7 +138,12 @@ __global__ __launch_bounds__(512) void acc_grammar_kernel(const emo_grammar_step
         return;
     }
     int32_t draws = sst[EMO_ACC_S_DRAWS];
+    // (read before thread 0 can have touched the state: it writes only behind the barriers of the first draw)
+    const bool scores = emo_grammar_wants_scores(a);
+    const int32_t len0 = scores ? sst[EMO_ACC_S_LEN] : 0, acc0 = scores ? sst[EMO_ACC_S_ACCEPTED] : 0;
     const int32_t status = acc_draw(a, a.logits + r * a.n_token, a.u_steps + r, row, srow, spr, sst, &sagain, lds, tid, draws);
+    // an acceptance appended its word at the old length (an injected bar follows it) and counted itself, in front of the loop's last barrier
+    if (scores && sst[EMO_ACC_S_ACCEPTED] != acc0) emo_grammar_score(a, a.logits + r * a.n_token, r, len0, row[len0], sred, tid);
     if (tid != 0) return;
     if (status == EMO_ACC_RUNNING) {                         // the accepted word (or Track_LeadSheet before an injected bar) is the next input
         a.tok_out[r] = row[consumed];
@@ -153,6 +163,7 @@ __global__ __launch_bounds__(512) void acc_grammar_kernel(const emo_grammar_step
 __global__ __launch_bounds__(512) void acc_window_kernel(const emo_grammar_step_t a) {
     __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
     __shared__ int32_t sst[EMO_ACC_STATE_WORDS], spr[EMO_ACC_PARAM_WORDS], sagain;
+    __shared__ float sred[EMO_DRAW_SCORES_WORDS];
     const int tid = (int)threadIdx.x;
     const int64_t b = blockIdx.x;                            // row of the batch: logits, win_tok, win_seg
     const int64_t r = a.rows ? a.rows[b] : b;                // the stream: state, params, seq, segs, column of u_steps
@@ -171,7 +182,10 @@ __global__ __launch_bounds__(512) void acc_window_kernel(const emo_grammar_step_
         return;
     }
     int32_t draws = sst[EMO_ACC_S_DRAWS];
+    const bool scores = emo_grammar_wants_scores(a);         // as in acc_grammar_kernel; the tables are indexed by the stream r, the logits by b
+    const int32_t len0 = scores ? sst[EMO_ACC_S_LEN] : 0, acc0 = scores ? sst[EMO_ACC_S_ACCEPTED] : 0;
     const int32_t status = acc_draw(a, a.logits + b * a.n_token, a.u_steps + r, row, srow, spr, sst, &sagain, lds, tid, draws);
+    if (scores && sst[EMO_ACC_S_ACCEPTED] != acc0) emo_grammar_score(a, a.logits + b * a.n_token, r, len0, row[len0], sred, tid);
     if (tid == 0) {
         if (status != EMO_ACC_RUNNING) atomicSub(a.running, 1);
         sst[EMO_ACC_S_STATUS] = status;

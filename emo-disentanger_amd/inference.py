@@ -855,10 +855,14 @@ def _stream_result(status, ids, out_of_draws, overflow, still_running):
 class AccompanimentLoop:
     """Device state of generate_accompaniments: the decode engine (prefilled with the common prefix, positions on the device), the logits of
     the last step, the uniform table, the grammar tables, the packed lead sheets, per-stream parameters / state and token / segment rows, and
-    the running count; one_step() = emo_grammar_step (kind ACC) + the engine step."""
+    the running count; one_step() = emo_grammar_step (kind ACC) + the engine step.  scores=True: the grammar launch also records every accepted
+    draw's log-probability, rank and entropy in self.score_tables (ops.draw_score_tables: laid out like seq, sentinels wherever a token was
+    given, not drawn: primer, injected bars, Track_Full); a WindowedLoop takes the rows over at the hand-off and goes on recording; scores()
+    reads them.  The streams that _resume_windowed finishes on the host (window='host') keep sentinels from the hand-off on: its draws are
+    NumPy's, made from host probabilities, and are not recorded."""
 
     def __init__(self, model, event2idx, idx2event, lead_sheets, primers, max_events=10000, skip_check=False, max_bars=None, temp=1.2, top_p=0.9,
-                 seed=0, n_u=None, persistent=True, redraw=True):
+                 seed=0, n_u=None, persistent=True, redraw=True, scores=False):
         n = self.n = len(lead_sheets)
         assert n == len(primers) and n > 0
         _refuse(model, None)
@@ -898,6 +902,10 @@ class AccompanimentLoop:
                       track_full=self.track_full, pad=self.pad, logits=self.logits, u_steps=self.U, ev_flags=self.ev_flags, ev_beat=self.ev_beat,
                       lead_tok=self.lead_tok, lead_off=self.lead_off, params=self.params, state=self.state, seq=self.seq, segs=self.segs,
                       tok_out=self.tok, seg_out=self.segv, running=self.running)
+        self.score_tables = ops.draw_score_tables(self.seq) if scores else None
+        if scores:
+            ops.block_set(self._gargs, self._gheld, **self.score_tables)
+        self.windowed = None
         with torch.no_grad():
             if model.kind == 'performer':
                 eng = PerformerDecodeEngine(model, n, redraw=redraw, persistent=persistent)
@@ -992,6 +1000,32 @@ class AccompanimentLoop:
                                           'stream %d still running at position %d (positional table / cache end)' % (i, self.pos)))
         return out
 
+    def scores(self, results):
+        """-> per stream, aligned with `results` (what results() returned): {'logp', 'rank', 'entropy'} numpy arrays with one entry per id of
+        the stream's result (NaN / -1 where the id was given, and from the hand-off on where the host finished the stream), or None where the
+        result is an error.  Needs scores=True."""
+        if self.score_tables is None:
+            raise EmoError('AccompanimentLoop.scores(): the loop was built without scores=True')
+        own = {k: self.score_tables['tok_' + k].cpu().numpy() for k in ('logp', 'rank', 'entropy')}
+        past, at = own, {}
+        if self.windowed is not None and self.windowed.score_tables is not None:
+            past = {k: self.windowed.score_tables['tok_' + k].cpu().numpy() for k in ('logp', 'rank', 'entropy')}
+            at = {i: j for j, i in enumerate(self.windowed.idx)}
+        out = []
+        for i, ids in enumerate(results):
+            if isinstance(ids, Exception):
+                out.append(None)
+                continue
+            tabs, row = (past, at[i]) if i in at else (own, i)
+            sc = {}
+            for k, t in tabs.items():
+                a = np.full(len(ids), -1 if k == 'rank' else np.nan, dtype=t.dtype)
+                n = min(len(ids), t.shape[1])
+                a[:n] = t[row, :n]
+                sc[k] = a
+            out.append(sc)
+        return out
+
 
 WINDOW_TAG = 0x57494E                  # the windowed phase's uniform table is seeded with (seed, this tag): never the in-window table's seed
 
@@ -1032,6 +1066,12 @@ class WindowedLoop:
         self.seq = torch.zeros(m0, width, dtype=torch.int64, device=dev)
         self.segs = torch.zeros(m0, width, dtype=torch.int64, device=dev)
         self.seq[:, :w0], self.segs[:, :w0] = loop.seq[sel], loop.segs[sel]
+        # the first loop's recorded draws travel with the token rows; the windowed launch goes on recording behind them
+        self.score_tables = None
+        if loop.score_tables is not None:
+            self.score_tables = ops.draw_score_tables(self.seq)
+            for k, t in self.score_tables.items():
+                t[:, :w0] = loop.score_tables[k][sel]
         self.params = loop.params[sel].contiguous()
         self.state = loop.state[sel].contiguous()
         self.state[:, ACC_S_STATUS] = ACC_RUNNING
@@ -1052,6 +1092,8 @@ class WindowedLoop:
                       track_full=loop.track_full, logits=self.logits, u_steps=self.U, ev_flags=loop.ev_flags, ev_beat=loop.ev_beat,
                       lead_tok=loop.lead_tok, lead_off=loop.lead_off, params=self.params, state=self.state, seq=self.seq, segs=self.segs, win_tok=self.win_tok,
                       win_seg=self.win_seg, running=self.running)
+        if self.score_tables is not None:
+            ops.block_set(self._gargs, self._gheld, **self.score_tables)
         self._set_rows(list(range(m0)))
 
     def _set_rows(self, rows):
@@ -1119,7 +1161,7 @@ class WindowedLoop:
 
 
 def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, max_events=10000, skip_check=False, max_bars=None, temp=1.2, top_p=0.9,
-                            inadmissibles=None, seed=0, use_graph=True, best_of=1, window='host'):
+                            inadmissibles=None, seed=0, use_graph=True, best_of=1, window='host', best_by='forward', return_scores=False):
     """The throughput path of generate_conditional_batch: the same arguments (no per-stream samplers) and result per stream, every draw and
     the grammar of _Stream.offer on the device (emo_grammar_step), each token step = grammar launch + one engine step (the one-launch
     persistent step where the engine has one), k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS, default 16) and replayed until
@@ -1139,13 +1181,29 @@ def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, m
     window = 'device': the streams that reach the window are finished together on the device by a WindowedLoop (one batched full-window
     forward and one windowed emo_grammar_step per draw, no host round trip per token) instead of one at a time by _resume_windowed.  Every id up to
     a stream's handoff is the one window = 'host' gives; past it the draws come from the windowed phase's own uniform table (seeded with (seed,
-    WINDOW_TAG)), so the continuation equals the host grammar on those draws, not the NumPy draws of _resume_windowed."""
+    WINDOW_TAG)), so the continuation equals the host grammar on those draws, not the NumPy draws of _resume_windowed.
+
+    best_by = 'draws': the candidates are ranked by what the grammar launch recorded at each draw instead (scoring.draw_scores_mean: mean -logp
+    over a candidate's drawn tokens; NaN for one that failed or drew nothing) and no second forward runs.  These are the probabilities of the
+    generating steps themselves: under the engine's own random features, over the whole piece (with window = 'device' past the window too).
+    They cover the drawn tokens the result keeps.  'forward' scores the targets of scoring.targets_of: the same tokens (everything inside a
+    Track_Full span up to and including the bar's Track_LeadSheet was drawn), plus an EOS target at the end of the last span, which stands for
+    the final draw that the result cuts off, and only on the first max_dec_inp_len tokens.
+
+    return_scores = True: the result tuple gets one more element at its end, a list aligned with the results: {'logp', 'rank', 'entropy'} numpy
+    arrays with one entry per id (NaN / -1 where the id was given: primer, injected bars, Track_Full; and, with window = 'host', from a
+    stream's hand-off on, where _resume_windowed draws on the host), or None where the result is an error.  With best_of > 1 these are the
+    chosen candidates' and every pick also carries 'scores': the N candidates'.  The ids are those of the call without it."""
     if window not in ('host', 'device'):
         raise ValueError("window must be 'host' or 'device' (got %r)" % (window,))
     _refuse(model, inadmissibles)
     best_of = int(best_of)
     if best_of < 1:
         raise ValueError('best_of must be at least 1')
+    from . import scoring
+    scoring.check_best_by(best_by)
+    by_draws = best_of > 1 and best_by == 'draws'
+    want = return_scores or by_draws
     n_sheets = len(lead_sheets)
     if best_of > 1:
         lead_sheets = [ls for ls in lead_sheets for _ in range(best_of)]
@@ -1155,25 +1213,28 @@ def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, m
     t0 = time.time()
     kw = dict(max_events=max_events, skip_check=skip_check, max_bars=max_bars, temp=temp, top_p=top_p, seed=seed)
     try:
-        loop = AccompanimentLoop(model, event2idx, idx2event, lead_sheets, primers, **kw)
+        loop = AccompanimentLoop(model, event2idx, idx2event, lead_sheets, primers, scores=want, **kw)
         try:
             loop.run(use_graph=use_graph)
         except _GaveUp as e:
             print('[gen] %s -> the batch again on the chain of launches' % e)
-            loop = AccompanimentLoop(model, event2idx, idx2event, lead_sheets, primers, persistent=False, redraw=False, **kw)
+            loop = AccompanimentLoop(model, event2idx, idx2event, lead_sheets, primers, persistent=False, redraw=False, scores=want, **kw)
             loop.run(use_graph=use_graph)
         out = loop.results(event2idx, idx2event, max_events, skip_check, seed, window=window)
+        sc = loop.scores(out) if want else None
         if best_of > 1:
-            from . import scoring
-            nll = scoring.candidate_scores(model, event2idx, out, loop.bound)
+            nll = scoring.draw_scores_mean(sc) if by_draws else scoring.candidate_scores(model, event2idx, out, loop.bound)
             picks = []
             for i in range(n_sheets):
                 sl = slice(i * best_of, (i + 1) * best_of)
                 picks.append({'chosen': scoring.best_of(nll[sl]), 'nll_mean': nll[sl], 'candidates': out[sl]})
-            return [p['candidates'][p['chosen']] for p in picks], time.time() - t0, picks
+                if return_scores:
+                    picks[-1]['scores'] = sc[sl]
+            res = [p['candidates'][p['chosen']] for p in picks], time.time() - t0, picks
+            return res + ([p['scores'][p['chosen']] for p in picks],) if return_scores else res
     finally:
         model.train(was_training)
-    return out, time.time() - t0
+    return (out, time.time() - t0, sc) if return_scores else (out, time.time() - t0)
 
 
 # ------------------------------------------------------------------------------------------------ command line (reference inference.py:330-485)
@@ -1192,17 +1253,9 @@ def emotions_of(file_name):
     raise ValueError('wrong emotion label')
 
 
-def main(argv=None):
-    """Same flags as the reference's stage-2 inference.py (-m / -c / -r / -i / -o): every lead sheet found in the output directory gets its
-    accompaniment, all jobs of a run in lock-step on ONE decode engine (--streams at a time): generate_conditional_batch (NumPy sampling and
-    grammar on the host, seeds 0, 1, ... in job order), or with --device generate_accompaniments (device draws and grammar).  The generated
-    events are written as text
-    (`<piece>_<emotion>_full.txt`, one event per line); turning them into MIDI is the reference's convert2midi.py (needs miditoolkit) and
-    is run on those files when that module is importable."""
+def parse_args(argv=None):
+    """The command line of main(), with the refusals of flag combinations."""
     import argparse
-    import yaml
-    from . import train as tr
-    from .data import load_vocab
     ap = argparse.ArgumentParser(description='stage-2 accompaniment generation on MI355X')
     req = ap.add_argument_group('required arguments')
     req.add_argument('-m', '--model_type', choices=['performer', 'gpt2'], required=True)
@@ -1219,11 +1272,33 @@ def main(argv=None):
                     help='--device: candidates generated per lead sheet; the one with the lowest mean negative log-probability is written')
     ap.add_argument('--window', choices=['host', 'device'], default='host',
                     help='--device: streams past the %d-token window are finished one at a time on the host, or together on the device' % max_dec_inp_len)
+    ap.add_argument('--best-by', dest='best_by', default='forward', choices=['forward', 'draws'],
+                    help='--best-of: rank the candidates by a scoring forward over the finished pieces, or by the log-probabilities recorded at each draw')
+    ap.add_argument('--scores', default=None, metavar='FILE',
+                    help='--device: write one JSON record per piece (scoring.draw_record) and its per-token logp / rank / entropy, as recorded at each draw')
     args = ap.parse_args(argv)
     if args.best_of < 1 or (args.best_of > 1 and not args.device):
         ap.error('--best-of needs --device and a count of at least 1')
     if args.window == 'device' and not args.device:
         ap.error('--window device needs --device')
+    if args.best_by != 'forward' and args.best_of < 2:
+        ap.error('--best-by goes with --best-of N, N > 1')
+    if args.scores and not args.device:
+        ap.error('--scores needs --device')
+    return args
+
+
+def main(argv=None):
+    """Same flags as the reference's stage-2 inference.py (-m / -c / -r / -i / -o): every lead sheet found in the output directory gets its
+    accompaniment, all jobs of a run in lock-step on ONE decode engine (--streams at a time): generate_conditional_batch (NumPy sampling and
+    grammar on the host, seeds 0, 1, ... in job order), or with --device generate_accompaniments (device draws and grammar).  The generated
+    events are written as text
+    (`<piece>_<emotion>_full.txt`, one event per line); turning them into MIDI is the reference's convert2midi.py (needs miditoolkit) and
+    is run on those files when that module is importable."""
+    import yaml
+    from . import train as tr
+    from .data import load_vocab
+    args = parse_args(argv)
     conf = yaml.load(open(args.configuration), Loader=yaml.FullLoader)
     torch.cuda.set_device(conf['training']['gpuid'])
     event2idx, idx2event, pad = load_vocab(conf['data_loader']['vocab_path'].format(args.representation))
@@ -1247,19 +1322,24 @@ def main(argv=None):
             jobs.append((out, key, bars, primer))
     print('[# jobs]', len(jobs))
     per_group = max(1, args.streams // args.best_of)              # --streams counts engine streams: N of them per lead sheet with --best-of N
+    want, score_pieces = bool(args.scores), []
     for j, i in enumerate(range(0, len(jobs), per_group)):
         group = jobs[i:i + per_group]
         if args.device and args.best_of > 1:
-            gen, _, picks = generate_accompaniments(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
-                                                    temp=temp, top_p=top_p, seed=args.seed + j, best_of=args.best_of, window=args.window)
+            gen, _, picks, *sc = generate_accompaniments(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group],
+                                                         max_bars=args.max_bars, temp=temp, top_p=top_p, seed=args.seed + j, best_of=args.best_of,
+                                                         window=args.window, best_by=args.best_by, return_scores=want)
             for g, p in zip(group, picks):
                 print('[info] %s: candidate %d of %s' % (g[0], p['chosen'], ['%.4f' % x for x in p['nll_mean']]))
         elif args.device:
-            gen, _ = generate_accompaniments(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
-                                             temp=temp, top_p=top_p, seed=args.seed + j, window=args.window)
+            gen, _, *sc = generate_accompaniments(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
+                                                  temp=temp, top_p=top_p, seed=args.seed + j, window=args.window, return_scores=want)
         else:
             gen = generate_conditional_batch(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
                                              temp=temp, top_p=top_p, seeds=list(range(i, i + len(group))))
+        if want:
+            from . import scoring
+            score_pieces += scoring.draw_pieces([os.path.basename(g[0]) for g in group], gen, sc[0])
         for (out, key, _, _), ids in zip(group, gen):
             if isinstance(ids, Exception):
                 print('[info] %s not written: %s' % (out, ids))
@@ -1267,6 +1347,10 @@ def main(argv=None):
             with open(out, 'w') as fh:
                 fh.write('\n'.join([key] + [idx2event[w] for w in ids]) + '\n')
             print('[info] wrote', out, len(ids), 'events')
+    if want:
+        from . import scoring
+        scoring.write_draw_scores(args.scores, score_pieces)
+        print('[info] wrote', args.scores, len(score_pieces), 'records')
     try:
         import convert2midi  # noqa: F401  (the reference's module, if the user put it on the path together with miditoolkit)
         print('[info] convert2midi is importable: run it on the *_full.txt files to obtain MIDI')

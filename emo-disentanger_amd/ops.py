@@ -14,7 +14,7 @@ from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, ATTN_BWD, ATTN_BW
                    dtype_code, lib, ptr, stream)
 
 __all__ = ['gemm', 'colsum', 'embed_fwd', 'embed_bwd', 'layernorm_fwd', 'layernorm_bwd', 'dropout_apply', 'favor_attn_fwd',
-           'favor_attn_bwd', 'favor_decode_step', 'decode_step', 'decode_step_set', 'block_set', 'DecodeStep', 'GrammarStep', 'grammar_step', 'favor_draw_omega', 'softmax_attn_fwd', 'softmax_attn_bwd', 'softmax_attn_decode', 'relpos_attn_fwd', 'relpos_attn_bwd', 'relpos_attn_decode', 'xent_fwd',
+           'favor_attn_bwd', 'favor_decode_step', 'decode_step', 'decode_step_set', 'block_set', 'DecodeStep', 'GrammarStep', 'grammar_step', 'draw_score_tables', 'favor_draw_omega', 'softmax_attn_fwd', 'softmax_attn_bwd', 'softmax_attn_decode', 'relpos_attn_fwd', 'relpos_attn_bwd', 'relpos_attn_decode', 'xent_fwd',
            'xent_bwd', 'token_scores', 'xent_bwd_rows', 'argmax', 'sample_nucleus', 'sample_nucleus_step', 'txl_grammar_step', 'acc_grammar_step', 'acc_window_step', 'accuracy_counts', 'sumsq', 'clip_coef', 'adam_step', 'cast', 'add_bias2',
            'ACT_NONE', 'ACT_RELU', 'ACT_GELU_NEW', 'ACT_GELU', 'MUL_NONE', 'MUL_NONZERO', 'MUL_DGELU_NEW', 'MUL_DGELU', 'MUL_BITMASK', 'gemm_bitmask_ok', 'gemm_lna_ok', 'bitmask_rows', 'favor_bwd_dn_ok', 'ffn_fwd', 'ffn_fwd_ok']
 
@@ -388,6 +388,10 @@ _GRAMMAR_STEP_LAYOUT = {
     'rows': lambda a, t: _is(t, _I32) and t.numel() == a.n_rows,
     'win_tok': lambda a, t: _is(t, _I64) and t.shape == (a.n_rows, a.window),
     'win_seg': lambda a, t: _is(t, _I64) and t.shape == (a.n_rows, a.window),
+    # the optional per-token outputs: laid out like seq (hand them over after it)
+    'tok_logp': lambda a, t: _is(t, _F32) and t.shape == (a.ld_u, a.ld_seq),
+    'tok_rank': lambda a, t: _is(t, _I32) and t.shape == (a.ld_u, a.ld_seq),
+    'tok_entropy': lambda a, t: _is(t, _F32) and t.shape == (a.ld_u, a.ld_seq),
 }
 # per struct: its name in messages, the layout table, the int64 vectors, and the numbers a tensor brings with it (field -> (number, of tensor))
 _BLOCKS = {
@@ -659,40 +663,55 @@ def _grammar_once(kind, **fields):
     grammar_step(args)
 
 
-def txl_grammar_step(logits, temperature, top_p, key_temperature, key_top_p, u_steps, ev_flags, ev_beat, params, state, seq, tok_out, running):
+def draw_score_tables(seq):
+    """The three optional outputs of a grammar step for the token rows `seq` [n, W], pre-filled with the sentinels a reader tells given tokens
+    from drawn ones by: {'tok_logp': NaN fp32, 'tok_rank': -1 int32, 'tok_entropy': NaN fp32}, each [n, W] (the GrammarStep field names)."""
+    n, W = seq.shape
+    return {'tok_logp': torch.full((n, W), float('nan'), dtype=_F32, device=seq.device),
+            'tok_rank': torch.full((n, W), -1, dtype=_I32, device=seq.device),
+            'tok_entropy': torch.full((n, W), float('nan'), dtype=_F32, device=seq.device)}
+
+
+def txl_grammar_step(logits, temperature, top_p, key_temperature, key_top_p, u_steps, ev_flags, ev_beat, params, state, seq, tok_out, running,
+                     tok_logp=None, tok_rank=None, tok_entropy=None):
     """One stage-1 sample-and-grammar step of n streams (include/emo_hip.h, EMO_GRAMMAR_TXL): logits fp32 [n, V], u_steps fp32 [n_u, n],
     ev_flags / ev_beat int32 [V], params / state int32 [n, 8], seq int64 [n, W], tok_out int64 [n], running int32 [1].  state, seq, tok_out
-    and running are updated in place."""
+    and running are updated in place.  tok_logp / tok_entropy fp32, tok_rank int32 [n, W] (each optional): the figures of every accepted draw
+    at its token's cell (draw_score_tables makes and pre-fills them)."""
     n, V = logits.shape
     _grammar_once(GRAMMAR_TXL, n_rows=n, n_token=V, ld_u=n, temperature=temperature, top_p=top_p, key_temperature=key_temperature,
                   key_top_p=key_top_p, logits=logits, u_steps=u_steps, ev_flags=ev_flags, ev_beat=ev_beat, params=params, state=state, seq=seq,
-                  tok_out=tok_out, running=running)
+                  tok_out=tok_out, running=running, tok_logp=tok_logp, tok_rank=tok_rank, tok_entropy=tok_entropy)
     return tok_out
 
 
 def acc_grammar_step(logits, temperature, top_p, u_steps, ev_flags, ev_beat, lead_tok, lead_off, params, state, seq, segs, max_len, track_full, pad,
-                     tok_out, seg_out, running):
+                     tok_out, seg_out, running, tok_logp=None, tok_rank=None, tok_entropy=None):
     """One stage-2 sample-and-grammar step of n streams (include/emo_hip.h, EMO_GRAMMAR_ACC): logits fp32 [n, V], u_steps fp32 [n_u, n],
     ev_flags / ev_beat int32 [V], lead_tok int64 (flat), lead_off int32, params / state int32 [n, 8], seq / segs int64 [n, W], tok_out / seg_out
-    int64 [n], running int32 [1].  state, seq, segs, tok_out, seg_out and running are updated in place."""
+    int64 [n], running int32 [1].  state, seq, segs, tok_out, seg_out and running are updated in place.  tok_logp / tok_rank / tok_entropy:
+    as in txl_grammar_step."""
     n, V = logits.shape
     _grammar_once(GRAMMAR_ACC, n_rows=n, n_token=V, ld_u=n, temperature=temperature, top_p=top_p, max_len=max_len, track_full=track_full, pad=pad,
                   logits=logits, u_steps=u_steps, ev_flags=ev_flags, ev_beat=ev_beat, lead_tok=lead_tok, lead_off=lead_off, params=params, state=state,
-                  seq=seq, segs=segs, tok_out=tok_out, seg_out=seg_out, running=running)
+                  seq=seq, segs=segs, tok_out=tok_out, seg_out=seg_out, running=running, tok_logp=tok_logp, tok_rank=tok_rank,
+                  tok_entropy=tok_entropy)
     return tok_out
 
 
 def acc_window_step(logits, temperature, top_p, u_steps, rows, ev_flags, ev_beat, lead_tok, lead_off, params, state, seq, segs, window, track_full,
-                    win_tok, win_seg, running):
+                    win_tok, win_seg, running, tok_logp=None, tok_rank=None, tok_entropy=None):
     """One stage-2 draw-and-grammar step of m streams past the window (include/emo_hip.h, EMO_GRAMMAR_ACC_WINDOW): logits fp32 [m, V], win_tok /
     win_seg int64 [m, window]; rows int32 [m] (or None: row b is stream b) names each row's stream in u_steps fp32 [n_u, n], params / state
-    int32 [n, 8] and seq / segs int64 [n, width].  state, seq, segs, win_tok, win_seg and running are updated in place."""
+    int32 [n, 8] and seq / segs int64 [n, width].  state, seq, segs, win_tok, win_seg and running are updated in place.  tok_logp / tok_rank /
+    tok_entropy [n, width]: as in txl_grammar_step, indexed by the stream like seq."""
     m, V = logits.shape
     n = state.shape[0]
     assert rows is not None or m <= n
     _grammar_once(GRAMMAR_ACC_WINDOW, n_rows=m, n_token=V, ld_u=n, temperature=temperature, top_p=top_p, window=window, track_full=track_full,
                   logits=logits, u_steps=u_steps, rows=rows, ev_flags=ev_flags, ev_beat=ev_beat, lead_tok=lead_tok, lead_off=lead_off, params=params,
-                  state=state, seq=seq, segs=segs, win_tok=win_tok, win_seg=win_seg, running=running)
+                  state=state, seq=seq, segs=segs, win_tok=win_tok, win_seg=win_seg, running=running, tok_logp=tok_logp, tok_rank=tok_rank,
+                  tok_entropy=tok_entropy)
     return win_tok
 
 

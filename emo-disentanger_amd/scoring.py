@@ -183,6 +183,78 @@ def best_of(scores):
     return arg
 
 
+# ------------------------------------------------------------------------------------------------ scores recorded at the draw
+BEST_BY = ('forward', 'draws')
+
+
+def check_best_by(best_by):
+    if best_by not in BEST_BY:
+        raise ValueError('best_by must be one of %s (got %r)' % (', '.join(repr(b) for b in BEST_BY), best_by))
+
+
+def drawn_mask(logp, rank):
+    """Which tokens of a piece were drawn: the cells the grammar launch wrote (the others still hold the sentinels, NaN / -1)."""
+    logp, rank = np.asarray(logp, dtype=np.float64), np.asarray(rank)
+    return (rank >= 0) & ~np.isnan(logp)
+
+
+def draw_record(ids, logp, rank, entropy, pid=None):
+    """The record of piece_record for one generated piece, from what emo_grammar_step recorded at each draw (generate_*(return_scores=True):
+    arrays aligned with `ids`), taken over the DRAWN tokens only: the tokens that were given (primer, injected lead-sheet bars, Track_Full)
+    hold sentinels and are skipped.  Sums in float64."""
+    logp, entropy, rank = np.asarray(logp, dtype=np.float64), np.asarray(entropy, dtype=np.float64), np.asarray(rank)
+    if not (len(logp) == len(rank) == len(entropy) == len(ids)):
+        raise ValueError('draw_record: %d ids, %d / %d / %d scores' % (len(ids), len(logp), len(rank), len(entropy)))
+    m = drawn_mask(logp, rank)
+    return piece_record(pid, len(ids), int(m.sum()), float(-logp[m].sum()), int((rank[m] == 0).sum()), int((rank[m] < 5).sum()),
+                        float(entropy[m].sum()))
+
+
+def draw_scores_mean(scores):
+    """Mean -logp over the drawn tokens of every candidate: `scores` as generate_*(return_scores=True) gives them, one {'logp', 'rank',
+    'entropy'} per candidate or None for a failed one.  None, and a candidate without a drawn token, score NaN (scoring.best_of never picks
+    it over a scored one)."""
+    out = []
+    for sc in scores:
+        if sc is None:
+            out.append(float('nan'))
+            continue
+        m = drawn_mask(sc['logp'], sc['rank'])
+        out.append(float(-np.asarray(sc['logp'], dtype=np.float64)[m].mean()) if m.any() else float('nan'))
+    return out
+
+
+def draw_pieces(names, results, scores):
+    """One entry per generated piece for write_draw_scores: draw_record plus the per-token arrays (a failed piece: its name and the reason)."""
+    out = []
+    for name, ids, sc in zip(names, results, scores):
+        if sc is None:
+            out.append({'id': name, 'failed': 'stuck after 256 rejected samples' if ids is None else str(ids)})
+            continue
+        rec = draw_record(ids, sc['logp'], sc['rank'], sc['entropy'], pid=name)
+        m = drawn_mask(sc['logp'], sc['rank'])
+        # (JSON has no NaN: a token that was given holds null in the float rows and -1 in the ranks)
+        rec['tokens'] = {'ids': [int(t) for t in ids], 'rank': [int(x) for x in sc['rank']],
+                         'logp': [float(x) if k else None for x, k in zip(sc['logp'], m)],
+                         'entropy': [float(x) if k else None for x, k in zip(sc['entropy'], m)]}
+        out.append(rec)
+    return out
+
+
+def write_draw_scores(path, pieces):
+    """The --scores FILE of the two generation command lines: {'pieces': [draw_pieces entries], 'corpus': summary over the scored ones}."""
+    scored = [{k: v for k, v in p.items() if k != 'tokens'} for p in pieces if 'failed' not in p]
+    for p in pieces:                                                 # (a piece without a drawn token: NaN means -> null, to stay JSON)
+        for k, v in list(p.items()):
+            if isinstance(v, float) and v != v:
+                p[k] = None
+    corpus = corpus_summary(scored) if scored else None
+    if corpus is not None:
+        corpus = {k: (None if isinstance(v, float) and v != v else v) for k, v in corpus.items()}
+    with open(path, 'w') as fh:
+        json.dump({'pieces': pieces, 'corpus': corpus}, fh, indent=1, allow_nan=False)
+
+
 # ------------------------------------------------------------------------------------------------ stage 1: lead sheets
 def lead_sheet_targets(tokens, lengths, primer_len, pad):
     """Next-token targets of lead sheets: tokens int64 [B, T] (rows padded to T with anything), lengths [B], primer_len an int or [B].

@@ -345,10 +345,12 @@ class OneLaunchStep(_EngineBase):
 class LeadSheetLoop:
     """Device state of generate_lead_sheets: a TXLMemory, the logits of the last step, the uniform table, the grammar tables and
     per-stream parameters / state, the output sequences and the running count; one_step() = emo_grammar_step (kind TXL) + decode_step
-    (step='chain') or + emo_decode_step, form 2 (step='one_launch': OneLaunchStep on the head-major copy of the prefill's memory)."""
+    (step='chain') or + emo_decode_step, form 2 (step='one_launch': OneLaunchStep on the head-major copy of the prefill's memory).
+    scores=True: the grammar launch (the same one under both steps) also records every accepted draw's log-probability, rank and entropy in
+    self.score_tables (ops.draw_score_tables: laid out like seq, sentinels wherever a token was given, not drawn); scores() reads them."""
 
     def __init__(self, model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
-                 representation='functional', key_determine=None, seed=0, step='chain'):
+                 representation='functional', key_determine=None, seed=0, step='chain', scores=False):
         from .model.plain_transformer import TXLMemory
         n = self.n = len(primers)
         assert n > 0
@@ -394,6 +396,9 @@ class LeadSheetLoop:
         ops.block_set(self._gargs, self._gheld, n_rows=n, n_token=V, ld_u=n, temperature=self.temp, top_p=self.top_p, key_temperature=KEY_TEMP,
                       key_top_p=KEY_TOP_P, logits=self.logits, u_steps=self.U, ev_flags=self.ev_flags, ev_beat=self.ev_beat, params=self.params,
                       state=self.state, seq=self.seq, tok_out=self.tok, running=self.running)
+        self.score_tables = ops.draw_score_tables(self.seq) if scores else None
+        if scores:
+            ops.block_set(self._gargs, self._gheld, **self.score_tables)
         with torch.no_grad():
             h, _, _ = model._prefill(self.seq[:, :self.L0].t(), self.mem)
             self.logits.copy_(model._logits(h.view(n, self.L0, -1)[:, -1].contiguous()))
@@ -449,13 +454,24 @@ class LeadSheetLoop:
                 out.append(EmoError('generation longer than max_gen_len=%d: construct the model with a larger max_gen_len' % self.max_len))
         return out
 
+    def scores(self):
+        """-> per stream, aligned with results(): {'logp', 'rank', 'entropy'} numpy arrays, one entry per id of the stream's result (NaN / -1 at the
+        primer's tokens, which were given), or None where the result is not an id list.  Needs scores=True."""
+        if self.score_tables is None:
+            raise EmoError('LeadSheetLoop.scores(): the loop was built without scores=True')
+        state = self.state.cpu().numpy()
+        tabs = {k: self.score_tables['tok_' + k].cpu().numpy() for k in ('logp', 'rank', 'entropy')}
+        return [{k: t[i, :int(state[i, S_LEN]) - 1].copy() for k, t in tabs.items()} if int(state[i, S_STATUS]) == DONE else None
+                for i in range(self.n)]
+
     def accepted_tokens(self):
         st = self.state.cpu().numpy()
         return int((st[:, S_LEN] - self.params.cpu().numpy()[:, P_PRIMER_LEN]).sum())
 
 
 def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
-                         representation='functional', key_determine=None, seed=0, use_graph=True, step='chain', best_of=1):
+                         representation='functional', key_determine=None, seed=0, use_graph=True, step='chain', best_of=1, best_by='forward',
+                         return_scores=False):
     """The throughput path of generate_plain_xl_batch: the same arguments and result shape, every draw and the grammar on the device
     (emo_grammar_step), each token step = grammar launch + decode_step, k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS,
     default 16) and replayed until every stream has finished.  Draws come from a uniform table seeded with `seed` (like generate_streams),
@@ -468,10 +484,21 @@ def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max
     scored (scoring.score_lead_sheets: mean negative log-probability of its generated tokens in one windowed forward, window = the model's
     dec_mem_len) and the candidate with the lowest one is returned; ties go to the lowest candidate index, a candidate that failed (stuck, key
     error, out of memory) never wins.  -> (results, seconds, picks), picks[i] = {'chosen': c, 'nll_mean': [N floats, NaN for a failed
-    candidate], 'candidates': [N results]}.  best_of = 1 is the path above, draw for draw."""
+    candidate], 'candidates': [N results]}.  best_of = 1 is the path above, draw for draw.
+
+    best_by = 'draws': the candidates are ranked by what the grammar launch recorded at each draw instead (scoring.draw_scores_mean: mean -logp
+    over a candidate's drawn tokens, NaN for one that failed or drew nothing); no second forward runs.  The figures are those of the generating
+    steps themselves, so they hold for any primer length and are the same under both steps.
+
+    return_scores = True: the result tuple gets one more element at its end, a list aligned with the results: {'logp', 'rank', 'entropy'} numpy
+    arrays with one entry per id (NaN / -1 where the id was given: the primer), or None where the result is not an id list.  With best_of > 1
+    these are the chosen candidates' and every pick also carries 'scores': the N candidates'.  The ids are those of the call without it."""
     best_of = int(best_of)
     if best_of < 1:
         raise ValueError('best_of must be at least 1')
+    from . import scoring
+    scoring.check_best_by(best_by)
+    by_draws = best_of > 1 and best_by == 'draws'
     n_primers = len(primers)
     if best_of > 1:
         rep = lambda v: [x for x in v for _ in range(best_of)] if isinstance(v, (list, tuple)) and len(v) == n_primers else v
@@ -483,15 +510,23 @@ def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max
     t0 = time.time()
     try:
         loop = LeadSheetLoop(model, event2idx, idx2event, primers, max_bars=max_bars, max_events=max_events, temp=temp, top_p=top_p,
-                             prompt_bars=prompt_bars, representation=representation, key_determine=key_determine, seed=seed, step=step)
+                             prompt_bars=prompt_bars, representation=representation, key_determine=key_determine, seed=seed, step=step,
+                             scores=return_scores or by_draws)
         loop.run(use_graph=use_graph)
         out = loop.results()
+        sc = loop.scores() if return_scores or by_draws else None
         if best_of > 1:
-            picks = pick_best(model, out, loop.params.cpu().numpy()[:, P_PRIMER_LEN].tolist(), best_of)
-            return [p['candidates'][p['chosen']] for p in picks], time.time() - t0, picks
+            picks = pick_best(model, out, loop.params.cpu().numpy()[:, P_PRIMER_LEN].tolist(), best_of,
+                              scorer=(lambda m, cands, plens: scoring.draw_scores_mean(sc)) if by_draws else None)
+            res = [p['candidates'][p['chosen']] for p in picks], time.time() - t0, picks
+            if return_scores:
+                for i, p in enumerate(picks):
+                    p['scores'] = sc[i * best_of:(i + 1) * best_of]
+                res += ([p['scores'][p['chosen']] for p in picks],)
+            return res
     finally:
         model.train(was_training)
-    return out, time.time() - t0
+    return (out, time.time() - t0, sc) if return_scores else (out, time.time() - t0)
 
 
 def pick_best(model, candidates, primer_lens, best_of, scorer=None):
@@ -544,9 +579,17 @@ def parse_args(argv=None):
                     help='the model step of the device loop: the chain of launches of decode_step, or one persistent launch (emo_decode_step, form 2)')
     ap.add_argument('--best-of', dest='best_of', type=int, default=1,
                     help='generate N candidates per piece in the same batch (N engine streams each) and keep the likeliest (device loop only)')
+    ap.add_argument('--best-by', dest='best_by', default='forward', choices=['forward', 'draws'],
+                    help='--best-of: rank the candidates by a scoring forward over the finished pieces, or by the log-probabilities recorded at each draw')
+    ap.add_argument('--scores', default=None, metavar='FILE',
+                    help='write one JSON record per piece (scoring.draw_record) and its per-token logp / rank / entropy, as recorded at each draw (device loop only)')
     args = ap.parse_args(argv)
     if args.best_of < 1 or (args.best_of > 1 and args.exact):
         ap.error('--best-of must be at least 1 and goes with the device loop (not --exact)')
+    if args.best_by != 'forward' and args.best_of < 2:
+        ap.error('--best-by goes with --best-of N, N > 1')
+    if args.scores and args.exact:
+        ap.error('--scores goes with the device loop (not --exact)')
     return args
 
 
@@ -584,7 +627,8 @@ def main(argv=None):
     print('[# jobs]', len(jobs))
     kw = dict(max_bars=max_bars, max_events=mode['max_events'], temp=mode['temp'], top_p=mode['top_p'], representation=args.representation,
               key_determine=key_determine)
-    times = []
+    times, score_pieces = [], []
+    want = bool(args.scores)
     per_group = max(1, args.streams // args.best_of)               # --streams counts engine streams: N of them per piece with --best-of N
     for j, i in enumerate(range(0, len(jobs), per_group)):
         group = jobs[i:i + per_group]
@@ -592,13 +636,17 @@ def main(argv=None):
         if args.exact:
             res, sec = generate_plain_xl_batch(model, event2idx, idx2event, primers, seeds=list(range(i, i + len(group))), **kw)
         elif args.best_of > 1:
-            res, sec, picks = generate_lead_sheets(model, event2idx, idx2event, primers, seed=args.seed + j, step=args.step.replace('-', '_'),
-                                                   best_of=args.best_of, **kw)
+            res, sec, picks, *sc = generate_lead_sheets(model, event2idx, idx2event, primers, seed=args.seed + j, step=args.step.replace('-', '_'),
+                                                        best_of=args.best_of, best_by=args.best_by, return_scores=want, **kw)
             for (out, _), p in zip(group, picks):
                 print('[info] %s: candidate %d of %d (nll_mean %s)' % (out, p['chosen'], args.best_of, ' '.join('%.4f' % x for x in p['nll_mean'])))
         else:
-            res, sec = generate_lead_sheets(model, event2idx, idx2event, primers, seed=args.seed + j, step=args.step.replace('-', '_'), **kw)
+            res, sec, *sc = generate_lead_sheets(model, event2idx, idx2event, primers, seed=args.seed + j, step=args.step.replace('-', '_'),
+                                                 return_scores=want, **kw)
         times.append(sec)
+        if want:
+            from . import scoring
+            score_pieces += scoring.draw_pieces([os.path.basename(out) for out, _ in group], res, sc[0])
         for (out, _), ids in zip(group, res):
             if ids is None or isinstance(ids, Exception):
                 print('[info] %s not written: %s' % (out, 'stuck after 256 rejected samples' if ids is None else ids))
@@ -606,6 +654,10 @@ def main(argv=None):
             with open(out, 'w') as fh:
                 fh.write('\n'.join(idx2event[w] for w in ids[1:]) + '\n')
             print('[info] wrote', out, len(ids) - 1, 'events')
+    if want:
+        from . import scoring
+        scoring.write_draw_scores(args.scores, score_pieces)
+        print('[info] wrote', args.scores, len(score_pieces), 'records')
     print('[info] finished {} jobs in {:.2f} s'.format(len(jobs), sum(times)))
 
 

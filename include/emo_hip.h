@@ -548,6 +548,16 @@ typedef struct {
     const int32_t* rows;       /* ACC_WINDOW: int32 [n_rows] or NULL */
     int64_t* win_tok;          /* ACC_WINDOW: int64 [n_rows, window] */
     int64_t* win_seg;          /* ACC_WINDOW: int64 [n_rows, window] */
+    /* --- all kinds, optional (NULL: not wanted; all three NULL: the launch is exactly the one without them).  What the model assigned to each
+     * DRAWN token, taken from the logits row the draw was made from: tables [streams, ld_seq] laid out like seq.  When a draw is accepted and
+     * appended at seq[r, c], cell [r, c] gets the figures of emo_token_scores (K9b) for that token at TEMPERATURE 1, whatever temperature the
+     * draw used (the TXL key draw included): logp = l[tok] - lse, rank = #{v : l[v] > l[tok]} + #{v < tok : l[v] == l[tok]}, entropy = lse -
+     * sum_v softmax(l)_v l_v.  No other cell is ever written: not a primer token, not an injected lead-sheet bar or track_full, not a rejected
+     * draw (ACC, ACC_WINDOW redraw inside the launch and record the accepted word only), not a step that ends in STUCK, OVERFLOW, OUT_OF_DRAWS,
+     * KEY_ERROR or WINDOW.  The caller pre-fills the tables (NaN / -1, say): the cells still holding its value are the tokens that were given. */
+    float* tok_logp;           /* f32 [streams, ld_seq] or NULL */
+    int32_t* tok_rank;         /* int32 [streams, ld_seq] or NULL */
+    float* tok_entropy;        /* f32 [streams, ld_seq] or NULL */
 } emo_grammar_step_t;
 /* sizeof(emo_grammar_step_t) as the library was built (a binding checks its mirror against it, as with emo_epilogue_size) */
 int emo_grammar_step_size(void);
