@@ -1,4 +1,4 @@
-// What the three kinds of emo_grammar_step (emo_stage1_gen.hip: TXL; emo_stage2_gen.hip: ACC, ACC_WINDOW and the entry) share besides the draw.
+// What the four kinds of emo_grammar_step (emo_stage1_gen.hip: TXL, TXL_QUEUE; emo_stage2_gen.hip: ACC, ACC_WINDOW and the entry) share besides the draw.
 // Each kernel takes the caller's emo_grammar_step_t by value as its one parameter (a field is fetched from the kernel arguments where it is used,
 // so the fields of the other kinds cost nothing) and runs as one 512-thread workgroup per row.
 #pragma once
@@ -28,5 +28,6 @@ __device__ __forceinline__ void emo_grammar_score(const emo_grammar_step_t& a, c
     if (tid == 0) emo_draw_scores_store(a.tok_logp, a.tok_rank, a.tok_entropy, r * a.ld_seq + c, logp, rank, entropy);
 }
 
-// The launch of the TXL kind (emo_stage1_gen.hip), for emo_grammar_step, which has checked the block.
+// The launches of the TXL and TXL_QUEUE kinds (emo_stage1_gen.hip), for emo_grammar_step, which has checked the block.
 int emo_txl_grammar_launch(const emo_grammar_step_t& a, emo_stream_t stream);
+int emo_txl_queue_launch(const emo_grammar_step_t& a, emo_stream_t stream);

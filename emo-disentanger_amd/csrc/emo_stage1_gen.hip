@@ -14,8 +14,9 @@
 
 namespace {
 
-// Thread 0's part of a drawing step: the grammar on `word`, the next input, the state.  -> the column of seq[r] the word was appended at, or -1.
-__device__ __forceinline__ int32_t txl_grammar(const emo_grammar_step_t& a, int64_t r, int64_t* row, int32_t* st,
+// Thread 0's part of a drawing step: the grammar on `word`, the next input (to tok_out[b]), the state.  -> the column of seq[r] the word was
+// appended at, or -1.
+__device__ __forceinline__ int32_t txl_grammar(const emo_grammar_step_t& a, int64_t b, int64_t* row, int32_t* st,
                                                const int32_t* sst, const int32_t* spr, int64_t word, int32_t draws, bool key_step, int32_t len) {
     const int32_t len0 = len;
     const int32_t fl = a.ev_flags[word];
@@ -59,10 +60,10 @@ __device__ __forceinline__ int32_t txl_grammar(const emo_grammar_step_t& a, int6
     }
     if (status == EMO_TXL_RUNNING && bars >= spr[EMO_TXL_P_MAX_BARS]) status = EMO_TXL_DONE;
     if (status == EMO_TXL_RUNNING && accepted == 0) {
-        a.tok_out[r] = row[0];                               // nothing accepted yet: the whole primer again, one token per step
+        a.tok_out[b] = row[0];                               // nothing accepted yet: the whole primer again, one token per step
         feed = 1;
     } else {
-        a.tok_out[r] = row[len - 1];                         // the accepted word, or after a rejection the previous input again (a finished
+        a.tok_out[b] = row[len - 1];                         // the accepted word, or after a rejection the previous input again (a finished
     }                                                        // stream's row idles on its last token)
     st[EMO_TXL_S_STATUS] = status;
     st[EMO_TXL_S_LEN] = len;
@@ -76,21 +77,17 @@ __device__ __forceinline__ int32_t txl_grammar(const emo_grammar_step_t& a, int6
     return len > len0 ? len0 : -1;
 }
 
-__global__ __launch_bounds__(512) void txl_grammar_kernel(const emo_grammar_step_t a) {
-    __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
-    __shared__ int32_t sst[EMO_TXL_STATE_WORDS], spr[EMO_TXL_PARAM_WORDS];
-    __shared__ int32_t sacc[2];
-    __shared__ float sred[EMO_DRAW_SCORES_WORDS];
-    const int tid = (int)threadIdx.x;
-    const int64_t r = blockIdx.x;
+// One token step of stream r (kind TXL: a stream of the batch; kind TXL_QUEUE: a job) in batch row b, whose logits row it draws from and whose
+// next input it writes, after emo_grammar_open has brought the stream's words to sst / spr and found it RUNNING.  All 512 threads call it; every
+// barrier inside lies on a path that sst, spr and the launch arguments alone decide.
+__device__ __forceinline__ void txl_stream_step(const emo_grammar_step_t& a, int64_t b, int64_t r, char* lds, const int32_t* sst, const int32_t* spr,
+                                                int32_t* sacc, float* sred, int tid) {
     int32_t* st = a.state + r * EMO_TXL_STATE_WORDS;
     int64_t* row = a.seq + r * a.ld_seq;
-    emo_grammar_open(st, EMO_TXL_STATE_WORDS, a.params + r * EMO_TXL_PARAM_WORDS, EMO_TXL_PARAM_WORDS, sst, spr, tid);
-    if (sst[EMO_TXL_S_STATUS] != EMO_TXL_RUNNING) return;
     const int32_t plen = spr[EMO_TXL_P_PRIMER_LEN];
     if (sst[EMO_TXL_S_FEED] < plen) {
         if (tid == 0) {
-            a.tok_out[r] = row[sst[EMO_TXL_S_FEED]];
+            a.tok_out[b] = row[sst[EMO_TXL_S_FEED]];
             st[EMO_TXL_S_FEED] = sst[EMO_TXL_S_FEED] + 1;
         }
         return;
@@ -105,24 +102,97 @@ __global__ __launch_bounds__(512) void txl_grammar_kernel(const emo_grammar_step
     }
     const int32_t len = sst[EMO_TXL_S_LEN];
     const bool key_step = spr[EMO_TXL_P_KEYED] != 0 && len == 1;          // the event after the emotion tag is the key (:81-89)
-    const int64_t word = emo_nucleus_draw(a.logits + r * a.n_token, a.n_token, key_step ? a.key_temperature : a.temperature,
+    const int64_t word = emo_nucleus_draw(a.logits + b * a.n_token, a.n_token, key_step ? a.key_temperature : a.temperature,
                                           key_step ? a.key_top_p : a.top_p, a.u_steps[(int64_t)draws * a.ld_u + r], lds, tid, [] { __syncthreads(); });
     if (!emo_grammar_wants_scores(a)) {
-        if (tid == 0) txl_grammar(a, r, row, st, sst, spr, word, draws, key_step, len);
+        if (tid == 0) txl_grammar(a, b, row, st, sst, spr, word, draws, key_step, len);
         return;
     }
     if (tid == 0) {
-        sacc[0] = txl_grammar(a, r, row, st, sst, spr, word, draws, key_step, len);
+        sacc[0] = txl_grammar(a, b, row, st, sst, spr, word, draws, key_step, len);
         sacc[1] = (int32_t)word;
     }
     __syncthreads();
-    if (sacc[0] >= 0) emo_grammar_score(a, a.logits + r * a.n_token, r, sacc[0], sacc[1], sred, tid);
+    if (sacc[0] >= 0) emo_grammar_score(a, a.logits + b * a.n_token, r, sacc[0], sacc[1], sred, tid);
+}
+
+__global__ __launch_bounds__(512) void txl_grammar_kernel(const emo_grammar_step_t a) {
+    __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
+    __shared__ int32_t sst[EMO_TXL_STATE_WORDS], spr[EMO_TXL_PARAM_WORDS];
+    __shared__ int32_t sacc[2];
+    __shared__ float sred[EMO_DRAW_SCORES_WORDS];
+    const int tid = (int)threadIdx.x;
+    const int64_t r = blockIdx.x;
+    emo_grammar_open(a.state + r * EMO_TXL_STATE_WORDS, EMO_TXL_STATE_WORDS, a.params + r * EMO_TXL_PARAM_WORDS, EMO_TXL_PARAM_WORDS, sst, spr, tid);
+    if (sst[EMO_TXL_S_STATUS] != EMO_TXL_RUNNING) return;
+    txl_stream_step(a, r, r, lds, sst, spr, sacc, sred, tid);
+}
+
+// Thread 0 of slot b, whose job (if it had one) is over: the next queued job that is RUNNING, or none.  queue_head only grows, so a slot that
+// has seen it at n_jobs never adds to it again.
+__device__ __forceinline__ void txl_queue_admit(const emo_grammar_step_t& a, int64_t b) {
+    int32_t next = -1;
+    while (__atomic_load_n(a.queue_head, __ATOMIC_RELAXED) < a.n_jobs) {
+        const int32_t h = atomicAdd(a.queue_head, 1);
+        if (h >= a.n_jobs) break;
+        if (a.state[(int64_t)h * EMO_TXL_STATE_WORDS + EMO_TXL_S_STATUS] == EMO_TXL_RUNNING) {      // (a job closed on the host is passed over)
+            next = h;
+            break;
+        }
+    }
+    a.slot_job[b] = next;
+    a.mem_lens[b] = 0;                                       // the row of the model's memory starts again; a free slot stays at row 0
+    if (next >= 0) {
+        a.tok_out[b] = a.seq[(int64_t)next * a.ld_seq];      // the model step behind this launch is the new job's first token
+        a.state[(int64_t)next * EMO_TXL_STATE_WORDS + EMO_TXL_S_FEED] = 1;
+    }
+}
+
+__global__ __launch_bounds__(512) void txl_queue_kernel(const emo_grammar_step_t a) {
+    __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
+    __shared__ int32_t sst[EMO_TXL_STATE_WORDS], spr[EMO_TXL_PARAM_WORDS];
+    __shared__ int32_t sacc[2], sslot[2];
+    __shared__ float sred[EMO_DRAW_SCORES_WORDS];
+    const int tid = (int)threadIdx.x;
+    const int64_t b = blockIdx.x;
+    if (tid == 0) {                                          // thread 0 writes slot_job[b] and mem_lens[b] below: the others decide from this copy
+        sslot[0] = a.slot_job[b];
+        sslot[1] = a.mem_lens[b] >= a.mem_rows;
+    }
+    __syncthreads();
+    const int64_t j = sslot[0];
+    if (j < 0 || j >= a.n_jobs) {                            // a free slot
+        if (tid == 0) txl_queue_admit(a, b);
+        return;
+    }
+    int32_t* st = a.state + j * EMO_TXL_STATE_WORDS;
+    emo_grammar_open(st, EMO_TXL_STATE_WORDS, a.params + j * EMO_TXL_PARAM_WORDS, EMO_TXL_PARAM_WORDS, sst, spr, tid);
+    if (sst[EMO_TXL_S_STATUS] == EMO_TXL_RUNNING) {
+        if (sslot[1]) {                                      // the row has no place for another token
+            if (tid == 0) {
+                st[EMO_TXL_S_STATUS] = EMO_TXL_MEM_FULL;
+                atomicSub(a.running, 1);
+            }
+        } else {
+            txl_stream_step(a, b, j, lds, sst, spr, sacc, sred, tid);
+        }
+    }
+    if (tid == 0 && st[EMO_TXL_S_STATUS] != EMO_TXL_RUNNING) {      // (thread 0 reads what it wrote itself)
+        if (a.job_steps) a.job_steps[j] = (int32_t)a.mem_lens[b];    // tokens the model was fed for the job = launches it held the slot
+        txl_queue_admit(a, b);
+    }
 }
 
 }  // namespace
 
 int emo_txl_grammar_launch(const emo_grammar_step_t& a, emo_stream_t stream) {
     hipLaunchKernelGGL(txl_grammar_kernel, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
+    EMO_LAUNCH_CHECK();
+    return EMO_OK;
+}
+
+int emo_txl_queue_launch(const emo_grammar_step_t& a, emo_stream_t stream) {
+    hipLaunchKernelGGL(txl_queue_kernel, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
     EMO_LAUNCH_CHECK();
     return EMO_OK;
 }

@@ -208,21 +208,21 @@ extern "C" int emo_grammar_step_size(void) { return (int)sizeof(emo_grammar_step
 extern "C" int emo_grammar_step(const emo_grammar_step_t* args, emo_stream_t stream) {
     EMO_CHECK(args, "emo_grammar_step: null argument block");
     const emo_grammar_step_t& a = *args;
-    EMO_CHECK(a.kind >= 0 && a.kind <= 2, "emo_grammar_step: kind %d is none of 0 (TXL), 1 (ACC), 2 (ACC_WINDOW)", (int)a.kind);
-    const bool txl = a.kind == EMO_GRAMMAR_TXL, acc = a.kind == EMO_GRAMMAR_ACC;
-    const char* const name = txl ? "txl" : acc ? "acc" : "acc_window";
+    EMO_CHECK(a.kind >= 0 && a.kind <= 3, "emo_grammar_step: kind %d is none of 0 (TXL), 1 (ACC), 2 (ACC_WINDOW), 3 (TXL_QUEUE)", (int)a.kind);
+    const bool queue = a.kind == EMO_GRAMMAR_TXL_QUEUE, txl = a.kind == EMO_GRAMMAR_TXL || queue, acc = a.kind == EMO_GRAMMAR_ACC;
+    const char* const name = queue ? "txl_queue" : txl ? "txl" : acc ? "acc" : "acc_window";
     const bool common = a.logits && a.u_steps && a.ev_flags && a.ev_beat && a.params && a.state && a.seq && a.running;
     const bool lead = a.lead_tok && a.lead_off && a.segs;
-    EMO_CHECK(common && (txl ? a.tok_out != nullptr : acc ? lead && a.tok_out && a.seg_out : lead && a.win_tok && a.win_seg),
+    EMO_CHECK(common && (queue ? a.tok_out && a.slot_job && a.queue_head && a.mem_lens : txl ? a.tok_out != nullptr : acc ? lead && a.tok_out && a.seg_out : lead && a.win_tok && a.win_seg),
               "emo_grammar_step[%s]: null pointer", name);
     // (TXL, ACC: workgroup r reads column r of the uniform table)
     EMO_CHECK(a.n_rows > 0 && a.n_u > 0 && a.ld_u > 0 && a.ld_seq > 0 &&
-                  (txl ? a.ld_u >= a.n_rows : acc ? a.ld_u >= a.n_rows && a.max_len > 0 : a.window > 0 && a.ld_seq >= a.window),
+                  (queue ? a.n_jobs > 0 && a.ld_u >= a.n_jobs && a.mem_rows > 0 && a.n_jobs <= INT32_MAX - a.n_rows : txl ? a.ld_u >= a.n_rows : acc ? a.ld_u >= a.n_rows && a.max_len > 0 : a.window > 0 && a.ld_seq >= a.window),
               "emo_grammar_step[%s]: bad sizes", name);
     EMO_CHECK(a.n_token > 0 && a.n_token <= 1024, "emo_grammar_step[%s]: V must be <= 1024 (got %lld)", name, (long long)a.n_token);
     if (txl) {
-        EMO_CHECK(a.temperature > 0.f && a.key_temperature > 0.f, "emo_grammar_step[txl]: temperatures must be > 0");
-        return emo_txl_grammar_launch(a, stream);
+        EMO_CHECK(a.temperature > 0.f && a.key_temperature > 0.f, "emo_grammar_step[%s]: temperatures must be > 0", name);
+        return queue ? emo_txl_queue_launch(a, stream) : emo_txl_grammar_launch(a, stream);
     }
     EMO_CHECK(a.temperature > 0.f, "emo_grammar_step[%s]: temperature must be > 0", name);
     if (acc) hipLaunchKernelGGL(acc_grammar_kernel, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);

@@ -10,12 +10,12 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, ATTN_BWD, ATTN_BWD_KV, ATTN_BWD_R, ATTN_DECODE, ATTN_FAVOR, ATTN_FWD, ATTN_RELPOS, ATTN_SOFTMAX, BF16, F32, MUL_BITMASK, MUL_DGELU, MUL_DGELU_NEW, MUL_NONE, MUL_NONZERO, GRAMMAR_ACC, GRAMMAR_ACC_WINDOW, GRAMMAR_TXL, Attn, DecodeStep, Epilogue, GrammarStep, check,
+from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, ATTN_BWD, ATTN_BWD_KV, ATTN_BWD_R, ATTN_DECODE, ATTN_FAVOR, ATTN_FWD, ATTN_RELPOS, ATTN_SOFTMAX, BF16, F32, MUL_BITMASK, MUL_DGELU, MUL_DGELU_NEW, MUL_NONE, MUL_NONZERO, GRAMMAR_ACC, GRAMMAR_ACC_WINDOW, GRAMMAR_TXL, GRAMMAR_TXL_QUEUE, Attn, DecodeStep, Epilogue, GrammarStep, check,
                    dtype_code, lib, ptr, stream)
 
 __all__ = ['gemm', 'colsum', 'embed_fwd', 'embed_bwd', 'layernorm_fwd', 'layernorm_bwd', 'dropout_apply', 'favor_attn_fwd',
            'favor_attn_bwd', 'favor_decode_step', 'decode_step', 'decode_step_set', 'block_set', 'DecodeStep', 'GrammarStep', 'grammar_step', 'draw_score_tables', 'favor_draw_omega', 'softmax_attn_fwd', 'softmax_attn_bwd', 'softmax_attn_decode', 'relpos_attn_fwd', 'relpos_attn_bwd', 'relpos_attn_decode', 'xent_fwd',
-           'xent_bwd', 'token_scores', 'xent_bwd_rows', 'argmax', 'sample_nucleus', 'sample_nucleus_step', 'txl_grammar_step', 'acc_grammar_step', 'acc_window_step', 'accuracy_counts', 'sumsq', 'clip_coef', 'adam_step', 'cast', 'add_bias2',
+           'xent_bwd', 'token_scores', 'xent_bwd_rows', 'argmax', 'sample_nucleus', 'sample_nucleus_step', 'txl_grammar_step', 'txl_queue_step', 'acc_grammar_step', 'acc_window_step', 'accuracy_counts', 'sumsq', 'clip_coef', 'adam_step', 'cast', 'add_bias2',
            'ACT_NONE', 'ACT_RELU', 'ACT_GELU_NEW', 'ACT_GELU', 'MUL_NONE', 'MUL_NONZERO', 'MUL_DGELU_NEW', 'MUL_DGELU', 'MUL_BITMASK', 'gemm_bitmask_ok', 'gemm_lna_ok', 'bitmask_rows', 'favor_bwd_dn_ok', 'ffn_fwd', 'ffn_fwd_ok']
 
 
@@ -392,6 +392,11 @@ _GRAMMAR_STEP_LAYOUT = {
     'tok_logp': lambda a, t: _is(t, _F32) and t.shape == (a.ld_u, a.ld_seq),
     'tok_rank': lambda a, t: _is(t, _I32) and t.shape == (a.ld_u, a.ld_seq),
     'tok_entropy': lambda a, t: _is(t, _F32) and t.shape == (a.ld_u, a.ld_seq),
+    # the queue kind: per slot (n_rows) and per job (ld_u = n_jobs)
+    'slot_job': lambda a, t: _is(t, _I32) and t.numel() == a.n_rows,
+    'queue_head': lambda a, t: _is(t, _I32) and t.numel() >= 1,
+    'mem_lens': lambda a, t: _is(t, _I64) and t.numel() == a.n_rows,
+    'job_steps': lambda a, t: _is(t, _I32) and t.numel() == a.ld_u,
 }
 # per struct: its name in messages, the layout table, the int64 vectors, and the numbers a tensor brings with it (field -> (number, of tensor))
 _BLOCKS = {
@@ -682,6 +687,22 @@ def txl_grammar_step(logits, temperature, top_p, key_temperature, key_top_p, u_s
     _grammar_once(GRAMMAR_TXL, n_rows=n, n_token=V, ld_u=n, temperature=temperature, top_p=top_p, key_temperature=key_temperature,
                   key_top_p=key_top_p, logits=logits, u_steps=u_steps, ev_flags=ev_flags, ev_beat=ev_beat, params=params, state=state, seq=seq,
                   tok_out=tok_out, running=running, tok_logp=tok_logp, tok_rank=tok_rank, tok_entropy=tok_entropy)
+    return tok_out
+
+
+def txl_queue_step(logits, temperature, top_p, key_temperature, key_top_p, u_steps, ev_flags, ev_beat, params, state, seq, tok_out, running,
+                   slot_job, queue_head, mem_lens, mem_rows, job_steps=None, tok_logp=None, tok_rank=None, tok_entropy=None):
+    """One stage-1 sample-and-grammar step of `slots` batch rows working through a queue of n_jobs jobs (include/emo_hip.h,
+    EMO_GRAMMAR_TXL_QUEUE): logits fp32 [slots, V], tok_out int64 [slots], slot_job int32 [slots] (-1: free), mem_lens int64 [slots] (the
+    model memory's per-row lengths), queue_head int32 [1]; u_steps fp32 [n_u, n_jobs], params / state int32 [n_jobs, 8], seq int64 [n_jobs, W]
+    and the optional tables (job_steps int32 [n_jobs]; the score tables [n_jobs, W]) are the jobs'.  Everything but logits, u_steps, params
+    and the event tables is updated in place."""
+    slots, V = logits.shape
+    n_jobs = params.shape[0]
+    _grammar_once(GRAMMAR_TXL_QUEUE, n_rows=slots, n_token=V, ld_u=n_jobs, n_jobs=n_jobs, mem_rows=mem_rows, temperature=temperature, top_p=top_p,
+                  key_temperature=key_temperature, key_top_p=key_top_p, logits=logits, u_steps=u_steps, ev_flags=ev_flags, ev_beat=ev_beat,
+                  params=params, state=state, seq=seq, tok_out=tok_out, running=running, slot_job=slot_job, queue_head=queue_head,
+                  mem_lens=mem_lens, job_steps=job_steps, tok_logp=tok_logp, tok_rank=tok_rank, tok_entropy=tok_entropy)
     return tok_out
 
 

@@ -109,7 +109,7 @@ def generate_plain_xl(model, event2idx, idx2event, max_bars=160, max_events=2048
 EV_BEAT, EV_BAR, EV_PAD, EV_EOS, EV_KEY, EV_MAJOR, EV_MINOR = 1, 2, 4, 8, 16, 32, 64
 P_MAX_BARS, P_MAX_EVENTS, P_PRIMER_LEN, P_KEYED, P_KEY_RULE, P_EMO_MODE = range(6)
 S_STATUS, S_LEN, S_ACCEPTED, S_BEAT, S_BARS, S_FAILED, S_FEED, S_DRAWS = range(8)
-RUNNING, DONE, STUCK, KEY_ERROR, OVERFLOW = range(5)
+RUNNING, DONE, STUCK, KEY_ERROR, OVERFLOW, MEM_FULL = range(6)
 KEY_TEMP, KEY_TOP_P = 1.1, 0.97                     # the key draw of generate_plain_xl (inference_utils.py:81-82)
 _KEY_ERROR = '[info] key generation failed'
 
@@ -363,29 +363,12 @@ class LeadSheetLoop:
         kw = _per_stream(n, max_bars=max_bars, max_events=max_events, prompt_bars=prompt_bars, representation=representation, key_determine=key_determine)
         self.model, self.temp, self.top_p = model, float(temp), float(top_p)
         dev = self.dev = next(model.parameters()).device
-        sheets = [_LeadSheet(event2idx, primers[i], kw[i]['prompt_bars'], kw[i]['max_bars'], kw[i]['max_events']) for i in range(n)]
+        plens, seq, params, state = self._job_tables(model, event2idx, idx2event, primers, kw)
         V = model.vocab_size
-        if V > 1024:
-            raise EmoError('generate_lead_sheets: the device draw takes V <= 1024 (got %d)' % V)
-        flags, beat = event_tables(idx2event, V)
-        self.ev_flags, self.ev_beat = torch.from_numpy(flags).to(dev), torch.from_numpy(beat).to(dev)
         self.mem = TXLMemory(model, n, model._max_gen_len)
         self.max_len = self.mem.max_len
-        self.L0 = min(len(s.tokens) for s in sheets)
-        if self.L0 < 1:
-            raise ValueError('generate_lead_sheets: empty primer')
-        plens = [len(s.tokens) for s in sheets]
-        width = max(max(plens), max(k['max_events'] for k in kw)) + 1
-        seq = np.zeros((n, width), np.int64)
-        params = np.zeros((n, ops.TXL_PARAM_WORDS), np.int32)
-        state = np.zeros((n, ops.TXL_STATE_WORDS), np.int32)
-        for i, (s, k) in enumerate(zip(sheets, kw)):
-            seq[i, :plens[i]] = s.tokens
-            params[i, [P_MAX_BARS, P_MAX_EVENTS, P_PRIMER_LEN]] = k['max_bars'], k['max_events'], plens[i]
-            params[i, P_KEYED] = k['representation'] in ('functional', 'key')
-            params[i, P_KEY_RULE] = k['key_determine'] == 'rule'
-            params[i, P_EMO_MODE] = emotion_mode(idx2event, s.tokens[0])
-            state[i, [S_STATUS, S_LEN, S_BARS, S_FEED]] = (RUNNING if s.open() else DONE), plens[i], s.bars, self.L0
+        self.L0 = min(plens)
+        state[:, S_FEED] = self.L0
         self.seq, self.params, self.state = (torch.from_numpy(a).to(dev) for a in (seq, params, state))
         self.running = torch.tensor([int((state[:, S_STATUS] == RUNNING).sum())], dtype=torch.int32, device=dev)
         self.U = uniform_table(self.max_len - self.L0 + 1, n, seed, dev)      # at most one draw per step, one more at the end
@@ -408,6 +391,32 @@ class LeadSheetLoop:
             self.mem = self.stepper.mem                              # (the token-major prefill memory goes)
         self.pos = self.L0                   # positions in the memory (host count: every row advances one per step)
         self.replayed = (0, 0.0)
+
+    def _job_tables(self, model, event2idx, idx2event, primers, kw):
+        """The grammar tables of the device (self.ev_flags, self.ev_beat) and, per stream, what the grammar launch reads and keeps
+        -> (primer lengths, seq int64 [n, width], params, state int32 [n, 8]: numpy, state[FEED] left to the caller)."""
+        n, dev = len(primers), self.dev
+        sheets = [_LeadSheet(event2idx, primers[i], kw[i]['prompt_bars'], kw[i]['max_bars'], kw[i]['max_events']) for i in range(n)]
+        V = model.vocab_size
+        if V > 1024:
+            raise EmoError('generate_lead_sheets: the device draw takes V <= 1024 (got %d)' % V)
+        flags, beat = event_tables(idx2event, V)
+        self.ev_flags, self.ev_beat = torch.from_numpy(flags).to(dev), torch.from_numpy(beat).to(dev)
+        plens = [len(s.tokens) for s in sheets]
+        if min(plens) < 1:
+            raise ValueError('generate_lead_sheets: empty primer')
+        width = max(max(plens), max(k['max_events'] for k in kw)) + 1
+        seq = np.zeros((n, width), np.int64)
+        params = np.zeros((n, ops.TXL_PARAM_WORDS), np.int32)
+        state = np.zeros((n, ops.TXL_STATE_WORDS), np.int32)
+        for i, (s, k) in enumerate(zip(sheets, kw)):
+            seq[i, :plens[i]] = s.tokens
+            params[i, [P_MAX_BARS, P_MAX_EVENTS, P_PRIMER_LEN]] = k['max_bars'], k['max_events'], plens[i]
+            params[i, P_KEYED] = k['representation'] in ('functional', 'key')
+            params[i, P_KEY_RULE] = k['key_determine'] == 'rule'
+            params[i, P_EMO_MODE] = emotion_mode(idx2event, s.tokens[0])
+            state[i, [S_STATUS, S_LEN, S_BARS]] = (RUNNING if s.open() else DONE), plens[i], s.bars
+        return plens, seq, params, state
 
     def grammar(self):
         ops.grammar_step(self._gargs)
@@ -469,9 +478,106 @@ class LeadSheetLoop:
         return int((st[:, S_LEN] - self.params.cpu().numpy()[:, P_PRIMER_LEN]).sum())
 
 
+def queue_plan(job_steps, slots):
+    """-> (launches, slot occupancy) of a LeadSheetQueue run whose job j holds a slot for job_steps[j] launches (the tokens the model is fed for
+    it: its primer, its accepted words, one more per rejected draw).  The first launch only admits: it hands jobs 0 .. slots - 1 out; after that
+    the job at the head of the queue goes to the slot that frees up first, in the launch in which its job ends (slots that free up in the same
+    launch are interchangeable), so launches = 1 + the time the last slot finishes.  Occupancy = sum(job_steps) / (launches * slots): the
+    share of the model's rows that carried a job's token."""
+    import heapq
+    slots = int(slots)
+    if slots < 1:
+        raise ValueError('slots must be at least 1')
+    steps = [int(x) for x in job_steps]
+    if any(x < 0 for x in steps):
+        raise ValueError('queue_plan: negative step count')
+    free_at = [0] * min(slots, max(len(steps), 1))               # (a slot that never gets a job does not change the end)
+    heapq.heapify(free_at)
+    end = 0
+    for x in steps:
+        t = heapq.heappop(free_at) + x
+        end = max(end, t)
+        heapq.heappush(free_at, t)
+    if not steps:
+        return 0, 0.0
+    launches = 1 + end
+    return launches, sum(steps) / float(launches * slots)
+
+
+class LeadSheetQueue(LeadSheetLoop):
+    """LeadSheetLoop for more jobs than rows: `slots` rows of the model batch (one TXLMemory / OneLaunchStep of that many rows) work through
+    len(primers) queued jobs.  one_step() = emo_grammar_step (kind TXL_QUEUE) + the model step: a slot whose job ends takes the next job inside
+    the grammar launch and restarts its row of the memory (length 0), so the replayed graphs go on and the running count stays the only thing
+    read back.  There is no prefill: the first launch admits the first jobs and every primer token goes through the one-token step.  Job j draws
+    from column j of the uniform table, whatever slot it lands in.  A job that fills its row of the memory (max_gen_len tokens) ends with
+    MEM_FULL, which results() reports like the lock-step loop's bound.  results() / scores() are LeadSheetLoop's, per job; job_steps: the
+    launches each finished job held a slot; launches: the launches run() queued (a k-step replay ends up to k - 1 launches past the drain)."""
+
+    def __init__(self, model, event2idx, idx2event, primers, slots, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
+                 representation='functional', key_determine=None, seed=0, step='chain', scores=False):
+        from .model.plain_transformer import TXLMemory
+        n = self.n = len(primers)
+        assert n > 0
+        slots = self.slots = int(slots)
+        if slots < 1:
+            raise ValueError('slots must be at least 1 (got %d)' % slots)
+        if step not in STEPS:
+            raise ValueError("step must be one of %s (got %r)" % (', '.join(repr(s) for s in STEPS), step))
+        if step == 'one_launch':                                     # refused before anything is allocated; never a silent fall-back to the chain
+            why = one_launch_unsupported(model, slots)
+            if why is not None:
+                raise EmoError("step='one_launch' (emo_decode_step[txl]) needs %s; use step='chain'" % why)
+        kw = _per_stream(n, max_bars=max_bars, max_events=max_events, prompt_bars=prompt_bars, representation=representation, key_determine=key_determine)
+        self.model, self.temp, self.top_p = model, float(temp), float(top_p)
+        dev = self.dev = next(model.parameters()).device
+        _, seq, params, state = self._job_tables(model, event2idx, idx2event, primers, kw)
+        V = model.vocab_size
+        state[:, S_FEED] = 1                                         # (what an admission sets: the first token goes out with it)
+        self.seq, self.params, self.state = (torch.from_numpy(a).to(dev) for a in (seq, params, state))
+        self.running = torch.tensor([int((state[:, S_STATUS] == RUNNING).sum())], dtype=torch.int32, device=dev)
+        self.stepper = OneLaunchStep(model, slots) if step == 'one_launch' else None
+        self.mem = self.stepper.mem if self.stepper is not None else TXLMemory(model, slots, model._max_gen_len)
+        self.max_len = self.mem.max_len
+        self.U = uniform_table(self.max_len, n, seed, dev)          # a job draws at most once per token of its row
+        self.tok = self.seq[0, :1].repeat(slots).contiguous()        # (a valid id in every row: a slot that never gets a job feeds it)
+        self.logits = torch.zeros(slots, V, dtype=torch.float32, device=dev)
+        self.slot_job = torch.full((slots,), -1, dtype=torch.int32, device=dev)
+        self.queue_head = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.job_steps_dev = torch.zeros(n, dtype=torch.int32, device=dev)
+        self._gargs, self._gheld = ops.GrammarStep(kind=ops.GRAMMAR_TXL_QUEUE), {}
+        ops.block_set(self._gargs, self._gheld, n_rows=slots, n_token=V, ld_u=n, n_jobs=n, mem_rows=self.max_len, temperature=self.temp,
+                      top_p=self.top_p, key_temperature=KEY_TEMP, key_top_p=KEY_TOP_P, logits=self.logits, u_steps=self.U, ev_flags=self.ev_flags,
+                      ev_beat=self.ev_beat, params=self.params, state=self.state, seq=self.seq, tok_out=self.tok, running=self.running,
+                      slot_job=self.slot_job, queue_head=self.queue_head, mem_lens=self.mem.lens, job_steps=self.job_steps_dev)
+        self.score_tables = ops.draw_score_tables(self.seq) if scores else None
+        if scores:
+            ops.block_set(self._gargs, self._gheld, **self.score_tables)
+        # no job can outlast its row of the memory, so the queue is drained before this many launches whatever the slots do: a budget for the
+        # replayer, not a limit that is meant to bind (the per-job limit is the kernel's MEM_FULL)
+        self.budget = n * self.max_len + 2
+        self.launches = 0
+        self.replayed = (0, 0.0)
+
+    def run(self, use_graph=True, steps_per_graph=None):
+        """Launches until the running count is 0; it is read once per replay (per step without graphs)."""
+        rp = StepReplayer(self.one_step, self.dev, steps_per_graph)  # (goes with the run: see LeadSheetLoop.run)
+        with torch.no_grad():
+            self.launches = rp.run(self.launches, self.budget, live=self._live, use_graph=use_graph)
+            self.replayed = rp.replayed
+            torch.cuda.synchronize()
+            if self._live() > 0:
+                raise EmoError('LeadSheetQueue: %d jobs still running after %d launches' % (self._live(), self.launches))
+        if self.stepper is not None:
+            self.stepper.check_persistent()                          # a launch that gave up must not pass for a result
+
+    def job_steps(self):
+        """-> per job, the launches it held a slot (0 for a job that was closed before the run)."""
+        return [int(x) for x in self.job_steps_dev.cpu().tolist()]
+
+
 def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
                          representation='functional', key_determine=None, seed=0, use_graph=True, step='chain', best_of=1, best_by='forward',
-                         return_scores=False):
+                         return_scores=False, slots=None):
     """The throughput path of generate_plain_xl_batch: the same arguments and result shape, every draw and the grammar on the device
     (emo_grammar_step), each token step = grammar launch + decode_step, k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS,
     default 16) and replayed until every stream has finished.  Draws come from a uniform table seeded with `seed` (like generate_streams),
@@ -492,10 +598,20 @@ def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max
 
     return_scores = True: the result tuple gets one more element at its end, a list aligned with the results: {'logp', 'rank', 'entropy'} numpy
     arrays with one entry per id (NaN / -1 where the id was given: the primer), or None where the result is not an id list.  With best_of > 1
-    these are the chosen candidates' and every pick also carries 'scores': the N candidates'.  The ids are those of the call without it."""
+    these are the chosen candidates' and every pick also carries 'scores': the N candidates'.  The ids are those of the call without it.
+
+    slots = None: one lock-step batch with a row per stream (the paths above, draw for draw).  slots = S: the streams (primers times best_of)
+    are JOBS that run through S rows (LeadSheetQueue): a row whose job ends takes the next job on the device, so no row idles while jobs wait
+    and no batch waits for its longest member; step='one_launch' then has to hold for S rows.  A job draws from its own column of the uniform
+    table, so its ids do not depend on S or on the slot it ran in beyond what the model step's arithmetic does; they are not those of slots =
+    None, whose streams share a prefill.  The results, best_of, best_by and return_scores are per job as they are per stream."""
     best_of = int(best_of)
     if best_of < 1:
         raise ValueError('best_of must be at least 1')
+    if slots is not None:
+        slots = int(slots)
+        if slots < 1:
+            raise ValueError('slots must be at least 1 (got %d)' % slots)
     from . import scoring
     scoring.check_best_by(best_by)
     by_draws = best_of > 1 and best_by == 'draws'
@@ -509,9 +625,10 @@ def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max
     model.eval()
     t0 = time.time()
     try:
-        loop = LeadSheetLoop(model, event2idx, idx2event, primers, max_bars=max_bars, max_events=max_events, temp=temp, top_p=top_p,
-                             prompt_bars=prompt_bars, representation=representation, key_determine=key_determine, seed=seed, step=step,
-                             scores=return_scores or by_draws)
+        kw = dict(max_bars=max_bars, max_events=max_events, temp=temp, top_p=top_p, prompt_bars=prompt_bars, representation=representation,
+                  key_determine=key_determine, seed=seed, step=step, scores=return_scores or by_draws)
+        loop = (LeadSheetLoop(model, event2idx, idx2event, primers, **kw) if slots is None else
+                LeadSheetQueue(model, event2idx, idx2event, primers, slots, **kw))
         loop.run(use_graph=use_graph)
         out = loop.results()
         sc = loop.scores() if return_scores or by_draws else None
@@ -572,6 +689,9 @@ def parse_args(argv=None):
     ap.add_argument('-o', '--output_dir', default='generation/emopia_functional_two')
     ap.add_argument('-n', '--n_groups', type=int, default=20, help='pieces per emotion')
     ap.add_argument('--streams', type=int, default=32, help='pieces generated in lock-step')
+    ap.add_argument('--slots', type=int, default=None,
+                    help='run ALL jobs (times --best-of) through this many rows of one model batch: a row whose job ends takes the next job on the device '
+                         '(device loop only; --streams is not used)')
     ap.add_argument('--dtype', default=None, choices=[None, 'bf16', 'fp32'])
     ap.add_argument('--exact', action='store_true', help='NumPy sampling and grammar on the host (reference-exact per seed) instead of the device loop')
     ap.add_argument('--seed', type=int, default=0, help='seed of the device uniform table (the group of streams j uses seed + j)')
@@ -590,6 +710,8 @@ def parse_args(argv=None):
         ap.error('--best-by goes with --best-of N, N > 1')
     if args.scores and args.exact:
         ap.error('--scores goes with the device loop (not --exact)')
+    if args.slots is not None and (args.slots < 1 or args.exact):
+        ap.error('--slots must be at least 1 and goes with the device loop (not --exact)')
     return args
 
 
@@ -597,7 +719,7 @@ def main(argv=None):
     """Same flags as the reference's stage-1 inference.py (-c -r -m -i -o -n): n_groups pieces for each emotion of the mode, key_determine
     'rule', max_bars 128, written as samp_XX_<emotion>_roman.txt (functional) / samp_XX_<emotion>.txt (remi) without the emotion tag — the
     files the stage-2 command line (inference.main) reads.  All jobs run --streams at a time through generate_lead_sheets (device draws and
-    grammar; --step one-launch: the model step as one persistent launch); --exact runs them through generate_plain_xl_batch (NumPy sampling, seeds 0, 1, ... in job order).  MIDI output (miditoolkit,
+    grammar; --step one-launch: the model step as one persistent launch; --slots S: all jobs as one queue through S rows); --exact runs them through generate_plain_xl_batch (NumPy sampling, seeds 0, 1, ... in job order).  MIDI output (miditoolkit,
     relative2absolute) is not part of this package."""
     import yaml
     from .model.plain_transformer import PlainTransformer
@@ -630,6 +752,8 @@ def main(argv=None):
     times, score_pieces = [], []
     want = bool(args.scores)
     per_group = max(1, args.streams // args.best_of)               # --streams counts engine streams: N of them per piece with --best-of N
+    if args.slots is not None:
+        per_group = max(1, len(jobs))                              # one call: the queue takes every job (seed: that of the first group)
     for j, i in enumerate(range(0, len(jobs), per_group)):
         group = jobs[i:i + per_group]
         primers = [['Emotion_{}'.format(e)] for _, e in group]
@@ -637,12 +761,12 @@ def main(argv=None):
             res, sec = generate_plain_xl_batch(model, event2idx, idx2event, primers, seeds=list(range(i, i + len(group))), **kw)
         elif args.best_of > 1:
             res, sec, picks, *sc = generate_lead_sheets(model, event2idx, idx2event, primers, seed=args.seed + j, step=args.step.replace('-', '_'),
-                                                        best_of=args.best_of, best_by=args.best_by, return_scores=want, **kw)
+                                                        best_of=args.best_of, best_by=args.best_by, return_scores=want, slots=args.slots, **kw)
             for (out, _), p in zip(group, picks):
                 print('[info] %s: candidate %d of %d (nll_mean %s)' % (out, p['chosen'], args.best_of, ' '.join('%.4f' % x for x in p['nll_mean'])))
         else:
             res, sec, *sc = generate_lead_sheets(model, event2idx, idx2event, primers, seed=args.seed + j, step=args.step.replace('-', '_'),
-                                                 return_scores=want, **kw)
+                                                 return_scores=want, slots=args.slots, **kw)
         times.append(sec)
         if want:
             from . import scoring

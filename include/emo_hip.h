@@ -473,7 +473,8 @@ enum { EMO_TXL_P_MAX_BARS = 0, EMO_TXL_P_MAX_EVENTS = 1, EMO_TXL_P_PRIMER_LEN = 
        EMO_TXL_P_EMO_MODE = 5 /* 0 none, 1 major (Q1 / Q4 / Positive), 2 minor (Q2 / Q3 / Negative) */, EMO_TXL_PARAM_WORDS = 8 };
 enum { EMO_TXL_S_STATUS = 0, EMO_TXL_S_LEN = 1 /* tokens in seq[r] */, EMO_TXL_S_ACCEPTED = 2, EMO_TXL_S_BEAT = 3, EMO_TXL_S_BARS = 4,
        EMO_TXL_S_FAILED = 5 /* rejected Beats in a row */, EMO_TXL_S_FEED = 6 /* next primer token to feed */, EMO_TXL_S_DRAWS = 7, EMO_TXL_STATE_WORDS = 8 };
-enum { EMO_TXL_RUNNING = 0, EMO_TXL_DONE = 1, EMO_TXL_STUCK = 2, EMO_TXL_KEY_ERROR = 3, EMO_TXL_OVERFLOW = 4 /* seq or u_steps exhausted */ };
+enum { EMO_TXL_RUNNING = 0, EMO_TXL_DONE = 1, EMO_TXL_STUCK = 2, EMO_TXL_KEY_ERROR = 3, EMO_TXL_OVERFLOW = 4 /* seq or u_steps exhausted */,
+       EMO_TXL_MEM_FULL = 5 /* TXL_QUEUE: the slot's row of the model's memory has no place for another token */ };
 enum { EMO_TXL_EV_BEAT = 1, EMO_TXL_EV_BAR = 2, EMO_TXL_EV_PAD = 4, EMO_TXL_EV_EOS = 8, EMO_TXL_EV_KEY = 16, EMO_TXL_EV_MAJOR = 32, EMO_TXL_EV_MINOR = 64 };
 /* EMO_GRAMMAR_ACC.  Stage-2 accompaniment generation (stage2_accompaniment/inference.py generate_conditional :231-327): the draw and the grammar of one lock-step
  * token step for n streams, one 512-thread workgroup per stream, all loop state in device memory (graph-capturable).  seq / segs (int64, pitch
@@ -512,21 +513,41 @@ enum { EMO_ACC_EV_BEAT = 1, EMO_ACC_EV_TRACK_LS = 2, EMO_ACC_EV_PAD = 4, EMO_ACC
  *   otherwise the draw, the in-launch redraws and the grammar of the ACC kind (the same device code), state[CONSUMED] untouched; a
  *   stream still RUNNING then gets its next model input, win_tok / win_seg[b, 0 .. window) = seq / segs[r, LEN - window .. LEN).
  * OUT_OF_DRAWS, OVERFLOW (ld_seq too short for the accepted tokens) and *running behave as in the ACC kind. */
-/* The three grammar steps above are the kinds of ONE entry with ONE argument block, as emo_decode_step_t is for the model step beside them in
+/* EMO_GRAMMAR_TXL_QUEUE.  The TXL kind for MORE JOBS THAN ROWS: the n_rows rows of the model batch are SLOTS, the streams are n_jobs JOBS waiting in a queue, and
+ * a slot whose job ends takes the next one inside the launch, so that no host round trip (and no break in a hipGraph replay) lies between two
+ * jobs of a row.  One 512-thread workgroup per slot b, which owns logits[b], tok_out[b] and mem_lens[b] (the per-row length of the model's
+ * memory: a Transformer-XL row restarts when its length is 0) and works on job j = slot_job[b] (int32 [n_rows]; -1: free).  Everything the TXL
+ * kind indexes by stream is indexed by job: params, state, seq, the score tables (n_jobs rows each) and the column of u_steps (ld_u = n_jobs;
+ * draw d of job j takes u_steps[d * ld_u + j]).  Per launch and slot:
+ *   slot_job[b] = a RUNNING job -> if mem_lens[b] >= mem_rows the job ends with MEM_FULL (the per-row form of the lock-step loop's bound:
+ *                                  the row cannot take the token of another step); otherwise exactly the TXL kind's step for stream j (the same
+ *                                  device code): primer feed, draw, key rule, Beat / Bar / PAD / EOS, the limits, the re-feeds, the scores;
+ *   slot_job[b] free, or the job left RUNNING in this launch -> thread 0 takes jobs from the queue (h = atomicAdd(queue_head, 1), h < n_jobs)
+ *                                  until one is RUNNING (a job the host closed before the run is passed over).  With a job j': slot_job[b] = j',
+ *                                  mem_lens[b] = 0, tok_out[b] = seq[j', 0], state[j', FEED] = 1: the model step behind this very launch is
+ *                                  the job's first token, no step idles in between.  With the queue empty: slot_job[b] = -1 and mem_lens[b] = 0,
+ *                                  in this and in every later launch (queue_head is not added to again), so the model step, which still runs
+ *                                  on the row, stays at the first row of its cache.
+ * The first launch starts from slot_job = -1 everywhere, queue_head = 0, mem_lens = 0 and tok_out = any valid id, and admits the first jobs
+ * itself: every primer token goes through the one-token model step (state[j, FEED] as the host leaves it is ignored).  *running starts at the
+ * number of RUNNING jobs and is decremented once per job.  Which of several slots that free up in one launch gets which job is not specified; a
+ * job's ids depend on the job (its rows, its uniform column, its counters) and the logits it is shown, nothing else.  job_steps (int32 [n_jobs]
+ * or NULL): when a job ends, job_steps[j] = mem_lens[b] = the tokens the model was fed for it = the launches it held its slot. */
+/* The four grammar steps above are the kinds of ONE entry with ONE argument block, as emo_decode_step_t is for the model step beside them in
  * every generation loop.  `kind` selects the kernel; a field that a kind does not read is ignored by it, whatever it holds (the comment of each
- * field names its readers; none = all three).  The block is read AT CALL TIME: its values travel as the launch's arguments, so under hipGraph
+ * field names its readers; none = all four; a field of TXL is a field of TXL_QUEUE too).  The block is read AT CALL TIME: its values travel as the launch's arguments, so under hipGraph
  * capture they are baked into the captured launch, exactly as positional arguments would be, and a later change of the block reaches only later
  * calls (and later captures).  The struct holds raw device addresses: its owner keeps the memory alive. */
-enum { EMO_GRAMMAR_TXL = 0, EMO_GRAMMAR_ACC = 1, EMO_GRAMMAR_ACC_WINDOW = 2 };   /* what each does: the three comments above (n = n_rows, V = n_token) */
+enum { EMO_GRAMMAR_TXL = 0, EMO_GRAMMAR_ACC = 1, EMO_GRAMMAR_ACC_WINDOW = 2, EMO_GRAMMAR_TXL_QUEUE = 3 };   /* what each does: the four comments above (n = n_rows, V = n_token) */
 typedef struct {
     int32_t kind;              /* EMO_GRAMMAR_* */
     /* --- all kinds */
-    int64_t n_rows;            /* workgroups launched: TXL, ACC the n streams; ACC_WINDOW the m rows of the batch */
+    int64_t n_rows;            /* workgroups launched: TXL, ACC the n streams; ACC_WINDOW the m rows of the batch; TXL_QUEUE the slots */
     const float* logits;       /* f32 [n_rows, n_token] */
     int64_t n_token;           /* V <= 1024 */
     float temperature, top_p;  /* temperature > 0 */
     const float* u_steps;      /* f32 [n_u, ld_u] uniforms: draw d of stream r takes u_steps[d * ld_u + r] */
-    int64_t n_u, ld_u;         /* ld_u = the number of streams (TXL, ACC: >= n_rows) */
+    int64_t n_u, ld_u;         /* ld_u = the number of streams (TXL, ACC: >= n_rows; TXL_QUEUE: >= n_jobs) */
     const int32_t* ev_flags;   /* int32 [n_token]: EMO_TXL_EV_* / EMO_ACC_EV_* bits */
     const int32_t* ev_beat;    /* int32 [n_token] */
     const int32_t* params;     /* int32 [streams, 8] */
@@ -548,6 +569,13 @@ typedef struct {
     const int32_t* rows;       /* ACC_WINDOW: int32 [n_rows] or NULL */
     int64_t* win_tok;          /* ACC_WINDOW: int64 [n_rows, window] */
     int64_t* win_seg;          /* ACC_WINDOW: int64 [n_rows, window] */
+    /* (TXL_QUEUE alone; the last of the kind-specific fields: the optional outputs below stay the tail of the block) */
+    int32_t* slot_job;         /* TXL_QUEUE: int32 [n_rows]: the job of each slot, -1 = free */
+    int32_t* queue_head;       /* TXL_QUEUE: int32 [1]: the next job to hand out */
+    int64_t n_jobs;            /* TXL_QUEUE: rows of params, state, seq and the score tables; 0 < n_jobs <= ld_u */
+    int64_t* mem_lens;         /* TXL_QUEUE: int64 [n_rows]: the per-row lengths of the model's memory (the array the model step advances) */
+    int64_t mem_rows;          /* TXL_QUEUE: cache rows per row of the memory, > 0 */
+    int32_t* job_steps;        /* TXL_QUEUE: int32 [n_jobs] or NULL: per finished job, the launches it held a slot */
     /* --- all kinds, optional (NULL: not wanted; all three NULL: the launch is exactly the one without them).  What the model assigned to each
      * DRAWN token, taken from the logits row the draw was made from: tables [streams, ld_seq] laid out like seq.  When a draw is accepted and
      * appended at seq[r, c], cell [r, c] gets the figures of emo_token_scores (K9b) for that token at TEMPERATURE 1, whatever temperature the
@@ -561,7 +589,7 @@ typedef struct {
 } emo_grammar_step_t;
 /* sizeof(emo_grammar_step_t) as the library was built (a binding checks its mirror against it, as with emo_epilogue_size) */
 int emo_grammar_step_size(void);
-/* Messages name the kind: "emo_grammar_step[txl]: ", "emo_grammar_step[acc]: ", "emo_grammar_step[acc_window]: ". */
+/* Messages name the kind: "emo_grammar_step[txl]: ", "emo_grammar_step[acc]: ", "emo_grammar_step[acc_window]: ", "emo_grammar_step[txl_queue]: ". */
 int emo_grammar_step(const emo_grammar_step_t* args, emo_stream_t stream);
 /* counts[0..5] += {nonpad, nonpad&correct, chord, chord&correct, melody, melody&correct} (train.py:184-193) */
 int emo_accuracy_counts(const float* logits, const int64_t* tgt, const int64_t* chord,
