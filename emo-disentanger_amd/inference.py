@@ -17,8 +17,9 @@ import time
 import numpy as np
 import torch
 
-from . import engine, ops
+from . import engine, ops, scoring
 from ._lib import EmoError
+from .gen_loop import GrammarLoop, check_vocab
 from .replay import StepReplayer, graph_steps
 
 max_dec_inp_len = 2048
@@ -834,8 +835,7 @@ def pack_lead_sheets(lead_sheets):
 def _refuse(model, inadmissibles):
     if inadmissibles is not None:
         raise ValueError('generate_accompaniments: `inadmissibles` is not supported by the device grammar')
-    if model.n_token > 1024:
-        raise EmoError('generate_accompaniments: the device draw takes V <= 1024 (got %d)' % model.n_token)
+    check_vocab('generate_accompaniments', model.n_token)
 
 
 class _GaveUp(Exception):
@@ -852,7 +852,7 @@ def _stream_result(status, ids, out_of_draws, overflow, still_running):
     return EmoError('generate_accompaniments: ' + (out_of_draws if status == ACC_OUT_OF_DRAWS else overflow if status == ACC_OVERFLOW else still_running))
 
 
-class AccompanimentLoop:
+class AccompanimentLoop(GrammarLoop):
     """Device state of generate_accompaniments: the decode engine (prefilled with the common prefix, positions on the device), the logits of
     the last step, the uniform table, the grammar tables, the packed lead sheets, per-stream parameters / state and token / segment rows, and
     the running count; one_step() = emo_grammar_step (kind ACC) + the engine step.  scores=True: the grammar launch also records every accepted
@@ -872,10 +872,9 @@ class AccompanimentLoop:
         dev = self.dev = next(model.parameters()).device
         self.streams = [_Stream(event2idx, lead_sheets[i], primers[i], max_bars) for i in range(n)]
         V = model.n_token
-        flags, beat = acc_event_tables(idx2event, V)
-        self.ev_flags, self.ev_beat = torch.from_numpy(flags).to(dev), torch.from_numpy(beat).to(dev)
+        self._upload_events(*acc_event_tables(idx2event, V))
         toks, offs, bar0, nbars, longest = pack_lead_sheets(lead_sheets)
-        self.lead_tok, self.lead_off = torch.from_numpy(toks).to(dev), torch.from_numpy(offs).to(dev)
+        self.lead_tok, self.lead_off = self._to_device(toks, offs)
         self.track_full, self.pad = event2idx['Track_Full'], event2idx.get('PAD_None', 0)
         self.longest_bar = longest
         lens = [len(s.generated) for s in self.streams]
@@ -890,21 +889,16 @@ class AccompanimentLoop:
                                                                                                             bar0[i], nbars[i])
             state[i, [ACC_S_STATUS, ACC_S_LEN, ACC_S_CONSUMED]] = (ACC_DONE if s.done else ACC_RUNNING), lens[i], self.L0
         self.len0 = np.array(lens)
-        self.seq, self.segs, self.params, self.state = (torch.from_numpy(a).to(dev) for a in (seq, segs, params, state))
+        self.seq, self.segs, self.params, self.state = self._to_device(seq, segs, params, state)
         self.running = torch.tensor([int((state[:, ACC_S_STATUS] == ACC_RUNNING).sum())], dtype=torch.int32, device=dev)
         self.U = uniform_table(int(n_u or 4 * self.W), n, seed, dev)
         self.tok = torch.zeros(n, dtype=torch.int64, device=dev)
         self.segv = torch.ones(n, dtype=torch.int64, device=dev)
         self.logits = torch.empty(n, V, dtype=torch.float32, device=dev)
-        # the grammar launch's argument block (emo_hip.h: emo_grammar_step_t), written once: _gheld keeps what its addresses point to alive
-        self._gargs, self._gheld = ops.GrammarStep(kind=ops.GRAMMAR_ACC), {}
-        ops.block_set(self._gargs, self._gheld, n_rows=n, n_token=V, ld_u=n, temperature=self.temp, top_p=self.top_p, max_len=self.W,
-                      track_full=self.track_full, pad=self.pad, logits=self.logits, u_steps=self.U, ev_flags=self.ev_flags, ev_beat=self.ev_beat,
-                      lead_tok=self.lead_tok, lead_off=self.lead_off, params=self.params, state=self.state, seq=self.seq, segs=self.segs,
-                      tok_out=self.tok, seg_out=self.segv, running=self.running)
-        self.score_tables = ops.draw_score_tables(self.seq) if scores else None
-        if scores:
-            ops.block_set(self._gargs, self._gheld, **self.score_tables)
+        self._build_block(ops.GRAMMAR_ACC, scores, n_rows=n, n_token=V, ld_u=n, temperature=self.temp, top_p=self.top_p, max_len=self.W,
+                          track_full=self.track_full, pad=self.pad, logits=self.logits, u_steps=self.U, ev_flags=self.ev_flags,
+                          ev_beat=self.ev_beat, lead_tok=self.lead_tok, lead_off=self.lead_off, params=self.params, state=self.state, seq=self.seq,
+                          segs=self.segs, tok_out=self.tok, seg_out=self.segv, running=self.running)
         self.windowed = None
         with torch.no_grad():
             if model.kind == 'performer':
@@ -919,10 +913,6 @@ class AccompanimentLoop:
         pe = model.pe.pe.shape[0] if model.use_pe else self.W
         self.bound = min(self.W, pe)           # the engine never runs a step at a position >= bound (the one-launch GPT-2 step would clamp it)
         self.pos = self.L0                     # host count of the engine position (every row advances one per step)
-        self.replayed = (0, 0.0)
-
-    def grammar(self):
-        ops.grammar_step(self._gargs)
 
     def one_step(self):
         self.grammar()
@@ -941,12 +931,8 @@ class AccompanimentLoop:
         """Steps until every stream has left RUNNING; the running count is read once per replay (per step without graphs).  A k-step replay
         runs only while it keeps the position below `bound`; at the bound one more grammar step runs alone (a stream still running there
         reaches the window in it)."""
-        # (the replayer holds graph / graph_k / stream of this run and goes with it: kept on the loop it would close a reference cycle through
-        # one_step, and graphs freed by the cycle collector can be freed in the middle of a later capture)
-        rp = StepReplayer(self.one_step, self.dev, steps_per_graph)
         with torch.no_grad():
-            self.pos = rp.run(self.pos, self.bound, live=self._live, use_graph=use_graph)
-            self.replayed = rp.replayed      # (steps, seconds) of the replays (the last poll synchronised)
+            self.pos = self._replay(self.pos, self.bound, use_graph, steps_per_graph)
             if self._live() > 0:
                 self.grammar()
             torch.cuda.synchronize()
@@ -1004,12 +990,10 @@ class AccompanimentLoop:
         """-> per stream, aligned with `results` (what results() returned): {'logp', 'rank', 'entropy'} numpy arrays with one entry per id of
         the stream's result (NaN / -1 where the id was given, and from the hand-off on where the host finished the stream), or None where the
         result is an error.  Needs scores=True."""
-        if self.score_tables is None:
-            raise EmoError('AccompanimentLoop.scores(): the loop was built without scores=True')
-        own = {k: self.score_tables['tok_' + k].cpu().numpy() for k in ('logp', 'rank', 'entropy')}
+        own = self.score_arrays()
         past, at = own, {}
         if self.windowed is not None and self.windowed.score_tables is not None:
-            past = {k: self.windowed.score_tables['tok_' + k].cpu().numpy() for k in ('logp', 'rank', 'entropy')}
+            past = self.windowed.score_arrays()
             at = {i: j for j, i in enumerate(self.windowed.idx)}
         out = []
         for i, ids in enumerate(results):
@@ -1038,7 +1022,7 @@ def window_compaction(live):
     return keep if 2 * len(keep) <= len(live) else list(range(len(live)))
 
 
-class WindowedLoop:
+class WindowedLoop(GrammarLoop):
     """The ACC_WINDOW streams of a finished AccompanimentLoop, continued together on the device (the reference's sliding window, inference.py
     :252-277, which _resume_windowed runs one stream and one host round trip at a time).  One step = one forward over the streams' last W tokens,
     model(win_tok, seg_inp=win_seg, keep_last_only=True) on [m, W] — positions restart at 0, so nothing carries over between steps — and
@@ -1066,12 +1050,6 @@ class WindowedLoop:
         self.seq = torch.zeros(m0, width, dtype=torch.int64, device=dev)
         self.segs = torch.zeros(m0, width, dtype=torch.int64, device=dev)
         self.seq[:, :w0], self.segs[:, :w0] = loop.seq[sel], loop.segs[sel]
-        # the first loop's recorded draws travel with the token rows; the windowed launch goes on recording behind them
-        self.score_tables = None
-        if loop.score_tables is not None:
-            self.score_tables = ops.draw_score_tables(self.seq)
-            for k, t in self.score_tables.items():
-                t[:, :w0] = loop.score_tables[k][sel]
         self.params = loop.params[sel].contiguous()
         self.state = loop.state[sel].contiguous()
         self.state[:, ACC_S_STATUS] = ACC_RUNNING
@@ -1086,14 +1064,14 @@ class WindowedLoop:
         self.logits = torch.zeros(m0, self.model.n_token, dtype=torch.float32, device=dev)
         self.fwd_kw = {'attn_kwargs': {'omit_feature_map_draw': True}} if self.model.kind == 'performer' else {}
         self.batch_rows, self.steps, self.seconds = [], 0, 0.0
-        # the windowed step's argument block (emo_hip.h: emo_grammar_step_t), written once for the full batch; _set_rows keeps n_rows / rows current
-        self._gargs, self._gheld = ops.GrammarStep(kind=ops.GRAMMAR_ACC_WINDOW), {}
-        ops.block_set(self._gargs, self._gheld, n_rows=m0, n_token=self.model.n_token, ld_u=m0, temperature=self.temp, top_p=self.top_p, window=W,
-                      track_full=loop.track_full, logits=self.logits, u_steps=self.U, ev_flags=loop.ev_flags, ev_beat=loop.ev_beat,
-                      lead_tok=loop.lead_tok, lead_off=loop.lead_off, params=self.params, state=self.state, seq=self.seq, segs=self.segs, win_tok=self.win_tok,
-                      win_seg=self.win_seg, running=self.running)
-        if self.score_tables is not None:
-            ops.block_set(self._gargs, self._gheld, **self.score_tables)
+        # the windowed step's block, written once for the full batch; _set_rows keeps n_rows / rows current
+        self._build_block(ops.GRAMMAR_ACC_WINDOW, loop.score_tables is not None, n_rows=m0, n_token=self.model.n_token, ld_u=m0,
+                          temperature=self.temp, top_p=self.top_p, window=W, track_full=loop.track_full, logits=self.logits, u_steps=self.U,
+                          ev_flags=loop.ev_flags, ev_beat=loop.ev_beat, lead_tok=loop.lead_tok, lead_off=loop.lead_off, params=self.params,
+                          state=self.state, seq=self.seq, segs=self.segs, win_tok=self.win_tok, win_seg=self.win_seg, running=self.running)
+        # the first loop's recorded draws travel with the token rows; the windowed launch goes on recording behind them
+        for k, t in (self.score_tables or {}).items():
+            t[:, :w0] = loop.score_tables[k][sel]
         self._set_rows(list(range(m0)))
 
     def _set_rows(self, rows):
@@ -1130,19 +1108,14 @@ class WindowedLoop:
 
     def run(self, max_steps=None):
         """Steps until no stream is RUNNING (or `max_steps` steps have run: benchmarks), polling every k steps."""
-        was_training = self.model.training
-        self.model.eval()
         t0 = time.perf_counter()
-        try:
-            with torch.no_grad():
-                while max_steps is None or self.steps < max_steps:
-                    for _ in range(self.k if max_steps is None else min(self.k, max_steps - self.steps)):
-                        self.one_step()
-                    if self.poll() == 0:
-                        break
-                torch.cuda.synchronize()
-        finally:
-            self.model.train(was_training)
+        with scoring.eval_mode(self.model), torch.no_grad():
+            while max_steps is None or self.steps < max_steps:
+                for _ in range(self.k if max_steps is None else min(self.k, max_steps - self.steps)):
+                    self.one_step()
+                if self.poll() == 0:
+                    break
+            torch.cuda.synchronize()
         self.seconds += time.perf_counter() - t0
 
     def accepted_draws(self):
@@ -1197,22 +1170,10 @@ def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, m
     if window not in ('host', 'device'):
         raise ValueError("window must be 'host' or 'device' (got %r)" % (window,))
     _refuse(model, inadmissibles)
-    best_of = int(best_of)
-    if best_of < 1:
-        raise ValueError('best_of must be at least 1')
-    from . import scoring
-    scoring.check_best_by(best_by)
-    by_draws = best_of > 1 and best_by == 'draws'
-    want = return_scores or by_draws
-    n_sheets = len(lead_sheets)
-    if best_of > 1:
-        lead_sheets = [ls for ls in lead_sheets for _ in range(best_of)]
-        primers = [p for p in primers for _ in range(best_of)]
-    was_training = model.training
-    model.eval()
+    best_of, by_draws, want, lead_sheets, primers = scoring.best_of_plan(best_of, best_by, return_scores, lead_sheets, primers)
     t0 = time.time()
     kw = dict(max_events=max_events, skip_check=skip_check, max_bars=max_bars, temp=temp, top_p=top_p, seed=seed)
-    try:
+    with scoring.eval_mode(model):
         loop = AccompanimentLoop(model, event2idx, idx2event, lead_sheets, primers, scores=want, **kw)
         try:
             loop.run(use_graph=use_graph)
@@ -1222,19 +1183,11 @@ def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, m
             loop.run(use_graph=use_graph)
         out = loop.results(event2idx, idx2event, max_events, skip_check, seed, window=window)
         sc = loop.scores(out) if want else None
+        picks = None
         if best_of > 1:
             nll = scoring.draw_scores_mean(sc) if by_draws else scoring.candidate_scores(model, event2idx, out, loop.bound)
-            picks = []
-            for i in range(n_sheets):
-                sl = slice(i * best_of, (i + 1) * best_of)
-                picks.append({'chosen': scoring.best_of(nll[sl]), 'nll_mean': nll[sl], 'candidates': out[sl]})
-                if return_scores:
-                    picks[-1]['scores'] = sc[sl]
-            res = [p['candidates'][p['chosen']] for p in picks], time.time() - t0, picks
-            return res + ([p['scores'][p['chosen']] for p in picks],) if return_scores else res
-    finally:
-        model.train(was_training)
-    return (out, time.time() - t0, sc) if return_scores else (out, time.time() - t0)
+            picks = scoring.picks_of(out, nll, best_of, sc if return_scores else None)
+    return scoring.generation_result(out, time.time() - t0, sc, picks, return_scores)
 
 
 # ------------------------------------------------------------------------------------------------ command line (reference inference.py:330-485)
@@ -1338,7 +1291,6 @@ def main(argv=None):
             gen = generate_conditional_batch(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
                                              temp=temp, top_p=top_p, seeds=list(range(i, i + len(group))))
         if want:
-            from . import scoring
             score_pieces += scoring.draw_pieces([os.path.basename(g[0]) for g in group], gen, sc[0])
         for (out, key, _, _), ids in zip(group, gen):
             if isinstance(ids, Exception):
@@ -1348,7 +1300,6 @@ def main(argv=None):
                 fh.write('\n'.join([key] + [idx2event[w] for w in ids]) + '\n')
             print('[info] wrote', out, len(ids), 'events')
     if want:
-        from . import scoring
         scoring.write_draw_scores(args.scores, score_pieces)
         print('[info] wrote', args.scores, len(score_pieces), 'records')
     try:

@@ -1,5 +1,5 @@
-"""The hipGraph replay driver of the device generation loops (generate_streams, AccompanimentLoop, LeadSheetLoop): no model knowledge, only
-`one_step` — a callable that queues ONE token step whose loop state lives on the device, so that a captured graph continues wherever the
+"""The hipGraph replay driver of the device generation loops (generate_streams, and gen_loop.GrammarLoop._replay for LeadSheetLoop,
+LeadSheetQueue and AccompanimentLoop): no model or grammar knowledge, only `one_step` — a callable that queues ONE token step whose loop state lives on the device, so that a captured graph continues wherever the
 streams are.  A replay costs the device a fixed ~10 us of idle time whatever it holds, so k token steps per replay amortise it (r04:
 EMO_GEN_GRAPH_STEPS, default 16); the one-step graph serves the remainder."""
 import os

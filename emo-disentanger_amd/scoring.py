@@ -4,6 +4,7 @@ Stage-1 lead sheets (the Transformer-XL model) are scored by score_lead_sheet_to
 
 The reference has no scoring tool; what is scored is exactly what its training loss sees — the targets `EventPieceDataset._targets`
 builds (stage2_accompaniment/dataloader.py:127-143: only the tokens inside Track_Full spans are predicted, everything else is pad)."""
+import contextlib
 import json
 import math
 import os
@@ -36,20 +37,15 @@ def score_tokens(model, dec_input, dec_target, seg_inp=None, want=WANT, pad_toke
     if unknown:
         raise ValueError('score_tokens: unknown output(s) %s (known: %s)' % (sorted(unknown), ', '.join(WANT)))
     pad = model.n_token - 1 if pad_token is None else int(pad_token)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            logits = model(dec_input, seg_inp=seg_inp)
-            V = logits.shape[-1]
-            l2 = engine.padded_logits(logits)
-            if l2 is None:
-                l2 = logits.reshape(-1, V)
-            tgt = dec_target.long().reshape(-1)
-            engine.check_ids(tgt, V, 'scoring targets', also=pad)
-            out = ops.token_scores(l2, tgt, pad, V=V, want=tuple(k for k in ('rank', 'entropy') if k in want))
-    finally:
-        model.train(was_training)
+    with eval_mode(model), torch.no_grad():
+        logits = model(dec_input, seg_inp=seg_inp)
+        V = logits.shape[-1]
+        l2 = engine.padded_logits(logits)
+        if l2 is None:
+            l2 = logits.reshape(-1, V)
+        tgt = dec_target.long().reshape(-1)
+        engine.check_ids(tgt, V, 'scoring targets', also=pad)
+        out = ops.token_scores(l2, tgt, pad, V=V, want=tuple(k for k in ('rank', 'entropy') if k in want))
     shape = dec_target.shape
     return TokenScores(out['nll'].neg().view(shape) if 'logprob' in want else None,
                        out['rank'].view(shape) if 'rank' in want else None,
@@ -183,6 +179,9 @@ def best_of(scores):
     return arg
 
 
+_lowest = best_of                       # (for picks_of, whose argument takes the name)
+
+
 # ------------------------------------------------------------------------------------------------ scores recorded at the draw
 BEST_BY = ('forward', 'draws')
 
@@ -190,6 +189,52 @@ BEST_BY = ('forward', 'draws')
 def check_best_by(best_by):
     if best_by not in BEST_BY:
         raise ValueError('best_by must be one of %s (got %r)' % (', '.join(repr(b) for b in BEST_BY), best_by))
+
+
+# ------------------------------------------------------------------------------------------------ the best-of tail of the two generators
+def best_of_plan(best_of, best_by, return_scores, *per_input):
+    """The checks and the bookkeeping of generate_*(best_of=N, best_by=..., return_scores=...) -> (N, by_draws: the candidates are ranked by
+    their recorded draws, want_scores: the loop has to record them, then every list of `per_input` with each entry N times in a row:
+    candidate c of input i is entry i * N + c)."""
+    n = int(best_of)
+    if n < 1:
+        raise ValueError('best_of must be at least 1')
+    check_best_by(best_by)
+    by_draws = n > 1 and best_by == 'draws'
+    return (n, by_draws, bool(return_scores or by_draws)) + tuple([x for x in v for _ in range(n)] for v in per_input)
+
+
+@contextlib.contextmanager
+def eval_mode(model):
+    """The model in eval mode for the block; the mode it was in comes back at the end, also when the block raises."""
+    was_training = model.training
+    model.eval()
+    try:
+        yield
+    finally:
+        model.train(was_training)
+
+
+def picks_of(results, nll, best_of, scores=None):
+    """The picks of generate_*(best_of=N): candidates i * N .. i * N + N - 1 belong to input i -> per input {'chosen': the index best_of() gives
+    for its N nll_mean (the lowest; ties -> the lowest index; a NaN never wins), 'nll_mean', 'candidates'[, 'scores': the N candidates' of
+    `scores`]}."""
+    picks, n = [], best_of
+    for i in range(len(results) // n):
+        sl = slice(i * n, (i + 1) * n)
+        picks.append({'chosen': _lowest(nll[sl]),'nll_mean': nll[sl], 'candidates': results[sl]})
+        if scores is not None:
+            picks[-1]['scores'] = scores[sl]
+    return picks
+
+
+def generation_result(results, seconds, scores, picks, return_scores):
+    """What generate_lead_sheets / generate_accompaniments return.  picks None (best_of = 1): (results, seconds[, scores]); else (the chosen
+    candidates, seconds, picks[, the chosen candidates' scores]); the last element only with return_scores."""
+    if picks is None:
+        return (results, seconds, scores) if return_scores else (results, seconds)
+    chosen = [p['candidates'][p['chosen']] for p in picks], seconds, picks
+    return chosen + ([p['scores'][p['chosen']] for p in picks],) if return_scores else chosen
 
 
 def drawn_mask(logp, rank):
@@ -285,16 +330,11 @@ def score_lead_sheet_tokens(model, tokens, lengths, primer_len, window=None):
     pad = model.n_token - 1
     tokens = tokens.long()
     tgt = lead_sheet_targets(tokens, lengths, primer_len, pad)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            engine.check_ids(tokens, model.n_token, 'lead-sheet tokens')
-            logits = model.forward_windowed(tokens.t(), window)           # [T, B, V]: the permuted view of the projection's [B * T, V] rows
-            V = logits.shape[-1]
-            out = ops.token_scores(logits.permute(1, 0, 2).reshape(-1, V), tgt.reshape(-1), pad, V=V, want=('rank', 'entropy'))
-    finally:
-        model.train(was_training)
+    with eval_mode(model), torch.no_grad():
+        engine.check_ids(tokens, model.n_token, 'lead-sheet tokens')
+        logits = model.forward_windowed(tokens.t(), window)               # [T, B, V]: the permuted view of the projection's [B * T, V] rows
+        V = logits.shape[-1]
+        out = ops.token_scores(logits.permute(1, 0, 2).reshape(-1, V), tgt.reshape(-1), pad, V=V, want=('rank', 'entropy'))
     shape = tgt.shape
     return TokenScores(out['nll'].neg().view(shape), out['rank'].view(shape), out['entropy'].view(shape), tgt != pad)
 

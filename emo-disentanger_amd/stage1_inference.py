@@ -12,10 +12,10 @@ import time
 import numpy as np
 import torch
 
-from . import ops, sampling
+from . import ops, sampling, scoring
 from ._lib import EmoError
+from .gen_loop import GrammarLoop, check_vocab
 from .inference import _EngineBase, uniform_table
-from .replay import StepReplayer
 from .sampling import beat_position, event_name, nucleus  # noqa: F401  (`nucleus` is looked up at call time: tests wrap it)
 
 SHARP_NAMES = ('C', 'C#', 'D', 'D#', 'E', 'F', 'F#', 'G', 'G#', 'A', 'A#', 'B')     # pitch-class spelling of convert_key.py:14-15
@@ -342,7 +342,7 @@ class OneLaunchStep(_EngineBase):
         return self._step_persistent(tok.reshape(-1), None, True, logits_out)
 
 
-class LeadSheetLoop:
+class LeadSheetLoop(GrammarLoop):
     """Device state of generate_lead_sheets: a TXLMemory, the logits of the last step, the uniform table, the grammar tables and
     per-stream parameters / state, the output sequences and the running count; one_step() = emo_grammar_step (kind TXL) + decode_step
     (step='chain') or + emo_decode_step, form 2 (step='one_launch': OneLaunchStep on the head-major copy of the prefill's memory).
@@ -352,56 +352,62 @@ class LeadSheetLoop:
     def __init__(self, model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
                  representation='functional', key_determine=None, seed=0, step='chain', scores=False):
         from .model.plain_transformer import TXLMemory
-        n = self.n = len(primers)
-        assert n > 0
-        if step not in STEPS:
-            raise ValueError("step must be one of %s (got %r)" % (', '.join(repr(s) for s in STEPS), step))
-        if step == 'one_launch':                                     # refused before anything is allocated; never a silent fall-back to the chain
-            why = one_launch_unsupported(model, n)
-            if why is not None:
-                raise EmoError("step='one_launch' (emo_decode_step[txl]) needs %s; use step='chain'" % why)
-        kw = _per_stream(n, max_bars=max_bars, max_events=max_events, prompt_bars=prompt_bars, representation=representation, key_determine=key_determine)
-        self.model, self.temp, self.top_p = model, float(temp), float(top_p)
-        dev = self.dev = next(model.parameters()).device
-        plens, seq, params, state = self._job_tables(model, event2idx, idx2event, primers, kw)
-        V = model.vocab_size
+        self._check_step(model, len(primers), step)
+        plens = self._load_jobs(model, event2idx, idx2event, primers, temp, top_p, None, max_bars=max_bars, max_events=max_events,
+                                prompt_bars=prompt_bars, representation=representation, key_determine=key_determine)
+        n, L0 = self.n, min(plens)
         self.mem = TXLMemory(model, n, model._max_gen_len)
-        self.max_len = self.mem.max_len
-        self.L0 = min(plens)
-        state[:, S_FEED] = self.L0
-        self.seq, self.params, self.state = (torch.from_numpy(a).to(dev) for a in (seq, params, state))
-        self.running = torch.tensor([int((state[:, S_STATUS] == RUNNING).sum())], dtype=torch.int32, device=dev)
-        self.U = uniform_table(self.max_len - self.L0 + 1, n, seed, dev)      # at most one draw per step, one more at the end
-        self.tok = self.seq[:, self.L0 - 1].contiguous()      # (a valid id in every row before the first grammar step)
-        self.logits = torch.empty(n, V, dtype=torch.float32, device=dev)
-        # the grammar launch's argument block (emo_hip.h: emo_grammar_step_t), written once: _gheld keeps what its addresses point to alive
-        self._gargs, self._gheld = ops.GrammarStep(kind=ops.GRAMMAR_TXL), {}
-        ops.block_set(self._gargs, self._gheld, n_rows=n, n_token=V, ld_u=n, temperature=self.temp, top_p=self.top_p, key_temperature=KEY_TEMP,
-                      key_top_p=KEY_TOP_P, logits=self.logits, u_steps=self.U, ev_flags=self.ev_flags, ev_beat=self.ev_beat, params=self.params,
-                      state=self.state, seq=self.seq, tok_out=self.tok, running=self.running)
-        self.score_tables = ops.draw_score_tables(self.seq) if scores else None
-        if scores:
-            ops.block_set(self._gargs, self._gheld, **self.score_tables)
+        self.max_len, self.L0 = self.mem.max_len, L0
+        self.U = uniform_table(self.max_len - L0 + 1, n, seed, self.dev)      # at most one draw per step, one more at the end
+        self.tok = self.seq[:, L0 - 1].contiguous()           # (a valid id in every row before the first grammar step)
+        self.logits = torch.empty(n, model.vocab_size, dtype=torch.float32, device=self.dev)
+        self._build_block(ops.GRAMMAR_TXL, scores, **self._block_fields(n))
         with torch.no_grad():
-            h, _, _ = model._prefill(self.seq[:, :self.L0].t(), self.mem)
-            self.logits.copy_(model._logits(h.view(n, self.L0, -1)[:, -1].contiguous()))
+            h, _, _ = model._prefill(self.seq[:, :L0].t(), self.mem)
+            self.logits.copy_(model._logits(h.view(n, L0, -1)[:, -1].contiguous()))
         self.stepper = None
         if step == 'one_launch':
-            self.stepper = OneLaunchStep(model, n, self.max_len, r_dist=self.mem.r_dist).take_over(self.mem, self.L0)
+            self.stepper = OneLaunchStep(model, n, self.max_len, r_dist=self.mem.r_dist).take_over(self.mem, L0)
             self.mem = self.stepper.mem                              # (the token-major prefill memory goes)
-        self.pos = self.L0                   # positions in the memory (host count: every row advances one per step)
-        self.replayed = (0, 0.0)
+        self.pos = L0                        # positions in the memory (host count: every row advances one per step)
+
+    @staticmethod
+    def _check_step(model, rows, step):
+        """The refusals of `step` for a model batch of `rows` rows, before anything is allocated; never a silent fall-back to the chain."""
+        if step not in STEPS:
+            raise ValueError("step must be one of %s (got %r)" % (', '.join(repr(s) for s in STEPS), step))
+        if step == 'one_launch':
+            why = one_launch_unsupported(model, rows)
+            if why is not None:
+                raise EmoError("step='one_launch' (emo_decode_step[txl]) needs %s; use step='chain'" % why)
+
+    def _load_jobs(self, model, event2idx, idx2event, primers, temp, top_p, feed, **per_stream):
+        """n, model, dev and the draw parameters; the jobs' tables (_job_tables) on the device as seq / params / state, state[FEED] = `feed`
+        (None: the shortest primer's length, the prefix a prefill takes); the running count.  -> the primer lengths."""
+        n = self.n = len(primers)
+        assert n > 0
+        kw = _per_stream(n, **per_stream)
+        self.model, self.temp, self.top_p = model, float(temp), float(top_p)
+        self.dev = next(model.parameters()).device
+        plens, seq, params, state = self._job_tables(model, event2idx, idx2event, primers, kw)
+        state[:, S_FEED] = min(plens) if feed is None else feed
+        self.seq, self.params, self.state = self._to_device(seq, params, state)
+        self.running = torch.tensor([int((state[:, S_STATUS] == RUNNING).sum())], dtype=torch.int32, device=self.dev)
+        return plens
+
+    def _block_fields(self, rows):
+        """The fields of the grammar launch's block that kinds TXL and TXL_QUEUE share, for a model batch of `rows` rows."""
+        return dict(n_rows=rows, n_token=self.model.vocab_size, ld_u=self.n, temperature=self.temp, top_p=self.top_p, key_temperature=KEY_TEMP,
+                    key_top_p=KEY_TOP_P, logits=self.logits, u_steps=self.U, ev_flags=self.ev_flags, ev_beat=self.ev_beat, params=self.params,
+                    state=self.state, seq=self.seq, tok_out=self.tok, running=self.running)
 
     def _job_tables(self, model, event2idx, idx2event, primers, kw):
         """The grammar tables of the device (self.ev_flags, self.ev_beat) and, per stream, what the grammar launch reads and keeps
         -> (primer lengths, seq int64 [n, width], params, state int32 [n, 8]: numpy, state[FEED] left to the caller)."""
-        n, dev = len(primers), self.dev
+        n = len(primers)
         sheets = [_LeadSheet(event2idx, primers[i], kw[i]['prompt_bars'], kw[i]['max_bars'], kw[i]['max_events']) for i in range(n)]
-        V = model.vocab_size
-        if V > 1024:
-            raise EmoError('generate_lead_sheets: the device draw takes V <= 1024 (got %d)' % V)
-        flags, beat = event_tables(idx2event, V)
-        self.ev_flags, self.ev_beat = torch.from_numpy(flags).to(dev), torch.from_numpy(beat).to(dev)
+        check_vocab('generate_lead_sheets', model.vocab_size)
+        self._upload_events(*event_tables(idx2event, model.vocab_size))
         plens = [len(s.tokens) for s in sheets]
         if min(plens) < 1:
             raise ValueError('generate_lead_sheets: empty primer')
@@ -418,9 +424,6 @@ class LeadSheetLoop:
             state[i, [S_STATUS, S_LEN, S_BARS]] = (RUNNING if s.open() else DONE), plens[i], s.bars
         return plens, seq, params, state
 
-    def grammar(self):
-        ops.grammar_step(self._gargs)
-
     def one_step(self):
         self.grammar()
         if self.stepper is not None:
@@ -428,19 +431,11 @@ class LeadSheetLoop:
         else:
             self.model.decode_step(self.tok, self.mem, logits_out=self.logits)
 
-    def _live(self):
-        """Running count (synchronises)."""
-        return int(self.running.item())
-
     def run(self, use_graph=True, steps_per_graph=None):
         """Steps until every stream is finished or the memory is full; the running count is read once per replay (per step without graphs).
         At the memory's end one more grammar step runs alone: a stream that then still wants a model step would overflow max_gen_len."""
-        # (the replayer holds graph / graph_k / stream of this run and goes with it: kept on the loop it would close a reference cycle through
-        # one_step, and graphs freed by the cycle collector can be freed in the middle of a later capture)
-        rp = StepReplayer(self.one_step, self.dev, steps_per_graph)
         with torch.no_grad():
-            self.pos = rp.run(self.pos, self.max_len, live=self._live, use_graph=use_graph)
-            self.replayed = rp.replayed
+            self.pos = self._replay(self.pos, self.max_len, use_graph, steps_per_graph)
             if self._live() > 0:
                 self.grammar()
             torch.cuda.synchronize()
@@ -466,10 +461,7 @@ class LeadSheetLoop:
     def scores(self):
         """-> per stream, aligned with results(): {'logp', 'rank', 'entropy'} numpy arrays, one entry per id of the stream's result (NaN / -1 at the
         primer's tokens, which were given), or None where the result is not an id list.  Needs scores=True."""
-        if self.score_tables is None:
-            raise EmoError('LeadSheetLoop.scores(): the loop was built without scores=True')
-        state = self.state.cpu().numpy()
-        tabs = {k: self.score_tables['tok_' + k].cpu().numpy() for k in ('logp', 'rank', 'entropy')}
+        tabs, state = self.score_arrays(), self.state.cpu().numpy()
         return [{k: t[i, :int(state[i, S_LEN]) - 1].copy() for k, t in tabs.items()} if int(state[i, S_STATUS]) == DONE else None
                 for i in range(self.n)]
 
@@ -516,54 +508,34 @@ class LeadSheetQueue(LeadSheetLoop):
     def __init__(self, model, event2idx, idx2event, primers, slots, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
                  representation='functional', key_determine=None, seed=0, step='chain', scores=False):
         from .model.plain_transformer import TXLMemory
-        n = self.n = len(primers)
-        assert n > 0
         slots = self.slots = int(slots)
         if slots < 1:
             raise ValueError('slots must be at least 1 (got %d)' % slots)
-        if step not in STEPS:
-            raise ValueError("step must be one of %s (got %r)" % (', '.join(repr(s) for s in STEPS), step))
-        if step == 'one_launch':                                     # refused before anything is allocated; never a silent fall-back to the chain
-            why = one_launch_unsupported(model, slots)
-            if why is not None:
-                raise EmoError("step='one_launch' (emo_decode_step[txl]) needs %s; use step='chain'" % why)
-        kw = _per_stream(n, max_bars=max_bars, max_events=max_events, prompt_bars=prompt_bars, representation=representation, key_determine=key_determine)
-        self.model, self.temp, self.top_p = model, float(temp), float(top_p)
-        dev = self.dev = next(model.parameters()).device
-        _, seq, params, state = self._job_tables(model, event2idx, idx2event, primers, kw)
-        V = model.vocab_size
-        state[:, S_FEED] = 1                                         # (what an admission sets: the first token goes out with it)
-        self.seq, self.params, self.state = (torch.from_numpy(a).to(dev) for a in (seq, params, state))
-        self.running = torch.tensor([int((state[:, S_STATUS] == RUNNING).sum())], dtype=torch.int32, device=dev)
+        self._check_step(model, slots, step)
+        # FEED 1 is what an admission sets: the first token goes out with it
+        self._load_jobs(model, event2idx, idx2event, primers, temp, top_p, 1, max_bars=max_bars, max_events=max_events, prompt_bars=prompt_bars,
+                        representation=representation, key_determine=key_determine)
+        n, dev = self.n, self.dev
         self.stepper = OneLaunchStep(model, slots) if step == 'one_launch' else None
-        self.mem = self.stepper.mem if self.stepper is not None else TXLMemory(model, slots, model._max_gen_len)
-        self.max_len = self.mem.max_len
-        self.U = uniform_table(self.max_len, n, seed, dev)          # a job draws at most once per token of its row
+        mem = self.mem = self.stepper.mem if self.stepper is not None else TXLMemory(model, slots, model._max_gen_len)
+        self.max_len = mem.max_len
+        self.U = uniform_table(mem.max_len, n, seed, dev)            # a job draws at most once per token of its row
         self.tok = self.seq[0, :1].repeat(slots).contiguous()        # (a valid id in every row: a slot that never gets a job feeds it)
-        self.logits = torch.zeros(slots, V, dtype=torch.float32, device=dev)
+        self.logits = torch.zeros(slots, model.vocab_size, dtype=torch.float32, device=dev)
         self.slot_job = torch.full((slots,), -1, dtype=torch.int32, device=dev)
         self.queue_head = torch.zeros(1, dtype=torch.int32, device=dev)
         self.job_steps_dev = torch.zeros(n, dtype=torch.int32, device=dev)
-        self._gargs, self._gheld = ops.GrammarStep(kind=ops.GRAMMAR_TXL_QUEUE), {}
-        ops.block_set(self._gargs, self._gheld, n_rows=slots, n_token=V, ld_u=n, n_jobs=n, mem_rows=self.max_len, temperature=self.temp,
-                      top_p=self.top_p, key_temperature=KEY_TEMP, key_top_p=KEY_TOP_P, logits=self.logits, u_steps=self.U, ev_flags=self.ev_flags,
-                      ev_beat=self.ev_beat, params=self.params, state=self.state, seq=self.seq, tok_out=self.tok, running=self.running,
-                      slot_job=self.slot_job, queue_head=self.queue_head, mem_lens=self.mem.lens, job_steps=self.job_steps_dev)
-        self.score_tables = ops.draw_score_tables(self.seq) if scores else None
-        if scores:
-            ops.block_set(self._gargs, self._gheld, **self.score_tables)
+        self._build_block(ops.GRAMMAR_TXL_QUEUE, scores, n_jobs=n, mem_rows=mem.max_len, slot_job=self.slot_job, queue_head=self.queue_head,
+                          mem_lens=mem.lens, job_steps=self.job_steps_dev, **self._block_fields(slots))
         # no job can outlast its row of the memory, so the queue is drained before this many launches whatever the slots do: a budget for the
         # replayer, not a limit that is meant to bind (the per-job limit is the kernel's MEM_FULL)
-        self.budget = n * self.max_len + 2
+        self.budget = n * mem.max_len + 2
         self.launches = 0
-        self.replayed = (0, 0.0)
 
     def run(self, use_graph=True, steps_per_graph=None):
         """Launches until the running count is 0; it is read once per replay (per step without graphs)."""
-        rp = StepReplayer(self.one_step, self.dev, steps_per_graph)  # (goes with the run: see LeadSheetLoop.run)
         with torch.no_grad():
-            self.launches = rp.run(self.launches, self.budget, live=self._live, use_graph=use_graph)
-            self.replayed = rp.replayed
+            self.launches = self._replay(self.launches, self.budget, use_graph, steps_per_graph)
             torch.cuda.synchronize()
             if self._live() > 0:
                 raise EmoError('LeadSheetQueue: %d jobs still running after %d launches' % (self._live(), self.launches))
@@ -605,57 +577,34 @@ def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max
     and no batch waits for its longest member; step='one_launch' then has to hold for S rows.  A job draws from its own column of the uniform
     table, so its ids do not depend on S or on the slot it ran in beyond what the model step's arithmetic does; they are not those of slots =
     None, whose streams share a prefill.  The results, best_of, best_by and return_scores are per job as they are per stream."""
-    best_of = int(best_of)
-    if best_of < 1:
-        raise ValueError('best_of must be at least 1')
+    # a per-primer list among the arguments is repeated like the primers; a value given once holds for every stream
+    opts = dict(max_bars=max_bars, max_events=max_events, prompt_bars=prompt_bars, representation=representation, key_determine=key_determine)
+    lists = [k for k, v in opts.items() if isinstance(v, (list, tuple)) and len(v) == len(primers)]
+    best_of, by_draws, want, primers, *repeated = scoring.best_of_plan(best_of, best_by, return_scores, primers, *(opts[k] for k in lists))
+    opts.update(zip(lists, repeated))
     if slots is not None:
         slots = int(slots)
         if slots < 1:
             raise ValueError('slots must be at least 1 (got %d)' % slots)
-    from . import scoring
-    scoring.check_best_by(best_by)
-    by_draws = best_of > 1 and best_by == 'draws'
-    n_primers = len(primers)
-    if best_of > 1:
-        rep = lambda v: [x for x in v for _ in range(best_of)] if isinstance(v, (list, tuple)) and len(v) == n_primers else v
-        max_bars, max_events, prompt_bars, representation, key_determine = (rep(v) for v in (max_bars, max_events, prompt_bars, representation,
-                                                                                               key_determine))
-        primers = [p for p in primers for _ in range(best_of)]
-    was_training = model.training
-    model.eval()
     t0 = time.time()
-    try:
-        kw = dict(max_bars=max_bars, max_events=max_events, temp=temp, top_p=top_p, prompt_bars=prompt_bars, representation=representation,
-                  key_determine=key_determine, seed=seed, step=step, scores=return_scores or by_draws)
-        loop = (LeadSheetLoop(model, event2idx, idx2event, primers, **kw) if slots is None else
-                LeadSheetQueue(model, event2idx, idx2event, primers, slots, **kw))
+    with scoring.eval_mode(model):
+        opts.update(temp=temp, top_p=top_p, seed=seed, step=step, scores=want)
+        loop = (LeadSheetLoop(model, event2idx, idx2event, primers, **opts) if slots is None else
+                LeadSheetQueue(model, event2idx, idx2event, primers, slots, **opts))
         loop.run(use_graph=use_graph)
         out = loop.results()
-        sc = loop.scores() if return_scores or by_draws else None
+        sc = loop.scores() if want else None
+        picks = None
         if best_of > 1:
-            picks = pick_best(model, out, loop.params.cpu().numpy()[:, P_PRIMER_LEN].tolist(), best_of,
-                              scorer=(lambda m, cands, plens: scoring.draw_scores_mean(sc)) if by_draws else None)
-            res = [p['candidates'][p['chosen']] for p in picks], time.time() - t0, picks
-            if return_scores:
-                for i, p in enumerate(picks):
-                    p['scores'] = sc[i * best_of:(i + 1) * best_of]
-                res += ([p['scores'][p['chosen']] for p in picks],)
-            return res
-    finally:
-        model.train(was_training)
-    return (out, time.time() - t0, sc) if return_scores else (out, time.time() - t0)
+            nll = scoring.draw_scores_mean(sc) if by_draws else scoring.lead_sheet_candidate_scores(model, out, loop.params.cpu().numpy()[:, P_PRIMER_LEN].tolist())
+            picks = scoring.picks_of(out, nll, best_of, sc if return_scores else None)
+    return scoring.generation_result(out, time.time() - t0, sc, picks, return_scores)
 
 
 def pick_best(model, candidates, primer_lens, best_of, scorer=None):
     """The picks of generate_lead_sheets(best_of=N): candidates i * N .. i * N + N - 1 belong to primer i.  scorer: a stand-in for
     scoring.lead_sheet_candidate_scores (model, candidates, primer_lens) -> nll_mean per candidate."""
-    from . import scoring
-    nll = (scorer or scoring.lead_sheet_candidate_scores)(model, candidates, primer_lens)
-    picks = []
-    for i in range(len(candidates) // best_of):
-        sl = slice(i * best_of, (i + 1) * best_of)
-        picks.append({'chosen': scoring.best_of(nll[sl]), 'nll_mean': nll[sl], 'candidates': candidates[sl]})
-    return picks
+    return scoring.picks_of(candidates, (scorer or scoring.lead_sheet_candidate_scores)(model, candidates, primer_lens), best_of)
 
 
 # ------------------------------------------------------------------------------------------------ command line (reference stage1_compose/inference.py:86-298)
@@ -769,7 +718,6 @@ def main(argv=None):
                                                  return_scores=want, slots=args.slots, **kw)
         times.append(sec)
         if want:
-            from . import scoring
             score_pieces += scoring.draw_pieces([os.path.basename(out) for out, _ in group], res, sc[0])
         for (out, _), ids in zip(group, res):
             if ids is None or isinstance(ids, Exception):
@@ -779,7 +727,6 @@ def main(argv=None):
                 fh.write('\n'.join(idx2event[w] for w in ids[1:]) + '\n')
             print('[info] wrote', out, len(ids) - 1, 'events')
     if want:
-        from . import scoring
         scoring.write_draw_scores(args.scores, score_pieces)
         print('[info] wrote', args.scores, len(score_pieces), 'records')
     print('[info] finished {} jobs in {:.2f} s'.format(len(jobs), sum(times)))
