@@ -42,17 +42,17 @@ class DecodeStep(ctypes.Structure):
 
 
 class GrammarStep(ctypes.Structure):
-    """emo_grammar_step_t (emo_hip.h), field for field: the argument block of the four device grammar steps.  Pointer fields hold raw device addresses."""
+    """emo_grammar_step_t (emo_hip.h), field for field: the argument block of the five device grammar steps.  Pointer fields hold raw device addresses."""
     _fields_ = [('kind', ctypes.c_int32), ('n_rows', c_l), ('logits', c_p), ('n_token', c_l), ('temperature', c_f), ('top_p', c_f),
                 ('u_steps', c_p), ('n_u', c_l), ('ld_u', c_l), ('ev_flags', c_p), ('ev_beat', c_p), ('params', c_p), ('state', c_p),
                 ('seq', c_p), ('ld_seq', c_l), ('running', c_p),
                 ('key_temperature', c_f), ('key_top_p', c_f), ('tok_out', c_p), ('seg_out', c_p), ('max_len', c_l), ('pad', c_l),
                 ('segs', c_p), ('lead_tok', c_p), ('lead_off', c_p), ('track_full', c_l), ('window', c_l), ('rows', c_p), ('win_tok', c_p), ('win_seg', c_p),
-                ('slot_job', c_p), ('queue_head', c_p), ('n_jobs', c_l), ('mem_lens', c_p), ('mem_rows', c_l), ('job_steps', c_p),
+                ('slot_job', c_p), ('queue_head', c_p), ('n_jobs', c_l), ('mem_lens', c_p), ('mem_rows', c_l), ('job_steps', c_p), ('row_reset', c_p),
                 ('tok_logp', c_p), ('tok_rank', c_p), ('tok_entropy', c_p)]
 
 
-GRAMMAR_TXL, GRAMMAR_ACC, GRAMMAR_ACC_WINDOW, GRAMMAR_TXL_QUEUE = 0, 1, 2, 3      # emo_hip.h: EMO_GRAMMAR_*
+GRAMMAR_TXL, GRAMMAR_ACC, GRAMMAR_ACC_WINDOW, GRAMMAR_TXL_QUEUE, GRAMMAR_ACC_QUEUE = 0, 1, 2, 3, 4      # emo_hip.h: EMO_GRAMMAR_*
 
 
 class Attn(ctypes.Structure):
@@ -99,6 +99,7 @@ _SIG = {
     'emo_decode_step_supported': (c_i, []),
     'emo_decode_step': (c_i, [ctypes.POINTER(DecodeStep), c_p]),
     'emo_favor_draw_omega': (c_i, [c_p, c_p, c_l, c_l, c_l, c_p]),
+    'emo_favor_state_reset': (c_i, [c_p, c_l, c_l, c_l, c_l, c_p, c_p]),
     'emo_softmax_attn_keep_bytes': (c_l, [c_i, c_l, c_l, c_l, c_l, c_f]),
     'emo_relpos_attn_bwd_r_workspace_bytes': (c_l, [c_l, c_l, c_l, c_l]),
     'emo_xent_fwd': (c_i, [c_p, c_p, c_l, c_l, c_l, c_p, c_p, c_p]),

@@ -1090,6 +1090,25 @@ __global__ __launch_bounds__(256) void favor_decode_kernel(const CT* __restrict_
     }
 }
 
+// Restart of decode rows (emo_favor_state_reset): workgroup (row, layer, chunk) zeroes chunk `chunk` (FAVOR_RESET_CHUNK floats) of the row's state in
+// the layer, S [s_row floats] followed by z [z_row floats], when row_reset[row] is set, and leaves at once otherwise: a launch in which no row is
+// flagged reads one word per workgroup and writes nothing.  table: [layer][2] = the layer's S and z base pointers; s_row, z_row: multiples of 4.
+constexpr int FAVOR_RESET_CHUNK = 4096;
+__global__ __launch_bounds__(256) void favor_state_reset_kernel(const void* const* __restrict__ table, int64_t s_row, int64_t z_row,
+                                                                const int32_t* __restrict__ row_reset) {
+    const int64_t row = blockIdx.x, layer = blockIdx.y;
+    if (row_reset[row] == 0) return;
+    float4* S = (float4*)((float*)table[2 * layer] + row * s_row);
+    float4* z = (float4*)((float*)table[2 * layer + 1] + row * z_row);
+    const int64_t s4 = s_row / 4, all4 = s4 + z_row / 4, base = (int64_t)blockIdx.z * (FAVOR_RESET_CHUNK / 4);
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = threadIdx.x; i < FAVOR_RESET_CHUNK / 4; i += 256) {
+        const int64_t e = base + i;
+        if (e < s4) S[e] = zero;
+        else if (e < all4) z[e - s4] = zero;
+    }
+}
+
 // Compile-time (dh, mf) variant of the decode step: the whole state slice of the block (F x dh fp32 = 32 KB at 128 x 64) is requested
 // with 16-B loads BEFORE the feature phase, so the HBM round trip overlaps the phi(q), phi(k) computation; everything is unrolled
 // (r01: the generic kernel took 18 us per layer for 16.8 MB of state traffic = 0.9 TB/s, latency-bound on 32 dependent 4-B accesses).
@@ -1442,6 +1461,19 @@ static int favor_decode(const emo_attn_t& a, hipStream_t st) {
     else
         hipLaunchKernelGGL(favor_decode_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)a.q, (const bf16_t*)a.k, (const bf16_t*)a.v, a.ld, a.omega, a.state_S,
                            a.state_z, (bf16_t*)a.out, a.ld_out, a.H, (int)a.dh, (int)(a.n_feat / 2), a.eps);
+    EMO_LAUNCH_CHECK();
+    return EMO_OK;
+}
+
+extern "C" int emo_favor_state_reset(const void* state_table, int64_t n_layers, int64_t n_rows, int64_t s_row_floats, int64_t z_row_floats,
+                                     const int32_t* row_reset, emo_stream_t stream) {
+    EMO_CHECK(state_table && row_reset, "emo_favor_state_reset: null pointer");
+    EMO_CHECK(n_layers > 0 && n_rows > 0 && s_row_floats > 0 && z_row_floats > 0, "emo_favor_state_reset: bad sizes");
+    EMO_CHECK(s_row_floats % 4 == 0 && z_row_floats % 4 == 0, "emo_favor_state_reset: the rows of S and z must be multiples of 4 floats (16-byte stores)");
+    const int64_t chunks = (s_row_floats + z_row_floats + FAVOR_RESET_CHUNK - 1) / FAVOR_RESET_CHUNK;
+    EMO_CHECK(n_layers <= 65535 && chunks <= 65535 && n_rows <= INT32_MAX, "emo_favor_state_reset: grid too large");
+    hipLaunchKernelGGL(favor_state_reset_kernel, dim3((unsigned)n_rows, (unsigned)n_layers, (unsigned)chunks), dim3(256), 0, (hipStream_t)stream,
+                       (const void* const*)state_table, s_row_floats, z_row_floats, row_reset);
     EMO_LAUNCH_CHECK();
     return EMO_OK;
 }

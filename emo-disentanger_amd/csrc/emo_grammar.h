@@ -1,4 +1,4 @@
-// What the four kinds of emo_grammar_step (emo_stage1_gen.hip: TXL, TXL_QUEUE; emo_stage2_gen.hip: ACC, ACC_WINDOW and the entry) share besides the draw.
+// What the five kinds of emo_grammar_step (emo_stage1_gen.hip: TXL, TXL_QUEUE; emo_stage2_gen.hip: ACC, ACC_WINDOW, ACC_QUEUE and the entry) share besides the draw.
 // Each kernel takes the caller's emo_grammar_step_t by value as its one parameter (a field is fetched from the kernel arguments where it is used,
 // so the fields of the other kinds cost nothing) and runs as one 512-thread workgroup per row.
 #pragma once

@@ -12,7 +12,10 @@
 // The ACC_WINDOW kind is the same draw and grammar (acc_draw below, shared) for streams past the window (reference :252-277: the model input is
 // the last max_dec_inp_len tokens, positions restarting at 0): nothing is fed token by token; after an acceptance the stream's next model input
 // win_tok / win_seg[b, 0..W) = seq / segs[r, LEN - W .. LEN) is written, an injected bar included.
-// Both kinds, when the caller wants them (tok_logp / tok_rank / tok_entropy): the figures of the ACCEPTED draw, from the same logits row at
+// The ACC_QUEUE kind is the in-window step (acc_stream_step below, shared with ACC) for more jobs than batch rows: a slot b works on job slot_job[b],
+// and in the launch in which the job leaves RUNNING thread 0 takes the next open job from queue_head, feeds its first token and flags the row in
+// row_reset (emo_hip.h: EMO_GRAMMAR_ACC_QUEUE).  The position of every token fed goes to mem_lens[b], the decode engine's position array.
+// All kinds, when the caller wants them (tok_logp / tok_rank / tok_entropy): the figures of the ACCEPTED draw, from the same logits row at
 // temperature 1, go to the cell of the token it appended (emo_draw_scores.h) — after the draw loop has ended, since the redraws read the sorted
 // state, and by the whole workgroup: whether and where a draw was accepted is read from the LDS state words thread 0 wrote before the loop's
 // last barrier.
@@ -102,37 +105,28 @@ __device__ __forceinline__ int32_t acc_draw(const emo_grammar_step_t& a, const f
     return status;
 }
 
-__global__ __launch_bounds__(512) void acc_grammar_kernel(const emo_grammar_step_t a) {
-    __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
-    __shared__ int32_t sst[EMO_ACC_STATE_WORDS], spr[EMO_ACC_PARAM_WORDS], sagain;
-    __shared__ float sred[EMO_DRAW_SCORES_WORDS];
-    const int tid = (int)threadIdx.x;
-    const int64_t r = blockIdx.x;
+// One token step of stream r (kind ACC: a stream of the batch; kind ACC_QUEUE: a job) in batch row b, whose logits row it draws from and whose
+// next input it writes, after emo_grammar_open has brought the stream's words to sst / spr and found it RUNNING.  All 512 threads call it; every
+// barrier inside lies on a path that sst, spr and the launch arguments alone decide.  Thread 0 leaves the stream's state words in memory.
+__device__ __forceinline__ void acc_stream_step(const emo_grammar_step_t& a, int64_t b, int64_t r, char* lds, int32_t* sst, const int32_t* spr,
+                                                int32_t* sagain, float* sred, int tid) {
     int32_t* st = a.state + r * EMO_ACC_STATE_WORDS;
     int64_t* row = a.seq + r * a.ld_seq;
     int64_t* srow = a.segs + r * a.ld_seq;
-    emo_grammar_open(st, EMO_ACC_STATE_WORDS, a.params + r * EMO_ACC_PARAM_WORDS, EMO_ACC_PARAM_WORDS, sst, spr, tid);
-    if (sst[EMO_ACC_S_STATUS] != EMO_ACC_RUNNING) {
-        if (tid == 0) {
-            a.tok_out[r] = a.pad;
-            a.seg_out[r] = 1;
-        }
-        return;
-    }
     if (sst[EMO_ACC_S_LEN] >= a.max_len) {                   // checked before the feed test, like the host loop's `overflow`
         if (tid == 0) {
             st[EMO_ACC_S_STATUS] = EMO_ACC_WINDOW;
             atomicSub(a.running, 1);
-            a.tok_out[r] = a.pad;
-            a.seg_out[r] = 1;
+            a.tok_out[b] = a.pad;
+            a.seg_out[b] = 1;
         }
         return;
     }
     int32_t consumed = sst[EMO_ACC_S_CONSUMED];
     if (consumed < sst[EMO_ACC_S_LEN]) {
         if (tid == 0) {
-            a.tok_out[r] = row[consumed];
-            a.seg_out[r] = srow[consumed];
+            a.tok_out[b] = row[consumed];
+            a.seg_out[b] = srow[consumed];
             st[EMO_ACC_S_CONSUMED] = consumed + 1;
         }
         return;
@@ -141,23 +135,100 @@ __global__ __launch_bounds__(512) void acc_grammar_kernel(const emo_grammar_step
     // (read before thread 0 can have touched the state: it writes only behind the barriers of the first draw)
     const bool scores = emo_grammar_wants_scores(a);
     const int32_t len0 = scores ? sst[EMO_ACC_S_LEN] : 0, acc0 = scores ? sst[EMO_ACC_S_ACCEPTED] : 0;
-    const int32_t status = acc_draw(a, a.logits + r * a.n_token, a.u_steps + r, row, srow, spr, sst, &sagain, lds, tid, draws);
+    const int32_t status = acc_draw(a, a.logits + b * a.n_token, a.u_steps + r, row, srow, spr, sst, sagain, lds, tid, draws);
     // an acceptance appended its word at the old length (an injected bar follows it) and counted itself, in front of the loop's last barrier
-    if (scores && sst[EMO_ACC_S_ACCEPTED] != acc0) emo_grammar_score(a, a.logits + r * a.n_token, r, len0, row[len0], sred, tid);
+    if (scores && sst[EMO_ACC_S_ACCEPTED] != acc0) emo_grammar_score(a, a.logits + b * a.n_token, r, len0, row[len0], sred, tid);
     if (tid != 0) return;
     if (status == EMO_ACC_RUNNING) {                         // the accepted word (or Track_LeadSheet before an injected bar) is the next input
-        a.tok_out[r] = row[consumed];
-        a.seg_out[r] = srow[consumed];
+        a.tok_out[b] = row[consumed];
+        a.seg_out[b] = srow[consumed];
         ++consumed;
     } else {
-        a.tok_out[r] = a.pad;
-        a.seg_out[r] = 1;
+        a.tok_out[b] = a.pad;
+        a.seg_out[b] = 1;
         atomicSub(a.running, 1);
     }
     sst[EMO_ACC_S_STATUS] = status;
     sst[EMO_ACC_S_CONSUMED] = consumed;
     sst[EMO_ACC_S_DRAWS] = draws;
     for (int i = 0; i < EMO_ACC_STATE_WORDS; ++i) st[i] = sst[i];
+}
+
+__global__ __launch_bounds__(512) void acc_grammar_kernel(const emo_grammar_step_t a) {
+    __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
+    __shared__ int32_t sst[EMO_ACC_STATE_WORDS], spr[EMO_ACC_PARAM_WORDS], sagain;
+    __shared__ float sred[EMO_DRAW_SCORES_WORDS];
+    const int tid = (int)threadIdx.x;
+    const int64_t r = blockIdx.x;
+    emo_grammar_open(a.state + r * EMO_ACC_STATE_WORDS, EMO_ACC_STATE_WORDS, a.params + r * EMO_ACC_PARAM_WORDS, EMO_ACC_PARAM_WORDS, sst, spr, tid);
+    if (sst[EMO_ACC_S_STATUS] != EMO_ACC_RUNNING) {
+        if (tid == 0) {
+            a.tok_out[r] = a.pad;
+            a.seg_out[r] = 1;
+        }
+        return;
+    }
+    acc_stream_step(a, r, r, lds, sst, spr, &sagain, sred, tid);
+}
+
+// Thread 0 of slot b, whose job (if it had one) is over: the next queued job that is RUNNING, or none.  queue_head only grows, so a slot that
+// has seen it at n_jobs never adds to it again.
+__device__ __forceinline__ void acc_queue_admit(const emo_grammar_step_t& a, int64_t b) {
+    int32_t next = -1;
+    while (__atomic_load_n(a.queue_head, __ATOMIC_RELAXED) < a.n_jobs) {
+        const int32_t h = atomicAdd(a.queue_head, 1);
+        if (h >= a.n_jobs) break;
+        if (a.state[(int64_t)h * EMO_ACC_STATE_WORDS + EMO_ACC_S_STATUS] == EMO_ACC_RUNNING) {      // (a job closed on the host is passed over)
+            next = h;
+            break;
+        }
+    }
+    a.slot_job[b] = next;
+    a.mem_lens[b] = 0;                                       // the row of the model starts again at position 0; a free slot stays there
+    a.row_reset[b] = next >= 0 ? 1 : 0;
+    if (next >= 0) {
+        a.tok_out[b] = a.seq[(int64_t)next * a.ld_seq];      // the model step behind this launch is the new job's first token
+        a.seg_out[b] = a.segs[(int64_t)next * a.ld_seq];
+        a.state[(int64_t)next * EMO_ACC_STATE_WORDS + EMO_ACC_S_CONSUMED] = 1;
+    } else {
+        a.tok_out[b] = a.pad;
+        a.seg_out[b] = 1;
+    }
+}
+
+__global__ __launch_bounds__(512) void acc_queue_kernel(const emo_grammar_step_t a) {
+    __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
+    __shared__ int32_t sst[EMO_ACC_STATE_WORDS], spr[EMO_ACC_PARAM_WORDS], sagain, sslot;
+    __shared__ float sred[EMO_DRAW_SCORES_WORDS];
+    const int tid = (int)threadIdx.x;
+    const int64_t b = blockIdx.x;
+    if (tid == 0) sslot = a.slot_job[b];                     // thread 0 writes slot_job[b] below: the others decide from this copy
+    __syncthreads();
+    const int64_t j = sslot;
+    if (j < 0 || j >= a.n_jobs) {                            // a free slot
+        if (tid == 0) acc_queue_admit(a, b);
+        return;
+    }
+    int32_t* st = a.state + j * EMO_ACC_STATE_WORDS;
+    emo_grammar_open(st, EMO_ACC_STATE_WORDS, a.params + j * EMO_ACC_PARAM_WORDS, EMO_ACC_PARAM_WORDS, sst, spr, tid);
+    if (sst[EMO_ACC_S_STATUS] == EMO_ACC_RUNNING) {
+        if (sst[EMO_ACC_S_LEN] < a.max_len && sst[EMO_ACC_S_CONSUMED] >= a.mem_rows) {      // the token of this step has no position: never fed
+            if (tid == 0) {
+                st[EMO_ACC_S_STATUS] = EMO_ACC_OVERFLOW;
+                atomicSub(a.running, 1);
+            }
+        } else {
+            acc_stream_step(a, b, j, lds, sst, spr, &sagain, sred, tid);
+        }
+    }
+    if (tid != 0) return;
+    if (st[EMO_ACC_S_STATUS] == EMO_ACC_RUNNING) {           // (thread 0 reads what it wrote itself)
+        a.mem_lens[b] = st[EMO_ACC_S_CONSUMED] - 1;          // the position of the token this launch feeds: its index in seq[j]
+        a.row_reset[b] = 0;
+    } else {
+        if (a.job_steps) a.job_steps[j] = st[EMO_ACC_S_CONSUMED];    // tokens the model was fed for the job = launches it held the slot
+        acc_queue_admit(a, b);
+    }
 }
 
 __global__ __launch_bounds__(512) void acc_window_kernel(const emo_grammar_step_t a) {
@@ -208,24 +279,29 @@ extern "C" int emo_grammar_step_size(void) { return (int)sizeof(emo_grammar_step
 extern "C" int emo_grammar_step(const emo_grammar_step_t* args, emo_stream_t stream) {
     EMO_CHECK(args, "emo_grammar_step: null argument block");
     const emo_grammar_step_t& a = *args;
-    EMO_CHECK(a.kind >= 0 && a.kind <= 3, "emo_grammar_step: kind %d is none of 0 (TXL), 1 (ACC), 2 (ACC_WINDOW), 3 (TXL_QUEUE)", (int)a.kind);
-    const bool queue = a.kind == EMO_GRAMMAR_TXL_QUEUE, txl = a.kind == EMO_GRAMMAR_TXL || queue, acc = a.kind == EMO_GRAMMAR_ACC;
-    const char* const name = queue ? "txl_queue" : txl ? "txl" : acc ? "acc" : "acc_window";
+    EMO_CHECK(a.kind >= 0 && a.kind <= 4, "emo_grammar_step: kind %d is none of 0 (TXL), 1 (ACC), 2 (ACC_WINDOW), 3 (TXL_QUEUE), 4 (ACC_QUEUE)", (int)a.kind);
+    const bool tq = a.kind == EMO_GRAMMAR_TXL_QUEUE, aq = a.kind == EMO_GRAMMAR_ACC_QUEUE, queue = tq || aq;
+    const bool txl = a.kind == EMO_GRAMMAR_TXL || tq, acc = a.kind == EMO_GRAMMAR_ACC || aq;
+    const char* const name = tq ? "txl_queue" : aq ? "acc_queue" : txl ? "txl" : acc ? "acc" : "acc_window";
     const bool common = a.logits && a.u_steps && a.ev_flags && a.ev_beat && a.params && a.state && a.seq && a.running;
     const bool lead = a.lead_tok && a.lead_off && a.segs;
-    EMO_CHECK(common && (queue ? a.tok_out && a.slot_job && a.queue_head && a.mem_lens : txl ? a.tok_out != nullptr : acc ? lead && a.tok_out && a.seg_out : lead && a.win_tok && a.win_seg),
+    const bool slots = a.slot_job && a.queue_head && a.mem_lens;
+    EMO_CHECK(common && (txl ? a.tok_out != nullptr : acc ? lead && a.tok_out && a.seg_out : lead && a.win_tok && a.win_seg) && (!queue || slots) &&
+                  (!aq || a.row_reset),
               "emo_grammar_step[%s]: null pointer", name);
-    // (TXL, ACC: workgroup r reads column r of the uniform table)
+    // (TXL, ACC: workgroup r reads column r of the uniform table; the queue kinds: job j reads column j)
     EMO_CHECK(a.n_rows > 0 && a.n_u > 0 && a.ld_u > 0 && a.ld_seq > 0 &&
-                  (queue ? a.n_jobs > 0 && a.ld_u >= a.n_jobs && a.mem_rows > 0 && a.n_jobs <= INT32_MAX - a.n_rows : txl ? a.ld_u >= a.n_rows : acc ? a.ld_u >= a.n_rows && a.max_len > 0 : a.window > 0 && a.ld_seq >= a.window),
+                  (queue ? a.n_jobs > 0 && a.ld_u >= a.n_jobs && a.mem_rows > 0 && a.n_jobs <= INT32_MAX - a.n_rows : txl || acc ? a.ld_u >= a.n_rows : a.window > 0 && a.ld_seq >= a.window) &&
+                  (!acc || a.max_len > 0),
               "emo_grammar_step[%s]: bad sizes", name);
     EMO_CHECK(a.n_token > 0 && a.n_token <= 1024, "emo_grammar_step[%s]: V must be <= 1024 (got %lld)", name, (long long)a.n_token);
     if (txl) {
         EMO_CHECK(a.temperature > 0.f && a.key_temperature > 0.f, "emo_grammar_step[%s]: temperatures must be > 0", name);
-        return queue ? emo_txl_queue_launch(a, stream) : emo_txl_grammar_launch(a, stream);
+        return tq ? emo_txl_queue_launch(a, stream) : emo_txl_grammar_launch(a, stream);
     }
     EMO_CHECK(a.temperature > 0.f, "emo_grammar_step[%s]: temperature must be > 0", name);
-    if (acc) hipLaunchKernelGGL(acc_grammar_kernel, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
+    if (aq) hipLaunchKernelGGL(acc_queue_kernel, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
+    else if (acc) hipLaunchKernelGGL(acc_grammar_kernel, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(acc_window_kernel, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
     EMO_LAUNCH_CHECK();
     return EMO_OK;

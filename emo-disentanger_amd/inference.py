@@ -235,6 +235,19 @@ class PerformerDecodeEngine(_EngineBase):
             # 96 KB LDS each, one per CU by the occupancy query; partitions / CU masks with fewer keep the chain of launches)
             self._prepare_persist()
 
+    def start_empty(self):
+        """Every row at S = 0, z = 0, as before its first token: the start of a loop without a prefill (AccompanimentQueue), whose rows are
+        restarted one by one later on (ops.favor_state_reset).  -> the int64 [n_layer, 2] device table of the S / z base addresses."""
+        m = self.model
+        H, F = m.n_head, 2 * self.omegas[0].shape[1]
+        rows = self.n_pad if self.persist is not None else self.n        # (the idle padding rows of the one-launch step: zero like the others)
+        for l in range(m.n_layer):
+            self.S[l] = torch.zeros(rows, H, F, m.d_model // H, device=self.dev, dtype=torch.float32)[:self.n]
+            self.z[l] = torch.zeros(rows, H, F, device=self.dev, dtype=torch.float32)[:self.n]
+        if self.persist is not None:
+            self._void_table()
+        return torch.tensor([[self.S[l].data_ptr(), self.z[l].data_ptr()] for l in range(m.n_layer)], dtype=torch.int64, device=self.dev)
+
     # ------------------------------------------------------------------------------------------ one-launch step
     step_entry = 'emo_decode_step[performer]'
 
@@ -863,6 +876,28 @@ class AccompanimentLoop(GrammarLoop):
 
     def __init__(self, model, event2idx, idx2event, lead_sheets, primers, max_events=10000, skip_check=False, max_bars=None, temp=1.2, top_p=0.9,
                  seed=0, n_u=None, persistent=True, redraw=True, scores=False):
+        self._load_jobs(model, event2idx, idx2event, lead_sheets, primers, max_events, skip_check, max_bars, temp, top_p, None)
+        n, dev, V = self.n, self.dev, model.n_token
+        self.U = uniform_table(int(n_u or 4 * self.W), n, seed, dev)
+        self.tok = torch.zeros(n, dtype=torch.int64, device=dev)
+        self.segv = torch.ones(n, dtype=torch.int64, device=dev)
+        self.logits = torch.empty(n, V, dtype=torch.float32, device=dev)
+        self._build_block(ops.GRAMMAR_ACC, scores, **self._block_fields(n))
+        self.windowed = None
+        with torch.no_grad():
+            eng = self._make_engine(n, persistent, redraw)
+            self.logits.copy_(eng.prefill(self.seq[:, :self.L0].contiguous(), self.segs[:, :self.L0].contiguous()))
+            eng.pos_dev.zero_()
+            eng.dev_pos0, eng.pos_auto = self.L0, True          # position = L0 + pos_dev[r], advanced by the engine
+        self.eng = eng
+        pe = model.pe.pe.shape[0] if model.use_pe else self.W
+        self.bound = min(self.W, pe)           # the engine never runs a step at a position >= bound (the one-launch GPT-2 step would clamp it)
+        self.pos = self.L0                     # host count of the engine position (every row advances one per step)
+
+    def _load_jobs(self, model, event2idx, idx2event, lead_sheets, primers, max_events, skip_check, max_bars, temp, top_p, consumed):
+        """n, model, dev, W and the draw parameters; the grammar tables, the packed lead sheets and, per stream, its _Stream and its token / segment
+        rows, parameters and state on the device, state[CONSUMED] = `consumed` (None: the shortest prompt's length L0, the prefix a prefill
+        takes); the running count."""
         n = self.n = len(lead_sheets)
         assert n == len(primers) and n > 0
         _refuse(model, None)
@@ -887,32 +922,25 @@ class AccompanimentLoop(GrammarLoop):
             seq[i, :lens[i]], segs[i, :lens[i]] = s.generated, s.seg
             params[i, [ACC_P_TARGET_BARS, ACC_P_MAX_EVENTS, ACC_P_SKIP_CHECK, ACC_P_BAR0, ACC_P_N_BARS]] = (s.target_bars, max_events, bool(skip_check),
                                                                                                             bar0[i], nbars[i])
-            state[i, [ACC_S_STATUS, ACC_S_LEN, ACC_S_CONSUMED]] = (ACC_DONE if s.done else ACC_RUNNING), lens[i], self.L0
+            state[i, [ACC_S_STATUS, ACC_S_LEN, ACC_S_CONSUMED]] = (ACC_DONE if s.done else ACC_RUNNING), lens[i], self.L0 if consumed is None else consumed
         self.len0 = np.array(lens)
         self.seq, self.segs, self.params, self.state = self._to_device(seq, segs, params, state)
         self.running = torch.tensor([int((state[:, ACC_S_STATUS] == ACC_RUNNING).sum())], dtype=torch.int32, device=dev)
-        self.U = uniform_table(int(n_u or 4 * self.W), n, seed, dev)
-        self.tok = torch.zeros(n, dtype=torch.int64, device=dev)
-        self.segv = torch.ones(n, dtype=torch.int64, device=dev)
-        self.logits = torch.empty(n, V, dtype=torch.float32, device=dev)
-        self._build_block(ops.GRAMMAR_ACC, scores, n_rows=n, n_token=V, ld_u=n, temperature=self.temp, top_p=self.top_p, max_len=self.W,
-                          track_full=self.track_full, pad=self.pad, logits=self.logits, u_steps=self.U, ev_flags=self.ev_flags,
-                          ev_beat=self.ev_beat, lead_tok=self.lead_tok, lead_off=self.lead_off, params=self.params, state=self.state, seq=self.seq,
-                          segs=self.segs, tok_out=self.tok, seg_out=self.segv, running=self.running)
-        self.windowed = None
-        with torch.no_grad():
-            if model.kind == 'performer':
-                eng = PerformerDecodeEngine(model, n, redraw=redraw, persistent=persistent)
-                eng.max_len = self.W
-            else:
-                eng = GPT2DecodeEngine(model, n, max_len=self.W, persistent=persistent)
-            self.logits.copy_(eng.prefill(self.seq[:, :self.L0].contiguous(), self.segs[:, :self.L0].contiguous()))
-            eng.pos_dev.zero_()
-            eng.dev_pos0, eng.pos_auto = self.L0, True          # position = L0 + pos_dev[r], advanced by the engine
-        self.eng = eng
-        pe = model.pe.pe.shape[0] if model.use_pe else self.W
-        self.bound = min(self.W, pe)           # the engine never runs a step at a position >= bound (the one-launch GPT-2 step would clamp it)
-        self.pos = self.L0                     # host count of the engine position (every row advances one per step)
+
+    def _block_fields(self, rows):
+        """The fields of the grammar launch's block that kinds ACC and ACC_QUEUE share, for a model batch of `rows` rows."""
+        return dict(n_rows=rows, n_token=self.model.n_token, ld_u=self.n, temperature=self.temp, top_p=self.top_p, max_len=self.W,
+                    track_full=self.track_full, pad=self.pad, logits=self.logits, u_steps=self.U, ev_flags=self.ev_flags,
+                    ev_beat=self.ev_beat, lead_tok=self.lead_tok, lead_off=self.lead_off, params=self.params, state=self.state, seq=self.seq,
+                    segs=self.segs, tok_out=self.tok, seg_out=self.segv, running=self.running)
+
+    def _make_engine(self, rows, persistent, redraw):
+        """The decode engine of `rows` rows whose positions and cache end at the window."""
+        if self.model.kind == 'performer':
+            eng = PerformerDecodeEngine(self.model, rows, redraw=redraw, persistent=persistent)
+            eng.max_len = self.W
+            return eng
+        return GPT2DecodeEngine(self.model, rows, max_len=self.W, persistent=persistent)
 
     def one_step(self):
         self.grammar()
@@ -1009,6 +1037,79 @@ class AccompanimentLoop(GrammarLoop):
                 sc[k] = a
             out.append(sc)
         return out
+
+
+class AccompanimentQueue(AccompanimentLoop):
+    """AccompanimentLoop for more jobs than rows: `slots` rows of the model batch (one decode engine of that many rows) work through
+    len(lead_sheets) queued jobs.  one_step() = emo_grammar_step (kind ACC_QUEUE) + the restart of the admitted rows' FAVOR+ state (Performer
+    only: emo_favor_state_reset on the launch's row_reset flags; a GPT-2 row restarts by being fed position 0) + the engine step: a slot whose
+    job ends takes the next job inside the grammar launch, so the replayed graphs go on and the running count stays the only thing read back.
+    There is no prefill: the first launch admits the first jobs and every prompt token goes through the one-token step, at the position the
+    grammar launch writes into the engine's device position array (pos_auto False, dev_pos0 0: generate_streams' mode).  Job j draws from column
+    j of the uniform table, whatever slot it lands in; all jobs run under the engine's one set of feature maps.  A job that reaches the window
+    ends with WINDOW and frees its slot; results() finishes it as it finishes a lock-step stream.  The lock-step loop's host position bound
+    does not apply: the per-job bound is the kernel's (mem_rows = the window; a positional table with fewer rows is refused here).  results() /
+    scores() / handed_off() are AccompanimentLoop's, per job; job_steps: the launches each finished job held a slot; launches: the launches run()
+    queued (a k-step replay ends up to k - 1 launches past the drain)."""
+
+    def __init__(self, model, event2idx, idx2event, lead_sheets, primers, slots, max_events=10000, skip_check=False, max_bars=None, temp=1.2,
+                 top_p=0.9, seed=0, n_u=None, persistent=True, redraw=True, scores=False):
+        slots = self.slots = int(slots)
+        if slots < 1:
+            raise ValueError('slots must be at least 1 (got %d)' % slots)
+        # CONSUMED 1 is what an admission sets: the first token goes out with it
+        self._load_jobs(model, event2idx, idx2event, lead_sheets, primers, max_events, skip_check, max_bars, temp, top_p, 1)
+        n, dev, V = self.n, self.dev, model.n_token
+        if model.use_pe and model.pe.pe.shape[0] < self.W:
+            raise EmoError('generate_accompaniments(slots=): the positional table has %d rows, fewer than the window of %d tokens'
+                           % (model.pe.pe.shape[0], self.W))
+        self.bound = self.W
+        self.U = uniform_table(int(n_u or 4 * self.W), n, seed, dev)
+        self.tok = torch.full((slots,), self.pad, dtype=torch.int64, device=dev)
+        self.segv = torch.ones(slots, dtype=torch.int64, device=dev)
+        self.logits = torch.zeros(slots, V, dtype=torch.float32, device=dev)
+        self.slot_job = torch.full((slots,), -1, dtype=torch.int32, device=dev)
+        self.queue_head = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.row_reset = torch.zeros(slots, dtype=torch.int32, device=dev)
+        self.job_steps_dev = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.windowed = None
+        with torch.no_grad():
+            eng = self.eng = self._make_engine(slots, persistent, redraw)
+            eng.pos_dev.zero_()
+            eng.dev_pos0, eng.pos_auto = 0, False                # position = pos_dev[b], written by the grammar launch
+            self.state_table = eng.start_empty() if model.kind == 'performer' else None
+        self._build_block(ops.GRAMMAR_ACC_QUEUE, scores, n_jobs=n, mem_rows=self.bound, slot_job=self.slot_job, queue_head=self.queue_head,
+                          mem_lens=eng.pos_dev, row_reset=self.row_reset, job_steps=self.job_steps_dev, **self._block_fields(slots))
+        # no job is fed more tokens than the window holds, so the queue is drained before this many launches whatever the slots do: a budget
+        # for the replayer, not a limit that is meant to bind (the per-job limit is the kernel's WINDOW)
+        self.budget = n * self.W + 2
+        self.launches = self.pos = 0
+
+    def model_step(self):
+        """What follows the grammar launch: the restart of the rows it flagged (Performer), then the engine step on the tokens, segments and
+        positions it wrote."""
+        if self.state_table is not None:
+            ops.favor_state_reset(self.state_table, self.slots, self.eng.S[0][0].numel(), self.eng.z[0][0].numel(), self.row_reset)
+        self.eng.step(self.tok, self.segv, dev_pos=True, logits_out=self.logits)
+
+    def one_step(self):
+        self.grammar()
+        self.model_step()
+
+    def run(self, use_graph=True, steps_per_graph=None):
+        """Launches until the running count is 0; it is read once per replay (per step without graphs)."""
+        with torch.no_grad():
+            self.launches = self.pos = self._replay(self.launches, self.budget, use_graph, steps_per_graph)
+            torch.cuda.synchronize()
+            if self._live() > 0:
+                raise EmoError('AccompanimentQueue: %d jobs still running after %d launches' % (self._live(), self.launches))
+
+    def steps(self):
+        return self.launches
+
+    def job_steps(self):
+        """-> per job, the launches it held a slot (0 for a job that was closed before the run)."""
+        return [int(x) for x in self.job_steps_dev.cpu().tolist()]
 
 
 WINDOW_TAG = 0x57494E                  # the windowed phase's uniform table is seeded with (seed, this tag): never the in-window table's seed
@@ -1134,7 +1235,7 @@ class WindowedLoop(GrammarLoop):
 
 
 def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, max_events=10000, skip_check=False, max_bars=None, temp=1.2, top_p=0.9,
-                            inadmissibles=None, seed=0, use_graph=True, best_of=1, window='host', best_by='forward', return_scores=False):
+                            inadmissibles=None, seed=0, use_graph=True, best_of=1, window='host', best_by='forward', return_scores=False, slots=None):
     """The throughput path of generate_conditional_batch: the same arguments (no per-stream samplers) and result per stream, every draw and
     the grammar of _Stream.offer on the device (emo_grammar_step), each token step = grammar launch + one engine step (the one-launch
     persistent step where the engine has one), k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS, default 16) and replayed until
@@ -1166,20 +1267,41 @@ def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, m
     return_scores = True: the result tuple gets one more element at its end, a list aligned with the results: {'logp', 'rank', 'entropy'} numpy
     arrays with one entry per id (NaN / -1 where the id was given: primer, injected bars, Track_Full; and, with window = 'host', from a
     stream's hand-off on, where _resume_windowed draws on the host), or None where the result is an error.  With best_of > 1 these are the
-    chosen candidates' and every pick also carries 'scores': the N candidates'.  The ids are those of the call without it."""
+    chosen candidates' and every pick also carries 'scores': the N candidates'.  The ids are those of the call without it.
+
+    slots = None: one lock-step batch with a row per stream (the paths above, draw for draw).  slots = S: the streams (lead sheets times best_of)
+    are JOBS that run through S rows (AccompanimentQueue), also when S is at least their number: a row whose job ends takes the next job on the
+    device, so no row idles while jobs wait and no batch waits for its longest member.  There is no prefill; a job draws from its own column of
+    the uniform table, so its ids do not depend on S or on the slot it ran in beyond what the model step's arithmetic does; they are not those
+    of slots = None, whose streams share a prefill.  All jobs run under the engine's one set of feature maps.  A job that reaches the window
+    frees its slot and is finished after the queue has drained, by `window` as above.  Refused (EmoError) when the model's positional table has
+    fewer rows than the window.  The results, best_of, best_by and return_scores are per job as they are per stream."""
     if window not in ('host', 'device'):
         raise ValueError("window must be 'host' or 'device' (got %r)" % (window,))
     _refuse(model, inadmissibles)
     best_of, by_draws, want, lead_sheets, primers = scoring.best_of_plan(best_of, best_by, return_scores, lead_sheets, primers)
+    if slots is not None:
+        try:
+            slots = int(slots)
+        except (TypeError, ValueError):
+            raise ValueError('slots must be None or a count of at least 1 (got %r)' % (slots,))
+        if slots < 1:
+            raise ValueError('slots must be at least 1 (got %d)' % slots)
     t0 = time.time()
     kw = dict(max_events=max_events, skip_check=skip_check, max_bars=max_bars, temp=temp, top_p=top_p, seed=seed)
+
+    def make(**more):
+        if slots is None:
+            return AccompanimentLoop(model, event2idx, idx2event, lead_sheets, primers, scores=want, **kw, **more)
+        return AccompanimentQueue(model, event2idx, idx2event, lead_sheets, primers, slots, scores=want, **kw, **more)
+
     with scoring.eval_mode(model):
-        loop = AccompanimentLoop(model, event2idx, idx2event, lead_sheets, primers, scores=want, **kw)
+        loop = make()
         try:
             loop.run(use_graph=use_graph)
         except _GaveUp as e:
             print('[gen] %s -> the batch again on the chain of launches' % e)
-            loop = AccompanimentLoop(model, event2idx, idx2event, lead_sheets, primers, persistent=False, redraw=False, scores=want, **kw)
+            loop = make(persistent=False, redraw=False)
             loop.run(use_graph=use_graph)
         out = loop.results(event2idx, idx2event, max_events, skip_check, seed, window=window)
         sc = loop.scores(out) if want else None
@@ -1227,6 +1349,8 @@ def parse_args(argv=None):
                     help='--device: streams past the %d-token window are finished one at a time on the host, or together on the device' % max_dec_inp_len)
     ap.add_argument('--best-by', dest='best_by', default='forward', choices=['forward', 'draws'],
                     help='--best-of: rank the candidates by a scoring forward over the finished pieces, or by the log-probabilities recorded at each draw')
+    ap.add_argument('--slots', type=int, default=None,
+                    help='--device: run ALL lead sheets (times --best-of) as queued jobs through this many rows of one decode engine, refilled on the device')
     ap.add_argument('--scores', default=None, metavar='FILE',
                     help='--device: write one JSON record per piece (scoring.draw_record) and its per-token logp / rank / entropy, as recorded at each draw')
     args = ap.parse_args(argv)
@@ -1238,6 +1362,8 @@ def parse_args(argv=None):
         ap.error('--best-by goes with --best-of N, N > 1')
     if args.scores and not args.device:
         ap.error('--scores needs --device')
+    if args.slots is not None and (not args.device or args.slots < 1):
+        ap.error('--slots needs --device and a count of at least 1')
     return args
 
 
@@ -1275,18 +1401,20 @@ def main(argv=None):
             jobs.append((out, key, bars, primer))
     print('[# jobs]', len(jobs))
     per_group = max(1, args.streams // args.best_of)              # --streams counts engine streams: N of them per lead sheet with --best-of N
+    if args.slots is not None:
+        per_group = max(1, len(jobs))                             # one call: the jobs queue for the slots
     want, score_pieces = bool(args.scores), []
     for j, i in enumerate(range(0, len(jobs), per_group)):
         group = jobs[i:i + per_group]
         if args.device and args.best_of > 1:
             gen, _, picks, *sc = generate_accompaniments(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group],
                                                          max_bars=args.max_bars, temp=temp, top_p=top_p, seed=args.seed + j, best_of=args.best_of,
-                                                         window=args.window, best_by=args.best_by, return_scores=want)
+                                                         window=args.window, best_by=args.best_by, return_scores=want, slots=args.slots)
             for g, p in zip(group, picks):
                 print('[info] %s: candidate %d of %s' % (g[0], p['chosen'], ['%.4f' % x for x in p['nll_mean']]))
         elif args.device:
             gen, _, *sc = generate_accompaniments(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
-                                                  temp=temp, top_p=top_p, seed=args.seed + j, window=args.window, return_scores=want)
+                                                  temp=temp, top_p=top_p, seed=args.seed + j, window=args.window, return_scores=want, slots=args.slots)
         else:
             gen = generate_conditional_batch(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
                                              temp=temp, top_p=top_p, seeds=list(range(i, i + len(group))))

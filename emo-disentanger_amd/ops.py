@@ -10,12 +10,12 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, ATTN_BWD, ATTN_BWD_KV, ATTN_BWD_R, ATTN_DECODE, ATTN_FAVOR, ATTN_FWD, ATTN_RELPOS, ATTN_SOFTMAX, BF16, F32, MUL_BITMASK, MUL_DGELU, MUL_DGELU_NEW, MUL_NONE, MUL_NONZERO, GRAMMAR_ACC, GRAMMAR_ACC_WINDOW, GRAMMAR_TXL, GRAMMAR_TXL_QUEUE, Attn, DecodeStep, Epilogue, GrammarStep, check,
+from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, ATTN_BWD, ATTN_BWD_KV, ATTN_BWD_R, ATTN_DECODE, ATTN_FAVOR, ATTN_FWD, ATTN_RELPOS, ATTN_SOFTMAX, BF16, F32, MUL_BITMASK, MUL_DGELU, MUL_DGELU_NEW, MUL_NONE, MUL_NONZERO, GRAMMAR_ACC, GRAMMAR_ACC_QUEUE, GRAMMAR_ACC_WINDOW, GRAMMAR_TXL, GRAMMAR_TXL_QUEUE, Attn, DecodeStep, Epilogue, GrammarStep, check,
                    dtype_code, lib, ptr, stream)
 
 __all__ = ['gemm', 'colsum', 'embed_fwd', 'embed_bwd', 'layernorm_fwd', 'layernorm_bwd', 'dropout_apply', 'favor_attn_fwd',
-           'favor_attn_bwd', 'favor_decode_step', 'decode_step', 'decode_step_set', 'block_set', 'DecodeStep', 'GrammarStep', 'grammar_step', 'draw_score_tables', 'favor_draw_omega', 'softmax_attn_fwd', 'softmax_attn_bwd', 'softmax_attn_decode', 'relpos_attn_fwd', 'relpos_attn_bwd', 'relpos_attn_decode', 'xent_fwd',
-           'xent_bwd', 'token_scores', 'xent_bwd_rows', 'argmax', 'sample_nucleus', 'sample_nucleus_step', 'txl_grammar_step', 'txl_queue_step', 'acc_grammar_step', 'acc_window_step', 'accuracy_counts', 'sumsq', 'clip_coef', 'adam_step', 'cast', 'add_bias2',
+           'favor_attn_bwd', 'favor_decode_step', 'decode_step', 'decode_step_set', 'block_set', 'DecodeStep', 'GrammarStep', 'grammar_step', 'draw_score_tables', 'favor_draw_omega', 'favor_state_reset', 'softmax_attn_fwd', 'softmax_attn_bwd', 'softmax_attn_decode', 'relpos_attn_fwd', 'relpos_attn_bwd', 'relpos_attn_decode', 'xent_fwd',
+           'xent_bwd', 'token_scores', 'xent_bwd_rows', 'argmax', 'sample_nucleus', 'sample_nucleus_step', 'txl_grammar_step', 'txl_queue_step', 'acc_grammar_step', 'acc_queue_step', 'acc_window_step', 'accuracy_counts', 'sumsq', 'clip_coef', 'adam_step', 'cast', 'add_bias2',
            'ACT_NONE', 'ACT_RELU', 'ACT_GELU_NEW', 'ACT_GELU', 'MUL_NONE', 'MUL_NONZERO', 'MUL_DGELU_NEW', 'MUL_DGELU', 'MUL_BITMASK', 'gemm_bitmask_ok', 'gemm_lna_ok', 'bitmask_rows', 'favor_bwd_dn_ok', 'ffn_fwd', 'ffn_fwd_ok']
 
 
@@ -397,6 +397,7 @@ _GRAMMAR_STEP_LAYOUT = {
     'queue_head': lambda a, t: _is(t, _I32) and t.numel() >= 1,
     'mem_lens': lambda a, t: _is(t, _I64) and t.numel() == a.n_rows,
     'job_steps': lambda a, t: _is(t, _I32) and t.numel() == a.ld_u,
+    'row_reset': lambda a, t: _is(t, _I32) and t.numel() == a.n_rows,
 }
 # per struct: its name in messages, the layout table, the int64 vectors, and the numbers a tensor brings with it (field -> (number, of tensor))
 _BLOCKS = {
@@ -451,6 +452,15 @@ def favor_draw_omega(gauss, omega):
     assert gauss.is_contiguous() and omega.is_contiguous() and omega.shape[:2] == (L, dh)
     check(lib.emo_favor_draw_omega(ptr(gauss), ptr(omega), L, dh, 2 * omega.shape[2], stream()))
     return omega
+
+
+def favor_state_reset(state_table, n_rows, s_row_floats, z_row_floats, row_reset):
+    """Zero the FAVOR+ state rows flagged in row_reset (int32 [n_rows]; emo_hip.h: emo_favor_state_reset).  state_table: int64 [n_layers, 2] on the
+    device, the data_ptr() of every layer's S [n_rows, H, F, dh] and z [n_rows, H, F] (fp32, contiguous; the caller keeps them alive).
+    Allocation-free (hipGraph capture)."""
+    assert state_table.dtype == _I64 and state_table.is_contiguous() and state_table.dim() == 2 and state_table.shape[1] == 2
+    assert _is(row_reset, _I32) and row_reset.numel() == n_rows
+    check(lib.emo_favor_state_reset(ptr(state_table), state_table.shape[0], n_rows, s_row_floats, z_row_floats, ptr(row_reset), stream()))
 
 
 def softmax_attn_fwd(q, k, v, B, T, H, p_drop=0.0, seed=0, offset=0, want_keep=False):
@@ -717,6 +727,24 @@ def acc_grammar_step(logits, temperature, top_p, u_steps, ev_flags, ev_beat, lea
                   logits=logits, u_steps=u_steps, ev_flags=ev_flags, ev_beat=ev_beat, lead_tok=lead_tok, lead_off=lead_off, params=params, state=state,
                   seq=seq, segs=segs, tok_out=tok_out, seg_out=seg_out, running=running, tok_logp=tok_logp, tok_rank=tok_rank,
                   tok_entropy=tok_entropy)
+    return tok_out
+
+
+def acc_queue_step(logits, temperature, top_p, u_steps, ev_flags, ev_beat, lead_tok, lead_off, params, state, seq, segs, max_len, track_full, pad,
+                   tok_out, seg_out, running, slot_job, queue_head, mem_lens, mem_rows, row_reset, job_steps=None, tok_logp=None, tok_rank=None,
+                   tok_entropy=None):
+    """One stage-2 sample-and-grammar step of `slots` batch rows working through a queue of n_jobs jobs (include/emo_hip.h,
+    EMO_GRAMMAR_ACC_QUEUE): logits fp32 [slots, V], tok_out / seg_out int64 [slots], slot_job int32 [slots] (-1: free), mem_lens int64 [slots]
+    (the positions the model step reads), row_reset int32 [slots], queue_head int32 [1]; u_steps fp32 [n_u, n_jobs], params / state int32
+    [n_jobs, 8], seq / segs int64 [n_jobs, W] and the optional tables (job_steps int32 [n_jobs]; the score tables [n_jobs, W]) are the jobs'.
+    Everything but logits, u_steps, params, the lead sheets and the event tables is updated in place."""
+    slots, V = logits.shape
+    n_jobs = params.shape[0]
+    _grammar_once(GRAMMAR_ACC_QUEUE, n_rows=slots, n_token=V, ld_u=n_jobs, n_jobs=n_jobs, mem_rows=mem_rows, temperature=temperature, top_p=top_p,
+                  max_len=max_len, track_full=track_full, pad=pad, logits=logits, u_steps=u_steps, ev_flags=ev_flags, ev_beat=ev_beat,
+                  lead_tok=lead_tok, lead_off=lead_off, params=params, state=state, seq=seq, segs=segs, tok_out=tok_out, seg_out=seg_out,
+                  running=running, slot_job=slot_job, queue_head=queue_head, mem_lens=mem_lens, row_reset=row_reset, job_steps=job_steps,
+                  tok_logp=tok_logp, tok_rank=tok_rank, tok_entropy=tok_entropy)
     return tok_out
 
 

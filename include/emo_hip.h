@@ -413,6 +413,14 @@ int emo_decode_step(const emo_decode_step_t* args, emo_stream_t stream);
  * omega [n_layers, dh, n_feat/2] with orthogonal columns per block scaled by the row norms of the block. */
 int emo_favor_draw_omega(const float* gauss, float* omega, int64_t n_layers, int64_t dh, int64_t n_feat,
                          emo_stream_t stream);
+/* Restart rows of the FAVOR+ recurrent state (no reference counterpart: the reference recomputes the whole prefix per token and has no state).  A
+ * decode row that takes a new piece (EMO_GRAMMAR_ACC_QUEUE: row_reset, written by the grammar launch in front of this one) must start from S = 0, z = 0.
+ * state_table: DEVICE array [n_layers][2] of pointers, the layer's state_S (f32 [n_rows][s_row_floats]) and state_z (f32 [n_rows][z_row_floats]), each
+ * 16-byte aligned; s_row_floats = H * n_feat * dh and z_row_floats = H * n_feat, both multiples of 4.  Grid (row, layer, chunk of 4096 floats): a
+ * workgroup reads row_reset[row] (int32 [n_rows]) and leaves at once when it is 0, otherwise zeroes its chunk of the row with 16-byte stores.  Rows
+ * that are not flagged are not touched.  Graph-capturable; nothing is allocated. */
+int emo_favor_state_reset(const void* state_table, int64_t n_layers, int64_t n_rows, int64_t s_row_floats, int64_t z_row_floats,
+                          const int32_t* row_reset, emo_stream_t stream);
 
 /* ------------------------------------------------------------------ K9: cross-entropy with ignore_index
  * Replaces F.cross_entropy in compute_loss (model/music_performer.py:72-81).
@@ -533,21 +541,43 @@ enum { EMO_ACC_EV_BEAT = 1, EMO_ACC_EV_TRACK_LS = 2, EMO_ACC_EV_PAD = 4, EMO_ACC
  * number of RUNNING jobs and is decremented once per job.  Which of several slots that free up in one launch gets which job is not specified; a
  * job's ids depend on the job (its rows, its uniform column, its counters) and the logits it is shown, nothing else.  job_steps (int32 [n_jobs]
  * or NULL): when a job ends, job_steps[j] = mem_lens[b] = the tokens the model was fed for it = the launches it held its slot. */
-/* The four grammar steps above are the kinds of ONE entry with ONE argument block, as emo_decode_step_t is for the model step beside them in
+/* EMO_GRAMMAR_ACC_QUEUE.  The ACC kind for MORE JOBS THAN ROWS, as TXL_QUEUE is for TXL: the n_rows rows of the model batch are SLOTS, the streams are n_jobs JOBS
+ * waiting in a queue, and a slot whose job ends takes the next one inside the launch.  One 512-thread workgroup per slot b, which owns logits[b],
+ * tok_out[b], seg_out[b], mem_lens[b] and row_reset[b] and works on job j = slot_job[b] (int32 [n_rows]; -1: free).  Everything the ACC kind indexes by
+ * stream is indexed by job: params, state, seq, segs, the score tables (n_jobs rows each) and the column of u_steps (ld_u >= n_jobs; draw d of job j takes
+ * u_steps[d * ld_u + j]).  The queue fields are TXL_QUEUE's with the ACC meaning: mem_lens (int64 [n_rows]) is the POSITION of the token each row is fed in
+ * the model step behind the launch (the decode engine's device position array: the positional-table row and, for a KV cache, the row the token's key is
+ * appended at, so a row restarts by being fed position 0), mem_rows the position bound (min(max_len, rows of the positional table)).  Per launch and slot:
+ *   slot_job[b] = a RUNNING job -> state[LEN] >= max_len: WINDOW, as in the ACC kind; otherwise state[CONSUMED] >= mem_rows: OVERFLOW (the token of this
+ *                                  step has no position; a caller whose table has max_len rows never sees it); otherwise exactly the ACC kind's step for
+ *                                  stream j (the same device code): the feed of a pending token, the draw, the in-launch redraws, the grammar, the bar
+ *                                  injection, the scores.  The token fed is seq[j, CONSUMED - 1] after the step: mem_lens[b] = CONSUMED - 1, row_reset[b] = 0;
+ *   slot_job[b] free, or the job left RUNNING in this launch (DONE, STUCK, WINDOW, OUT_OF_DRAWS, OVERFLOW) -> job_steps[j] = state[j, CONSUMED] = the tokens
+ *                                  the model was fed for it = the launches it held its slot; then thread 0 takes jobs from the queue (h =
+ *                                  atomicAdd(queue_head, 1), h < n_jobs) until one is RUNNING (a job the host closed before the run is passed over).  With
+ *                                  a job j': slot_job[b] = j', row_reset[b] = 1, state[j', CONSUMED] = 1, tok_out[b] / seg_out[b] = seq / segs[j', 0],
+ *                                  mem_lens[b] = 0: the model step behind this very launch is the job's first token.  With the queue empty: slot_job[b] =
+ *                                  -1, row_reset[b] = 0, tok_out[b] = pad, seg_out[b] = 1, mem_lens[b] = 0, in this and in every later launch (queue_head
+ *                                  is not added to again).
+ * row_reset (int32 [n_rows]) is written in EVERY launch: 1 for a slot that admitted a job in it, else 0.  A model whose rows carry state besides the
+ * cache that position 0 overwrites (the Performer's S / z) clears the flagged rows between this launch and its step: emo_favor_state_reset.  The first
+ * launch starts from slot_job = -1 everywhere and queue_head = 0 and admits the first jobs itself: there is no prefill, every primer token goes through the
+ * one-token step (state[j, CONSUMED] as the host leaves it is ignored).  *running starts at the number of RUNNING jobs and is decremented once per job. */
+/* The five grammar steps above are the kinds of ONE entry with ONE argument block, as emo_decode_step_t is for the model step beside them in
  * every generation loop.  `kind` selects the kernel; a field that a kind does not read is ignored by it, whatever it holds (the comment of each
- * field names its readers; none = all four; a field of TXL is a field of TXL_QUEUE too).  The block is read AT CALL TIME: its values travel as the launch's arguments, so under hipGraph
+ * field names its readers; none = all five; a field of TXL is a field of TXL_QUEUE too, a field of ACC a field of ACC_QUEUE).  The block is read AT CALL TIME: its values travel as the launch's arguments, so under hipGraph
  * capture they are baked into the captured launch, exactly as positional arguments would be, and a later change of the block reaches only later
  * calls (and later captures).  The struct holds raw device addresses: its owner keeps the memory alive. */
-enum { EMO_GRAMMAR_TXL = 0, EMO_GRAMMAR_ACC = 1, EMO_GRAMMAR_ACC_WINDOW = 2, EMO_GRAMMAR_TXL_QUEUE = 3 };   /* what each does: the four comments above (n = n_rows, V = n_token) */
+enum { EMO_GRAMMAR_TXL = 0, EMO_GRAMMAR_ACC = 1, EMO_GRAMMAR_ACC_WINDOW = 2, EMO_GRAMMAR_TXL_QUEUE = 3, EMO_GRAMMAR_ACC_QUEUE = 4 };   /* what each does: the five comments above (n = n_rows, V = n_token) */
 typedef struct {
     int32_t kind;              /* EMO_GRAMMAR_* */
     /* --- all kinds */
-    int64_t n_rows;            /* workgroups launched: TXL, ACC the n streams; ACC_WINDOW the m rows of the batch; TXL_QUEUE the slots */
+    int64_t n_rows;            /* workgroups launched: TXL, ACC the n streams; ACC_WINDOW the m rows of the batch; TXL_QUEUE, ACC_QUEUE the slots */
     const float* logits;       /* f32 [n_rows, n_token] */
     int64_t n_token;           /* V <= 1024 */
     float temperature, top_p;  /* temperature > 0 */
     const float* u_steps;      /* f32 [n_u, ld_u] uniforms: draw d of stream r takes u_steps[d * ld_u + r] */
-    int64_t n_u, ld_u;         /* ld_u = the number of streams (TXL, ACC: >= n_rows; TXL_QUEUE: >= n_jobs) */
+    int64_t n_u, ld_u;         /* ld_u = the number of streams (TXL, ACC: >= n_rows; TXL_QUEUE, ACC_QUEUE: >= n_jobs) */
     const int32_t* ev_flags;   /* int32 [n_token]: EMO_TXL_EV_* / EMO_ACC_EV_* bits */
     const int32_t* ev_beat;    /* int32 [n_token] */
     const int32_t* params;     /* int32 [streams, 8] */
@@ -569,13 +599,15 @@ typedef struct {
     const int32_t* rows;       /* ACC_WINDOW: int32 [n_rows] or NULL */
     int64_t* win_tok;          /* ACC_WINDOW: int64 [n_rows, window] */
     int64_t* win_seg;          /* ACC_WINDOW: int64 [n_rows, window] */
-    /* (TXL_QUEUE alone; the last of the kind-specific fields: the optional outputs below stay the tail of the block) */
-    int32_t* slot_job;         /* TXL_QUEUE: int32 [n_rows]: the job of each slot, -1 = free */
-    int32_t* queue_head;       /* TXL_QUEUE: int32 [1]: the next job to hand out */
-    int64_t n_jobs;            /* TXL_QUEUE: rows of params, state, seq and the score tables; 0 < n_jobs <= ld_u */
-    int64_t* mem_lens;         /* TXL_QUEUE: int64 [n_rows]: the per-row lengths of the model's memory (the array the model step advances) */
-    int64_t mem_rows;          /* TXL_QUEUE: cache rows per row of the memory, > 0 */
-    int32_t* job_steps;        /* TXL_QUEUE: int32 [n_jobs] or NULL: per finished job, the launches it held a slot */
+    /* (the queue kinds alone, TXL_QUEUE and ACC_QUEUE; the last of the kind-specific fields: the optional outputs below stay the tail of the block) */
+    int32_t* slot_job;         /* queue kinds: int32 [n_rows]: the job of each slot, -1 = free */
+    int32_t* queue_head;       /* queue kinds: int32 [1]: the next job to hand out */
+    int64_t n_jobs;            /* queue kinds: rows of params, state, seq (segs) and the score tables; 0 < n_jobs <= ld_u */
+    int64_t* mem_lens;         /* TXL_QUEUE: int64 [n_rows]: the per-row lengths of the model's memory (the array the model step advances);
+                                * ACC_QUEUE: int64 [n_rows]: the per-row positions the model step reads (the decode engine's pos_dev) */
+    int64_t mem_rows;          /* TXL_QUEUE: cache rows per row of the memory, > 0; ACC_QUEUE: the position bound, > 0 */
+    int32_t* job_steps;        /* queue kinds: int32 [n_jobs] or NULL: per finished job, the launches it held a slot */
+    int32_t* row_reset;        /* ACC_QUEUE: int32 [n_rows], written every launch: 1 where the slot admitted a job in this launch, else 0 */
     /* --- all kinds, optional (NULL: not wanted; all three NULL: the launch is exactly the one without them).  What the model assigned to each
      * DRAWN token, taken from the logits row the draw was made from: tables [streams, ld_seq] laid out like seq.  When a draw is accepted and
      * appended at seq[r, c], cell [r, c] gets the figures of emo_token_scores (K9b) for that token at TEMPERATURE 1, whatever temperature the
@@ -589,7 +621,8 @@ typedef struct {
 } emo_grammar_step_t;
 /* sizeof(emo_grammar_step_t) as the library was built (a binding checks its mirror against it, as with emo_epilogue_size) */
 int emo_grammar_step_size(void);
-/* Messages name the kind: "emo_grammar_step[txl]: ", "emo_grammar_step[acc]: ", "emo_grammar_step[acc_window]: ", "emo_grammar_step[txl_queue]: ". */
+/* Messages name the kind: "emo_grammar_step[txl]: ", "emo_grammar_step[acc]: ", "emo_grammar_step[acc_window]: ", "emo_grammar_step[txl_queue]: ",
+ * "emo_grammar_step[acc_queue]: ". */
 int emo_grammar_step(const emo_grammar_step_t* args, emo_stream_t stream);
 /* counts[0..5] += {nonpad, nonpad&correct, chord, chord&correct, melody, melody&correct} (train.py:184-193) */
 int emo_accuracy_counts(const float* logits, const int64_t* tgt, const int64_t* chord,
