@@ -724,7 +724,7 @@ __device__ __forceinline__ int64_t row_argmax(const float* l, int64_t V, int lan
         if (x > best || (x != x && bi == INT64_MAX)) { best = x; bi = c; }  // first max wins inside a lane (ascending c)
     }
     wave_argmax(best, bi);
-    return bi;
+    return bi == INT64_MAX ? 0 : bi;          // a row of -inf only: nothing beats the start value; index 0, as numpy / torch argmax
 }
 __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ logits, int64_t rows, int64_t V, int64_t* __restrict__ out) {
     const int lane = threadIdx.x & 63;
@@ -790,6 +790,8 @@ __global__ __launch_bounds__(256) void accuracy_regs_kernel(const float* __restr
         }
         wave_argmax(ba, ia);
         wave_argmax(bb, ib);
+        if (ia == INT64_MAX) ia = 0;            // all -inf row, as row_argmax
+        if (ib == INT64_MAX) ib = 0;
         if (lane == 0) {
             const int64_t t0 = tgt[r0];
             const unsigned long long ok0 = (ia == t0);
