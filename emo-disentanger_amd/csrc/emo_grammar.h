@@ -28,6 +28,31 @@ __device__ __forceinline__ void emo_grammar_score(const emo_grammar_step_t& a, c
     if (tid == 0) emo_draw_scores_store(a.tok_logp, a.tok_rank, a.tok_entropy, r * a.ld_seq + c, logp, rank, entropy);
 }
 
+// Whether the block has any of the optional sampling controls (mask_of alone is not read).  emo_grammar_step asks on the host and launches the
+// kernel's <true> or <false> instance: without controls a launch runs the code it ran before they existed.
+__host__ __device__ __forceinline__ bool emo_grammar_has_controls(const emo_grammar_step_t& a) { return a.tok_mask || a.temp_of || a.top_p_of; }
+
+// What the draw of stream r runs under (r: the index of its params row: a stream, a job, or rows[b]): its ban row (NULL: none) and its
+// temperature / top_p.  CTL false: the block's two scalars, and the accessor of the draw folds to the plain load.  CTL true: temp_of / top_p_of
+// where present, and row mask_of[r] of tok_mask; a value outside [0, n_masks) is no mask, so nothing outside the table is ever read.
+struct emo_grammar_controls_t {
+    const uint32_t* ban;
+    float temp, top_p;
+};
+template <bool CTL>
+__device__ __forceinline__ emo_grammar_controls_t emo_grammar_controls(const emo_grammar_step_t& a, int64_t r) {
+    emo_grammar_controls_t c{nullptr, a.temperature, a.top_p};
+    if constexpr (CTL) {
+        if (a.tok_mask && a.mask_of) {
+            const int64_t m = a.mask_of[r];
+            if (m >= 0 && m < a.n_masks) c.ban = a.tok_mask + m * ((a.n_token + 31) >> 5);
+        }
+        if (a.temp_of) c.temp = a.temp_of[r];
+        if (a.top_p_of) c.top_p = a.top_p_of[r];
+    }
+    return c;
+}
+
 // The launches of the TXL and TXL_QUEUE kinds (emo_stage1_gen.hip), for emo_grammar_step, which has checked the block.
 int emo_txl_grammar_launch(const emo_grammar_step_t& a, emo_stream_t stream);
 int emo_txl_queue_launch(const emo_grammar_step_t& a, emo_stream_t stream);

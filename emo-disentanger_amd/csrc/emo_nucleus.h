@@ -8,6 +8,8 @@
 // unstable argsort produces (on tests/golden/sampling.json neither ascending nor descending index), so a tie group that straddles the cut keeps
 // its lowest indices here and an arbitrary subset of the same size there.  tests/test_gpu_sampling.py pins the rule and holds this header to a
 // float64 restatement (tests/nucleus_ref.py) with derived rounding bounds.
+// The logits are read through an accessor (emo_nucleus_draw_from): emo_plain_logits is the load itself, emo_banned_logits reads a banned token's
+// logit as -INFINITY and leaves the arithmetic alone, so a draw under a ban is bit for bit the plain draw from a row overwritten that way.
 #pragma once
 #include "emo_common.h"
 
@@ -54,10 +56,22 @@ __device__ __forceinline__ int64_t emo_nucleus_pick(int64_t V, float top_p, floa
     return tok;
 }
 
+// The logit accessors of the draw: l(c) = the logit of token c, c in [0, V).
+struct emo_plain_logits {
+    const float* __restrict__ row;
+    __device__ __forceinline__ float operator()(int c) const { return row[c]; }
+};
+// `ban` (NULL: no ban, the plain load): uint32 words, bit c & 31 of word c >> 5 set = token c is banned.  Only bits of c < V are ever read.
+struct emo_banned_logits {
+    const float* __restrict__ row;
+    const uint32_t* __restrict__ ban;
+    __device__ __forceinline__ float operator()(int c) const { return (ban && ((ban[c >> 5] >> (c & 31)) & 1u)) ? -INFINITY : row[c]; }
+};
+
 // tid in [0, 512); `sync` = a barrier over exactly the calling threads (+ any others that call it the same number of times).  Returns the picked
 // token id in thread 0 (other threads: undefined).  u = the uniform draw of this stream.
-template <typename Sync>
-__device__ __forceinline__ int64_t emo_nucleus_draw(const float* __restrict__ l, int64_t V, float temp, float top_p, float u, char* lds, int tid, Sync sync) {
+template <typename Logits, typename Sync>
+__device__ __forceinline__ int64_t emo_nucleus_draw_from(const Logits l, int64_t V, float temp, float top_p, float u, char* lds, int tid, Sync sync) {
     float* sp = (float*)lds;
     float* sq = sp + 1024 + 8;
     float* cumf = sq + 1024 + 8;
@@ -68,7 +82,7 @@ __device__ __forceinline__ int64_t emo_nucleus_draw(const float* __restrict__ l,
     const int Vp = ((int)V + 7) & ~7;
     const int lane = tid & 63, wave = tid >> 6;
     float mx = -INFINITY;
-    for (int c = tid; c < V; c += 512) mx = fmaxf(mx, l[c] / temp);
+    for (int c = tid; c < V; c += 512) mx = fmaxf(mx, l(c) / temp);
     mx = wave_max(mx);
     if (lane == 0) red[wave] = mx;
     sync();
@@ -76,7 +90,7 @@ __device__ __forceinline__ int64_t emo_nucleus_draw(const float* __restrict__ l,
     sync();
     float s = 0.f;
     for (int c = tid; c < V; c += 512) {
-        const float e = expf(l[c] / temp - mx);
+        const float e = expf(l(c) / temp - mx);
         sp[c] = e;
         s += e;
     }
@@ -143,4 +157,10 @@ __device__ __forceinline__ int64_t emo_nucleus_draw(const float* __restrict__ l,
     }
     sync();
     return emo_nucleus_pick(V, top_p, u, lds, tid, sync);
+}
+
+// The draw from a plain row of logits.
+template <typename Sync>
+__device__ __forceinline__ int64_t emo_nucleus_draw(const float* __restrict__ l, int64_t V, float temp, float top_p, float u, char* lds, int tid, Sync sync) {
+    return emo_nucleus_draw_from(emo_plain_logits{l}, V, temp, top_p, u, lds, tid, sync);
 }

@@ -10,6 +10,9 @@
 // When the caller wants them (tok_logp / tok_rank / tok_entropy), an accepted draw's figures go to the cell of the token it appended: from the
 // same logits row at temperature 1 — the key draw too, which draws at key_temperature — by the whole workgroup (emo_draw_scores.h), so thread 0
 // publishes the accepted column and word through LDS.  A rejection records nothing.
+// The optional sampling controls (tok_mask / mask_of / temp_of / top_p_of, indexed by the stream r as params is: emo_grammar_controls) reach the
+// draw alone: a banned token's logit is read as -inf there, the scores above are still taken from the row as the model wrote it, and primer
+// tokens are fed whether banned or not.
 #include "emo_grammar.h"
 
 namespace {
@@ -79,7 +82,8 @@ __device__ __forceinline__ int32_t txl_grammar(const emo_grammar_step_t& a, int6
 
 // One token step of stream r (kind TXL: a stream of the batch; kind TXL_QUEUE: a job) in batch row b, whose logits row it draws from and whose
 // next input it writes, after emo_grammar_open has brought the stream's words to sst / spr and found it RUNNING.  All 512 threads call it; every
-// barrier inside lies on a path that sst, spr and the launch arguments alone decide.
+// barrier inside lies on a path that sst, spr and the launch arguments alone decide.  CTL: the block has sampling controls (emo_grammar_controls).
+template <bool CTL>
 __device__ __forceinline__ void txl_stream_step(const emo_grammar_step_t& a, int64_t b, int64_t r, char* lds, const int32_t* sst, const int32_t* spr,
                                                 int32_t* sacc, float* sred, int tid) {
     int32_t* st = a.state + r * EMO_TXL_STATE_WORDS;
@@ -102,8 +106,9 @@ __device__ __forceinline__ void txl_stream_step(const emo_grammar_step_t& a, int
     }
     const int32_t len = sst[EMO_TXL_S_LEN];
     const bool key_step = spr[EMO_TXL_P_KEYED] != 0 && len == 1;          // the event after the emotion tag is the key (:81-89)
-    const int64_t word = emo_nucleus_draw(a.logits + b * a.n_token, a.n_token, key_step ? a.key_temperature : a.temperature,
-                                          key_step ? a.key_top_p : a.top_p, a.u_steps[(int64_t)draws * a.ld_u + r], lds, tid, [] { __syncthreads(); });
+    const emo_grammar_controls_t ctl = emo_grammar_controls<CTL>(a, r);  // (the key draw keeps key_temperature / key_top_p; the ban holds for it too)
+    const int64_t word = emo_nucleus_draw_from(emo_banned_logits{a.logits + b * a.n_token, ctl.ban}, a.n_token, key_step ? a.key_temperature : ctl.temp,
+                                               key_step ? a.key_top_p : ctl.top_p, a.u_steps[(int64_t)draws * a.ld_u + r], lds, tid, [] { __syncthreads(); });
     if (!emo_grammar_wants_scores(a)) {
         if (tid == 0) txl_grammar(a, b, row, st, sst, spr, word, draws, key_step, len);
         return;
@@ -116,6 +121,7 @@ __device__ __forceinline__ void txl_stream_step(const emo_grammar_step_t& a, int
     if (sacc[0] >= 0) emo_grammar_score(a, a.logits + b * a.n_token, r, sacc[0], sacc[1], sred, tid);
 }
 
+template <bool CTL>
 __global__ __launch_bounds__(512) void txl_grammar_kernel(const emo_grammar_step_t a) {
     __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
     __shared__ int32_t sst[EMO_TXL_STATE_WORDS], spr[EMO_TXL_PARAM_WORDS];
@@ -125,7 +131,7 @@ __global__ __launch_bounds__(512) void txl_grammar_kernel(const emo_grammar_step
     const int64_t r = blockIdx.x;
     emo_grammar_open(a.state + r * EMO_TXL_STATE_WORDS, EMO_TXL_STATE_WORDS, a.params + r * EMO_TXL_PARAM_WORDS, EMO_TXL_PARAM_WORDS, sst, spr, tid);
     if (sst[EMO_TXL_S_STATUS] != EMO_TXL_RUNNING) return;
-    txl_stream_step(a, r, r, lds, sst, spr, sacc, sred, tid);
+    txl_stream_step<CTL>(a, r, r, lds, sst, spr, sacc, sred, tid);
 }
 
 // Thread 0 of slot b, whose job (if it had one) is over: the next queued job that is RUNNING, or none.  queue_head only grows, so a slot that
@@ -148,6 +154,7 @@ __device__ __forceinline__ void txl_queue_admit(const emo_grammar_step_t& a, int
     }
 }
 
+template <bool CTL>
 __global__ __launch_bounds__(512) void txl_queue_kernel(const emo_grammar_step_t a) {
     __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
     __shared__ int32_t sst[EMO_TXL_STATE_WORDS], spr[EMO_TXL_PARAM_WORDS];
@@ -174,7 +181,7 @@ __global__ __launch_bounds__(512) void txl_queue_kernel(const emo_grammar_step_t
                 atomicSub(a.running, 1);
             }
         } else {
-            txl_stream_step(a, b, j, lds, sst, spr, sacc, sred, tid);
+            txl_stream_step<CTL>(a, b, j, lds, sst, spr, sacc, sred, tid);
         }
     }
     if (tid == 0 && st[EMO_TXL_S_STATUS] != EMO_TXL_RUNNING) {      // (thread 0 reads what it wrote itself)
@@ -186,13 +193,15 @@ __global__ __launch_bounds__(512) void txl_queue_kernel(const emo_grammar_step_t
 }  // namespace
 
 int emo_txl_grammar_launch(const emo_grammar_step_t& a, emo_stream_t stream) {
-    hipLaunchKernelGGL(txl_grammar_kernel, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
+    if (emo_grammar_has_controls(a)) hipLaunchKernelGGL(txl_grammar_kernel<true>, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(txl_grammar_kernel<false>, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
     EMO_LAUNCH_CHECK();
     return EMO_OK;
 }
 
 int emo_txl_queue_launch(const emo_grammar_step_t& a, emo_stream_t stream) {
-    hipLaunchKernelGGL(txl_queue_kernel, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
+    if (emo_grammar_has_controls(a)) hipLaunchKernelGGL(txl_queue_kernel<true>, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(txl_queue_kernel<false>, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
     EMO_LAUNCH_CHECK();
     return EMO_OK;
 }

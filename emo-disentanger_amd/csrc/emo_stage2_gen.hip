@@ -19,6 +19,9 @@
 // temperature 1, go to the cell of the token it appended (emo_draw_scores.h) — after the draw loop has ended, since the redraws read the sorted
 // state, and by the whole workgroup: whether and where a draw was accepted is read from the LDS state words thread 0 wrote before the loop's
 // last barrier.
+// All kinds, optional sampling controls (tok_mask / mask_of / temp_of / top_p_of, indexed by the stream r as params is: emo_grammar_controls): a
+// banned token's logit is read as -inf by the draw and by nothing else: the scores above are still the model's, from the row as it wrote it, and
+// primer tokens, injected bars and track_full are fed whether banned or not.
 #include "emo_grammar.h"
 
 namespace {
@@ -26,8 +29,9 @@ namespace {
 // The draws of one launch of one stream, shared by the in-window and the windowed step: draw until the grammar accepts or ends the stream.
 // `draws` advances in every thread alike, and thread 0 runs the grammar on the LDS copy of the state (kept there, not in registers, across the
 // draws); it alone gets the status back (the other threads: RUNNING).  Besides the block, what differs per call: lr the stream's logits row,
-// u_col its column of the uniform table (pitch a.ld_u), row / srow its token and segment rows.
-__device__ __forceinline__ int32_t acc_draw(const emo_grammar_step_t& a, const float* __restrict__ lr, const float* __restrict__ u_col,
+// u_col its column of the uniform table (pitch a.ld_u), row / srow its token and segment rows, ctl its sampling controls (emo_grammar_controls:
+// the ban reaches the first draw's sort, which the redraws reuse; the scores are taken from lr as the model wrote it).
+__device__ __forceinline__ int32_t acc_draw(const emo_grammar_step_t& a, const emo_grammar_controls_t ctl, const float* __restrict__ lr, const float* __restrict__ u_col,
                                             int64_t* __restrict__ row, int64_t* __restrict__ srow, const int32_t* spr, int32_t* sst, int32_t* sagain_p,
                                             char* lds, int tid, int32_t& draws) {
     const int64_t V = a.n_token, ld_seq = a.ld_seq;
@@ -42,8 +46,8 @@ __device__ __forceinline__ int32_t acc_draw(const emo_grammar_step_t& a, const f
         // a redraw from the same logits needs only the cut and the pick over the sorted state the first draw left in LDS (the same operations
         // on the same data: the id a fresh emo_nucleus_draw with this uniform would give)
         const float u = u_col[(int64_t)draws * a.ld_u];
-        const int64_t word = draws == draws0 ? emo_nucleus_draw(lr, V, a.temperature, a.top_p, u, lds, tid, [] { __syncthreads(); })
-                                            : emo_nucleus_pick(V, a.top_p, u, lds, tid, [] { __syncthreads(); });
+        const int64_t word = draws == draws0 ? emo_nucleus_draw_from(emo_banned_logits{lr, ctl.ban}, V, ctl.temp, ctl.top_p, u, lds, tid, [] { __syncthreads(); })
+                                            : emo_nucleus_pick(V, ctl.top_p, u, lds, tid, [] { __syncthreads(); });
         ++draws;
         if (tid == 0) {
             const int32_t fl = a.ev_flags[word], target = spr[EMO_ACC_P_TARGET_BARS], bars = sst[EMO_ACC_S_BARS];
@@ -108,6 +112,8 @@ __device__ __forceinline__ int32_t acc_draw(const emo_grammar_step_t& a, const f
 // One token step of stream r (kind ACC: a stream of the batch; kind ACC_QUEUE: a job) in batch row b, whose logits row it draws from and whose
 // next input it writes, after emo_grammar_open has brought the stream's words to sst / spr and found it RUNNING.  All 512 threads call it; every
 // barrier inside lies on a path that sst, spr and the launch arguments alone decide.  Thread 0 leaves the stream's state words in memory.
+// CTL: the block has sampling controls (emo_grammar_controls).
+template <bool CTL>
 __device__ __forceinline__ void acc_stream_step(const emo_grammar_step_t& a, int64_t b, int64_t r, char* lds, int32_t* sst, const int32_t* spr,
                                                 int32_t* sagain, float* sred, int tid) {
     int32_t* st = a.state + r * EMO_ACC_STATE_WORDS;
@@ -135,7 +141,7 @@ __device__ __forceinline__ void acc_stream_step(const emo_grammar_step_t& a, int
     // (read before thread 0 can have touched the state: it writes only behind the barriers of the first draw)
     const bool scores = emo_grammar_wants_scores(a);
     const int32_t len0 = scores ? sst[EMO_ACC_S_LEN] : 0, acc0 = scores ? sst[EMO_ACC_S_ACCEPTED] : 0;
-    const int32_t status = acc_draw(a, a.logits + b * a.n_token, a.u_steps + r, row, srow, spr, sst, sagain, lds, tid, draws);
+    const int32_t status = acc_draw(a, emo_grammar_controls<CTL>(a, r), a.logits + b * a.n_token, a.u_steps + r, row, srow, spr, sst, sagain, lds, tid, draws);
     // an acceptance appended its word at the old length (an injected bar follows it) and counted itself, in front of the loop's last barrier
     if (scores && sst[EMO_ACC_S_ACCEPTED] != acc0) emo_grammar_score(a, a.logits + b * a.n_token, r, len0, row[len0], sred, tid);
     if (tid != 0) return;
@@ -154,6 +160,7 @@ __device__ __forceinline__ void acc_stream_step(const emo_grammar_step_t& a, int
     for (int i = 0; i < EMO_ACC_STATE_WORDS; ++i) st[i] = sst[i];
 }
 
+template <bool CTL>
 __global__ __launch_bounds__(512) void acc_grammar_kernel(const emo_grammar_step_t a) {
     __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
     __shared__ int32_t sst[EMO_ACC_STATE_WORDS], spr[EMO_ACC_PARAM_WORDS], sagain;
@@ -168,7 +175,7 @@ __global__ __launch_bounds__(512) void acc_grammar_kernel(const emo_grammar_step
         }
         return;
     }
-    acc_stream_step(a, r, r, lds, sst, spr, &sagain, sred, tid);
+    acc_stream_step<CTL>(a, r, r, lds, sst, spr, &sagain, sred, tid);
 }
 
 // Thread 0 of slot b, whose job (if it had one) is over: the next queued job that is RUNNING, or none.  queue_head only grows, so a slot that
@@ -196,6 +203,7 @@ __device__ __forceinline__ void acc_queue_admit(const emo_grammar_step_t& a, int
     }
 }
 
+template <bool CTL>
 __global__ __launch_bounds__(512) void acc_queue_kernel(const emo_grammar_step_t a) {
     __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
     __shared__ int32_t sst[EMO_ACC_STATE_WORDS], spr[EMO_ACC_PARAM_WORDS], sagain, sslot;
@@ -218,7 +226,7 @@ __global__ __launch_bounds__(512) void acc_queue_kernel(const emo_grammar_step_t
                 atomicSub(a.running, 1);
             }
         } else {
-            acc_stream_step(a, b, j, lds, sst, spr, &sagain, sred, tid);
+            acc_stream_step<CTL>(a, b, j, lds, sst, spr, &sagain, sred, tid);
         }
     }
     if (tid != 0) return;
@@ -231,6 +239,7 @@ __global__ __launch_bounds__(512) void acc_queue_kernel(const emo_grammar_step_t
     }
 }
 
+template <bool CTL>
 __global__ __launch_bounds__(512) void acc_window_kernel(const emo_grammar_step_t a) {
     __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
     __shared__ int32_t sst[EMO_ACC_STATE_WORDS], spr[EMO_ACC_PARAM_WORDS], sagain;
@@ -255,7 +264,7 @@ __global__ __launch_bounds__(512) void acc_window_kernel(const emo_grammar_step_
     int32_t draws = sst[EMO_ACC_S_DRAWS];
     const bool scores = emo_grammar_wants_scores(a);         // as in acc_grammar_kernel; the tables are indexed by the stream r, the logits by b
     const int32_t len0 = scores ? sst[EMO_ACC_S_LEN] : 0, acc0 = scores ? sst[EMO_ACC_S_ACCEPTED] : 0;
-    const int32_t status = acc_draw(a, a.logits + b * a.n_token, a.u_steps + r, row, srow, spr, sst, &sagain, lds, tid, draws);
+    const int32_t status = acc_draw(a, emo_grammar_controls<CTL>(a, r), a.logits + b * a.n_token, a.u_steps + r, row, srow, spr, sst, &sagain, lds, tid, draws);
     if (scores && sst[EMO_ACC_S_ACCEPTED] != acc0) emo_grammar_score(a, a.logits + b * a.n_token, r, len0, row[len0], sred, tid);
     if (tid == 0) {
         if (status != EMO_ACC_RUNNING) atomicSub(a.running, 1);
@@ -300,9 +309,11 @@ extern "C" int emo_grammar_step(const emo_grammar_step_t* args, emo_stream_t str
         return tq ? emo_txl_queue_launch(a, stream) : emo_txl_grammar_launch(a, stream);
     }
     EMO_CHECK(a.temperature > 0.f, "emo_grammar_step[%s]: temperature must be > 0", name);
-    if (aq) hipLaunchKernelGGL(acc_queue_kernel, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
-    else if (acc) hipLaunchKernelGGL(acc_grammar_kernel, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(acc_window_kernel, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
+    // (the <false> instances are the kernels as they were before the sampling controls: a block without any launches those)
+    const bool ctl = emo_grammar_has_controls(a);
+    const auto kernel = aq ? (ctl ? acc_queue_kernel<true> : acc_queue_kernel<false>) : acc ? (ctl ? acc_grammar_kernel<true> : acc_grammar_kernel<false>)
+                                                                                            : (ctl ? acc_window_kernel<true> : acc_window_kernel<false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
     EMO_LAUNCH_CHECK();
     return EMO_OK;
 }

@@ -1,6 +1,9 @@
 """What the device generation loops that drive emo_grammar_step share (stage1_inference.LeadSheetLoop / LeadSheetQueue, inference.AccompanimentLoop
 / WindowedLoop): the launch's argument block and the draw-score tables behind it, the grammar launch, the running count, the replay phase of a
 run and the read-back of the recorded scores.  A subclass brings its tables, its model step (one_step) and what its run() does after the replays."""
+import numbers
+
+import numpy as np
 import torch
 
 from . import ops
@@ -13,9 +16,141 @@ def check_vocab(who, V):
         raise EmoError('%s: the device draw takes V <= 1024 (got %d)' % (who, V))
 
 
+def mask_words(V):
+    """Words of one row of the ban table (emo_hip.h: tok_mask): ceil(V / 32)."""
+    return (int(V) + 31) // 32
+
+
+def pack_token_masks(bans, V):
+    """Per-stream bans (None, or ids in [0, V)) -> (tok_mask uint32 [n_masks, mask_words(V)], mask_of int32 [n]) as the grammar launch reads
+    them: bit v & 31 of word v >> 5 of row mask_of[r] set = token v is banned for stream r's draws; mask_of[r] = -1: no mask.  Equal bans
+    share a row (rows in the order of first use); a stream without a ban, or with an empty one, has none."""
+    rows, at, mask_of = [], {}, np.full(len(bans), -1, np.int32)
+    for r, ban in enumerate(bans):
+        ids = tuple(sorted(set(int(v) for v in ban))) if ban is not None else ()
+        if not ids:
+            continue
+        if ids[0] < 0 or ids[-1] >= V:
+            raise ValueError('banned token id %d is outside [0, %d)' % (ids[0] if ids[0] < 0 else ids[-1], V))
+        if ids not in at:
+            at[ids] = len(rows)
+            row = np.zeros(mask_words(V), np.uint32)
+            v = np.array(ids, np.int64)
+            np.bitwise_or.at(row, v >> 5, (np.uint32(1) << (v & 31).astype(np.uint32)))
+            rows.append(row)
+        mask_of[r] = at[ids]
+    mask = np.stack(rows) if rows else np.zeros((0, mask_words(V)), np.uint32)
+    return mask, mask_of
+
+
+class DrawControls:
+    """The per-stream sampling controls of a device generation loop, checked: bans[r] (None, or the sorted ids stream r never draws), temps /
+    top_ps (one float per stream, or None where the caller gave one value for all: then `temp` / `top_p`, the launch's scalars, hold)."""
+
+    def __init__(self, n, V, bans, temp, temps, top_p, top_ps):
+        self.n, self.V, self.bans, self.temp, self.temps, self.top_p, self.top_ps = n, V, bans, temp, temps, top_p, top_ps
+
+    @property
+    def temp_arg(self):
+        """What the caller gave as `temp`, in the checked form: the per-stream list, or the one value."""
+        return self.temp if self.temps is None else list(self.temps)
+
+    @property
+    def top_p_arg(self):
+        return self.top_p if self.top_ps is None else list(self.top_ps)
+
+    def temp_at(self, r):
+        return self.temp if self.temps is None else self.temps[r]
+
+    def top_p_at(self, r):
+        return self.top_p if self.top_ps is None else self.top_ps[r]
+
+    def take(self, idx):
+        """The controls of the streams `idx` (a list of stream indices, repeats allowed), in that order: candidates of an input under best_of,
+        the streams a windowed loop takes over."""
+        pick = lambda v: None if v is None else [v[i] for i in idx]          # noqa: E731
+        return DrawControls(len(idx), self.V, [self.bans[i] for i in idx], self.temp, pick(self.temps), self.top_p, pick(self.top_ps))
+
+    def repeat(self, k):
+        """Every stream k times in a row: stream i * k + c has the controls of input i (scoring.best_of_plan's order)."""
+        return self.take([i for i in range(self.n) for _ in range(k)])
+
+    def tables(self):
+        """-> the optional fields of emo_grammar_step_t that are present, as numpy: {'tok_mask' uint32 [n_masks, words], 'mask_of' int32 [n]}
+        when a stream has a ban, {'temp_of'} / {'top_p_of'} f32 [n] when the caller gave per-stream values.  {} = every new field NULL."""
+        out = {}
+        if any(b is not None for b in self.bans):
+            out['tok_mask'], out['mask_of'] = pack_token_masks(self.bans, self.V)
+        if self.temps is not None:
+            out['temp_of'] = np.array(self.temps, np.float32)
+        if self.top_ps is not None:
+            out['top_p_of'] = np.array(self.top_ps, np.float32)
+        return out
+
+
+def _is_id(v):
+    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+
+
+def _per_input(who, name, value, n, ok, rule):
+    """A number for all inputs, or one per input -> (the number, None) or (the first, the list of n floats); each checked by `ok`."""
+    if isinstance(value, numbers.Real):
+        vals, per = [float(value)], None
+    else:
+        try:
+            vals = [float(v) for v in value]
+        except TypeError:
+            raise ValueError('%s: %s must be a number or one number per input (got %r)' % (who, name, value))
+        if len(vals) != n:
+            raise ValueError('%s: %s has %d entries for %d inputs' % (who, name, len(vals), n))
+        per = vals
+    for v in vals:
+        if not ok(v):
+            raise ValueError('%s: %s must be %s (got %r)' % (who, name, rule, v))
+    return vals[0], per
+
+
+def draw_controls(who, n, V, banned=None, temp=1.2, top_p=0.9):
+    """The sampling controls of n inputs over a vocabulary of V tokens (read only where there is a ban), checked before anything is allocated
+    -> DrawControls.  banned: None (no ban), one sequence of token ids (for every input), or one entry per input, each a sequence of ids or
+    None; temp / top_p: a number, or one per input.  ValueError for an id outside [0, V), a ban that leaves no token, a per-input list of the
+    wrong length, a temperature <= 0, a top_p outside (0, 1]."""
+    if banned is None:
+        bans = [None] * n
+    else:
+        banned = list(banned)
+        if all(_is_id(v) for v in banned):                       # one ban for every input (an empty one bans nothing)
+            bans = [banned] * n
+        elif any(_is_id(v) for v in banned):
+            raise ValueError('%s: banned mixes token ids and per-input entries' % who)
+        elif len(banned) != n:
+            raise ValueError('%s: banned has %d entries for %d inputs' % (who, len(banned), n))
+        else:
+            bans = banned
+    checked = []
+    for i, ban in enumerate(bans):
+        if ban is None:
+            checked.append(None)
+            continue
+        ban = list(ban)
+        if not all(_is_id(v) for v in ban):
+            raise ValueError('%s: banned[%d] is not a sequence of token ids' % (who, i))
+        ids = tuple(sorted(set(int(v) for v in ban)))
+        if ids and (ids[0] < 0 or ids[-1] >= V):
+            raise ValueError('%s: banned token id %d is outside [0, %d)' % (who, ids[0] if ids[0] < 0 else ids[-1], V))
+        if len(ids) >= V:
+            raise ValueError('%s: banned[%d] bans every token' % (who, i))
+        checked.append(ids or None)
+    t, ts = _per_input(who, 'temp', temp, n, lambda v: v > 0 and v == v and v != float('inf'), '> 0')
+    p, ps = _per_input(who, 'top_p', top_p, n, lambda v: 0 < v <= 1, 'in (0, 1]')
+    return DrawControls(n, V, checked, t, ts, p, ps)
+
+
 class GrammarLoop:
     """Expects of a subclass: self.dev, self.seq and self.running before _build_block; one_step() before _replay."""
     score_tables = None
+    controls = None                      # DrawControls of the loop's streams (None: a loop built without any)
+    control_tables = None                # the device tensors behind the block's tok_mask / mask_of / temp_of / top_p_of ({}: all NULL)
     replayed = (0, 0.0)                  # (steps, seconds) of the last run's replays
 
     def _to_device(self, *arrays):
@@ -25,12 +160,21 @@ class GrammarLoop:
     def _upload_events(self, flags, beat):
         self.ev_flags, self.ev_beat = self._to_device(flags, beat)
 
-    def _build_block(self, kind, scores, **fields):
+    def _build_block(self, kind, scores, controls=None, **fields):
         """The grammar launch's argument block (emo_hip.h: emo_grammar_step_t), written once: _gheld keeps what its addresses point to alive,
-        the score tables (self.score_tables: ops.draw_score_tables laid out like self.seq, None without `scores`) included.  No tensor of the
-        block is allocated again after this: captured graphs hold the raw addresses."""
+        the score tables (self.score_tables: ops.draw_score_tables laid out like self.seq, None without `scores`) included, and the tables of
+        `controls` (a DrawControls over the streams that `params` holds, or None: self.control_tables, {} where every one of the block's
+        optional tok_mask / mask_of / temp_of / top_p_of stays NULL).  No tensor of the block is allocated again after this: captured graphs
+        hold the raw addresses."""
         self._gargs, self._gheld = ops.GrammarStep(kind=kind), {}
         ops.block_set(self._gargs, self._gheld, **fields)
+        self.controls = controls
+        tabs = controls.tables() if controls is not None else {}
+        if 'tok_mask' in tabs:                                   # (torch has no arithmetic on uint32: the words travel as int32, bit for bit)
+            tabs['tok_mask'] = tabs['tok_mask'].view(np.int32)
+        self.control_tables = dict(zip(tabs, self._to_device(*tabs.values())))
+        if tabs:
+            ops.block_set(self._gargs, self._gheld, n_masks=len(tabs['tok_mask']) if 'tok_mask' in tabs else 0, **self.control_tables)
         self.score_tables = ops.draw_score_tables(self.seq) if scores else None
         if scores:
             ops.block_set(self._gargs, self._gheld, **self.score_tables)

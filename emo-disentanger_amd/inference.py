@@ -19,7 +19,7 @@ import torch
 
 from . import engine, ops, scoring
 from ._lib import EmoError
-from .gen_loop import GrammarLoop, check_vocab
+from .gen_loop import GrammarLoop, check_vocab, draw_controls
 from .replay import StepReplayer, graph_steps
 
 max_dec_inp_len = 2048
@@ -845,6 +845,13 @@ def pack_lead_sheets(lead_sheets):
     return np.array(toks or [0], np.int64), np.array(offs, np.int32), bar0, nbars, longest
 
 
+def tempo_ban(event2idx, tempo, tolerance=20):
+    """The ids of the tempo events further than `tolerance` from `tempo`: every key of event2idx that contains 'Tempo' and not 'Conti' and
+    whose trailing integer differs from tempo by more than tolerance.  As `banned` of generate_accompaniments (or `inadmissibles` of the host
+    loops) it keeps the drawn tempi within tempo +- tolerance."""
+    return sorted(i for e, i in event2idx.items() if 'Tempo' in e and 'Conti' not in e and abs(int(e.rsplit('_', 1)[-1]) - tempo) > tolerance)
+
+
 def _refuse(model, inadmissibles):
     if inadmissibles is not None:
         raise ValueError('generate_accompaniments: `inadmissibles` is not supported by the device grammar')
@@ -875,14 +882,14 @@ class AccompanimentLoop(GrammarLoop):
     NumPy's, made from host probabilities, and are not recorded."""
 
     def __init__(self, model, event2idx, idx2event, lead_sheets, primers, max_events=10000, skip_check=False, max_bars=None, temp=1.2, top_p=0.9,
-                 seed=0, n_u=None, persistent=True, redraw=True, scores=False):
-        self._load_jobs(model, event2idx, idx2event, lead_sheets, primers, max_events, skip_check, max_bars, temp, top_p, None)
+                 seed=0, n_u=None, persistent=True, redraw=True, scores=False, banned=None):
+        self._load_jobs(model, event2idx, idx2event, lead_sheets, primers, max_events, skip_check, max_bars, temp, top_p, None, banned)
         n, dev, V = self.n, self.dev, model.n_token
         self.U = uniform_table(int(n_u or 4 * self.W), n, seed, dev)
         self.tok = torch.zeros(n, dtype=torch.int64, device=dev)
         self.segv = torch.ones(n, dtype=torch.int64, device=dev)
         self.logits = torch.empty(n, V, dtype=torch.float32, device=dev)
-        self._build_block(ops.GRAMMAR_ACC, scores, **self._block_fields(n))
+        self._build_block(ops.GRAMMAR_ACC, scores, self.job_controls, **self._block_fields(n))
         self.windowed = None
         with torch.no_grad():
             eng = self._make_engine(n, persistent, redraw)
@@ -894,14 +901,16 @@ class AccompanimentLoop(GrammarLoop):
         self.bound = min(self.W, pe)           # the engine never runs a step at a position >= bound (the one-launch GPT-2 step would clamp it)
         self.pos = self.L0                     # host count of the engine position (every row advances one per step)
 
-    def _load_jobs(self, model, event2idx, idx2event, lead_sheets, primers, max_events, skip_check, max_bars, temp, top_p, consumed):
-        """n, model, dev, W and the draw parameters; the grammar tables, the packed lead sheets and, per stream, its _Stream and its token / segment
+    def _load_jobs(self, model, event2idx, idx2event, lead_sheets, primers, max_events, skip_check, max_bars, temp, top_p, consumed, banned=None):
+        """n, model, dev, W and the draw parameters (job_controls: gen_loop.draw_controls of temp / top_p / banned, each one value for all streams
+        or one per stream, checked before anything is allocated; temp / top_p: the launch's scalars); the grammar tables, the packed lead sheets and, per stream, its _Stream and its token / segment
         rows, parameters and state on the device, state[CONSUMED] = `consumed` (None: the shortest prompt's length L0, the prefix a prefill
         takes); the running count."""
         n = self.n = len(lead_sheets)
         assert n == len(primers) and n > 0
         _refuse(model, None)
-        self.model, self.temp, self.top_p = model, float(temp), float(top_p)
+        ctl = self.job_controls = draw_controls('generate_accompaniments', n, model.n_token, banned, temp, top_p)
+        self.model, self.temp, self.top_p = model, ctl.temp, ctl.top_p
         self.max_events = int(max_events)
         self.W = int(max_dec_inp_len)                 # read at call time (tests lower it)
         dev = self.dev = next(model.parameters()).device
@@ -1006,8 +1015,10 @@ class AccompanimentLoop(GrammarLoop):
             elif st == ACC_WINDOW:
                 s = self.handed_off(i, state, seq, segs)
                 rs = np.random.RandomState([seed, i])
-                out.append(_resume_windowed(self.model, event2idx, idx2event, s, max_events, skip_check, self.temp, None,
-                                            lambda probs, rs=rs: nucleus(probs, self.top_p, rng=rs)))
+                ctl = self.job_controls                      # the stream keeps its controls: the host loop's `inadmissibles` is its ban
+                out.append(_resume_windowed(self.model, event2idx, idx2event, s, max_events, skip_check, ctl.temp_at(i),
+                                            list(ctl.bans[i]) if ctl.bans[i] else None,
+                                            lambda probs, rs=rs, p=ctl.top_p_at(i): nucleus(probs, p, rng=rs)))
             else:
                 out.append(_stream_result(st, [int(t) for t in seq[i, :ln]], 'stream %d used all %d uniforms of its table' % (i, self.U.shape[0]),
                                           'stream %d: token row or lead-sheet table too short' % i,
@@ -1053,12 +1064,12 @@ class AccompanimentQueue(AccompanimentLoop):
     queued (a k-step replay ends up to k - 1 launches past the drain)."""
 
     def __init__(self, model, event2idx, idx2event, lead_sheets, primers, slots, max_events=10000, skip_check=False, max_bars=None, temp=1.2,
-                 top_p=0.9, seed=0, n_u=None, persistent=True, redraw=True, scores=False):
+                 top_p=0.9, seed=0, n_u=None, persistent=True, redraw=True, scores=False, banned=None):
         slots = self.slots = int(slots)
         if slots < 1:
             raise ValueError('slots must be at least 1 (got %d)' % slots)
         # CONSUMED 1 is what an admission sets: the first token goes out with it
-        self._load_jobs(model, event2idx, idx2event, lead_sheets, primers, max_events, skip_check, max_bars, temp, top_p, 1)
+        self._load_jobs(model, event2idx, idx2event, lead_sheets, primers, max_events, skip_check, max_bars, temp, top_p, 1, banned)
         n, dev, V = self.n, self.dev, model.n_token
         if model.use_pe and model.pe.pe.shape[0] < self.W:
             raise EmoError('generate_accompaniments(slots=): the positional table has %d rows, fewer than the window of %d tokens'
@@ -1078,7 +1089,7 @@ class AccompanimentQueue(AccompanimentLoop):
             eng.pos_dev.zero_()
             eng.dev_pos0, eng.pos_auto = 0, False                # position = pos_dev[b], written by the grammar launch
             self.state_table = eng.start_empty() if model.kind == 'performer' else None
-        self._build_block(ops.GRAMMAR_ACC_QUEUE, scores, n_jobs=n, mem_rows=self.bound, slot_job=self.slot_job, queue_head=self.queue_head,
+        self._build_block(ops.GRAMMAR_ACC_QUEUE, scores, self.job_controls, n_jobs=n, mem_rows=self.bound, slot_job=self.slot_job, queue_head=self.queue_head,
                           mem_lens=eng.pos_dev, row_reset=self.row_reset, job_steps=self.job_steps_dev, **self._block_fields(slots))
         # no job is fed more tokens than the window holds, so the queue is drained before this many launches whatever the slots do: a budget
         # for the replayer, not a limit that is meant to bind (the per-job limit is the kernel's WINDOW)
@@ -1166,7 +1177,7 @@ class WindowedLoop(GrammarLoop):
         self.fwd_kw = {'attn_kwargs': {'omit_feature_map_draw': True}} if self.model.kind == 'performer' else {}
         self.batch_rows, self.steps, self.seconds = [], 0, 0.0
         # the windowed step's block, written once for the full batch; _set_rows keeps n_rows / rows current
-        self._build_block(ops.GRAMMAR_ACC_WINDOW, loop.score_tables is not None, n_rows=m0, n_token=self.model.n_token, ld_u=m0,
+        self._build_block(ops.GRAMMAR_ACC_WINDOW, loop.score_tables is not None, loop.job_controls.take(self.idx), n_rows=m0, n_token=self.model.n_token, ld_u=m0,
                           temperature=self.temp, top_p=self.top_p, window=W, track_full=loop.track_full, logits=self.logits, u_steps=self.U,
                           ev_flags=loop.ev_flags, ev_beat=loop.ev_beat, lead_tok=loop.lead_tok, lead_off=loop.lead_off, params=self.params,
                           state=self.state, seq=self.seq, segs=self.segs, win_tok=self.win_tok, win_seg=self.win_seg, running=self.running)
@@ -1235,7 +1246,8 @@ class WindowedLoop(GrammarLoop):
 
 
 def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, max_events=10000, skip_check=False, max_bars=None, temp=1.2, top_p=0.9,
-                            inadmissibles=None, seed=0, use_graph=True, best_of=1, window='host', best_by='forward', return_scores=False, slots=None):
+                            inadmissibles=None, seed=0, use_graph=True, best_of=1, window='host', best_by='forward', return_scores=False, slots=None,
+                            banned=None):
     """The throughput path of generate_conditional_batch: the same arguments (no per-stream samplers) and result per stream, every draw and
     the grammar of _Stream.offer on the device (emo_grammar_step), each token step = grammar launch + one engine step (the one-launch
     persistent step where the engine has one), k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS, default 16) and replayed until
@@ -1275,7 +1287,17 @@ def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, m
     the uniform table, so its ids do not depend on S or on the slot it ran in beyond what the model step's arithmetic does; they are not those
     of slots = None, whose streams share a prefill.  All jobs run under the engine's one set of feature maps.  A job that reaches the window
     frees its slot and is finished after the queue has drained, by `window` as above.  Refused (EmoError) when the model's positional table has
-    fewer rows than the window.  The results, best_of, best_by and return_scores are per job as they are per stream."""
+    fewer rows than the window.  The results, best_of, best_by and return_scores are per job as they are per stream.
+
+    banned: the device form of the host loops' `inadmissibles` (which stays refused here: its one index array for all streams is not what the
+    launch reads).  None: no ban; one sequence of token ids: no lead sheet's stream ever DRAWS one of them; or one entry per lead sheet, each
+    a sequence of ids or None.  The grammar launch reads a banned token's logit as -inf (emo_hip.h: tok_mask), so the ids are those of the
+    unbanned call on logits masked that way; primers, injected lead-sheet bars and Track_Full are fed as they are, and the recorded scores stay
+    the model's own (unmasked).  tempo_ban() builds the reference's tempo constraint.  temp / top_p: one value, or one per lead sheet.  With
+    best_of = N the N candidates of a lead sheet share its ban, temp and top_p; with slots = S they belong to the job.  A stream that leaves the
+    device loop at the window keeps them: as `inadmissibles`, temp and top_p of _resume_windowed (window = 'host'), in the WindowedLoop's block
+    (window = 'device').  ValueError, before anything is allocated, for an id outside [0, V), a ban that leaves no token, a per-input list of
+    the wrong length, a temp <= 0 or a top_p outside (0, 1]."""
     if window not in ('host', 'device'):
         raise ValueError("window must be 'host' or 'device' (got %r)" % (window,))
     _refuse(model, inadmissibles)
@@ -1287,8 +1309,11 @@ def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, m
             raise ValueError('slots must be None or a count of at least 1 (got %r)' % (slots,))
         if slots < 1:
             raise ValueError('slots must be at least 1 (got %d)' % slots)
+    # checked per input, before a loop allocates anything; every candidate of an input inherits the input's controls
+    ctl = draw_controls('generate_accompaniments', len(lead_sheets) // best_of, model.n_token, banned, temp, top_p).repeat(best_of)
     t0 = time.time()
-    kw = dict(max_events=max_events, skip_check=skip_check, max_bars=max_bars, temp=temp, top_p=top_p, seed=seed)
+    kw = dict(max_events=max_events, skip_check=skip_check, max_bars=max_bars, temp=ctl.temp_arg, top_p=ctl.top_p_arg, seed=seed,
+              banned=ctl.bans)
 
     def make(**more):
         if slots is None:
@@ -1353,7 +1378,15 @@ def parse_args(argv=None):
                     help='--device: run ALL lead sheets (times --best-of) as queued jobs through this many rows of one decode engine, refilled on the device')
     ap.add_argument('--scores', default=None, metavar='FILE',
                     help='--device: write one JSON record per piece (scoring.draw_record) and its per-token logp / rank / entropy, as recorded at each draw')
+    ap.add_argument('--tempo', type=int, default=None, metavar='T',
+                    help='never draw a Tempo event further than --tempo-tolerance from T (tempo_ban): with --device in the grammar launch, else '
+                         'as the host loop\'s inadmissibles')
+    ap.add_argument('--tempo-tolerance', dest='tempo_tolerance', type=int, default=None, metavar='N', help='--tempo: the distance allowed (default 20)')
     args = ap.parse_args(argv)
+    if args.tempo_tolerance is not None and (args.tempo is None or args.tempo_tolerance < 0):
+        ap.error('--tempo-tolerance goes with --tempo T and is at least 0')
+    if args.tempo is not None and args.tempo_tolerance is None:
+        args.tempo_tolerance = 20
     if args.best_of < 1 or (args.best_of > 1 and not args.device):
         ap.error('--best-of needs --device and a count of at least 1')
     if args.window == 'device' and not args.device:
@@ -1400,6 +1433,9 @@ def main(argv=None):
             primer = [event2idx['Emotion_%s' % e]] + ([event2idx[key]] if args.representation == 'functional' else []) + [event2idx['Tempo_110']]
             jobs.append((out, key, bars, primer))
     print('[# jobs]', len(jobs))
+    ban = tempo_ban(event2idx, args.tempo, args.tempo_tolerance) if args.tempo is not None else None
+    if ban is not None:
+        print('[info] tempo %d +- %d: %d tempo events banned' % (args.tempo, args.tempo_tolerance, len(ban)))
     per_group = max(1, args.streams // args.best_of)              # --streams counts engine streams: N of them per lead sheet with --best-of N
     if args.slots is not None:
         per_group = max(1, len(jobs))                             # one call: the jobs queue for the slots
@@ -1409,15 +1445,18 @@ def main(argv=None):
         if args.device and args.best_of > 1:
             gen, _, picks, *sc = generate_accompaniments(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group],
                                                          max_bars=args.max_bars, temp=temp, top_p=top_p, seed=args.seed + j, best_of=args.best_of,
-                                                         window=args.window, best_by=args.best_by, return_scores=want, slots=args.slots)
+                                                         window=args.window, best_by=args.best_by, return_scores=want, slots=args.slots,
+                                                         banned=ban)
             for g, p in zip(group, picks):
                 print('[info] %s: candidate %d of %s' % (g[0], p['chosen'], ['%.4f' % x for x in p['nll_mean']]))
         elif args.device:
             gen, _, *sc = generate_accompaniments(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
-                                                  temp=temp, top_p=top_p, seed=args.seed + j, window=args.window, return_scores=want, slots=args.slots)
+                                                  temp=temp, top_p=top_p, seed=args.seed + j, window=args.window, return_scores=want, slots=args.slots,
+                                                  banned=ban)
         else:
             gen = generate_conditional_batch(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
-                                             temp=temp, top_p=top_p, seeds=list(range(i, i + len(group))))
+                                             temp=temp, top_p=top_p, seeds=list(range(i, i + len(group))),
+                                             inadmissibles=np.array(ban, np.int64) if ban else None)
         if want:
             score_pieces += scoring.draw_pieces([os.path.basename(g[0]) for g in group], gen, sc[0])
         for (out, key, _, _), ids in zip(group, gen):

@@ -398,6 +398,13 @@ _GRAMMAR_STEP_LAYOUT = {
     'mem_lens': lambda a, t: _is(t, _I64) and t.numel() == a.n_rows,
     'job_steps': lambda a, t: _is(t, _I32) and t.numel() == a.ld_u,
     'row_reset': lambda a, t: _is(t, _I32) and t.numel() == a.n_rows,
+    # the optional sampling controls: per stream (ld_u) like params; the ban rows hold uint32 words (as int32, bit for bit), n_masks of them,
+    # given in the same call (numbers are written first)
+    'tok_mask': lambda a, t: _is(t, _I32) and t.shape == (a.n_masks, (a.n_token + 31) // 32) and a.n_masks > 0,
+    # (the values are read back once, when the table enters the block: a row outside [-1, n_masks) is refused here; the kernel would treat it as -1)
+    'mask_of': lambda a, t: _is(t, _I32) and t.numel() == a.ld_u and int(t.min()) >= -1 and int(t.max()) < a.n_masks,
+    'temp_of': lambda a, t: _is(t, _F32) and t.numel() == a.ld_u,
+    'top_p_of': lambda a, t: _is(t, _F32) and t.numel() == a.ld_u,
 }
 # per struct: its name in messages, the layout table, the int64 vectors, and the numbers a tensor brings with it (field -> (number, of tensor))
 _BLOCKS = {

@@ -14,7 +14,7 @@ import torch
 
 from . import ops, sampling, scoring
 from ._lib import EmoError
-from .gen_loop import GrammarLoop, check_vocab
+from .gen_loop import GrammarLoop, check_vocab, draw_controls
 from .inference import _EngineBase, uniform_table
 from .sampling import beat_position, event_name, nucleus  # noqa: F401  (`nucleus` is looked up at call time: tests wrap it)
 
@@ -350,10 +350,10 @@ class LeadSheetLoop(GrammarLoop):
     self.score_tables (ops.draw_score_tables: laid out like seq, sentinels wherever a token was given, not drawn); scores() reads them."""
 
     def __init__(self, model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
-                 representation='functional', key_determine=None, seed=0, step='chain', scores=False):
+                 representation='functional', key_determine=None, seed=0, step='chain', scores=False, banned=None):
         from .model.plain_transformer import TXLMemory
         self._check_step(model, len(primers), step)
-        plens = self._load_jobs(model, event2idx, idx2event, primers, temp, top_p, None, max_bars=max_bars, max_events=max_events,
+        plens = self._load_jobs(model, event2idx, idx2event, primers, temp, top_p, None, banned, max_bars=max_bars, max_events=max_events,
                                 prompt_bars=prompt_bars, representation=representation, key_determine=key_determine)
         n, L0 = self.n, min(plens)
         self.mem = TXLMemory(model, n, model._max_gen_len)
@@ -361,7 +361,7 @@ class LeadSheetLoop(GrammarLoop):
         self.U = uniform_table(self.max_len - L0 + 1, n, seed, self.dev)      # at most one draw per step, one more at the end
         self.tok = self.seq[:, L0 - 1].contiguous()           # (a valid id in every row before the first grammar step)
         self.logits = torch.empty(n, model.vocab_size, dtype=torch.float32, device=self.dev)
-        self._build_block(ops.GRAMMAR_TXL, scores, **self._block_fields(n))
+        self._build_block(ops.GRAMMAR_TXL, scores, self.job_controls, **self._block_fields(n))
         with torch.no_grad():
             h, _, _ = model._prefill(self.seq[:, :L0].t(), self.mem)
             self.logits.copy_(model._logits(h.view(n, L0, -1)[:, -1].contiguous()))
@@ -381,13 +381,15 @@ class LeadSheetLoop(GrammarLoop):
             if why is not None:
                 raise EmoError("step='one_launch' (emo_decode_step[txl]) needs %s; use step='chain'" % why)
 
-    def _load_jobs(self, model, event2idx, idx2event, primers, temp, top_p, feed, **per_stream):
-        """n, model, dev and the draw parameters; the jobs' tables (_job_tables) on the device as seq / params / state, state[FEED] = `feed`
+    def _load_jobs(self, model, event2idx, idx2event, primers, temp, top_p, feed, banned=None, **per_stream):
+        """n, model, dev and the draw parameters (job_controls: gen_loop.draw_controls of temp / top_p / banned, each one value for all streams
+        or one per stream, checked before anything is allocated; temp / top_p: the launch's scalars); the jobs' tables (_job_tables) on the device as seq / params / state, state[FEED] = `feed`
         (None: the shortest primer's length, the prefix a prefill takes); the running count.  -> the primer lengths."""
         n = self.n = len(primers)
         assert n > 0
         kw = _per_stream(n, **per_stream)
-        self.model, self.temp, self.top_p = model, float(temp), float(top_p)
+        ctl = self.job_controls = draw_controls('generate_lead_sheets', n, model.vocab_size, banned, temp, top_p)
+        self.model, self.temp, self.top_p = model, ctl.temp, ctl.top_p
         self.dev = next(model.parameters()).device
         plens, seq, params, state = self._job_tables(model, event2idx, idx2event, primers, kw)
         state[:, S_FEED] = min(plens) if feed is None else feed
@@ -506,14 +508,14 @@ class LeadSheetQueue(LeadSheetLoop):
     launches each finished job held a slot; launches: the launches run() queued (a k-step replay ends up to k - 1 launches past the drain)."""
 
     def __init__(self, model, event2idx, idx2event, primers, slots, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
-                 representation='functional', key_determine=None, seed=0, step='chain', scores=False):
+                 representation='functional', key_determine=None, seed=0, step='chain', scores=False, banned=None):
         from .model.plain_transformer import TXLMemory
         slots = self.slots = int(slots)
         if slots < 1:
             raise ValueError('slots must be at least 1 (got %d)' % slots)
         self._check_step(model, slots, step)
         # FEED 1 is what an admission sets: the first token goes out with it
-        self._load_jobs(model, event2idx, idx2event, primers, temp, top_p, 1, max_bars=max_bars, max_events=max_events, prompt_bars=prompt_bars,
+        self._load_jobs(model, event2idx, idx2event, primers, temp, top_p, 1, banned, max_bars=max_bars, max_events=max_events, prompt_bars=prompt_bars,
                         representation=representation, key_determine=key_determine)
         n, dev = self.n, self.dev
         self.stepper = OneLaunchStep(model, slots) if step == 'one_launch' else None
@@ -525,7 +527,7 @@ class LeadSheetQueue(LeadSheetLoop):
         self.slot_job = torch.full((slots,), -1, dtype=torch.int32, device=dev)
         self.queue_head = torch.zeros(1, dtype=torch.int32, device=dev)
         self.job_steps_dev = torch.zeros(n, dtype=torch.int32, device=dev)
-        self._build_block(ops.GRAMMAR_TXL_QUEUE, scores, n_jobs=n, mem_rows=mem.max_len, slot_job=self.slot_job, queue_head=self.queue_head,
+        self._build_block(ops.GRAMMAR_TXL_QUEUE, scores, self.job_controls, n_jobs=n, mem_rows=mem.max_len, slot_job=self.slot_job, queue_head=self.queue_head,
                           mem_lens=mem.lens, job_steps=self.job_steps_dev, **self._block_fields(slots))
         # no job can outlast its row of the memory, so the queue is drained before this many launches whatever the slots do: a budget for the
         # replayer, not a limit that is meant to bind (the per-job limit is the kernel's MEM_FULL)
@@ -549,7 +551,7 @@ class LeadSheetQueue(LeadSheetLoop):
 
 def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
                          representation='functional', key_determine=None, seed=0, use_graph=True, step='chain', best_of=1, best_by='forward',
-                         return_scores=False, slots=None):
+                         return_scores=False, slots=None, banned=None):
     """The throughput path of generate_plain_xl_batch: the same arguments and result shape, every draw and the grammar on the device
     (emo_grammar_step), each token step = grammar launch + decode_step, k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS,
     default 16) and replayed until every stream has finished.  Draws come from a uniform table seeded with `seed` (like generate_streams),
@@ -576,7 +578,14 @@ def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max
     are JOBS that run through S rows (LeadSheetQueue): a row whose job ends takes the next job on the device, so no row idles while jobs wait
     and no batch waits for its longest member; step='one_launch' then has to hold for S rows.  A job draws from its own column of the uniform
     table, so its ids do not depend on S or on the slot it ran in beyond what the model step's arithmetic does; they are not those of slots =
-    None, whose streams share a prefill.  The results, best_of, best_by and return_scores are per job as they are per stream."""
+    None, whose streams share a prefill.  The results, best_of, best_by and return_scores are per job as they are per stream.
+
+    banned: None (no ban), one sequence of token ids (no stream ever DRAWS one of them), or one entry per primer, each a sequence of ids or
+    None.  The grammar launch reads a banned token's logit as -inf (emo_hip.h: tok_mask), the key draw included, so the ids are those of the
+    unbanned call on logits masked that way; primer tokens are fed as they are and the recorded scores stay the model's own (unmasked).
+    key_ban() forces a key.  temp / top_p: one value, or one per primer (the key draw keeps its own 1.1 / 0.97).  With best_of = N the N
+    candidates of a primer share its ban, temp and top_p; with slots = S they belong to the job.  ValueError, before anything is allocated, for
+    an id outside [0, V), a ban that leaves no token, a per-input list of the wrong length, a temp <= 0 or a top_p outside (0, 1]."""
     # a per-primer list among the arguments is repeated like the primers; a value given once holds for every stream
     opts = dict(max_bars=max_bars, max_events=max_events, prompt_bars=prompt_bars, representation=representation, key_determine=key_determine)
     lists = [k for k, v in opts.items() if isinstance(v, (list, tuple)) and len(v) == len(primers)]
@@ -586,9 +595,12 @@ def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max
         slots = int(slots)
         if slots < 1:
             raise ValueError('slots must be at least 1 (got %d)' % slots)
+    # checked per primer, before a loop allocates anything; every candidate of a primer inherits the primer's controls
+    ctl = draw_controls('generate_lead_sheets', len(primers) // best_of, model.vocab_size if banned is not None else None, banned, temp,
+                        top_p).repeat(best_of)
     t0 = time.time()
     with scoring.eval_mode(model):
-        opts.update(temp=temp, top_p=top_p, seed=seed, step=step, scores=want)
+        opts.update(temp=ctl.temp_arg, top_p=ctl.top_p_arg, banned=ctl.bans, seed=seed, step=step, scores=want)
         loop = (LeadSheetLoop(model, event2idx, idx2event, primers, **opts) if slots is None else
                 LeadSheetQueue(model, event2idx, idx2event, primers, slots, **opts))
         loop.run(use_graph=use_graph)
@@ -599,6 +611,14 @@ def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max
             nll = scoring.draw_scores_mean(sc) if by_draws else scoring.lead_sheet_candidate_scores(model, out, loop.params.cpu().numpy()[:, P_PRIMER_LEN].tolist())
             picks = scoring.picks_of(out, nll, best_of, sc if return_scores else None)
     return scoring.generation_result(out, time.time() - t0, sc, picks, return_scores)
+
+
+def key_ban(event2idx, key):
+    """The ids of every Key_* event but `key` (an event of the vocabulary): as `banned` of generate_lead_sheets no other key is ever drawn.
+    Under key_determine='rule' a forced key whose mode does not match the emotion is rejected draw after draw, as any such key is."""
+    if key not in event2idx or not key.startswith('Key_'):
+        raise ValueError('key_ban: %r is not a Key_* event of the vocabulary' % (key,))
+    return sorted(i for e, i in event2idx.items() if e.startswith('Key_') and e != key)
 
 
 def pick_best(model, candidates, primer_lens, best_of, scorer=None):
@@ -652,7 +672,11 @@ def parse_args(argv=None):
                     help='--best-of: rank the candidates by a scoring forward over the finished pieces, or by the log-probabilities recorded at each draw')
     ap.add_argument('--scores', default=None, metavar='FILE',
                     help='write one JSON record per piece (scoring.draw_record) and its per-token logp / rank / entropy, as recorded at each draw (device loop only)')
+    ap.add_argument('--key', default=None, metavar='NAME',
+                    help='force the key: a Key_* event of the vocabulary, e.g. Key_C (key_ban: no other key is ever drawn; device loop, functional representation)')
     args = ap.parse_args(argv)
+    if args.key is not None and (args.exact or args.representation != 'functional' or not args.key.startswith('Key_')):
+        ap.error('--key takes a Key_* event and goes with the device loop (not --exact) and -r functional')
     if args.best_of < 1 or (args.best_of > 1 and args.exact):
         ap.error('--best-of must be at least 1 and goes with the device loop (not --exact)')
     if args.best_by != 'forward' and args.best_of < 2:
@@ -698,6 +722,7 @@ def main(argv=None):
     print('[# jobs]', len(jobs))
     kw = dict(max_bars=max_bars, max_events=mode['max_events'], temp=mode['temp'], top_p=mode['top_p'], representation=args.representation,
               key_determine=key_determine)
+    dev_kw = dict(banned=key_ban(event2idx, args.key)) if args.key is not None else {}
     times, score_pieces = [], []
     want = bool(args.scores)
     per_group = max(1, args.streams // args.best_of)               # --streams counts engine streams: N of them per piece with --best-of N
@@ -710,12 +735,12 @@ def main(argv=None):
             res, sec = generate_plain_xl_batch(model, event2idx, idx2event, primers, seeds=list(range(i, i + len(group))), **kw)
         elif args.best_of > 1:
             res, sec, picks, *sc = generate_lead_sheets(model, event2idx, idx2event, primers, seed=args.seed + j, step=args.step.replace('-', '_'),
-                                                        best_of=args.best_of, best_by=args.best_by, return_scores=want, slots=args.slots, **kw)
+                                                        best_of=args.best_of, best_by=args.best_by, return_scores=want, slots=args.slots, **kw, **dev_kw)
             for (out, _), p in zip(group, picks):
                 print('[info] %s: candidate %d of %d (nll_mean %s)' % (out, p['chosen'], args.best_of, ' '.join('%.4f' % x for x in p['nll_mean'])))
         else:
             res, sec, *sc = generate_lead_sheets(model, event2idx, idx2event, primers, seed=args.seed + j, step=args.step.replace('-', '_'),
-                                                 return_scores=want, slots=args.slots, **kw)
+                                                 return_scores=want, slots=args.slots, **kw, **dev_kw)
         times.append(sec)
         if want:
             score_pieces += scoring.draw_pieces([os.path.basename(out) for out, _ in group], res, sc[0])

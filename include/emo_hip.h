@@ -565,7 +565,7 @@ enum { EMO_ACC_EV_BEAT = 1, EMO_ACC_EV_TRACK_LS = 2, EMO_ACC_EV_PAD = 4, EMO_ACC
  * one-token step (state[j, CONSUMED] as the host leaves it is ignored).  *running starts at the number of RUNNING jobs and is decremented once per job. */
 /* The five grammar steps above are the kinds of ONE entry with ONE argument block, as emo_decode_step_t is for the model step beside them in
  * every generation loop.  `kind` selects the kernel; a field that a kind does not read is ignored by it, whatever it holds (the comment of each
- * field names its readers; none = all five; a field of TXL is a field of TXL_QUEUE too, a field of ACC a field of ACC_QUEUE).  The block is read AT CALL TIME: its values travel as the launch's arguments, so under hipGraph
+ * field names its readers; none = all five, as are the optional sampling controls and score outputs at the end of the block; a field of TXL is a field of TXL_QUEUE too, a field of ACC a field of ACC_QUEUE).  The block is read AT CALL TIME: its values travel as the launch's arguments, so under hipGraph
  * capture they are baked into the captured launch, exactly as positional arguments would be, and a later change of the block reaches only later
  * calls (and later captures).  The struct holds raw device addresses: its owner keeps the memory alive. */
 enum { EMO_GRAMMAR_TXL = 0, EMO_GRAMMAR_ACC = 1, EMO_GRAMMAR_ACC_WINDOW = 2, EMO_GRAMMAR_TXL_QUEUE = 3, EMO_GRAMMAR_ACC_QUEUE = 4 };   /* what each does: the five comments above (n = n_rows, V = n_token) */
@@ -607,6 +607,22 @@ typedef struct {
                                 * ACC_QUEUE: int64 [n_rows]: the per-row positions the model step reads (the decode engine's pos_dev) */
     int64_t mem_rows;          /* TXL_QUEUE: cache rows per row of the memory, > 0; ACC_QUEUE: the position bound, > 0 */
     int32_t* job_steps;        /* queue kinds: int32 [n_jobs] or NULL: per finished job, the launches it held a slot */
+    /* --- all kinds, optional sampling controls (in front of row_reset: row_reset and the outputs below stay the tail of the block; NULL:
+     * absent; all four NULL: the launch is exactly the one without them).  Per STREAM, indexed as params is: by the stream r (TXL, ACC), by
+     * the job (TXL_QUEUE, ACC_QUEUE), by r = rows[b] (ACC_WINDOW).  They reach the DRAW alone: the
+     * draw reads a banned token's logit as -INFINITY and otherwise runs the arithmetic it always runs, so the id, every state word, seq and
+     * segs are bit for bit those of the launch without a mask on logits whose banned entries were overwritten with -inf (the in-launch redraws
+     * of ACC / ACC_WINDOW reuse the masked sort).  Primer tokens, injected lead-sheet bars and track_full are fed as they are, banned or not.
+     * tok_logp / tok_rank / tok_entropy below are still taken from the model's UNMASKED logits row at temperature 1: they say what the model
+     * assigned to the drawn token, not what the constraint left of the distribution.  The host owns the checks the launch cannot make (a
+     * temp_of value > 0, a top_p_of value in (0, 1], a mask that leaves a token): the kernel reads nothing out of bounds whatever they hold. */
+    const uint32_t* tok_mask;  /* uint32 [n_masks, ceil(n_token / 32)] or NULL: bit v & 31 of word v >> 5 of a row set = token v is banned for draws
+                                * (bits at or beyond n_token in the last word are ignored) */
+    int64_t n_masks;           /* rows of tok_mask */
+    const int32_t* mask_of;    /* int32 [streams] or NULL: the row of tok_mask each stream draws under; -1 = none, and so is any value outside
+                                * [-1, n_masks) to the kernel, which never reads outside the table (ops.block_set refuses such a value).  Without tok_mask it is not read */
+    const float* temp_of;      /* f32 [streams] or NULL: replaces `temperature` per stream (the TXL key draw keeps key_temperature) */
+    const float* top_p_of;     /* f32 [streams] or NULL: replaces `top_p` per stream (the TXL key draw keeps key_top_p) */
     int32_t* row_reset;        /* ACC_QUEUE: int32 [n_rows], written every launch: 1 where the slot admitted a job in this launch, else 0 */
     /* --- all kinds, optional (NULL: not wanted; all three NULL: the launch is exactly the one without them).  What the model assigned to each
      * DRAWN token, taken from the logits row the draw was made from: tables [streams, ld_seq] laid out like seq.  When a draw is accepted and
