@@ -513,9 +513,11 @@ __device__ __forceinline__ void load_den(float (&dn)[NI_], const float* __restri
     }
 }
 
-// a = dPhi * Phi ; Adiff[t][m] = a+ - a- ; sumA[t] += a+ + a-   (lane owns f0..f0+3 (plus) and MF+f0.. (minus) of column t)
+// a = dPhi * Phi ; Adiff[t][m] = a+ - a- ; sumA[m0 / 16][t] = the tile's share of sum_f (a+ + a-)   (lane owns f0..f0+3 (plus) and MF+f0.. (minus)
+// of column t).  One slot per 16-feature tile, summed in tile order by dx_from_adiff: an atomicAdd into one float per row took the waves' shares
+// in whatever order they arrived, and the fp32 dq / dk of two identical calls differed in their last bits.
 template <typename CT, int MF>
-__device__ __forceinline__ void jac_epilogue(const f32x4& accP, const f32x4& accM, const CT* Ff, int ldf, CT* Adiff, int lda, float* sumA,
+__device__ __forceinline__ void jac_epilogue(const f32x4& accP, const f32x4& accM, const CT* Ff, int ldf, CT* Adiff, int lda, float* sumA, int lds_,
                                              const float* extra_vec /* z or r, [F] */, float extra_scale, int t, int m0, int lane) {
     float ad[4], s = 0.f;
 #pragma unroll
@@ -527,7 +529,7 @@ __device__ __forceinline__ void jac_epilogue(const f32x4& accP, const f32x4& acc
     }
     Img<CT>::store4(Adiff + t * lda + m0, ad[0], ad[1], ad[2], ad[3]);
     s = rows4_sum(s);
-    if ((lane >> 4) == 0) atomicAdd(&sumA[t], s);
+    if ((lane >> 4) == 0) sumA[(m0 >> 4) * lds_ + t] = s;
 }
 
 // pad columns m in [MF, MFP) of the (aliased) Adiff image must be finite zeros
@@ -539,7 +541,7 @@ __device__ __forceinline__ void zero_adiff_pad(CT* Adiff, int lda, int tid) {
 }
 
 // dx[t][d] = c * ( sum_m W[d][m] Adiff[t][m] - (c x[t][d]) sumA[t] ) : rows<->d (R=W), col<->t (C=Adiff)
-template <typename CT, int DH, int MFP, int C>
+template <typename CT, int DH, int MFP, int C, int NSA>
 __device__ __forceinline__ void dx_from_adiff(const CT* W, int ldw, const CT* Adiff, int lda, const float* sumA, const CT* __restrict__ xg,
                                               int64_t ld, CT* __restrict__ dxg, int64_t ld_d, float cs, int valid, int wave, int lane) {
     constexpr int NT = (DH / 16) * (C / 16);
@@ -554,7 +556,9 @@ __device__ __forceinline__ void dx_from_adiff(const CT* W, int ldw, const CT* Ad
         mm16_c<CT, MFP>(acc, W, ldw, dt * 16, adf, lane);
         const int t = tt * 16 + (lane & 15), d0 = dt * 16 + (lane >> 4) * 4;
         if (t < valid) {
-            const float sa = sumA[t];
+            float sa = sumA[t];
+#pragma unroll
+            for (int i = 1; i < NSA; ++i) sa += sumA[i * C + t];
             float o[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[r] = cs * (acc[r] - cs * to_f32<CT>(xg[(int64_t)t * ld + d0 + r]) * sa);
@@ -589,8 +593,8 @@ __global__ __launch_bounds__(FT) void favor_bwd_dq_kernel(const CT* __restrict__
     float* offq = (float*)(SF + F * LDX);
     float* offk = offq + C;
     float* dD = offk + C;
-    float* sumA = dD + C;
-    float* zz = sumA + C;          // [F]
+    float* sumA = dD + C;          // [MF / 16][C]
+    float* zz = sumA + (MF / 16) * C;   // [F]
 
     const int abl = P >> 8;   // diagnostics (EMO_FAVOR_ABLATE_DQ)
     P &= 0xFF;
@@ -663,7 +667,7 @@ __global__ __launch_bounds__(FT) void favor_bwd_dq_kernel(const CT* __restrict__
         }
         if (!(abl & 2)) pv.store_T(VT, LDC, tid);
         if (!(abl & 4)) store_grads<CT, DH, DHP, C>(pg, po, dn, valid, G, LDX, (CT*)nullptr, 0, dD, tid);
-        for (int i = tid; i < C; i += FT) sumA[i] = 0.f;
+        for (int i = tid; i < (MF / 16) * C; i += FT) sumA[i] = 0.f;
         if (t0 + C < tend) {
             const int64_t tn_ = t0 + C;
             const int vn = (int)((tend - tn_) < C ? (tend - tn_) : C);
@@ -714,11 +718,11 @@ __global__ __launch_bounds__(FT) void favor_bwd_dq_kernel(const CT* __restrict__
                 mm16_c<CT, CP>(aM, KfT, LDC, MF + ft * 16, pmf, lane);
                 mm16_c<CT, DHP>(aM, SF, LDX, MF + ft * 16, gf, lane);
                 const int t = tt * 16 + (lane & 15), m0 = ft * 16 + (lane >> 4) * 4;
-                jac_epilogue<CT, MF>(aP, aM, Qf, LDF, Adiff, LDM, sumA, zz, dD[t], t, m0, lane);
+                jac_epilogue<CT, MF>(aP, aM, Qf, LDF, Adiff, LDM, sumA, C, zz, dD[t], t, m0, lane);
             }
         }
         __syncthreads();
-        if (!(abl & 64)) dx_from_adiff<CT, DH, MFP, C>(W, LDM, Adiff, LDM, sumA, qb + t0 * ld, ld, dqb + t0 * ld_d, ld_d, cs, valid, wave, lane);
+        if (!(abl & 64)) dx_from_adiff<CT, DH, MFP, C, MF / 16>(W, LDM, Adiff, LDM, sumA, qb + t0 * ld, ld, dqb + t0 * ld_d, ld_d, cs, valid, wave, lane);
         // state S[f][d] (+)= ; mirror SF[f][d0..] ; z += colsum(KfT)
         if (!(abl & 128)) {
         static_assert(FW % (F / 16) == 0 || (F / 16) % FW == 0, "state tiles of a wave share the feature block");
@@ -793,8 +797,8 @@ __global__ __launch_bounds__(FT) void favor_bwd_dkv_kernel(const CT* __restrict_
     float* offq = (float*)(RT + DH * LDF);
     float* offk = offq + C;
     float* dD = offk + C;
-    float* sumA = dD + C;
-    float* rr = sumA + C;           // [F]  r[f] = sum_{t>chunk} Qf_t[f] dD_t
+    float* sumA = dD + C;           // [MF / 16][C]
+    float* rr = sumA + (MF / 16) * C;   // [F]  r[f] = sum_{t>chunk} Qf_t[f] dD_t
 
     const int abl = P >> 8;   // diagnostics (EMO_FAVOR_ABLATE_DKV)
     P &= 0xFF;
@@ -876,7 +880,7 @@ __global__ __launch_bounds__(FT) void favor_bwd_dkv_kernel(const CT* __restrict_
         }
         }
         if (!(abl & 4)) store_grads<CT, DH, DHP, C>(pg, po, dn, valid, G, LDX, GT, LDC, dD, tid);
-        for (int i = tid; i < C; i += FT) sumA[i] = 0.f;
+        for (int i = tid; i < (MF / 16) * C; i += FT) sumA[i] = 0.f;
         if (ci > 0) {                                  // previous (earlier) chunk: full, stays in flight during this chunk's compute
             const int64_t tn_ = t0 - C;
             pq.load(qb + tn_ * ld, ld, C, tid);
@@ -947,7 +951,7 @@ __global__ __launch_bounds__(FT) void favor_bwd_dkv_kernel(const CT* __restrict_
                 mm16_c<CT, CP>(aM, QfT, LDC, MF + ft * 16, pmf, lane);
                 mm16_c<CT, DHP>(aM, RF, LDX, MF + ft * 16, vrf, lane);
                 const int j = jt * 16 + (lane & 15), m0 = ft * 16 + (lane >> 4) * 4;
-                jac_epilogue<CT, MF>(aP, aM, Kf, LDF, Adiff, LDM, sumA, rr, 1.f, j, m0, lane);
+                jac_epilogue<CT, MF>(aP, aM, Kf, LDF, Adiff, LDM, sumA, C, rr, 1.f, j, m0, lane);
             }
         }
         // dV^T: rows<->d, col<->j : GT.AmT^T (K=C) + RT.Kf^T (K=F)
@@ -970,7 +974,7 @@ __global__ __launch_bounds__(FT) void favor_bwd_dkv_kernel(const CT* __restrict_
             }
         }
         __syncthreads();
-        if (!(abl & 64)) dx_from_adiff<CT, DH, MFP, C>(W, LDM, Adiff, LDM, sumA, kb + t0 * ld, ld, dkb + t0 * ld_d, ld_d, cs, valid, wave, lane);
+        if (!(abl & 64)) dx_from_adiff<CT, DH, MFP, C, MF / 16>(W, LDM, Adiff, LDM, sumA, kb + t0 * ld, ld, dkb + t0 * ld_d, ld_d, cs, valid, wave, lane);
         }   // !SO
         // state R[f][d] += sum_t QfT[f][t] GT[d][t]
         if (!(abl & 128)) {
@@ -1257,13 +1261,13 @@ template <typename CT, int DH, int MF, int C> static size_t dq_lds() {
     typedef FavorDims<CT, DH, MF, C, 1> D;
     return sizeof(CT) * (size_t)(MF * D::LDX + DH * D::LDM + C * D::LDX + C * CMax<D::LDX, D::LDM>::v + C * D::LDX + DH * D::LDC + C * D::LDX +
                                  C * D::LDF + D::F * D::LDC + C * D::LDC + D::F * D::LDX) +
-           sizeof(float) * (size_t)(4 * C + D::F);
+           sizeof(float) * (size_t)((3 + MF / 16) * C + D::F);
 }
 template <typename CT, int DH, int MF, int C> static size_t dkv_lds() {
     typedef FavorDims<CT, DH, MF, C, 2> D;
     return sizeof(CT) * (size_t)(MF * D::LDX + DH * D::LDM + 2 * C * CMax<D::LDX, D::LDC>::v + C * D::LDX + C * CMax<D::LDX, D::LDM>::v + DH * D::LDC +
                                  2 * C * D::LDF + D::F * D::LDC + D::F * D::LDX + DH * D::LDF) +
-           sizeof(float) * (size_t)(4 * C + D::F);
+           sizeof(float) * (size_t)((3 + MF / 16) * C + D::F);
 }
 
 #define EMO_MAX_LDS (160 * 1024)
