@@ -4,7 +4,7 @@
 //   logp    = l[tok] - lse,  lse = mx + log sum_v exp(l_v - mx)
 //   rank    = #{v : l[v] > l[tok]} + #{v < tok : l[v] == l[tok]}
 //   entropy = lse - sum_v softmax(l)_v l_v = log s - w / s      (s = sum exp(l - mx), w = sum exp(l - mx) (l - mx))
-// The arithmetic per column is that of token_scores_kernel; the reduction order is not (8 waves of 64 lanes, two columns per thread, wave
+// The arithmetic per column is that of emo_token_scores; the reduction order is not (8 waves of 64 lanes, two columns per thread, wave
 // partials added in wave order), so the floats agree with emo_token_scores to rounding, not bit for bit.  Ranks are exact.
 // LDS: EMO_DRAW_SCORES_WORDS words of the caller's, used for the cross-wave reductions only — nothing of the nucleus scratch (emo_nucleus.h)
 // is read or written, so the sorted state a redraw needs is still there afterwards.

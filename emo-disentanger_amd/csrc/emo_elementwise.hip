@@ -1,6 +1,6 @@
 // HBM-bound kernels of the path: K1 embedding prologue (fwd/bwd), K6 LayerNorm (fwd/bwd),
-// dropout re-application, K9 cross-entropy (fwd/bwd), K12 accuracy counts, optimizer plumbing
-// (sum of squares, clip coefficient, Adam, dtype cast).  All are one-pass, 16-B-per-lane
+// dropout re-application, optimizer plumbing (sum of squares, clip coefficient, Adam, dtype cast); the kernels that walk logits
+// rows (K9 cross-entropy, K12 accuracy counts, argmax) are in emo_score.hip.  All are one-pass, 16-B-per-lane
 // coalesced streams with wave64 shuffle reductions; none is reshaped into a GEMM.
 #include <stdarg.h>
 
@@ -579,250 +579,6 @@ extern "C" int emo_dropout_apply(const void* x, void* out, int dtype, int64_t n,
     hipStream_t st = (hipStream_t)stream;
     if (dtype == EMO_F32) hipLaunchKernelGGL(dropout_apply_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)x, (float*)out, n, drop);
     else hipLaunchKernelGGL(dropout_apply_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)out, n, drop);
-    EMO_LAUNCH_CHECK();
-    return EMO_OK;
-}
-
-// ================================================================================================ K9 cross-entropy
-__global__ __launch_bounds__(256) void xent_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ tgt, int64_t M,
-                                                       int64_t V, int64_t ignore, float* __restrict__ row_lse, float* __restrict__ acc) {
-    __shared__ float part[2][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float lsum = 0.f, lcnt = 0.f;
-    for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < M; row += (int64_t)gridDim.x * 4) {
-        const float* l = logits + row * V;
-        float mx = -INFINITY;
-        for (int64_t c = lane; c < V; c += 64) mx = fmaxf(mx, l[c]);
-        mx = wave_max(mx);
-        float s = 0.f;
-        for (int64_t c = lane; c < V; c += 64) s += expf(l[c] - mx);
-        s = wave_sum(s);
-        const float lse = mx + logf(s);
-        if (lane == 0) {
-            row_lse[row] = lse;
-            const int64_t t = tgt[row];
-            if (t != ignore) { lsum += lse - l[t]; lcnt += 1.f; }
-        }
-    }
-    if (lane == 0) { part[0][wave] = lsum; part[1][wave] = lcnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicAdd(acc, part[0][0] + part[0][1] + part[0][2] + part[0][3]);
-        atomicAdd(acc + 1, part[1][0] + part[1][1] + part[1][2] + part[1][3]);
-    }
-}
-// V <= 64 * NV: the row lives in registers (one global read instead of two) and every wave keeps two rows in flight
-// (r01: 126 us for 131072 x 327 fp32 logits = 1.4 TB/s with the generic kernel: one row per wave, two dependent passes).
-template <int NV>
-__global__ __launch_bounds__(256) void xent_fwd_regs_kernel(const float* __restrict__ logits, const int64_t* __restrict__ tgt, int64_t M,
-                                                            int64_t V, int64_t ignore, float* __restrict__ row_lse, float* __restrict__ acc) {
-    __shared__ float part[2][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float lsum = 0.f, lcnt = 0.f;
-    const int64_t nw = (int64_t)gridDim.x * 4;
-    for (int64_t r0 = ((int64_t)blockIdx.x * 4 + wave) * 2; r0 < M; r0 += nw * 2) {
-        const int64_t r1 = r0 + 1 < M ? r0 + 1 : r0;
-        const float* l0 = logits + r0 * V;
-        const float* l1 = logits + r1 * V;
-        float a[NV], b[NV];
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int64_t c = lane + 64 * i;
-            a[i] = c < V ? l0[c] : -INFINITY;
-            b[i] = c < V ? l1[c] : -INFINITY;
-        }
-        float ma = a[0], mb = b[0];
-#pragma unroll
-        for (int i = 1; i < NV; ++i) { ma = fmaxf(ma, a[i]); mb = fmaxf(mb, b[i]); }
-        ma = wave_max(ma); mb = wave_max(mb);
-        float sa = 0.f, sb = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int64_t c = lane + 64 * i;
-            if (c < V) { sa += expf(a[i] - ma); sb += expf(b[i] - mb); }
-        }
-        sa = wave_sum(sa); sb = wave_sum(sb);
-        const float lse_a = ma + logf(sa), lse_b = mb + logf(sb);
-        if (lane == 0) {
-            row_lse[r0] = lse_a;
-            const int64_t t0 = tgt[r0];
-            if (t0 != ignore) { lsum += lse_a - l0[t0]; lcnt += 1.f; }
-            if (r0 + 1 < M) {
-                row_lse[r1] = lse_b;
-                const int64_t t1 = tgt[r1];
-                if (t1 != ignore) { lsum += lse_b - l1[t1]; lcnt += 1.f; }
-            }
-        }
-    }
-    if (lane == 0) { part[0][wave] = lsum; part[1][wave] = lcnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicAdd(acc, part[0][0] + part[0][1] + part[0][2] + part[0][3]);
-        atomicAdd(acc + 1, part[1][0] + part[1][1] + part[1][2] + part[1][3]);
-    }
-}
-
-extern "C" int emo_xent_fwd(const float* logits, const int64_t* tgt, int64_t M, int64_t V, int64_t ignore_index, float* row_lse,
-                            float* acc, emo_stream_t stream) {
-    EMO_CHECK(logits && tgt && row_lse && acc, "emo_xent_fwd: null pointer");
-    int64_t blocks = cdiv64(M, 4);
-    if (blocks > 2048) blocks = 2048;
-    if (V <= 512 && M >= 1024) {
-        if (V <= 384) hipLaunchKernelGGL(xent_fwd_regs_kernel<6>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, tgt, M, V, ignore_index, row_lse, acc);
-        else hipLaunchKernelGGL(xent_fwd_regs_kernel<8>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, tgt, M, V, ignore_index, row_lse, acc);
-        EMO_LAUNCH_CHECK();
-        return EMO_OK;
-    }
-    hipLaunchKernelGGL(xent_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, tgt, M, V, ignore_index, row_lse, acc);
-    EMO_LAUNCH_CHECK();
-    return EMO_OK;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void xent_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ tgt,
-                                                       const float* __restrict__ row_lse, const float* __restrict__ gscale,
-                                                       T* __restrict__ dl, int64_t ld, int64_t M, int64_t V, int64_t ignore) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float gs = gscale[0];
-    for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < M; row += (int64_t)gridDim.x * 4) {
-        const int64_t t = tgt[row];
-        const float lse = row_lse[row];
-        const float keep = (t != ignore) ? gs : 0.f;
-        for (int64_t c = lane; c < ld; c += 64) {
-            float v = 0.f;
-            if (c < V) v = (expf(logits[row * V + c] - lse) - (c == t ? 1.f : 0.f)) * keep;
-            dl[row * ld + c] = from_f32<T>(v);
-        }
-    }
-}
-extern "C" int emo_xent_bwd(const float* logits, const int64_t* tgt, const float* row_lse, const float* gscale, void* dlogits,
-                            int64_t ld_out, int dtype_out, int64_t M, int64_t V, int64_t ignore_index, emo_stream_t stream) {
-    EMO_CHECK(logits && tgt && row_lse && gscale && dlogits && ld_out >= V, "emo_xent_bwd: bad args");
-    int64_t blocks = cdiv64(M, 4);
-    if (blocks > 4096) blocks = 4096;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype_out == EMO_F32) hipLaunchKernelGGL(xent_bwd_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, logits, tgt, row_lse, gscale, (float*)dlogits, ld_out, M, V, ignore_index);
-    else hipLaunchKernelGGL(xent_bwd_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, st, logits, tgt, row_lse, gscale, (bf16_t*)dlogits, ld_out, M, V, ignore_index);
-    EMO_LAUNCH_CHECK();
-    return EMO_OK;
-}
-
-// ================================================================================================ argmax / accuracy
-__device__ __forceinline__ void wave_argmax(float& v, int64_t& idx) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        float ov = __shfl_xor(v, o, 64);
-        int64_t oi = __shfl_xor(idx, o, 64);
-        if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
-    }
-}
-__device__ __forceinline__ int64_t row_argmax(const float* l, int64_t V, int lane) {
-    float best = -INFINITY;
-    int64_t bi = INT64_MAX;
-    for (int64_t c = lane; c < V; c += 64) {
-        float x = l[c];
-        if (x > best || (x != x && bi == INT64_MAX)) { best = x; bi = c; }  // first max wins inside a lane (ascending c)
-    }
-    wave_argmax(best, bi);
-    return bi == INT64_MAX ? 0 : bi;          // a row of -inf only: nothing beats the start value; index 0, as numpy / torch argmax
-}
-__global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ logits, int64_t rows, int64_t V, int64_t* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    int64_t bi = row_argmax(logits + row * V, V, lane);
-    if (lane == 0) out[row] = bi;
-}
-extern "C" int emo_argmax(const float* logits, int64_t rows, int64_t V, int64_t* out, emo_stream_t stream) {
-    EMO_CHECK(logits && out && rows > 0 && V > 0, "emo_argmax: bad args");
-    hipLaunchKernelGGL(argmax_kernel, dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, (hipStream_t)stream, logits, rows, V, out);
-    EMO_LAUNCH_CHECK();
-    return EMO_OK;
-}
-
-__global__ __launch_bounds__(256) void accuracy_kernel(const float* __restrict__ logits, const int64_t* __restrict__ tgt,
-                                                       const int64_t* __restrict__ chord, const int64_t* __restrict__ melody, int64_t M,
-                                                       int64_t V, int64_t pad, unsigned long long* __restrict__ counts) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long c[6] = {0, 0, 0, 0, 0, 0};
-    for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < M; row += (int64_t)gridDim.x * 4) {
-        int64_t bi = row_argmax(logits + row * V, V, lane);
-        if (lane == 0) {
-            const int64_t t = tgt[row];
-            const unsigned long long ok = (bi == t);
-            if (t != pad) { c[0]++; c[1] += ok; }
-            if (chord && chord[row] == 1) { c[2]++; c[3] += ok; }
-            if (melody && melody[row] == 1) { c[4]++; c[5] += ok; }
-        }
-    }
-    if (lane == 0)
-        for (int i = 0; i < 6; ++i)
-            if (c[i]) atomicAdd(counts + i, c[i]);
-}
-// same idea for the accuracy counts: two rows per wave step, the row read once into registers
-template <int NV>
-__global__ __launch_bounds__(256) void accuracy_regs_kernel(const float* __restrict__ logits, const int64_t* __restrict__ tgt,
-                                                            const int64_t* __restrict__ chord, const int64_t* __restrict__ melody, int64_t M,
-                                                            int64_t V, int64_t pad, unsigned long long* __restrict__ counts) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long c[6] = {0, 0, 0, 0, 0, 0};
-    const int64_t nw = (int64_t)gridDim.x * 4;
-    for (int64_t r0 = ((int64_t)blockIdx.x * 4 + wave) * 2; r0 < M; r0 += nw * 2) {
-        const int64_t r1 = r0 + 1 < M ? r0 + 1 : r0;
-        const float* l0 = logits + r0 * V;
-        const float* l1 = logits + r1 * V;
-        float a[NV], b[NV];
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int64_t cc = lane + 64 * i;
-            a[i] = cc < V ? l0[cc] : -INFINITY;
-            b[i] = cc < V ? l1[cc] : -INFINITY;
-        }
-        float ba = -INFINITY, bb = -INFINITY;
-        int64_t ia = INT64_MAX, ib = INT64_MAX;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {          // first max wins inside a lane (ascending column), NaN as in row_argmax
-            const int64_t cc = lane + 64 * i;
-            if (cc < V) {
-                if (a[i] > ba || (a[i] != a[i] && ia == INT64_MAX)) { ba = a[i]; ia = cc; }
-                if (b[i] > bb || (b[i] != b[i] && ib == INT64_MAX)) { bb = b[i]; ib = cc; }
-            }
-        }
-        wave_argmax(ba, ia);
-        wave_argmax(bb, ib);
-        if (ia == INT64_MAX) ia = 0;            // all -inf row, as row_argmax
-        if (ib == INT64_MAX) ib = 0;
-        if (lane == 0) {
-            const int64_t t0 = tgt[r0];
-            const unsigned long long ok0 = (ia == t0);
-            if (t0 != pad) { c[0]++; c[1] += ok0; }
-            if (chord && chord[r0] == 1) { c[2]++; c[3] += ok0; }
-            if (melody && melody[r0] == 1) { c[4]++; c[5] += ok0; }
-            if (r0 + 1 < M) {
-                const int64_t t1 = tgt[r1];
-                const unsigned long long ok1 = (ib == t1);
-                if (t1 != pad) { c[0]++; c[1] += ok1; }
-                if (chord && chord[r1] == 1) { c[2]++; c[3] += ok1; }
-                if (melody && melody[r1] == 1) { c[4]++; c[5] += ok1; }
-            }
-        }
-    }
-    if (lane == 0)
-        for (int i = 0; i < 6; ++i)
-            if (c[i]) atomicAdd(counts + i, c[i]);
-}
-extern "C" int emo_accuracy_counts(const float* logits, const int64_t* tgt, const int64_t* chord, const int64_t* melody, int64_t M,
-                                   int64_t V, int64_t pad, int64_t* counts, emo_stream_t stream) {
-    EMO_CHECK(logits && tgt && counts, "emo_accuracy_counts: null pointer");
-    int64_t blocks = cdiv64(M, 4);
-    if (blocks > 2048) blocks = 2048;
-    if (V <= 512 && M >= 1024) {
-        if (V <= 384) hipLaunchKernelGGL(accuracy_regs_kernel<6>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, tgt, chord, melody, M, V, pad, (unsigned long long*)counts);
-        else hipLaunchKernelGGL(accuracy_regs_kernel<8>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, tgt, chord, melody, M, V, pad, (unsigned long long*)counts);
-        EMO_LAUNCH_CHECK();
-        return EMO_OK;
-    }
-    hipLaunchKernelGGL(accuracy_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, tgt, chord, melody, M, V, pad, (unsigned long long*)counts);
     EMO_LAUNCH_CHECK();
     return EMO_OK;
 }

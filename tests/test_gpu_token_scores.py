@@ -4,6 +4,8 @@ ops.argmax)."""
 import pytest
 import torch
 
+from test_gpu_train_rows_edges import MS as EDGE_MS, VS as EDGE_VS, _argmax_case, _xent_case
+
 pytestmark = pytest.mark.gpu
 
 DT = [torch.float32, torch.bfloat16]
@@ -147,6 +149,43 @@ def test_token_scores_lse_is_bitwise_the_training_kernels(M, V, padded):
     kept = (tgt != V - 1)
     assert int(acc[1]) == int(kept.sum())
     assert abs(float(out['nll'].double().sum() / kept.sum()) - float(acc[0] / acc[1])) < 1e-5
+
+
+@pytest.mark.parametrize('V', EDGE_VS)
+@pytest.mark.parametrize('M', EDGE_MS)
+def test_lse_bits_are_equal_across_entries_at_every_dispatch_edge(M, V):
+    """emo_xent_fwd takes the register kernels from M = 1024, emo_token_scores at any M; both take NV = 6 up to V = 384, NV = 8 up to V = 512 and
+    the memory kernel above.  So M = 1023 compares the memory kernel of one entry with the register kernel of the other, M = 1025 the odd tail,
+    V = 513 the two memory kernels.  Shifted rows and -inf holes included; once on contiguous logits and once on a [M, V + 8] view."""
+    ops = _ops()
+    l, tgt = _xent_case(M, V, seed=M + V)
+    tgt[::7] = -100
+    lse_t, _ = ops.xent_fwd(l.cuda(), tgt.cuda(), -100)
+    assert bool(torch.isfinite(lse_t).all())
+    wide = torch.full((M, V + 8), PAD_FILL, dtype=torch.float32)
+    wide[:, :V] = l
+    for dl in (l.cuda(), wide.cuda()[:, :V]):
+        lse_s = ops.token_scores(dl, tgt.cuda(), -100, want=('lse',))['lse']
+        bad = (lse_s.view(torch.int32) != lse_t.view(torch.int32)).nonzero().view(-1)
+        assert bad.numel() == 0, 'ld %d: %d rows differ, first %s' % (dl.stride(0), bad.numel(), bad[:8].tolist())
+
+
+@pytest.mark.parametrize('V', [65, 384, 513])
+def test_rank_zero_is_exactly_where_argmax_is_the_target(V):
+    """The identity emo_hip.h states under rank[m], on the planted ties of the edges file (two lanes, one lane, first and last column, tie of three,
+    all equal, all -inf, -inf but one) at M = 1025: it follows from the two definitions for any input without NaN, so nothing is approximate."""
+    ops = _ops()
+    M, pad = 1025, 2
+    l = _argmax_case(M, V, seed=M * 7 + V)
+    am = ops.argmax(l.cuda()).cpu()
+    g = torch.Generator().manual_seed(1)
+    tgt = torch.where(torch.rand(M, generator=g) < 0.7, am, torch.randint(0, V, (M,), generator=g))
+    hit = am == tgt
+    assert 0 < int(hit.sum()) < M and bool(hit[4]) == (int(tgt[4]) == 0)          # row 4 is all -inf: argmax 0
+    rank = ops.token_scores(l.cuda(), tgt.cuda(), -100, want=('rank',))['rank'].cpu()
+    assert torch.equal(rank == 0, hit), 'rows %s' % ((rank == 0) != hit).nonzero().view(-1)[:8].tolist()
+    counts = ops.accuracy_counts(l.cuda(), tgt.cuda(), None, None, pad).cpu().tolist()
+    assert counts[:2] == [int((tgt != pad).sum()), int((hit & (tgt != pad)).sum())]
 
 
 @pytest.mark.parametrize('padded', [False, True])

@@ -1,4 +1,4 @@
-"""The training row kernels (csrc/emo_elementwise.hip, colsum in csrc/emo_gemm.hip) at the edges of their ranges, against float64 references
+"""The training row kernels (csrc/emo_elementwise.hip, the logits-row kernels in csrc/emo_score.hip, colsum in csrc/emo_gemm.hip) at the edges of their ranges, against float64 references
 computed on the CPU from the same stored inputs (bf16 values upcast exactly, so both sides start from identical numbers).
 
 Covered here and nowhere else: the LayerNorm template selection at D = 4 / 260 / 512 / 768 (NV = 4 with a dead fourth group) / 1024, rows with a
