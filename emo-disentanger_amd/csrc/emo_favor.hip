@@ -16,6 +16,7 @@
 //   dN_t = dout_t/den_t,  dD_t = -(dout_t.out_t)/den_t
 #include "emo_common.h"
 
+#include "emo_attn_host.h"
 #include "emo_lds_mma.h"
 
 // 8 waves per workgroup, one workgroup per (b, h, time segment).  Backward kernels: 120-155 KB of LDS => one workgroup per CU (two waves
@@ -1272,20 +1273,13 @@ template <typename CT, int DH, int MF, int C> static size_t dkv_lds() {
 
 #define EMO_MAX_LDS (160 * 1024)
 
-// emo_favor_fs.hip: the bf16 / d_head 64 / 128-feature "slice" kernels (false: shape or mode not covered -> the generic kernels below)
-int emo_favor_fs_try(int which, int stage, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld, const float* omega, bf16_t* out, int64_t ld_out,
-                     float* den, float* sS, float* sz, const bf16_t* dout, bf16_t* dq, bf16_t* dk, bf16_t* dv, int64_t ld_d, int64_t B, int64_t T, int64_t H,
-                     float eps, const float* ws_S, const float* ws_z, int P, int64_t Ts, hipStream_t st);
-
 // ---- segment-parallel scan geometry (see favor_fwd_kernel).  One workgroup per (b, h, segment); segments only when B*H alone cannot
 // fill the 256 CUs.  Ts is a multiple of 64 (every chunk size divides it) and at least 2 chunks long.
 #define EMO_FAVOR_SEG_ALIGN 64
 #define EMO_FAVOR_MAX_SEGMENTS 16
 static void favor_segments(int64_t B, int64_t T, int64_t H, int* P_out, int64_t* Ts_out) {
-    int64_t want = 1;
-    const char* e = getenv("EMO_FAVOR_SEGMENTS");
-    if (e && atoi(e) > 0) want = atoi(e);
-    else if (B * H < 256) want = (256 + B * H - 1) / (B * H);
+    int64_t want = env_int("EMO_FAVOR_SEGMENTS", 0);
+    if (want <= 0) want = B * H < 256 ? (256 + B * H - 1) / (B * H) : 1;
     if (want > EMO_FAVOR_MAX_SEGMENTS) want = EMO_FAVOR_MAX_SEGMENTS;
     const int64_t max_p = T / (2 * EMO_FAVOR_SEG_ALIGN);
     if (want > max_p) want = max_p;
@@ -1305,168 +1299,146 @@ extern "C" int64_t emo_favor_attn_workspace_bytes(int64_t B, int64_t T, int64_t 
     return B * H * P * (n_feat * dh + n_feat) * (int64_t)sizeof(float);
 }
 
-template <typename CT, int DH, int MF, int CF, int CQ, int CK>
-static int run_favor(int which, const void* q, const void* k, const void* v, int64_t ld, const float* omega, void* out, int64_t ld_out, float* den,
-                     float* sS, float* sz, const void* dout, void* dq, void* dk, void* dv, int64_t ld_d, int64_t B, int64_t T, int64_t H, float eps,
-                     void* workspace, int64_t workspace_bytes, hipStream_t st, bool kstate_valid, bool dn) {
+// ---- the built instances: one row per (d_head, n_feat / 2), for the training passes and for the fast decode kernels alike.
+// FavorChunks: tokens per scan step of the forward / dq / dk,dv kernels of a row, per dtype.
+template <typename CT, int DH, int MF> struct FavorChunks { static constexpr int CF = sizeof(CT) == 2 ? 64 : 32, CQ = CF, CK = CF; };
+template <> struct FavorChunks<bf16_t, 64, 64> { static constexpr int CF = FAVOR_CFB, CQ = FAVOR_CQB, CK = FAVOR_CKB; };
+template <> struct FavorChunks<float, 64, 64> { static constexpr int CF = 32, CQ = 32, CK = 16; };
+template <typename F, int DH, int MF> struct FavorAt {
+    template <typename CT, typename... A> static int run(const emo_attn_t& a, A... args) { return F::template run<CT, DH, MF>(a, args...); }
+};
+// *rc = F::run<CT, DH, MF>(a, ...) at the row of (a.dh, a.n_feat); false: no such row
+template <typename F, typename... A> static bool favor_table(const emo_attn_t& a, int* rc, A... args) {
+#define FAVOR_CASE(DHv, MFv)                                                                                                                  \
+    if (a.dh == DHv && a.n_feat == 2 * MFv) {                                                                                                 \
+        *rc = attn_by_dtype<FavorAt<F, DHv, MFv>>(a, args...);                                                                                \
+        return true;                                                                                                                          \
+    }
+    FAVOR_CASE(64, 64)
+    FAVOR_CASE(32, 64)
+    FAVOR_CASE(32, 32)
+    FAVOR_CASE(16, 16)
+    FAVOR_CASE(16, 32)
+#undef FAVOR_CASE
+    return false;
+}
+
+// The FWD and BWD passes.  What a pass does not read never reaches a kernel (emo_hip.h: "A field that a kind/pass does not read is ignored"):
+// FWD hands over no dout, dq, dk, dv; BWD no state_S, state_z (also not in the state-only forward it launches); with dout_is_dn, den, workspace,
+// workspace_bytes and kstate_valid are dropped too, which forces P = 1; kstate_valid counts only with a workspace.
+struct FavorRun {
+template <typename CT, int DH, int MF> static int run(const emo_attn_t& a, hipStream_t st) {
+    typedef FavorChunks<CT, DH, MF> C;
     constexpr int F = 2 * MF;
+    const bool fwd = a.pass == EMO_ATTN_FWD, dn = !fwd && a.dout_is_dn != 0;
+    const int64_t B = a.B, T = a.T, H = a.H;
+    void* const workspace = dn ? nullptr : a.workspace;
     int P = 1; int64_t Ts = T > 0 ? T : 1;
     if (workspace) {
         favor_segments(B, T, H, &P, &Ts);
         const int64_t need = P > 1 ? B * H * P * (int64_t)(F * DH + F) * (int64_t)sizeof(float) : 0;
-        EMO_CHECK(workspace_bytes >= need, "workspace %lld B < %lld B (emo_favor_attn_workspace_bytes)", (long long)workspace_bytes, (long long)need);
+        EMO_CHECK(a.workspace_bytes >= need, "workspace %lld B < %lld B (emo_favor_attn_workspace_bytes)", (long long)a.workspace_bytes, (long long)need);
         EMO_CHECK(((uintptr_t)workspace & 15) == 0, "workspace must be 16-B aligned");
     }
     if (P <= 1) { P = 1; Ts = T > 0 ? T : 1; }
     float* wsS = (float*)workspace;
     float* wsz = wsS ? wsS + B * H * P * (int64_t)F * DH : nullptr;
-    dim3 grid((unsigned)(B * H * P));
+    const dim3 grid((unsigned)(B * H * P)), block(FT);
+    const CT *q = (const CT*)a.q, *k = (const CT*)a.k, *v = (const CT*)a.v;
     // bf16 / d_head 64 / 128 features: the main passes run on the slice kernels (emo_favor_fs.hip); with P > 1 they start every segment from the
-    // increments that the generic state-only passes below leave in the workspace
-    constexpr bool FS = sizeof(CT) == 2 && DH == 64 && MF == 64;
-    auto fs_try = [&](int stage) -> bool {
-        if constexpr (FS) {
-            if (emo_favor_fs_try(which, stage, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ld, omega, (bf16_t*)out, ld_out, den, sS, sz, (const bf16_t*)dout,
-                                 (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, ld_d, B, T, H, eps, wsS, wsz, P, Ts, st))
-                return true;
+    // increments that the generic state-only passes below leave in the workspace.
+    // 1: served; 0: the generic kernel runs; < 0: error — a refusal under EMO_FAVOR_FS=2 is one (EMO_ERR_INVALID)
+    auto slice = [&](favor_stage_t stage) -> int {
+        if constexpr (sizeof(CT) == 2 && DH == 64 && MF == 64) {
+            const int rc = emo_favor_fs_try(a, stage, P, Ts, wsS, wsz, st);
+            if (rc) return rc;
         }
-        const char* e = getenv("EMO_FAVOR_FS");
-        if (e && atoi(e) == 2) emo_set_error("EMO_FAVOR_FS=2 but the slice kernels do not cover this call");
-        return false;
+        if (env_int("EMO_FAVOR_FS", 0) != 2) return 0;
+        emo_set_error("EMO_FAVOR_FS=2 but the slice kernels do not cover this call");
+        return EMO_ERR_INVALID;
     };
-    auto fs_required_failed = [&]() { const char* e = getenv("EMO_FAVOR_FS"); return e && atoi(e) == 2; };
-    if (which == 0) {
-        const size_t lds = fwd_lds<CT, DH, MF, CF>();
-        EMO_CHECK(lds <= EMO_MAX_LDS, "LDS %zu too large", lds);
-        auto kf = favor_fwd_kernel<CT, DH, MF, CF, false>;
-        auto ks = favor_fwd_kernel<CT, DH, MF, CF, true>;
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute((const void*)ks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr = true;
-        }
-        if (P > 1)
-            hipLaunchKernelGGL(ks, grid, dim3(FT), lds, st, (const CT*)q, (const CT*)k, (const CT*)v, ld, omega, (CT*)out, ld_out, den, sS, sz, T, H, eps, wsS,
-                               wsz, P, Ts);
-        const char* ab = getenv("EMO_FAVOR_ABLATE");   // diagnostics only
-        if (!fs_try(0)) {
-            if (fs_required_failed()) return EMO_ERR_INVALID;
-            hipLaunchKernelGGL(kf, grid, dim3(FT), lds, st, (const CT*)q, (const CT*)k, (const CT*)v, ld, omega, (CT*)out, ld_out, den, sS, sz, T, H, eps, wsS, wsz,
-                               P | (ab ? atoi(ab) << 8 : 0), Ts);
-        }
-    } else {
-        const size_t l0 = fwd_lds<CT, DH, MF, CF>(), l1 = dq_lds<CT, DH, MF, CQ>(), l2 = dkv_lds<CT, DH, MF, CK>();
-        EMO_CHECK(l0 <= EMO_MAX_LDS && l1 <= EMO_MAX_LDS && l2 <= EMO_MAX_LDS, "LDS %zu / %zu / %zu too large", l0, l1, l2);
-        auto k0 = favor_fwd_kernel<CT, DH, MF, CF, true>;
-        auto k1 = favor_bwd_dq_kernel<CT, DH, MF, CQ>;
-        auto k2 = favor_bwd_dkv_kernel<CT, DH, MF, CK, false>;
-        auto k2s = favor_bwd_dkv_kernel<CT, DH, MF, CK, true>;
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute((const void*)k0, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l0);
-            (void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l1);
-            (void)hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
-            (void)hipFuncSetAttribute((const void*)k2s, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
-            attr = true;
-        }
-        if (dn) {
-            // dout_is_dn: `dout` is dN = dout / den already (den = NULL down here) — only the slice kernels' single-segment instances take that form
-            EMO_CHECK(FS && P == 1, "dout_is_dn needs bf16, d_head 64, 128 features and a single-segment scan (B * H >= 256): emo_favor_attn_bwd_dn_supported()");
-            if (!fs_try(1) || !fs_try(2)) {
-                emo_set_error("the slice kernels refused this call (T %% 32, 16-B alignment, EMO_FAVOR_FS / EMO_FAVOR_FS_BWD = 0)");
-                return EMO_ERR_UNSUPPORTED;
-            }
-            EMO_LAUNCH_CHECK();
-            return EMO_OK;
-        }
-        // P > 1: the K-state increments are recomputed (state-only forward pass), then the workspace is reused for the R-state increments
-        // (kstate_valid: the caller kept the forward's workspace — the same increments — for this call)
-        if (P > 1 && !kstate_valid)
-            hipLaunchKernelGGL(k0, grid, dim3(FT), l0, st, (const CT*)q, (const CT*)k, (const CT*)v, ld, omega, (CT*)nullptr, ld_out, (float*)nullptr,
-                               (float*)nullptr, (float*)nullptr, T, H, eps, wsS, wsz, P, Ts);
-        if (!fs_try(1)) {
-            if (fs_required_failed()) return EMO_ERR_INVALID;
-            hipLaunchKernelGGL(k1, grid, dim3(FT), l1, st, (const CT*)q, (const CT*)k, (const CT*)v, ld, omega, (const CT*)out, (const CT*)dout, ld_out, den,
-                               (CT*)dq, ld_d, T, H, (const float*)wsS, (const float*)wsz, P | (getenv("EMO_FAVOR_ABLATE_DQ") ? atoi(getenv("EMO_FAVOR_ABLATE_DQ")) << 8 : 0), Ts);
-        }
-        if (P > 1)
-            hipLaunchKernelGGL(k2s, grid, dim3(FT), l2, st, (const CT*)q, (const CT*)k, (const CT*)v, ld, omega, (const CT*)out, (const CT*)dout, ld_out, den,
-                               (CT*)dk, (CT*)dv, ld_d, T, H, wsS, wsz, P, Ts);
-        if (!fs_try(2)) {
-            if (fs_required_failed()) return EMO_ERR_INVALID;
-            hipLaunchKernelGGL(k2, grid, dim3(FT), l2, st, (const CT*)q, (const CT*)k, (const CT*)v, ld, omega, (const CT*)out, (const CT*)dout, ld_out, den,
-                               (CT*)dk, (CT*)dv, ld_d, T, H, wsS, wsz, P | (getenv("EMO_FAVOR_ABLATE_DKV") ? atoi(getenv("EMO_FAVOR_ABLATE_DKV")) << 8 : 0), Ts);
-        }
+    const size_t l0 = fwd_lds<CT, DH, MF, C::CF>();
+    constexpr auto state_only = favor_fwd_kernel<CT, DH, MF, C::CF, true>;
+    if (fwd) {
+        EMO_CHECK(l0 <= EMO_MAX_LDS, "LDS %zu too large", l0);
+        if (P > 1) EMO_TRY(emo_launch<state_only>(grid, block, l0, st, q, k, v, a.ld, a.omega, (CT*)a.out, a.ld_out, a.den, a.state_S, a.state_z, T, H, a.eps, wsS, wsz, P, Ts));
+        const int served = slice(FAVOR_STAGE_FWD);
+        if (served) return served < 0 ? served : EMO_OK;
+        return emo_launch<favor_fwd_kernel<CT, DH, MF, C::CF, false>>(grid, block, l0, st, q, k, v, a.ld, a.omega, (CT*)a.out, a.ld_out, a.den, a.state_S, a.state_z, T, H,
+                                                                      a.eps, wsS, wsz, P | (env_int("EMO_FAVOR_ABLATE", 0) << 8), Ts);   // (ABLATE*: diagnostics only)
     }
-    EMO_LAUNCH_CHECK();
-    return EMO_OK;
+    const size_t l1 = dq_lds<CT, DH, MF, C::CQ>(), l2 = dkv_lds<CT, DH, MF, C::CK>();
+    EMO_CHECK(l0 <= EMO_MAX_LDS && l1 <= EMO_MAX_LDS && l2 <= EMO_MAX_LDS, "LDS %zu / %zu / %zu too large", l0, l1, l2);
+    if (dn) {
+        // dout_is_dn: `dout` is dN = dout / den already — only the slice kernels' single-segment instances take that form
+        EMO_CHECK(sizeof(CT) == 2 && DH == 64 && MF == 64 && P == 1,
+                  "dout_is_dn needs bf16, d_head 64, 128 features and a single-segment scan (B * H >= 256): emo_favor_attn_bwd_dn_supported()");
+        int served = slice(FAVOR_STAGE_DQ);
+        if (served > 0) served = slice(FAVOR_STAGE_DKV);
+        if (served == EMO_ERR_LAUNCH) return served;
+        if (served <= 0) {
+            emo_set_error("the slice kernels refused this call (T %% 32, 16-B alignment, EMO_FAVOR_FS / EMO_FAVOR_FS_BWD = 0)");
+            return EMO_ERR_UNSUPPORTED;
+        }
+        return EMO_OK;
+    }
+    const CT *out = (const CT*)a.out, *dout = (const CT*)a.dout;
+    // Launch order: K-state, dq, R-state, dk/dv.  P > 1: the K-state increments are recomputed (state-only forward pass), then the workspace is
+    // reused for the R-state increments (kstate_valid: the caller kept the forward's workspace — the same increments — for this call)
+    if (P > 1 && !(a.kstate_valid != 0 && workspace))
+        EMO_TRY(emo_launch<state_only>(grid, block, l0, st, q, k, v, a.ld, a.omega, (CT*)nullptr, a.ld_out, (float*)nullptr, (float*)nullptr, (float*)nullptr, T, H, a.eps,
+                                       wsS, wsz, P, Ts));
+    int served = slice(FAVOR_STAGE_DQ);
+    if (served < 0) return served;
+    if (!served)
+        EMO_TRY(emo_launch<favor_bwd_dq_kernel<CT, DH, MF, C::CQ>>(grid, block, l1, st, q, k, v, a.ld, a.omega, out, dout, a.ld_out, a.den, (CT*)a.dq, a.ld_d, T, H,
+                                                                   (const float*)wsS, (const float*)wsz, P | (env_int("EMO_FAVOR_ABLATE_DQ", 0) << 8), Ts));
+    if (P > 1)
+        EMO_TRY(emo_launch<favor_bwd_dkv_kernel<CT, DH, MF, C::CK, true>>(grid, block, l2, st, q, k, v, a.ld, a.omega, out, dout, a.ld_out, a.den, (CT*)a.dk, (CT*)a.dv,
+                                                                          a.ld_d, T, H, wsS, wsz, P, Ts));
+    served = slice(FAVOR_STAGE_DKV);
+    if (served) return served < 0 ? served : EMO_OK;
+    return emo_launch<favor_bwd_dkv_kernel<CT, DH, MF, C::CK, false>>(grid, block, l2, st, q, k, v, a.ld, a.omega, out, dout, a.ld_out, a.den, (CT*)a.dk, (CT*)a.dv, a.ld_d,
+                                                                      T, H, wsS, wsz, P | (env_int("EMO_FAVOR_ABLATE_DKV", 0) << 8), Ts);
 }
+};
 
-static int dispatch_favor(int which, int dtype, int64_t dh, int64_t mf, const void* q, const void* k, const void* v, int64_t ld, const float* omega,
-                          void* out, int64_t ld_out, float* den, float* sS, float* sz, const void* dout, void* dq, void* dk, void* dv, int64_t ld_d,
-                          int64_t B, int64_t T, int64_t H, float eps, void* ws, int64_t ws_bytes, hipStream_t st, bool kstate_valid, bool dn) {
-#define FAVOR_CASE(DHv, MFv, CFb, CQb, CKb, CFf, CQf, CKf)                                                                                   \
-    if (dh == DHv && mf == MFv) {                                                                                                            \
-        if (dtype == EMO_BF16)                                                                                                               \
-            return run_favor<bf16_t, DHv, MFv, CFb, CQb, CKb>(which, q, k, v, ld, omega, out, ld_out, den, sS, sz, dout, dq, dk, dv, ld_d, B, T, H, eps, ws, \
-                                                              ws_bytes, st, kstate_valid, dn);                                               \
-        return run_favor<float, DHv, MFv, CFf, CQf, CKf>(which, q, k, v, ld, omega, out, ld_out, den, sS, sz, dout, dq, dk, dv, ld_d, B, T, H, eps, ws,      \
-                                                         ws_bytes, st, kstate_valid, dn);                                                    \
-    }
-    FAVOR_CASE(64, 64, FAVOR_CFB, FAVOR_CQB, FAVOR_CKB, 32, 32, 16)
-    FAVOR_CASE(32, 64, 64, 64, 64, 32, 32, 32)
-    FAVOR_CASE(32, 32, 64, 64, 64, 32, 32, 32)
-    FAVOR_CASE(16, 16, 64, 64, 64, 32, 32, 32)
-    FAVOR_CASE(16, 32, 64, 64, 64, 32, 32, 32)
-#undef FAVOR_CASE
-    emo_set_error("unsupported (d_head=%lld, n_feat=%lld); built: (64,128) (32,128) (32,64) (16,32) (16,64)", (long long)dh,
-                  (long long)(2 * mf));
+static int favor_train(const emo_attn_t& a, hipStream_t st) {
+    int rc;
+    if (favor_table<FavorRun>(a, &rc, st)) return rc;
+    emo_set_error("unsupported (d_head=%lld, n_feat=%lld); built: (64,128) (32,128) (32,64) (16,32) (16,64)", (long long)a.dh, (long long)a.n_feat);
     return EMO_ERR_UNSUPPORTED;
 }
 
 // 1 when the dout_is_dn form of the backward serves this problem (the single-segment slice kernels), else 0
 extern "C" int emo_favor_attn_bwd_dn_supported(int dtype, int64_t B, int64_t T, int64_t H, int64_t dh, int64_t n_feat) {
     if (dtype != EMO_BF16 || dh != 64 || n_feat != 128 || T < 32 || (T % 32) != 0 || B * H <= 0) return 0;
-    const char* e = getenv("EMO_FAVOR_FS");
-    const char* e2 = getenv("EMO_FAVOR_FS_BWD");
-    if ((e && atoi(e) == 0) || (e2 && atoi(e2) == 0)) return 0;
+    if (env_off("EMO_FAVOR_FS") || env_off("EMO_FAVOR_FS_BWD")) return 0;
     int P; int64_t Ts;
     favor_segments(B, T, H, &P, &Ts);
     return P <= 1 ? 1 : 0;
 }
 
 // The DECODE pass of the FAVOR kind: one recurrent step per stream
+struct FavorDecodeFast {
+    template <typename CT, int DH, int MF> static int run(const emo_attn_t& a, hipStream_t st) {
+        return emo_launch<favor_decode_fast_kernel<CT, DH, MF>>(dim3((unsigned)(a.B * a.H)), dim3(256), 0, st, (const CT*)a.q, (const CT*)a.k, (const CT*)a.v, a.ld, a.omega,
+                                                                a.state_S, a.state_z, (CT*)a.out, a.ld_out, a.H, a.eps);
+    }
+};
+struct FavorDecodeGeneric {
+    template <typename CT> static int run(const emo_attn_t& a, hipStream_t st) {
+        return emo_launch<favor_decode_kernel<CT>>(dim3((unsigned)(a.B * a.H)), dim3(256), 0, st, (const CT*)a.q, (const CT*)a.k, (const CT*)a.v, a.ld, a.omega, a.state_S,
+                                                   a.state_z, (CT*)a.out, a.ld_out, a.H, (int)a.dh, (int)(a.n_feat / 2), a.eps);
+    }
+};
 static int favor_decode(const emo_attn_t& a, hipStream_t st) {
     EMO_CHECK(a.q && a.k && a.v && a.omega && a.state_S && a.state_z && a.out, "null pointer");
     EMO_CHECK(a.dh <= 64 && a.dh >= 16 && 256 % a.dh == 0 && a.n_feat <= 128, "needs 16<=d_head<=64 dividing 256, n_feat<=128");
-    dim3 grid((unsigned)(a.B * a.H));
-#define DECODE_LAUNCH(CTv, DHv, MFv)                                                                                                            \
-    hipLaunchKernelGGL((favor_decode_fast_kernel<CTv, DHv, MFv>), grid, dim3(256), 0, st, (const CTv*)a.q, (const CTv*)a.k, (const CTv*)a.v, a.ld, a.omega, \
-                       a.state_S, a.state_z, (CTv*)a.out, a.ld_out, a.H, a.eps)
-#define DECODE_CASE(DHv, MFv)                                                                                                                   \
-    if (a.dh == DHv && a.n_feat == 2 * MFv) {                                                                                                   \
-        if (a.dtype == EMO_F32) DECODE_LAUNCH(float, DHv, MFv); else DECODE_LAUNCH(bf16_t, DHv, MFv);                                           \
-        EMO_LAUNCH_CHECK();                                                                                                                     \
-        return EMO_OK;                                                                                                                          \
-    }
-    if (getenv("EMO_FAVOR_DECODE_GENERIC") == nullptr && (((uintptr_t)a.state_S) & 15) == 0) {
-        DECODE_CASE(64, 64)
-        DECODE_CASE(32, 64)
-        DECODE_CASE(32, 32)
-        DECODE_CASE(16, 16)
-        DECODE_CASE(16, 32)
-    }
-#undef DECODE_CASE
-#undef DECODE_LAUNCH
-    if (a.dtype == EMO_F32)
-        hipLaunchKernelGGL(favor_decode_kernel<float>, grid, dim3(256), 0, st, (const float*)a.q, (const float*)a.k, (const float*)a.v, a.ld, a.omega, a.state_S,
-                           a.state_z, (float*)a.out, a.ld_out, a.H, (int)a.dh, (int)(a.n_feat / 2), a.eps);
-    else
-        hipLaunchKernelGGL(favor_decode_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)a.q, (const bf16_t*)a.k, (const bf16_t*)a.v, a.ld, a.omega, a.state_S,
-                           a.state_z, (bf16_t*)a.out, a.ld_out, a.H, (int)a.dh, (int)(a.n_feat / 2), a.eps);
-    EMO_LAUNCH_CHECK();
-    return EMO_OK;
+    // the instance of the table row (16-B accesses to the state), else the generic kernel
+    int rc;
+    if (getenv("EMO_FAVOR_DECODE_GENERIC") == nullptr && (((uintptr_t)a.state_S) & 15) == 0 && favor_table<FavorDecodeFast>(a, &rc, st)) return rc;
+    return attn_by_dtype<FavorDecodeGeneric>(a, st);
 }
 
 extern "C" int emo_favor_state_reset(const void* state_table, int64_t n_layers, int64_t n_rows, int64_t s_row_floats, int64_t z_row_floats,
@@ -1490,8 +1462,7 @@ int emo_attn_favor(const emo_attn_t& a, hipStream_t st) {
         EMO_CHECK(a.omega && a.out && a.den, "null pointer");
         EMO_CHECK(((uintptr_t)a.out & 15) == 0, "out must be 16-B aligned");
         EMO_CHECK(!(a.state_S && !a.state_z), "state_S without state_z");
-        return dispatch_favor(0, a.dtype, a.dh, a.n_feat / 2, a.q, a.k, a.v, a.ld, a.omega, a.out, a.ld_out, a.den, a.state_S, a.state_z, nullptr, nullptr, nullptr,
-                              nullptr, 0, a.B, a.T, a.H, a.eps, a.workspace, a.workspace_bytes, st, false, false);
+        return favor_train(a, st);
     }
     // dout_is_dn: neither the normaliser nor a workspace is read (single-segment scan)
     const bool dn = a.dout_is_dn != 0;
@@ -1499,7 +1470,5 @@ int emo_attn_favor(const emo_attn_t& a, hipStream_t st) {
     EMO_CHECK(!dn || emo_favor_attn_bwd_dn_supported(a.dtype, a.B, a.T, a.H, a.dh, a.n_feat), "dout_is_dn outside its class (emo_favor_attn_bwd_dn_supported)");
     EMO_CHECK(a.ld_d % 4 == 0, "ld_d must be a multiple of 4");
     EMO_CHECK((((uintptr_t)a.dq | (uintptr_t)a.dk | (uintptr_t)a.dv | (uintptr_t)a.out | (uintptr_t)a.dout) & 15) == 0, "pointers must be 16-B aligned");
-    void* const ws = dn ? nullptr : a.workspace;
-    return dispatch_favor(1, a.dtype, a.dh, a.n_feat / 2, a.q, a.k, a.v, a.ld, a.omega, a.out, a.ld_out, dn ? nullptr : a.den, nullptr, nullptr, a.dout, a.dq, a.dk,
-                          a.dv, a.ld_d, a.B, a.T, a.H, a.eps, ws, dn ? 0 : a.workspace_bytes, st, a.kstate_valid != 0 && ws != nullptr, dn);
+    return favor_train(a, st);
 }

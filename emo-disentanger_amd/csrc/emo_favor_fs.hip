@@ -20,6 +20,7 @@
 // Requirements: bf16, d_head 64, n_feat 128, T % 32 == 0, single-segment scan; everything else stays on emo_favor.hip.
 #include "emo_common.h"
 
+#include "emo_attn_host.h"
 #include "emo_lds_mma.h"
 
 #ifdef EMO_DIAG
@@ -1174,63 +1175,43 @@ __global__ __launch_bounds__(FS_NT, 2) void favor_fs_dkv_kernel(const bf16_t* __
 }
 }  // namespace
 
-// which: 0 forward, 1 backward main passes (P > 1: the caller has run the generic state-only pass into S_ws / z_ws — for the backward the
-// K-state increments before `stage` 1 (dq) and the R-state increments before `stage` 2 (dk, dv)).  stage: 0 = whole call (P == 1 only),
-// 1 = dq, 2 = dk / dv.  Returns 0 when the shape / mode is not covered (the caller then runs the generic kernels), 1 when it was served.
-// den == nullptr in a backward call: `dout` is dN = dout / den (emo_attn_t.dout_is_dn) — the PRE instances.
-int emo_favor_fs_try(int which, int stage, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld, const float* omega, bf16_t* out, int64_t ld_out,
-                     float* den, float* sS, float* sz, const bf16_t* dout, bf16_t* dq, bf16_t* dk, bf16_t* dv, int64_t ld_d, int64_t B, int64_t T, int64_t H,
-                     float eps, const float* ws_S, const float* ws_z, int P, int64_t Ts, hipStream_t st) {
-    const char* e = getenv("EMO_FAVOR_FS");                // (read per call: tests toggle it in-process)  "0": generic kernels only
-    if (e && atoi(e) == 0) return 0;
-    if (T < FS_C || (T % FS_C) != 0 || B * H <= 0 || P < 1 || (P > 1 && (Ts % FS_C) != 0)) return 0;
-    if ((ld & 7) || (ld_out & 7) || (ld_d & 3)) return 0;
+// =============================================================================================== host (contract: emo_attn_host.h)
+// The FWD stage reads no dout, dq, dk, dv or ld_d, the backward stages no state_S / state_z; with a.dout_is_dn, `dout` is dN = dout / den and the PRE
+// instances run, which take no den.
+int emo_favor_fs_try(const emo_attn_t& a, favor_stage_t stage, int P, int64_t Ts, const float* ws_S, const float* ws_z, hipStream_t st) {
+    if (env_off("EMO_FAVOR_FS")) return 0;                 // generic kernels only
+    const bool fwd = stage == FAVOR_STAGE_FWD;
+    const int64_t T = a.T, H = a.H;
+    if (T < FS_C || (T % FS_C) != 0 || a.B * H <= 0 || P < 1 || (P > 1 && (Ts % FS_C) != 0)) return 0;
+    if ((a.ld & 7) || (a.ld_out & 7) || (!fwd && (a.ld_d & 3))) return 0;
     // 16-B LDS-DMA pieces of q / k / v / out / dout rows and 8-/16-B output stores: unaligned views fall back to the generic kernels
-    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)dout) & 15) || (((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 15)) return 0;
+    if (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.out) & 15) return 0;
+    if (!fwd && (((uintptr_t)a.dout | (uintptr_t)a.dq | (uintptr_t)a.dk | (uintptr_t)a.dv) & 15)) return 0;
     if (P == 1) Ts = T;
     // short segments (B*H < 256; r03: the generic forward was faster there, 66 vs 89 us per layer at B=4 x T=2048 in 8 segments, because of the
     // carried-in state loop below)
     // (r04: with the carried-in state loaded without a branch between the loads the segmented forward is 44 us against the generic 66 — default on)
-    dim3 grid((unsigned)(B * H * P));
-    if (which == 0) {
+    const dim3 grid((unsigned)(a.B * H * P)), block(FS_NT);
+    const bf16_t *q = (const bf16_t*)a.q, *k = (const bf16_t*)a.k, *v = (const bf16_t*)a.v, *out = (const bf16_t*)a.out, *dout = (const bf16_t*)a.dout;
+    int rc;
+    if (fwd) {
         const size_t lds = (size_t)(3 * 2 + 4) * FS_TILEB + sizeof(bf16_t) * (size_t)(4 * FS_C * FS_LDF);
-        static bool attr = false;
-        if (!attr) { (void)hipFuncSetAttribute((const void*)favor_fs_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-        hipLaunchKernelGGL(favor_fs_fwd_kernel, grid, dim3(FS_NT), lds, st, q, k, v, ld, omega, out, ld_out, den, sS, sz, T, H, eps, ws_S, ws_z, P, Ts);
-        return 1;
+        rc = emo_launch<favor_fs_fwd_kernel>(grid, block, lds, st, q, k, v, a.ld, a.omega, (bf16_t*)a.out, a.ld_out, a.den, a.state_S, a.state_z, T, H, a.eps, ws_S, ws_z, P, Ts);
+        return rc ? rc : 1;
     }
-    const char* e2 = getenv("EMO_FAVOR_FS_BWD");               // "0": generic backward kernels
-    if (e2 && atoi(e2) == 0) return 0;
-    const bool pre = den == nullptr;
-    if (stage == 0 || stage == 1) {
+    if (env_off("EMO_FAVOR_FS_BWD")) return 0;             // generic backward kernels
+    const bool pre = a.dout_is_dn != 0;
+    const float* den = pre ? nullptr : a.den;
+    if (stage == FAVOR_STAGE_DQ) {
         const size_t lds = (size_t)3 * FS_SLOTB + 3 * 256 + 4 * 2048 + 2 * FS_TILEB + 2 * 4 * 32 * sizeof(float);
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute((const void*)favor_fs_dq_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute((const void*)favor_fs_dq_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr = true;
-        }
-        if (pre)
-            hipLaunchKernelGGL(favor_fs_dq_kernel<true>, grid, dim3(FS_NT), lds, st, q, k, v, ld, omega, (const bf16_t*)out, dout, ld_out, (const float*)nullptr, dq, ld_d, T, H,
-                               ws_S, ws_z, P, Ts);
-        else
-            hipLaunchKernelGGL(favor_fs_dq_kernel<false>, grid, dim3(FS_NT), lds, st, q, k, v, ld, omega, (const bf16_t*)out, dout, ld_out, (const float*)den, dq, ld_d, T, H,
-                               ws_S, ws_z, P, Ts);
+        rc = pre ? emo_launch<favor_fs_dq_kernel<true>>(grid, block, lds, st, q, k, v, a.ld, a.omega, out, dout, a.ld_out, den, (bf16_t*)a.dq, a.ld_d, T, H, ws_S, ws_z, P, Ts)
+                 : emo_launch<favor_fs_dq_kernel<false>>(grid, block, lds, st, q, k, v, a.ld, a.omega, out, dout, a.ld_out, den, (bf16_t*)a.dq, a.ld_d, T, H, ws_S, ws_z, P, Ts);
+    } else {
+        const size_t lds = (size_t)2 * FS_SLOTB + 2 * 256 + sizeof(bf16_t) * (size_t)(2 * FS_C * FS_LDF) + FS_TILEB + sizeof(float) * (128 + 4 * 96);
+        rc = pre ? emo_launch<favor_fs_dkv_kernel<true>>(grid, block, lds, st, q, k, v, a.ld, a.omega, out, dout, a.ld_out, den, (bf16_t*)a.dk, (bf16_t*)a.dv, a.ld_d, T, H,
+                                                         ws_S, ws_z, P, Ts)
+                 : emo_launch<favor_fs_dkv_kernel<false>>(grid, block, lds, st, q, k, v, a.ld, a.omega, out, dout, a.ld_out, den, (bf16_t*)a.dk, (bf16_t*)a.dv, a.ld_d, T, H,
+                                                          ws_S, ws_z, P, Ts);
     }
-    if (stage == 0 || stage == 2) {
-        const size_t lds2 = (size_t)2 * FS_SLOTB + 2 * 256 + sizeof(bf16_t) * (size_t)(2 * FS_C * FS_LDF) + FS_TILEB + sizeof(float) * (128 + 4 * 96);
-        static bool attr2 = false;
-        if (!attr2) {
-            (void)hipFuncSetAttribute((const void*)favor_fs_dkv_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-            (void)hipFuncSetAttribute((const void*)favor_fs_dkv_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-            attr2 = true;
-        }
-        if (pre)
-            hipLaunchKernelGGL(favor_fs_dkv_kernel<true>, grid, dim3(FS_NT), lds2, st, q, k, v, ld, omega, (const bf16_t*)out, dout, ld_out, (const float*)nullptr, dk, dv, ld_d, T, H,
-                               ws_S, ws_z, P, Ts);
-        else
-            hipLaunchKernelGGL(favor_fs_dkv_kernel<false>, grid, dim3(FS_NT), lds2, st, q, k, v, ld, omega, (const bf16_t*)out, dout, ld_out, (const float*)den, dk, dv, ld_d, T, H,
-                               ws_S, ws_z, P, Ts);
-    }
-    return 1;
+    return rc ? rc : 1;
 }

@@ -5,6 +5,7 @@
 // cross-lane-group shuffles.  K/V/Q/dO tiles are staged in padded LDS images and every contraction
 // is an NT product on MFMA (emo_lds_mma.h); masked key tiles above the diagonal are skipped.
 // Attention-prob dropout is regenerated from (seed, offset, ((b*H+h)*T+i)*T+j).
+#include "emo_attn_host.h"
 #include "emo_lds_mma.h"
 
 template <typename CT, int DH> struct SaDims {
@@ -497,83 +498,49 @@ template <typename CT, int DH> static size_t sa_fwd_lds() { typedef SaDims<CT, D
 template <typename CT, int DH> static size_t sa_dq_lds() { typedef SaDims<CT, DH> D; return sizeof(CT) * (size_t)(4 * 64 * D::LDX + (sizeof(CT) == 2 ? 0 : DH * D::LDC)) + 64 * sizeof(float); }
 template <typename CT, int DH> static size_t sa_dkv_lds() { typedef SaDims<CT, DH> D; return sizeof(CT) * (size_t)(4 * 64 * D::LDX + (sizeof(CT) == 2 ? 0 : 2 * DH * D::LDC)) + 128 * sizeof(float); }
 
-// emo_softmax_attn32.hip: bf16 / d_head 64 / T % 128 == 0 kernels on 32 x 32 x 16 tiles (false: not covered -> the kernels of this file)
-bool emo_sattn32_dkv_try(const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld, const bf16_t* dout, int64_t ld_out, const float* lse, const float* delta,
-                         bf16_t* dk, bf16_t* dv, int64_t ld_d, int64_t B, int64_t T, int64_t H, DropCtx drop, const uint32_t* keep, hipStream_t st);
-bool emo_sattn32_try(int which, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld, bf16_t* out, int64_t ld_out, float* lse, int64_t B, int64_t T,
-                     int64_t H, DropCtx drop, uint32_t* keep, hipStream_t st);
-int64_t emo_sattn32_keep_bytes(int64_t B, int64_t T, int64_t H, int64_t dh, float p_drop);
-bool emo_sattn32_dq_try(const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld, const bf16_t* out, const bf16_t* dout, int64_t ld_out, const float* lse,
-                        float* delta, bf16_t* dq, int64_t ld_d, int64_t B, int64_t T, int64_t H, DropCtx drop, const uint32_t* keep, hipStream_t st);
-
-template <typename CT, int DH>
-static int run_sattn(int which, const void* q, const void* k, const void* v, int64_t ld, const void* out, const void* dout, int64_t ld_out, float* lse,
-                     float* delta, void* dq, void* dk, void* dv, int64_t ld_d, int64_t B, int64_t T, int64_t H, DropCtx drop, uint32_t* keep, hipStream_t st) {
-    if constexpr (sizeof(CT) == 2 && DH == 64) {
-        if (which == 0 && emo_sattn32_try(0, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ld, (bf16_t*)out, ld_out, lse, B, T, H, drop, keep, st)) {
-            EMO_LAUNCH_CHECK();
-            return EMO_OK;
-        }
+// The FWD and BWD passes: the 32 x 32 kernels (emo_softmax_attn32.hip) where they serve the call, else the kernels of this file.  FWD reads no dout,
+// delta_ws, dq, dk or dv.  BWD launches dQ before dK/dV (the dQ pass writes delta_ws).
+struct SattnRun {
+template <typename CT, int DH> static int run(const emo_attn_t& a, DropCtx drop, hipStream_t st) {
+    constexpr bool A32 = sizeof(CT) == 2 && DH == 64;
+    const bool fwd = a.pass == EMO_ATTN_FWD;
+    int served = 0;
+    if constexpr (A32) {
+        if (fwd && (served = emo_sattn32_fwd_try(a, drop, st)) != 0) return served < 0 ? served : EMO_OK;
     }
     // keep words exist only in the 32 x 32 kernels' layout: a forward that cannot write them must not pretend to, a backward must not half-use them
-    EMO_CHECK(!(which == 0 && keep), "keep words requested but the call is not served by the 32 x 32 kernels (bf16, d_head 64, T %% 128 == 0, 16-B aligned views)");
-    dim3 grid((unsigned)(B * H), (unsigned)((T + 63) / 64));
-    static bool attr = false;
-    const size_t lfwd = sa_fwd_lds<CT, DH>(), ldq = sa_dq_lds<CT, DH>(), ldkv = sa_dkv_lds<CT, DH>();
-    auto kfwd = sattn_fwd_kernel<CT, DH>;
-    auto kdq = sattn_bwd_dq_kernel<CT, DH>;
-    auto kdkv = sattn_bwd_dkv_kernel<CT, DH>;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)kfwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lfwd);
-        (void)hipFuncSetAttribute((const void*)kdq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldq);
-        (void)hipFuncSetAttribute((const void*)kdkv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldkv);
-        attr = true;
-    }
-    if (which == 0) {
-        hipLaunchKernelGGL(kfwd, grid, dim3(256), lfwd, st, (const CT*)q, (const CT*)k, (const CT*)v, ld, (CT*)out, ld_out,
-                           lse, T, H, drop);
-    } else {
-        bool dq32 = false;
-        if constexpr (sizeof(CT) == 2 && DH == 64)
-            dq32 = emo_sattn32_dq_try((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ld, (const bf16_t*)out, (const bf16_t*)dout, ld_out, lse, delta, (bf16_t*)dq,
-                                      ld_d, B, T, H, drop, keep, st);
-        if (!dq32)
-            hipLaunchKernelGGL(kdq, grid, dim3(256), ldq, st, (const CT*)q, (const CT*)k, (const CT*)v, ld, (const CT*)out,
-                               (const CT*)dout, ld_out, lse, delta, (CT*)dq, ld_d, T, H, drop);
-        bool dkv32 = false;
-        if constexpr (sizeof(CT) == 2 && DH == 64)
-            dkv32 = emo_sattn32_dkv_try((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ld, (const bf16_t*)dout, ld_out, lse, delta, (bf16_t*)dk, (bf16_t*)dv, ld_d,
-                                        B, T, H, drop, keep, st);
-        EMO_CHECK(dkv32 || !keep, "keep words given but the 32 x 32 dK/dV kernel does not serve the call");
-        if (!dkv32)
-            hipLaunchKernelGGL(kdkv, grid, dim3(256), ldkv, st, (const CT*)q, (const CT*)k, (const CT*)v, ld, (const CT*)dout, ld_out, lse, delta, (CT*)dk,
-                               (CT*)dv, ld_d, T, H, drop);
-    }
-    EMO_LAUNCH_CHECK();
-    return EMO_OK;
+    EMO_CHECK(!(fwd && a.keep), "keep words requested but the call is not served by the 32 x 32 kernels (bf16, d_head 64, T %% 128 == 0, 16-B aligned views)");
+    const dim3 grid((unsigned)(a.B * a.H), (unsigned)((a.T + 63) / 64)), block(256);
+    const CT *q = (const CT*)a.q, *k = (const CT*)a.k, *v = (const CT*)a.v;
+    if (fwd) return emo_launch<sattn_fwd_kernel<CT, DH>>(grid, block, sa_fwd_lds<CT, DH>(), st, q, k, v, a.ld, (CT*)a.out, a.ld_out, a.lse, a.T, a.H, drop);
+    if constexpr (A32) served = emo_sattn32_dq_try(a, drop, st);
+    if (served < 0) return served;
+    if (!served)
+        EMO_TRY(emo_launch<sattn_bwd_dq_kernel<CT, DH>>(grid, block, sa_dq_lds<CT, DH>(), st, q, k, v, a.ld, (const CT*)a.out, (const CT*)a.dout, a.ld_out, a.lse, a.delta_ws,
+                                                        (CT*)a.dq, a.ld_d, a.T, a.H, drop));
+    served = 0;
+    if constexpr (A32) served = emo_sattn32_dkv_try(a, drop, st);
+    if (served < 0) return served;
+    EMO_CHECK(served || !a.keep, "keep words given but the 32 x 32 dK/dV kernel does not serve the call");
+    if (served) return EMO_OK;
+    return emo_launch<sattn_bwd_dkv_kernel<CT, DH>>(grid, block, sa_dkv_lds<CT, DH>(), st, q, k, v, a.ld, (const CT*)a.dout, a.ld_out, a.lse, a.delta_ws, (CT*)a.dk,
+                                                    (CT*)a.dv, a.ld_d, a.T, a.H, drop);
 }
-
-static int dispatch_sattn(int which, int dtype, int64_t dh, const void* q, const void* k, const void* v, int64_t ld, const void* out, const void* dout,
-                          int64_t ld_out, float* lse, float* delta, void* dq, void* dk, void* dv, int64_t ld_d, int64_t B, int64_t T, int64_t H,
-                          DropCtx drop, uint32_t* keep, hipStream_t st) {
-#define SA_CASE(DHv)                                                                                                                      \
-    if (dh == DHv) {                                                                                                                      \
-        if (dtype == EMO_BF16) return run_sattn<bf16_t, DHv>(which, q, k, v, ld, out, dout, ld_out, lse, delta, dq, dk, dv, ld_d, B, T, H, drop, keep, st); \
-        return run_sattn<float, DHv>(which, q, k, v, ld, out, dout, ld_out, lse, delta, dq, dk, dv, ld_d, B, T, H, drop, keep, st);             \
-    }
-    SA_CASE(64)
-    SA_CASE(32)
-    SA_CASE(16)
-#undef SA_CASE
-    emo_set_error("unsupported d_head=%lld (built: 16, 32, 64)", (long long)dh);
-    return EMO_ERR_UNSUPPORTED;
-}
+};
 
 extern "C" int64_t emo_softmax_attn_keep_bytes(int dtype, int64_t B, int64_t T, int64_t H, int64_t dh, float p_drop) {
     return dtype == EMO_BF16 ? emo_sattn32_keep_bytes(B, T, H, dh, p_drop) : 0;
 }
 
 // The DECODE pass of the SOFTMAX kind: one query row per stream against the KV caches
+struct SattnDecode {
+    template <typename CT, int NT> static int launch(const emo_attn_t& a, hipStream_t st) {
+        return emo_launch_lds<sattn_decode_kernel<CT, NT>>(dim3((unsigned)(a.B * a.H)), dim3(NT), (NT == 1024 ? 96 : 128) * 1024, (size_t)a.T_max * sizeof(float), st,
+                                                           (const CT*)a.q, a.ld, (CT*)a.kcache, (CT*)a.vcache, a.T_max, a.lens, a.lens_off, (const CT*)a.k, (const CT*)a.v,
+                                                           a.ld, (CT*)a.out, a.ld_out, a.H, (int)a.dh, (int)a.head_major);
+    }
+    template <typename CT> static int run(const emo_attn_t& a, int nt, hipStream_t st) { return nt == 1024 ? launch<CT, 1024>(a, st) : launch<CT, 256>(a, st); }
+};
 static int softmax_decode(const emo_attn_t& a, hipStream_t st) {
     EMO_CHECK(a.q && a.kcache && a.vcache && a.lens && a.out, "null pointer");
     EMO_CHECK(a.dh == 16 || a.dh == 32 || a.dh == 64 || a.dh == 128, "d_head must be 16, 32, 64 or 128");
@@ -581,8 +548,6 @@ static int softmax_decode(const emo_attn_t& a, hipStream_t st) {
     const int64_t ve = a.dtype == EMO_BF16 ? 8 : 4;
     EMO_CHECK((((uintptr_t)a.kcache | (uintptr_t)a.vcache) & 15) == 0 && (a.H * a.dh) % ve == 0, "caches must be 16-B aligned");
     EMO_CHECK(a.T_max * 4 <= 128 * 1024, "T_max too large for the LDS score buffer");
-    dim3 grid((unsigned)(a.B * a.H));
-    const size_t lds = (size_t)a.T_max * sizeof(float);
     // one workgroup per (stream, head) = at most one per CU at 32 streams x 8 heads: 16 waves instead of 4 give the CU's memory pipe four
     // times the requests in flight (r05; EMO_SATTN_DECODE_NT=256 keeps the 4-wave instance).  GPT-2 generation, 32 streams x 2048: 25 us per
     // layer with 8 rows per thread in flight, 20 us with 16 waves (the CU's own ~10 B/clk HBM rate gives 12 us for its 270 KB at the mean
@@ -592,21 +557,9 @@ static int softmax_decode(const emo_attn_t& a, hipStream_t st) {
     // 1.5 x the bytes (every step fetches 1024 rows per (stream, head) whatever its context) and the kernel is bound by the CU's fetch rate, not
     // by its chain of round trips; removed, tools/ab_gen_gpt2.sh kept.  Requesting the next iteration's rows before the current ones are used
     // (software-pipelined sweeps) measured 0.585 against 0.566: more requests in flight per CU do not help either)
-    int nt = 1024;
-    { const char* e = getenv("EMO_SATTN_DECODE_NT"); if (e && atoi(e) == 256) nt = 256; }
+    int nt = env_int("EMO_SATTN_DECODE_NT", 0) == 256 ? 256 : 1024;
     if (a.T_max * 4 > 96 * 1024) nt = 256;                            // (two-pass kernel: score buffer + the 1024-thread instance's partial sums must fit the LDS)
-#define SD_LAUNCH(CTv, NTv)                                                                                                                \
-    do {                                                                                                                                   \
-        static bool set = false;                                                                                                           \
-        if (!set) { (void)hipFuncSetAttribute((const void*)sattn_decode_kernel<CTv, NTv>, hipFuncAttributeMaxDynamicSharedMemorySize, (NTv == 1024 ? 96 : 128) * 1024); set = true; } \
-        hipLaunchKernelGGL((sattn_decode_kernel<CTv, NTv>), grid, dim3(NTv), lds, st, (const CTv*)a.q, a.ld, (CTv*)a.kcache, (CTv*)a.vcache, a.T_max, a.lens, \
-                           a.lens_off, (const CTv*)a.k, (const CTv*)a.v, a.ld, (CTv*)a.out, a.ld_out, a.H, (int)a.dh, (int)a.head_major);          \
-    } while (0)
-    if (a.dtype == EMO_F32) { if (nt == 1024) SD_LAUNCH(float, 1024); else SD_LAUNCH(float, 256); }
-    else { if (nt == 1024) SD_LAUNCH(bf16_t, 1024); else SD_LAUNCH(bf16_t, 256); }
-#undef SD_LAUNCH
-    EMO_LAUNCH_CHECK();
-    return EMO_OK;
+    return attn_by_dtype<SattnDecode>(a, nt, st);
 }
 
 // The SOFTMAX kind of emo_attn (the entry, with the checks every kind shares, is at the end of this file)
@@ -626,11 +579,7 @@ static int attn_softmax(const emo_attn_t& a, hipStream_t st) {
                   "keep buffer of %lld bytes, need %lld (emo_softmax_attn_keep_bytes; 0 = not available for this call)", (long long)a.keep_bytes, (long long)need);
     }
     const DropCtx drop = make_drop(a.p_drop, a.seed, a.offset);
-    if (fwd)
-        return dispatch_sattn(0, a.dtype, a.dh, a.q, a.k, a.v, a.ld, a.out, nullptr, a.ld_out, a.lse, nullptr, nullptr, nullptr, nullptr, 0, a.B, a.T, a.H, drop,
-                              (uint32_t*)a.keep, st);
-    return dispatch_sattn(1, a.dtype, a.dh, a.q, a.k, a.v, a.ld, a.out, a.dout, a.ld_out, a.lse, a.delta_ws, a.dq, a.dk, a.dv, a.ld_d, a.B, a.T, a.H, drop,
-                          (uint32_t*)a.keep, st);
+    return attn_by_dtype_dh<SattnRun>(a, drop, st);
 }
 
 // =============================================================================================== relative-position attention (stage-1 Transformer-XL)
@@ -1528,69 +1477,49 @@ template <typename CT, int DH> static size_t ra_fwd_lds() {
     typedef SaDims<CT, DH> D;
     return sizeof(CT) * (size_t)(2 * 64 * D::LDX + CMax<DH * D::LDC, 64 * D::LDX>::v + 128 * D::LDX) + sizeof(float) * 4 * 16 * 84;
 }
-template <typename CT, int DH>
-static int run_relattn(const void* q, const void* k, const void* v, int64_t ld, const void* rd, int64_t ld_r, int64_t n_dist, const float* ub, const float* vb,
-                       void* out, int64_t ld_out, float* lse, float* zden, int64_t window, int64_t B, int64_t T, int64_t H, DropCtx drop, hipStream_t st) {
-    dim3 grid((unsigned)(B * H), (unsigned)((T + 63) / 64));
+// The four training passes of RELPOS, one launcher each.  A common grid: one workgroup per (b, h, 64-row tile).
+static dim3 ra_grid(const emo_attn_t& a) { return dim3((unsigned)(a.B * a.H), (unsigned)((a.T + 63) / 64)); }
+struct RelattnFwd {       // zden may be NULL
+template <typename CT, int DH> static int run(const emo_attn_t& a, DropCtx drop, hipStream_t st) {
     const size_t lds = ra_fwd_lds<CT, DH>();
-    if (window > 0 && window + 1 < T) {                        // (a band that holds every key j <= i is the causal kernel)
-        auto kb = relattn_fwd_kernel<CT, DH, true, int64_t>;
-        static bool attr_b = false;
-        if (!attr_b) { (void)hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_b = true; }
-        hipLaunchKernelGGL(kb, grid, dim3(256), lds, st, (const CT*)q, (const CT*)k, (const CT*)v, ld, (const CT*)rd, ld_r, n_dist, ub, vb, (CT*)out, ld_out,
-                           lse, zden, T, H, drop, window);
-        EMO_LAUNCH_CHECK();
-        return EMO_OK;
-    }
-    auto kf = relattn_fwd_kernel<CT, DH, false>;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-    hipLaunchKernelGGL(kf, grid, dim3(256), lds, st, (const CT*)q, (const CT*)k, (const CT*)v, ld, (const CT*)rd, ld_r, n_dist, ub, vb, (CT*)out, ld_out, lse,
-                       zden, T, H, drop);
-    EMO_LAUNCH_CHECK();
-    return EMO_OK;
+    const CT* rd = (const CT*)a.r_dist;
+    if (a.window > 0 && a.window + 1 < a.T)                    // (a band that holds every key j <= i is the causal kernel)
+        return emo_launch<relattn_fwd_kernel<CT, DH, true, int64_t>>(ra_grid(a), dim3(256), lds, st, (const CT*)a.q, (const CT*)a.k, (const CT*)a.v, a.ld, rd, a.ld_r, a.n_dist,
+                                                                     a.r_w_bias, a.r_r_bias, (CT*)a.out, a.ld_out, a.lse, a.zden, a.T, a.H, drop, a.window);
+    return emo_launch<relattn_fwd_kernel<CT, DH, false>>(ra_grid(a), dim3(256), lds, st, (const CT*)a.q, (const CT*)a.k, (const CT*)a.v, a.ld, rd, a.ld_r, a.n_dist, a.r_w_bias,
+                                                         a.r_r_bias, (CT*)a.out, a.ld_out, a.lse, a.zden, a.T, a.H, drop);
 }
+};
+
 
 template <typename CT, int DH> static size_t ra_bwd_lds() {
     typedef SaDims<CT, DH> D;
     return sizeof(CT) * (size_t)(3 * 64 * D::LDX + (sizeof(CT) == 2 ? 0 : DH * D::LDC) + 128 * D::LDX) + sizeof(float) * (4 * 16 * 84 + 64);
 }
-template <typename CT, int DH>
-static int run_relattn_bwd(const void* q, const void* k, const void* v, int64_t ld, const void* rd, int64_t ld_r, int64_t n_dist, const float* ub,
-                           const float* vb, const void* out, const void* dout, int64_t ld_out, const float* lse, const float* zden, void* dq, int64_t ld_d,
-                           void* dq_rel, int64_t ld_rel, float* delta, int64_t B, int64_t T, int64_t H, DropCtx drop, hipStream_t st) {
-    dim3 grid((unsigned)(B * H), (unsigned)((T + 63) / 64));
-    const size_t lds = ra_bwd_lds<CT, DH>();
-    auto kf = relattn_bwd_kernel<CT, DH>;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-    hipLaunchKernelGGL(kf, grid, dim3(256), lds, st, (const CT*)q, (const CT*)k, (const CT*)v, ld, (const CT*)rd, ld_r, n_dist, ub, vb, (const CT*)out,
-                       (const CT*)dout, ld_out, lse, zden, (CT*)dq, ld_d, (CT*)dq_rel, ld_rel, delta, T, H, drop);
-    EMO_LAUNCH_CHECK();
-    return EMO_OK;
+struct RelattnBwd {       // the query-tile pass
+template <typename CT, int DH> static int run(const emo_attn_t& a, DropCtx drop, hipStream_t st) {
+    return emo_launch<relattn_bwd_kernel<CT, DH>>(ra_grid(a), dim3(256), ra_bwd_lds<CT, DH>(), st, (const CT*)a.q, (const CT*)a.k, (const CT*)a.v, a.ld, (const CT*)a.r_dist,
+                                                  a.ld_r, a.n_dist, a.r_w_bias, a.r_r_bias, (const CT*)a.out, (const CT*)a.dout, a.ld_out, (const float*)a.lse,
+                                                  (const float*)a.zden, (CT*)a.dq, a.ld_d, (CT*)a.dq_rel, a.ld_rel, a.delta, a.T, a.H, drop);
 }
+};
+
 
 template <typename CT, int DH> static size_t ra_dr_lds() {
     typedef SaDims<CT, DH> D;
     return sizeof(CT) * (size_t)(CMax<2 * 64 * D::LDX, 64 * (sizeof(CT) == 2 ? 136 : 130)>::v + 3 * 64 * D::LDX + 128 * D::LDX) + sizeof(float) * (4 * 16 * 84);
 }
-template <typename CT, int DH>
-static int run_relattn_dr(const void* qu, const void* qv, int64_t ld_q, const void* k, const void* v, int64_t ld, const void* rd, int64_t ld_r, int64_t n_dist,
-                          const void* dout, int64_t ld_out, const float* lse, const float* zden, const float* delta, float* dR, int64_t ld_dr, float* part,
-                          int64_t B, int64_t T, int64_t H, DropCtx drop, hipStream_t st) {
-    dim3 grid((unsigned)(B * H), (unsigned)((T + 63) / 64));
-    const size_t lds = ra_dr_lds<CT, DH>();
-    auto kf = relattn_bwd_dr_kernel<CT, DH>;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-    hipLaunchKernelGGL(kf, grid, dim3(256), lds, st, (const CT*)qu, (const CT*)qv, ld_q, (const CT*)k, (const CT*)v, ld, (const CT*)rd, ld_r, n_dist,
-                       (const CT*)dout, ld_out, lse, zden, delta, part, T, H, drop);
-    EMO_LAUNCH_CHECK();
-    const int64_t n = T * H * DH;
-    hipLaunchKernelGGL(relattn_dr_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)part, dR, ld_dr, B, T, H, DH);
-    EMO_LAUNCH_CHECK();
-    return EMO_OK;
+struct RelattnDr {        // the distance-window pass: its kernel into the workspace, then the reduce
+template <typename CT, int DH> static int run(const emo_attn_t& a, DropCtx drop, hipStream_t st) {
+    float* part = (float*)a.workspace;
+    EMO_TRY(emo_launch<relattn_bwd_dr_kernel<CT, DH>>(ra_grid(a), dim3(256), ra_dr_lds<CT, DH>(), st, (const CT*)a.qu, (const CT*)a.qv, a.ld_q, (const CT*)a.k, (const CT*)a.v,
+                                                      a.ld, (const CT*)a.r_dist, a.ld_r, a.n_dist, (const CT*)a.dout, a.ld_out, (const float*)a.lse, (const float*)a.zden,
+                                                      (const float*)a.delta, part, a.T, a.H, drop));
+    const int64_t n = a.T * a.H * DH;
+    return emo_launch<relattn_dr_reduce_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)part, a.dR, a.ld_dr, a.B, a.T, a.H, DH);
 }
+};
+
 
 extern "C" int64_t emo_relpos_attn_bwd_r_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t dh) {
     return B * H * ((T + 63) / 64) * 128 * dh * (int64_t)sizeof(float);
@@ -1600,37 +1529,21 @@ template <typename CT, int DH> static size_t ra_dkv_lds() {
     typedef SaDims<CT, DH> D;
     return sizeof(CT) * (size_t)(5 * 64 * D::LDX + 128 * D::LDX + (sizeof(CT) == 2 ? 0 : 2 * DH * D::LDC)) + sizeof(float) * (4 * 16 * 36 + 3 * 64);
 }
-template <typename CT, int DH>
-static int run_relattn_dkv(const void* qu, const void* qv, int64_t ld_q, const void* k, const void* v, int64_t ld, const void* rd, int64_t ld_r, int64_t n_dist,
-                           const void* dout, int64_t ld_out, const float* lse, const float* zden, const float* delta, void* dk, void* dv, int64_t ld_d,
-                           int64_t B, int64_t T, int64_t H, DropCtx drop, hipStream_t st) {
-    dim3 grid((unsigned)(B * H), (unsigned)((T + 63) / 64));
-    const size_t lds = ra_dkv_lds<CT, DH>();
-    auto kf = relattn_bwd_dkv_kernel<CT, DH>;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-    hipLaunchKernelGGL(kf, grid, dim3(256), lds, st, (const CT*)qu, (const CT*)qv, ld_q, (const CT*)k, (const CT*)v, ld, (const CT*)rd, ld_r, n_dist,
-                       (const CT*)dout, ld_out, lse, zden, delta, (CT*)dk, (CT*)dv, ld_d, T, H, drop);
-    EMO_LAUNCH_CHECK();
-    return EMO_OK;
+struct RelattnDkv {       // the key-tile pass
+template <typename CT, int DH> static int run(const emo_attn_t& a, DropCtx drop, hipStream_t st) {
+    return emo_launch<relattn_bwd_dkv_kernel<CT, DH>>(ra_grid(a), dim3(256), ra_dkv_lds<CT, DH>(), st, (const CT*)a.qu, (const CT*)a.qv, a.ld_q, (const CT*)a.k, (const CT*)a.v,
+                                                      a.ld, (const CT*)a.r_dist, a.ld_r, a.n_dist, (const CT*)a.dout, a.ld_out, (const float*)a.lse, (const float*)a.zden,
+                                                      (const float*)a.delta, (CT*)a.dk, (CT*)a.dv, a.ld_d, a.T, a.H, drop);
 }
+};
 
 static int relpos_decode(const emo_attn_t& a, hipStream_t st);   // (at the end of this file, where its kernel instances have always been named)
 
 // The RELPOS kind of emo_attn: its four training passes, in the order of the kernels above
 static int attn_relpos(const emo_attn_t& a, hipStream_t st) {
     if (a.pass == EMO_ATTN_DECODE) return relpos_decode(a, st);
-    const bool bf = a.dtype == EMO_BF16;
-    const int64_t ve = bf ? 8 : 4;
+    const int64_t ve = a.dtype == EMO_BF16 ? 8 : 4;
     const DropCtx drop = make_drop(a.p_drop, a.seed, a.offset);
-#define RA_RUN(run, ...)                                                                                  \
-    do {                                                                                                  \
-        if (a.dh == 64) return bf ? run<bf16_t, 64>(__VA_ARGS__, a.B, a.T, a.H, drop, st) : run<float, 64>(__VA_ARGS__, a.B, a.T, a.H, drop, st); \
-        if (a.dh == 32) return bf ? run<bf16_t, 32>(__VA_ARGS__, a.B, a.T, a.H, drop, st) : run<float, 32>(__VA_ARGS__, a.B, a.T, a.H, drop, st); \
-        if (a.dh == 16) return bf ? run<bf16_t, 16>(__VA_ARGS__, a.B, a.T, a.H, drop, st) : run<float, 16>(__VA_ARGS__, a.B, a.T, a.H, drop, st); \
-        emo_set_error("unsupported d_head=%lld (built: 16, 32, 64)", (long long)a.dh);                    \
-        return EMO_ERR_UNSUPPORTED;                                                                       \
-    } while (0)
     EMO_CHECK(a.r_dist && a.lse, "null pointer");
     EMO_CHECK(a.ld_r % ve == 0 && ((uintptr_t)a.r_dist & 15) == 0, "r_dist must keep rows 16-B aligned");
     if (a.pass == EMO_ATTN_FWD && a.window > 0) {              // a query sees distances 0 .. window only
@@ -1642,14 +1555,13 @@ static int attn_relpos(const emo_attn_t& a, hipStream_t st) {
     if (a.pass == EMO_ATTN_FWD) {
         EMO_CHECK(a.r_w_bias && a.r_r_bias && a.out, "null pointer");
         EMO_CHECK(((uintptr_t)a.out & 15) == 0, "out must be 16-B aligned");
-        RA_RUN(run_relattn, a.q, a.k, a.v, a.ld, a.r_dist, a.ld_r, a.n_dist, a.r_w_bias, a.r_r_bias, a.out, a.ld_out, a.lse, a.zden, a.window);
+        return attn_by_dtype_dh<RelattnFwd>(a, drop, st);
     }
     if (a.pass == EMO_ATTN_BWD) {
         EMO_CHECK(a.r_w_bias && a.r_r_bias && a.out && a.dout && a.zden && a.dq && a.dq_rel, "null pointer");
         EMO_CHECK(a.ld_d % 4 == 0 && a.ld_rel % 4 == 0 && (((uintptr_t)a.dq | (uintptr_t)a.dq_rel | (uintptr_t)a.out | (uintptr_t)a.dout) & 15) == 0,
                   "pointers must be 16-B aligned with ld_d %% 4 == 0 and ld_rel %% 4 == 0");
-        RA_RUN(run_relattn_bwd, a.q, a.k, a.v, a.ld, a.r_dist, a.ld_r, a.n_dist, a.r_w_bias, a.r_r_bias, a.out, a.dout, a.ld_out, a.lse, a.zden, a.dq, a.ld_d,
-               a.dq_rel, a.ld_rel, a.delta);
+        return attn_by_dtype_dh<RelattnBwd>(a, drop, st);
     }
     // the distance-window and the key-tile pass: the biased query copies in the place of q
     EMO_CHECK(a.qv && a.dout && a.zden && a.delta, "null pointer");
@@ -1658,13 +1570,11 @@ static int attn_relpos(const emo_attn_t& a, hipStream_t st) {
         EMO_CHECK(a.dR && a.workspace && ((uintptr_t)a.workspace & 15) == 0, "dR / workspace: null pointer or not 16-B aligned");
         EMO_CHECK(a.ld_dr >= a.H * a.dh, "dR needs a column for every (h, d)");
         EMO_CHECK(a.workspace_bytes >= emo_relpos_attn_bwd_r_workspace_bytes(a.B, a.T, a.H, a.dh), "workspace too small (emo_relpos_attn_bwd_r_workspace_bytes)");
-        RA_RUN(run_relattn_dr, a.qu, a.qv, a.ld_q, a.k, a.v, a.ld, a.r_dist, a.ld_r, a.n_dist, a.dout, a.ld_out, a.lse, a.zden, a.delta, a.dR, a.ld_dr,
-               (float*)a.workspace);
+        return attn_by_dtype_dh<RelattnDr>(a, drop, st);
     }
     EMO_CHECK(a.dk && a.dv, "null pointer");
     EMO_CHECK(a.ld_d % 4 == 0 && (((uintptr_t)a.dk | (uintptr_t)a.dv) & 15) == 0, "dk / dv must be 16-B aligned with ld_d %% 4 == 0");
-    RA_RUN(run_relattn_dkv, a.qu, a.qv, a.ld_q, a.k, a.v, a.ld, a.r_dist, a.ld_r, a.n_dist, a.dout, a.ld_out, a.lse, a.zden, a.delta, a.dk, a.dv, a.ld_d);
-#undef RA_RUN
+    return attn_by_dtype_dh<RelattnDkv>(a, drop, st);
 }
 
 // ----------------------------------------------------------------------------------------------- emo_attn: one entry for the three attention kinds
@@ -1710,6 +1620,13 @@ extern "C" int emo_attn(const emo_attn_t* args, emo_stream_t stream) {
 }
 
 // The DECODE pass of the RELPOS kind: one query row per stream against the KV caches, keys len-1-window .. len-1
+struct RelattnDecode {
+    template <typename CT> static int run(const emo_attn_t& a, hipStream_t st) {
+        return emo_launch_lds<relattn_decode_kernel<CT>>(dim3((unsigned)(a.B * a.H)), dim3(256), 128 * 1024, (size_t)a.T_max * sizeof(float), st, (const CT*)a.q, a.ld,
+                                                         (CT*)a.kcache, (CT*)a.vcache, a.T_max, a.lens, a.lens_off, a.window, (const CT*)a.k, (const CT*)a.v, a.ld,
+                                                         (const CT*)a.r_dist, a.ld_r, a.r_w_bias, a.r_r_bias, (CT*)a.out, a.ld_out, a.H, (int)a.dh);
+    }
+};
 static int relpos_decode(const emo_attn_t& a, hipStream_t st) {
     EMO_CHECK(a.q && a.kcache && a.vcache && a.lens && a.out && a.r_dist && a.r_w_bias && a.r_r_bias, "null pointer");
     EMO_CHECK(a.dh == 16 || a.dh == 32 || a.dh == 64 || a.dh == 128, "d_head must be 16, 32, 64 or 128");
@@ -1719,21 +1636,5 @@ static int relpos_decode(const emo_attn_t& a, hipStream_t st) {
     const int64_t ve = a.dtype == EMO_BF16 ? 8 : 4;
     EMO_CHECK((((uintptr_t)a.kcache | (uintptr_t)a.vcache | (uintptr_t)a.r_dist) & 15) == 0 && (a.H * a.dh) % ve == 0 && a.ld_r % ve == 0,
               "caches / r_dist must be 16-B aligned");
-    dim3 grid((unsigned)(a.B * a.H));
-    const size_t lds = (size_t)a.T_max * sizeof(float);
-    if (a.dtype == EMO_F32) {
-        static bool set = false;
-        if (!set) { (void)hipFuncSetAttribute((const void*)relattn_decode_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); set = true; }
-        hipLaunchKernelGGL(relattn_decode_kernel<float>, grid, dim3(256), lds, st, (const float*)a.q, a.ld, (float*)a.kcache, (float*)a.vcache, a.T_max, a.lens,
-                           a.lens_off, a.window, (const float*)a.k, (const float*)a.v, a.ld, (const float*)a.r_dist, a.ld_r, a.r_w_bias, a.r_r_bias,
-                           (float*)a.out, a.ld_out, a.H, (int)a.dh);
-    } else {
-        static bool set = false;
-        if (!set) { (void)hipFuncSetAttribute((const void*)relattn_decode_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); set = true; }
-        hipLaunchKernelGGL(relattn_decode_kernel<bf16_t>, grid, dim3(256), lds, st, (const bf16_t*)a.q, a.ld, (bf16_t*)a.kcache, (bf16_t*)a.vcache, a.T_max, a.lens,
-                           a.lens_off, a.window, (const bf16_t*)a.k, (const bf16_t*)a.v, a.ld, (const bf16_t*)a.r_dist, a.ld_r, a.r_w_bias, a.r_r_bias,
-                           (bf16_t*)a.out, a.ld_out, a.H, (int)a.dh);
-    }
-    EMO_LAUNCH_CHECK();
-    return EMO_OK;
+    return attn_by_dtype<RelattnDecode>(a, st);
 }

@@ -14,6 +14,8 @@
 // (seed, offset, ((b H + h) T + t) T + j) with one keyed hash per 4 consecutive keys, lse = m ln 2 + ln(l).
 #include "emo_common.h"
 
+#include "emo_attn_host.h"
+
 namespace {
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 constexpr float A32_LOG2E = 1.4426950408889634f, A32_LN2 = 0.6931471805599453f;
@@ -496,81 +498,46 @@ __global__ __launch_bounds__(256, 2) void sattn32_dkv_kernel(const bf16_t* __res
 }
 }  // namespace
 
-// which: 0 forward.  Returns false when the call is not covered (the caller then runs the generic kernels).
-// bytes of the keep words of one attention call (0: the 32 x 32 kernels do not serve the shape, or dropout is off)
+// =============================================================================================== host (emo_attn_host.h)
 int64_t emo_sattn32_keep_bytes(int64_t B, int64_t T, int64_t H, int64_t dh, float p_drop) {
-    const char* e = getenv("EMO_SATTN32");
-    if (e && atoi(e) == 0) return 0;
-    const char* e2 = getenv("EMO_SATTN32_BWD");
-    if (e2 && atoi(e2) == 0) return 0;
-    const char* e3 = getenv("EMO_SATTN_KEEP");               // "0": every pass re-evaluates the hash
-    if (e3 && atoi(e3) == 0) return 0;
+    // EMO_SATTN_KEEP=0: every pass re-evaluates the hash
+    if (env_off("EMO_SATTN32") || env_off("EMO_SATTN32_BWD") || env_off("EMO_SATTN_KEEP")) return 0;
     if (dh != 64 || T < 128 || (T % 128) != 0 || !(p_drop > 0.f)) return 0;
     return B * H * (T / 64) * 2 * T * (int64_t)sizeof(uint32_t);
 }
 
-bool emo_sattn32_try(int which, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld, bf16_t* out, int64_t ld_out, float* lse, int64_t B, int64_t T,
-                     int64_t H, DropCtx drop, uint32_t* keep, hipStream_t st) {
-    const char* e = getenv("EMO_SATTN32");                   // "0": generic kernels only (read per call: tests toggle it)
-    if (e && atoi(e) == 0) return false;
-    if (which != 0 || T < 128 || (T % 128) != 0 || (ld & 7) || (ld_out & 3)) return false;
-    // 16-B LDS-DMA pieces and bf16x8 row accesses: an unaligned view (a C-ABI caller's column-offset slice) falls back to the generic kernels
-    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) || ((uintptr_t)lse & 3)) return false;
-    dim3 grid((unsigned)(B * H), (unsigned)(T / 128));
-    const size_t lds = 4 * A32_TILEB;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)sattn32_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)sattn32_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
-    if (keep && drop.thr16) hipLaunchKernelGGL(sattn32_fwd_kernel<true>, grid, dim3(256), lds, st, q, k, v, ld, out, ld_out, lse, T, H, drop, keep);
-    else hipLaunchKernelGGL(sattn32_fwd_kernel<false>, grid, dim3(256), lds, st, q, k, v, ld, out, ld_out, lse, T, H, drop, (uint32_t*)nullptr);
-    return true;
+// what the three passes share: the shape these kernels serve, 16-B LDS-DMA pieces and bf16x8 row accesses of q / k / v (an unaligned view, a C-ABI
+// caller's column-offset slice, falls back to the generic kernels), and the keep words, which count only with dropout on
+static bool a32_covers(const emo_attn_t& a) {
+    return a.T >= 128 && (a.T % 128) == 0 && !(a.ld & 7) && !(((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) & 15);
+}
+template <auto WithKeep, auto Without, typename... Args>
+static int a32_launch(const emo_attn_t& a, size_t lds, DropCtx drop, hipStream_t st, Args... args) {
+    const dim3 grid((unsigned)(a.B * a.H), (unsigned)(a.T / 128));
+    const bf16_t *q = (const bf16_t*)a.q, *k = (const bf16_t*)a.k, *v = (const bf16_t*)a.v;
+    const int rc = a.keep && drop.thr16 ? emo_launch<WithKeep>(grid, dim3(256), lds, st, q, k, v, a.ld, args..., a.T, a.H, drop, (uint32_t*)a.keep)
+                                        : emo_launch<Without>(grid, dim3(256), lds, st, q, k, v, a.ld, args..., a.T, a.H, drop, (uint32_t*)nullptr);
+    return rc ? rc : 1;
 }
 
-// dQ pass of the backward (writes delta for the dK / dV pass); false: not covered, the caller runs the generic kernel
-bool emo_sattn32_dq_try(const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld, const bf16_t* out, const bf16_t* dout, int64_t ld_out, const float* lse,
-                        float* delta, bf16_t* dq, int64_t ld_d, int64_t B, int64_t T, int64_t H, DropCtx drop, const uint32_t* keep, hipStream_t st) {
-    const char* e = getenv("EMO_SATTN32");
-    if (e && atoi(e) == 0) return false;
-    const char* e2 = getenv("EMO_SATTN32_BWD");
-    if (e2 && atoi(e2) == 0) return false;
-    const char* e3 = getenv("EMO_SATTN32_DQ");                // "0": generic dQ kernel
-    if (e3 && atoi(e3) == 0) return false;
-    if (T < 128 || (T % 128) != 0 || (ld & 7) || (ld_out & 7) || (ld_d & 3) || !delta) return false;
-    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)dout | (uintptr_t)dq) & 15) return false;
-    dim3 grid((unsigned)(B * H), (unsigned)(T / 128));
-    const size_t lds = 4 * A32_TILEB;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)sattn32_dq_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)sattn32_dq_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
-    if (keep && drop.thr16) hipLaunchKernelGGL(sattn32_dq_kernel<true>, grid, dim3(256), lds, st, q, k, v, ld, out, dout, ld_out, lse, delta, dq, ld_d, T, H, drop, keep);
-    else hipLaunchKernelGGL(sattn32_dq_kernel<false>, grid, dim3(256), lds, st, q, k, v, ld, out, dout, ld_out, lse, delta, dq, ld_d, T, H, drop, (const uint32_t*)nullptr);
-    return true;
+int emo_sattn32_fwd_try(const emo_attn_t& a, DropCtx drop, hipStream_t st) {
+    if (env_off("EMO_SATTN32")) return 0;                    // generic kernels only
+    if (!a32_covers(a) || (a.ld_out & 3) || ((uintptr_t)a.out & 15) || ((uintptr_t)a.lse & 3)) return 0;
+    return a32_launch<sattn32_fwd_kernel<true>, sattn32_fwd_kernel<false>>(a, 4 * A32_TILEB, drop, st, (bf16_t*)a.out, a.ld_out, a.lse);
 }
 
-// dK / dV pass of the backward (after the dQ pass has written delta); false: not covered, the caller runs the generic kernel
-bool emo_sattn32_dkv_try(const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld, const bf16_t* dout, int64_t ld_out, const float* lse, const float* delta,
-                         bf16_t* dk, bf16_t* dv, int64_t ld_d, int64_t B, int64_t T, int64_t H, DropCtx drop, const uint32_t* keep, hipStream_t st) {
-    const char* e = getenv("EMO_SATTN32");
-    if (e && atoi(e) == 0) return false;
-    const char* e2 = getenv("EMO_SATTN32_BWD");
-    if (e2 && atoi(e2) == 0) return false;
-    if (T < 128 || (T % 128) != 0 || (ld & 7) || (ld_out & 7) || (ld_d & 3) || !delta) return false;
-    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dout | (uintptr_t)dk | (uintptr_t)dv) & 15) return false;
-    dim3 grid((unsigned)(B * H), (unsigned)(T / 128));
-    const size_t lds = 2 * A32_QSLOT;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)sattn32_dkv_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)sattn32_dkv_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
-    if (keep && drop.thr16) hipLaunchKernelGGL(sattn32_dkv_kernel<true>, grid, dim3(256), lds, st, q, k, v, ld, dout, ld_out, lse, delta, dk, dv, ld_d, T, H, drop, keep);
-    else hipLaunchKernelGGL(sattn32_dkv_kernel<false>, grid, dim3(256), lds, st, q, k, v, ld, dout, ld_out, lse, delta, dk, dv, ld_d, T, H, drop, (const uint32_t*)nullptr);
-    return true;
+// dQ pass of the backward (writes delta_ws for the dK / dV pass)
+int emo_sattn32_dq_try(const emo_attn_t& a, DropCtx drop, hipStream_t st) {
+    if (env_off("EMO_SATTN32") || env_off("EMO_SATTN32_BWD") || env_off("EMO_SATTN32_DQ")) return 0;   // EMO_SATTN32_DQ=0: generic dQ kernel
+    if (!a32_covers(a) || (a.ld_out & 7) || (a.ld_d & 3) || !a.delta_ws || (((uintptr_t)a.out | (uintptr_t)a.dout | (uintptr_t)a.dq) & 15)) return 0;
+    return a32_launch<sattn32_dq_kernel<true>, sattn32_dq_kernel<false>>(a, 4 * A32_TILEB, drop, st, (const bf16_t*)a.out, (const bf16_t*)a.dout, a.ld_out,
+                                                                         (const float*)a.lse, a.delta_ws, (bf16_t*)a.dq, a.ld_d);
+}
+
+// dK / dV pass of the backward (after the dQ pass has written delta_ws)
+int emo_sattn32_dkv_try(const emo_attn_t& a, DropCtx drop, hipStream_t st) {
+    if (env_off("EMO_SATTN32") || env_off("EMO_SATTN32_BWD")) return 0;
+    if (!a32_covers(a) || (a.ld_out & 7) || (a.ld_d & 3) || !a.delta_ws || (((uintptr_t)a.dout | (uintptr_t)a.dk | (uintptr_t)a.dv) & 15)) return 0;
+    return a32_launch<sattn32_dkv_kernel<true>, sattn32_dkv_kernel<false>>(a, 2 * A32_QSLOT, drop, st, (const bf16_t*)a.dout, a.ld_out, (const float*)a.lse,
+                                                                           (const float*)a.delta_ws, (bf16_t*)a.dk, (bf16_t*)a.dv, a.ld_d);
 }

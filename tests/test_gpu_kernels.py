@@ -955,6 +955,113 @@ def test_decode_pass_ignores_foreign_fields(dt, kind, dh, opt, monkeypatch):
     assert torch.isnan(scratch).all()
 
 
+# the fields of emo_attn_t that each training pass reads, from the field comments of emo_hip.h.  `window` counts everywhere (the entry refuses W > 0
+# outside [relpos, fwd]); the key-tile and distance-window passes of RELPOS take qu, qv and read no q
+_TRAIN_SHARED = {'kind', 'pass_', 'q', 'k', 'v', 'ld', 'dtype', 'B', 'T', 'H', 'dh', 'window'}
+_TRAIN_DROP = {'p_drop', 'seed', 'offset'}
+_FAVOR_OWN = _TRAIN_SHARED | {'out', 'ld_out', 'omega', 'den', 'n_feat', 'eps', 'workspace', 'workspace_bytes'}
+_SOFTMAX_OWN = _TRAIN_SHARED | _TRAIN_DROP | {'out', 'ld_out', 'lse', 'keep', 'keep_bytes'}
+_RELPOS_OWN = (_TRAIN_SHARED | _TRAIN_DROP | {'r_dist', 'ld_r', 'n_dist', 'lse', 'zden'})
+_RELPOS_BACK = (_RELPOS_OWN - {'q'}) | {'qu', 'qv', 'ld_q', 'dout', 'ld_out', 'delta'}
+_TRAIN_OWN = {('favor', 'fwd'): _FAVOR_OWN | {'state_S', 'state_z'},
+              ('favor', 'bwd'): _FAVOR_OWN | {'dout', 'dq', 'dk', 'dv', 'ld_d', 'kstate_valid', 'dout_is_dn'},
+              ('softmax', 'fwd'): _SOFTMAX_OWN,
+              ('softmax', 'bwd'): _SOFTMAX_OWN | {'dout', 'delta_ws', 'dq', 'dk', 'dv', 'ld_d'},
+              ('relpos', 'fwd'): _RELPOS_OWN | {'r_w_bias', 'r_r_bias', 'out', 'ld_out'},
+              ('relpos', 'bwd'): _RELPOS_OWN | {'r_w_bias', 'r_r_bias', 'out', 'dout', 'ld_out', 'dq', 'ld_d', 'dq_rel', 'ld_rel', 'delta'},
+              ('relpos', 'bwd_kv'): _RELPOS_BACK | {'dk', 'dv', 'ld_d'},
+              ('relpos', 'bwd_r'): _RELPOS_BACK | {'dR', 'ld_dr', 'workspace', 'workspace_bytes'}}
+_FAVOR_DN_DROPS = {'den', 'workspace', 'workspace_bytes', 'kstate_valid'}      # FAVOR BWD with dout_is_dn reads none of these
+# (no field is read against the header's word: the list of exceptions is empty)
+
+
+@pytest.mark.parametrize('case', ['favor-slice', 'favor-generic-bf16', 'favor-segments', 'favor-dn', 'favor-generic-f32', 'softmax-32x32', 'softmax-generic',
+                                  'relpos-f32', 'relpos-bf16'])
+def test_training_passes_ignore_foreign_fields(case, monkeypatch):
+    """Every training pass of emo_attn, run twice on the same inputs: on the block ops builds, and on that block with every field the (kind, pass)
+    does not read set to a non-NULL address (a NaN-filled scratch tensor, larger than anything a pass writes) or a non-zero value.  Outputs must
+    be bit-identical and the scratch untouched.  The cases are the smallest that reach each launcher: the FAVOR slice kernels (EMO_FAVOR_FS=2)
+    and the generic ones on the same bf16 problem, the segmented scan (workspace, kstate_valid 0 and 1, the state-only passes), the dout_is_dn
+    backward, the generic fp32 instances; SOFTMAX on the 32 x 32 kernels with keep words and on the generic kernels; the four RELPOS passes
+    (FWD with window 0 and 8) on one full and one partial 64-row tile."""
+    ops = _ops()
+    from emo_disentanger_amd import _lib
+    from oracle.weights import orthogonal_omega
+    scratch = torch.full((1 << 18,), float('nan'), device='cuda')
+    kinds, passes = ('favor', 'softmax', 'relpos'), ('fwd', 'bwd', 'bwd_kv', 'bwd_r')
+    blocks = []
+
+    def block_with_foreign_fields(**fields):
+        a = _lib.Attn(**fields)
+        own = _TRAIN_OWN[kinds[a.kind], passes[a.pass_]]
+        if a.dout_is_dn and (kinds[a.kind], passes[a.pass_]) == ('favor', 'bwd'):
+            own = own - _FAVOR_DN_DROPS
+        for name, ctype in _lib.Attn._fields_:
+            if name not in own:
+                setattr(a, name, scratch.data_ptr() if ctype is _lib.c_p else 3)
+        blocks.append((kinds[a.kind], passes[a.pass_]))
+        return a
+
+    B, H = 1, 2
+    if case.startswith('favor'):
+        dt, dh, nf, T = (torch.float32, 32, 64, 40) if case == 'favor-generic-f32' else (torch.bfloat16, 64, 128, 256 if case == 'favor-segments' else 64)
+        monkeypatch.setenv('EMO_FAVOR_SEGMENTS', '2' if case == 'favor-segments' else '1')
+        if case in ('favor-slice', 'favor-generic-bf16'):
+            monkeypatch.setenv('EMO_FAVOR_FS', '2' if case == 'favor-slice' else '0')
+        HD = H * dh
+        om = orthogonal_omega(dh, nf, np.random.default_rng(6)).cuda()
+        qkv = _r(B * T, 3 * HD, seed=21, dt=dt, scale=0.7).cuda()
+        q, k, v = qkv[:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:]
+        dout = _r(B * T, HD, seed=22, dt=dt).cuda()
+        assert (ops.lib.emo_favor_attn_workspace_bytes(B, T, H, dh, nf) > 0) == (case == 'favor-segments')
+        n_calls = 4 if case == 'favor-segments' else 2
+
+        def run():
+            out, den, S, z = ops.favor_attn_fwd(q, k, v, om, B, T, H, want_state=True)
+            if case == 'favor-dn':
+                assert ops.favor_bwd_dn_ok(dt, B, T, H, dh, nf)
+                return (out, den, S, z) + tuple(g.clone() for g in ops.favor_attn_bwd(q, k, v, om, out, dout, den, B, T, H, dn=True))
+            res = (out, den, S, z) + tuple(g.clone() for g in ops.favor_attn_bwd(q, k, v, om, out, dout, den, B, T, H))
+            if case == 'favor-segments':                         # kstate_valid = 1: the backward on the forward's own workspace
+                out2, den2, ws = ops.favor_attn_fwd(q, k, v, om, B, T, H, keep_ws=True)
+                res += (out2, den2) + tuple(g.clone() for g in ops.favor_attn_bwd(q, k, v, om, out2, dout, den2, B, T, H, ws_saved=ws))
+            return res
+    elif case.startswith('softmax'):
+        dt, dh, T = (torch.bfloat16, 64, 128) if case == 'softmax-32x32' else (torch.float32, 32, 40)
+        HD = H * dh
+        qkv = _r(B * T, 3 * HD, seed=23, dt=dt).cuda()
+        q, k, v = qkv[:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:]
+        dout = _r(B * T, HD, seed=24, dt=dt).cuda()
+        n_calls = 2
+
+        def run():
+            out, lse, keep = ops.softmax_attn_fwd(q, k, v, B, T, H, p_drop=0.1, seed=3, offset=9, want_keep=True)
+            assert (keep is not None) == (case == 'softmax-32x32')
+            return (out, lse) + tuple(g.clone() for g in ops.softmax_attn_bwd(q, k, v, out, dout, lse, B, T, H, p_drop=0.1, seed=3, offset=9, keep=keep))
+    else:
+        dt, dh, T = torch.float32 if case == 'relpos-f32' else torch.bfloat16, 32, 70
+        HD = H * dh
+        qkv = _r(B * T, 3 * HD, seed=25, dt=dt, scale=0.7).cuda()
+        q, k, v = qkv[:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:]
+        R, u, vb = _r(T, HD, seed=26, dt=dt, scale=0.7).cuda(), _r(H, dh, seed=27, scale=0.3).cuda(), _r(H, dh, seed=28, scale=0.3).cuda()
+        dout = _r(B * T, HD, seed=29, dt=dt).cuda()
+        n_calls = 5
+
+        def run():
+            band = ops.relpos_attn_fwd(q, k, v, R, u, vb, B, T, H, window=8)
+            out, lse, zden = ops.relpos_attn_fwd(q, k, v, R, u, vb, B, T, H, p_drop=0.1, seed=3, offset=9)
+            return band + (out, lse, zden) + ops.relpos_attn_bwd(qkv, R, u, vb, out, dout, lse, zden, B, T, H, p_drop=0.1, seed=3, offset=9)
+
+    plain = run()
+    monkeypatch.setattr(ops, 'Attn', block_with_foreign_fields)
+    loaded = run()
+    assert len(blocks) == n_calls and len(plain) == len(loaded)
+    assert all(torch.isfinite(t).all() for t in plain)
+    for a, b in zip(plain, loaded):
+        assert torch.equal(a, b)
+    assert torch.isnan(scratch).all()
+
+
 @pytest.mark.parametrize('B,T,H,p', [(2, 256, 2, 0.0), (1, 128, 1, 0.0), (1, 640, 3, 0.0), (2, 384, 2, 0.2)])
 def test_softmax_attention_32x32_kernels_vs_reference_and_generic(B, T, H, p, monkeypatch):
     """bf16 / d_head 64 / T % 128 == 0 runs on the 32 x 32 x 16 kernels (emo_softmax_attn32.hip): against the fp64 reference (p = 0) and against
