@@ -80,6 +80,7 @@ _SIG = {
     'emo_device_cus': (c_i, []),
     'emo_gemm': (c_i, [c_p, c_i, c_l, c_p, c_i, c_l, c_p, c_l, c_l, c_l, c_l, c_i, c_i, c_i, ctypes.POINTER(Epilogue), c_p]),
     'emo_gemm_last_kernel': (c_i, []),
+    'emo_gemm_last_plan': (c_i, []),
     'emo_epilogue_size': (c_i, []),
     'emo_gemm_workspace_bytes': (c_l, [c_l, c_l, c_l, c_i, c_i]),
     'emo_ffn_fwd_supported': (c_i, [c_i, c_l, c_l, c_l]),

@@ -946,6 +946,7 @@ static void dispatch_glds(bool akc, bool bkc, dim3 grid, hipStream_t st, const b
     // long reduction (K=2048) the double buffer of full 128-B lines is best (842 vs 796); for MN-contiguous B (dgrad)
     // the 2-stage ring of 32-deep tiles (32 KB, 4 blocks per CU) is best (in-step A/B of the other geometries: DESIGN.md §4.1).
     const bool can64 = (kps % 64) == 0 && (K % 64) == 0;
+    const int nsplit = kps < K ? (int)cdiv64(K, kps) : 0;            // (emo_gemm_last_plan: the split count of this launch)
     // Small grids (at most two tiles per CU: the reference YAML's batch size 4, stage 1): occupancy has nothing to offer, a block is alone on
     // its CU and every K step exposed an L2 / HBM round trip -> the 4-stage ring of 32-deep tiles (three tiles in flight inside the block)
     static const bool small_off = getenv("EMO_GEMM_SMALLGRID") != nullptr && atoi(getenv("EMO_GEMM_SMALLGRID")) == 0;
@@ -955,13 +956,14 @@ static void dispatch_glds(bool akc, bool bkc, dim3 grid, hipStream_t st, const b
         // the bytes one block keeps in flight (r04, same box, two pairs: stage 1 262 / 266 -> 284 / 283 k tokens/s, batch-size-4 steps unchanged);
         // EMO_GEMM_SMALL64=0: the 32-deep ring
         static const bool small64 = !(getenv("EMO_GEMM_SMALL64") != nullptr && atoi(getenv("EMO_GEMM_SMALL64")) == 0);
-        if (small64 && can64 && kps >= 512) { dispatch_glds2<OutT, 64, 4>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, kps, ep); return; }
+        if (small64 && can64 && kps >= 512) { emo_gemm_note_plan(64, 4, nsplit, 0); dispatch_glds2<OutT, 64, 4>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, kps, ep); return; }
+        emo_gemm_note_plan(32, 4, nsplit, 0);
         dispatch_glds2<OutT, 32, 4>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, kps, ep);
         return;
     }
-    if (bkc && K > 1024 && can64) dispatch_glds2<OutT, 64, 2>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, kps, ep);
-    else if (bkc) dispatch_glds2<OutT, 32, 3>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, kps, ep);
-    else dispatch_glds2<OutT, 32, 2>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, kps, ep);
+    if (bkc && K > 1024 && can64) { emo_gemm_note_plan(64, 2, nsplit, 0); dispatch_glds2<OutT, 64, 2>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, kps, ep); }
+    else if (bkc) { emo_gemm_note_plan(32, 3, nsplit, 0); dispatch_glds2<OutT, 32, 3>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, kps, ep); }
+    else { emo_gemm_note_plan(32, 2, nsplit, 0); dispatch_glds2<OutT, 32, 2>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, kps, ep); }
 }
 
 static int g_gemm_variant = -1;   // EMO_GEMM_VARIANT: 1 = register-staged v1, 2 = LDS-DMA ring for k-contiguous A, 3 = also for the TN (wgrad) layout; unset = per call
@@ -1128,6 +1130,10 @@ static int64_t choose_splits(int64_t M, int64_t N, int64_t K, bool big, bool has
 static thread_local int g_last_gemm_kernel = 0;
 extern "C" int emo_epilogue_size(void) { return (int)sizeof(emo_epilogue_t); }
 extern "C" int emo_gemm_last_kernel(void) { return g_last_gemm_kernel; }
+// what ran inside that family (emo_hip.h: emo_gemm_last_plan): BK | stages << 8 | splits << 16 | A-stationary column split << 24
+static thread_local int g_last_gemm_plan = 0;
+void emo_gemm_note_plan(int bk, int stages, int splits, int col_split) { g_last_gemm_plan = bk | stages << 8 | splits << 16 | col_split << 24; }
+extern "C" int emo_gemm_last_plan(void) { return g_last_gemm_plan; }
 
 // fp32 products: tile edge of the kernel that serves the shape (a pure function of the shape: the split-K plan and the workspace size follow it).
 // EMO_GEMM_F32_TILE=64 keeps every shape on the 64 x 64 kernel (A/B, tests).
@@ -1239,6 +1245,7 @@ extern "C" int emo_gemm(const void* A, int a_trans, int64_t lda, const void* B, 
 #undef SKINNY_LAUNCH
         EMO_LAUNCH_CHECK();
         g_last_gemm_kernel = 1;
+        emo_gemm_note_plan(nw >= 16 ? 64 : 128, nw, 0, 0);                 // (chunk width, waves)
         return EMO_OK;
     }
 #ifdef EMO_EXPERIMENTAL
@@ -1319,6 +1326,7 @@ extern "C" int emo_gemm(const void* A, int a_trans, int64_t lda, const void* B, 
     if (splits > 1)   // see splitk_coords()
         grid.x = ep.atomic > 1 ? (unsigned)(8 * cdiv64(tiles_m * tiles_n, ep.atomic)) : (unsigned)(tiles_m * tiles_n * (cdiv64(splits, 8) * 8));
     g_last_gemm_kernel = (dtype_in == EMO_F32 ? 7 : 6) + (use_ws ? (epi_split ? 32 : 16) : 0);
+    emo_gemm_note_plan(dtype_in == EMO_F32 ? 16 : GB_K, 0, splits > 1 ? (int)splits : 0, 0);      // (dispatch_glds overwrites BK / stages with its ring)
     if (dtype_in == EMO_F32) {
         const float* a = (const float*)A;
         const float* b = (const float*)B;

@@ -701,5 +701,6 @@ bool emo_gemm_astat_try(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t l
     else if (fl == AF_GELUAUX) AS_LAUNCH(bf16_t, AF_GELUAUX);
     else AS_LAUNCH(bf16_t, AF_GENERIC);
 #undef AS_LAUNCH
+    emo_gemm_note_plan(AS_KS, 4, 0, split);
     return true;
 }

@@ -217,6 +217,8 @@ __device__ __forceinline__ void epi_row8(const EpiParams& ep, OutT* __restrict__
 }
 
 
+// plan of the launch being queued, for emo_gemm_last_plan() (emo_hip.h; defined in emo_gemm.hip): zero = the family has no such field
+void emo_gemm_note_plan(int bk, int stages, int splits, int col_split);
 // A-stationary K = 512 kernel (emo_gemm_astat.hip): true when the shape / epilogue is eligible and the launch was queued.
 bool emo_gemm_astat_try(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, int dtype_out, int64_t M, int64_t N, int64_t K,
                         const EpiParams& ep, hipStream_t st);

@@ -467,6 +467,7 @@ bool emo_gemm_w128_try(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ld
     static bool attr = false;
     if (!attr) { (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS); attr = true; }
     hipLaunchKernelGGL(k, grid, dim3(256), W_LDS, st, A, lda, B, ldb, (bf16_t*)C, M, N, K, ep2);
+    emo_gemm_note_plan(W_BK, W_NA, 0, 0);
     return true;
 }
 
@@ -544,5 +545,6 @@ bool emo_gemm_w128_tn_try(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t
                                     (int)(splits0 * (a_rowsum ? N / W_BN : M / W_BM)), a_rowsum ? a_rowsum : b_rowsum, st);
     else
         emo_splitk_reduce_launch((const float*)ws, M * N, (int)splits0, C, (M * N) >> 2, accumulate, st);
+    emo_gemm_note_plan(W_BK, W_NA, (int)splits0, 0);
     return true;
 }

@@ -115,6 +115,12 @@ typedef struct {
 /* diagnostics: kernel family of the calling thread's last emo_gemm (1 skinny, 2 A-stationary K = 512, 3 / 4 256 x 256 tile wgrad / NT,
  * 5 / 6 128 x 128 LDS-DMA / register-staged, 7 exact-fp32, 8 persistent 256 x 256 tile walk (EMO_GEMM_P256=1), 9 128 x 512 tile (EMO_GEMM_Q512=1); + 16 split-K via the workspace, + 32 with the reduce-and-epilogue pass) */
 int emo_gemm_last_kernel(void);
+/* diagnostics: what ran inside that family, for the calling thread's last emo_gemm:
+ *   BK | stages << 8 | splits << 16 | astat_column_split << 24        (a zero field = the family has none)
+ * BK: depth of one K step (LDS-DMA ring 32 / 64, register-staged 64, fp32 16, A-stationary 128, 256 x 256 tiles 64; skinny: the 64- / 128-wide chunk);
+ * stages: slots of the ring (skinny: waves per block; register-staged and fp32: 0);  splits: K-splits that ran (0 = unsplit; the 256 x 256 wgrad kernel's
+ * full + extra splits);  astat_column_split: blocks that share a 128-row panel of the A-stationary kernel (1 = one block sweeps all of N). */
+int emo_gemm_last_plan(void);
 /* sizeof(emo_epilogue_t) as the library was built — a binding checks its own mirror of the struct against it before the first call */
 int emo_epilogue_size(void);
 int64_t emo_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, int dtype_in, int dtype_out);

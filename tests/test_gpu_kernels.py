@@ -105,6 +105,7 @@ def test_gemm_epilogue_bias_act_residual_aux(dt):
                     (ops.ACT_NONE, lambda x: x)):
         aux = torch.empty(M, N, device='cuda', dtype=dt)
         out = ops.gemm(A.cuda(), W.cuda(), bias=bias.cuda(), act=act, residual=res.cuda(), aux_out=aux)
+        assert ops.lib.emo_gemm_last_kernel() == (7 if dt == torch.float32 else 5)      # (gelu_new included: the fp32 kernel / the LDS-DMA ring)
         _close(aux, z, dt)
         _close(out, fn(z) + res.double(), dt)
 
@@ -123,6 +124,7 @@ def test_gemm_epilogue_mul_modes_and_dropout(dt):
     u = math.sqrt(2 / math.pi) * (x + 0.044715 * x ** 3)
     dg = 0.5 * (1 + torch.tanh(u)) + 0.5 * x * (1 - torch.tanh(u) ** 2) * math.sqrt(2 / math.pi) * (1 + 3 * 0.044715 * x ** 2)
     out = ops.gemm(A.cuda(), W.cuda(), mul_aux=aux.cuda(), mul_mode=ops.MUL_DGELU_NEW)
+    assert ops.lib.emo_gemm_last_kernel() == (7 if dt == torch.float32 else 5)
     _close(out, z * dg, dt)
     # dropout: deterministic in (seed, offset), ~p zeros, survivors scaled by 1/(1-p), and consistent
     # with emo_dropout_apply / layernorm_bwd masks (same element indexing m*N+n)
@@ -153,18 +155,24 @@ def test_gemm_small_grid_long_k_split_with_epilogue(M, N, K, b_trans):
     bias, res = _r(N, seed=23), _r(M, N, seed=24, dt=dt)
     z = A.double() @ (W.double() if b_trans else W.double().T)
     Ac, Wc = A.cuda(), W.cuda()
+    def split4():      # the ring + the reduce-and-epilogue pass over 4 K-splits
+        return lib.emo_gemm_last_kernel() == 5 + 32 and (lib.emo_gemm_last_plan() >> 16) & 255 == 4
     plain = ops.gemm(Ac, Wc, b_trans=b_trans)
+    assert split4()
     _close(plain, z, dt)
     aux = torch.empty(M, N, device='cuda', dtype=dt)
     out = ops.gemm(Ac, Wc, b_trans=b_trans, bias=bias.cuda(), act=ops.ACT_RELU, residual=res.cuda(), aux_out=aux)
+    assert split4()
     _close(aux, z + bias.double(), dt)
     _close(out, torch.relu(z + bias.double()) + res.double(), dt)
     o1 = ops.gemm(Ac, Wc, b_trans=b_trans, p_drop=0.1, seed=11, offset=3, residual=res.cuda())
+    assert split4()
     masked = ops.dropout_apply(plain, 0.1, 11, 3)
     _close(o1, masked.double().cpu() + res.double(), dt, mult=2.0)
     mask = _r(M, N, seed=25, dt=dt)
     mask[mask.abs() < 0.6] = 0
     o2 = ops.gemm(Ac, Wc, b_trans=b_trans, mul_aux=mask.cuda(), mul_mode=ops.MUL_NONZERO, mul_scale=1.25)
+    assert split4()
     _close(o2, z * (mask.double() != 0) * 1.25, dt)
 
 
@@ -241,6 +249,7 @@ def test_gemm_large_wgrad_matches_torch_and_is_deterministic():
     for _ in range(3):
         dw, db = torch.zeros(M, N, device='cuda'), torch.zeros(M, device='cuda')
         ops.gemm(dy, x, a_trans=True, b_trans=True, out=dw, a_rowsum=db)
+        assert ops.lib.emo_gemm_last_kernel() == 3 and (ops.lib.emo_gemm_last_plan() >> 16) & 255 == 21      # 12 tiles: 2 whole splits per XCD + 5 extra
         outs.append(dw)
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
     ref = dy.double().T @ x.double()
@@ -261,8 +270,10 @@ def test_gemm_256_tile_nt_matches_reference_and_128_tile(shape, monkeypatch):
     for kw in ({}, dict(bias=bias), dict(residual=res), dict(bias=bias, p_drop=0.1, seed=5, offset=7, residual=res)):
         monkeypatch.setenv('EMO_GEMM_W128', '1')
         y1, y2 = ops.gemm(A, W, **kw), ops.gemm(A, W, **kw)
+        assert ops.lib.emo_gemm_last_kernel() == 4 and ops.lib.emo_gemm_last_plan() & 255 == 64, kw.keys()
         monkeypatch.setenv('EMO_GEMM_W128', '0')
         y0 = ops.gemm(A, W, **kw)
+        assert ops.lib.emo_gemm_last_kernel() == 5, kw.keys()      # the other side of the switch: the 128 x 128 ring, unsplit
         assert torch.equal(y1, y2) and torch.equal(y1, y0), kw.keys()
         if 'p_drop' not in kw:
             ref = A.double() @ W.double().T + (bias.double() if 'bias' in kw else 0.0) + (res.double() if 'residual' in kw else 0.0)
@@ -415,6 +426,7 @@ def test_gemm_skinny_layernorm_folding(M):
     bias = (b + W @ beta).cuda()
     stats = torch.empty(M, 2, device='cuda')
     y = ops.gemm(x.cuda(), Wg, bias=bias, act=ops.ACT_RELU, ln_c1=c1, ln_stats_out=stats)
+    assert ops.lib.emo_gemm_last_kernel() == 1
     _close(y, ref, torch.bfloat16, mult=2)
     _close(stats[:, 0], mean[:, 0], torch.float32, scale=1.0, mult=10)
     _close(stats[:, 1], 1.0 / torch.sqrt(var[:, 0] + 1e-5), torch.float32, scale=1.0, mult=10)
@@ -424,6 +436,7 @@ def test_gemm_skinny_layernorm_folding(M):
     b2 = _r(K, seed=8, scale=0.1)
     ref2 = f.double() @ W2.double().T + b2.double() + ln
     y2 = ops.gemm(f.cuda(), W2.cuda(), bias=b2.cuda(), rln=(x.cuda(), stats, gamma.cuda(), beta.cuda()))
+    assert ops.lib.emo_gemm_last_kernel() == 1
     _close(y2, ref2, torch.bfloat16, mult=2)
     with pytest.raises(Exception, match='skinny'):
         ops.gemm(_r(64, K, seed=1).to(torch.bfloat16).cuda(), Wg, ln_c1=c1)
@@ -1301,8 +1314,10 @@ def test_gemm_skinny_decode_shapes(M):
         A, W = _r(M, K, seed=1, dt=dt), _r(N, K, seed=2, dt=dt, scale=0.1)
         bias, res = _r(N, seed=3), _r(M, N, seed=4, dt=dt)
         out = ops.gemm(A.cuda(), W.cuda(), bias=bias.cuda(), act=ops.ACT_RELU, residual=res.cuda())
+        assert ops.lib.emo_gemm_last_kernel() == 1 and (ops.lib.emo_gemm_last_plan() >> 8) & 255 == (16 if K >= 2048 else 4)     # skinny, waves per block
         _close(out, torch.relu(A.double() @ W.double().T + bias.double()) + res.double(), dt)
         out32 = ops.gemm(A.cuda(), W.cuda(), bias=bias.cuda(), out_dtype=torch.float32)
+        assert ops.lib.emo_gemm_last_kernel() == 1
         _close(out32, A.double() @ W.double().T + bias.double(), dt, mult=0.3)
 
 
@@ -1338,6 +1353,8 @@ def test_gemm_astat_k512_matches_reference_and_the_tiled_kernel(M, N, out_dt, mo
             if k2.get('aux_out') == 'alloc':
                 aux = k2['aux_out'] = torch.empty(M, N, device='cuda', dtype=out_dt)
             outs.append((ops.gemm(A, W, out_dtype=out_dt, **k2), aux))
+            fam = ops.lib.emo_gemm_last_kernel() & 15          # both sides of the switch ran what they claim: A-stationary (with a column split >= 1) / tiled
+            assert (fam in (5, 6)) if no_astat else (fam == 2 and ops.lib.emo_gemm_last_plan() >> 24 >= 1), (fam, sorted(kw))
         torch.cuda.synchronize()
         (new, new_aux), (old, old_aux) = outs
         if out_dt == torch.bfloat16 and 'bias' not in kw:
@@ -1358,6 +1375,7 @@ def test_gemm_astat_k512_matches_reference_and_the_tiled_kernel(M, N, out_dt, mo
     big = _r(M, 3 * K, seed=6, dt=torch.bfloat16).cuda()
     outb = torch.zeros(M, 2 * N, device='cuda', dtype=out_dt)
     ops.gemm(big[:, K:2 * K], W, out=outb[:, N:], bias=bias)
+    assert ops.lib.emo_gemm_last_kernel() == 2
     _close(outb[:, N:], big[:, K:2 * K].double() @ W.double().t() + bias.double(), torch.bfloat16, mult=1.0)
     assert float(outb[:, :N].abs().max()) == 0.0
 
@@ -1373,13 +1391,17 @@ def test_gemm_astat_bitmask_epilogue_equals_the_activation_mask(M):
     h, W1, b1 = _r(M, K, seed=1, dt=torch.bfloat16).cuda(), _r(N, K, seed=2, dt=torch.bfloat16, scale=0.05).cuda(), _r(N, seed=3).cuda()
     fmask = torch.zeros(M, N // 8, device='cuda', dtype=torch.uint8)
     f = ops.gemm(h, W1, bias=b1, act=ops.ACT_RELU, p_drop=0.1, seed=5, offset=2, mask_out=fmask)
+    assert ops.lib.emo_gemm_last_kernel() == 2
     f_plain = ops.gemm(h, W1, bias=b1, act=ops.ACT_RELU, p_drop=0.1, seed=5, offset=2)
+    assert ops.lib.emo_gemm_last_kernel() == 2
     assert torch.equal(f, f_plain)                                  # writing the mask does not change the output
     bits = (ops.bitmask_rows(fmask, M, N)[:, :, None] >> torch.arange(8, device='cuda', dtype=torch.uint8)) & 1   # (the mask is stored tile by tile)
     assert torch.equal(bits.reshape(M, N).bool(), f != 0) and 0.3 < float((f != 0).float().mean()) < 0.6
     dy, W2t = _r(M, K, seed=6, dt=torch.bfloat16).cuda(), _r(N, K, seed=7, dt=torch.bfloat16, scale=0.05).cuda()
     a = ops.gemm(dy, W2t, mul_aux=fmask, mul_mode=ops.MUL_BITMASK, mul_scale=1.0 / 0.9)
+    assert ops.lib.emo_gemm_last_kernel() == 2
     b = ops.gemm(dy, W2t, mul_aux=f, mul_mode=ops.MUL_NONZERO, mul_scale=1.0 / 0.9)
+    assert ops.lib.emo_gemm_last_kernel() == 2
     assert torch.equal(a, b)
     with pytest.raises((EmoError, AssertionError)):                 # outside the A-stationary shape class: refused, never ignored
         ops.gemm(h[:100], W1, mask_out=fmask[:100])
@@ -1410,6 +1432,7 @@ def test_gemm_layernorm_of_the_a_operand_matches_the_separate_kernels(M, N):
     assert ops.gemm_lna_ok(M, N, K, torch.bfloat16)
     for kw in (dict(bias=bias), dict(bias=bias, act=ops.ACT_RELU, p_drop=0.1, seed=7, offset=3)):
         y, h, mean, rstd = ops.gemm(x, W, lna=(g, b, 1e-5), **kw)
+        assert ops.lib.emo_gemm_last_kernel() == 2
         h_ref, m_ref, r_ref = ops.layernorm_fwd(x, g, b)
         xd = x.double()
         mu = xd.mean(1)
@@ -1433,6 +1456,7 @@ def test_gemm_layernorm_of_the_a_operand_rows_with_a_large_mean():
     W = _r(N, K, seed=2, scale=0.05).to(torch.bfloat16).cuda()
     g, b = torch.ones(K, device='cuda'), torch.zeros(K, device='cuda')
     y, h, mean, rstd = ops.gemm(x, W, lna=(g, b, 1e-5))
+    assert ops.lib.emo_gemm_last_kernel() == 2
     xd = x.double()
     mu = xd.mean(1)
     var = ((xd - mu[:, None]) ** 2).mean(1)
