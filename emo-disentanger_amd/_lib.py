@@ -53,6 +53,15 @@ class GrammarStep(ctypes.Structure):
                 ('tok_logp', c_p), ('tok_rank', c_p), ('tok_entropy', c_p)]
 
 
+class AccRebase(ctypes.Structure):
+    """emo_acc_rebase_t (emo_hip.h), field for field: the argument block of the re-anchoring launch.  Pointer fields hold raw device addresses."""
+    _fields_ = [('n_rows', c_l), ('seq', c_p), ('segs', c_p), ('ld_seq', c_l), ('state', c_p), ('params', c_p), ('primer_len', c_p),
+                ('track_leadsheet', c_l), ('keep', c_l), ('window', c_l), ('longest_bar', c_l), ('pad', c_l),
+                ('dst_seq', c_p), ('dst_segs', c_p), ('ld_dst', c_l), ('arch_tok', c_p), ('arch_len', c_p), ('ld_arch', c_l),
+                ('tok_logp', c_p), ('tok_rank', c_p), ('tok_entropy', c_p), ('dst_logp', c_p), ('dst_rank', c_p), ('dst_entropy', c_p),
+                ('arch_logp', c_p), ('arch_rank', c_p), ('arch_entropy', c_p), ('new_len', c_p), ('running', c_p)]
+
+
 GRAMMAR_TXL, GRAMMAR_ACC, GRAMMAR_ACC_WINDOW, GRAMMAR_TXL_QUEUE, GRAMMAR_ACC_QUEUE = 0, 1, 2, 3, 4      # emo_hip.h: EMO_GRAMMAR_*
 
 
@@ -102,6 +111,7 @@ _SIG = {
     'emo_decode_step': (c_i, [ctypes.POINTER(DecodeStep), c_p]),
     'emo_favor_draw_omega': (c_i, [c_p, c_p, c_l, c_l, c_l, c_p]),
     'emo_favor_state_reset': (c_i, [c_p, c_l, c_l, c_l, c_l, c_p, c_p]),
+    'emo_favor_state_at': (c_i, [c_p, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_l, c_p]),
     'emo_softmax_attn_keep_bytes': (c_l, [c_i, c_l, c_l, c_l, c_l, c_f]),
     'emo_relpos_attn_bwd_r_workspace_bytes': (c_l, [c_l, c_l, c_l, c_l]),
     'emo_xent_fwd': (c_i, [c_p, c_p, c_l, c_l, c_l, c_p, c_p, c_p]),
@@ -113,6 +123,8 @@ _SIG = {
     'emo_sample_nucleus_step': (c_i, [c_p, c_l, c_l, c_f, c_f, c_p, c_p, c_p, c_l, c_l, c_p, c_p]),
     'emo_grammar_step_size': (c_i, []),
     'emo_grammar_step': (c_i, [ctypes.POINTER(GrammarStep), c_p]),
+    'emo_acc_rebase_size': (c_i, []),
+    'emo_acc_rebase': (c_i, [ctypes.POINTER(AccRebase), c_p]),
     'emo_accuracy_counts': (c_i, [c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_p, c_p]),
     'emo_sumsq': (c_i, [c_p, c_l, c_p, c_p]),
     'emo_clip_coef': (c_i, [c_p, c_f, c_f, c_p, c_p, c_p]),
@@ -134,7 +146,8 @@ for _name, (_res, _args) in _SIG.items():
     _fn = getattr(lib, _name)          # AttributeError here = header/library mismatch
     _fn.restype, _fn.argtypes = _res, _args
 for _cname, _size, _mirror in (('emo_epilogue_t', lib.emo_epilogue_size, Epilogue), ('emo_decode_step_t', lib.emo_decode_step_size, DecodeStep),
-                               ('emo_grammar_step_t', lib.emo_grammar_step_size, GrammarStep), ('emo_attn_t', lib.emo_attn_size, Attn)):
+                               ('emo_grammar_step_t', lib.emo_grammar_step_size, GrammarStep), ('emo_attn_t', lib.emo_attn_size, Attn),
+                               ('emo_acc_rebase_t', lib.emo_acc_rebase_size, AccRebase)):
     if _size() != ctypes.sizeof(_mirror):                   # a stale libemo_hip.so (or a stale mirror above) would read garbage pointers
         raise ImportError('libemo_hip.so was built with an %s of %d bytes, this binding has %d: rebuild (python -c "import __graft_entry__ as g; g.build()")'
                           % (_cname, _size(), ctypes.sizeof(_mirror)))

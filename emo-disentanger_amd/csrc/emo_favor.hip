@@ -1454,6 +1454,129 @@ extern "C" int emo_favor_state_reset(const void* state_table, int64_t n_layers, 
     return EMO_OK;
 }
 
+// =============================================================================================== state at a per-row length (emo_favor_state_at)
+// S[b,h] = sum_{t < lens[b]} phi(k_t) (x) v_t and z[b,h] = sum_{t < lens[b]} phi(k_t): the recurrent state a decode row continues from after a
+// prefill of rows of different lengths.  A masked reduction, no scan: one workgroup (8 waves) per (b, h) walks the row's first lens[b] tokens in
+// tiles of C = 32.  Per tile the forward's own pieces: RowPrefetch zero-fills the rows at and beyond the length (an element mask: a tile that
+// straddles lens[b] is computed, its rows t >= lens[b] contribute exact zeros and are never loaded), features_transposed is the forward's phi
+// (scaling dh^-1/4, offset |c k|^2 / 2 + ln(F) / 2, the omega image) written as the image KfT [F][LDC] whose reduction index is the token,
+// V goes to the transposed image VT [DH][LDC], and the state tiles are the forward's product KfT . VT^T on its MFMA route (bf16 operands with
+// f32 accumulation: v_mfma_f32_16x16x32_bf16; exact f32: v_mfma_f32_16x16x4_f32) with the accumulators in registers for the whole walk; z adds
+// the rows of KfT as stored (the rounded features, as the forward's z does).  LDS images: rows padded by Img<CT>::PAD (bf16 +16 B, f32 +8 B) so
+// that the 16 rows of a fragment read start in different banks; 15 KB (bf16) / 43 KB (f32) at d_head 64, 128 features.
+template <typename CT, int DH, int MF, int C>
+__global__ __launch_bounds__(FT) void favor_state_at_kernel(const CT* __restrict__ k, const CT* __restrict__ v, int64_t ld, const float* __restrict__ omega,
+                                                            const int32_t* __restrict__ lens, float* __restrict__ state_S, float* __restrict__ state_z,
+                                                            int64_t T, int64_t H) {
+    typedef FavorDims<CT, DH, MF, C, 0> D;
+    constexpr int F = D::F, LDX = D::LDX, LDC = D::LDC, DHP = D::DHP, CP = D::CP;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    CT* WT = (CT*)smem;                 // [MF][LDX]  omega^T
+    CT* Xk = WT + MF * LDX;             // [C][LDX]   the tile's k rows
+    CT* VT = Xk + C * LDX;              // [DH][LDC]  the tile's v rows, transposed
+    CT* KfT = VT + DH * LDC;            // [F][LDC]   phi(k)^T
+    float* offk = (float*)(KfT + F * LDC);
+    float* zz = offk + C;               // [F]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t bh = blockIdx.x, b = bh / H, h = bh % H;
+    int64_t len = lens[b];
+    len = len < 0 ? 0 : (len > T ? T : len);        // never a read outside the row's T tokens
+    const CT* kb = k + (b * T) * ld + h * DH;
+    const CT* vb = v + (b * T) * ld + h * DH;
+    const float cs = rsqrtf(sqrtf((float)DH));
+    const float half_ln_f = 0.5f * logf((float)F);
+
+    zero_img(WT, MF * LDX, tid);
+    zero_img(VT, DH * LDC, tid);
+    zero_img(KfT, F * LDC, tid);
+    for (int i = tid; i < F; i += FT) zz[i] = 0.f;
+    __syncthreads();
+    for (int i = tid; i < DH * MF; i += FT) { const int d = i / MF, m = i % MF; WT[m * LDX + d] = from_f32<CT>(omega[i]); }
+
+    constexpr int NTS = (F / 16) * (DH / 16);          // state tiles: rows<->f (R=KfT), col<->d (C=VT)
+    constexpr int NTS_W = (NTS + FW - 1) / FW;
+    static_assert(FW % (DH / 16) == 0, "a wave's state tiles share the d block");
+    f32x4 sacc[NTS_W];
+#pragma unroll
+    for (int i = 0; i < NTS_W; ++i) sacc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    RowPrefetch<CT, DH, DHP, C, FT> pk;
+    RowPrefetch<CT, DH, DHP, C, FT, true> pv;
+    if (len > 0) {
+        const int v0 = (int)(len < C ? len : C);
+        pk.load(kb, ld, v0, tid);
+        pv.load(vb, ld, v0, tid);
+    }
+    for (int64_t t0 = 0; t0 < len; t0 += C) {
+        const int valid = (int)((len - t0) < C ? (len - t0) : C);
+        __syncthreads();                               // the last tile's products have read Xk / VT / KfT
+        pk.store_rows_off(Xk, LDX, tid, offk, cs * cs, half_ln_f);
+        pv.store_T(VT, LDC, tid);
+        if (t0 + C < len) {                            // the next tile's rows stay in flight during this tile's compute
+            const int vn = (int)((len - t0 - C) < C ? (len - t0 - C) : C);
+            pk.load(kb + (t0 + C) * ld, ld, vn, tid);
+            pv.load(vb + (t0 + C) * ld, ld, vn, tid);
+        }
+        __syncthreads();
+        features_transposed<CT, DHP, MF, C>(KfT, LDC, WT, Xk, LDX, offk, cs, valid, wave, lane);
+        __syncthreads();
+        Frags<CT, CP> vtf;
+        vtf.load(VT, LDC, (wave % (DH / 16)) * 16, lane);
+#pragma unroll
+        for (int i = 0; i < NTS_W; ++i) {
+            const int tile = wave + FW * i;
+            if (tile < NTS) mm16_c<CT, CP>(sacc[i], KfT, LDC, (tile / (DH / 16)) * 16, vtf, lane);
+        }
+        for (int f = tid; f < F; f += FT) {
+            float s = 0.f;
+#pragma unroll
+            for (int j = 0; j < C; ++j) s += to_f32<CT>(KfT[f * LDC + j]);
+            zz[f] += s;
+        }
+    }
+    __syncthreads();
+    float* So = state_S + bh * (int64_t)F * DH;
+#pragma unroll
+    for (int i = 0; i < NTS_W; ++i) {
+        const int tile = wave + FW * i;
+        if (tile < NTS) {
+            const int ft = tile / (DH / 16), dt = tile % (DH / 16);
+            const int d = dt * 16 + (lane & 15), f0 = ft * 16 + (lane >> 4) * 4;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) So[(f0 + r) * DH + d] = sacc[i][r];
+        }
+    }
+    for (int f = tid; f < F; f += FT) state_z[bh * (int64_t)F + f] = zz[f];
+}
+
+struct FavorStateAt {
+    static constexpr int C = 32;
+    template <typename CT, int DH, int MF> static int run(const emo_attn_t& a, hipStream_t st, const int32_t* lens) {
+        typedef FavorDims<CT, DH, MF, C, 0> D;
+        const size_t lds = sizeof(CT) * (size_t)(MF * D::LDX + C * D::LDX + DH * D::LDC + D::F * D::LDC) + sizeof(float) * (size_t)(C + D::F);
+        EMO_CHECK(lds <= EMO_MAX_LDS, "LDS %zu too large", lds);
+        return emo_launch<favor_state_at_kernel<CT, DH, MF, C>>(dim3((unsigned)(a.B * a.H)), dim3(FT), lds, st, (const CT*)a.k, (const CT*)a.v, a.ld, a.omega,
+                                                                 lens, a.state_S, a.state_z, a.T, a.H);
+    }
+};
+
+extern "C" int emo_favor_state_at(const void* k, const void* v, int64_t ld, int dtype, const float* omega, const int32_t* lens, float* state_S,
+                                  float* state_z, int64_t B, int64_t T, int64_t H, int64_t dh, int64_t n_feat, emo_stream_t stream) {
+    EMO_CHECK(k && v && omega && lens && state_S && state_z, "emo_favor_state_at: null pointer");
+    EMO_CHECK(dtype == EMO_F32 || dtype == EMO_BF16, "emo_favor_state_at: bad dtype %d", dtype);
+    EMO_CHECK(B > 0 && T > 0 && H > 0 && B * H <= INT32_MAX && n_feat % 2 == 0, "emo_favor_state_at: bad sizes");
+    const int64_t esz = dtype == EMO_BF16 ? 2 : 4;
+    EMO_CHECK(ld >= H * dh && (ld * esz) % 16 == 0 && (dh * esz) % 16 == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0,
+              "emo_favor_state_at: k / v rows must be 16-B aligned (ld %lld, d_head %lld)", (long long)ld, (long long)dh);
+    emo_attn_t a = {};                                 // the carrier of the (dtype, d_head, n_feat) table, as for the passes of emo_attn
+    a.k = k; a.v = v; a.ld = ld; a.dtype = dtype; a.omega = omega; a.state_S = state_S; a.state_z = state_z;
+    a.B = B; a.T = T; a.H = H; a.dh = dh; a.n_feat = n_feat;
+    int rc;
+    if (favor_table<FavorStateAt>(a, &rc, (hipStream_t)stream, lens)) return rc;
+    emo_set_error("emo_favor_state_at: unsupported (d_head=%lld, n_feat=%lld); built: (64,128) (32,128) (32,64) (16,32) (16,64)", (long long)dh, (long long)n_feat);
+    return EMO_ERR_UNSUPPORTED;
+}
+
 // The FAVOR kind of emo_attn (emo_softmax_attn.hip: the entry, the checks every kind shares and the prefix of the messages)
 int emo_attn_favor(const emo_attn_t& a, hipStream_t st) {
     EMO_CHECK(a.n_feat % 2 == 0, "n_feat must be even");

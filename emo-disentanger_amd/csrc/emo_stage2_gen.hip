@@ -317,3 +317,124 @@ extern "C" int emo_grammar_step(const emo_grammar_step_t* args, emo_stream_t str
     EMO_LAUNCH_CHECK();
     return EMO_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- re-anchoring on a bar (emo_acc_rebase)
+// A stream that filled the window (status WINDOW) drops its oldest whole bars and keeps its primer: the context the model was trained on (the
+// reference dataloader, dataloader.py:179-186: the piece's opening events followed by the piece from a random bar on, positions from 0).  One
+// 512-thread workgroup per row.  The cut b is found by a strided scan of the row (every thread keeps the smallest bar start at or behind the
+// first index that fits `keep`, and the largest bar start of all), a wave reduction (wave size 64) and a reduction across the 8 waves through
+// LDS; inference.rebase_plan is the rule on the host.  The row is then copied, primer + tail, into the destination row (another buffer: source
+// and destination never alias), the dropped tokens and their recorded scores go to the row's archive, and thread 0 writes the state and
+// parameter words of the new phase.  Every global read of a word that thread 0 rewrites lies in front of the first barrier.
+namespace {
+
+__global__ __launch_bounds__(512) void acc_rebase_kernel(const emo_acc_rebase_t a) {
+    __shared__ int32_t smin[8], smax[8], scur;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t r = blockIdx.x;
+    int32_t* st = a.state + r * EMO_ACC_STATE_WORDS;
+    if (st[EMO_ACC_S_STATUS] != EMO_ACC_WINDOW) {            // (nobody writes the word in this branch: every thread reads the same value)
+        if (tid == 0) a.new_len[r] = 0;
+        return;
+    }
+    const int64_t n = st[EMO_ACC_S_LEN], P = a.primer_len[r];
+    const int64_t* row = a.seq + r * a.ld_seq;
+    const int64_t* srow = a.segs + r * a.ld_seq;
+    if (tid == 0) scur = a.arch_len[r];
+    const bool sane = P >= 0 && P <= n && n <= a.ld_seq;     // a row that cannot be read is a caller error (OVERFLOW below), never a read outside it
+    const int64_t first = P + n - a.keep > P ? P + n - a.keep : P;      // bar starts at or behind it leave at most `keep` tokens
+    int32_t lo = INT32_MAX, hi = -1;
+    if (sane) {
+        for (int64_t i = P + tid; i < n; i += 512) {
+            if (row[i] == a.track_leadsheet) {
+                if (i >= first && (int32_t)i < lo) lo = (int32_t)i;
+                hi = (int32_t)i;                             // (i grows: the last one seen is the thread's largest)
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int32_t l2 = __shfl_xor(lo, o, 64), h2 = __shfl_xor(hi, o, 64);
+        lo = l2 < lo ? l2 : lo;
+        hi = h2 > hi ? h2 : hi;
+    }
+    if (lane == 0) {
+        smin[wave] = lo;
+        smax[wave] = hi;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < 8; ++w) {
+        lo = smin[w] < lo ? smin[w] : lo;
+        hi = smax[w] > hi ? smax[w] : hi;
+    }
+    int64_t b = P;
+    int32_t err = 0;
+    if (!sane) err = EMO_ACC_OVERFLOW;
+    else if (lo != INT32_MAX) b = lo;
+    else if (hi >= 0 && P + n - hi <= a.window - a.longest_bar - 2) b = hi;
+    else err = EMO_REBASE_BAR_TOO_LONG;
+    const int64_t drop = b - P, len2 = P + n - b, cur = scur;
+    if (!err && (len2 > a.ld_dst || cur < 0 || cur + drop > a.ld_arch)) err = EMO_ACC_OVERFLOW;
+    if (err) {
+        if (tid == 0) {
+            st[EMO_ACC_S_STATUS] = err;
+            a.new_len[r] = 0;
+        }
+        return;
+    }
+    const bool scores = a.tok_logp != nullptr;                   // (the entry takes the three sources and destinations together or not at all)
+    const float nan = __builtin_nanf("");
+    for (int64_t i = tid; i < a.ld_dst; i += 512) {
+        const int64_t s = i < P ? i : b + (i - P);
+        const bool in = i < len2;
+        a.dst_seq[r * a.ld_dst + i] = in ? row[s] : a.pad;
+        a.dst_segs[r * a.ld_dst + i] = in ? srow[s] : 1;
+        if (scores) {
+            a.dst_logp[r * a.ld_dst + i] = in ? a.tok_logp[r * a.ld_seq + s] : nan;
+            a.dst_rank[r * a.ld_dst + i] = in ? a.tok_rank[r * a.ld_seq + s] : -1;
+            a.dst_entropy[r * a.ld_dst + i] = in ? a.tok_entropy[r * a.ld_seq + s] : nan;
+        }
+    }
+    for (int64_t j = tid; j < drop; j += 512) {
+        a.arch_tok[r * a.ld_arch + cur + j] = row[P + j];
+        if (scores) {
+            a.arch_logp[r * a.ld_arch + cur + j] = a.tok_logp[r * a.ld_seq + P + j];
+            a.arch_rank[r * a.ld_arch + cur + j] = a.tok_rank[r * a.ld_seq + P + j];
+            a.arch_entropy[r * a.ld_arch + cur + j] = a.tok_entropy[r * a.ld_seq + P + j];
+        }
+    }
+    if (tid != 0) return;
+    a.arch_len[r] = (int32_t)(cur + drop);
+    st[EMO_ACC_S_STATUS] = EMO_ACC_RUNNING;
+    st[EMO_ACC_S_LEN] = (int32_t)len2;
+    st[EMO_ACC_S_CONSUMED] = (int32_t)len2;                  // the prefill of the phase takes the whole context
+    st[EMO_ACC_S_DRAWS] = 0;
+    a.params[r * EMO_ACC_PARAM_WORDS + EMO_ACC_P_MAX_EVENTS] -= (int32_t)drop;     // the whole-piece limit, in the new row's indices
+    a.new_len[r] = (int32_t)len2;
+    atomicAdd(a.running, 1);
+}
+
+}  // namespace
+
+extern "C" int emo_acc_rebase_size(void) { return (int)sizeof(emo_acc_rebase_t); }
+
+extern "C" int emo_acc_rebase(const emo_acc_rebase_t* args, emo_stream_t stream) {
+    EMO_CHECK(args, "emo_acc_rebase: null argument block");
+    const emo_acc_rebase_t& a = *args;
+    EMO_CHECK(a.seq && a.segs && a.state && a.params && a.primer_len && a.dst_seq && a.dst_segs && a.arch_tok && a.arch_len && a.new_len && a.running,
+              "emo_acc_rebase: null pointer");
+    EMO_CHECK(a.n_rows > 0 && a.ld_seq > 0 && a.ld_dst > 0 && a.ld_arch > 0 && a.ld_seq <= INT32_MAX && a.ld_dst <= INT32_MAX && a.ld_arch <= INT32_MAX,
+              "emo_acc_rebase: bad sizes");
+    EMO_CHECK(a.longest_bar >= 0 && a.keep > 0 && a.keep <= a.window - a.longest_bar - 2 && a.window <= a.ld_dst,
+              "emo_acc_rebase: needs 0 < keep <= window - longest_bar - 2 and rows of at least window tokens (keep %lld, window %lld, longest_bar %lld, ld_dst %lld)",
+              (long long)a.keep, (long long)a.window, (long long)a.longest_bar, (long long)a.ld_dst);
+    EMO_CHECK(a.dst_seq != a.seq && a.dst_segs != a.segs, "emo_acc_rebase: source and destination rows must not alias");
+    const int have = (a.tok_logp != nullptr) + (a.tok_rank != nullptr) + (a.tok_entropy != nullptr) + (a.dst_logp != nullptr) + (a.dst_rank != nullptr) +
+                     (a.dst_entropy != nullptr) + (a.arch_logp != nullptr) + (a.arch_rank != nullptr) + (a.arch_entropy != nullptr);
+    EMO_CHECK(have == 0 || (have == 9 && a.dst_logp != a.tok_logp && a.dst_rank != a.tok_rank && a.dst_entropy != a.tok_entropy),
+              "emo_acc_rebase: the score tables come as three sources, three destinations and three archives that do not alias, or not at all");
+    hipLaunchKernelGGL(acc_rebase_kernel, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
+    EMO_LAUNCH_CHECK();
+    return EMO_OK;
+}

@@ -80,6 +80,21 @@ class _EngineBase:
     def _logits(self, h, out=None):
         return ops.gemm(h, self.ps.w('dec_out_proj.weight'), bias=self.ps.f32('dec_out_proj.bias'), out=out, out_dtype=torch.float32)
 
+    def _check_lens(self, tok, lens):
+        """The per-row lengths of prefill(lens=): int32 [B] on the engine's device."""
+        if lens.dtype != torch.int32 or lens.shape != (tok.shape[0],) or lens.device != tok.device:
+            raise EmoError('prefill(lens=): lens must be int32 [%d] on the device of the tokens' % tok.shape[0])
+        return lens.contiguous()
+
+    def _rows_at(self, x, lens, B, T):
+        """Rows lens[b] - 1 of the hidden states x [B*T, D], and the engine's positions set to the rows' own: pos_dev = lens (in place: the
+        array's address may sit in an argument block), dev_pos0 = 0, the host count at the longest row."""
+        at = torch.arange(B, device=self.dev) * T + (lens.long() - 1).clamp_(0, T - 1)
+        self.pos = T
+        self.pos_dev.copy_(lens)
+        self.dev_pos0 = 0
+        return x.index_select(0, at).contiguous()
+
     @torch.no_grad()
     def append(self, tok, seg):
         """tok, seg: int64 [n, k]; consumes k tokens per stream, returns logits [n, V] after the last one."""
@@ -321,7 +336,12 @@ class PerformerDecodeEngine(_EngineBase):
         return ops.gemm(res[0], Wg, bias=bb, ln_c1=c1, out=logits_out, out_dtype=torch.float32)
 
     @torch.no_grad()
-    def prefill(self, tok, seg):
+    def prefill(self, tok, seg, lens=None):
+        """lens (int32 [B] on the device, 1 <= lens[b] <= T): row b holds lens[b] tokens and padding behind them.  Causality keeps the attention
+        outputs below lens[b] independent of the padding; the state is the row's own (ops.favor_state_at, not the scan's end state), the logits
+        returned are those of position lens[b] - 1 and every row steps on from its own position (pos_dev = lens, dev_pos0 = 0)."""
+        if lens is not None:
+            return self._prefill_varlen(tok, seg, self._check_lens(tok, lens))
         m, ps = self.model, self.ps
         B, T = tok.shape
         D, H = m.d_model, m.n_head
@@ -344,6 +364,27 @@ class PerformerDecodeEngine(_EngineBase):
         self.pos = T
         self.pos_dev.fill_(T)
         return self._logits(x.view(B, T, D)[:, -1].contiguous())
+
+    def _prefill_varlen(self, tok, seg, lens):
+        m, ps = self.model, self.ps
+        B, T = tok.shape
+        D, H = m.d_model, m.n_head
+        F = 2 * self.omegas[0].shape[1]
+        rows = self.n_pad if self.persist is not None else B     # (the idle padding rows of the one-launch step: zero, as in prefill)
+        x = self._embed(tok, seg, 0)
+        for l in range(m.n_layer):
+            pfx = m._layer_prefix(l)
+            q = pfx + 'attention.query_projection.'
+            qkv = ops.gemm(x, ps.w(q + 'weight', 3 * D), bias=ps.f32(q + 'bias', 3 * D))
+            attn, _ = ops.favor_attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], self.omegas[l], B, T, H)
+            Sp = torch.zeros(rows, H, F, D // H, device=self.dev, dtype=torch.float32)
+            zp = torch.zeros(rows, H, F, device=self.dev, dtype=torch.float32)
+            self.S[l], self.z[l] = Sp[:B], zp[:B]
+            ops.favor_state_at(qkv[:, D:2 * D], qkv[:, 2 * D:], self.omegas[l], lens, B, T, H, out=(self.S[l], self.z[l]))
+            x = self._tail(pfx, x, attn)
+        if self.persist is not None:
+            self._void_table()
+        return self._logits(self._rows_at(x, lens, B, T))
 
     def _tail(self, pfx, x, attn):
         ps = self.ps
@@ -487,7 +528,12 @@ class GPT2DecodeEngine(_EngineBase):
         return ops.gemm(f, ps.w(pfx + 'mlp.c_proj.weight'), b_trans=True, bias=ps.f32(pfx + 'mlp.c_proj.bias'), residual=h)
 
     @torch.no_grad()
-    def prefill(self, tok, seg):
+    def prefill(self, tok, seg, lens=None):
+        """lens (int32 [B] on the device, 1 <= lens[b] <= T): row b holds lens[b] tokens and padding behind them.  The cache rows at and beyond
+        lens[b] then hold the padding's keys; the decode step overwrites each of them before it reads it (it appends at row lens[b], then
+        attends over lens[b] + 1 rows).  The logits returned are those of position lens[b] - 1; self.lens = pos_dev = lens, dev_pos0 = 0."""
+        if lens is not None:
+            lens = self._check_lens(tok, lens)
         m, ps = self.model, self.ps
         B, T = tok.shape
         D, H = m.d_model, m.n_head
@@ -504,6 +550,9 @@ class GPT2DecodeEngine(_EngineBase):
                 self.vc[l][:, :T].copy_(qkv[:, 2 * D:].view(B, T, D))
             a, _ = ops.softmax_attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B, T, H)
             x = self._block_tail(pfx, x, a)
+        if lens is not None:
+            self.lens.copy_(lens)
+            return self._logits(self._rows_at(x, lens, B, T))
         self.pos = T
         self.pos_dev.fill_(T)
         self.lens.fill_(T)
@@ -920,6 +969,7 @@ class AccompanimentLoop(GrammarLoop):
         toks, offs, bar0, nbars, longest = pack_lead_sheets(lead_sheets)
         self.lead_tok, self.lead_off = self._to_device(toks, offs)
         self.track_full, self.pad = event2idx['Track_Full'], event2idx.get('PAD_None', 0)
+        self.track_leadsheet, self.primer_lens = event2idx['Track_LeadSheet'], [len(p) for p in primers]      # (what a RebaseLoop cuts by)
         self.longest_bar = longest
         lens = [len(s.generated) for s in self.streams]
         width = max(self.W, max(lens)) + longest + 2              # an injected bar + Track_Full always fit behind an accepted word
@@ -996,7 +1046,7 @@ class AccompanimentLoop(GrammarLoop):
         s.consumed = int(state[i, ACC_S_CONSUMED])
         return s
 
-    def results(self, event2idx, idx2event, max_events, skip_check, seed, window='host'):
+    def results(self, event2idx, idx2event, max_events, skip_check, seed, window='host', rebase_keep=None, use_graph=True):
         """Per stream what _Stream.result() gives: DONE -> generated[:-1], STUCK -> generated; WINDOW -> the stream rebuilt from the device
         state and finished by _resume_windowed with nucleus(probs, top_p, rng=RandomState([seed, i])), or with window='device' finished
         together with the other WINDOW streams by a WindowedLoop (kept in self.windowed); an exhausted uniform table (or a row / position
@@ -1006,6 +1056,11 @@ class AccompanimentLoop(GrammarLoop):
         if window == 'device' and (state[:, ACC_S_STATUS] == ACC_WINDOW).any():
             self.windowed = WindowedLoop(self, seed)
             self.windowed.run()
+            past = dict(zip(self.windowed.idx, self.windowed.results()))
+        elif window == 'rebase' and (state[:, ACC_S_STATUS] == ACC_WINDOW).any():
+            # re-anchored on a bar and continued with cached one-token steps (RebaseLoop, kept in self.windowed like the WindowedLoop)
+            self.windowed = RebaseLoop(self, seed, rebase_keep)
+            self.windowed.run(use_graph=use_graph)
             past = dict(zip(self.windowed.idx, self.windowed.results()))
         out = []
         for i, s in enumerate(self.streams):
@@ -1245,9 +1300,233 @@ class WindowedLoop(GrammarLoop):
         return out
 
 
+REBASE_TAG = 0x524542                  # a rebase phase's uniform table is seeded with (seed, this tag, phase): never WINDOW_TAG's or the in-window seed
+ACC_BAR_TOO_LONG = 6                   # emo_hip.h: EMO_REBASE_BAR_TOO_LONG, the status emo_acc_rebase alone writes
+
+
+def rebase_plan(seq_row, n, primer_len, track_leadsheet, keep, W, longest_bar):
+    """The re-anchoring rule of window='rebase' for one stream, on the host (emo_acc_rebase is the same rule on the device).  seq_row[:n]: the
+    stream's tokens, primer_len primer ids followed by bars that each open with track_leadsheet (a drawn one counts like an injected one).
+    -> (b, new_len): the context continues as seq_row[:primer_len] + seq_row[b:n], new_len = primer_len + n - b tokens; b is the smallest bar
+    start that leaves at most `keep` tokens, else the last bar start when that leaves at most W - longest_bar - 2 (an injected bar and
+    Track_Full still fit below the window); else ACC_BAR_TOO_LONG (an int: a bar longer than the window).  b - primer_len tokens are dropped:
+    the stream's max_events goes down by as many (rebase_max_events)."""
+    P, n = int(primer_len), int(n)
+    starts = [i for i in range(P, n) if int(seq_row[i]) == track_leadsheet]
+    fit = [i for i in starts if P + (n - i) <= keep]
+    if fit:
+        return fit[0], P + n - fit[0]
+    if starts and P + (n - starts[-1]) <= W - longest_bar - 2:
+        return starts[-1], P + n - starts[-1]
+    return ACC_BAR_TOO_LONG
+
+
+def rebase_max_events(max_events, b, primer_len):
+    """max_events of a re-anchored stream: the reference's whole-piece limit len(generated) > max_events, counted in the new context's indices."""
+    return int(max_events) - (int(b) - int(primer_len))
+
+
+def rebase_stitch(primer, archive, tail):
+    """The piece so far of a re-anchored stream: its primer, the tokens (or score cells) its rebases dropped, in order, and its current context
+    behind the primer."""
+    return list(primer) + list(archive) + list(tail)
+
+
+def check_rebase_keep(rebase_keep, W, longest_primer, longest_bar):
+    """rebase_keep of generate_accompaniments -> the checked value (None: W // 2).  ValueError unless the longest primer, a Track_LeadSheet and
+    one token more fit it and a context of that size leaves room for the longest lead-sheet bar and its two Track marks below the window."""
+    keep = W // 2 if rebase_keep is None else rebase_keep
+    if isinstance(keep, bool) or not isinstance(keep, (int, np.integer)):
+        raise ValueError('rebase_keep must be an integer (got %r)' % (rebase_keep,))
+    lo, hi = int(longest_primer) + 2, W - int(longest_bar) - 2
+    if not lo <= keep <= hi:
+        raise ValueError('rebase_keep = %d is outside [%d, %d] = [len(primer) + 2, window - longest bar - 2]' % (keep, lo, hi))
+    return int(keep)
+
+
+class RebaseLoop(GrammarLoop):
+    """The ACC_WINDOW streams of a finished AccompanimentLoop / AccompanimentQueue, continued by re-anchoring (window='rebase').  A phase =
+    emo_acc_rebase (every WINDOW row drops its oldest whole bars, keeps its primer and becomes a context of at most `keep` tokens: rebase_plan),
+    one variable-length prefill of the batch (prefill(lens=)), then an ordinary in-window run on the shorter rows: emo_grammar_step of kind ACC
+    (unchanged) + the engine's one-token step, replayed by the shared replay driver until the longest row reaches the bound.  Rows still
+    RUNNING there are shorter than the row that reached it; they are marked WINDOW and re-anchored with it (a rebase of a row below `keep`
+    moves nothing).  Phases repeat while any row is at WINDOW.  Streams are indexed by their place j among the WINDOW streams (self.idx[j] = the
+    stream of the first loop).  Rows that are done stay in the batch as no-ops (they are prefilled as one pad token and fed pad): the batch is
+    never compacted, so the engine and, for the Performer, its feature maps (those of the first loop: redraw off) are the same objects
+    through all phases.  Token / segment rows and score tables are double-buffered (emo_acc_rebase never writes its source); self.home[j] is the
+    buffer that holds row j's latest context.  The dropped tokens and their scores go to a per-row archive; results() / score_arrays() stitch
+    primer + archive + context.  Phase p draws from a fresh uniform table seeded with (seed, REBASE_TAG, p).  If the one-launch step gives up,
+    the phase runs again from its saved state words on the chain of launches.  self.seconds: {'rebase', 'prefill', 'capture', 'replay'} of all
+    phases (capture: the run minus its replays: the graph captures and the eager steps around them)."""
+
+    def __init__(self, loop, seed, keep=None, n_u=None, persistent=True):
+        self.loop, self.model, self.dev = loop, loop.model, loop.dev
+        self.W, self.temp, self.top_p, self.seed = loop.W, loop.temp, loop.top_p, int(seed)
+        dev, W = self.dev, self.W
+        state = loop.state.cpu().numpy()
+        self.idx = [i for i in range(loop.n) if state[i, ACC_S_STATUS] == ACC_WINDOW]
+        m0 = self.m0 = len(self.idx)
+        assert m0 > 0, 'no stream reached the window'
+        self.keep = check_rebase_keep(keep, W, max(loop.primer_lens[i] for i in self.idx), loop.longest_bar)
+        # a phase steps its rows up to the window: with fewer positions than that a re-anchored row could have none left (AccompanimentQueue's refusal)
+        if self.model.use_pe and self.model.pe.pe.shape[0] < W:
+            raise EmoError("generate_accompaniments(window='rebase'): the positional table has %d rows, fewer than the window of %d tokens"
+                           % (self.model.pe.pe.shape[0], W))
+        sel = torch.tensor(self.idx, dtype=torch.long, device=dev)
+        self.seq_pp = [loop.seq[sel].contiguous(), None]
+        self.segs_pp = [loop.segs[sel].contiguous(), None]
+        self.seq_pp[1], self.segs_pp[1] = torch.zeros_like(self.seq_pp[0]), torch.zeros_like(self.segs_pp[0])
+        self.params = loop.params[sel].contiguous()
+        self.state = loop.state[sel].contiguous()
+        self.primer_len = torch.tensor([loop.primer_lens[i] for i in self.idx], dtype=torch.int32, device=dev)
+        self.accepted0 = int(self.state[:, ACC_S_ACCEPTED].sum().item())
+        cap = int(state[self.idx, ACC_S_LEN].max()) + loop.max_events + loop.longest_bar + 2       # the whole piece
+        self.arch_tok = torch.zeros(m0, cap, dtype=torch.int64, device=dev)
+        self.arch_len = torch.zeros(m0, dtype=torch.int32, device=dev)
+        self.new_len = torch.zeros(m0, dtype=torch.int32, device=dev)
+        self.running = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.U = torch.zeros(int(n_u or 4 * W), m0, dtype=torch.float32, device=dev)
+        self.tok = torch.full((m0,), loop.pad, dtype=torch.int64, device=dev)
+        self.segv = torch.ones(m0, dtype=torch.int64, device=dev)
+        self.logits = torch.zeros(m0, self.model.n_token, dtype=torch.float32, device=dev)
+        self.cur, self.home, self.rebased = 0, [0] * m0, [0] * m0      # (rebased[j]: the phases row j took part in)
+        self.phases, self.steps, self.prefill_tokens = 0, 0, []
+        self.seconds = {'rebase': 0.0, 'prefill': 0.0, 'capture': 0.0, 'replay': 0.0}
+        self.bound = W
+        self.persistent = persistent
+        with torch.no_grad():
+            self.eng = AccompanimentLoop._make_engine(self, m0, persistent, False)
+        self._build_block(ops.GRAMMAR_ACC, False, loop.job_controls.take(self.idx), n_rows=m0, n_token=self.model.n_token, ld_u=m0, temperature=self.temp,
+                          top_p=self.top_p, max_len=W, track_full=loop.track_full, pad=loop.pad, logits=self.logits, u_steps=self.U,
+                          ev_flags=loop.ev_flags, ev_beat=loop.ev_beat, lead_tok=loop.lead_tok, lead_off=loop.lead_off, params=self.params,
+                          state=self.state, seq=self.seq_pp[0], segs=self.segs_pp[0], tok_out=self.tok, seg_out=self.segv, running=self.running)
+        self.scores_pp = self.arch_scores = None
+        if loop.score_tables is not None:                       # the first loop's recorded draws travel with the token rows
+            self.scores_pp = [{k: t[sel].contiguous() for k, t in loop.score_tables.items()}, ops.draw_score_tables(self.seq_pp[1])]
+            self.arch_scores = ops.draw_score_tables(self.arch_tok)
+            self.score_tables = self.scores_pp[0]
+
+    def one_step(self):
+        self.grammar()
+        self.eng.step(self.tok, self.segv, dev_pos=True, logits_out=self.logits)
+
+    _live = AccompanimentLoop._live
+
+    def _phase_table(self):
+        """The phase's uniforms, into the table the block points to."""
+        gen = torch.Generator(device=self.dev)
+        gen.manual_seed((self.seed * 0x9E3779B1 + REBASE_TAG * 0x85EBCA6B + self.phases) & 0x7FFFFFFFFFFFFFFF)
+        self.U.copy_(torch.rand(self.U.shape, device=self.dev, generator=gen))
+
+    def phase(self, use_graph=True, steps_per_graph=None):
+        """One rebase, prefill and in-window run -> whether a row went on (False: no row was at WINDOW, or none could be re-anchored)."""
+        src, dst = self.cur, 1 - self.cur
+        saved = (self.state.clone(), self.params.clone(), self.arch_len.clone())
+        while True:
+            t0 = time.perf_counter()
+            self.running.zero_()
+            sc = self.scores_pp
+            ops.acc_rebase(self.seq_pp[src], self.segs_pp[src], self.state, self.params, self.primer_len, self.loop.track_leadsheet,
+                           self.keep, self.W, self.loop.longest_bar, self.loop.pad, self.seq_pp[dst], self.segs_pp[dst], self.arch_tok, self.arch_len,
+                           self.new_len, self.running, scores=sc and sc[src], dst_scores=sc and sc[dst], arch_scores=self.arch_scores)
+            nl = self.new_len.cpu().numpy()                     # (synchronises: once per phase)
+            t1 = time.perf_counter()
+            self.seconds['rebase'] += t1 - t0
+            if int(nl.max()) == 0:
+                return False
+            lmax = int(nl.max())
+            self.logits.copy_(self.eng.prefill(self.seq_pp[dst][:, :lmax].contiguous(), self.segs_pp[dst][:, :lmax].contiguous(),
+                                               lens=self.new_len.clamp(min=1)))
+            self.eng.pos_auto = True
+            self._phase_table()
+            ops.block_set(self._gargs, self._gheld, seq=self.seq_pp[dst], segs=self.segs_pp[dst], **(sc[dst] if sc else {}))
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            self.seconds['prefill'] += t2 - t1
+            try:
+                pos = self._replay(lmax, self.bound, use_graph, steps_per_graph)
+                if self._live() > 0:
+                    self.grammar()
+                torch.cuda.synchronize()
+                break
+            except _GaveUp as e:
+                if not self.persistent:
+                    raise
+                print('[gen] %s -> the phase again on the chain of launches' % e)
+                for t, s in zip((self.state, self.params, self.arch_len), saved):
+                    t.copy_(s)
+                self.persistent = False
+                self.eng = AccompanimentLoop._make_engine(self, self.m0, False, False)
+        t3 = time.perf_counter()
+        self.seconds['replay'] += self.replayed[1]
+        self.seconds['capture'] += t3 - t2 - self.replayed[1]
+        self.steps += pos - lmax
+        self.prefill_tokens.append(int(nl.sum()))
+        for j in range(self.m0):
+            if nl[j] > 0:
+                self.home[j] = dst
+                self.rebased[j] += 1
+        self.cur = dst
+        if sc:
+            self.score_tables = sc[dst]
+        self.phases += 1
+        # a row still RUNNING stopped at the bound of the longest row: it is re-anchored with it
+        status = self.state[:, ACC_S_STATUS]
+        status.masked_fill_(status == ACC_RUNNING, ACC_WINDOW)
+        return True
+
+    def run(self, use_graph=True, steps_per_graph=None, max_phases=None):
+        """Phases until no row is at WINDOW (or `max_phases` phases have run: benchmarks)."""
+        with scoring.eval_mode(self.model), torch.no_grad():
+            while max_phases is None or self.phases < max_phases:
+                if not (self.state[:, ACC_S_STATUS] == ACC_WINDOW).any().item() or not self.phase(use_graph, steps_per_graph):
+                    break
+
+    def accepted_draws(self):
+        return int(self.state[:, ACC_S_ACCEPTED].sum().item()) - self.accepted0
+
+    def _stitched(self, rows_pp, archive, dtype):
+        """Per stream primer + archive + context, from the buffers of rows_pp by self.home."""
+        state, alen, P = self.state.cpu().numpy(), self.arch_len.cpu().numpy(), self.primer_len.cpu().numpy()
+        host = [t.cpu().numpy() for t in rows_pp]
+        arch = archive.cpu().numpy()
+        out = []
+        for j in range(self.m0):
+            row, ln = host[self.home[j]][j], int(state[j, ACC_S_LEN])
+            out.append(np.array(rebase_stitch(row[:P[j]], arch[j, :alen[j]], row[P[j]:ln]), dtype=dtype))
+        return out
+
+    def results(self):
+        """Per WINDOW stream, in the order of self.idx, what _Stream.result() gives (or an EmoError, as AccompanimentLoop.results)."""
+        status = self.state[:, ACC_S_STATUS].cpu().numpy()
+        out = []
+        for j, (i, ids) in enumerate(zip(self.idx, self._stitched(self.seq_pp, self.arch_tok, np.int64))):
+            if status[j] == ACC_BAR_TOO_LONG:
+                out.append(EmoError('generate_accompaniments: stream %d: a bar longer than the window' % i))
+                continue
+            out.append(_stream_result(int(status[j]), [int(t) for t in ids], 'stream %d used all %d uniforms of a rebase phase\'s table' % (i, self.U.shape[0]),
+                                      'stream %d: token row, archive or lead-sheet table too short past the window' % i,
+                                      'stream %d still running after %d rebase phases' % (i, self.phases)))
+        return out
+
+    def score_arrays(self, tables=None):
+        """-> {'logp', 'rank', 'entropy'}: [m0, longest piece] host arrays stitched like results() (sentinels behind a piece's end)."""
+        if self.scores_pp is None:
+            raise EmoError('RebaseLoop.score_arrays(): the first loop was built without scores=True')
+        out = {}
+        for k in ('logp', 'rank', 'entropy'):
+            fill, dt = (-1, np.int32) if k == 'rank' else (np.nan, np.float32)
+            rows = self._stitched([t['tok_' + k] for t in self.scores_pp], self.arch_scores['tok_' + k], dt)
+            a = np.full((self.m0, max(len(r) for r in rows)), fill, dtype=dt)
+            for j, r in enumerate(rows):
+                a[j, :len(r)] = r
+            out[k] = a
+        return out
+
+
 def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, max_events=10000, skip_check=False, max_bars=None, temp=1.2, top_p=0.9,
                             inadmissibles=None, seed=0, use_graph=True, best_of=1, window='host', best_by='forward', return_scores=False, slots=None,
-                            banned=None):
+                            banned=None, rebase_keep=None):
     """The throughput path of generate_conditional_batch: the same arguments (no per-stream samplers) and result per stream, every draw and
     the grammar of _Stream.offer on the device (emo_grammar_step), each token step = grammar launch + one engine step (the one-launch
     persistent step where the engine has one), k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS, default 16) and replayed until
@@ -1289,6 +1568,17 @@ def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, m
     frees its slot and is finished after the queue has drained, by `window` as above.  Refused (EmoError) when the model's positional table has
     fewer rows than the window.  The results, best_of, best_by and return_scores are per job as they are per stream.
 
+    window = 'rebase' (rebase_keep = None: max_dec_inp_len // 2, read at call time): a stream that fills the window drops its oldest whole bars,
+    keeps its primer and goes on from a context of at most rebase_keep tokens with positions from 0 (RebaseLoop, rebase_plan): one prefill per
+    phase, then the cached one-token step again, instead of a full-window forward per draw.  This is the context the reference's dataloader
+    trains on (the piece's opening events followed by the piece from a bar on); it is NOT the reference's sliding window, so past a stream's
+    first hand-off the ids are neither those of window = 'host' nor of 'device'.  Up to the hand-off they are.  The continuation obeys the
+    same grammar, keeps the stream's ban, temp and top_p, its bar, position, failed and accepted counts and the whole-piece max_events, and
+    draws from per-phase uniform tables seeded with (seed, REBASE_TAG, phase).  A stream whose last bar alone does not fit below the window
+    holds an EmoError ("a bar longer than the window").  ValueError, before anything is allocated, unless len(primer) + 2 <= rebase_keep <=
+    max_dec_inp_len - longest lead-sheet bar - 2, or when rebase_keep is given with another window.  best_of, best_by, return_scores, banned,
+    per-stream temp / top_p and slots work as with window = 'device'.
+
     banned: the device form of the host loops' `inadmissibles` (which stays refused here: its one index array for all streams is not what the
     launch reads).  None: no ban; one sequence of token ids: no lead sheet's stream ever DRAWS one of them; or one entry per lead sheet, each
     a sequence of ids or None.  The grammar launch reads a banned token's logit as -inf (emo_hip.h: tok_mask), so the ids are those of the
@@ -1298,9 +1588,17 @@ def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, m
     device loop at the window keeps them: as `inadmissibles`, temp and top_p of _resume_windowed (window = 'host'), in the WindowedLoop's block
     (window = 'device').  ValueError, before anything is allocated, for an id outside [0, V), a ban that leaves no token, a per-input list of
     the wrong length, a temp <= 0 or a top_p outside (0, 1]."""
-    if window not in ('host', 'device'):
-        raise ValueError("window must be 'host' or 'device' (got %r)" % (window,))
+    if window not in ('host', 'device', 'rebase'):
+        raise ValueError("window must be 'host', 'device' or 'rebase' (got %r)" % (window,))
+    if rebase_keep is not None and window != 'rebase':
+        raise ValueError("rebase_keep goes with window='rebase' (got window=%r)" % (window,))
     _refuse(model, inadmissibles)
+    if window == 'rebase':
+        rebase_keep = check_rebase_keep(rebase_keep, int(max_dec_inp_len), max([len(p) for p in primers] or [0]),
+                                        max([len(b) for lead in lead_sheets for b in lead] or [0]))
+        if getattr(model, 'use_pe', False) and model.pe.pe.shape[0] < int(max_dec_inp_len):       # (RebaseLoop's refusal, before the first loop runs)
+            raise EmoError("generate_accompaniments(window='rebase'): the positional table has %d rows, fewer than the window of %d tokens"
+                           % (model.pe.pe.shape[0], int(max_dec_inp_len)))
     best_of, by_draws, want, lead_sheets, primers = scoring.best_of_plan(best_of, best_by, return_scores, lead_sheets, primers)
     if slots is not None:
         try:
@@ -1328,7 +1626,7 @@ def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, m
             print('[gen] %s -> the batch again on the chain of launches' % e)
             loop = make(persistent=False, redraw=False)
             loop.run(use_graph=use_graph)
-        out = loop.results(event2idx, idx2event, max_events, skip_check, seed, window=window)
+        out = loop.results(event2idx, idx2event, max_events, skip_check, seed, window=window, rebase_keep=rebase_keep, use_graph=use_graph)
         sc = loop.scores(out) if want else None
         picks = None
         if best_of > 1:
@@ -1370,8 +1668,11 @@ def parse_args(argv=None):
     ap.add_argument('--seed', type=int, default=0, help='--device: seed of the uniform table (the group of streams j uses seed + j)')
     ap.add_argument('--best-of', dest='best_of', type=int, default=1,
                     help='--device: candidates generated per lead sheet; the one with the lowest mean negative log-probability is written')
-    ap.add_argument('--window', choices=['host', 'device'], default='host',
-                    help='--device: streams past the %d-token window are finished one at a time on the host, or together on the device' % max_dec_inp_len)
+    ap.add_argument('--window', choices=['host', 'device', 'rebase'], default='host',
+                    help='--device: streams past the %d-token window are finished one at a time on the host, together on the device, or (rebase) '
+                         're-anchored on a bar and continued with cached one-token steps' % max_dec_inp_len)
+    ap.add_argument('--rebase-keep', dest='rebase_keep', type=int, default=None, metavar='N',
+                    help='--window rebase: the largest context a re-anchored stream starts from (default: half the window)')
     ap.add_argument('--best-by', dest='best_by', default='forward', choices=['forward', 'draws'],
                     help='--best-of: rank the candidates by a scoring forward over the finished pieces, or by the log-probabilities recorded at each draw')
     ap.add_argument('--slots', type=int, default=None,
@@ -1389,8 +1690,10 @@ def parse_args(argv=None):
         args.tempo_tolerance = 20
     if args.best_of < 1 or (args.best_of > 1 and not args.device):
         ap.error('--best-of needs --device and a count of at least 1')
-    if args.window == 'device' and not args.device:
-        ap.error('--window device needs --device')
+    if args.window != 'host' and not args.device:
+        ap.error('--window %s needs --device' % args.window)
+    if args.rebase_keep is not None and args.window != 'rebase':
+        ap.error('--rebase-keep goes with --window rebase')
     if args.best_by != 'forward' and args.best_of < 2:
         ap.error('--best-by goes with --best-of N, N > 1')
     if args.scores and not args.device:
@@ -1446,13 +1749,13 @@ def main(argv=None):
             gen, _, picks, *sc = generate_accompaniments(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group],
                                                          max_bars=args.max_bars, temp=temp, top_p=top_p, seed=args.seed + j, best_of=args.best_of,
                                                          window=args.window, best_by=args.best_by, return_scores=want, slots=args.slots,
-                                                         banned=ban)
+                                                         banned=ban, rebase_keep=args.rebase_keep)
             for g, p in zip(group, picks):
                 print('[info] %s: candidate %d of %s' % (g[0], p['chosen'], ['%.4f' % x for x in p['nll_mean']]))
         elif args.device:
             gen, _, *sc = generate_accompaniments(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
                                                   temp=temp, top_p=top_p, seed=args.seed + j, window=args.window, return_scores=want, slots=args.slots,
-                                                  banned=ban)
+                                                  banned=ban, rebase_keep=args.rebase_keep)
         else:
             gen = generate_conditional_batch(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
                                              temp=temp, top_p=top_p, seeds=list(range(i, i + len(group))),

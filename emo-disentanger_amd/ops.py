@@ -14,7 +14,7 @@ from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, ATTN_BWD, ATTN_BW
                    dtype_code, lib, ptr, stream)
 
 __all__ = ['gemm', 'colsum', 'embed_fwd', 'embed_bwd', 'layernorm_fwd', 'layernorm_bwd', 'dropout_apply', 'favor_attn_fwd',
-           'favor_attn_bwd', 'favor_decode_step', 'decode_step', 'decode_step_set', 'block_set', 'DecodeStep', 'GrammarStep', 'grammar_step', 'draw_score_tables', 'favor_draw_omega', 'favor_state_reset', 'softmax_attn_fwd', 'softmax_attn_bwd', 'softmax_attn_decode', 'relpos_attn_fwd', 'relpos_attn_bwd', 'relpos_attn_decode', 'xent_fwd',
+           'favor_attn_bwd', 'favor_decode_step', 'decode_step', 'decode_step_set', 'block_set', 'DecodeStep', 'GrammarStep', 'grammar_step', 'draw_score_tables', 'favor_draw_omega', 'favor_state_reset', 'favor_state_at', 'acc_rebase', 'softmax_attn_fwd', 'softmax_attn_bwd', 'softmax_attn_decode', 'relpos_attn_fwd', 'relpos_attn_bwd', 'relpos_attn_decode', 'xent_fwd',
            'xent_bwd', 'token_scores', 'xent_bwd_rows', 'argmax', 'sample_nucleus', 'sample_nucleus_step', 'txl_grammar_step', 'txl_queue_step', 'acc_grammar_step', 'acc_queue_step', 'acc_window_step', 'accuracy_counts', 'sumsq', 'clip_coef', 'adam_step', 'cast', 'add_bias2',
            'ACT_NONE', 'ACT_RELU', 'ACT_GELU_NEW', 'ACT_GELU', 'MUL_NONE', 'MUL_NONZERO', 'MUL_DGELU_NEW', 'MUL_DGELU', 'MUL_BITMASK', 'gemm_bitmask_ok', 'gemm_lna_ok', 'bitmask_rows', 'favor_bwd_dn_ok', 'ffn_fwd', 'ffn_fwd_ok']
 
@@ -470,6 +470,23 @@ def favor_state_reset(state_table, n_rows, s_row_floats, z_row_floats, row_reset
     check(lib.emo_favor_state_reset(ptr(state_table), state_table.shape[0], n_rows, s_row_floats, z_row_floats, ptr(row_reset), stream()))
 
 
+def favor_state_at(k, v, omega, lens, B, T, H, out=None):
+    """The FAVOR+ recurrent state of every row at its own length (emo_hip.h: emo_favor_state_at).  k, v: [B*T, H*dh] (row-strided views allowed),
+    lens int32 [B] on the device, 1 <= lens[b] <= T -> (S f32 [B, H, n_feat, dh], z f32 [B, H, n_feat]); out = (S, z): written in place.
+    Allocation-free with `out`."""
+    HD = k.shape[1]
+    dh, n_feat = HD // H, 2 * omega.shape[1]
+    assert k.shape == v.shape and k.shape[0] == B * T and k.dtype == v.dtype and _rows(k) == _rows(v)
+    assert omega.shape[0] == dh and omega.dtype == _F32 and omega.is_contiguous()
+    assert _is(lens, _I32) and lens.numel() == B
+    if out is None:
+        out = (torch.empty(B, H, n_feat, dh, device=k.device, dtype=_F32), torch.empty(B, H, n_feat, device=k.device, dtype=_F32))
+    S, z = out
+    assert _is(S, _F32) and S.shape == (B, H, n_feat, dh) and _is(z, _F32) and z.shape == (B, H, n_feat)
+    check(lib.emo_favor_state_at(ptr(k), ptr(v), _rows(k), dtype_code(k.dtype), ptr(omega), ptr(lens), ptr(S), ptr(z), B, T, H, dh, n_feat, stream()))
+    return S, z
+
+
 def softmax_attn_fwd(q, k, v, B, T, H, p_drop=0.0, seed=0, offset=0, want_keep=False):
     """want_keep: also return the dropout keep words for softmax_attn_bwd (None when the call has none: include/emo_hip.h)."""
     M, HD = q.shape
@@ -769,6 +786,33 @@ def acc_window_step(logits, temperature, top_p, u_steps, rows, ev_flags, ev_beat
                   state=state, seq=seq, segs=segs, win_tok=win_tok, win_seg=win_seg, running=running, tok_logp=tok_logp, tok_rank=tok_rank,
                   tok_entropy=tok_entropy)
     return win_tok
+
+
+def acc_rebase(seq, segs, state, params, primer_len, track_leadsheet, keep, W, longest_bar, pad, dst_seq, dst_segs, arch_tok, arch_len, new_len, running,
+               scores=None, dst_scores=None, arch_scores=None):
+    """Re-anchor the WINDOW rows on a bar (include/emo_hip.h: emo_acc_rebase): seq / segs int64 [n, width] -> dst_seq / dst_segs int64 [n, width2]
+    (other buffers), state / params int32 [n, 8] updated in place, primer_len int32 [n], arch_tok int64 [n, cap] with its cursors arch_len int32
+    [n], new_len int32 [n], running int32 [1] (+= 1 per row that continues).  scores / dst_scores / arch_scores: the three tables of
+    draw_score_tables laid out like seq / dst_seq / arch_tok (dicts with its keys), all three or none.  Allocation-free."""
+    n, width = seq.shape
+    assert _is(seq, _I64) and _is(segs, _I64) and segs.shape == seq.shape
+    assert _is(dst_seq, _I64) and _is(dst_segs, _I64) and dst_seq.shape[0] == n and dst_segs.shape == dst_seq.shape
+    assert _is(state, _I32) and state.shape == (n, ACC_STATE_WORDS) and _is(params, _I32) and params.shape == (n, ACC_PARAM_WORDS)
+    assert _is(primer_len, _I32) and primer_len.numel() == n and _is(arch_len, _I32) and arch_len.numel() == n
+    assert _is(arch_tok, _I64) and arch_tok.dim() == 2 and arch_tok.shape[0] == n
+    assert _is(new_len, _I32) and new_len.numel() == n and _is(running, _I32) and running.numel() >= 1
+    a = _lib.AccRebase(n_rows=n, seq=ptr(seq), segs=ptr(segs), ld_seq=width, state=ptr(state), params=ptr(params), primer_len=ptr(primer_len),
+                       track_leadsheet=int(track_leadsheet), keep=int(keep), window=int(W), longest_bar=int(longest_bar), pad=int(pad),
+                       dst_seq=ptr(dst_seq), dst_segs=ptr(dst_segs), ld_dst=dst_seq.shape[1], arch_tok=ptr(arch_tok), arch_len=ptr(arch_len),
+                       ld_arch=arch_tok.shape[1], new_len=ptr(new_len), running=ptr(running))
+    for t, like, pre in ((scores, seq, 'tok_'), (dst_scores, dst_seq, 'dst_'), (arch_scores, arch_tok, 'arch_')):
+        assert (t is None) == (scores is None), 'acc_rebase: the score tables come as sources, destinations and archives, or not at all'
+        for key, dt in (('logp', _F32), ('rank', _I32), ('entropy', _F32)):
+            if t is not None:
+                assert _is(t['tok_' + key], dt) and t['tok_' + key].shape == like.shape
+                setattr(a, pre + key, ptr(t['tok_' + key]))
+    check(lib.emo_acc_rebase(ctypes.byref(a), stream()))     # (the block lives for this call: the library reads it at call time)
+    return new_len
 
 
 def accuracy_counts(logits, tgt, chord, melody, pad):

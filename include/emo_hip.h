@@ -427,6 +427,17 @@ int emo_favor_draw_omega(const float* gauss, float* omega, int64_t n_layers, int
  * that are not flagged are not touched.  Graph-capturable; nothing is allocated. */
 int emo_favor_state_reset(const void* state_table, int64_t n_layers, int64_t n_rows, int64_t s_row_floats, int64_t z_row_floats,
                           const int32_t* row_reset, emo_stream_t stream);
+/* The FAVOR+ recurrent state of every row AT ITS OWN LENGTH (no reference counterpart: the state a decode row continues from after a prefill of rows
+ * of different lengths, inference prefill(lens=)).  k, v: [B*T, H*dh] views with the row stride ld (elements; rows 16-byte aligned), dtype EMO_F32 or
+ * EMO_BF16; omega f32 [dh, n_feat/2]; lens int32 [B] on the device, 1 <= lens[b] <= T (a value outside [0, T] is clamped: nothing outside the row is
+ * read).  Per (b, h):  state_S[b,h] = sum_{t < lens[b]} phi(k_t) (x) v_t  (f32 [B,H,n_feat,dh]),  state_z[b,h] = sum_{t < lens[b]} phi(k_t)  (f32
+ * [B,H,n_feat]), phi the forward's feature map (the same device function, scaling, offset and omega image) and the products on the forward's route for
+ * the dtype (bf16 operands into v_mfma_f32_16x16x32_bf16 with f32 accumulation; exact f32 on v_mfma_f32_16x16x4_f32), so the state has the error class
+ * of the FWD pass's state_S / state_z.  A masked reduction over tiles of 32 tokens, one workgroup per (b, h): tokens at t >= lens[b] are never loaded
+ * and contribute exact zeros, whatever they hold (a tile that straddles lens[b] is masked by element, not skipped).  Built for the (d_head, n_feat)
+ * rows of the FAVOR kind of emo_attn.  Graph-capturable; nothing is allocated. */
+int emo_favor_state_at(const void* k, const void* v, int64_t ld, int dtype, const float* omega, const int32_t* lens, float* state_S, float* state_z,
+                       int64_t B, int64_t T, int64_t H, int64_t dh, int64_t n_feat, emo_stream_t stream);
 
 /* ------------------------------------------------------------------ K9: cross-entropy with ignore_index
  * Replaces F.cross_entropy in compute_loss (model/music_performer.py:72-81).
@@ -515,6 +526,7 @@ enum { EMO_ACC_S_STATUS = 0, EMO_ACC_S_LEN = 1 /* tokens in seq[r] */, EMO_ACC_S
        EMO_ACC_S_BARS = 3 /* generated_bars */, EMO_ACC_S_CUR_POS = 4, EMO_ACC_S_FAILED = 5 /* rejected Beats in a row */, EMO_ACC_S_DRAWS = 6,
        EMO_ACC_S_ACCEPTED = 7 /* accepted draws */, EMO_ACC_STATE_WORDS = 8 };
 enum { EMO_ACC_RUNNING = 0, EMO_ACC_DONE = 1, EMO_ACC_STUCK = 2, EMO_ACC_WINDOW = 3, EMO_ACC_OUT_OF_DRAWS = 4, EMO_ACC_OVERFLOW = 5 };
+enum { EMO_REBASE_BAR_TOO_LONG = 6 };   /* a further value of state[STATUS], written by emo_acc_rebase alone: no grammar step ever writes it, all read it as finished */
 enum { EMO_ACC_EV_BEAT = 1, EMO_ACC_EV_TRACK_LS = 2, EMO_ACC_EV_PAD = 4, EMO_ACC_EV_EOS = 8 };
 /* EMO_GRAMMAR_ACC_WINDOW.  The same draw and grammar for streams PAST the window (stage2_accompaniment/inference.py:252-277: the model input is the last max_dec_inp_len
  * tokens of `generated`, positions restarting at 0 on every step, so nothing is fed token by token and an injected bar is simply part of the next
@@ -646,6 +658,55 @@ int emo_grammar_step_size(void);
 /* Messages name the kind: "emo_grammar_step[txl]: ", "emo_grammar_step[acc]: ", "emo_grammar_step[acc_window]: ", "emo_grammar_step[txl_queue]: ",
  * "emo_grammar_step[acc_queue]: ". */
 int emo_grammar_step(const emo_grammar_step_t* args, emo_stream_t stream);
+/* Re-anchor the streams that filled the window on a bar (no reference counterpart past the window: the reference slides the window token by token,
+ * stage2_accompaniment/inference.py:252-257; this is the context its dataloader builds, dataloader.py:179-186: the piece's opening events followed by the
+ * piece from a bar on, positions from 0).  One launch per phase, one 512-thread workgroup per row r of seq / segs (int64 [n_rows, ld_seq]), state / params
+ * (int32 [n_rows, 8], the ACC layout) and primer_len (int32 [n_rows]: the row is primer_len[r] primer ids followed by bars that each open with
+ * track_leadsheet).  For a row with state[STATUS] == EMO_ACC_WINDOW, n = state[LEN], P = primer_len[r]:
+ *   b = the smallest i >= P with seq[i] == track_leadsheet and P + (n - i) <= keep; when no bar start fits, the last bar start, provided
+ *       P + (n - b) <= window - longest_bar - 2; otherwise state[STATUS] = EMO_REBASE_BAR_TOO_LONG, new_len[r] = 0 and nothing else is written
+ *       (inference.rebase_plan is the same rule on the host);
+ *   dst_seq / dst_segs[r, 0 .. ld_dst) (int64 [n_rows, ld_dst], buffers other than seq / segs) = primer + seq / segs[b .. n), then pad / segment 1;
+ *   the archive (arch_tok int64 [n_rows, ld_arch], arch_len int32 [n_rows], a cursor per row) takes seq[P .. b) at its cursor, which advances by b - P;
+ *   with the score tables (tok_logp / tok_rank / tok_entropy [n_rows, ld_seq]; dst_* [n_rows, ld_dst]; arch_* [n_rows, ld_arch]: all nine or none) the
+ *   same columns move with the tokens, and the destination cells behind the new length get the sentinels NaN / -1 / NaN;
+ *   state: STATUS = RUNNING, LEN = CONSUMED = new_len = P + n - b, DRAWS = 0, the other words kept (bars, position, failed and accepted counts);
+ *   params[MAX_EVENTS] -= b - P (the reference's whole-piece limit len(generated) > max_events, in the new row's indices); new_len[r] = the new
+ *   length (int32 [n_rows]); *running (int32 [1]) += 1.
+ * A row the archive or the destination cannot hold, or with a length outside its row, ends with EMO_ACC_OVERFLOW and new_len 0.  Any other row:
+ * new_len[r] = 0 and nothing else is touched.  Requires 0 < keep <= window - longest_bar - 2 and window <= ld_dst.  Graph-capturable; nothing is allocated. */
+typedef struct {
+    int64_t n_rows;            /* workgroups launched: the rows of every table below */
+    const int64_t* seq;        /* int64 [n_rows, ld_seq]: the rows as the last phase left them (never written) */
+    const int64_t* segs;       /* int64 [n_rows, ld_seq] */
+    int64_t ld_seq;
+    int32_t* state;            /* int32 [n_rows, 8], the ACC layout: read, and rewritten for the rows that go on or end here */
+    int32_t* params;           /* int32 [n_rows, 8]: MAX_EVENTS is lowered by the tokens dropped */
+    const int32_t* primer_len; /* int32 [n_rows] */
+    int64_t track_leadsheet, keep, window, longest_bar, pad;   /* 0 < keep <= window - longest_bar - 2 */
+    int64_t* dst_seq;          /* int64 [n_rows, ld_dst], ld_dst >= window: the new contexts */
+    int64_t* dst_segs;         /* int64 [n_rows, ld_dst] */
+    int64_t ld_dst;
+    int64_t* arch_tok;         /* int64 [n_rows, ld_arch]: the dropped tokens of every row, in order */
+    int32_t* arch_len;         /* int32 [n_rows]: the archive cursors */
+    int64_t ld_arch;
+    /* the score tables of emo_grammar_step_t, all nine or none (NULL) */
+    const float* tok_logp;     /* f32 [n_rows, ld_seq] */
+    const int32_t* tok_rank;   /* int32 [n_rows, ld_seq] */
+    const float* tok_entropy;  /* f32 [n_rows, ld_seq] */
+    float* dst_logp;           /* f32 [n_rows, ld_dst] */
+    int32_t* dst_rank;         /* int32 [n_rows, ld_dst] */
+    float* dst_entropy;        /* f32 [n_rows, ld_dst] */
+    float* arch_logp;          /* f32 [n_rows, ld_arch] */
+    int32_t* arch_rank;        /* int32 [n_rows, ld_arch] */
+    float* arch_entropy;       /* f32 [n_rows, ld_arch] */
+    int32_t* new_len;          /* int32 [n_rows]: written for every row */
+    int32_t* running;          /* int32 [1]: += 1 per row that goes on */
+} emo_acc_rebase_t;
+/* sizeof(emo_acc_rebase_t) as the library was built (a binding checks its mirror against it, as with emo_grammar_step_size) */
+int emo_acc_rebase_size(void);
+/* The block is read at call time, as emo_grammar_step_t is. */
+int emo_acc_rebase(const emo_acc_rebase_t* args, emo_stream_t stream);
 /* counts[0..5] += {nonpad, nonpad&correct, chord, chord&correct, melody, melody&correct} (train.py:184-193) */
 int emo_accuracy_counts(const float* logits, const int64_t* tgt, const int64_t* chord,
                         const int64_t* melody, int64_t M, int64_t V, int64_t pad, int64_t* counts,
