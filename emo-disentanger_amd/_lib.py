@@ -47,6 +47,7 @@ class GrammarStep(ctypes.Structure):
                 ('u_steps', c_p), ('n_u', c_l), ('ld_u', c_l), ('ev_flags', c_p), ('ev_beat', c_p), ('params', c_p), ('state', c_p),
                 ('seq', c_p), ('ld_seq', c_l), ('running', c_p),
                 ('key_temperature', c_f), ('key_top_p', c_f), ('tok_out', c_p), ('seg_out', c_p), ('max_len', c_l), ('pad', c_l),
+                ('guide_cond', c_p), ('guide_uncond', c_p), ('guide_scale', c_p),
                 ('segs', c_p), ('lead_tok', c_p), ('lead_off', c_p), ('track_full', c_l), ('window', c_l), ('rows', c_p), ('win_tok', c_p), ('win_seg', c_p),
                 ('slot_job', c_p), ('queue_head', c_p), ('n_jobs', c_l), ('mem_lens', c_p), ('mem_rows', c_l), ('job_steps', c_p),
                 ('tok_mask', c_p), ('n_masks', c_l), ('mask_of', c_p), ('temp_of', c_p), ('top_p_of', c_p), ('row_reset', c_p),

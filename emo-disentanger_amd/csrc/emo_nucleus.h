@@ -9,7 +9,8 @@
 // its lowest indices here and an arbitrary subset of the same size there.  tests/test_gpu_sampling.py pins the rule and holds this header to a
 // float64 restatement (tests/nucleus_ref.py) with derived rounding bounds.
 // The logits are read through an accessor (emo_nucleus_draw_from): emo_plain_logits is the load itself, emo_banned_logits reads a banned token's
-// logit as -INFINITY and leaves the arithmetic alone, so a draw under a ban is bit for bit the plain draw from a row overwritten that way.
+// logit as -INFINITY and leaves the arithmetic alone, so a draw under a ban is bit for bit the plain draw from a row overwritten that way;
+// emo_guided_logits combines two rows (classifier-free guidance), bit for bit the plain draw from the row a float32 host combination writes.
 #pragma once
 #include "emo_common.h"
 
@@ -66,6 +67,24 @@ struct emo_banned_logits {
     const float* __restrict__ row;
     const uint32_t* __restrict__ ban;
     __device__ __forceinline__ float operator()(int c) const { return (ban && ((ban[c >> 5] >> (c & 31)) & 1u)) ? -INFINITY : row[c]; }
+};
+// Classifier-free guidance: l(c) = lc + s * (lc - lu) over a conditioned and an unconditioned row, as __fadd_rn(lc, __fmul_rn(s, __fsub_rn(lc,
+// lu))): THREE separately rounded fp32 operations.  Those intrinsics are plain operators in this toolchain, which the default contraction may
+// fuse after inlining, so the operators stand here themselves with contraction switched off: NumPy's float32 `lc + s * (lc - lu)` is then the
+// same row bit for bit.  The ban is applied after the combination (no inf - inf arises from it); s = 0 is the conditioned row itself.
+struct emo_guided_logits {
+    const float* __restrict__ cond;
+    const float* __restrict__ uncond;
+    float scale;
+    const uint32_t* __restrict__ ban;
+    __device__ __forceinline__ float operator()(int c) const {
+#pragma clang fp contract(off)
+        if (ban && ((ban[c >> 5] >> (c & 31)) & 1u)) return -INFINITY;
+        const float lc = cond[c];
+        const float d = lc - uncond[c];
+        const float m = scale * d;
+        return lc + m;
+    }
 };
 
 // tid in [0, 512); `sync` = a barrier over exactly the calling threads (+ any others that call it the same number of times).  Returns the picked

@@ -22,16 +22,22 @@
 // All kinds, optional sampling controls (tok_mask / mask_of / temp_of / top_p_of, indexed by the stream r as params is: emo_grammar_controls): a
 // banned token's logit is read as -inf by the draw and by nothing else: the scores above are still the model's, from the row as it wrote it, and
 // primer tokens, injected bars and track_full are fed whether banned or not.
+// Kind ACC, optional classifier-free guidance (guide_cond / guide_uncond / guide_scale: emo_hip.h): a guided piece is two rows of the batch, a
+// leader on the conditioned primer and a follower on the unconditioned one.  Both workgroups draw from the same combination of the same two
+// logits rows with the same uniform and run the same grammar, so the follower stays token for token with its leader and no workgroup reads or
+// writes another's state; the scores stay those of each row's own logits.
 #include "emo_grammar.h"
 
 namespace {
 
 // The draws of one launch of one stream, shared by the in-window and the windowed step: draw until the grammar accepts or ends the stream.
 // `draws` advances in every thread alike, and thread 0 runs the grammar on the LDS copy of the state (kept there, not in registers, across the
-// draws); it alone gets the status back (the other threads: RUNNING).  Besides the block, what differs per call: lr the stream's logits row,
-// u_col its column of the uniform table (pitch a.ld_u), row / srow its token and segment rows, ctl its sampling controls (emo_grammar_controls:
-// the ban reaches the first draw's sort, which the redraws reuse; the scores are taken from lr as the model wrote it).
-__device__ __forceinline__ int32_t acc_draw(const emo_grammar_step_t& a, const emo_grammar_controls_t ctl, const float* __restrict__ lr, const float* __restrict__ u_col,
+// draws); it alone gets the status back (the other threads: RUNNING).  Besides the block, what differs per call: l the accessor of the stream's
+// logits (emo_nucleus.h: its row under its ban, or the guided combination of two rows), u_col its column of the uniform table (pitch a.ld_u),
+// row / srow its token and segment rows, ctl its sampling controls (emo_grammar_controls: the ban is the accessor's and reaches the first
+// draw's sort, which the redraws reuse; the scores are taken by the caller from the row as the model wrote it).
+template <typename Logits>
+__device__ __forceinline__ int32_t acc_draw(const emo_grammar_step_t& a, const emo_grammar_controls_t ctl, const Logits l, const float* __restrict__ u_col,
                                             int64_t* __restrict__ row, int64_t* __restrict__ srow, const int32_t* spr, int32_t* sst, int32_t* sagain_p,
                                             char* lds, int tid, int32_t& draws) {
     const int64_t V = a.n_token, ld_seq = a.ld_seq;
@@ -46,7 +52,7 @@ __device__ __forceinline__ int32_t acc_draw(const emo_grammar_step_t& a, const e
         // a redraw from the same logits needs only the cut and the pick over the sorted state the first draw left in LDS (the same operations
         // on the same data: the id a fresh emo_nucleus_draw with this uniform would give)
         const float u = u_col[(int64_t)draws * a.ld_u];
-        const int64_t word = draws == draws0 ? emo_nucleus_draw_from(emo_banned_logits{lr, ctl.ban}, V, ctl.temp, ctl.top_p, u, lds, tid, [] { __syncthreads(); })
+        const int64_t word = draws == draws0 ? emo_nucleus_draw_from(l, V, ctl.temp, ctl.top_p, u, lds, tid, [] { __syncthreads(); })
                                             : emo_nucleus_pick(V, ctl.top_p, u, lds, tid, [] { __syncthreads(); });
         ++draws;
         if (tid == 0) {
@@ -112,8 +118,11 @@ __device__ __forceinline__ int32_t acc_draw(const emo_grammar_step_t& a, const e
 // One token step of stream r (kind ACC: a stream of the batch; kind ACC_QUEUE: a job) in batch row b, whose logits row it draws from and whose
 // next input it writes, after emo_grammar_open has brought the stream's words to sst / spr and found it RUNNING.  All 512 threads call it; every
 // barrier inside lies on a path that sst, spr and the launch arguments alone decide.  Thread 0 leaves the stream's state words in memory.
-// CTL: the block has sampling controls (emo_grammar_controls).
-template <bool CTL>
+// CTL: the block has sampling controls (emo_grammar_controls).  GUIDE (kind ACC alone): the block has the three guidance tables; a stream whose
+// pair (guide_cond[r], guide_uncond[r]) is two distinct rows of the batch draws from their combination (emo_guided_logits) with the uniforms of
+// column guide_cond[r], every other stream as without them.  The pair is the same word in every thread, so the barriers stay uniform.  The
+// scores are still taken from the stream's own row b.
+template <bool CTL, bool GUIDE = false>
 __device__ __forceinline__ void acc_stream_step(const emo_grammar_step_t& a, int64_t b, int64_t r, char* lds, int32_t* sst, const int32_t* spr,
                                                 int32_t* sagain, float* sred, int tid) {
     int32_t* st = a.state + r * EMO_ACC_STATE_WORDS;
@@ -141,7 +150,18 @@ __device__ __forceinline__ void acc_stream_step(const emo_grammar_step_t& a, int
     // (read before thread 0 can have touched the state: it writes only behind the barriers of the first draw)
     const bool scores = emo_grammar_wants_scores(a);
     const int32_t len0 = scores ? sst[EMO_ACC_S_LEN] : 0, acc0 = scores ? sst[EMO_ACC_S_ACCEPTED] : 0;
-    const int32_t status = acc_draw(a, emo_grammar_controls<CTL>(a, r), a.logits + b * a.n_token, a.u_steps + r, row, srow, spr, sst, sagain, lds, tid, draws);
+    const emo_grammar_controls_t ctl = emo_grammar_controls<CTL>(a, r);
+    int32_t status;
+    int64_t gc = -1, gu = -1;
+    if constexpr (GUIDE) {
+        gc = a.guide_cond[r];
+        gu = a.guide_uncond[r];
+    }
+    if (GUIDE && gc != gu && gc >= 0 && gc < a.n_rows && gu >= 0 && gu < a.n_rows)
+        status = acc_draw(a, ctl, emo_guided_logits{a.logits + gc * a.n_token, a.logits + gu * a.n_token, a.guide_scale[r], ctl.ban}, a.u_steps + gc, row,
+                          srow, spr, sst, sagain, lds, tid, draws);
+    else
+        status = acc_draw(a, ctl, emo_banned_logits{a.logits + b * a.n_token, ctl.ban}, a.u_steps + r, row, srow, spr, sst, sagain, lds, tid, draws);
     // an acceptance appended its word at the old length (an injected bar follows it) and counted itself, in front of the loop's last barrier
     if (scores && sst[EMO_ACC_S_ACCEPTED] != acc0) emo_grammar_score(a, a.logits + b * a.n_token, r, len0, row[len0], sred, tid);
     if (tid != 0) return;
@@ -160,7 +180,7 @@ __device__ __forceinline__ void acc_stream_step(const emo_grammar_step_t& a, int
     for (int i = 0; i < EMO_ACC_STATE_WORDS; ++i) st[i] = sst[i];
 }
 
-template <bool CTL>
+template <bool CTL, bool GUIDE>
 __global__ __launch_bounds__(512) void acc_grammar_kernel(const emo_grammar_step_t a) {
     __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
     __shared__ int32_t sst[EMO_ACC_STATE_WORDS], spr[EMO_ACC_PARAM_WORDS], sagain;
@@ -175,7 +195,7 @@ __global__ __launch_bounds__(512) void acc_grammar_kernel(const emo_grammar_step
         }
         return;
     }
-    acc_stream_step<CTL>(a, r, r, lds, sst, spr, &sagain, sred, tid);
+    acc_stream_step<CTL, GUIDE>(a, r, r, lds, sst, spr, &sagain, sred, tid);
 }
 
 // Thread 0 of slot b, whose job (if it had one) is over: the next queued job that is RUNNING, or none.  queue_head only grows, so a slot that
@@ -264,7 +284,8 @@ __global__ __launch_bounds__(512) void acc_window_kernel(const emo_grammar_step_
     int32_t draws = sst[EMO_ACC_S_DRAWS];
     const bool scores = emo_grammar_wants_scores(a);         // as in acc_grammar_kernel; the tables are indexed by the stream r, the logits by b
     const int32_t len0 = scores ? sst[EMO_ACC_S_LEN] : 0, acc0 = scores ? sst[EMO_ACC_S_ACCEPTED] : 0;
-    const int32_t status = acc_draw(a, emo_grammar_controls<CTL>(a, r), a.logits + b * a.n_token, a.u_steps + r, row, srow, spr, sst, &sagain, lds, tid, draws);
+    const emo_grammar_controls_t ctl = emo_grammar_controls<CTL>(a, r);
+    const int32_t status = acc_draw(a, ctl, emo_banned_logits{a.logits + b * a.n_token, ctl.ban}, a.u_steps + r, row, srow, spr, sst, &sagain, lds, tid, draws);
     if (scores && sst[EMO_ACC_S_ACCEPTED] != acc0) emo_grammar_score(a, a.logits + b * a.n_token, r, len0, row[len0], sred, tid);
     if (tid == 0) {
         if (status != EMO_ACC_RUNNING) atomicSub(a.running, 1);
@@ -311,8 +332,13 @@ extern "C" int emo_grammar_step(const emo_grammar_step_t* args, emo_stream_t str
     EMO_CHECK(a.temperature > 0.f, "emo_grammar_step[%s]: temperature must be > 0", name);
     // (the <false> instances are the kernels as they were before the sampling controls: a block without any launches those)
     const bool ctl = emo_grammar_has_controls(a);
-    const auto kernel = aq ? (ctl ? acc_queue_kernel<true> : acc_queue_kernel<false>) : acc ? (ctl ? acc_grammar_kernel<true> : acc_grammar_kernel<false>)
-                                                                                            : (ctl ? acc_window_kernel<true> : acc_window_kernel<false>);
+    // (kind ACC alone reads the guidance tables; a block without them launches the <.., false> instance, the kernel as it was before they existed)
+    const int guide = a.kind == EMO_GRAMMAR_ACC ? (a.guide_cond != nullptr) + (a.guide_uncond != nullptr) + (a.guide_scale != nullptr) : 0;
+    EMO_CHECK(guide == 0 || guide == 3, "emo_grammar_step[%s]: guide_cond, guide_uncond and guide_scale come together or not at all", name);
+    const auto kernel = aq       ? (ctl ? acc_queue_kernel<true> : acc_queue_kernel<false>)
+                        : !acc   ? (ctl ? acc_window_kernel<true> : acc_window_kernel<false>)
+                        : guide  ? (ctl ? acc_grammar_kernel<true, true> : acc_grammar_kernel<false, true>)
+                                 : (ctl ? acc_grammar_kernel<true, false> : acc_grammar_kernel<false, false>);
     hipLaunchKernelGGL(kernel, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
     EMO_LAUNCH_CHECK();
     return EMO_OK;

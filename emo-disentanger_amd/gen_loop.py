@@ -45,10 +45,13 @@ def pack_token_masks(bans, V):
 
 class DrawControls:
     """The per-stream sampling controls of a device generation loop, checked: bans[r] (None, or the sorted ids stream r never draws), temps /
-    top_ps (one float per stream, or None where the caller gave one value for all: then `temp` / `top_p`, the launch's scalars, hold)."""
+    top_ps (one float per stream, or None where the caller gave one value for all: then `temp` / `top_p`, the launch's scalars, hold), and the
+    classifier-free guidance pairs guide_cond / guide_uncond / guide_scale (one entry per stream as emo_hip.h lays them out: (-1, -1, 0.0) for a
+    stream without guidance; all three None where no stream is guided)."""
 
-    def __init__(self, n, V, bans, temp, temps, top_p, top_ps):
+    def __init__(self, n, V, bans, temp, temps, top_p, top_ps, guide=None):
         self.n, self.V, self.bans, self.temp, self.temps, self.top_p, self.top_ps = n, V, bans, temp, temps, top_p, top_ps
+        self.guide_cond, self.guide_uncond, self.guide_scale = guide if guide is not None else (None, None, None)
 
     @property
     def temp_arg(self):
@@ -59,25 +62,74 @@ class DrawControls:
     def top_p_arg(self):
         return self.top_p if self.top_ps is None else list(self.top_ps)
 
+    @property
+    def guide_arg(self):
+        """The guidance pairs in the form the loop classes take as `guidance`: (cond, uncond, scale) lists, or None."""
+        return None if self.guide_cond is None else (list(self.guide_cond), list(self.guide_uncond), list(self.guide_scale))
+
     def temp_at(self, r):
         return self.temp if self.temps is None else self.temps[r]
 
     def top_p_at(self, r):
         return self.top_p if self.top_ps is None else self.top_ps[r]
 
+    def guided(self, r):
+        """Whether stream r is one row of a guidance pair."""
+        return self.guide_cond is not None and self.guide_cond[r] >= 0
+
+    def followers(self):
+        """The streams that are the unconditioned row of a pair."""
+        return [] if self.guide_cond is None else [r for r in range(self.n) if self.guide_uncond[r] == r]
+
+    def with_guidance(self, scales):
+        """scales: one float per stream (0: no guidance) -> the controls of these streams followed by one FOLLOWER per guided stream, in their
+        order: a copy of its leader's ban, temp and top_p.  Leader i and its follower g both hold the pair (i, g) and the leader's scale."""
+        lead = [i for i in range(self.n) if scales[i] > 0]
+        if not lead:
+            return self
+        assert self.guide_cond is None, 'with_guidance: the streams are guided already'
+        out = self.take(list(range(self.n)) + lead)
+        cond, unc, sc = [-1] * out.n, [-1] * out.n, [0.0] * out.n
+        for j, i in enumerate(lead):
+            g = self.n + j
+            cond[i], unc[i], sc[i] = cond[g], unc[g], sc[g] = i, g, float(scales[i])
+        out.guide_cond, out.guide_uncond, out.guide_scale = cond, unc, sc
+        return out
+
     def take(self, idx):
         """The controls of the streams `idx` (a list of stream indices, repeats allowed), in that order: candidates of an input under best_of,
-        the streams a windowed loop takes over."""
+        the streams a windowed loop takes over.  Guidance pairs are renumbered: the t-th copy of a stream is paired with the t-th copy of its
+        partner (ValueError when `idx` splits a pair)."""
         pick = lambda v: None if v is None else [v[i] for i in idx]          # noqa: E731
-        return DrawControls(len(idx), self.V, [self.bans[i] for i in idx], self.temp, pick(self.temps), self.top_p, pick(self.top_ps))
+        guide = None
+        if self.guide_cond is not None:
+            where, nth = {}, []
+            for j, i in enumerate(idx):
+                nth.append(len(where.setdefault(i, [])))
+                where[i].append(j)
+
+            def at(o, j):
+                if o < 0:
+                    return -1
+                if o not in where or nth[j] >= len(where[o]):
+                    raise ValueError('DrawControls.take: stream %d is one row of a guidance pair and its partner %d was not taken with it' % (idx[j], o))
+                return where[o][nth[j]]
+
+            guide = ([at(self.guide_cond[i], j) for j, i in enumerate(idx)], [at(self.guide_uncond[i], j) for j, i in enumerate(idx)],
+                     [self.guide_scale[i] for i in idx])
+            if all(c < 0 for c in guide[0]):
+                guide = None
+        return DrawControls(len(idx), self.V, [self.bans[i] for i in idx], self.temp, pick(self.temps), self.top_p, pick(self.top_ps), guide)
 
     def repeat(self, k):
-        """Every stream k times in a row: stream i * k + c has the controls of input i (scoring.best_of_plan's order)."""
+        """Every stream k times in a row: stream i * k + c has the controls of input i (scoring.best_of_plan's order); copy c of a leader is
+        paired with copy c of its follower."""
         return self.take([i for i in range(self.n) for _ in range(k)])
 
     def tables(self):
         """-> the optional fields of emo_grammar_step_t that are present, as numpy: {'tok_mask' uint32 [n_masks, words], 'mask_of' int32 [n]}
-        when a stream has a ban, {'temp_of'} / {'top_p_of'} f32 [n] when the caller gave per-stream values.  {} = every new field NULL."""
+        when a stream has a ban, {'temp_of'} / {'top_p_of'} f32 [n] when the caller gave per-stream values, {'guide_cond', 'guide_uncond' int32
+        [n], 'guide_scale' f32 [n]} when a stream is guided.  {} = every new field NULL."""
         out = {}
         if any(b is not None for b in self.bans):
             out['tok_mask'], out['mask_of'] = pack_token_masks(self.bans, self.V)
@@ -85,6 +137,9 @@ class DrawControls:
             out['temp_of'] = np.array(self.temps, np.float32)
         if self.top_ps is not None:
             out['top_p_of'] = np.array(self.top_ps, np.float32)
+        if self.guide_cond is not None:
+            out['guide_cond'], out['guide_uncond'] = np.array(self.guide_cond, np.int32), np.array(self.guide_uncond, np.int32)
+            out['guide_scale'] = np.array(self.guide_scale, np.float32)
         return out
 
 
@@ -110,11 +165,13 @@ def _per_input(who, name, value, n, ok, rule):
     return vals[0], per
 
 
-def draw_controls(who, n, V, banned=None, temp=1.2, top_p=0.9):
+def draw_controls(who, n, V, banned=None, temp=1.2, top_p=0.9, guidance=None):
     """The sampling controls of n inputs over a vocabulary of V tokens (read only where there is a ban), checked before anything is allocated
     -> DrawControls.  banned: None (no ban), one sequence of token ids (for every input), or one entry per input, each a sequence of ids or
     None; temp / top_p: a number, or one per input.  ValueError for an id outside [0, V), a ban that leaves no token, a per-input list of the
-    wrong length, a temperature <= 0, a top_p outside (0, 1]."""
+    wrong length, a temperature <= 0, a top_p outside (0, 1].  guidance: None, or the classifier-free guidance pairs of the n inputs as (guide_cond,
+    guide_uncond, guide_scale) lists (emo_hip.h; ops.guide_pairs_error is the rule, ValueError where it is broken, and where the two rows of a
+    pair differ in ban, temp or top_p)."""
     if banned is None:
         bans = [None] * n
     else:
@@ -143,7 +200,19 @@ def draw_controls(who, n, V, banned=None, temp=1.2, top_p=0.9):
         checked.append(ids or None)
     t, ts = _per_input(who, 'temp', temp, n, lambda v: v > 0 and v == v and v != float('inf'), '> 0')
     p, ps = _per_input(who, 'top_p', top_p, n, lambda v: 0 < v <= 1, 'in (0, 1]')
-    return DrawControls(n, V, checked, t, ts, p, ps)
+    ctl = DrawControls(n, V, checked, t, ts, p, ps)
+    if guidance is not None:
+        cond, unc, scale = ([int(x) for x in guidance[0]], [int(x) for x in guidance[1]], [float(x) for x in guidance[2]])
+        bad = ops.guide_pairs_error(cond, unc, scale) if len(cond) == n else 'guide tables of %d rows for %d inputs' % (len(cond), n)
+        if bad:
+            raise ValueError('%s: %s' % (who, bad))
+        for r in range(n):
+            o = unc[r] if cond[r] == r else cond[r]
+            if cond[r] >= 0 and (ctl.bans[r], ctl.temp_at(r), ctl.top_p_at(r)) != (ctl.bans[o], ctl.temp_at(o), ctl.top_p_at(o)):
+                raise ValueError('%s: rows %d and %d of a guidance pair differ in ban, temp or top_p' % (who, r, o))
+        if any(c >= 0 for c in cond):
+            ctl.guide_cond, ctl.guide_uncond, ctl.guide_scale = cond, unc, scale
+    return ctl
 
 
 class GrammarLoop:
@@ -164,12 +233,14 @@ class GrammarLoop:
         """The grammar launch's argument block (emo_hip.h: emo_grammar_step_t), written once: _gheld keeps what its addresses point to alive,
         the score tables (self.score_tables: ops.draw_score_tables laid out like self.seq, None without `scores`) included, and the tables of
         `controls` (a DrawControls over the streams that `params` holds, or None: self.control_tables, {} where every one of the block's
-        optional tok_mask / mask_of / temp_of / top_p_of stays NULL).  No tensor of the block is allocated again after this: captured graphs
+        optional tok_mask / mask_of / temp_of / top_p_of and guide_cond / guide_uncond / guide_scale stays NULL).  No tensor of the block is allocated again after this: captured graphs
         hold the raw addresses."""
         self._gargs, self._gheld = ops.GrammarStep(kind=kind), {}
         ops.block_set(self._gargs, self._gheld, **fields)
         self.controls = controls
         tabs = controls.tables() if controls is not None else {}
+        if 'guide_cond' in tabs and kind != ops.GRAMMAR_ACC:      # (the other kinds ignore the tables: the streams would run unguided, silently)
+            raise EmoError('%s: guidance pairs run in the lock-step ACC launch alone (kind %d ignores them)' % (type(self).__name__, kind))
         if 'tok_mask' in tabs:                                   # (torch has no arithmetic on uint32: the words travel as int32, bit for bit)
             tabs['tok_mask'] = tabs['tok_mask'].view(np.int32)
         self.control_tables = dict(zip(tabs, self._to_device(*tabs.values())))

@@ -14,7 +14,7 @@ from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, ATTN_BWD, ATTN_BW
                    dtype_code, lib, ptr, stream)
 
 __all__ = ['gemm', 'colsum', 'embed_fwd', 'embed_bwd', 'layernorm_fwd', 'layernorm_bwd', 'dropout_apply', 'favor_attn_fwd',
-           'favor_attn_bwd', 'favor_decode_step', 'decode_step', 'decode_step_set', 'block_set', 'DecodeStep', 'GrammarStep', 'grammar_step', 'draw_score_tables', 'favor_draw_omega', 'favor_state_reset', 'favor_state_at', 'acc_rebase', 'softmax_attn_fwd', 'softmax_attn_bwd', 'softmax_attn_decode', 'relpos_attn_fwd', 'relpos_attn_bwd', 'relpos_attn_decode', 'xent_fwd',
+           'favor_attn_bwd', 'favor_decode_step', 'decode_step', 'decode_step_set', 'block_set', 'DecodeStep', 'GrammarStep', 'grammar_step', 'draw_score_tables', 'guide_pairs_error', 'favor_draw_omega', 'favor_state_reset', 'favor_state_at', 'acc_rebase', 'softmax_attn_fwd', 'softmax_attn_bwd', 'softmax_attn_decode', 'relpos_attn_fwd', 'relpos_attn_bwd', 'relpos_attn_decode', 'xent_fwd',
            'xent_bwd', 'token_scores', 'xent_bwd_rows', 'argmax', 'sample_nucleus', 'sample_nucleus_step', 'txl_grammar_step', 'txl_queue_step', 'acc_grammar_step', 'acc_queue_step', 'acc_window_step', 'accuracy_counts', 'sumsq', 'clip_coef', 'adam_step', 'cast', 'add_bias2',
            'ACT_NONE', 'ACT_RELU', 'ACT_GELU_NEW', 'ACT_GELU', 'MUL_NONE', 'MUL_NONZERO', 'MUL_DGELU_NEW', 'MUL_DGELU', 'MUL_BITMASK', 'gemm_bitmask_ok', 'gemm_lna_ok', 'bitmask_rows', 'favor_bwd_dn_ok', 'ffn_fwd', 'ffn_fwd_ok']
 
@@ -405,7 +405,50 @@ _GRAMMAR_STEP_LAYOUT = {
     'mask_of': lambda a, t: _is(t, _I32) and t.numel() == a.ld_u and int(t.min()) >= -1 and int(t.max()) < a.n_masks,
     'temp_of': lambda a, t: _is(t, _F32) and t.numel() == a.ld_u,
     'top_p_of': lambda a, t: _is(t, _F32) and t.numel() == a.ld_u,
+    # kind ACC, classifier-free guidance: per row of the batch; what the three hold together is checked by _check_guidance once they are in
+    'guide_cond': lambda a, t: _is(t, _I32) and t.numel() == a.n_rows,
+    'guide_uncond': lambda a, t: _is(t, _I32) and t.numel() == a.n_rows,
+    'guide_scale': lambda a, t: _is(t, _F32) and t.numel() == a.n_rows,
 }
+_GUIDE = ('guide_cond', 'guide_uncond', 'guide_scale')
+
+
+def guide_pairs_error(c, g, s):
+    """The rule of the three guidance tables (lists of equal length n: guide_cond, guide_uncond, guide_scale) -> None, or what is wrong with
+    them.  Row r holds (-1, -1) (unguided) or a pair (c, g) of two distinct rows, r one of them, whose other row holds the same pair and the
+    same scale; every scale is finite and >= 0."""
+    n = len(c)
+    if not (len(g) == n and len(s) == n):
+        return 'guide tables of %d / %d / %d rows' % (n, len(g), len(s))
+    for r in range(n):
+        if not (s[r] >= 0 and s[r] != float('inf')):             # (NaN fails the first)
+            return 'guide_scale[%d] = %r is not a finite scale >= 0' % (r, s[r])
+        if c[r] == -1 and g[r] == -1:
+            continue
+        if not (0 <= c[r] < n and 0 <= g[r] < n):
+            return 'guide pair (%d, %d) of row %d is outside [0, %d)' % (c[r], g[r], r, n)
+        if c[r] == g[r]:
+            return 'guide pair (%d, %d) of row %d names one row twice' % (c[r], g[r], r)
+        if r not in (c[r], g[r]):
+            return 'row %d is neither row of its guide pair (%d, %d)' % (r, c[r], g[r])
+        o = g[r] if r == c[r] else c[r]
+        if (c[o], g[o]) != (c[r], g[r]) or s[o] != s[r]:
+            return 'rows %d and %d of a guide pair disagree: (%d, %d) x %r against (%d, %d) x %r' % (r, o, c[r], g[r], s[r], c[o], g[o], s[o])
+    return None
+
+
+def _check_guidance(args, held):
+    """The three guidance tables of a GrammarStep as they stand in `held` (read back once, when one of them enters the block, as mask_of is):
+    all three or none, and guide_pairs_error's rule.  The kernel reads nothing out of bounds whatever they hold (any other pair is unguided to
+    it): these are the checks the launch cannot make."""
+    cond, unc, scale = (held.get(k) for k in _GUIDE)
+    if cond is None and unc is None and scale is None:
+        return
+    assert cond is not None and unc is not None and scale is not None, 'grammar step: guide_cond, guide_uncond and guide_scale come together or not at all'
+    bad = guide_pairs_error(cond.tolist(), unc.tolist(), scale.tolist())
+    assert bad is None, 'grammar step: ' + bad
+
+
 # per struct: its name in messages, the layout table, the int64 vectors, and the numbers a tensor brings with it (field -> (number, of tensor))
 _BLOCKS = {
     DecodeStep: ('decode step', _DECODE_STEP_LAYOUT, _DECODE_STEP_I64,
@@ -418,7 +461,8 @@ _BLOCKS = {
 def block_set(args, held, **fields):
     """Write fields of an argument block, a DecodeStep or a GrammarStep (emo_hip.h: emo_decode_step_t, emo_grammar_step_t): numbers as they are,
     tensors (or None) as device addresses after the layout check of the field in the struct's table; a tensor that brings a number with it sets
-    that too (`seq` ld_seq; DecodeStep `sync_ws` sync_ws_bytes; GrammarStep `u_steps` n_u).  The struct holds raw addresses, so the rule of _c()
+    that too (`seq` ld_seq; DecodeStep `sync_ws` sync_ws_bytes; GrammarStep `u_steps` n_u); the three guidance tables of a GrammarStep are given
+    in one call and checked together (_check_guidance).  The struct holds raw addresses, so the rule of _c()
     applies to its owner: `held` (field -> tensor) is the owner's dict that keeps every tensor whose address is in the struct alive, the
     contiguous copies made here included.  A tensor that `held` already has for the field is the one the struct points to, checked when it went
     in: it is not looked at again (a token loop hands over the same buffers step after step).  Numbers are written first: a tensor may be
@@ -443,6 +487,14 @@ def block_set(args, held, **fields):
         if k in brings:
             number, of = brings[k]
             setattr(args, number, 0 if t is None else of(t))
+    if tensors and type(args) is GrammarStep and any(k in _GUIDE for k, _ in tensors):
+        try:
+            _check_guidance(args, held)
+        except AssertionError:
+            for k in _GUIDE:                                      # a refused set never stays in the block
+                held.pop(k, None)
+                setattr(args, k, None)
+            raise
 
 
 decode_step_set = block_set
@@ -741,16 +793,17 @@ def txl_queue_step(logits, temperature, top_p, key_temperature, key_top_p, u_ste
 
 
 def acc_grammar_step(logits, temperature, top_p, u_steps, ev_flags, ev_beat, lead_tok, lead_off, params, state, seq, segs, max_len, track_full, pad,
-                     tok_out, seg_out, running, tok_logp=None, tok_rank=None, tok_entropy=None):
+                     tok_out, seg_out, running, tok_logp=None, tok_rank=None, tok_entropy=None, guide_cond=None, guide_uncond=None, guide_scale=None):
     """One stage-2 sample-and-grammar step of n streams (include/emo_hip.h, EMO_GRAMMAR_ACC): logits fp32 [n, V], u_steps fp32 [n_u, n],
     ev_flags / ev_beat int32 [V], lead_tok int64 (flat), lead_off int32, params / state int32 [n, 8], seq / segs int64 [n, W], tok_out / seg_out
     int64 [n], running int32 [1].  state, seq, segs, tok_out, seg_out and running are updated in place.  tok_logp / tok_rank / tok_entropy:
-    as in txl_grammar_step."""
+    as in txl_grammar_step.  guide_cond / guide_uncond int32 [n], guide_scale fp32 [n] (all three or none): classifier-free guidance over
+    mirrored pairs of streams (emo_hip.h)."""
     n, V = logits.shape
     _grammar_once(GRAMMAR_ACC, n_rows=n, n_token=V, ld_u=n, temperature=temperature, top_p=top_p, max_len=max_len, track_full=track_full, pad=pad,
                   logits=logits, u_steps=u_steps, ev_flags=ev_flags, ev_beat=ev_beat, lead_tok=lead_tok, lead_off=lead_off, params=params, state=state,
                   seq=seq, segs=segs, tok_out=tok_out, seg_out=seg_out, running=running, tok_logp=tok_logp, tok_rank=tok_rank,
-                  tok_entropy=tok_entropy)
+                  tok_entropy=tok_entropy, guide_cond=guide_cond, guide_uncond=guide_uncond, guide_scale=guide_scale)
     return tok_out
 
 

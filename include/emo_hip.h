@@ -609,6 +609,21 @@ typedef struct {
     int64_t* seg_out;          /* ACC: int64 [n_rows] */
     int64_t max_len;           /* ACC: > 0 */
     int64_t pad;               /* ACC */
+    /* (kind ACC alone - ACC_QUEUE and every other kind ignore the three, whatever they hold; all three or none; all NULL: the launch is exactly
+     * the one without them.)  Classifier-free guidance over a MIRRORED PAIR of streams of the batch.  Stream r is guided when guide_cond[r] = c
+     * and guide_uncond[r] = g are two distinct values in [0, n_rows); any other pair of values is "unguided" to the kernel, which never reads
+     * outside the tables.  A guided stream draws from l[v] = lc + s * (lc - lu), lc = logits[c, v], lu = logits[g, v], s = guide_scale[r]: three
+     * separately rounded fp32 operations, never contracted, so NumPy's float32 `lc + s * (lc - lu)` is the same row bit for bit; the stream's ban
+     * is applied AFTER the combination (a banned token is -INFINITY, no inf - inf arises from it; the logits themselves are finite); s = 0 is
+     * row c itself.  Its uniforms come from column c of u_steps.  The leader of a pair is c (the conditioned primer), its follower g (the same
+     * primer with the unconditioned token in the condition's place); both carry the same (c, g, s), equal temp / top_p / ban, and run the same
+     * grammar on the same draw in their own workgroups: the follower stays token for token with its leader without any traffic between the two,
+     * and every row writes only its own tok_out / seg_out / state / seq / segs.  tok_logp / tok_rank / tok_entropy stay the model's figures from
+     * the row's OWN logits at temperature 1: the leader's are the conditioned model's, the follower's the unconditioned model's for the same
+     * tokens.  The host owns the checks that need the values (ops.block_set: indices in range, pairs consistent, 0 <= s < inf). */
+    const int32_t* guide_cond;    /* ACC: int32 [n_rows] or NULL: the row whose logits are the conditioned ones for stream r, or -1 */
+    const int32_t* guide_uncond;  /* ACC: int32 [n_rows] or NULL: the row whose logits are the unconditioned ones, or -1 */
+    const float* guide_scale;     /* ACC: f32 [n_rows] or NULL: s >= 0 */
     int64_t* segs;             /* ACC, ACC_WINDOW: int64 [streams, ld_seq] */
     const int64_t* lead_tok;   /* ACC, ACC_WINDOW */
     const int32_t* lead_off;   /* ACC, ACC_WINDOW */
