@@ -26,6 +26,10 @@
 // leader on the conditioned primer and a follower on the unconditioned one.  Both workgroups draw from the same combination of the same two
 // logits rows with the same uniform and run the same grammar, so the follower stays token for token with its leader and no workgroup reads or
 // writes another's state; the scores stay those of each row's own logits.
+// Kinds ACC and ACC_QUEUE, optional kept bars (keep_tok / keep_beg / keep_end: emo_hip.h): when the accepted Track_LeadSheet opens a bar the caller
+// already has, thread 0 writes the bar out behind the injected lead-sheet bar in the same launch, closes it, and goes on through consecutive kept
+// bars (acc_keep_chain below, between the barriers that were there); the feed path then hands the tokens out one per launch.  They are no draws:
+// S_ACCEPTED, S_DRAWS and the score cell belong to the Track_LeadSheet alone.  inference._Stream._open_bar is the rule on the host.
 #include "emo_grammar.h"
 
 namespace {
@@ -36,7 +40,52 @@ namespace {
 // logits (emo_nucleus.h: its row under its ban, or the guided combination of two rows), u_col its column of the uniform table (pitch a.ld_u),
 // row / srow its token and segment rows, ctl its sampling controls (emo_grammar_controls: the ban is the accessor's and reaches the first
 // draw's sort, which the redraws reuse; the scores are taken by the caller from the row as the model wrote it).
-template <typename Logits>
+// Thread 0, after an accepted Track_LeadSheet has opened bar k (its lead-sheet bar and track_full are at the end of the row, `len` tokens long):
+// the chain of consecutive kept bars from k on (emo_hip.h: keep_tok).  WRITE false walks it without touching the row, so the caller tests the
+// whole chain against ld_seq before it writes anything; both walks take the same path.  -> RUNNING (bar k, or the bar behind the chain, is
+// drawn), DONE (max_events inside a kept bar, or the last bar was kept: closed with keep_eos) or OVERFLOW (the row, a table or a range is too
+// short); len / bars as the chain leaves them, kept: whether bar k was kept.  At most TARGET_BARS turns, each bounded by its table range.
+template <bool WRITE>
+__device__ __forceinline__ int32_t acc_keep_chain(const emo_grammar_step_t& a, const int32_t* spr, int64_t track_ls, int64_t* __restrict__ row,
+                                                  int64_t* __restrict__ srow, int32_t k, int32_t& len, int32_t& bars, bool& kept) {
+    const int32_t target = spr[EMO_ACC_P_TARGET_BARS], n_bars = spr[EMO_ACC_P_N_BARS], max_events = spr[EMO_ACC_P_MAX_EVENTS];
+    const int64_t bar0 = spr[EMO_ACC_P_BAR0], ld_seq = a.ld_seq;
+    auto put = [&](int64_t tok, int64_t seg) {
+        if (WRITE) {
+            row[len] = tok;
+            srow[len] = seg;
+        }
+        ++len;
+    };
+    while (k >= 0 && k < target && k < n_bars) {
+        const int32_t kb = a.keep_beg[bar0 + k], ke = a.keep_end[bar0 + k];
+        if (kb < 0) break;                                   // bar k is drawn
+        if (ke < kb || ke > a.n_keep) return EMO_ACC_OVERFLOW;
+        kept = true;
+        for (int32_t i = kb; i < ke; ++i) {
+            if (len + 1 > ld_seq) return EMO_ACC_OVERFLOW;
+            put(a.keep_tok[i], 1);
+            if (len > max_events) return EMO_ACC_DONE;
+        }
+        if (k == target - 1) {                               // the last bar: closed like a drawn EOS
+            if (len + 1 > ld_seq) return EMO_ACC_OVERFLOW;
+            put(a.keep_eos, 1);
+            return EMO_ACC_DONE;
+        }
+        if (k + 1 >= n_bars) return EMO_ACC_OVERFLOW;        // closed like a drawn Track_LeadSheet: the next lead-sheet bar, track_full
+        const int32_t a0 = a.lead_off[bar0 + k + 1], b = a.lead_off[bar0 + k + 2];
+        if (b < a0 || (int64_t)len + 1 + (b - a0) + 1 > ld_seq) return EMO_ACC_OVERFLOW;
+        put(track_ls, 0);
+        for (int32_t i = a0; i < b; ++i) put(a.lead_tok[i], 0);
+        put(a.track_full, 1);
+        ++bars;
+        ++k;
+    }
+    return EMO_ACC_RUNNING;
+}
+
+// (KEEP: the block has the kept-bar tables; false: the code as it was before they existed.)
+template <bool KEEP, typename Logits>
 __device__ __forceinline__ int32_t acc_draw(const emo_grammar_step_t& a, const emo_grammar_controls_t ctl, const Logits l, const float* __restrict__ u_col,
                                             int64_t* __restrict__ row, int64_t* __restrict__ srow, const int32_t* spr, int32_t* sst, int32_t* sagain_p,
                                             char* lds, int tid, int32_t& draws) {
@@ -75,7 +124,18 @@ __device__ __forceinline__ int32_t acc_draw(const emo_grammar_step_t& a, const e
                     const bool have = more && bars + 1 < spr[EMO_ACC_P_N_BARS];
                     const int32_t j = spr[EMO_ACC_P_BAR0] + bars + 1;
                     const int32_t a0 = have ? a.lead_off[j] : 0, b = have ? a.lead_off[j + 1] : 0;
-                    if ((more && (!have || b < a0)) || len + 1 + (more ? b - a0 + 1 : 0) > ld_seq) {
+                    bool fits = !((more && (!have || b < a0)) || len + 1 + (more ? b - a0 + 1 : 0) > ld_seq);
+                    if constexpr (KEEP) {                    // the kept bars behind the one this opens: walked once, tested before any write
+                        if (fits && more) {
+                            int32_t len2 = len + 1 + (b - a0) + 1, bars2 = bars + 1;
+                            bool kept = false;
+                            if (acc_keep_chain<false>(a, spr, word, row, srow, bars + 1, len2, bars2, kept) == EMO_ACC_OVERFLOW) {
+                                fits = false;
+                                --draws;                     // (thread 0's copy, the one that is stored: the counters as before the draw)
+                            }
+                        }
+                    }
+                    if (!fits) {
                         status = EMO_ACC_OVERFLOW;
                     } else {
                         row[len] = word;
@@ -90,6 +150,13 @@ __device__ __forceinline__ int32_t acc_draw(const emo_grammar_step_t& a, const e
                             row[len] = a.track_full;
                             srow[len++] = 1;
                             sst[EMO_ACC_S_CUR_POS] = 0;
+                            if constexpr (KEEP) {
+                                int32_t bars2 = bars + 1;
+                                bool kept = false;
+                                status = acc_keep_chain<true>(a, spr, word, row, srow, bars + 1, len, bars2, kept);
+                                sst[EMO_ACC_S_BARS] = bars2;
+                                if (kept) sst[EMO_ACC_S_FAILED] = 0;
+                            }
                         } else {
                             status = EMO_ACC_DONE;
                         }
@@ -122,7 +189,7 @@ __device__ __forceinline__ int32_t acc_draw(const emo_grammar_step_t& a, const e
 // pair (guide_cond[r], guide_uncond[r]) is two distinct rows of the batch draws from their combination (emo_guided_logits) with the uniforms of
 // column guide_cond[r], every other stream as without them.  The pair is the same word in every thread, so the barriers stay uniform.  The
 // scores are still taken from the stream's own row b.
-template <bool CTL, bool GUIDE = false>
+template <bool CTL, bool GUIDE, bool KEEP>
 __device__ __forceinline__ void acc_stream_step(const emo_grammar_step_t& a, int64_t b, int64_t r, char* lds, int32_t* sst, const int32_t* spr,
                                                 int32_t* sagain, float* sred, int tid) {
     int32_t* st = a.state + r * EMO_ACC_STATE_WORDS;
@@ -158,10 +225,10 @@ __device__ __forceinline__ void acc_stream_step(const emo_grammar_step_t& a, int
         gu = a.guide_uncond[r];
     }
     if (GUIDE && gc != gu && gc >= 0 && gc < a.n_rows && gu >= 0 && gu < a.n_rows)
-        status = acc_draw(a, ctl, emo_guided_logits{a.logits + gc * a.n_token, a.logits + gu * a.n_token, a.guide_scale[r], ctl.ban}, a.u_steps + gc, row,
+        status = acc_draw<KEEP>(a, ctl, emo_guided_logits{a.logits + gc * a.n_token, a.logits + gu * a.n_token, a.guide_scale[r], ctl.ban}, a.u_steps + gc, row,
                           srow, spr, sst, sagain, lds, tid, draws);
     else
-        status = acc_draw(a, ctl, emo_banned_logits{a.logits + b * a.n_token, ctl.ban}, a.u_steps + r, row, srow, spr, sst, sagain, lds, tid, draws);
+        status = acc_draw<KEEP>(a, ctl, emo_banned_logits{a.logits + b * a.n_token, ctl.ban}, a.u_steps + r, row, srow, spr, sst, sagain, lds, tid, draws);
     // an acceptance appended its word at the old length (an injected bar follows it) and counted itself, in front of the loop's last barrier
     if (scores && sst[EMO_ACC_S_ACCEPTED] != acc0) emo_grammar_score(a, a.logits + b * a.n_token, r, len0, row[len0], sred, tid);
     if (tid != 0) return;
@@ -180,7 +247,7 @@ __device__ __forceinline__ void acc_stream_step(const emo_grammar_step_t& a, int
     for (int i = 0; i < EMO_ACC_STATE_WORDS; ++i) st[i] = sst[i];
 }
 
-template <bool CTL, bool GUIDE>
+template <bool CTL, bool GUIDE, bool KEEP>
 __global__ __launch_bounds__(512) void acc_grammar_kernel(const emo_grammar_step_t a) {
     __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
     __shared__ int32_t sst[EMO_ACC_STATE_WORDS], spr[EMO_ACC_PARAM_WORDS], sagain;
@@ -195,7 +262,7 @@ __global__ __launch_bounds__(512) void acc_grammar_kernel(const emo_grammar_step
         }
         return;
     }
-    acc_stream_step<CTL, GUIDE>(a, r, r, lds, sst, spr, &sagain, sred, tid);
+    acc_stream_step<CTL, GUIDE, KEEP>(a, r, r, lds, sst, spr, &sagain, sred, tid);
 }
 
 // Thread 0 of slot b, whose job (if it had one) is over: the next queued job that is RUNNING, or none.  queue_head only grows, so a slot that
@@ -223,7 +290,7 @@ __device__ __forceinline__ void acc_queue_admit(const emo_grammar_step_t& a, int
     }
 }
 
-template <bool CTL>
+template <bool CTL, bool KEEP>
 __global__ __launch_bounds__(512) void acc_queue_kernel(const emo_grammar_step_t a) {
     __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
     __shared__ int32_t sst[EMO_ACC_STATE_WORDS], spr[EMO_ACC_PARAM_WORDS], sagain, sslot;
@@ -246,7 +313,7 @@ __global__ __launch_bounds__(512) void acc_queue_kernel(const emo_grammar_step_t
                 atomicSub(a.running, 1);
             }
         } else {
-            acc_stream_step<CTL>(a, b, j, lds, sst, spr, &sagain, sred, tid);
+            acc_stream_step<CTL, false, KEEP>(a, b, j, lds, sst, spr, &sagain, sred, tid);
         }
     }
     if (tid != 0) return;
@@ -285,7 +352,7 @@ __global__ __launch_bounds__(512) void acc_window_kernel(const emo_grammar_step_
     const bool scores = emo_grammar_wants_scores(a);         // as in acc_grammar_kernel; the tables are indexed by the stream r, the logits by b
     const int32_t len0 = scores ? sst[EMO_ACC_S_LEN] : 0, acc0 = scores ? sst[EMO_ACC_S_ACCEPTED] : 0;
     const emo_grammar_controls_t ctl = emo_grammar_controls<CTL>(a, r);
-    const int32_t status = acc_draw(a, ctl, emo_banned_logits{a.logits + b * a.n_token, ctl.ban}, a.u_steps + r, row, srow, spr, sst, &sagain, lds, tid, draws);
+    const int32_t status = acc_draw<false>(a, ctl, emo_banned_logits{a.logits + b * a.n_token, ctl.ban}, a.u_steps + r, row, srow, spr, sst, &sagain, lds, tid, draws);
     if (scores && sst[EMO_ACC_S_ACCEPTED] != acc0) emo_grammar_score(a, a.logits + b * a.n_token, r, len0, row[len0], sred, tid);
     if (tid == 0) {
         if (status != EMO_ACC_RUNNING) atomicSub(a.running, 1);
@@ -335,10 +402,18 @@ extern "C" int emo_grammar_step(const emo_grammar_step_t* args, emo_stream_t str
     // (kind ACC alone reads the guidance tables; a block without them launches the <.., false> instance, the kernel as it was before they existed)
     const int guide = a.kind == EMO_GRAMMAR_ACC ? (a.guide_cond != nullptr) + (a.guide_uncond != nullptr) + (a.guide_scale != nullptr) : 0;
     EMO_CHECK(guide == 0 || guide == 3, "emo_grammar_step[%s]: guide_cond, guide_uncond and guide_scale come together or not at all", name);
-    const auto kernel = aq       ? (ctl ? acc_queue_kernel<true> : acc_queue_kernel<false>)
+    // (kinds ACC and ACC_QUEUE read the kept-bar tables; a block without them launches a <.., false> instance, the kernel as it was before they
+    // existed: six instances are new, the four of ACC and the two of ACC_QUEUE; ACC_WINDOW has none and ignores the tables)
+    const int keep = acc ? (a.keep_tok != nullptr) + (a.keep_beg != nullptr) + (a.keep_end != nullptr) : 0;
+    EMO_CHECK(keep == 0 || (keep == 3 && a.n_keep >= 0 && a.n_keep <= INT32_MAX),
+              "emo_grammar_step[%s]: keep_tok, keep_beg and keep_end come together or not at all, with 0 <= n_keep < 2^31", name);
+    const auto kernel = aq       ? (keep ? (ctl ? acc_queue_kernel<true, true> : acc_queue_kernel<false, true>)
+                                         : (ctl ? acc_queue_kernel<true, false> : acc_queue_kernel<false, false>))
                         : !acc   ? (ctl ? acc_window_kernel<true> : acc_window_kernel<false>)
-                        : guide  ? (ctl ? acc_grammar_kernel<true, true> : acc_grammar_kernel<false, true>)
-                                 : (ctl ? acc_grammar_kernel<true, false> : acc_grammar_kernel<false, false>);
+                        : keep   ? (guide ? (ctl ? acc_grammar_kernel<true, true, true> : acc_grammar_kernel<false, true, true>)
+                                          : (ctl ? acc_grammar_kernel<true, false, true> : acc_grammar_kernel<false, false, true>))
+                        : guide  ? (ctl ? acc_grammar_kernel<true, true, false> : acc_grammar_kernel<false, true, false>)
+                                 : (ctl ? acc_grammar_kernel<true, false, false> : acc_grammar_kernel<false, false, false>);
     hipLaunchKernelGGL(kernel, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
     EMO_LAUNCH_CHECK();
     return EMO_OK;

@@ -409,8 +409,14 @@ _GRAMMAR_STEP_LAYOUT = {
     'guide_cond': lambda a, t: _is(t, _I32) and t.numel() == a.n_rows,
     'guide_uncond': lambda a, t: _is(t, _I32) and t.numel() == a.n_rows,
     'guide_scale': lambda a, t: _is(t, _F32) and t.numel() == a.n_rows,
+    # kinds ACC / ACC_QUEUE, kept bars: keep_beg / keep_end are indexed like lead_off (hand them over after it, and n_keep in the same call or
+    # before); what the three hold together is checked by _check_keep once they are in
+    'keep_tok': lambda a, t: _is(t, _I64) and t.numel() >= max(a.n_keep, 1),
+    'keep_beg': lambda a, t: _is(t, _I32),
+    'keep_end': lambda a, t: _is(t, _I32),
 }
 _GUIDE = ('guide_cond', 'guide_uncond', 'guide_scale')
+_KEEP = ('keep_tok', 'keep_beg', 'keep_end')
 
 
 def guide_pairs_error(c, g, s):
@@ -447,6 +453,23 @@ def _check_guidance(args, held):
     assert cond is not None and unc is not None and scale is not None, 'grammar step: guide_cond, guide_uncond and guide_scale come together or not at all'
     bad = guide_pairs_error(cond.tolist(), unc.tolist(), scale.tolist())
     assert bad is None, 'grammar step: ' + bad
+
+
+def _check_keep(args, held):
+    """The three kept-bar tables of a GrammarStep as they stand in `held` (read back once, when one of them enters the block): all three or
+    none, keep_beg / keep_end as long as lead_off, and every kept range inside keep_tok's n_keep entries.  The kernel reads nothing out of
+    bounds whatever they hold (such a range ends its stream OVERFLOW)."""
+    tok, beg, end = (held.get(k) for k in _KEEP)
+    if tok is None and beg is None and end is None:
+        return
+    assert tok is not None and beg is not None and end is not None, 'grammar step: keep_tok, keep_beg and keep_end come together or not at all'
+    off = held.get('lead_off')
+    assert off is not None and beg.numel() == off.numel() and end.numel() == off.numel(), \
+        'grammar step: keep_beg and keep_end have one entry per entry of lead_off'
+    b, e = beg.cpu().numpy(), end.cpu().numpy()
+    kept = b >= 0
+    assert 0 <= args.n_keep <= tok.numel() and bool((e[kept] >= b[kept]).all()) and bool((e[kept] <= args.n_keep).all()), \
+        'grammar step: a kept bar lies outside keep_tok[0 .. n_keep)'
 
 
 # per struct: its name in messages, the layout table, the int64 vectors, and the numbers a tensor brings with it (field -> (number, of tensor))
@@ -492,6 +515,14 @@ def block_set(args, held, **fields):
             _check_guidance(args, held)
         except AssertionError:
             for k in _GUIDE:                                      # a refused set never stays in the block
+                held.pop(k, None)
+                setattr(args, k, None)
+            raise
+    if tensors and type(args) is GrammarStep and any(k in _KEEP for k, _ in tensors):
+        try:
+            _check_keep(args, held)
+        except AssertionError:
+            for k in _KEEP:
                 held.pop(k, None)
                 setattr(args, k, None)
             raise

@@ -520,6 +520,8 @@ enum { EMO_TXL_EV_BEAT = 1, EMO_TXL_EV_BAR = 2, EMO_TXL_EV_PAD = 4, EMO_TXL_EV_E
  * Beat events) are built on the host from idx2event.  Lead sheets: lead_tok int64 (all bars of all streams, flat) and lead_off int32: bar j of
  * stream r is lead_tok[lead_off[params[BAR0] + j] .. lead_off[params[BAR0] + j + 1]), j < params[N_BARS].  Rows of width >= max_len + the
  * longest bar + 2 always hold an injected bar; a row or a bar table too short for a step is a caller error (OVERFLOW).
+ * Optional kept bars (keep_tok / keep_beg / keep_end, the comment of the fields below): a bar the caller already has is written out, not drawn, in
+ * the launch that accepts the Track_LeadSheet in front of it, and fed like an injected lead-sheet bar; rows then need the longest kept run on top.
  * params int32 [n, EMO_ACC_PARAM_WORDS], state int32 [n, EMO_ACC_STATE_WORDS], laid out as the enums below. */
 enum { EMO_ACC_P_TARGET_BARS = 0, EMO_ACC_P_MAX_EVENTS = 1, EMO_ACC_P_SKIP_CHECK = 2, EMO_ACC_P_BAR0 = 3, EMO_ACC_P_N_BARS = 4, EMO_ACC_PARAM_WORDS = 8 };
 enum { EMO_ACC_S_STATUS = 0, EMO_ACC_S_LEN = 1 /* tokens in seq[r] */, EMO_ACC_S_CONSUMED = 2 /* tokens fed to the model */,
@@ -627,6 +629,26 @@ typedef struct {
     int64_t* segs;             /* ACC, ACC_WINDOW: int64 [streams, ld_seq] */
     const int64_t* lead_tok;   /* ACC, ACC_WINDOW */
     const int32_t* lead_off;   /* ACC, ACC_WINDOW */
+    /* (kinds ACC and ACC_QUEUE - ACC_WINDOW and every other kind ignore the five, whatever they hold; the three tables come together or not at
+     * all; all NULL: the launch is exactly the one without them.)  KEPT BARS: accompaniment bars the caller already has.  keep_beg / keep_end are
+     * indexed like lead_off, by params[BAR0] + j, j < params[N_BARS] (one entry per lead-sheet bar: the host checks the lengths against
+     * lead_off's); keep_beg < 0: bar j is drawn, as ever; otherwise its accompaniment is keep_tok[keep_beg .. keep_end), possibly empty (a kept
+     * empty bar is not a drawn bar), without the Track_Full before it and the Track_LeadSheet / EOS behind it.  A range outside [0, n_keep] or
+     * running backwards ends the stream OVERFLOW: nothing outside keep_tok is read.  When an accepted Track_LeadSheet opens bar j (the next
+     * lead-sheet bar and track_full appended) and bar j is kept, thread 0 goes on in the same launch: the kept tokens with segment 1 (the
+     * length test against params[MAX_EVENTS] after each one, DONE inside the bar where it fires; no Beat check, no PAD / EOS rejection); then,
+     * for a bar that is not the last of params[TARGET_BARS], the Track_LeadSheet id with segment 0, BARS += 1 and the opening of bar j + 1 (a
+     * chain through consecutive kept bars), for the last one keep_eos with segment 1 and DONE.  The chain is walked once without writing: if it
+     * does not fit ld_seq the stream ends OVERFLOW with its row, LEN, BARS, ACCEPTED and DRAWS as before the draw (without a kept bar behind
+     * the Track_LeadSheet the overflowing draw stays counted, as ever).  ACCEPTED and DRAWS move for the drawn Track_LeadSheet alone, the score cell is its
+     * cell; kept tokens lie in seq / segs beyond CONSUMED and are fed one per launch like an injected lead-sheet bar.  CUR_POS is 0 at the bar
+     * that is next opened for drawing, and FAILED is 0 there when a kept bar lay in between (without one it is carried, as ever).  Kept bars at
+     * the start of a piece are in the row when the host loads it (inference._Stream is the rule on the host). */
+    const int64_t* keep_tok;   /* ACC, ACC_QUEUE: int64 [n_keep] or NULL: all kept bars of all streams, flat */
+    const int32_t* keep_beg;   /* ACC, ACC_QUEUE: int32 [bars of lead_off] or NULL: < 0 = the bar is drawn */
+    const int32_t* keep_end;   /* ACC, ACC_QUEUE: int32 [bars of lead_off] or NULL */
+    int64_t n_keep;            /* ACC, ACC_QUEUE: entries of keep_tok */
+    int64_t keep_eos;          /* ACC, ACC_QUEUE: the id that closes a kept last bar (EOS_None) */
     int64_t track_full;        /* ACC, ACC_WINDOW */
     int64_t window;            /* ACC_WINDOW: 0 < window <= ld_seq */
     const int32_t* rows;       /* ACC_WINDOW: int32 [n_rows] or NULL */
