@@ -90,6 +90,9 @@ _SIG = {
     'emo_last_error': (ctypes.c_char_p, []),
     'emo_device_cus': (c_i, []),
     'emo_gemm': (c_i, [c_p, c_i, c_l, c_p, c_i, c_l, c_p, c_l, c_l, c_l, c_l, c_i, c_i, c_i, ctypes.POINTER(Epilogue), c_p]),
+    'emo_gemm_route': (c_i, [c_p, c_i, c_l, c_p, c_i, c_l, c_p, c_l, c_l, c_l, c_l, c_i, c_i, c_i, ctypes.POINTER(Epilogue), ctypes.POINTER(c_i), ctypes.POINTER(c_i)]),
+    'emo_gemm_astat_supported': (c_i, [c_i, c_i, c_l, c_l, c_l]),
+    'emo_gemm_astat_min_rows': (c_l, []),
     'emo_gemm_last_kernel': (c_i, []),
     'emo_gemm_last_plan': (c_i, []),
     'emo_epilogue_size': (c_i, []),

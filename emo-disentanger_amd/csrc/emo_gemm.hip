@@ -528,6 +528,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const bf16_t* __restr
 // lane-linearly, so the swizzle is applied to the per-lane SOURCE address and again on the read.
 // Requires K (per split) % 32 == 0; edge rows are clamped to valid addresses (their outputs are dropped).
 constexpr int G2_BK = 32;   // K granularity the host guarantees for this kernel family
+static_assert(GB_M == GP_BM && GB_N == GP_BN && GB_K == GP_BK && G2_BK == GP_RING_BK, "emo_gemm_plan.h plans for this geometry");
 
 // per-lane BYTE offsets of the 16-B pieces this lane fetches for one operand tile (constant over the K loop);
 // the K position is carried by a wave-uniform base pointer so that a K step costs no per-lane address arithmetic.
@@ -878,17 +879,6 @@ __global__ __launch_bounds__(64 * NW) void gemm_bf16_skinny_kernel(const bf16_t*
 }
 
 // ================================================================================================
-static bool g_safe_tr = false;
-static bool g_safe_tr_init = false;
-static bool use_safe_tr() {
-    if (!g_safe_tr_init) {
-        const char* e = getenv("EMO_GEMM_SAFE_TR");
-        g_safe_tr = e && e[0] == '1';
-        g_safe_tr_init = true;
-    }
-    return g_safe_tr;
-}
-
 template <bool A_KC, bool B_KC, bool SAFE, typename OutT>
 static void launch_bf16(dim3 grid, hipStream_t st, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C,
                         int64_t M, int64_t N, int64_t K, int64_t kps, const EpiParams& ep) {
@@ -937,51 +927,15 @@ static void dispatch_glds2(bool akc, bool bkc, dim3 grid, hipStream_t st, const 
     else if (!akc && bkc) launch_glds<false, true, OutT, BK, ST>(grid, st, A, lda, B, ldb, C, M, N, K, kps, ep);
     else launch_glds<false, false, OutT, BK, ST>(grid, st, A, lda, B, ldb, C, M, N, K, kps, ep);
 }
+// the ring geometry the plan chose (emo_gemm_plan.h, gp_tiled): 64 x 4 / 32 x 4 on small grids, 64 x 2 for long reductions, 32 x 3, 32 x 2 for MN-contiguous B
 template <typename OutT>
-static void dispatch_glds(bool akc, bool bkc, dim3 grid, hipStream_t st, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C,
-                          int64_t M, int64_t N, int64_t K, int64_t kps, const EpiParams& ep) {
-    // measured r01 (tools/bench_gemm.py of that round — git history — MI355X): the per-tile fixed cost (prologue latency + epilogue, ~4-5 us) is what
-    // limits the K=512 GEMMs, so OCCUPANCY wins over prefetch depth: a 3-stage ring of 32-deep tiles (48 KB LDS, 3 blocks
-    // per CU) beats the 4-stage ring (64 KB, 2 blocks) by 13-16 % (qkv 575 vs 509, ffn1 659 vs 568 TFLOP/s); for the
-    // long reduction (K=2048) the double buffer of full 128-B lines is best (842 vs 796); for MN-contiguous B (dgrad)
-    // the 2-stage ring of 32-deep tiles (32 KB, 4 blocks per CU) is best (in-step A/B of the other geometries: DESIGN.md §4.1).
-    const bool can64 = (kps % 64) == 0 && (K % 64) == 0;
-    const int nsplit = kps < K ? (int)cdiv64(K, kps) : 0;            // (emo_gemm_last_plan: the split count of this launch)
-    // Small grids (at most two tiles per CU: the reference YAML's batch size 4, stage 1): occupancy has nothing to offer, a block is alone on
-    // its CU and every K step exposed an L2 / HBM round trip -> the 4-stage ring of 32-deep tiles (three tiles in flight inside the block)
-    static const bool small_off = getenv("EMO_GEMM_SMALLGRID") != nullptr && atoi(getenv("EMO_GEMM_SMALLGRID")) == 0;
-    // (r03, same box: batch-4 step 8.85 -> 8.79 ms, stage 1 7.64 -> 7.47 ms; a 64-deep double buffer instead was erratic: 8.5 / 9.2 ms)
-    if (grid.x <= 512 && !small_off && K >= 128) {
-        // 64-deep tiles in the same 4-stage ring = twice the bytes in flight per block (128 KB of LDS, one block per CU): what bounds these products is
-        // the bytes one block keeps in flight (r04, same box, two pairs: stage 1 262 / 266 -> 284 / 283 k tokens/s, batch-size-4 steps unchanged);
-        // EMO_GEMM_SMALL64=0: the 32-deep ring
-        static const bool small64 = !(getenv("EMO_GEMM_SMALL64") != nullptr && atoi(getenv("EMO_GEMM_SMALL64")) == 0);
-        if (small64 && can64 && kps >= 512) { emo_gemm_note_plan(64, 4, nsplit, 0); dispatch_glds2<OutT, 64, 4>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, kps, ep); return; }
-        emo_gemm_note_plan(32, 4, nsplit, 0);
-        dispatch_glds2<OutT, 32, 4>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, kps, ep);
-        return;
-    }
-    if (bkc && K > 1024 && can64) { emo_gemm_note_plan(64, 2, nsplit, 0); dispatch_glds2<OutT, 64, 2>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, kps, ep); }
-    else if (bkc) { emo_gemm_note_plan(32, 3, nsplit, 0); dispatch_glds2<OutT, 32, 3>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, kps, ep); }
-    else { emo_gemm_note_plan(32, 2, nsplit, 0); dispatch_glds2<OutT, 32, 2>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, kps, ep); }
-}
-
-static int g_gemm_variant = -1;   // EMO_GEMM_VARIANT: 1 = register-staged v1, 2 = LDS-DMA ring for k-contiguous A, 3 = also for the TN (wgrad) layout; unset = per call
-static bool g_gemm_variant_auto = true;
-static int gemm_variant() {
-    if (g_gemm_variant < 0) {
-        const char* e = getenv("EMO_GEMM_VARIANT");
-        g_gemm_variant_auto = !(e && e[0] >= '1' && e[0] <= '3');
-        g_gemm_variant = g_gemm_variant_auto ? 2 : (e[0] - '0');
-    }
-    return g_gemm_variant;
-}
-// Per call (r05): the weight-gradient layout (A stored [K, M]) on the LDS-DMA kernel when the reduction is short — stage 1 (2048 tokens per step:
-// 48 weight gradients on the register-staged kernel) 6.35 -> 6.13 ms per step; at 8192 tokens it measures the same, at 131072 it loses 1.5 ms
-// (those shapes have the 256 x 256 wgrad kernel; what reaches this point then is better off with the in-kernel bias gradient of v1).
-static int gemm_variant_for(int a_trans, int64_t K) {
-    const int v = gemm_variant();
-    return (g_gemm_variant_auto && a_trans && K <= 4096) ? 3 : v;
+static void dispatch_glds(const GemmPlan& p, bool akc, bool bkc, dim3 grid, hipStream_t st, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C,
+                          int64_t M, int64_t N, int64_t K, const EpiParams& ep) {
+    if (p.stages == 4 && p.bk == 64) dispatch_glds2<OutT, 64, 4>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, p.kps, ep);
+    else if (p.stages == 4) dispatch_glds2<OutT, 32, 4>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, p.kps, ep);
+    else if (p.bk == 64) dispatch_glds2<OutT, 64, 2>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, p.kps, ep);
+    else if (p.stages == 3) dispatch_glds2<OutT, 32, 3>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, p.kps, ep);
+    else dispatch_glds2<OutT, 32, 2>(akc, bkc, grid, st, A, lda, B, ldb, C, M, N, K, p.kps, ep);
 }
 
 template <bool SAFE, typename OutT>
@@ -995,9 +949,7 @@ static void dispatch_bf16(bool akc, bool bkc, dim3 grid, hipStream_t st, const b
 
 // ------------------------------------------------------------------------------------------------ split-K
 // out (+)= sum over splits of the partial results written by the GEMM (deterministic: fixed summation order, no atomics)
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ ws, int64_t stride, int splits, float* __restrict__ out, int64_t n4,
-                                                            int accumulate) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void splitk_sum4(const float* __restrict__ ws, int64_t stride, int splits, float* __restrict__ out, int64_t n4, int accumulate, int64_t i) {
     if (i >= n4) return;
     // four independent partial sums: up to 32 loads per thread, 4 in flight instead of a dependent chain (fixed order: still deterministic)
     f32x4 a = accumulate ? ((const f32x4*)out)[i] : (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1011,6 +963,10 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     }
     for (; s < splits; ++s) a += *(const f32x4*)(p + (int64_t)s * stride);
     ((f32x4*)out)[i] = (a + b) + (c + d);
+}
+__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ ws, int64_t stride, int splits, float* __restrict__ out, int64_t n4,
+                                                            int accumulate) {
+    splitk_sum4(ws, stride, splits, out, n4, accumulate, (int64_t)blockIdx.x * 256 + threadIdx.x);
 }
 
 // The same sum followed by the FULL fused epilogue (bias -> aux -> act -> mul -> dropout -> residual, emo_gemm_epi.h) and the store in the output
@@ -1033,19 +989,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_epi_kernel(const float* __r
     epi_row8<OutT>(ep, C, m, n, v, N);
 }
 
-// K-splits of a bf16-output product with an epilogue (0 / 1 = none): a tile grid of at most 256 blocks and a long reduction
-static int64_t choose_epi_splits(int64_t M, int64_t N, int64_t K) {
-    const char* e = getenv("EMO_GEMM_EPI_SPLIT");                     // (read per call: tests toggle it in-process)
-    if ((e && atoi(e) == 0) || (N & 7) || (K % (4 * G2_BK)) != 0) return 1;
-    const int64_t tiles = cdiv64(M, GB_M) * cdiv64(N, GB_N);
-    // measured r04 (same-box A/B script of that round, rocprofv3 per kernel; profiles/r04_ab_epi_split*): stage 1's K = 2048 dgrads on 64 tiles 48 -> 22 + 6 us with 4 splits; at 256 tiles
-    // (batch-size-4 stage-2 dgrads) 2 splits only tie (52 -> 45 + 15 us: the 32 MB of fp32 partials cost what the second resident block gains)
-    if (tiles > 128) return 1;
-    // (K = 512 products on <= 64 tiles, 4 splits: 18.6 -> 13.4 + 5 us per launch, the step's kernel time unchanged at 89.9 vs 89.8 ms: not split)
-    return K >= 1024 ? 4 : 1;
-}
-
-// the same pass with a tail of blocks that adds up the bias-gradient partials of the 256 x 256 weight-gradient kernel: rs_out[i] += sum over
+// the plain pass with a tail of blocks that adds up the bias-gradient partials of the 256 x 256 weight-gradient kernel: rs_out[i] += sum over
 // rs_parts vectors of length rs_stride (fixed order)
 __global__ __launch_bounds__(256) void splitk_reduce_rs_kernel(const float* __restrict__ ws, int64_t stride, int splits, float* __restrict__ out, int64_t n4,
                                                                int accumulate, const float* __restrict__ rs_ws, int64_t rs_stride, int rs_parts,
@@ -1061,132 +1005,64 @@ __global__ __launch_bounds__(256) void splitk_reduce_rs_kernel(const float* __re
         ((f32x4*)rs_out)[i] = a + b;
         return;
     }
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n4) return;
-    f32x4 a = accumulate ? ((const f32x4*)out)[i] : (f32x4){0.f, 0.f, 0.f, 0.f};
-    f32x4 b = {0.f, 0.f, 0.f, 0.f}, c = {0.f, 0.f, 0.f, 0.f}, d = {0.f, 0.f, 0.f, 0.f};
-    const float* p = ws + 4 * i;
-    int s = 0;
-    for (; s + 4 <= splits; s += 4) {
-        const f32x4 x0 = *(const f32x4*)(p + (int64_t)s * stride), x1 = *(const f32x4*)(p + (int64_t)(s + 1) * stride);
-        const f32x4 x2 = *(const f32x4*)(p + (int64_t)(s + 2) * stride), x3 = *(const f32x4*)(p + (int64_t)(s + 3) * stride);
-        a += x0; b += x1; c += x2; d += x3;
-    }
-    for (; s < splits; ++s) a += *(const f32x4*)(p + (int64_t)s * stride);
-    ((f32x4*)out)[i] = (a + b) + (c + d);
+    splitk_sum4(ws, stride, splits, out, n4, accumulate, (int64_t)blockIdx.x * 256 + threadIdx.x);
 }
-void emo_splitk_reduce_rs_launch(const float* ws, int64_t stride, int splits, float* out, int64_t n4, int accumulate, const float* rs_ws, int64_t rs_stride,
-                                 int rs_parts, float* rs_out, hipStream_t st) {
-    const int64_t mb = cdiv64(n4, 256), rb = cdiv64(rs_stride >> 2, 256);
-    hipLaunchKernelGGL(splitk_reduce_rs_kernel, dim3((unsigned)(mb + rb)), dim3(256), 0, st, ws, stride, splits, out, n4, accumulate, rs_ws, rs_stride, rs_parts,
-                       rs_out, mb);
+// rs_ws = nullptr: the plain pass
+void emo_splitk_reduce_launch(const float* ws, int64_t stride, int splits, float* out, int64_t n4, int accumulate, const float* rs_ws, int64_t rs_stride, int rs_parts,
+                              float* rs_out, hipStream_t st) {
+    const int64_t mb = cdiv64(n4, 256);
+    if (rs_ws)
+        hipLaunchKernelGGL(splitk_reduce_rs_kernel, dim3((unsigned)(mb + cdiv64(rs_stride >> 2, 256))), dim3(256), 0, st, ws, stride, splits, out, n4, accumulate, rs_ws,
+                           rs_stride, rs_parts, rs_out, mb);
+    else hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)mb), dim3(256), 0, st, ws, stride, splits, out, n4, accumulate);
 }
 
-void emo_splitk_reduce_launch(const float* ws, int64_t stride, int splits, float* out, int64_t n4, int accumulate, hipStream_t st) {
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)cdiv64(n4, 256)), dim3(256), 0, st, ws, stride, splits, out, n4, accumulate);
-}
-
-// number of K-splits for a plain fp32-output GEMM (wgrad).  max_ws_splits > 0: partials go to a caller workspace (plain stores +
-// splitk_reduce_kernel); 0: fp32 atomics into C.
-static int64_t choose_splits(int64_t M, int64_t N, int64_t K, bool big, bool has_epi, int dtype_out, int64_t BMt, int64_t BNt, int64_t BKt,
-                             int64_t max_ws_splits) {
-    const int64_t tiles_m = cdiv64(M, BMt), tiles_n = cdiv64(N, BNt);
-    int64_t splits = 1;
-    if (dtype_out == EMO_F32 && !has_epi && tiles_m * tiles_n < 256 && K >= 8 * BKt) {
-        const int64_t max_splits = K / (4 * BKt);
-        if (big) {
-            // Cost model fitted to the r01 sweep (tools/bench_wgrad_splits.py of that round — git history —, M = 8k/32k/131k tokens): a 128^2 x 64 K-step takes ~1.1 us
-            // with one block per CU and ~1.4 us with two; blocks run in rounds of 512 (2 per CU); every split pays ~0.18 us per output
-            // tile for its fp32 atomics (device-scope atomics from 8 XCDs resolve beyond the L2s: ~0.3 TB/s), or ~0.03 us per tile for
-            // plain stores + its share of the reduce pass when a workspace is available.
-            static const int cand[] = {1, 2, 4, 8, 16, 24, 32};
-            const double tiles = (double)(tiles_m * tiles_n), ksteps = (double)cdiv64(K, BKt);
-            const double per_split = max_ws_splits > 0 ? 0.03 : 0.18;
-            double best = 1e30;
-            for (int c : cand) {
-                if (c > 1 && (c > max_splits || (max_ws_splits > 0 && c > max_ws_splits))) break;
-                const double blocks = tiles * c, rounds = (double)cdiv64((int64_t)blocks, 512);
-                const double t = rounds * (double)cdiv64((int64_t)ksteps, c) * (blocks > 256 ? 1.4 : 1.1) + c * tiles * per_split;
-                if (t < best) { best = t; splits = c; }
-            }
-        } else {
-            splits = cdiv64(512, tiles_m * tiles_n);
-            if (splits > max_splits) splits = max_splits;
-            if (splits >= 4) {                       // one K-split per XCD round (splitk_coords): keep the 8 XCDs evenly loaded
-                const int64_t r8 = cdiv64(splits, 8) * 8;
-                splits = r8 <= max_splits ? r8 : ((splits / 8) * 8 > 0 ? (splits / 8) * 8 : splits);
-            }
-            if (max_ws_splits > 0 && splits > max_ws_splits) splits = max_ws_splits;
-        }
-        if (splits < 1) splits = 1;
-        { const char* fs = getenv("EMO_GEMM_SPLITS"); if (fs && atoi(fs) > 0) splits = atoi(fs) <= max_splits ? atoi(fs) : max_splits; }   // tuning sweeps
-    }
-    return splits;
-}
-
+// ------------------------------------------------------------------------------------------------ validate -> plan -> execute
 // which kernel family the calling thread's last emo_gemm went to (diagnostics: bench.py attributes a launch to the kernel that RAN, not to the
-// one its shape suggests): 1 skinny (M <= 32), 2 A-stationary K = 512, 3 256 x 256 tile wgrad, 4 256 x 256 tile NT, 5 128 x 128 LDS-DMA ring,
-// 6 128 x 128 register-staged, 7 exact-fp32; + 16 split-K through the workspace, + 32 split-K with the reduce-and-epilogue pass
-static thread_local int g_last_gemm_kernel = 0;
+// one its shape suggests), and what ran inside that family: emo_hip.h (emo_gemm_last_kernel / emo_gemm_last_plan), written from the GemmPlan
+static thread_local int g_last_gemm_kernel = 0, g_last_gemm_plan = 0;
 extern "C" int emo_epilogue_size(void) { return (int)sizeof(emo_epilogue_t); }
 extern "C" int emo_gemm_last_kernel(void) { return g_last_gemm_kernel; }
-// what ran inside that family (emo_hip.h: emo_gemm_last_plan): BK | stages << 8 | splits << 16 | A-stationary column split << 24
-static thread_local int g_last_gemm_plan = 0;
-void emo_gemm_note_plan(int bk, int stages, int splits, int col_split) { g_last_gemm_plan = bk | stages << 8 | splits << 16 | col_split << 24; }
 extern "C" int emo_gemm_last_plan(void) { return g_last_gemm_plan; }
+extern "C" int emo_gemm_astat_supported(int dtype_in, int dtype_out, int64_t M, int64_t N, int64_t K) { return gp_astat_class(dtype_in, dtype_out, M, N, K) ? 1 : 0; }
+extern "C" int64_t emo_gemm_astat_min_rows(void) { return gp_astat_min_rows(); }
 
-// fp32 products: tile edge of the kernel that serves the shape (a pure function of the shape: the split-K plan and the workspace size follow it).
-// EMO_GEMM_F32_TILE=64 keeps every shape on the 64 x 64 kernel (A/B, tests).
-static int64_t f32_tile(int64_t M, int64_t N) {
-    const char* e = getenv("EMO_GEMM_F32_TILE");                 // (read per call: tests toggle it in-process)
-    const bool small_only = e != nullptr && atoi(e) == 64;
-    return (!small_only && M >= 128 && N >= 128) ? 128 : 64;
-}
-
-#define EMO_GEMM_MAX_SPLITS 32
+// the largest workspace a layout of this problem asks the planner for (split-K partials; behind them the 256 x 256 wgrad kernel's bias-gradient partials)
 extern "C" int64_t emo_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, int dtype_in, int dtype_out) {
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    if (dtype_in == EMO_BF16 && dtype_out == EMO_BF16) {               // split-K + reduce-with-epilogue of the small-grid long-K products
-        const int64_t es = choose_epi_splits(M, N, K);
-        return es > 1 ? es * M * N * (int64_t)sizeof(float) : 0;
+    if (M <= 0 || N <= 0 || K <= 0 || !(dtype_out == EMO_F32 || (dtype_in == EMO_BF16 && dtype_out == EMO_BF16))) return 0;
+    int64_t ws = 0, rs = 0;
+    for (int layout = 0; layout < 4; ++layout) {
+        GemmCall c = {};
+        c.a_trans = layout >> 1; c.b_trans = layout & 1; c.dtype_in = dtype_in; c.dtype_out = dtype_out; c.workspace_bytes = -1;
+        c.M = M; c.N = N; c.K = K; c.ldc = N; c.lda = ((c.a_trans ? M : K) + 7) & ~(int64_t)7; c.ldb = ((c.b_trans ? N : K) + 7) & ~(int64_t)7;
+        const GemmPlan p = gemm_plan(c);
+        if (!p.error && p.ws_floats > ws) ws = p.ws_floats;
+        if (!p.error && p.rs_floats > rs) rs = p.rs_floats;
     }
-    if (dtype_out != EMO_F32) return 0;
-    const bool big = dtype_in == EMO_BF16;
-    const int64_t BMt = big ? GB_M : f32_tile(M, N), BNt = big ? GB_N : f32_tile(M, N), BKt = big ? (gemm_variant() >= 2 ? G2_BK : GB_K) : 16;
-    int64_t splits = choose_splits(M, N, K, big, false, dtype_out, BMt, BNt, BKt, EMO_GEMM_MAX_SPLITS);
-    int64_t rs_floats = 0;
-    if (big) {                                                  // (layout unknown here: sized for the wgrad kernel too, with its bias-gradient partials)
-        const int64_t s2 = emo_gemm_w128_tn_splits(M, N, K);
-        if (s2 > splits) splits = s2;
-        if (s2 > 0) rs_floats = emo_gemm_w128_tn_rs_floats(M, N, s2);
-    }
-    return splits > 1 ? (splits * M * N + rs_floats) * (int64_t)sizeof(float) : 0;
+    return (ws + rs) * (int64_t)sizeof(float);
 }
 
-extern "C" int emo_gemm(const void* A, int a_trans, int64_t lda, const void* B, int b_trans, int64_t ldb, void* C,
-                        int64_t ldc, int64_t M, int64_t N, int64_t K, int dtype_in, int dtype_out, int accumulate,
-                        const emo_epilogue_t* e, emo_stream_t stream) {
-    hipStream_t st = (hipStream_t)stream;
+// emo_gemm's argument checks, then the plan: on success the call as routing sees it (c), as the kernels see it (ep), and its route (p)
+static int gemm_route(const void* A, int a_trans, int64_t lda, const void* B, int b_trans, int64_t ldb, const void* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
+                      int dtype_in, int dtype_out, int accumulate, const emo_epilogue_t* e, GemmCall& c, EpiParams& ep, GemmPlan& p) {
     EMO_CHECK(A && B && C, "emo_gemm: null pointer");
     EMO_CHECK(M > 0 && N > 0 && K > 0, "emo_gemm: bad dims M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
     EMO_CHECK(dtype_in == EMO_F32 || dtype_in == EMO_BF16, "emo_gemm: bad dtype_in");
     EMO_CHECK(dtype_out == EMO_F32 || dtype_out == EMO_BF16, "emo_gemm: bad dtype_out");
     EMO_CHECK(!(accumulate && dtype_out != EMO_F32), "emo_gemm: accumulate needs fp32 output");
     EMO_CHECK(!(dtype_in == EMO_F32 && dtype_out != EMO_F32), "emo_gemm: fp32 inputs need fp32 output");
-    EpiParams ep;
     memset(&ep, 0, sizeof(ep));
     ep.ldc = ldc;
     ep.accumulate = accumulate;
     ep.drop = make_drop(0.f, 0, 0);
 #ifdef EMO_DIAG
-    { const char* ab = getenv("EMO_GEMM_ABLATE"); ep.ablate = ab ? atoi(ab) : 0; }
+    ep.ablate = gp_env_int("EMO_GEMM_ABLATE", 0);
 #endif
-    bool has_epi = false;
     if (e) {
         ep.bias = e->bias; ep.act = e->act; ep.aux_out = e->aux_out; ep.mul_aux = e->mul_aux;
         ep.mul_mode = e->mul_aux ? e->mul_mode : EMO_MUL_NONE; ep.mul_scale = e->mul_scale;
         ep.drop = make_drop(e->p_drop, e->seed, e->offset); ep.residual = e->residual;
-        has_epi = e->bias || e->act || e->aux_out || ep.mul_mode || ep.drop.thr16 || e->residual;
+        const bool has_epi = e->bias || e->act || e->aux_out || ep.mul_mode || ep.drop.thr16 || e->residual;
         ep.a_rowsum = e->a_rowsum; ep.b_rowsum = e->b_rowsum; ep.mask_out = e->mask_out;
         ep.ln_c1 = e->ln_c1; ep.ln_stats_out = e->ln_stats_out; ep.ln_eps = e->ln_eps;
         ep.rln_x = e->rln_x; ep.rln_stats = e->rln_stats; ep.rln_gamma = e->rln_gamma; ep.rln_beta = e->rln_beta;
@@ -1206,182 +1082,132 @@ extern "C" int emo_gemm(const void* A, int a_trans, int64_t lda, const void* B, 
                   "emo_gemm: rln_x needs rln_stats/gamma/beta and no activation / dropout / mul epilogue");
         EMO_CHECK(!e->ln_stats_out || e->ln_c1, "emo_gemm: ln_stats_out needs ln_c1");
     }
-    const bool ln_fused = e && (e->ln_c1 || e->rln_x);
     EMO_CHECK(!(ep.a_rowsum && ep.b_rowsum), "emo_gemm: a_rowsum and b_rowsum are exclusive");
-    if (ep.b_rowsum) {
-        EMO_CHECK(a_trans && b_trans, "emo_gemm: b_rowsum needs a_trans and b_trans (B stored [K, N]: the Conv1D wgrad layout)");
-        const bool in_kernel = dtype_in == EMO_BF16 && dtype_out == EMO_F32 && gemm_variant_for(a_trans, K) < 3 && !use_safe_tr();
-        if (!in_kernel) {
-            const int rc = emo_colsum(B, dtype_in, K, N, ldb, ep.b_rowsum, 1, stream);
-            if (rc) return rc;
-            ep.b_rowsum = nullptr;
-        }
-    }
-    if (ep.a_rowsum) {
-        EMO_CHECK(a_trans, "emo_gemm: a_rowsum needs a_trans (A stored [K, M]: the wgrad layout)");
-        const bool in_kernel = dtype_in == EMO_BF16 && dtype_out == EMO_F32 && b_trans && gemm_variant_for(a_trans, K) < 3 && !use_safe_tr();
-        if (!in_kernel) {                                   // other kernels: the plain column-sum launch over A [K, M]
-            const int rc = emo_colsum(A, dtype_in, K, M, lda, ep.a_rowsum, 1, stream);
-            if (rc) return rc;
-            ep.a_rowsum = nullptr;
-        }
-    }
-    const bool big = dtype_in == EMO_BF16;
-    const int variant = big ? gemm_variant_for(a_trans, K) : 0;
-    if (big && M <= 32 && !a_trans && !b_trans && (K % 32) == 0 && (lda & 7) == 0 && (ldb & 7) == 0 && (((uintptr_t)A | (uintptr_t)B) & 15) == 0 &&
-        !accumulate) {
-        dim3 g((unsigned)cdiv64(N, 16));
-        const int nw = K >= 2048 ? 16 : (K >= 1024 ? 8 : 4);   // 16 waves x two 64-wide chunks at K = 2048
+    EMO_CHECK(!ep.b_rowsum || (a_trans && b_trans), "emo_gemm: b_rowsum needs a_trans and b_trans (B stored [K, N]: the Conv1D wgrad layout)");
+    EMO_CHECK(!ep.a_rowsum || a_trans, "emo_gemm: a_rowsum needs a_trans (A stored [K, M]: the wgrad layout)");
+    const auto low4 = [](const void* q) { return (unsigned)((uintptr_t)q & 15); };
+    c = GemmCall{};
+    c.a_trans = a_trans; c.b_trans = b_trans; c.dtype_in = dtype_in; c.dtype_out = dtype_out; c.accumulate = accumulate;
+    c.M = M; c.N = N; c.K = K; c.lda = lda; c.ldb = ldb; c.ldc = ldc;
+    c.a_bits = low4(A); c.b_bits = low4(B); c.c_bits = low4(C); c.rowsum_bits = low4(ep.a_rowsum) | low4(ep.b_rowsum); c.bias_bits = low4(ep.bias); c.residual_bits = low4(ep.residual);
+    if (e && e->workspace && e->workspace_bytes > 0) { c.workspace_bytes = e->workspace_bytes; c.ws_bits = low4(e->workspace); }
+    c.act = ep.act; c.mul_mode = ep.mul_mode; c.bias = ep.bias; c.aux_out = ep.aux_out; c.drop = ep.drop.thr16 != 0; c.residual = ep.residual;
+    c.a_rowsum = ep.a_rowsum; c.b_rowsum = ep.b_rowsum; c.mask_out = ep.mask_out; c.ln_fused = ep.ln_c1 || ep.rln_x; c.lna = ep.lna_gamma; c.hdiv = ep.hdiv;
+    c.drop_index_64 = c.drop && (uint64_t)M * (uint64_t)N >= (1ull << 32);
+    p = gemm_plan(c);
+    EMO_CHECK(!p.error, "%s", p.error);
+    return EMO_OK;
+}
+extern "C" int emo_gemm_route(const void* A, int a_trans, int64_t lda, const void* B, int b_trans, int64_t ldb, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
+                              int dtype_in, int dtype_out, int accumulate, const emo_epilogue_t* e, int* kernel, int* plan) {
+    GemmCall c; EpiParams ep; GemmPlan p;
+    const int rc = gemm_route(A, a_trans, lda, B, b_trans, ldb, C, ldc, M, N, K, dtype_in, dtype_out, accumulate, e, c, ep, p);
+    if (rc) return rc;
+    if (kernel) *kernel = p.last_kernel();
+    if (plan) *plan = p.last_plan();
+    return EMO_OK;
+}
+
+// family 1: p.stages waves per block
+static void gemm_skinny_launch(const GemmPlan& p, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, int dtype_out, int64_t M, int64_t N, int64_t K,
+                               const EpiParams& ep, hipStream_t st) {
 #define SKINNY_LAUNCH(OutT, NWv, CWv)                                                                                                       \
     do {                                                                                                                                    \
         constexpr size_t lds_ = (size_t)NWv * 48 * (CWv + 16) * 2 + sizeof(f32x4) * (NWv - 1) * 2 * 64 + sizeof(float) * NWv * 2 * 16 * 2;   \
         auto kfn = gemm_bf16_skinny_kernel<OutT, NWv, CWv>;                                                                                 \
         static bool attr_ = false;                                                                                                          \
         if (!attr_) { (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_); attr_ = true; }   \
-        hipLaunchKernelGGL(kfn, g, dim3(64 * NWv), lds_, st, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, (OutT*)C, M, N, K, ep);          \
+        hipLaunchKernelGGL(kfn, dim3(p.grid_x), dim3(64 * NWv), lds_, st, A, lda, B, ldb, (OutT*)C, M, N, K, ep);                           \
     } while (0)
-        if (dtype_out == EMO_F32) { if (nw == 16) SKINNY_LAUNCH(float, 16, 64); else if (nw == 8) SKINNY_LAUNCH(float, 8, 128); else SKINNY_LAUNCH(float, 4, 128); }
-        else { if (nw == 16) SKINNY_LAUNCH(bf16_t, 16, 64); else if (nw == 8) SKINNY_LAUNCH(bf16_t, 8, 128); else SKINNY_LAUNCH(bf16_t, 4, 128); }
+    const int nw = p.stages;
+    if (dtype_out == EMO_F32) { if (nw == 16) SKINNY_LAUNCH(float, 16, 64); else if (nw == 8) SKINNY_LAUNCH(float, 8, 128); else SKINNY_LAUNCH(float, 4, 128); }
+    else { if (nw == 16) SKINNY_LAUNCH(bf16_t, 16, 64); else if (nw == 8) SKINNY_LAUNCH(bf16_t, 8, 128); else SKINNY_LAUNCH(bf16_t, 4, 128); }
 #undef SKINNY_LAUNCH
-        EMO_LAUNCH_CHECK();
-        g_last_gemm_kernel = 1;
-        emo_gemm_note_plan(nw >= 16 ? 64 : 128, nw, 0, 0);                 // (chunk width, waves)
-        return EMO_OK;
-    }
-#ifdef EMO_EXPERIMENTAL
-    if (big && !a_trans && !b_trans && !ln_fused && !accumulate && !use_safe_tr() && !ep.lna_gamma && !ep.hdiv) {
-        const int pk = emo_gemm_p256_try((const bf16_t*)A, lda, (const bf16_t*)B, ldb, C, dtype_out, M, N, K, ep, st);   // opt-in persistent tile walks (r05)
-        if (pk) {
-            EMO_LAUNCH_CHECK();
-            g_last_gemm_kernel = pk;                              // 8: 256 x 256 tile, 9: 128 x 512 tile
-            return EMO_OK;
-        }
-    }
-#endif
-    if (big && !a_trans && !b_trans && !ln_fused && !use_safe_tr() &&
-        emo_gemm_astat_try((const bf16_t*)A, lda, (const bf16_t*)B, ldb, C, dtype_out, M, N, K, ep, st)) {   // K = 512, A stationary in registers
-        EMO_LAUNCH_CHECK();
-        g_last_gemm_kernel = 2;
-        return EMO_OK;
-    }
-    if (big && a_trans && b_trans && dtype_out == EMO_F32 && !has_epi && !ln_fused && !use_safe_tr() && e &&
-        emo_gemm_w128_tn_try((const bf16_t*)A, lda, (const bf16_t*)B, ldb, (float*)C, ldc, M, N, K, accumulate, ep.a_rowsum, ep.b_rowsum, e->workspace,
-                             e->workspace_bytes, st)) {
-        EMO_LAUNCH_CHECK();
-        g_last_gemm_kernel = 3;
-        return EMO_OK;
-    }
-    EMO_CHECK(!ep.lna_gamma, "emo_gemm: lna_* (LayerNorm of the A operand) exists only on the A-stationary kernel: bf16, NT, K = 512, M %% 128 == 0, M >= 4096, N %% 64 == 0, N <= 2048");
-    EMO_CHECK(!ep.hdiv, "emo_gemm: hdiv exists only on the A-stationary kernel and this call was refused by it (alignment / strides / EMO_GEMM_NO_ASTAT)");
-    if (big && !a_trans && !b_trans && !ln_fused && !accumulate &&
-        emo_gemm_w128_try((const bf16_t*)A, lda, (const bf16_t*)B, ldb, C, dtype_out, M, N, K, ep, st)) {    // long-K NT products on 256 x 256 tiles (opt-in)
-        EMO_LAUNCH_CHECK();
-        g_last_gemm_kernel = 4;
-        return EMO_OK;
-    }
-    EMO_CHECK(!ep.mask_out && ep.mul_mode != EMO_MUL_BITMASK, "emo_gemm: mask_out / EMO_MUL_BITMASK need bf16 in/out, NT, K = 512, M %% 128 == 0, M >= 4096, N %% 64 == 0, N <= 2048");
-    EMO_CHECK(!ln_fused, "emo_gemm: the LayerNorm-folded epilogue (ln_c1 / rln_x) exists only on the skinny path (bf16, M <= 32, NT, K %% 32 == 0)");
-    const int64_t BMt = big ? GB_M : f32_tile(M, N), BNt = big ? GB_N : f32_tile(M, N);
-    const int64_t BKt = big ? (variant >= 2 ? G2_BK : GB_K) : 16;
-    const int64_t tiles_m = cdiv64(M, BMt), tiles_n = cdiv64(N, BNt);
-    const int64_t tiles_m8 = cdiv64(tiles_m, 8) * 8;
-    // split-K: only for plain fp32 outputs (wgrad) when the tile grid cannot fill the chip
-    void* ws = e ? e->workspace : nullptr;
-    const int64_t ws_bytes = e ? e->workspace_bytes : 0;
-    const bool ws_ok = ws && ldc == N && ((M * N) & 3) == 0 && ((uintptr_t)ws & 15) == 0 && getenv("EMO_GEMM_SPLIT_ATOMIC") == nullptr;
-    int64_t max_ws_splits = ws_ok ? ws_bytes / (M * N * (int64_t)sizeof(float)) : 0;
-    int64_t splits = choose_splits(M, N, K, big, has_epi, dtype_out, BMt, BNt, BKt, max_ws_splits >= 2 ? max_ws_splits : 0);
-    if (ldc != N) splits = 1;                                // split-K partials need a contiguous C: a strided output view runs unsplit
-    // bf16 outputs (with or without an epilogue) on a small tile grid: split-K through the workspace + splitk_reduce_epi_kernel
+}
+
+// families 5 / 6 / 7: the 128 x 128 bf16 tiles and the fp32 kernels, with their split-K passes
+static int gemm_tiled_launch(const GemmPlan& p, const GemmCall& c, const void* A, const void* B, void* C, void* ws, EpiParams ep, hipStream_t st) {
+    const int64_t M = c.M, N = c.N, K = c.K, lda = c.lda, ldb = c.ldb;
     EpiParams ep_final = ep;
-    bool epi_split = false;
-    if (big && dtype_out == EMO_BF16 && !accumulate && ldc == N && ws_ok && variant >= 2 && !use_safe_tr() && (!a_trans || variant >= 3) && !ep.a_rowsum && !ep.b_rowsum) {
-        const int64_t es = choose_epi_splits(M, N, K);
-        if (es > 1 && max_ws_splits >= es) {
-            splits = es;
-            epi_split = true;
-            ep.bias = nullptr; ep.act = EMO_ACT_NONE; ep.aux_out = nullptr; ep.mul_aux = nullptr; ep.mul_mode = EMO_MUL_NONE; ep.mul_scale = 1.f;
-            ep.drop = make_drop(0.f, 0, 0); ep.residual = nullptr;
-        }
+    if (p.epi_split) {                                       // the GEMM pass of an epilogue split writes raw fp32 partial sums
+        ep.bias = nullptr; ep.act = EMO_ACT_NONE; ep.aux_out = nullptr; ep.mul_aux = nullptr; ep.mul_mode = EMO_MUL_NONE; ep.mul_scale = 1.f;
+        ep.drop = make_drop(0.f, 0, 0); ep.residual = nullptr;
     }
-    const int kdt = epi_split ? EMO_F32 : dtype_out;         // the GEMM pass of an epilogue split writes raw fp32 partial sums
-    int64_t kps = cdiv64(cdiv64(K, splits), BKt) * BKt;
-    splits = cdiv64(K, kps);
-    const bool use_ws = splits > 1 && max_ws_splits >= splits;
-    const int accumulate_final = accumulate;
-    if (splits > 1) {
-        EMO_CHECK(ldc == N, "emo_gemm: split-K needs contiguous C");
-        if (use_ws) {
-            ep.ws_stride = M * N;
-            ep.accumulate = 0;
-        } else if (!accumulate) {
-            hipError_t me = hipMemsetAsync(C, 0, (size_t)(M * N) * sizeof(float), st);
-            EMO_CHECK(me == hipSuccess, "emo_gemm: memset failed");
-        }
-        ep.atomic = (splits == 2 || splits == 4) ? (int)(8 / splits) : 1;
+    if (p.use_ws) { ep.ws_stride = M * N; ep.accumulate = 0; }
+    else if (p.memset_c) {
+        hipError_t me = hipMemsetAsync(C, 0, (size_t)(M * N) * sizeof(float), st);
+        EMO_CHECK(me == hipSuccess, "emo_gemm: memset failed");
     }
-    void* const C_final = C;
-    if (use_ws) C = ws;
-    dim3 grid((unsigned)(tiles_m8 * tiles_n), 1, 1);
-    if (splits > 1)   // see splitk_coords()
-        grid.x = ep.atomic > 1 ? (unsigned)(8 * cdiv64(tiles_m * tiles_n, ep.atomic)) : (unsigned)(tiles_m * tiles_n * (cdiv64(splits, 8) * 8));
-    g_last_gemm_kernel = (dtype_in == EMO_F32 ? 7 : 6) + (use_ws ? (epi_split ? 32 : 16) : 0);
-    emo_gemm_note_plan(dtype_in == EMO_F32 ? 16 : GB_K, 0, splits > 1 ? (int)splits : 0, 0);      // (dispatch_glds overwrites BK / stages with its ring)
-    if (dtype_in == EMO_F32) {
-        const float* a = (const float*)A;
-        const float* b = (const float*)B;
-        const int64_t sam = a_trans ? 1 : lda, sak = a_trans ? lda : 1;
-        const int64_t sbn = b_trans ? 1 : ldb, sbk = b_trans ? ldb : 1;
-        // 128 x 128 tile kernel when one of each operand's two strides is 1 (always, for the layouts emo_gemm takes); vector loads need 16-B aligned
-        // bases and non-unit strides that are multiples of 4 elements
-        const bool akc = sak == 1, bkc = sbk == 1;
-        if (BMt == 128 && (akc || sam == 1) && (bkc || sbn == 1)) {
-            const int av = (((uintptr_t)a & 15) == 0 && ((akc ? sam : sak) & 3) == 0 && (kps & 3) == 0) ? 1 : 0;
-            const int bv = (((uintptr_t)b & 15) == 0 && ((bkc ? sbn : sbk) & 3) == 0 && (kps & 3) == 0) ? 1 : 0;
-#define F3_LAUNCH(AKv, BKv) hipLaunchKernelGGL((gemm_f32_t128_kernel<AKv, BKv>), grid, dim3(256), 0, st, a, sam, sak, b, sbn, sbk, (float*)C, M, N, K, kps, ep, av, bv)
+    ep.atomic = p.atomic;
+    void* const Ck = p.use_ws ? ws : C;
+    const dim3 grid(p.grid_x, 1, 1);
+    const bool f32_out = p.epi_split || c.dtype_out == EMO_F32, akc = !c.a_trans, bkc = !c.b_trans;
+    if (p.family == 7) {
+        const float *a = (const float*)A, *b = (const float*)B;
+        const int64_t sam = akc ? lda : 1, sak = akc ? 1 : lda, sbn = bkc ? ldb : 1, sbk = bkc ? 1 : ldb;
+        if (p.f32_tile == 128) {
+            // vector loads need 16-B aligned bases and non-unit strides that are multiples of 4 elements
+            const int av = (c.a_bits == 0 && (lda & 3) == 0 && (p.kps & 3) == 0) ? 1 : 0;
+            const int bv = (c.b_bits == 0 && (ldb & 3) == 0 && (p.kps & 3) == 0) ? 1 : 0;
+#define F3_LAUNCH(AKv, BKv) hipLaunchKernelGGL((gemm_f32_t128_kernel<AKv, BKv>), grid, dim3(256), 0, st, a, sam, sak, b, sbn, sbk, (float*)Ck, M, N, K, p.kps, ep, av, bv)
             if (akc && bkc) F3_LAUNCH(true, true); else if (akc) F3_LAUNCH(true, false); else if (bkc) F3_LAUNCH(false, true); else F3_LAUNCH(false, false);
 #undef F3_LAUNCH
-        } else {
-            EMO_CHECK(BMt == 64, "emo_gemm(fp32): operand with two non-unit strides on the 128-tile plan");
-            hipLaunchKernelGGL(gemm_f32_kernel<float>, grid, dim3(256), 0, st, a, sam, sak, b, sbn, sbk, (float*)C, M, N, K, kps, ep);
-        }
+        } else hipLaunchKernelGGL(gemm_f32_kernel<float>, grid, dim3(256), 0, st, a, sam, sak, b, sbn, sbk, (float*)Ck, M, N, K, p.kps, ep);
     } else {
-        EMO_CHECK((lda & 7) == 0 && (ldb & 7) == 0, "emo_gemm(bf16): lda/ldb must be multiples of 8 (16-B rows)");
-        EMO_CHECK(((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0, "emo_gemm(bf16): A/B must be 16-B aligned");
-        const bf16_t* a = (const bf16_t*)A;
-        const bf16_t* b = (const bf16_t*)B;
-        const bool akc = !a_trans, bkc = !b_trans;
-        const bool safe = use_safe_tr();
-        const int64_t rowsA = a_trans ? G2_BK : M, rowsB = b_trans ? G2_BK : N;
-        const int64_t spanA = (rowsA * lda + (a_trans ? M : 0)) * 2, spanB = (rowsB * ldb + (b_trans ? N : 0)) * 2;
-        const bool span_ok = spanA < (int64_t)0xFFFF0000 && spanB < (int64_t)0xFFFF0000;
-        const bool glds_ok = !safe && variant >= 2 && (akc || variant >= 3) && (K % G2_BK) == 0 && (kps % G2_BK) == 0 && M >= 8 && N >= 8 && span_ok;
-        if (glds_ok) {
-            g_last_gemm_kernel += 5 - 6;
-            if (kdt == EMO_F32) dispatch_glds<float>(akc, bkc, grid, st, a, lda, b, ldb, C, M, N, K, kps, ep);
-            else dispatch_glds<bf16_t>(akc, bkc, grid, st, a, lda, b, ldb, C, M, N, K, kps, ep);
-        } else if (kdt == EMO_F32) {   // register-staged v1 (same 128^2 grid; any K, predicated edges)
-            if (safe) dispatch_bf16<true, float>(akc, bkc, grid, st, a, lda, b, ldb, C, M, N, K, kps, ep);
-            else dispatch_bf16<false, float>(akc, bkc, grid, st, a, lda, b, ldb, C, M, N, K, kps, ep);
+        const bf16_t *a = (const bf16_t*)A, *b = (const bf16_t*)B;
+        if (p.ring) {
+            if (f32_out) dispatch_glds<float>(p, akc, bkc, grid, st, a, lda, b, ldb, Ck, M, N, K, ep);
+            else dispatch_glds<bf16_t>(p, akc, bkc, grid, st, a, lda, b, ldb, Ck, M, N, K, ep);
+        } else if (f32_out) {   // register-staged v1 (same 128^2 grid; any K, predicated edges)
+            if (p.safe) dispatch_bf16<true, float>(akc, bkc, grid, st, a, lda, b, ldb, Ck, M, N, K, p.kps, ep);
+            else dispatch_bf16<false, float>(akc, bkc, grid, st, a, lda, b, ldb, Ck, M, N, K, p.kps, ep);
         } else {
-            if (safe) dispatch_bf16<true, bf16_t>(akc, bkc, grid, st, a, lda, b, ldb, C, M, N, K, kps, ep);
-            else dispatch_bf16<false, bf16_t>(akc, bkc, grid, st, a, lda, b, ldb, C, M, N, K, kps, ep);
+            if (p.safe) dispatch_bf16<true, bf16_t>(akc, bkc, grid, st, a, lda, b, ldb, Ck, M, N, K, p.kps, ep);
+            else dispatch_bf16<false, bf16_t>(akc, bkc, grid, st, a, lda, b, ldb, Ck, M, N, K, p.kps, ep);
         }
     }
     EMO_LAUNCH_CHECK();
-    if (use_ws && epi_split) {
+    if (p.epi_split) {
         ep_final.atomic = 0; ep_final.ws_stride = 0; ep_final.accumulate = 0; ep_final.ldc = N;
-        hipLaunchKernelGGL(splitk_reduce_epi_kernel<bf16_t>, dim3((unsigned)cdiv64(M * N / 8, 256)), dim3(256), 0, st, (const float*)ws, M * N, (int)splits,
-                           (bf16_t*)C_final, M, N, ep_final);
-        EMO_LAUNCH_CHECK();
-    } else if (use_ws) {
-        const int64_t n4 = (M * N) >> 2;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)cdiv64(n4, 256)), dim3(256), 0, st, (const float*)ws, M * N, (int)splits, (float*)C_final, n4,
-                           accumulate_final);
-        EMO_LAUNCH_CHECK();
-    }
+        hipLaunchKernelGGL(splitk_reduce_epi_kernel<bf16_t>, dim3((unsigned)cdiv64(M * N / 8, 256)), dim3(256), 0, st, (const float*)ws, M * N, p.splits, (bf16_t*)C, M, N,
+                           ep_final);
+    } else if (p.use_ws) emo_splitk_reduce_launch((const float*)ws, M * N, p.splits, (float*)C, (M * N) >> 2, c.accumulate, nullptr, 0, 0, nullptr, st);
     return EMO_OK;
 }
+
+extern "C" int emo_gemm(const void* A, int a_trans, int64_t lda, const void* B, int b_trans, int64_t ldb, void* C,
+                        int64_t ldc, int64_t M, int64_t N, int64_t K, int dtype_in, int dtype_out, int accumulate,
+                        const emo_epilogue_t* e, emo_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    GemmCall c; EpiParams ep; GemmPlan p;
+    int rc = gemm_route(A, a_trans, lda, B, b_trans, ldb, C, ldc, M, N, K, dtype_in, dtype_out, accumulate, e, c, ep, p);
+    if (rc) return rc;
+    if (p.colsum_b) {                                        // a bias gradient the chosen kernel cannot produce: the plain column-sum launch over the operand
+        if ((rc = emo_colsum(B, dtype_in, K, N, ldb, ep.b_rowsum, 1, stream))) return rc;
+        ep.b_rowsum = nullptr;
+    }
+    if (p.colsum_a) {
+        if ((rc = emo_colsum(A, dtype_in, K, M, lda, ep.a_rowsum, 1, stream))) return rc;
+        ep.a_rowsum = nullptr;
+    }
+    const bf16_t *a = (const bf16_t*)A, *b = (const bf16_t*)B;
+    void* const ws = e ? e->workspace : nullptr;
+    switch (p.family) {
+        case 1: gemm_skinny_launch(p, a, lda, b, ldb, C, dtype_out, M, N, K, ep, st); break;
+        case 2: emo_gemm_astat_launch(p, a, lda, b, ldb, C, dtype_out, M, N, ep, st); break;
+        case 3: emo_gemm_w128_tn_launch(p, a, lda, b, ldb, (float*)C, M, N, K, accumulate, ep.a_rowsum, ep.b_rowsum, (float*)ws, st); break;
+        case 4: emo_gemm_w128_launch(p, a, lda, b, ldb, C, M, N, K, ep, st); break;
+#ifdef EMO_EXPERIMENTAL
+        case 8: case 9: emo_gemm_p256_launch(p, a, lda, b, ldb, C, M, N, K, ep, st); break;
+#endif
+        default: if ((rc = gemm_tiled_launch(p, c, A, B, C, ws, ep, st))) return rc;
+    }
+    EMO_LAUNCH_CHECK();
+    g_last_gemm_kernel = p.last_kernel();
+    g_last_gemm_plan = p.last_plan();
+    return EMO_OK;
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // column sums (bias gradients): HBM-bound stream.  A thread owns 16 B of columns (8 bf16 / 4 f32), a wave a

@@ -23,8 +23,8 @@
 
 namespace {
 constexpr int AS_K = 512, AS_BM = 128, AS_BN = 64, AS_KS = 128, AS_SLOT = AS_BN * AS_KS * 2, AS_RING = 4 * AS_SLOT;
-constexpr int AS_MIN_BLOCKS = 32;                              // = ops.ASTAT_MIN_ROWS / 128 (ops.gemm_bitmask_ok mirrors it): below one panel per CU the columns are split
 constexpr int AS_MAXN = 2048;                                   // bias copy in LDS: 8 KB
+static_assert(AS_K == GP_AS_K && AS_BM == GP_AS_BM && AS_BN == GP_AS_BN && AS_KS == GP_AS_KS && AS_MAXN == GP_AS_MAXN, "emo_gemm_plan.h plans for this geometry");
 
 // sum over the four 16-lane rows of a wave (lanes l % 16 + 16 j), result in every lane: two VALU lane swaps (permlane32_swap / permlane16_swap)
 __device__ __forceinline__ float as_sum_lane_rows(float x) {
@@ -145,7 +145,6 @@ __device__ __forceinline__ void as_unpack8(const u32x4& r, float (&t)[8]) {
 // The epilogue is specialised at COMPILE time (FL = feature flags): with run-time `ep.*` tests the column-tile epilogue was ~650 lines of
 // branchy code per tile (dead mul / residual / aux paths with their own `s_waitcnt vmcnt(0)`, per-lane parity branches of the dropout
 // hash) and took 35-52 % of a wave's cycles (s_memtime, tools/astat_cycles.py); the flag sets the Performer step uses are straight-line.
-enum { AF_RELU = 1, AF_DROP = 2, AF_RES = 4, AF_BITS = 8, AF_MASKOUT = 16, AF_GENERIC = 32, AF_DGELU = 64, AF_GELUAUX = 128, AF_HDIV = 256 };   // (DGELU, GELUAUX: GPT-2's MLP; HDIV: emo_hip.h hdiv)
 
 // 8 consecutive elements starting at a multiple of 8 of a 32-bit linear index: two hashes + two xorshifts, no parity branch, no 64-bit
 // arithmetic (bit-identical to drop_mult(); the launcher sends outputs of 2^32 elements or more to the generic epilogue)
@@ -632,75 +631,30 @@ __global__ __launch_bounds__(256, 2) void gemm_astat_kernel(const bf16_t* __rest
 }
 }  // namespace
 
-bool emo_gemm_astat_try(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, int dtype_out, int64_t M, int64_t N, int64_t K,
-                        const EpiParams& ep_in, hipStream_t st) {
-    EpiParams ep = ep_in;
-    const bool off = getenv("EMO_GEMM_NO_ASTAT") != nullptr;      // (read per call: the parity test toggles it in-process)
-    // one block owns a 128-row panel and sweeps all of N: the grid is M / 128 blocks.  Below one panel per CU (the reference's batch_size 4:
-    // 64 panels) the column tiles of a panel are split over blockIdx.y, every block keeping at least two column tiles (r05; until then these
-    // shapes ran on the 128 x 128 tiling at 0.15 of the MFMA peak)
-    int64_t min_rows = (int64_t)AS_BM * AS_MIN_BLOCKS;
-    { const char* e = getenv("EMO_ASTAT_MIN_ROWS"); if (e && atoll(e) > 0) min_rows = atoll(e); }      // (A/B of the column split; ops.py reads the same variable)
-    if (off || K != AS_K || (M % AS_BM) != 0 || M < min_rows || (N % AS_BN) != 0 || N > AS_MAXN || N < AS_BN) return false;
-    if (ep.atomic || ep.accumulate || ep.ws_stride || ep.a_rowsum || ep.b_rowsum || ep.ln_c1 || ep.rln_x) return false;
-    if (ep.hdiv && dtype_out != EMO_BF16) return false;
-    if ((ep.mask_out || ep.mul_mode == EMO_MUL_BITMASK) && dtype_out != EMO_BF16) return false;
-    if (ep.act == EMO_ACT_GELU || ep.mul_mode == EMO_MUL_DGELU) return false;          // (exact erf GELU: the generic tiled epilogue only)
-    if ((lda & 7) || (ldb & 7) || (ep.ldc & 7) || (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15)) return false;
-    if ((uint64_t)(AS_BN * ldb + AS_K) * 2 >= 0xFFFF0000ull) return false;
+void emo_gemm_astat_launch(const GemmPlan& p, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, int dtype_out, int64_t M, int64_t N, EpiParams ep,
+                           hipStream_t st) {
     const size_t lds = AS_RING + AS_MAXN * sizeof(float);
-    const int n_tiles_all = (int)(N / AS_BN);
-    int split = 1;
-    // the smallest split that gives every CU one block — two for the long column sweeps (N >= 2048), where a lone block per CU leaves the MFMA pipe
-    // without a partner wave for 32 column tiles (tools/bench_astat_split.py at 8192 / 16384 / 32768 rows; GPT-2 step at 32768 tokens, whose
-    // products ran one block per CU: 19.0 -> 18.4 ms with two)
-    const int64_t want_blocks = N >= 2048 ? 512 : 256;
-    if (M / AS_BM < want_blocks)
-        for (int sp = 2; sp <= n_tiles_all / 2; ++sp)
-            if (n_tiles_all % sp == 0) {
-                split = sp;
-                if ((M / AS_BM) * sp >= want_blocks) break;
-            }
-    { const char* e = getenv("EMO_ASTAT_SPLIT"); if (e && atoi(e) > 0 && n_tiles_all % atoi(e) == 0) split = atoi(e); }      // (tests / experiments)
-    const int tiles_per_block = n_tiles_all / split;
-    dim3 grid((unsigned)(M / AS_BM), (unsigned)split);
-    // Non-temporal output stores only for the FFN1 forward (the mask-out instance: 537 MB + the mask, read back once by the FFN2 forward).  r02
-    // streamed every output beyond the 256-MB MALL; r03 per-instance sweep inside the step (EMO_ASTAT_NT_MASK, same box, 3 alternations):
-    // all three large outputs 46.40 ms/step, FFN1 only 46.15, none 46.45 (the A-stationary kernels then run 0.9 ms faster and the kernels that
-    // read the outputs 0.7 ms slower).  PMC: with nt stores WRITE_SIZE is 1.31 x the algorithmic bytes.
-    ep.nt_store = (M * N * 2 >= (int64_t)256 << 20 && ep.mask_out) ? 1 : 0;
-    { const char* e = getenv("EMO_ASTAT_NT"); if (e) ep.nt_store = atoi(e); }
-    { const char* e = getenv("EMO_ASTAT_A_NT"); ep.a_nt = e ? atoi(e) : 0; }
-    { const char* e = getenv("EMO_ASTAT_NT_MASK");                 // diagnostics: 1 = mask-out instance, 2 = bit-mask instance, 4 = the others (outputs >= 256 MB)
-      if (e && M * N * 2 >= (int64_t)256 << 20) { const int m = atoi(e); ep.nt_store = (m & (ep.mask_out ? 1 : (ep.mul_mode == EMO_MUL_BITMASK ? 2 : 4))) ? 1 : 0; } }
+    const dim3 grid(p.grid_x, p.grid_y);
+    ep.nt_store = p.nt_store; ep.a_nt = p.a_nt;
 #define AS_LAUNCH(OutT, FLv)                                                                                                              \
     do {                                                                                                                                  \
         auto k = gemm_astat_kernel<OutT, FLv>;                                                                                            \
         static bool attr = false;                                                                                                         \
         if (!attr) { (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }      \
-        hipLaunchKernelGGL(k, grid, dim3(256), lds, st, A, lda, B, ldb, (OutT*)C, M, N, ep, tiles_per_block);                             \
+        hipLaunchKernelGGL(k, grid, dim3(256), lds, st, A, lda, B, ldb, (OutT*)C, M, N, ep, p.tiles_per_block);                           \
     } while (0)
-    // feature flags of this launch; the sets the Performer layer uses have their own straight-line instantiation, the rest runs the generic one
-    const bool gelu_aux = ep.act == EMO_ACT_GELU_NEW && ep.aux_out;
-    int fl = (ep.act == EMO_ACT_RELU ? AF_RELU : 0) | (ep.drop.thr16 ? AF_DROP : 0) | (ep.residual ? AF_RES : 0) | (ep.mul_mode == EMO_MUL_BITMASK ? AF_BITS : 0) |
-             (ep.mask_out ? AF_MASKOUT : 0) | (ep.mul_mode == EMO_MUL_DGELU_NEW ? AF_DGELU : 0) | (gelu_aux ? AF_GELUAUX : 0);
-    const bool other = (!gelu_aux && (ep.aux_out || ep.act == EMO_ACT_GELU_NEW)) || ep.mul_mode == EMO_MUL_NONZERO ||
-                       (ep.drop.thr16 && (uint64_t)M * (uint64_t)N >= (1ull << 32));
-    if (ep.hdiv) AS_LAUNCH(bf16_t, AF_HDIV);                       // (emo_gemm admits hdiv only with a plain epilogue)
-    else if (dtype_out == EMO_F32) AS_LAUNCH(float, AF_GENERIC);
-    else if (other) AS_LAUNCH(bf16_t, AF_GENERIC);
-    else if (fl == 0) AS_LAUNCH(bf16_t, 0);
-    else if (fl == AF_RELU) AS_LAUNCH(bf16_t, AF_RELU);
-    // (relu + dropout WITHOUT the mask output — no caller in the training or decoding paths — runs the generic instance: its straight-line
-    // instantiation no longer fits 256 VGPRs without an in-loop reload, which drains the ring)
-    else if (fl == (AF_RELU | AF_DROP | AF_MASKOUT)) AS_LAUNCH(bf16_t, AF_RELU | AF_DROP | AF_MASKOUT);
-    else if (fl == AF_RES) AS_LAUNCH(bf16_t, AF_RES);
-    else if (fl == (AF_DROP | AF_RES)) AS_LAUNCH(bf16_t, AF_DROP | AF_RES);
-    else if (fl == AF_BITS) AS_LAUNCH(bf16_t, AF_BITS);
-    else if (fl == AF_DGELU) AS_LAUNCH(bf16_t, AF_DGELU);
-    else if (fl == AF_GELUAUX) AS_LAUNCH(bf16_t, AF_GELUAUX);
-    else AS_LAUNCH(bf16_t, AF_GENERIC);
+    if (dtype_out == EMO_F32) { AS_LAUNCH(float, AF_GENERIC); return; }
+    switch (p.astat_instance) {
+        case AF_HDIV: AS_LAUNCH(bf16_t, AF_HDIV); break;
+        case 0: AS_LAUNCH(bf16_t, 0); break;
+        case AF_RELU: AS_LAUNCH(bf16_t, AF_RELU); break;
+        case AF_RELU | AF_DROP | AF_MASKOUT: AS_LAUNCH(bf16_t, AF_RELU | AF_DROP | AF_MASKOUT); break;
+        case AF_RES: AS_LAUNCH(bf16_t, AF_RES); break;
+        case AF_DROP | AF_RES: AS_LAUNCH(bf16_t, AF_DROP | AF_RES); break;
+        case AF_BITS: AS_LAUNCH(bf16_t, AF_BITS); break;
+        case AF_DGELU: AS_LAUNCH(bf16_t, AF_DGELU); break;
+        case AF_GELUAUX: AS_LAUNCH(bf16_t, AF_GELUAUX); break;
+        default: AS_LAUNCH(bf16_t, AF_GENERIC);
+    }
 #undef AS_LAUNCH
-    emo_gemm_note_plan(AS_KS, 4, 0, split);
-    return true;
 }

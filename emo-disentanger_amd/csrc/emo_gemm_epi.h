@@ -2,6 +2,7 @@
 // (+bias -> aux_out -> act -> *mul(aux) -> dropout -> +residual -> store), see include/emo_hip.h (emo_epilogue_t).
 #pragma once
 #include "emo_common.h"
+#include "emo_gemm_plan.h"
 
 struct EpiParams {
     const float* bias;
@@ -217,19 +218,12 @@ __device__ __forceinline__ void epi_row8(const EpiParams& ep, OutT* __restrict__
 }
 
 
-// plan of the launch being queued, for emo_gemm_last_plan() (emo_hip.h; defined in emo_gemm.hip): zero = the family has no such field
-void emo_gemm_note_plan(int bk, int stages, int splits, int col_split);
-// A-stationary K = 512 kernel (emo_gemm_astat.hip): true when the shape / epilogue is eligible and the launch was queued.
-bool emo_gemm_astat_try(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, int dtype_out, int64_t M, int64_t N, int64_t K,
-                        const EpiParams& ep, hipStream_t st);
-// 256 x 256 tile, one wave per SIMD (emo_gemm_w128.hip): long-K NT products; true when eligible and queued.
-bool emo_gemm_w128_try(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, int dtype_out, int64_t M, int64_t N, int64_t K,
-                       const EpiParams& ep, hipStream_t st);
-// persistent 256 x 256 tile walk, 32 x 32 x 16 MFMA (emo_gemm_p256.hip, r05): true when eligible and queued.
-int emo_gemm_p256_try(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, int dtype_out, int64_t M, int64_t N, int64_t K,
-                       const EpiParams& ep, hipStream_t st);
+// One launch function per kernel file: it takes the plan emo_gemm made (emo_gemm_plan.h) and the operands; no gate, no switch.
+void emo_gemm_astat_launch(const GemmPlan& p, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, int dtype_out, int64_t M, int64_t N, EpiParams ep,
+                           hipStream_t st);
+void emo_gemm_w128_launch(const GemmPlan& p, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, int64_t M, int64_t N, int64_t K, EpiParams ep, hipStream_t st);
 // the same tile for the wgrad layout (A stored [K, M], B stored [K, N], fp32 out, split-K through the caller's workspace)
-int64_t emo_gemm_w128_tn_splits(int64_t M, int64_t N, int64_t K);
-int64_t emo_gemm_w128_tn_rs_floats(int64_t M, int64_t N, int64_t splits);
-bool emo_gemm_w128_tn_try(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int accumulate,
-                          float* a_rowsum, float* b_rowsum, void* ws, int64_t ws_bytes, hipStream_t st);
+void emo_gemm_w128_tn_launch(const GemmPlan& p, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, float* C, int64_t M, int64_t N, int64_t K, int accumulate,
+                             float* a_rowsum, float* b_rowsum, float* ws, hipStream_t st);
+// persistent 256 x 256 / 128 x 512 tile walks (emo_gemm_p256.hip, -DEMO_EXPERIMENTAL)
+void emo_gemm_p256_launch(const GemmPlan& p, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, int64_t M, int64_t N, int64_t K, EpiParams ep, hipStream_t st);

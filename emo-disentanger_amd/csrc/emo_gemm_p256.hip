@@ -625,65 +625,25 @@ __global__ __launch_bounds__(256, 1) void gemm_q512_kernel(const bf16_t* __restr
 }
 }  // namespace
 
-// NT bf16 product on the persistent 256 x 256 kernel; true when the shape is eligible and the launch was queued.
-// EMO_GEMM_P256: 1 = every eligible shape (tests, tools/bench_p256.py), 2 = long reductions with at least one tile per CU; unset / 0 = off
-// (r05: behind the tile-per-block kernel inside the training step, see the header and profiles/r05_gemm_isa_diff.txt).
-// 128 x 512 tile (gemm_q512_kernel): EMO_GEMM_Q512 = 1 every eligible shape, 2 long reductions only; EMO_Q512_PERSIST=1: one workgroup per CU
-// walking its tiles instead of one tile per workgroup.
-static bool emo_gemm_q512_try(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, int dtype_out, int64_t M, int64_t N, int64_t K,
-                              const EpiParams& ep, hipStream_t st) {
-    const char* e = getenv("EMO_GEMM_Q512");
-    const int mode = e ? atoi(e) : 0;
-    if (mode <= 0) return false;
-    if ((M % Q_BM) || (N % Q_BN) || (K % P_BK) || K < 2 * P_BK || dtype_out != EMO_BF16) return false;
-    if (mode == 2 && (K < 1024 || (M / Q_BM) * (N / Q_BN) < 256)) return false;
-    if (ep.atomic || ep.accumulate || ep.ws_stride || ep.a_rowsum || ep.b_rowsum || ep.ln_c1 || ep.rln_x || ep.mask_out) return false;
-    if (ep.aux_out || ep.mul_mode != EMO_MUL_NONE || ep.act != EMO_ACT_NONE) return false;
-    if ((lda & 7) || (ldb & 7) || (ep.ldc & 7) || (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15)) return false;
-    if (ep.residual && ((uintptr_t)ep.residual & 15)) return false;
-    if (ep.bias && ((uintptr_t)ep.bias & 15)) return false;
-    if ((uint64_t)(512 * (lda > ldb ? lda : ldb) + 64) * 2 >= 0x7FFF0000ull) return false;
-    const int64_t tiles = (M / Q_BM) * (N / Q_BN);
-    int64_t nslot = (tiles + 7) / 8;
-    { const char* e2 = getenv("EMO_Q512_PERSIST"); if (e2 && atoi(e2) && nslot > 32) nslot = 32; }
-    auto k = gemm_q512_kernel<bf16_t>;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, Q_LDS); attr = true; }
-    hipLaunchKernelGGL(k, dim3((unsigned)(8 * nslot)), dim3(256), Q_LDS, st, A, lda, B, ldb, (bf16_t*)C, M, N, K, ep);
-    return true;
-}
-
-int emo_gemm_p256_try(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, int dtype_out, int64_t M, int64_t N, int64_t K,
-                      const EpiParams& ep, hipStream_t st) {
-    if (emo_gemm_q512_try(A, lda, B, ldb, C, dtype_out, M, N, K, ep, st)) return 9;
-    const char* e = getenv("EMO_GEMM_P256");                   // (read per call: tests toggle it in-process)
-    const int mode = e ? atoi(e) : 0;
-    if (mode <= 0) return 0;
-    if ((M % P_BM) || (N % P_BN) || (K % P_BK) || K < 2 * P_BK || dtype_out != EMO_BF16) return 0;
-    if (mode == 2 && (K < 1024 || (M / P_BM) * (N / P_BN) < 256)) return 0;
-    if (ep.atomic || ep.accumulate || ep.ws_stride || ep.a_rowsum || ep.b_rowsum || ep.ln_c1 || ep.rln_x || ep.mask_out) return 0;
-    if (ep.aux_out || ep.mul_mode != EMO_MUL_NONE || ep.act != EMO_ACT_NONE) return 0;       // register epilogue: bias, dropout, residual
-    if ((lda & 7) || (ldb & 7) || (ep.ldc & 7) || (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15)) return 0;
-    if (ep.residual && ((uintptr_t)ep.residual & 15)) return 0;
-    if (ep.bias && ((uintptr_t)ep.bias & 15)) return 0;
-    if ((uint64_t)(256 * (lda > ldb ? lda : ldb) + 64) * 2 >= 0x7FFF0000ull) return 0;
-    const int64_t tiles = (M / P_BM) * (N / P_BN);
-    int64_t nslot = (tiles + 7) / 8;
-    if (nslot > 32) nslot = 32;                                // one workgroup per CU
-    EpiParams ep2 = ep;
-    { const char* e3 = getenv("EMO_P256_SKEW"); ep2.nt_store = e3 ? atoi(e3) : 0; }
-    int sched = 0;
-    { const char* e4 = getenv("EMO_P256_SCHED"); if (e4) sched = atoi(e4); }
+// family 9: the 128 x 512 tile, family 8: the persistent 256 x 256 tile walk (gates and switches: emo_gemm_plan.h, gp_persistent)
+void emo_gemm_p256_launch(const GemmPlan& p, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, int64_t M, int64_t N, int64_t K, EpiParams ep, hipStream_t st) {
+    if (p.family == 9) {
+        auto k = gemm_q512_kernel<bf16_t>;
+        static bool attr = false;
+        if (!attr) { (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, Q_LDS); attr = true; }
+        hipLaunchKernelGGL(k, dim3(p.grid_x), dim3(256), Q_LDS, st, A, lda, B, ldb, (bf16_t*)C, M, N, K, ep);
+        return;
+    }
+    ep.nt_store = p.nt_store;
 #define P_LAUNCH(Sv)                                                                                                                   \
     do {                                                                                                                               \
         auto k = gemm_p256_kernel<bf16_t, Sv>;                                                                                         \
         static bool attr = false;                                                                                                      \
         if (!attr) { (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS); attr = true; }     \
-        hipLaunchKernelGGL(k, dim3((unsigned)(8 * nslot)), dim3(256), P_LDS, st, A, lda, B, ldb, (bf16_t*)C, M, N, K, ep2);           \
+        hipLaunchKernelGGL(k, dim3(p.grid_x), dim3(256), P_LDS, st, A, lda, B, ldb, (bf16_t*)C, M, N, K, ep);                         \
     } while (0)
-    switch (sched) { case 1: P_LAUNCH(1); break; case 2: P_LAUNCH(2); break; case 3: P_LAUNCH(3); break; case 4: P_LAUNCH(4); break; case 5: P_LAUNCH(5); break; case 6: P_LAUNCH(6); break; case 7: P_LAUNCH(7); break; case 8: P_LAUNCH(8); break; default: P_LAUNCH(0); }
+    switch (p.sched) { case 1: P_LAUNCH(1); break; case 2: P_LAUNCH(2); break; case 3: P_LAUNCH(3); break; case 4: P_LAUNCH(4); break; case 5: P_LAUNCH(5); break; case 6: P_LAUNCH(6); break; case 7: P_LAUNCH(7); break; case 8: P_LAUNCH(8); break; default: P_LAUNCH(0); }
 #undef P_LAUNCH
-    return 8;
 }
 
 #endif  // EMO_EXPERIMENTAL

@@ -29,6 +29,7 @@ namespace {
 constexpr int W_BM = 256, W_BN = 256, W_BK = 64;
 constexpr int W_TILE = 256 * W_BK * 2;                        // one operand tile: 32 KB
 constexpr int W_NA = 3, W_NB = 2;
+static_assert(W_BM == GP_W_BM && W_BN == GP_W_BN && W_BK == GP_W_BK && W_NA == GP_W_STAGES, "emo_gemm_plan.h plans for this geometry");
 constexpr int W_LDS = (W_NA + W_NB) * W_TILE;                 // 160 KB
 
 __device__ __forceinline__ uint32_t w_lds_addr(const void* p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)p; }
@@ -445,106 +446,31 @@ __global__ __launch_bounds__(256, 1) void gemm_w128_tn_kernel(const bf16_t* __re
 }
 }  // namespace
 
-// NT bf16 product on 256 x 256 tiles; true when the shape is eligible and the launch was queued.  Default: long reductions (K >= 1024) with at
-// least one tile per CU; EMO_GEMM_W128=0 switches it off, =1 admits every eligible shape (tests).
-bool emo_gemm_w128_try(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, int dtype_out, int64_t M, int64_t N, int64_t K,
-                       const EpiParams& ep, hipStream_t st) {
-    const char* e = getenv("EMO_GEMM_W128");                   // (read per call: tests toggle it in-process)
-    const int mode = e ? atoi(e) : -1;
-    if (mode == 0) return false;
-    if ((M % W_BM) || (N % W_BN) || (K % W_BK) || K < 4 * W_BK || dtype_out != EMO_BF16) return false;
-    if (mode < 0 && (K < 1024 || (M / W_BM) * (N / W_BN) < 256)) return false;
-    if (ep.atomic || ep.accumulate || ep.ws_stride || ep.a_rowsum || ep.b_rowsum || ep.ln_c1 || ep.rln_x || ep.mask_out) return false;
-    if (ep.aux_out || ep.mul_mode != EMO_MUL_NONE || ep.act != EMO_ACT_NONE) return false;       // register epilogue: bias, dropout, residual
-    if ((lda & 7) || (ldb & 7) || (ep.ldc & 7) || (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15)) return false;
-    if ((uint64_t)(256 * (lda > ldb ? lda : ldb) + 64) * 2 >= 0xFFFF0000ull) return false;
-    const int64_t tiles_m = M / W_BM, tiles_n = N / W_BN;
-    dim3 grid((unsigned)(((tiles_m + 7) / 8) * 8 * tiles_n));
-    EpiParams ep2 = ep;
-    { const char* e4 = getenv("EMO_W128_NT_STORE"); ep2.nt_store = e4 ? atoi(e4) : 0; }
-    { const char* e3 = getenv("EMO_W128_A_NT"); ep2.a_nt = e3 ? atoi(e3) : 1; }     // default on (r03: -0.4 .. -0.55 ms/step; the wgrad kernel loses with it)
+void emo_gemm_w128_launch(const GemmPlan& p, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, int64_t M, int64_t N, int64_t K, EpiParams ep, hipStream_t st) {
+    ep.nt_store = p.nt_store; ep.a_nt = p.a_nt;
     auto k = gemm_w128_kernel<bf16_t>;
     static bool attr = false;
     if (!attr) { (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS); attr = true; }
-    hipLaunchKernelGGL(k, grid, dim3(256), W_LDS, st, A, lda, B, ldb, (bf16_t*)C, M, N, K, ep2);
-    emo_gemm_note_plan(W_BK, W_NA, 0, 0);
-    return true;
+    hipLaunchKernelGGL(k, dim3(p.grid_x), dim3(256), W_LDS, st, A, lda, B, ldb, (bf16_t*)C, M, N, K, ep);
 }
 
-// K-splits of the TN (wgrad) product on 256 x 256 tiles (at most one block per CU, see the kernel's block mapping); 0 = shape not taken.
-static int64_t w_tn_plan(int64_t M, int64_t N, int64_t K, int& full, int& extra) {
-    full = extra = 0;
-    const char* e = getenv("EMO_GEMM_W128");
-    if (e && atoi(e) == 0) return 0;
-    const char* e2 = getenv("EMO_GEMM_W128_TN");
-    if (e2 && atoi(e2) == 0) return 0;
-    if ((M % W_BM) || (N % W_BN) || (K % W_BK)) return 0;
-    const int64_t ntile = (M / W_BM) * (N / W_BN), nkt = K / W_BK;
-    if (ntile > 32) return 0;
-    int64_t f = 32 / ntile;
-    if (f > 8) f = 8;                                          // at most 64 splits
-    int64_t x = f < 8 ? (8 * (32 - f * ntile)) / ntile : 0;
-    if (e2 && atoi(e2) == 2) x = 0;                            // (diagnostics: whole splits per XCD only)
-    int64_t min_kt = 16;                                       // K-tiles per split (r04: 8 let batch-size-4 steps — 512 tokens per split — onto this tile, where
-    { const char* e3 = getenv("EMO_W128_TN_MINKT"); if (e3 && atoi(e3) > 0) min_kt = atoi(e3); }      // prologue + epilogue dominate: 8.89 vs 8.39 ms per step)
-    while (nkt / (8 * f + x) < min_kt) {
-        if (x) x = 0;
-        else if (f > 1) --f;
-        else return 0;
-    }
-    int64_t min_blk = 96;                                      // (r04: 160 -> 96 lets the batch-size-4 FFN / QKV weight gradients on: 8.30 -> 7.97 ms per step)
-    { const char* e4 = getenv("EMO_W128_TN_MINBLK"); if (e4 && atoi(e4) > 0) min_blk = atoi(e4); }
-    if (ntile * (8 * f + x) < min_blk) return 0;                   // (too few blocks for the chip: the 128 x 128 kernel's finer tiles win)
-    full = (int)f;
-    extra = (int)x;
-    return 8 * f + x;
-}
-int64_t emo_gemm_w128_tn_splits(int64_t M, int64_t N, int64_t K) {
-    int full, extra;
-    return w_tn_plan(M, N, K, full, extra);
-}
+void emo_splitk_reduce_launch(const float* ws, int64_t stride, int splits, float* out, int64_t n4, int accumulate, const float* rs_ws, int64_t rs_stride, int rs_parts,
+                              float* rs_out, hipStream_t st);
 
-void emo_splitk_reduce_launch(const float* ws, int64_t stride, int splits, float* out, int64_t n4, int accumulate, hipStream_t st);
-void emo_splitk_reduce_rs_launch(const float* ws, int64_t stride, int splits, float* out, int64_t n4, int accumulate, const float* rs_ws, int64_t rs_stride,
-                                 int rs_parts, float* rs_out, hipStream_t st);
-// floats of bias-gradient partials behind the weight partials (one vector per (split, tile of the other dimension))
-int64_t emo_gemm_w128_tn_rs_floats(int64_t M, int64_t N, int64_t splits) {
-    const int64_t a = (N / W_BN) * M, b = (M / W_BM) * N;
-    return splits * (a > b ? a : b);
-}
-
-// dW[M,N] (+)= A[K,M]^T B[K,N], fp32 out, contiguous C, workspace of >= splits * M * N floats; optional a_rowsum[M] += column sums of A or
-// b_rowsum[N] += column sums of B (one of them)
-bool emo_gemm_w128_tn_try(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int accumulate,
-                          float* a_rowsum, float* b_rowsum, void* ws, int64_t ws_bytes, hipStream_t st) {
-    int full, extra;
-    const int64_t splits0 = w_tn_plan(M, N, K, full, extra);
-    if (!splits0 || ldc != N || !ws || ((uintptr_t)ws & 15) || ws_bytes < splits0 * M * N * (int64_t)sizeof(float)) return false;
-    if ((lda & 7) || (ldb & 7) || (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15)) return false;
-    if ((uint64_t)(64 * (lda > ldb ? lda : ldb) + 256) * 2 >= 0xFFFF0000ull) return false;
-    const int64_t kps = ((K / W_BK + splits0 - 1) / splits0) * W_BK;
-    const int64_t ntile = (M / W_BM) * (N / W_BN);
-    dim3 grid(256);                                            // 32 block slots per XCD (w_tn_plan)
-    int nt_mask = 0;
-    { const char* e3 = getenv("EMO_W128_TN_NT"); if (e3) nt_mask = atoi(e3); }
-    float* rs_ws = nullptr;                                     // bias-gradient partials through the workspace when it has room for them
-    if ((a_rowsum || b_rowsum) && ws_bytes >= (splits0 * M * N + emo_gemm_w128_tn_rs_floats(M, N, splits0)) * (int64_t)sizeof(float) &&
-        !(((uintptr_t)a_rowsum | (uintptr_t)b_rowsum) & 15))
-        rs_ws = (float*)ws + splits0 * M * N;
+// dW[M,N] (+)= A[K,M]^T B[K,N] through the workspace (p.splits * M * N floats, then the bias-gradient partials when p.tn_rs_ws); optional a_rowsum[M] +=
+// column sums of A or b_rowsum[N] += column sums of B (one of them)
+void emo_gemm_w128_tn_launch(const GemmPlan& p, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, float* C, int64_t M, int64_t N, int64_t K, int accumulate,
+                             float* a_rowsum, float* b_rowsum, float* ws, hipStream_t st) {
+    float* rs_ws = p.tn_rs_ws ? ws + (int64_t)p.splits * M * N : nullptr;
 #define W_TN_LAUNCH(RSv)                                                                                                                     \
     do {                                                                                                                                     \
         auto k = gemm_w128_tn_kernel<RSv>;                                                                                                   \
         static bool attr = false;                                                                                                            \
         if (!attr) { (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS); attr = true; }            \
-        hipLaunchKernelGGL(k, grid, dim3(256), W_LDS, st, A, lda, B, ldb, (float*)ws, M, N, K, kps, a_rowsum, b_rowsum, full, extra, nt_mask, rs_ws); \
+        hipLaunchKernelGGL(k, dim3(p.grid_x), dim3(256), W_LDS, st, A, lda, B, ldb, ws, M, N, K, p.kps, a_rowsum, b_rowsum, p.tn_full, p.tn_extra, p.nt_mask, rs_ws); \
     } while (0)
     if (a_rowsum) W_TN_LAUNCH(1); else if (b_rowsum) W_TN_LAUNCH(2); else W_TN_LAUNCH(0);
 #undef W_TN_LAUNCH
-    if (rs_ws)
-        emo_splitk_reduce_rs_launch((const float*)ws, M * N, (int)splits0, C, (M * N) >> 2, accumulate, rs_ws, a_rowsum ? M : N,
-                                    (int)(splits0 * (a_rowsum ? N / W_BN : M / W_BM)), a_rowsum ? a_rowsum : b_rowsum, st);
-    else
-        emo_splitk_reduce_launch((const float*)ws, M * N, (int)splits0, C, (M * N) >> 2, accumulate, st);
-    emo_gemm_note_plan(W_BK, W_NA, (int)splits0, 0);
-    return true;
+    emo_splitk_reduce_launch(ws, M * N, p.splits, C, (M * N) >> 2, accumulate, rs_ws, a_rowsum ? M : N, (int)(p.splits * (a_rowsum ? N / W_BN : M / W_BM)),
+                             a_rowsum ? a_rowsum : b_rowsum, st);
 }

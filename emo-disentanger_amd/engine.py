@@ -378,7 +378,7 @@ def performer_layer_bwd(ps, pfx, dout, B, T, H, p, seed, off, save):
                                 want_drop=p > 0, p_drop=p, seed=seed, offset=off + 3, dcol=ps.g(pfx + 'linear2.bias'))
     if dyd is None:
         dyd = g2
-    bf = ps.flat16 is not None and D == 512 and dout.shape[0] % 128 == 0 and dout.shape[0] >= ops.ASTAT_MIN_ROWS
+    bf = ps.flat16 is not None and ops.gemm_astat_ok(dout.shape[0], D, D, torch.bfloat16, torch.bfloat16)     # the A-stationary K = 512 class
     chb = int(_os.environ.get('EMO_FFN_CHUNK_B', 0))
     chunked = bool(bf and chb and s['fmask'] is not None and s.get('z') is None and dout.shape[0] > chb and dout.shape[0] % chb == 0)
     if chunked:                                                     # PROBE: the FFN backward per row chunk (df stays in the Infinity Cache for its two readers)
@@ -391,7 +391,6 @@ def performer_layer_bwd(ps, pfx, dout, B, T, H, p, seed, off, save):
             ops.gemm(dfc, ps.wT(pfx + 'linear1.weight'), residual=g2[sl], out=dh1[sl])
     else:
         _wgrad(ps, pfx + 'linear2.weight', pfx + 'linear2.bias', dyd, s['f'], bias_done=True)
-    bf = ps.flat16 is not None and D == 512 and dout.shape[0] % 128 == 0 and dout.shape[0] >= ops.ASTAT_MIN_ROWS     # the A-stationary K = 512 class
     if chunked:
         pass
     elif s.get('z') is not None:                       # activation = 'gelu': df = (dyd W2) * gelu'(z), then the hidden dropout's multipliers again

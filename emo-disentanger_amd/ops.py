@@ -16,7 +16,7 @@ from ._lib import (ACT_GELU, ACT_GELU_NEW, ACT_NONE, ACT_RELU, ATTN_BWD, ATTN_BW
 __all__ = ['gemm', 'colsum', 'embed_fwd', 'embed_bwd', 'layernorm_fwd', 'layernorm_bwd', 'dropout_apply', 'favor_attn_fwd',
            'favor_attn_bwd', 'favor_decode_step', 'decode_step', 'decode_step_set', 'block_set', 'DecodeStep', 'GrammarStep', 'grammar_step', 'draw_score_tables', 'guide_pairs_error', 'favor_draw_omega', 'favor_state_reset', 'favor_state_at', 'acc_rebase', 'softmax_attn_fwd', 'softmax_attn_bwd', 'softmax_attn_decode', 'relpos_attn_fwd', 'relpos_attn_bwd', 'relpos_attn_decode', 'xent_fwd',
            'xent_bwd', 'token_scores', 'xent_bwd_rows', 'argmax', 'sample_nucleus', 'sample_nucleus_step', 'txl_grammar_step', 'txl_queue_step', 'acc_grammar_step', 'acc_queue_step', 'acc_window_step', 'accuracy_counts', 'sumsq', 'clip_coef', 'adam_step', 'cast', 'add_bias2',
-           'ACT_NONE', 'ACT_RELU', 'ACT_GELU_NEW', 'ACT_GELU', 'MUL_NONE', 'MUL_NONZERO', 'MUL_DGELU_NEW', 'MUL_DGELU', 'MUL_BITMASK', 'gemm_bitmask_ok', 'gemm_lna_ok', 'bitmask_rows', 'favor_bwd_dn_ok', 'ffn_fwd', 'ffn_fwd_ok']
+           'ACT_NONE', 'ACT_RELU', 'ACT_GELU_NEW', 'ACT_GELU', 'MUL_NONE', 'MUL_NONZERO', 'MUL_DGELU_NEW', 'MUL_DGELU', 'MUL_BITMASK', 'gemm_astat_ok', 'gemm_bitmask_ok', 'gemm_lna_ok', 'bitmask_rows', 'favor_bwd_dn_ok', 'ffn_fwd', 'ffn_fwd_ok']
 
 
 def _c(t):
@@ -160,21 +160,26 @@ def gemm(A, B, *, a_trans=False, b_trans=False, out=None, out_dtype=None, accumu
     return out
 
 
-ASTAT_MIN_ROWS = int(os.environ.get('EMO_ASTAT_MIN_ROWS', 0)) or 128 * 32       # emo_gemm_astat.hip (AS_MIN_BLOCKS): 128-row panels; below one panel per CU the kernel splits the columns over the grid
+def __getattr__(name):
+    if name == 'ASTAT_MIN_ROWS':       # fewest rows of the A-stationary class (128-row panels; below one panel per CU the kernel splits the columns over the grid)
+        return lib.emo_gemm_astat_min_rows()
+    raise AttributeError(name)
+
+
+def gemm_astat_ok(M, N, K, in_dtype, out_dtype):
+    """The A-stationary K = 512 class of emo_gemm as far as it does not depend on the tensors: the library's own predicate (emo_hip.h)."""
+    return in_dtype == torch.bfloat16 and bool(lib.emo_gemm_astat_supported(BF16, dtype_code(out_dtype), M, N, K))
 
 
 def gemm_bitmask_ok(M, N, K, in_dtype, out_dtype):
     """Shape class in which emo_gemm writes / reads the 1-bit epilogue mask (mask_out / MUL_BITMASK): the A-stationary K = 512 kernel."""
-    return in_dtype == torch.bfloat16 and out_dtype == torch.bfloat16 and K == 512 and M % 128 == 0 and M >= ASTAT_MIN_ROWS and N % 64 == 0 and 64 <= N <= 2048
+    return out_dtype == torch.bfloat16 and gemm_astat_ok(M, N, K, in_dtype, out_dtype)
 
 
 def gemm_lna_ok(M, N, K, in_dtype):
-    """Shape class in which emo_gemm can take the LayerNorm of its A operand (lna=): the A-stationary K = 512 kernel (emo_hip.h: lna_*)."""
-    # (mirrors every refusal of emo_gemm_astat_try that does not depend on the tensors: shape class, EMO_GEMM_NO_ASTAT, the safe-transpose
-    # diagnostics mode; strides / alignment are asserted by gemm() itself, which owns the tensors — lna_* has no other kernel to fall back to)
-    return (in_dtype == torch.bfloat16 and K == 512 and M % 128 == 0 and M >= ASTAT_MIN_ROWS and N % 64 == 0 and 64 <= N <= 2048
-            and os.environ.get('EMO_GEMM_NO_ASTAT') is None and os.environ.get('EMO_LN_IN_GEMM', '1') != '0'
-            and os.environ.get('EMO_GEMM_SAFE_TR', '0') in ('', '0'))
+    """Shape class in which emo_gemm can take the LayerNorm of its A operand (lna=): the A-stationary K = 512 kernel (emo_hip.h: lna_*).
+    Strides / alignment are asserted by gemm() itself, which owns the tensors — lna_* has no other kernel to fall back to."""
+    return os.environ.get('EMO_LN_IN_GEMM', '1') != '0' and gemm_astat_ok(M, N, K, in_dtype, in_dtype)
 
 
 def bitmask_rows(mask, M, N):

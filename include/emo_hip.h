@@ -129,6 +129,17 @@ int emo_gemm(const void* A, int a_trans, int64_t lda, const void* B, int b_trans
              void* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
              int dtype_in, int dtype_out, int accumulate /* C += result; fp32 out only */,
              const emo_epilogue_t* epi /* may be NULL */, emo_stream_t stream);
+/* The route emo_gemm would take for these arguments, without launching anything: EMO_OK and the two words emo_gemm_last_kernel() /
+ * emo_gemm_last_plan() would show after that call (either pointer may be NULL), or the error emo_gemm would return.  Operand pointers are used for
+ * their alignment only; the calling thread's last-kernel / last-plan words are left alone.  Needs no GPU. */
+int emo_gemm_route(const void* A, int a_trans, int64_t lda, const void* B, int b_trans, int64_t ldb,
+                   void* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
+                   int dtype_in, int dtype_out, int accumulate, const emo_epilogue_t* epi, int* kernel, int* plan);
+/* 1 when the problem is in the class of the A-stationary K = 512 kernel as far as that does not depend on the tensors (shape, dtypes, switches: the
+ * predicate the planner itself uses) — the class in which mask_out / EMO_MUL_BITMASK / lna_* / hdiv exist.  emo_gemm_astat_min_rows(): the fewest rows
+ * of that class (4096; EMO_ASTAT_MIN_ROWS). */
+int emo_gemm_astat_supported(int dtype_in, int dtype_out, int64_t M, int64_t N, int64_t K);
+int64_t emo_gemm_astat_min_rows(void);
 
 /* ------------------------------------------------------------------ K7f: the feed-forward block in one launch (r06)
  *   h1 = LayerNorm(x1) * gamma + beta;  f = dropout(relu(h1 W1^T + b1));  x2 = h1 + dropout(f W2^T + b2)

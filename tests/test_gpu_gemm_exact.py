@@ -32,6 +32,7 @@ Where the dispatcher admits something else than the issue behind this file assum
     extra branch runs at 5, 6 and 12 tiles (3 / 2 / 5 extra splits), so 5 tiles was added and 3 tiles asserts 64 splits;
   * an A operand one element off its 16-byte alignment is refused by EVERY bf16 kernel (emo_gemm raises); the A-stationary refusal that lands on
     the ring is an output row stride that is no multiple of 8 elements."""
+import ctypes
 import os
 import subprocess
 import sys
@@ -149,17 +150,25 @@ def _run(M, N, K, fam, *, layout='NT', in_dtype=BF16, out_dtype=BF16, flags=0, p
         held['size'] = size
         return held['buf'][GUARD:GUARD + size], size
 
-    real_workspace = ops._workspace
+    real_workspace, real_gemm, routed = ops._workspace, ops.lib.emo_gemm, []
+
+    def routed_gemm(*a):                   # the route query for the very arguments of the launch, asked first
+        words = ctypes.c_int(-1), ctypes.c_int(-1)
+        assert ops.lib.emo_gemm_route(*a[:-1], ctypes.byref(words[0]), ctypes.byref(words[1])) == 0, ops.lib.emo_last_error()
+        routed.append((words[0].value, words[1].value))
+        return real_gemm(*a)
+
     with _Env(env):
-        ops._workspace = guarded_workspace
+        ops._workspace, ops.lib.emo_gemm = guarded_workspace, routed_gemm
         try:
             out = ops.gemm(Ad, Bd, **kw)
             code, p = ops.lib.emo_gemm_last_kernel(), ops.lib.emo_gemm_last_plan()
         finally:
-            ops._workspace = real_workspace
+            ops._workspace, ops.lib.emo_gemm = real_workspace, real_gemm
     torch.cuda.synchronize()
     what = (M, N, K, layout, sorted(epi), env)
-    # 1. the route
+    # 1. the route, and the route query (which launches nothing) saying the same
+    assert routed == [(code, p)], (routed, code, p, what)
     assert (code & 15) in (fam if isinstance(fam, tuple) else (fam,)), ('family %d' % (code & 15), what)
     assert (code & 48) == flags, ('split flags %d' % (code & 48), what)
     # 2. the plan fields the case names
