@@ -13,6 +13,11 @@
 // The optional sampling controls (tok_mask / mask_of / temp_of / top_p_of, indexed by the stream r as params is: emo_grammar_controls) reach the
 // draw alone: a banned token's logit is read as -inf there, the scores above are still taken from the row as the model wrote it, and primer
 // tokens are fed whether banned or not.
+// Kind TXL, optional classifier-free guidance (guide_cond / guide_uncond / guide_scale: emo_hip.h): a guided piece is two rows of the batch, a
+// leader on the conditioned primer and a follower on the same primer with the unconditioned token in the emotion's place.  Both workgroups draw
+// (the key draw included) from the same combination of the same two logits rows with the leader's uniform and the leader's controls, then each
+// runs the grammar on its own row and state: the follower stays token for token with its leader, a rejection or a primer re-feed included, and
+// no workgroup reads what another writes in the launch; the scores stay those of each row's own logits.
 #include "emo_grammar.h"
 
 namespace {
@@ -83,7 +88,10 @@ __device__ __forceinline__ int32_t txl_grammar(const emo_grammar_step_t& a, int6
 // One token step of stream r (kind TXL: a stream of the batch; kind TXL_QUEUE: a job) in batch row b, whose logits row it draws from and whose
 // next input it writes, after emo_grammar_open has brought the stream's words to sst / spr and found it RUNNING.  All 512 threads call it; every
 // barrier inside lies on a path that sst, spr and the launch arguments alone decide.  CTL: the block has sampling controls (emo_grammar_controls).
-template <bool CTL>
+// GUIDE (kind TXL alone): the block has the three guidance tables; a stream whose pair (guide_cond[r], guide_uncond[r]) is two distinct rows of
+// the batch draws from their combination (emo_guided_logits) with the uniforms and the controls of row guide_cond[r], every other stream as
+// without them.  The pair is the same word in every thread, so the barriers stay uniform.  The scores are still taken from the stream's own row b.
+template <bool CTL, bool GUIDE>
 __device__ __forceinline__ void txl_stream_step(const emo_grammar_step_t& a, int64_t b, int64_t r, char* lds, const int32_t* sst, const int32_t* spr,
                                                 int32_t* sacc, float* sred, int tid) {
     int32_t* st = a.state + r * EMO_TXL_STATE_WORDS;
@@ -106,9 +114,24 @@ __device__ __forceinline__ void txl_stream_step(const emo_grammar_step_t& a, int
     }
     const int32_t len = sst[EMO_TXL_S_LEN];
     const bool key_step = spr[EMO_TXL_P_KEYED] != 0 && len == 1;          // the event after the emotion tag is the key (:81-89)
-    const emo_grammar_controls_t ctl = emo_grammar_controls<CTL>(a, r);  // (the key draw keeps key_temperature / key_top_p; the ban holds for it too)
-    const int64_t word = emo_nucleus_draw_from(emo_banned_logits{a.logits + b * a.n_token, ctl.ban}, a.n_token, key_step ? a.key_temperature : ctl.temp,
-                                               key_step ? a.key_top_p : ctl.top_p, a.u_steps[(int64_t)draws * a.ld_u + r], lds, tid, [] { __syncthreads(); });
+    int64_t word;
+    if constexpr (GUIDE) {
+        const int64_t gc = a.guide_cond[r], gu = a.guide_uncond[r];
+        if (gc != gu && gc >= 0 && gc < a.n_rows && gu >= 0 && gu < a.n_rows) {
+            const emo_grammar_controls_t ctl = emo_grammar_controls<CTL>(a, gc);
+            word = emo_nucleus_draw_from(emo_guided_logits{a.logits + gc * a.n_token, a.logits + gu * a.n_token, a.guide_scale[r], ctl.ban}, a.n_token,
+                                         key_step ? a.key_temperature : ctl.temp, key_step ? a.key_top_p : ctl.top_p,
+                                         a.u_steps[(int64_t)draws * a.ld_u + gc], lds, tid, [] { __syncthreads(); });
+        } else {
+            const emo_grammar_controls_t ctl = emo_grammar_controls<CTL>(a, r);
+            word = emo_nucleus_draw_from(emo_banned_logits{a.logits + b * a.n_token, ctl.ban}, a.n_token, key_step ? a.key_temperature : ctl.temp,
+                                         key_step ? a.key_top_p : ctl.top_p, a.u_steps[(int64_t)draws * a.ld_u + r], lds, tid, [] { __syncthreads(); });
+        }
+    } else {
+        const emo_grammar_controls_t ctl = emo_grammar_controls<CTL>(a, r);  // (the key draw keeps key_temperature / key_top_p; the ban holds for it too)
+        word = emo_nucleus_draw_from(emo_banned_logits{a.logits + b * a.n_token, ctl.ban}, a.n_token, key_step ? a.key_temperature : ctl.temp,
+                                     key_step ? a.key_top_p : ctl.top_p, a.u_steps[(int64_t)draws * a.ld_u + r], lds, tid, [] { __syncthreads(); });
+    }
     if (!emo_grammar_wants_scores(a)) {
         if (tid == 0) txl_grammar(a, b, row, st, sst, spr, word, draws, key_step, len);
         return;
@@ -121,7 +144,7 @@ __device__ __forceinline__ void txl_stream_step(const emo_grammar_step_t& a, int
     if (sacc[0] >= 0) emo_grammar_score(a, a.logits + b * a.n_token, r, sacc[0], sacc[1], sred, tid);
 }
 
-template <bool CTL>
+template <bool CTL, bool GUIDE>
 __global__ __launch_bounds__(512) void txl_grammar_kernel(const emo_grammar_step_t a) {
     __shared__ __attribute__((aligned(16))) char lds[EMO_NUCLEUS_LDS];
     __shared__ int32_t sst[EMO_TXL_STATE_WORDS], spr[EMO_TXL_PARAM_WORDS];
@@ -131,7 +154,7 @@ __global__ __launch_bounds__(512) void txl_grammar_kernel(const emo_grammar_step
     const int64_t r = blockIdx.x;
     emo_grammar_open(a.state + r * EMO_TXL_STATE_WORDS, EMO_TXL_STATE_WORDS, a.params + r * EMO_TXL_PARAM_WORDS, EMO_TXL_PARAM_WORDS, sst, spr, tid);
     if (sst[EMO_TXL_S_STATUS] != EMO_TXL_RUNNING) return;
-    txl_stream_step<CTL>(a, r, r, lds, sst, spr, sacc, sred, tid);
+    txl_stream_step<CTL, GUIDE>(a, r, r, lds, sst, spr, sacc, sred, tid);
 }
 
 // Thread 0 of slot b, whose job (if it had one) is over: the next queued job that is RUNNING, or none.  queue_head only grows, so a slot that
@@ -181,7 +204,7 @@ __global__ __launch_bounds__(512) void txl_queue_kernel(const emo_grammar_step_t
                 atomicSub(a.running, 1);
             }
         } else {
-            txl_stream_step<CTL>(a, b, j, lds, sst, spr, sacc, sred, tid);
+            txl_stream_step<CTL, false>(a, b, j, lds, sst, spr, sacc, sred, tid);      // (the queue kind ignores the guidance tables)
         }
     }
     if (tid == 0 && st[EMO_TXL_S_STATUS] != EMO_TXL_RUNNING) {      // (thread 0 reads what it wrote itself)
@@ -192,9 +215,13 @@ __global__ __launch_bounds__(512) void txl_queue_kernel(const emo_grammar_step_t
 
 }  // namespace
 
+// (a block without the guidance tables launches a <.., false> instance, the kernel as it was before they existed; emo_grammar_step has checked
+// that the three come together)
 int emo_txl_grammar_launch(const emo_grammar_step_t& a, emo_stream_t stream) {
-    if (emo_grammar_has_controls(a)) hipLaunchKernelGGL(txl_grammar_kernel<true>, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(txl_grammar_kernel<false>, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
+    const bool ctl = emo_grammar_has_controls(a), guide = a.guide_cond != nullptr;
+    const auto kernel = guide ? (ctl ? txl_grammar_kernel<true, true> : txl_grammar_kernel<false, true>)
+                              : (ctl ? txl_grammar_kernel<true, false> : txl_grammar_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)a.n_rows), dim3(512), 0, (hipStream_t)stream, a);
     EMO_LAUNCH_CHECK();
     return EMO_OK;
 }

@@ -394,12 +394,15 @@ extern "C" int emo_grammar_step(const emo_grammar_step_t* args, emo_stream_t str
     EMO_CHECK(a.n_token > 0 && a.n_token <= 1024, "emo_grammar_step[%s]: V must be <= 1024 (got %lld)", name, (long long)a.n_token);
     if (txl) {
         EMO_CHECK(a.temperature > 0.f && a.key_temperature > 0.f, "emo_grammar_step[%s]: temperatures must be > 0", name);
+        // (kind TXL reads the guidance tables as kind ACC does, TXL_QUEUE ignores them: the check comes behind every other one of the kind)
+        const int txl_guide = tq ? 0 : (a.guide_cond != nullptr) + (a.guide_uncond != nullptr) + (a.guide_scale != nullptr);
+        EMO_CHECK(txl_guide == 0 || txl_guide == 3, "emo_grammar_step[%s]: guide_cond, guide_uncond and guide_scale come together or not at all", name);
         return tq ? emo_txl_queue_launch(a, stream) : emo_txl_grammar_launch(a, stream);
     }
     EMO_CHECK(a.temperature > 0.f, "emo_grammar_step[%s]: temperature must be > 0", name);
     // (the <false> instances are the kernels as they were before the sampling controls: a block without any launches those)
     const bool ctl = emo_grammar_has_controls(a);
-    // (kind ACC alone reads the guidance tables; a block without them launches the <.., false> instance, the kernel as it was before they existed)
+    // (of the kinds below ACC alone reads the guidance tables; a block without them launches the <.., false> instance, the kernel as it was before they existed)
     const int guide = a.kind == EMO_GRAMMAR_ACC ? (a.guide_cond != nullptr) + (a.guide_uncond != nullptr) + (a.guide_scale != nullptr) : 0;
     EMO_CHECK(guide == 0 || guide == 3, "emo_grammar_step[%s]: guide_cond, guide_uncond and guide_scale come together or not at all", name);
     // (kinds ACC and ACC_QUEUE read the kept-bar tables; a block without them launches a <.., false> instance, the kernel as it was before they

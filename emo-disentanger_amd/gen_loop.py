@@ -220,6 +220,8 @@ class GrammarLoop:
     score_tables = None
     controls = None                      # DrawControls of the loop's streams (None: a loop built without any)
     control_tables = None                # the device tensors behind the block's tok_mask / mask_of / temp_of / top_p_of ({}: all NULL)
+    guided_kinds = (ops.GRAMMAR_ACC,)    # the kinds whose block may hold guidance pairs: a lock-step kind that reads them, in a loop that feeds the
+                                         # two rows of a pair alike (LeadSheetLoop: GRAMMAR_TXL)
     replayed = (0, 0.0)                  # (steps, seconds) of the last run's replays
 
     def _to_device(self, *arrays):
@@ -239,8 +241,10 @@ class GrammarLoop:
         ops.block_set(self._gargs, self._gheld, **fields)
         self.controls = controls
         tabs = controls.tables() if controls is not None else {}
-        if 'guide_cond' in tabs and kind != ops.GRAMMAR_ACC:      # (the other kinds ignore the tables: the streams would run unguided, silently)
-            raise EmoError('%s: guidance pairs run in the lock-step ACC launch alone (kind %d ignores them)' % (type(self).__name__, kind))
+        # (any other kind ignores the tables, or its loop does not keep a pair together: the streams would run unguided, silently)
+        if 'guide_cond' in tabs and kind not in self.guided_kinds:
+            raise EmoError('%s: guidance pairs run in the lock-step launch of a loop that pairs its rows (kind %d is not one of %s)'
+                           % (type(self).__name__, kind, list(self.guided_kinds)))
         if 'tok_mask' in tabs:                                   # (torch has no arithmetic on uint32: the words travel as int32, bit for bit)
             tabs['tok_mask'] = tabs['tok_mask'].view(np.int32)
         self.control_tables = dict(zip(tabs, self._to_device(*tabs.values())))

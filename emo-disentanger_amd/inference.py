@@ -1093,9 +1093,10 @@ def guidance_plan(who, guidance, uncond, event2idx, idx2event, primers):
     return GuidancePlan(scales, guided, emo_pos, followers)
 
 
-def check_pairs(results, statuses, scores, controls, emo_pos):
+def check_pairs(results, statuses, scores, controls, emo_pos, who='generate_accompaniments'):
     """The pair invariant of a guided run, per follower g of `controls` (DrawControls over the rows of `results`) and its leader c: the same
-    status word, both results or both errors, the same length and the same ids except at emo_pos[c].  A pair that broke it leaves an EmoError
+    status word, both results or both errors, the same length and the same ids except at emo_pos[c] (a result that is no id list, stage 1's
+    None of a stuck stream, is told by its status word alone).  A pair that broke it leaves an EmoError
     in the LEADER's slot (its scores: None).  Where `scores` is given, a sound pair's leader gets 'logp_uncond': the follower's recorded logp,
     the unconditioned model's figure for the leader's tokens.  -> (results, scores) without the followers' rows."""
     out, sc = list(results), None if scores is None else list(scores)
@@ -1108,7 +1109,9 @@ def check_pairs(results, statuses, scores, controls, emo_pos):
             bad = 'status %d against %d' % (statuses[c], statuses[g])
         elif isinstance(a, Exception) != isinstance(b, Exception):
             bad = 'one row failed alone'
-        elif not isinstance(a, Exception):
+        elif (a is None) != (b is None):
+            bad = 'one row got stuck alone'
+        elif a is not None and not isinstance(a, Exception):
             if len(a) != len(b):
                 bad = '%d against %d tokens' % (len(a), len(b))
             else:
@@ -1116,7 +1119,7 @@ def check_pairs(results, statuses, scores, controls, emo_pos):
                 if diff:
                     bad = 'the ids part at token %d' % diff[0]
         if bad:
-            out[c] = EmoError('generate_accompaniments: stream %d and its unconditioned follower %d left lock-step: %s' % (c, g, bad))
+            out[c] = EmoError('%s: stream %d and its unconditioned follower %d left lock-step: %s' % (who, c, g, bad))
             if sc is not None:
                 sc[c] = None
         elif sc is not None and sc[c] is not None and sc[g] is not None:

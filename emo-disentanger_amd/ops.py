@@ -410,7 +410,7 @@ _GRAMMAR_STEP_LAYOUT = {
     'mask_of': lambda a, t: _is(t, _I32) and t.numel() == a.ld_u and int(t.min()) >= -1 and int(t.max()) < a.n_masks,
     'temp_of': lambda a, t: _is(t, _F32) and t.numel() == a.ld_u,
     'top_p_of': lambda a, t: _is(t, _F32) and t.numel() == a.ld_u,
-    # kind ACC, classifier-free guidance: per row of the batch; what the three hold together is checked by _check_guidance once they are in
+    # kinds ACC and TXL, classifier-free guidance: per row of the batch; what the three hold together is checked by _check_guidance once they are in
     'guide_cond': lambda a, t: _is(t, _I32) and t.numel() == a.n_rows,
     'guide_uncond': lambda a, t: _is(t, _I32) and t.numel() == a.n_rows,
     'guide_scale': lambda a, t: _is(t, _F32) and t.numel() == a.n_rows,
@@ -800,15 +800,16 @@ def draw_score_tables(seq):
 
 
 def txl_grammar_step(logits, temperature, top_p, key_temperature, key_top_p, u_steps, ev_flags, ev_beat, params, state, seq, tok_out, running,
-                     tok_logp=None, tok_rank=None, tok_entropy=None):
+                     tok_logp=None, tok_rank=None, tok_entropy=None, guide_cond=None, guide_uncond=None, guide_scale=None):
     """One stage-1 sample-and-grammar step of n streams (include/emo_hip.h, EMO_GRAMMAR_TXL): logits fp32 [n, V], u_steps fp32 [n_u, n],
     ev_flags / ev_beat int32 [V], params / state int32 [n, 8], seq int64 [n, W], tok_out int64 [n], running int32 [1].  state, seq, tok_out
     and running are updated in place.  tok_logp / tok_entropy fp32, tok_rank int32 [n, W] (each optional): the figures of every accepted draw
-    at its token's cell (draw_score_tables makes and pre-fills them)."""
+    at its token's cell (draw_score_tables makes and pre-fills them).  guide_cond / guide_uncond / guide_scale: as in acc_grammar_step."""
     n, V = logits.shape
     _grammar_once(GRAMMAR_TXL, n_rows=n, n_token=V, ld_u=n, temperature=temperature, top_p=top_p, key_temperature=key_temperature,
                   key_top_p=key_top_p, logits=logits, u_steps=u_steps, ev_flags=ev_flags, ev_beat=ev_beat, params=params, state=state, seq=seq,
-                  tok_out=tok_out, running=running, tok_logp=tok_logp, tok_rank=tok_rank, tok_entropy=tok_entropy)
+                  tok_out=tok_out, running=running, tok_logp=tok_logp, tok_rank=tok_rank, tok_entropy=tok_entropy, guide_cond=guide_cond,
+                  guide_uncond=guide_uncond, guide_scale=guide_scale)
     return tok_out
 
 

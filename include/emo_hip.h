@@ -596,7 +596,7 @@ enum { EMO_ACC_EV_BEAT = 1, EMO_ACC_EV_TRACK_LS = 2, EMO_ACC_EV_PAD = 4, EMO_ACC
  * one-token step (state[j, CONSUMED] as the host leaves it is ignored).  *running starts at the number of RUNNING jobs and is decremented once per job. */
 /* The five grammar steps above are the kinds of ONE entry with ONE argument block, as emo_decode_step_t is for the model step beside them in
  * every generation loop.  `kind` selects the kernel; a field that a kind does not read is ignored by it, whatever it holds (the comment of each
- * field names its readers; none = all five, as are the optional sampling controls and score outputs at the end of the block; a field of TXL is a field of TXL_QUEUE too, a field of ACC a field of ACC_QUEUE).  The block is read AT CALL TIME: its values travel as the launch's arguments, so under hipGraph
+ * field names its readers; none = all five, as are the optional sampling controls and score outputs at the end of the block; a field of TXL is a field of TXL_QUEUE too, a field of ACC a field of ACC_QUEUE, where the field's comment does not say otherwise).  The block is read AT CALL TIME: its values travel as the launch's arguments, so under hipGraph
  * capture they are baked into the captured launch, exactly as positional arguments would be, and a later change of the block reaches only later
  * calls (and later captures).  The struct holds raw device addresses: its owner keeps the memory alive. */
 enum { EMO_GRAMMAR_TXL = 0, EMO_GRAMMAR_ACC = 1, EMO_GRAMMAR_ACC_WINDOW = 2, EMO_GRAMMAR_TXL_QUEUE = 3, EMO_GRAMMAR_ACC_QUEUE = 4 };   /* what each does: the five comments above (n = n_rows, V = n_token) */
@@ -622,8 +622,8 @@ typedef struct {
     int64_t* seg_out;          /* ACC: int64 [n_rows] */
     int64_t max_len;           /* ACC: > 0 */
     int64_t pad;               /* ACC */
-    /* (kind ACC alone - ACC_QUEUE and every other kind ignore the three, whatever they hold; all three or none; all NULL: the launch is exactly
-     * the one without them.)  Classifier-free guidance over a MIRRORED PAIR of streams of the batch.  Stream r is guided when guide_cond[r] = c
+    /* (kinds ACC and TXL, the two lock-step kinds - ACC_QUEUE, TXL_QUEUE and ACC_WINDOW ignore the three, whatever they hold; all three or none;
+     * all NULL: the launch is exactly the one without them.)  Classifier-free guidance over a MIRRORED PAIR of streams of the batch.  Stream r is guided when guide_cond[r] = c
      * and guide_uncond[r] = g are two distinct values in [0, n_rows); any other pair of values is "unguided" to the kernel, which never reads
      * outside the tables.  A guided stream draws from l[v] = lc + s * (lc - lu), lc = logits[c, v], lu = logits[g, v], s = guide_scale[r]: three
      * separately rounded fp32 operations, never contracted, so NumPy's float32 `lc + s * (lc - lu)` is the same row bit for bit; the stream's ban
@@ -633,10 +633,14 @@ typedef struct {
      * grammar on the same draw in their own workgroups: the follower stays token for token with its leader without any traffic between the two,
      * and every row writes only its own tok_out / seg_out / state / seq / segs.  tok_logp / tok_rank / tok_entropy stay the model's figures from
      * the row's OWN logits at temperature 1: the leader's are the conditioned model's, the follower's the unconditioned model's for the same
-     * tokens.  The host owns the checks that need the values (ops.block_set: indices in range, pairs consistent, 0 <= s < inf). */
-    const int32_t* guide_cond;    /* ACC: int32 [n_rows] or NULL: the row whose logits are the conditioned ones for stream r, or -1 */
-    const int32_t* guide_uncond;  /* ACC: int32 [n_rows] or NULL: the row whose logits are the unconditioned ones, or -1 */
-    const float* guide_scale;     /* ACC: f32 [n_rows] or NULL: s >= 0 */
+     * tokens.  The host owns the checks that need the values (ops.block_set: indices in range, pairs consistent, 0 <= s < inf).
+     * Kind TXL (stage 1: the condition is the valence tag, the follower's primer holds Emotion_None in its place): the same, the key draw
+     * included (the combination at key_temperature / key_top_p).  A TXL stream has one draw per launch and a rejection re-feeds an input, so the
+     * pair also shares every rejection: the follower's params[EMO_MODE] is its LEADER's (the key rule then rejects for both or for neither), and
+     * the draw runs under the controls of row c.  There is no seg_out / segs to speak of. */
+    const int32_t* guide_cond;    /* ACC, TXL (not TXL_QUEUE): int32 [n_rows] or NULL: the row whose logits are the conditioned ones for stream r, or -1 */
+    const int32_t* guide_uncond;  /* ACC, TXL (not TXL_QUEUE): int32 [n_rows] or NULL: the row whose logits are the unconditioned ones, or -1 */
+    const float* guide_scale;     /* ACC, TXL (not TXL_QUEUE): f32 [n_rows] or NULL: s >= 0 */
     int64_t* segs;             /* ACC, ACC_WINDOW: int64 [streams, ld_seq] */
     const int64_t* lead_tok;   /* ACC, ACC_WINDOW */
     const int32_t* lead_off;   /* ACC, ACC_WINDOW */
