@@ -397,6 +397,12 @@ extern "C" int emo_grammar_step(const emo_grammar_step_t* args, emo_stream_t str
         // (kind TXL reads the guidance tables as kind ACC does, TXL_QUEUE ignores them: the check comes behind every other one of the kind)
         const int txl_guide = tq ? 0 : (a.guide_cond != nullptr) + (a.guide_uncond != nullptr) + (a.guide_scale != nullptr);
         EMO_CHECK(txl_guide == 0 || txl_guide == 3, "emo_grammar_step[%s]: guide_cond, guide_uncond and guide_scale come together or not at all", name);
+        // (both kinds read the kept-bar tables and keep_left; a block without them launches a <.., false> instance, the kernel as it was before they existed)
+        const int txl_keep = (a.keep_tok != nullptr) + (a.keep_beg != nullptr) + (a.keep_end != nullptr) + (a.keep_left != nullptr);
+        EMO_CHECK(txl_keep == 0 || (txl_keep == 4 && a.n_keep >= 0 && a.n_keep <= INT32_MAX),
+                  "emo_grammar_step[%s]: keep_tok, keep_beg, keep_end and keep_left come together or not at all, with 0 <= n_keep < 2^31", name);
+        EMO_CHECK(txl_keep == 0 || (a.keep_bar >= 0 && a.keep_bar < a.n_token), "emo_grammar_step[%s]: keep_bar %lld lies outside [0, V)", name,
+                  (long long)a.keep_bar);
         return tq ? emo_txl_queue_launch(a, stream) : emo_txl_grammar_launch(a, stream);
     }
     EMO_CHECK(a.temperature > 0.f, "emo_grammar_step[%s]: temperature must be > 0", name);

@@ -419,9 +419,14 @@ _GRAMMAR_STEP_LAYOUT = {
     'keep_tok': lambda a, t: _is(t, _I64) and t.numel() >= max(a.n_keep, 1),
     'keep_beg': lambda a, t: _is(t, _I32),
     'keep_end': lambda a, t: _is(t, _I32),
+    # kinds TXL / TXL_QUEUE, kept bars: the three tables above, indexed by params[KEEP0] + bar (hand them over with or after params), and the
+    # per-stream count of kept tokens not yet fed
+    'keep_left': lambda a, t: _is(t, _I32) and t.numel() == a.ld_u,
 }
 _GUIDE = ('guide_cond', 'guide_uncond', 'guide_scale')
 _KEEP = ('keep_tok', 'keep_beg', 'keep_end')
+_KEEP_TXL = _KEEP + ('keep_left',)
+TXL_P_KEEP0, TXL_P_KEEP_BARS = 6, 7                            # emo_hip.h: EMO_TXL_P_KEEP0 / EMO_TXL_P_KEEP_BARS
 
 
 def guide_pairs_error(c, g, s):
@@ -464,6 +469,8 @@ def _check_keep(args, held):
     """The three kept-bar tables of a GrammarStep as they stand in `held` (read back once, when one of them enters the block): all three or
     none, keep_beg / keep_end as long as lead_off, and every kept range inside keep_tok's n_keep entries.  The kernel reads nothing out of
     bounds whatever they hold (such a range ends its stream OVERFLOW)."""
+    if args.kind in (GRAMMAR_TXL, GRAMMAR_TXL_QUEUE):
+        return _check_keep_txl(args, held)
     tok, beg, end = (held.get(k) for k in _KEEP)
     if tok is None and beg is None and end is None:
         return
@@ -475,6 +482,32 @@ def _check_keep(args, held):
     kept = b >= 0
     assert 0 <= args.n_keep <= tok.numel() and bool((e[kept] >= b[kept]).all()) and bool((e[kept] <= args.n_keep).all()), \
         'grammar step: a kept bar lies outside keep_tok[0 .. n_keep)'
+
+
+def _check_keep_txl(args, held):
+    """The same for kinds TXL / TXL_QUEUE (messages name the kind): keep_tok, keep_beg, keep_end and keep_left all four or none; keep_beg and
+    keep_end of one length that holds every stream's params[KEEP0] .. KEEP0 + params[KEEP_BARS]; every kept range inside keep_tok's n_keep
+    entries; keep_left within [0, ld_seq]."""
+    who = 'grammar step[%s]' % ('txl' if args.kind == GRAMMAR_TXL else 'txl_queue')
+    tok, beg, end, left = (held.get(k) for k in _KEEP_TXL)
+    if tok is None and beg is None and end is None and left is None:
+        return
+    assert tok is not None and beg is not None and end is not None and left is not None, \
+        who + ': keep_tok, keep_beg, keep_end and keep_left come together or not at all'
+    assert beg.numel() == end.numel(), who + ': keep_beg and keep_end have one length'
+    assert 0 <= args.keep_bar < args.n_token, who + ': keep_bar = %d lies outside [0, %d)' % (args.keep_bar, args.n_token)
+    params = held.get('params')
+    assert params is not None, who + ': the kept-bar tables are indexed by params: hand them over with it or after it'
+    p = params.cpu().numpy()
+    k0, kn = p[:, TXL_P_KEEP0].astype('int64'), p[:, TXL_P_KEEP_BARS].astype('int64')
+    assert bool((k0 >= 0).all()) and bool((kn >= 0).all()) and bool((k0 + kn <= beg.numel()).all()), \
+        who + ': params[KEEP0] .. KEEP0 + params[KEEP_BARS] lies outside keep_beg / keep_end'
+    b, e = beg.cpu().numpy(), end.cpu().numpy()
+    kept = b >= 0
+    assert 0 <= args.n_keep <= tok.numel() and bool((e[kept] >= b[kept]).all()) and bool((e[kept] <= args.n_keep).all()), \
+        who + ': a kept bar lies outside keep_tok[0 .. n_keep)'
+    lf = left.cpu().numpy()
+    assert bool((lf >= 0).all()) and bool((lf <= args.ld_seq).all()), who + ': keep_left lies outside [0, ld_seq]'
 
 
 # per struct: its name in messages, the layout table, the int64 vectors, and the numbers a tensor brings with it (field -> (number, of tensor))
@@ -523,11 +556,12 @@ def block_set(args, held, **fields):
                 held.pop(k, None)
                 setattr(args, k, None)
             raise
-    if tensors and type(args) is GrammarStep and any(k in _KEEP for k, _ in tensors):
+    # (kinds TXL / TXL_QUEUE index keep_beg / keep_end by words of params: a new params is checked against the tables the block holds)
+    if tensors and type(args) is GrammarStep and any(k in _KEEP_TXL or k == 'params' for k, _ in tensors):
         try:
             _check_keep(args, held)
         except AssertionError:
-            for k in _KEEP:
+            for k in _KEEP_TXL:
                 held.pop(k, None)
                 setattr(args, k, None)
             raise

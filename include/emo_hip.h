@@ -504,9 +504,13 @@ int emo_sample_nucleus_step(const float* logits, int64_t rows, int64_t V, float 
  * idles).  *running is decremented once per stream that leaves RUNNING.
  * ev_flags [V] (EMO_TXL_EV_* bits: 'Beat' in e, 'Bar' in e, e == 'PAD_None', e == 'EOS_None', e.split('_')[0] == 'Key', the key's tonic in
  * MAJOR_KEY / MINOR_KEY) and ev_beat [V] (int(e.split('_')[-1]) of Beat events) are built on the host from idx2event.
+ * Optional kept bars (keep_tok / keep_beg / keep_end / keep_left, the comment of the fields below): a bar the caller already has is written out,
+ * not drawn, in the launch that accepts the Bar in front of it, and fed one token per launch; rows then need the longest kept run on top.
  * params int32 [n, EMO_TXL_PARAM_WORDS], state int32 [n, EMO_TXL_STATE_WORDS], laid out as the enums below. */
 enum { EMO_TXL_P_MAX_BARS = 0, EMO_TXL_P_MAX_EVENTS = 1, EMO_TXL_P_PRIMER_LEN = 2, EMO_TXL_P_KEYED = 3, EMO_TXL_P_KEY_RULE = 4,
-       EMO_TXL_P_EMO_MODE = 5 /* 0 none, 1 major (Q1 / Q4 / Positive), 2 minor (Q2 / Q3 / Negative) */, EMO_TXL_PARAM_WORDS = 8 };
+       EMO_TXL_P_EMO_MODE = 5 /* 0 none, 1 major (Q1 / Q4 / Positive), 2 minor (Q2 / Q3 / Negative) */,
+       EMO_TXL_P_KEEP0 = 6 /* kept bars: the stream's first entry of keep_beg / keep_end */, EMO_TXL_P_KEEP_BARS = 7 /* and how many it has (0: none) */,
+       EMO_TXL_PARAM_WORDS = 8 };
 enum { EMO_TXL_S_STATUS = 0, EMO_TXL_S_LEN = 1 /* tokens in seq[r] */, EMO_TXL_S_ACCEPTED = 2, EMO_TXL_S_BEAT = 3, EMO_TXL_S_BARS = 4,
        EMO_TXL_S_FAILED = 5 /* rejected Beats in a row */, EMO_TXL_S_FEED = 6 /* next primer token to feed */, EMO_TXL_S_DRAWS = 7, EMO_TXL_STATE_WORDS = 8 };
 enum { EMO_TXL_RUNNING = 0, EMO_TXL_DONE = 1, EMO_TXL_STUCK = 2, EMO_TXL_KEY_ERROR = 3, EMO_TXL_OVERFLOW = 4 /* seq or u_steps exhausted */,
@@ -644,7 +648,7 @@ typedef struct {
     int64_t* segs;             /* ACC, ACC_WINDOW: int64 [streams, ld_seq] */
     const int64_t* lead_tok;   /* ACC, ACC_WINDOW */
     const int32_t* lead_off;   /* ACC, ACC_WINDOW */
-    /* (kinds ACC and ACC_QUEUE - ACC_WINDOW and every other kind ignore the five, whatever they hold; the three tables come together or not at
+    /* (kinds ACC and ACC_QUEUE - ACC_WINDOW ignores the five, whatever they hold, and kinds TXL / TXL_QUEUE read the first four their own way: the comment behind keep_eos; the three tables come together or not at
      * all; all NULL: the launch is exactly the one without them.)  KEPT BARS: accompaniment bars the caller already has.  keep_beg / keep_end are
      * indexed like lead_off, by params[BAR0] + j, j < params[N_BARS] (one entry per lead-sheet bar: the host checks the lengths against
      * lead_off's); keep_beg < 0: bar j is drawn, as ever; otherwise its accompaniment is keep_tok[keep_beg .. keep_end), possibly empty (a kept
@@ -659,11 +663,33 @@ typedef struct {
      * cell; kept tokens lie in seq / segs beyond CONSUMED and are fed one per launch like an injected lead-sheet bar.  CUR_POS is 0 at the bar
      * that is next opened for drawing, and FAILED is 0 there when a kept bar lay in between (without one it is carried, as ever).  Kept bars at
      * the start of a piece are in the row when the host loads it (inference._Stream is the rule on the host). */
-    const int64_t* keep_tok;   /* ACC, ACC_QUEUE: int64 [n_keep] or NULL: all kept bars of all streams, flat */
-    const int32_t* keep_beg;   /* ACC, ACC_QUEUE: int32 [bars of lead_off] or NULL: < 0 = the bar is drawn */
-    const int32_t* keep_end;   /* ACC, ACC_QUEUE: int32 [bars of lead_off] or NULL */
-    int64_t n_keep;            /* ACC, ACC_QUEUE: entries of keep_tok */
+    const int64_t* keep_tok;   /* ACC, ACC_QUEUE, TXL, TXL_QUEUE: int64 [n_keep] or NULL: all kept bars of all streams, flat */
+    const int32_t* keep_beg;   /* ACC, ACC_QUEUE: int32 [bars of lead_off] or NULL: < 0 = the bar is drawn; TXL, TXL_QUEUE: int32 [all streams' kept-bar entries] */
+    const int32_t* keep_end;   /* ACC, ACC_QUEUE: int32 [bars of lead_off] or NULL; TXL, TXL_QUEUE: as keep_beg */
+    int64_t n_keep;            /* ACC, ACC_QUEUE, TXL, TXL_QUEUE: entries of keep_tok */
     int64_t keep_eos;          /* ACC, ACC_QUEUE: the id that closes a kept last bar (EOS_None) */
+    /* (kinds TXL and TXL_QUEUE read the four fields keep_tok / keep_beg / keep_end / n_keep above and the two below; the three tables and keep_left
+     * come together or not at all; all NULL: the launch is exactly the one without them.)  KEPT BARS of a lead sheet.  Stream r (a job, for
+     * TXL_QUEUE) has params[KEEP_BARS] entries of keep_beg / keep_end from params[KEEP0] on, indexed by the BAR NUMBER j: bar j is the bar opened
+     * by the Bar event that is accepted while state[BARS] == j (BARS then becomes j + 1; a primer's own bars are never kept).  keep_beg < 0, or
+     * j >= params[KEEP_BARS]: the bar is drawn, as ever; otherwise its content is keep_tok[keep_beg .. keep_end), possibly empty, with neither
+     * Bar.  KEEP0 < 0 or KEEP_BARS <= 0 is "no kept bars" to the kernel; the host checks KEEP0 + KEEP_BARS against the tables' length
+     * (ops.block_set).  When a drawn Bar has been accepted and appended, has opened bar j and left the stream RUNNING, and bar j is kept, thread
+     * 0 goes on in the same launch: the kept tokens (the length test against params[MAX_EVENTS] after each one, DONE inside the bar where it
+     * fires; no Beat check, no PAD / EOS rejection), then keep_bar, the Bar that closes it and opens bar j + 1: BARS += 1, the length test, DONE
+     * when BARS has reached params[MAX_BARS] (the closing Bar a caller drops, as it drops a drawn one); else a chain through consecutive kept
+     * bars.  The chain is walked once without writing: a range outside [0, n_keep], a range running backwards, or a chain that does not fit
+     * ld_seq ends the stream OVERFLOW with its row, LEN, BARS, BEAT, FAILED, ACCEPTED and DRAWS as before the draw (the reading of kinds ACC /
+     * ACC_QUEUE: the overflowing draw is not counted), and nothing outside keep_tok is read.  ACCEPTED and DRAWS move for the drawn Bar alone, the
+     * score cell is its cell.  The launch feeds the drawn Bar (tok_out); keep_left[r] = the tokens the chain wrote, which lie in seq[r] below LEN
+     * and are not yet fed: a RUNNING stream past its primer feed with keep_left[r] > 0 writes tok_out = seq[r, LEN - keep_left[r]], decrements
+     * keep_left[r] and does not draw, so the next draw is made from the logits behind the last forced Bar, and a rejection there feeds that Bar
+     * again.  BEAT and FAILED are 0 at the bar that is next opened for drawing.  A stream that ends inside the chain has keep_left[r] = 0 and
+     * leaves its last token in tok_out.  TXL_QUEUE: the fed kept tokens count against mem_rows like any other (MEM_FULL), and job_steps includes
+     * them.  A guided pair carries the same kept bars in both rows (the same KEEP0 / KEEP_BARS): each row writes its own chain.
+     * stage1_inference._LeadSheet._open_bar is the rule on the host. */
+    int64_t keep_bar;          /* TXL, TXL_QUEUE: the id that closes a kept bar (Bar_None), in [0, n_token) where the tables are present */
+    int32_t* keep_left;        /* TXL, TXL_QUEUE: int32 [streams] or NULL: kept tokens written in the row and not yet fed; the caller starts it at 0 */
     int64_t track_full;        /* ACC, ACC_WINDOW */
     int64_t window;            /* ACC_WINDOW: 0 < window <= ld_seq */
     const int32_t* rows;       /* ACC_WINDOW: int32 [n_rows] or NULL */
