@@ -50,6 +50,7 @@ class GrammarStep(ctypes.Structure):
                 ('guide_cond', c_p), ('guide_uncond', c_p), ('guide_scale', c_p),
                 ('segs', c_p), ('lead_tok', c_p), ('lead_off', c_p),
                 ('keep_tok', c_p), ('keep_beg', c_p), ('keep_end', c_p), ('n_keep', c_l), ('keep_eos', c_l), ('keep_bar', c_l), ('keep_left', c_p), ('track_full', c_l), ('window', c_l), ('rows', c_p), ('win_tok', c_p), ('win_seg', c_p),
+                ('tok_bias', c_p), ('n_biases', c_l), ('bias_of', c_p), ('top_k_of', c_p), ('min_p_of', c_p),
                 ('slot_job', c_p), ('queue_head', c_p), ('n_jobs', c_l), ('mem_lens', c_p), ('mem_rows', c_l), ('job_steps', c_p),
                 ('tok_mask', c_p), ('n_masks', c_l), ('mask_of', c_p), ('temp_of', c_p), ('top_p_of', c_p), ('row_reset', c_p),
                 ('tok_logp', c_p), ('tok_rank', c_p), ('tok_entropy', c_p)]

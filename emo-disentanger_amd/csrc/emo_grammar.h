@@ -28,20 +28,27 @@ __device__ __forceinline__ void emo_grammar_score(const emo_grammar_step_t& a, c
     if (tid == 0) emo_draw_scores_store(a.tok_logp, a.tok_rank, a.tok_entropy, r * a.ld_seq + c, logp, rank, entropy);
 }
 
-// Whether the block has any of the optional sampling controls (mask_of alone is not read).  emo_grammar_step asks on the host and launches the
-// kernel's <true> or <false> instance: without controls a launch runs the code it ran before they existed.
-__host__ __device__ __forceinline__ bool emo_grammar_has_controls(const emo_grammar_step_t& a) { return a.tok_mask || a.temp_of || a.top_p_of; }
+// Whether the block has any of the optional sampling controls (mask_of / bias_of alone are not read).  emo_grammar_step asks on the host and
+// launches the kernel's <true> or <false> instance: without controls a launch runs the code it ran before they existed.
+__host__ __device__ __forceinline__ bool emo_grammar_has_controls(const emo_grammar_step_t& a) {
+    return a.tok_mask || a.temp_of || a.top_p_of || a.tok_bias || a.top_k_of || a.min_p_of;
+}
 
-// What the draw of stream r runs under (r: the index of its params row: a stream, a job, or rows[b]): its ban row (NULL: none) and its
-// temperature / top_p.  CTL false: the block's two scalars, and the accessor of the draw folds to the plain load.  CTL true: temp_of / top_p_of
-// where present, and row mask_of[r] of tok_mask; a value outside [0, n_masks) is no mask, so nothing outside the table is ever read.
+// What the draw of stream r runs under (r: the index of its params row: a stream, a job, or rows[b]): its ban row (NULL: none), its
+// temperature / top_p, its bias row (NULL: none) and the two cuts behind top-p (top_k <= 0, min_p <= 0: off).  CTL false: the block's two
+// scalars, both cuts off, and the accessor of the draw folds to the plain load.  CTL true: temp_of / top_p_of / top_k_of / min_p_of where
+// present, row mask_of[r] of tok_mask and row bias_of[r] of tok_bias; a value outside [0, n_masks) is no mask and one outside [0, n_biases)
+// no bias, so nothing outside the tables is ever read.
 struct emo_grammar_controls_t {
     const uint32_t* ban;
     float temp, top_p;
+    const float* bias;
+    int32_t top_k;
+    float min_p;
 };
 template <bool CTL>
 __device__ __forceinline__ emo_grammar_controls_t emo_grammar_controls(const emo_grammar_step_t& a, int64_t r) {
-    emo_grammar_controls_t c{nullptr, a.temperature, a.top_p};
+    emo_grammar_controls_t c{nullptr, a.temperature, a.top_p, nullptr, 0, 0.f};
     if constexpr (CTL) {
         if (a.tok_mask && a.mask_of) {
             const int64_t m = a.mask_of[r];
@@ -49,6 +56,12 @@ __device__ __forceinline__ emo_grammar_controls_t emo_grammar_controls(const emo
         }
         if (a.temp_of) c.temp = a.temp_of[r];
         if (a.top_p_of) c.top_p = a.top_p_of[r];
+        if (a.tok_bias && a.bias_of) {
+            const int64_t m = a.bias_of[r];
+            if (m >= 0 && m < a.n_biases) c.bias = a.tok_bias + m * a.n_token;
+        }
+        if (a.top_k_of) c.top_k = a.top_k_of[r];
+        if (a.min_p_of) c.min_p = a.min_p_of[r];
     }
     return c;
 }

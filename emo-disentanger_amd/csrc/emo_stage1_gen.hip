@@ -10,9 +10,10 @@
 // When the caller wants them (tok_logp / tok_rank / tok_entropy), an accepted draw's figures go to the cell of the token it appended: from the
 // same logits row at temperature 1 — the key draw too, which draws at key_temperature — by the whole workgroup (emo_draw_scores.h), so thread 0
 // publishes the accepted column and word through LDS.  A rejection records nothing.
-// The optional sampling controls (tok_mask / mask_of / temp_of / top_p_of, indexed by the stream r as params is: emo_grammar_controls) reach the
-// draw alone: a banned token's logit is read as -inf there, the scores above are still taken from the row as the model wrote it, and primer
-// tokens are fed whether banned or not.
+// The optional sampling controls (tok_mask / mask_of / temp_of / top_p_of and tok_bias / bias_of / top_k_of / min_p_of, indexed by the stream r
+// as params is: emo_grammar_controls) reach the draw alone: a banned token's logit is read as -inf there and a biased one as l + bias, the
+// candidate count is cut by top_k and min_p behind top-p, the scores above are still taken from the row as the model wrote it, and primer
+// tokens are fed whether banned or not.  The key draw keeps key_temperature / key_top_p and runs under the ban, the bias and both cuts.
 // Kind TXL, optional classifier-free guidance (guide_cond / guide_uncond / guide_scale: emo_hip.h): a guided piece is two rows of the batch, a
 // leader on the conditioned primer and a follower on the same primer with the unconditioned token in the emotion's place.  Both workgroups draw
 // (the key draw included) from the same combination of the same two logits rows with the leader's uniform and the leader's controls, then each
@@ -193,22 +194,25 @@ __device__ __forceinline__ void txl_stream_step(const emo_grammar_step_t& a, int
     const int32_t len = sst[EMO_TXL_S_LEN];
     const bool key_step = spr[EMO_TXL_P_KEYED] != 0 && len == 1;          // the event after the emotion tag is the key (:81-89)
     int64_t word;
+    // (the key draw keeps key_temperature / key_top_p; the ban, the bias and the two cuts hold for it too)
     if constexpr (GUIDE) {
         const int64_t gc = a.guide_cond[r], gu = a.guide_uncond[r];
         if (gc != gu && gc >= 0 && gc < a.n_rows && gu >= 0 && gu < a.n_rows) {
             const emo_grammar_controls_t ctl = emo_grammar_controls<CTL>(a, gc);
-            word = emo_nucleus_draw_from(emo_guided_logits{a.logits + gc * a.n_token, a.logits + gu * a.n_token, a.guide_scale[r], ctl.ban}, a.n_token,
-                                         key_step ? a.key_temperature : ctl.temp, key_step ? a.key_top_p : ctl.top_p,
+            word = emo_nucleus_draw_from(emo_guided_logits{a.logits + gc * a.n_token, a.logits + gu * a.n_token, a.guide_scale[r], ctl.ban, ctl.bias},
+                                         a.n_token, key_step ? a.key_temperature : ctl.temp, key_step ? a.key_top_p : ctl.top_p, ctl.top_k, ctl.min_p,
                                          a.u_steps[(int64_t)draws * a.ld_u + gc], lds, tid, [] { __syncthreads(); });
         } else {
             const emo_grammar_controls_t ctl = emo_grammar_controls<CTL>(a, r);
-            word = emo_nucleus_draw_from(emo_banned_logits{a.logits + b * a.n_token, ctl.ban}, a.n_token, key_step ? a.key_temperature : ctl.temp,
-                                         key_step ? a.key_top_p : ctl.top_p, a.u_steps[(int64_t)draws * a.ld_u + r], lds, tid, [] { __syncthreads(); });
+            word = emo_nucleus_draw_from(emo_banned_logits{a.logits + b * a.n_token, ctl.ban, ctl.bias}, a.n_token, key_step ? a.key_temperature : ctl.temp,
+                                         key_step ? a.key_top_p : ctl.top_p, ctl.top_k, ctl.min_p, a.u_steps[(int64_t)draws * a.ld_u + r], lds, tid,
+                                         [] { __syncthreads(); });
         }
     } else {
-        const emo_grammar_controls_t ctl = emo_grammar_controls<CTL>(a, r);  // (the key draw keeps key_temperature / key_top_p; the ban holds for it too)
-        word = emo_nucleus_draw_from(emo_banned_logits{a.logits + b * a.n_token, ctl.ban}, a.n_token, key_step ? a.key_temperature : ctl.temp,
-                                     key_step ? a.key_top_p : ctl.top_p, a.u_steps[(int64_t)draws * a.ld_u + r], lds, tid, [] { __syncthreads(); });
+        const emo_grammar_controls_t ctl = emo_grammar_controls<CTL>(a, r);
+        word = emo_nucleus_draw_from(emo_banned_logits{a.logits + b * a.n_token, ctl.ban, ctl.bias}, a.n_token, key_step ? a.key_temperature : ctl.temp,
+                                     key_step ? a.key_top_p : ctl.top_p, ctl.top_k, ctl.min_p, a.u_steps[(int64_t)draws * a.ld_u + r], lds, tid,
+                                     [] { __syncthreads(); });
     }
     if (!emo_grammar_wants_scores(a)) {
         if (tid == 0) txl_grammar<KEEP>(a, b, r, row, st, sst, spr, word, draws, key_step, len);

@@ -19,9 +19,10 @@
 // temperature 1, go to the cell of the token it appended (emo_draw_scores.h) — after the draw loop has ended, since the redraws read the sorted
 // state, and by the whole workgroup: whether and where a draw was accepted is read from the LDS state words thread 0 wrote before the loop's
 // last barrier.
-// All kinds, optional sampling controls (tok_mask / mask_of / temp_of / top_p_of, indexed by the stream r as params is: emo_grammar_controls): a
-// banned token's logit is read as -inf by the draw and by nothing else: the scores above are still the model's, from the row as it wrote it, and
-// primer tokens, injected bars and track_full are fed whether banned or not.
+// All kinds, optional sampling controls (tok_mask / mask_of / temp_of / top_p_of and tok_bias / bias_of / top_k_of / min_p_of, indexed by the
+// stream r as params is: emo_grammar_controls): a banned token's logit is read as -inf and a biased one as l + bias by the draw and by nothing
+// else, and the draw's candidate count is cut by top_k and min_p behind top-p (the redraws of a launch use the same count): the scores above
+// are still the model's, from the row as it wrote it, and primer tokens, injected bars and track_full are fed whether banned or not.
 // Kind ACC, optional classifier-free guidance (guide_cond / guide_uncond / guide_scale: emo_hip.h): a guided piece is two rows of the batch, a
 // leader on the conditioned primer and a follower on the unconditioned one.  Both workgroups draw from the same combination of the same two
 // logits rows with the same uniform and run the same grammar, so the follower stays token for token with its leader and no workgroup reads or
@@ -38,8 +39,8 @@ namespace {
 // `draws` advances in every thread alike, and thread 0 runs the grammar on the LDS copy of the state (kept there, not in registers, across the
 // draws); it alone gets the status back (the other threads: RUNNING).  Besides the block, what differs per call: l the accessor of the stream's
 // logits (emo_nucleus.h: its row under its ban, or the guided combination of two rows), u_col its column of the uniform table (pitch a.ld_u),
-// row / srow its token and segment rows, ctl its sampling controls (emo_grammar_controls: the ban is the accessor's and reaches the first
-// draw's sort, which the redraws reuse; the scores are taken by the caller from the row as the model wrote it).
+// row / srow its token and segment rows, ctl its sampling controls (emo_grammar_controls: the ban and the bias are the accessor's and reach
+// the first draw's sort, which the redraws reuse with the same two cuts; the scores are taken by the caller from the row as the model wrote it).
 // Thread 0, after an accepted Track_LeadSheet has opened bar k (its lead-sheet bar and track_full are at the end of the row, `len` tokens long):
 // the chain of consecutive kept bars from k on (emo_hip.h: keep_tok).  WRITE false walks it without touching the row, so the caller tests the
 // whole chain against ld_seq before it writes anything; both walks take the same path.  -> RUNNING (bar k, or the bar behind the chain, is
@@ -101,8 +102,8 @@ __device__ __forceinline__ int32_t acc_draw(const emo_grammar_step_t& a, const e
         // a redraw from the same logits needs only the cut and the pick over the sorted state the first draw left in LDS (the same operations
         // on the same data: the id a fresh emo_nucleus_draw with this uniform would give)
         const float u = u_col[(int64_t)draws * a.ld_u];
-        const int64_t word = draws == draws0 ? emo_nucleus_draw_from(l, V, ctl.temp, ctl.top_p, u, lds, tid, [] { __syncthreads(); })
-                                            : emo_nucleus_pick(V, ctl.top_p, u, lds, tid, [] { __syncthreads(); });
+        const int64_t word = draws == draws0 ? emo_nucleus_draw_from(l, V, ctl.temp, ctl.top_p, ctl.top_k, ctl.min_p, u, lds, tid, [] { __syncthreads(); })
+                                            : emo_nucleus_pick(V, ctl.top_p, ctl.top_k, ctl.min_p, u, lds, tid, [] { __syncthreads(); });
         ++draws;
         if (tid == 0) {
             const int32_t fl = a.ev_flags[word], target = spr[EMO_ACC_P_TARGET_BARS], bars = sst[EMO_ACC_S_BARS];
@@ -224,11 +225,11 @@ __device__ __forceinline__ void acc_stream_step(const emo_grammar_step_t& a, int
         gc = a.guide_cond[r];
         gu = a.guide_uncond[r];
     }
-    if (GUIDE && gc != gu && gc >= 0 && gc < a.n_rows && gu >= 0 && gu < a.n_rows)
-        status = acc_draw<KEEP>(a, ctl, emo_guided_logits{a.logits + gc * a.n_token, a.logits + gu * a.n_token, a.guide_scale[r], ctl.ban}, a.u_steps + gc, row,
-                          srow, spr, sst, sagain, lds, tid, draws);
+    if (GUIDE && gc != gu && gc >= 0 && gc < a.n_rows && gu >= 0 && gu < a.n_rows)      // (both rows of a pair add the LEADER's bias row)
+        status = acc_draw<KEEP>(a, ctl, emo_guided_logits{a.logits + gc * a.n_token, a.logits + gu * a.n_token, a.guide_scale[r], ctl.ban,
+                                                          emo_grammar_controls<CTL>(a, gc).bias}, a.u_steps + gc, row, srow, spr, sst, sagain, lds, tid, draws);
     else
-        status = acc_draw<KEEP>(a, ctl, emo_banned_logits{a.logits + b * a.n_token, ctl.ban}, a.u_steps + r, row, srow, spr, sst, sagain, lds, tid, draws);
+        status = acc_draw<KEEP>(a, ctl, emo_banned_logits{a.logits + b * a.n_token, ctl.ban, ctl.bias}, a.u_steps + r, row, srow, spr, sst, sagain, lds, tid, draws);
     // an acceptance appended its word at the old length (an injected bar follows it) and counted itself, in front of the loop's last barrier
     if (scores && sst[EMO_ACC_S_ACCEPTED] != acc0) emo_grammar_score(a, a.logits + b * a.n_token, r, len0, row[len0], sred, tid);
     if (tid != 0) return;
@@ -352,7 +353,7 @@ __global__ __launch_bounds__(512) void acc_window_kernel(const emo_grammar_step_
     const bool scores = emo_grammar_wants_scores(a);         // as in acc_grammar_kernel; the tables are indexed by the stream r, the logits by b
     const int32_t len0 = scores ? sst[EMO_ACC_S_LEN] : 0, acc0 = scores ? sst[EMO_ACC_S_ACCEPTED] : 0;
     const emo_grammar_controls_t ctl = emo_grammar_controls<CTL>(a, r);
-    const int32_t status = acc_draw<false>(a, ctl, emo_banned_logits{a.logits + b * a.n_token, ctl.ban}, a.u_steps + r, row, srow, spr, sst, &sagain, lds, tid, draws);
+    const int32_t status = acc_draw<false>(a, ctl, emo_banned_logits{a.logits + b * a.n_token, ctl.ban, ctl.bias}, a.u_steps + r, row, srow, spr, sst, &sagain, lds, tid, draws);
     if (scores && sst[EMO_ACC_S_ACCEPTED] != acc0) emo_grammar_score(a, a.logits + b * a.n_token, r, len0, row[len0], sred, tid);
     if (tid == 0) {
         if (status != EMO_ACC_RUNNING) atomicSub(a.running, 1);
@@ -403,6 +404,9 @@ extern "C" int emo_grammar_step(const emo_grammar_step_t* args, emo_stream_t str
                   "emo_grammar_step[%s]: keep_tok, keep_beg, keep_end and keep_left come together or not at all, with 0 <= n_keep < 2^31", name);
         EMO_CHECK(txl_keep == 0 || (a.keep_bar >= 0 && a.keep_bar < a.n_token), "emo_grammar_step[%s]: keep_bar %lld lies outside [0, V)", name,
                   (long long)a.keep_bar);
+        // (the bias table comes with the map that reads it and with its row count; asked last, behind every other refusal of the kind)
+        EMO_CHECK(!a.tok_bias || (a.bias_of && a.n_biases > 0), "emo_grammar_step[%s]: tok_bias needs bias_of and n_biases > 0 (got n_biases %lld)", name,
+                  (long long)a.n_biases);
         return tq ? emo_txl_queue_launch(a, stream) : emo_txl_grammar_launch(a, stream);
     }
     EMO_CHECK(a.temperature > 0.f, "emo_grammar_step[%s]: temperature must be > 0", name);
@@ -416,6 +420,9 @@ extern "C" int emo_grammar_step(const emo_grammar_step_t* args, emo_stream_t str
     const int keep = acc ? (a.keep_tok != nullptr) + (a.keep_beg != nullptr) + (a.keep_end != nullptr) : 0;
     EMO_CHECK(keep == 0 || (keep == 3 && a.n_keep >= 0 && a.n_keep <= INT32_MAX),
               "emo_grammar_step[%s]: keep_tok, keep_beg and keep_end come together or not at all, with 0 <= n_keep < 2^31", name);
+    // (the bias table comes with the map that reads it and with its row count; asked last, behind every other refusal of the kind)
+    EMO_CHECK(!a.tok_bias || (a.bias_of && a.n_biases > 0), "emo_grammar_step[%s]: tok_bias needs bias_of and n_biases > 0 (got n_biases %lld)", name,
+              (long long)a.n_biases);
     const auto kernel = aq       ? (keep ? (ctl ? acc_queue_kernel<true, true> : acc_queue_kernel<false, true>)
                                          : (ctl ? acc_queue_kernel<true, false> : acc_queue_kernel<false, false>))
                         : !acc   ? (ctl ? acc_window_kernel<true> : acc_window_kernel<false>)

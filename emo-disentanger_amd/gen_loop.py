@@ -43,15 +43,59 @@ def pack_token_masks(bans, V):
     return mask, mask_of
 
 
+def pack_token_biases(biases, V):
+    """Per-stream bias rows (None, or float32 [V]) -> (tok_bias f32 [n_biases, V], bias_of int32 [n]) as the grammar launch reads them
+    (emo_hip.h: tok_bias): stream r's draw reads token c's logit as l + tok_bias[bias_of[r], c]; bias_of[r] = -1: no bias.  Equal rows share a
+    row of the table (rows in the order of first use), as ban rows do."""
+    rows, at, bias_of = [], {}, np.full(len(biases), -1, np.int32)
+    for r, b in enumerate(biases):
+        if b is None:
+            continue
+        b = np.ascontiguousarray(b, np.float32)
+        if b.shape != (V,):
+            raise ValueError('a bias row has shape %s, not (%d,)' % (b.shape, V))
+        key = b.tobytes()
+        if key not in at:
+            at[key] = len(rows)
+            rows.append(b)
+        bias_of[r] = at[key]
+    return (np.stack(rows) if rows else np.zeros((0, V), np.float32)), bias_of
+
+
 class DrawControls:
     """The per-stream sampling controls of a device generation loop, checked: bans[r] (None, or the sorted ids stream r never draws), temps /
     top_ps (one float per stream, or None where the caller gave one value for all: then `temp` / `top_p`, the launch's scalars, hold), and the
     classifier-free guidance pairs guide_cond / guide_uncond / guide_scale (one entry per stream as emo_hip.h lays them out: (-1, -1, 0.0) for a
-    stream without guidance; all three None where no stream is guided)."""
+    stream without guidance; all three None where no stream is guided).  The soft controls: biases[r] (None, or the float32 [V] row added to
+    stream r's logits in the draw; None in place of the list where no stream has one), top_ks / min_ps (one int / float per stream, 0 = off,
+    or None where the caller gave none)."""
 
-    def __init__(self, n, V, bans, temp, temps, top_p, top_ps, guide=None):
+    def __init__(self, n, V, bans, temp, temps, top_p, top_ps, guide=None, biases=None, top_ks=None, min_ps=None):
         self.n, self.V, self.bans, self.temp, self.temps, self.top_p, self.top_ps = n, V, bans, temp, temps, top_p, top_ps
         self.guide_cond, self.guide_uncond, self.guide_scale = guide if guide is not None else (None, None, None)
+        self.biases, self.top_ks, self.min_ps = biases, top_ks, min_ps
+
+    @property
+    def soft_arg(self):
+        """The soft controls in the form the loop classes take as `soft` (draw_controls' bias / top_k / min_p, per stream), or None."""
+        if self.biases is None and self.top_ks is None and self.min_ps is None:
+            return None
+        return dict(bias=None if self.biases is None else list(self.biases), top_k=None if self.top_ks is None else list(self.top_ks),
+                    min_p=None if self.min_ps is None else list(self.min_ps))
+
+    def bias_at(self, r):
+        return None if self.biases is None else self.biases[r]
+
+    def top_k_at(self, r):
+        return 0 if self.top_ks is None else self.top_ks[r]
+
+    def min_p_at(self, r):
+        return 0.0 if self.min_ps is None else self.min_ps[r]
+
+    def soft_key(self, r):
+        """What two rows of a guidance pair must share of the soft controls."""
+        b = self.bias_at(r)
+        return (None if b is None else b.tobytes(), self.top_k_at(r), self.min_p_at(r))
 
     @property
     def temp_arg(self):
@@ -83,7 +127,7 @@ class DrawControls:
 
     def with_guidance(self, scales):
         """scales: one float per stream (0: no guidance) -> the controls of these streams followed by one FOLLOWER per guided stream, in their
-        order: a copy of its leader's ban, temp and top_p.  Leader i and its follower g both hold the pair (i, g) and the leader's scale."""
+        order: a copy of its leader's ban, temp, top_p, bias row, top_k and min_p.  Leader i and its follower g both hold the pair (i, g) and the leader's scale."""
         lead = [i for i in range(self.n) if scales[i] > 0]
         if not lead:
             return self
@@ -119,7 +163,8 @@ class DrawControls:
                      [self.guide_scale[i] for i in idx])
             if all(c < 0 for c in guide[0]):
                 guide = None
-        return DrawControls(len(idx), self.V, [self.bans[i] for i in idx], self.temp, pick(self.temps), self.top_p, pick(self.top_ps), guide)
+        return DrawControls(len(idx), self.V, [self.bans[i] for i in idx], self.temp, pick(self.temps), self.top_p, pick(self.top_ps), guide,
+                            pick(self.biases), pick(self.top_ks), pick(self.min_ps))
 
     def repeat(self, k):
         """Every stream k times in a row: stream i * k + c has the controls of input i (scoring.best_of_plan's order); copy c of a leader is
@@ -129,8 +174,16 @@ class DrawControls:
     def tables(self):
         """-> the optional fields of emo_grammar_step_t that are present, as numpy: {'tok_mask' uint32 [n_masks, words], 'mask_of' int32 [n]}
         when a stream has a ban, {'temp_of'} / {'top_p_of'} f32 [n] when the caller gave per-stream values, {'guide_cond', 'guide_uncond' int32
-        [n], 'guide_scale' f32 [n]} when a stream is guided.  {} = every new field NULL."""
+        [n], 'guide_scale' f32 [n]} when a stream is guided, {'tok_bias' f32 [n_biases, V], 'bias_of' int32 [n]} when a stream has a bias (equal
+        rows share a row of the table, in the order of first use; -1: none), {'top_k_of'} int32 [n] / {'min_p_of'} f32 [n] when the caller gave
+        them.  {} = every new field NULL."""
         out = {}
+        if self.biases is not None and any(b is not None for b in self.biases):
+            out['tok_bias'], out['bias_of'] = pack_token_biases(self.biases, self.V)
+        if self.top_ks is not None:
+            out['top_k_of'] = np.array(self.top_ks, np.int32)
+        if self.min_ps is not None:
+            out['min_p_of'] = np.array(self.min_ps, np.float32)
         if any(b is not None for b in self.bans):
             out['tok_mask'], out['mask_of'] = pack_token_masks(self.bans, self.V)
         if self.temps is not None:
@@ -165,13 +218,93 @@ def _per_input(who, name, value, n, ok, rule):
     return vals[0], per
 
 
-def draw_controls(who, n, V, banned=None, temp=1.2, top_p=0.9, guidance=None):
+def _bias_row(who, i, entry, V, event2idx):
+    """One bias entry (None, a dict {token id or event name: value}, or a full-length array) -> None or the checked float32 [V] row."""
+    if entry is None:
+        return None
+    if isinstance(entry, dict):
+        row = np.zeros(V, np.float32)
+        for k, v in entry.items():
+            if isinstance(k, str):
+                if event2idx is None or k not in event2idx:
+                    raise ValueError('%s: bias[%d] names %r, which is no event of the vocabulary' % (who, i, k))
+                k = event2idx[k]
+            if not _is_id(k) or not 0 <= k < V:
+                raise ValueError('%s: bias[%d] has token id %r outside [0, %d)' % (who, i, k, V))
+            row[int(k)] = v
+    else:
+        try:
+            row = np.array(entry, np.float32)
+        except (TypeError, ValueError):
+            raise ValueError('%s: bias[%d] is neither a dict nor an array of %d values' % (who, i, V))
+        if row.shape != (V,):
+            raise ValueError('%s: bias[%d] has shape %s, a full-length row has (%d,)' % (who, i, row.shape, V))
+    if np.isnan(row).any() or (row == np.inf).any():
+        raise ValueError('%s: bias[%d] holds NaN or +inf (values are finite, or -inf for a ban)' % (who, i))
+    if (row == -np.inf).all():
+        raise ValueError('%s: bias[%d] bans every token' % (who, i))
+    return row if row.any() else None                          # (all zeros: no bias)
+
+
+def _bias_rows(who, bias, n, V, event2idx):
+    """bias: None, one entry for all inputs (a dict, or a 1-D array of V numbers), or one entry per input -> None or the n checked rows."""
+    if bias is None:
+        return None
+    one = isinstance(bias, dict) or (isinstance(bias, np.ndarray) and bias.ndim == 1 and bias.dtype.kind in 'fiu')
+    if not one and not isinstance(bias, np.ndarray):
+        bias = list(bias)
+        one = len(bias) > 0 and all(isinstance(v, numbers.Real) for v in bias)
+    if V is None:
+        raise ValueError('%s: a bias needs the vocabulary size' % who)
+    if one:
+        return [_bias_row(who, 0, bias, V, event2idx)] * n
+    if len(bias) != n:
+        raise ValueError('%s: bias has %d entries for %d inputs' % (who, len(bias), n))
+    rows = [_bias_row(who, i, b, V, event2idx) for i, b in enumerate(bias)]
+    return rows if any(r is not None for r in rows) else None
+
+
+def _per_input_soft(who, name, value, n, conv):
+    """top_k / min_p: None, one value for all inputs, or one per input (None in a list: off) -> None or the n checked values."""
+    if value is None:
+        return None
+    if isinstance(value, (numbers.Real, np.generic)):
+        return [conv(who, name, value)] * n
+    try:
+        vals = list(value)
+    except TypeError:
+        raise ValueError('%s: %s must be a number or one per input (got %r)' % (who, name, value))
+    if len(vals) != n:
+        raise ValueError('%s: %s has %d entries for %d inputs' % (who, name, len(vals), n))
+    return [conv(who, name, 0 if v is None else v) for v in vals]
+
+
+def _as_top_k(who, name, v):
+    if isinstance(v, (bool, np.bool_)) or not (isinstance(v, (numbers.Integral, np.integer)) or (isinstance(v, numbers.Real) and float(v) == int(v))):
+        raise ValueError('%s: %s must be an integer (got %r)' % (who, name, v))
+    return max(0, min(int(v), 2 ** 31 - 1))
+
+
+def _as_min_p(who, name, v):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (numbers.Real, np.floating)) or float(v) != float(v):
+        raise ValueError('%s: %s must be a number, not NaN (got %r)' % (who, name, v))
+    return max(0.0, float(v))
+
+
+def draw_controls(who, n, V, banned=None, temp=1.2, top_p=0.9, guidance=None, bias=None, top_k=None, min_p=None, event2idx=None):
     """The sampling controls of n inputs over a vocabulary of V tokens (read only where there is a ban), checked before anything is allocated
     -> DrawControls.  banned: None (no ban), one sequence of token ids (for every input), or one entry per input, each a sequence of ids or
     None; temp / top_p: a number, or one per input.  ValueError for an id outside [0, V), a ban that leaves no token, a per-input list of the
     wrong length, a temperature <= 0, a top_p outside (0, 1].  guidance: None, or the classifier-free guidance pairs of the n inputs as (guide_cond,
     guide_uncond, guide_scale) lists (emo_hip.h; ops.guide_pairs_error is the rule, ValueError where it is broken, and where the two rows of a
-    pair differ in ban, temp or top_p)."""
+    pair differ in ban, temp, top_p or a soft control).
+    The soft controls (emo_hip.h: tok_bias / top_k_of / min_p_of), each None, one value for all inputs, or one per input: bias entries are
+    dicts {token id or event name (needs event2idx): value} or full-length arrays of V values, finite or -inf (a ban); top_k an integer (<= 0
+    or None: off); min_p a number (<= 0 or None: off).  ValueError for a wrong length, an id outside [0, V), an unknown event name, a NaN or
+    +inf bias value, a top_k that is no integer, a min_p that is NaN."""
+    biases = _bias_rows(who, bias, n, V, event2idx)
+    top_ks = _per_input_soft(who, 'top_k', top_k, n, _as_top_k)
+    min_ps = _per_input_soft(who, 'min_p', min_p, n, _as_min_p)
     if banned is None:
         bans = [None] * n
     else:
@@ -200,7 +333,7 @@ def draw_controls(who, n, V, banned=None, temp=1.2, top_p=0.9, guidance=None):
         checked.append(ids or None)
     t, ts = _per_input(who, 'temp', temp, n, lambda v: v > 0 and v == v and v != float('inf'), '> 0')
     p, ps = _per_input(who, 'top_p', top_p, n, lambda v: 0 < v <= 1, 'in (0, 1]')
-    ctl = DrawControls(n, V, checked, t, ts, p, ps)
+    ctl = DrawControls(n, V, checked, t, ts, p, ps, None, biases, top_ks, min_ps)
     if guidance is not None:
         cond, unc, scale = ([int(x) for x in guidance[0]], [int(x) for x in guidance[1]], [float(x) for x in guidance[2]])
         bad = ops.guide_pairs_error(cond, unc, scale) if len(cond) == n else 'guide tables of %d rows for %d inputs' % (len(cond), n)
@@ -210,6 +343,8 @@ def draw_controls(who, n, V, banned=None, temp=1.2, top_p=0.9, guidance=None):
             o = unc[r] if cond[r] == r else cond[r]
             if cond[r] >= 0 and (ctl.bans[r], ctl.temp_at(r), ctl.top_p_at(r)) != (ctl.bans[o], ctl.temp_at(o), ctl.top_p_at(o)):
                 raise ValueError('%s: rows %d and %d of a guidance pair differ in ban, temp or top_p' % (who, r, o))
+            if cond[r] >= 0 and ctl.soft_key(r) != ctl.soft_key(o):
+                raise ValueError('%s: rows %d and %d of a guidance pair differ in bias, top_k or min_p' % (who, r, o))
         if any(c >= 0 for c in cond):
             ctl.guide_cond, ctl.guide_uncond, ctl.guide_scale = cond, unc, scale
     return ctl
@@ -235,7 +370,7 @@ class GrammarLoop:
         """The grammar launch's argument block (emo_hip.h: emo_grammar_step_t), written once: _gheld keeps what its addresses point to alive,
         the score tables (self.score_tables: ops.draw_score_tables laid out like self.seq, None without `scores`) included, and the tables of
         `controls` (a DrawControls over the streams that `params` holds, or None: self.control_tables, {} where every one of the block's
-        optional tok_mask / mask_of / temp_of / top_p_of and guide_cond / guide_uncond / guide_scale stays NULL).  No tensor of the block is allocated again after this: captured graphs
+        optional tok_mask / mask_of / temp_of / top_p_of, tok_bias / bias_of / top_k_of / min_p_of and guide_cond / guide_uncond / guide_scale stays NULL).  No tensor of the block is allocated again after this: captured graphs
         hold the raw addresses."""
         self._gargs, self._gheld = ops.GrammarStep(kind=kind), {}
         ops.block_set(self._gargs, self._gheld, **fields)
@@ -249,7 +384,8 @@ class GrammarLoop:
             tabs['tok_mask'] = tabs['tok_mask'].view(np.int32)
         self.control_tables = dict(zip(tabs, self._to_device(*tabs.values())))
         if tabs:
-            ops.block_set(self._gargs, self._gheld, n_masks=len(tabs['tok_mask']) if 'tok_mask' in tabs else 0, **self.control_tables)
+            ops.block_set(self._gargs, self._gheld, n_masks=len(tabs['tok_mask']) if 'tok_mask' in tabs else 0,
+                          n_biases=len(tabs['tok_bias']) if 'tok_bias' in tabs else 0, **self.control_tables)
         self.score_tables = ops.draw_score_tables(self.seq) if scores else None
         if scores:
             ops.block_set(self._gargs, self._gheld, **self.score_tables)

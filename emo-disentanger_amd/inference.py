@@ -18,7 +18,7 @@ import time
 import numpy as np
 import torch
 
-from . import engine, ops, scoring
+from . import engine, ops, sampling, scoring
 from ._lib import EmoError
 from .gen_loop import GrammarLoop, check_vocab, draw_controls
 from .replay import StepReplayer, graph_steps
@@ -747,7 +747,7 @@ class _Stream:
 
 
 def generate_conditional_batch(model, event2idx, idx2event, lead_sheets, primers, max_events=10000, skip_check=False, max_bars=None,
-                               temp=1.2, top_p=0.9, inadmissibles=None, samplers=None, seeds=None, keep=None):
+                               temp=1.2, top_p=0.9, inadmissibles=None, samplers=None, seeds=None, keep=None, bias=None, top_k=None, min_p=None):
     """n independent generate_conditional() runs (one lead sheet + primer each) in lock-step on ONE decode engine: per-stream bar
     counter, Beat position, rejection counter and RNG; every engine step feeds each unfinished stream its next pending token (a
     sampled word, or the next token of an injected lead-sheet bar), so streams of different lengths stay aligned in position.
@@ -755,13 +755,17 @@ def generate_conditional_batch(model, event2idx, idx2event, lead_sheets, primers
     generate_conditional(..., sampler=samplers[i]) returns for it alone (tests/test_gpu_generate.py), as long as it stays inside
     the 2048-token window (max_dec_inp_len); a stream that reaches the window is finished by the single-stream windowed path.
     keep (None: every bar is drawn): one entry per input, None or a per-bar list of None / token ids: the bars that are given, not drawn
-    (_Stream._open_bar is the rule; check_keep the refusals).  This is the reference the device loops' keep= is held to."""
+    (_Stream._open_bar is the rule; check_keep the refusals).  This is the reference the device loops' keep= is held to.
+    bias / top_k / min_p (gen_loop.draw_controls: None, one value for all, or one per input): the soft controls of the device draw on the host.
+    Stream i's probabilities are taken from float32 `logits + bias` (sampling.biased), and a stream with a cut calls its sampler as
+    samplers[i](probs, top_k=k, min_p=m) (sampling.nucleus applies sampling.soft_cut_count); a stream without one as samplers[i](probs)."""
     n = len(lead_sheets)
     assert n == len(primers) and n > 0
     keep = check_keep('generate_conditional_batch', keep, lead_sheets, model.n_token, event2idx)
+    soft = draw_controls('generate_conditional_batch', n, model.n_token, bias=bias, top_k=top_k, min_p=min_p, event2idx=event2idx)
     if samplers is None:
         rss = [np.random.RandomState((seeds[i] if seeds is not None else i)) for i in range(n)]
-        samplers = [(lambda probs, rs=rs: nucleus(probs, top_p, rng=rs)) for rs in rss]
+        samplers = [(lambda probs, rs=rs, **cut: nucleus(probs, top_p, rng=rs, **cut)) for rs in rss]
     dev = next(model.parameters()).device
     st = [_Stream(event2idx, lead_sheets[i], primers[i], max_bars, keep[i] if keep else None, max_events) for i in range(n)]
     pad = event2idx.get('PAD_None', 0)
@@ -793,8 +797,8 @@ def generate_conditional_batch(model, event2idx, idx2event, lead_sheets, primers
                         if getattr(eng, 'persist', None) is not None:
                             eng.check_persistent()
                     while True:                                  # a rejected sample re-derives probs from the same logits (reference: `continue`)
-                        probs = temperature(logits_np[i].copy(), temp, inadmissibles=inadmissibles)
-                        if s.offer(int(samplers[i](probs)), event2idx, idx2event, skip_check, max_events):
+                        probs = temperature(sampling.biased(logits_np[i].copy(), soft.bias_at(i)), temp, inadmissibles=inadmissibles)
+                        if s.offer(int(samplers[i](probs, **_cut_kw(soft, i))), event2idx, idx2event, skip_check, max_events):
                             break
                 if all(s.done for s in st):
                     break
@@ -808,11 +812,27 @@ def generate_conditional_batch(model, event2idx, idx2event, lead_sheets, primers
         model.train(was_training)
     out = [s.result() for s in st]
     for i in overflow:       # rare: hand the stream to the reference-shaped single-stream loop (full-window forward per token)
-        out[i] = _resume_windowed(model, event2idx, idx2event, st[i], max_events, skip_check, temp, inadmissibles, samplers[i])
+        out[i] = _resume_windowed(model, event2idx, idx2event, st[i], max_events, skip_check, temp, inadmissibles, samplers[i], **_soft_kw(soft, i))
     return out
 
 
-def _resume_windowed(model, event2idx, idx2event, s, max_events, skip_check, temp, inadmissibles, sampler):
+def _cut_kw(ctl, i):
+    """The keyword arguments a sampler is called with for stream i of the controls `ctl`: its cuts where it has one, else none."""
+    k, m = ctl.top_k_at(i), ctl.min_p_at(i)
+    return dict(top_k=k, min_p=m) if k > 0 or m > 0 else {}
+
+
+def _soft_kw(ctl, i):
+    """The soft controls of stream i as keyword arguments of _resume_windowed: none where the stream has none."""
+    kw = _cut_kw(ctl, i)
+    if ctl.bias_at(i) is not None:
+        kw['bias'] = ctl.bias_at(i)
+    return kw
+
+
+def _resume_windowed(model, event2idx, idx2event, s, max_events, skip_check, temp, inadmissibles, sampler, bias=None, top_k=0, min_p=0.0):
+    """bias / top_k / min_p: the stream's soft controls (a float32 row added to the logits; the cuts handed to `sampler` as keywords)."""
+    cut = dict(top_k=top_k, min_p=min_p) if top_k > 0 or min_p > 0 else {}
     dev = next(model.parameters()).device
     s.done = False
     was_training = model.training
@@ -825,8 +845,8 @@ def _resume_windowed(model, event2idx, idx2event, s, max_events, skip_check, tem
                 kw = {'attn_kwargs': {'omit_feature_map_draw': True}} if model.kind == 'performer' else {}
                 logits_np = model(dec_input, seg_inp=dec_seg, keep_last_only=True, **kw)[0].cpu().numpy().copy()
                 while True:
-                    probs = temperature(logits_np.copy(), temp, inadmissibles=inadmissibles)
-                    if s.offer(int(sampler(probs)), event2idx, idx2event, skip_check, max_events):
+                    probs = temperature(sampling.biased(logits_np.copy(), bias), temp, inadmissibles=inadmissibles)
+                    if s.offer(int(sampler(probs, **cut)), event2idx, idx2event, skip_check, max_events):
                         break
     finally:
         model.train(was_training)
@@ -1034,6 +1054,29 @@ def parse_reroll(spec, n_bars):
     return sorted(bars)
 
 
+def event_bias(event2idx, values):
+    """A bias for generate_accompaniments / generate_lead_sheets (bias=) from event names -> {token id: value}.  values: {key: value}, a key an
+    event name of the vocabulary ('Bar_None') or a prefix that at least one event starts with ('Note_Pitch_': every such event); a name
+    wins over a prefix, a longer prefix over a shorter one.  ValueError for a key that matches nothing."""
+    out = {}
+    for key in sorted(values, key=lambda k: (k in event2idx, len(k))):
+        ids = [event2idx[key]] if key in event2idx else [i for e, i in event2idx.items() if e.startswith(key)]
+        if not ids:
+            raise ValueError('event_bias: %r is neither an event of the vocabulary nor the prefix of one' % (key,))
+        for i in ids:
+            out[i] = float(values[key])
+    return out
+
+
+def pitch_range_bias(event2idx, lo, hi, value):
+    """-> {token id: value} for every Note_Pitch_<n> event with n outside [lo, hi]: as bias= (value < 0, or -inf) the draw stays in the
+    register.  ValueError when the vocabulary has no Note_Pitch_* event."""
+    pitches = {e: i for e, i in event2idx.items() if e.startswith('Note_Pitch_')}
+    if not pitches:
+        raise ValueError('pitch_range_bias: the vocabulary has no Note_Pitch_* event')
+    return {i: float(value) for e, i in pitches.items() if not lo <= int(e.rsplit('_', 1)[1]) <= hi}
+
+
 def tempo_ban(event2idx, tempo, tolerance=20):
     """The ids of the tempo events further than `tolerance` from `tempo`: every key of event2idx that contains 'Tempo' and not 'Conti' and
     whose trailing integer differs from tempo by more than tolerance.  As `banned` of generate_accompaniments (or `inadmissibles` of the host
@@ -1158,8 +1201,8 @@ class AccompanimentLoop(GrammarLoop):
     NumPy's, made from host probabilities, and are not recorded."""
 
     def __init__(self, model, event2idx, idx2event, lead_sheets, primers, max_events=10000, skip_check=False, max_bars=None, temp=1.2, top_p=0.9,
-                 seed=0, n_u=None, persistent=True, redraw=True, scores=False, banned=None, guidance=None, keep=None):
-        self._load_jobs(model, event2idx, idx2event, lead_sheets, primers, max_events, skip_check, max_bars, temp, top_p, None, banned, guidance, keep)
+                 seed=0, n_u=None, persistent=True, redraw=True, scores=False, banned=None, guidance=None, keep=None, soft=None):
+        self._load_jobs(model, event2idx, idx2event, lead_sheets, primers, max_events, skip_check, max_bars, temp, top_p, None, banned, guidance, keep, soft)
         n, dev, V = self.n, self.dev, model.n_token
         # guidance: (guide_cond, guide_uncond, guide_scale) over the n streams (emo_hip.h), the followers behind every other stream.  The other
         # streams draw from the table the call without followers builds; a follower reads its leader's column, its own is never read
@@ -1186,9 +1229,9 @@ class AccompanimentLoop(GrammarLoop):
         self.pos = self.L0                     # host count of the engine position (every row advances one per step)
 
     def _load_jobs(self, model, event2idx, idx2event, lead_sheets, primers, max_events, skip_check, max_bars, temp, top_p, consumed, banned=None,
-                   guidance=None, keep=None):
+                   guidance=None, keep=None, soft=None):
         """n, model, dev, W and the draw parameters (job_controls: gen_loop.draw_controls of temp / top_p / banned, each one value for all streams
-        or one per stream, and of the guidance pairs, checked before anything is allocated; temp / top_p: the launch's scalars); the grammar tables, the packed lead sheets and, per stream, its _Stream and its token / segment
+        or one per stream, of `soft` (None, or a dict of draw_controls' bias / top_k / min_p) and of the guidance pairs, checked before anything is allocated; temp / top_p: the launch's scalars); the grammar tables, the packed lead sheets and, per stream, its _Stream and its token / segment
         rows, parameters and state on the device, state[CONSUMED] = `consumed` (None: the shortest prompt's length L0, the prefix a prefill
         takes); the running count.  keep (None, or per stream None / a per-bar list of None / ids: check_keep): the kept bars, packed beside
         the lead sheets (pack_keep -> self.keep_tables, None without any); _Stream has written a kept first bar, or run of first bars, into the
@@ -1197,7 +1240,8 @@ class AccompanimentLoop(GrammarLoop):
         assert n == len(primers) and n > 0
         _refuse(model, None)
         keep = self.keep = check_keep('generate_accompaniments', keep, lead_sheets, model.n_token, event2idx)
-        ctl = self.job_controls = draw_controls('generate_accompaniments', n, model.n_token, banned, temp, top_p, guidance)
+        ctl = self.job_controls = draw_controls('generate_accompaniments', n, model.n_token, banned, temp, top_p, guidance, event2idx=event2idx,
+                                                **(soft or {}))
         self.model, self.temp, self.top_p = model, ctl.temp, ctl.top_p
         self.max_events = int(max_events)
         self.W = int(max_dec_inp_len)                 # read at call time (tests lower it)
@@ -1337,7 +1381,7 @@ class AccompanimentLoop(GrammarLoop):
                 ctl = self.job_controls                      # the stream keeps its controls: the host loop's `inadmissibles` is its ban
                 out.append(_resume_windowed(self.model, event2idx, idx2event, s, max_events, skip_check, ctl.temp_at(i),
                                             list(ctl.bans[i]) if ctl.bans[i] else None,
-                                            lambda probs, rs=rs, p=ctl.top_p_at(i): nucleus(probs, p, rng=rs)))
+                                            lambda probs, rs=rs, p=ctl.top_p_at(i), **cut: nucleus(probs, p, rng=rs, **cut), **_soft_kw(ctl, i)))
             else:
                 out.append(_stream_result(st, [int(t) for t in seq[i, :ln]], 'stream %d used all %d uniforms of its table' % (i, self.U.shape[0]),
                                           'stream %d: token row or lead-sheet table too short' % i,
@@ -1383,12 +1427,12 @@ class AccompanimentQueue(AccompanimentLoop):
     queued (a k-step replay ends up to k - 1 launches past the drain)."""
 
     def __init__(self, model, event2idx, idx2event, lead_sheets, primers, slots, max_events=10000, skip_check=False, max_bars=None, temp=1.2,
-                 top_p=0.9, seed=0, n_u=None, persistent=True, redraw=True, scores=False, banned=None, keep=None):
+                 top_p=0.9, seed=0, n_u=None, persistent=True, redraw=True, scores=False, banned=None, keep=None, soft=None):
         slots = self.slots = int(slots)
         if slots < 1:
             raise ValueError('slots must be at least 1 (got %d)' % slots)
         # CONSUMED 1 is what an admission sets: the first token goes out with it
-        self._load_jobs(model, event2idx, idx2event, lead_sheets, primers, max_events, skip_check, max_bars, temp, top_p, 1, banned, None, keep)
+        self._load_jobs(model, event2idx, idx2event, lead_sheets, primers, max_events, skip_check, max_bars, temp, top_p, 1, banned, None, keep, soft)
         n, dev, V = self.n, self.dev, model.n_token
         if model.use_pe and model.pe.pe.shape[0] < self.W:
             raise EmoError('generate_accompaniments(slots=): the positional table has %d rows, fewer than the window of %d tokens'
@@ -1790,7 +1834,7 @@ class RebaseLoop(GrammarLoop):
 
 def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, max_events=10000, skip_check=False, max_bars=None, temp=1.2, top_p=0.9,
                             inadmissibles=None, seed=0, use_graph=True, best_of=1, window='host', best_by='forward', return_scores=False, slots=None,
-                            banned=None, rebase_keep=None, guidance=None, uncond=None, keep=None):
+                            banned=None, rebase_keep=None, guidance=None, uncond=None, keep=None, bias=None, top_k=None, min_p=None):
     """The throughput path of generate_conditional_batch: the same arguments (no per-stream samplers) and result per stream, every draw and
     the grammar of _Stream.offer on the device (emo_grammar_step), each token step = grammar launch + one engine step (the one-launch
     persistent step where the engine has one), k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS, default 16) and replayed until
@@ -1842,6 +1886,14 @@ def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, m
     holds an EmoError ("a bar longer than the window").  ValueError, before anything is allocated, unless len(primer) + 2 <= rebase_keep <=
     max_dec_inp_len - longest lead-sheet bar - 2, or when rebase_keep is given with another window.  best_of, best_by, return_scores, banned,
     per-stream temp / top_p and slots work as with window = 'device'.
+
+    bias / top_k / min_p: the soft controls of the device draw (emo_hip.h: tok_bias / top_k_of / min_p_of), each None, one value for all
+    inputs, or one per input.  bias: a dict {token id or event name: value} or a full-length array, added to the logits the draw reads (float32,
+    -inf a ban; event_bias / pitch_range_bias build one); top_k: keep at most k candidates of top-p's set; min_p: drop the candidates below
+    min_p times the best probability.  They follow an input through best_of, slots=, a guidance pair (the follower has its leader's), the
+    windowed phase on the device and the hand-over to the host finish; primers, injected bars and kept bars are fed as they are and the
+    recorded scores stay the model's own.  ValueError, before anything is allocated, for a wrong length, an id outside [0, V), an unknown
+    event name, a NaN or +inf bias value, a top_k that is no integer or a min_p that is NaN.
 
     banned: the device form of the host loops' `inadmissibles` (which stays refused here: its one index array for all streams is not what the
     launch reads).  None: no ban; one sequence of token ids: no lead sheet's stream ever DRAWS one of them; or one entry per lead sheet, each
@@ -1921,13 +1973,15 @@ def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, m
         if slots < 1:
             raise ValueError('slots must be at least 1 (got %d)' % slots)
     # checked per input, before a loop allocates anything; every candidate of an input inherits the input's controls
-    ctl = draw_controls('generate_accompaniments', n_in, model.n_token, banned, temp, top_p)
+    ctl = draw_controls('generate_accompaniments', n_in, model.n_token, banned, temp, top_p, bias=bias, top_k=top_k, min_p=min_p, event2idx=event2idx)
     if plan is not None:
         ctl = ctl.with_guidance(plan.scales)
     ctl = ctl.repeat(best_of)                                    # (leaders stay rows [0, n_in * best_of), candidate c of a follower behind them)
     t0 = time.time()
     kw = dict(max_events=max_events, skip_check=skip_check, max_bars=max_bars, temp=ctl.temp_arg, top_p=ctl.top_p_arg, seed=seed,
               banned=ctl.bans)
+    if ctl.soft_arg is not None:
+        kw['soft'] = ctl.soft_arg
     if plan is not None:
         kw['guidance'] = ctl.guide_arg
     if keep is not None:
@@ -2008,6 +2062,11 @@ def parse_args(argv=None):
                     help='never draw a Tempo event further than --tempo-tolerance from T (tempo_ban): with --device in the grammar launch, else '
                          'as the host loop\'s inadmissibles')
     ap.add_argument('--tempo-tolerance', dest='tempo_tolerance', type=int, default=None, metavar='N', help='--tempo: the distance allowed (default 20)')
+    ap.add_argument('--top-k', dest='top_k', type=int, default=None, metavar='K',
+                    help='draw from at most K candidates of the top-p set (the K most likely; <= 0: off): with --device in the grammar launch, '
+                         'else in the host sampler')
+    ap.add_argument('--min-p', dest='min_p', type=float, default=None, metavar='M',
+                    help='drop the candidates whose probability lies below M times the most likely token\'s (<= 0: off)')
     ap.add_argument('--variation-of', dest='variation_of', default=None, metavar='FILE',
                     help='--device: instead of the lead sheets of the output directory, take this generated piece (a *_full.txt this command wrote) '
                          'and draw the bars of --reroll again; every other bar is kept.  Written to <FILE stem>_reroll.txt in the output directory')
@@ -2020,6 +2079,8 @@ def parse_args(argv=None):
             ap.error('--variation-of needs --device')
         if args.window != 'host':
             ap.error('--variation-of keeps bars: not with --window %s (the kept-bar tables are read in the window alone)' % args.window)
+    if args.min_p is not None and args.min_p != args.min_p:
+        ap.error('--min-p takes a number, not NaN')
     if args.tempo_tolerance is not None and (args.tempo is None or args.tempo_tolerance < 0):
         ap.error('--tempo-tolerance goes with --tempo T and is at least 0')
     if args.tempo is not None and args.tempo_tolerance is None:
@@ -2103,17 +2164,17 @@ def main(argv=None):
             gen, _, picks, *sc = generate_accompaniments(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group],
                                                          max_bars=args.max_bars, temp=temp, top_p=top_p, seed=args.seed + j, best_of=args.best_of,
                                                          window=args.window, best_by=args.best_by, return_scores=want, slots=args.slots,
-                                                         banned=ban, rebase_keep=args.rebase_keep, guidance=args.guidance, keep=kept)
+                                                         banned=ban, rebase_keep=args.rebase_keep, guidance=args.guidance, keep=kept, top_k=args.top_k, min_p=args.min_p)
             for g, p in zip(group, picks):
                 print('[info] %s: candidate %d of %s' % (g[0], p['chosen'], ['%.4f' % x for x in p['nll_mean']]))
         elif args.device:
             gen, _, *sc = generate_accompaniments(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
                                                   temp=temp, top_p=top_p, seed=args.seed + j, window=args.window, return_scores=want, slots=args.slots,
-                                                  banned=ban, rebase_keep=args.rebase_keep, guidance=args.guidance, keep=kept)
+                                                  banned=ban, rebase_keep=args.rebase_keep, guidance=args.guidance, keep=kept, top_k=args.top_k, min_p=args.min_p)
         else:
             gen = generate_conditional_batch(model, event2idx, idx2event, [g[2] for g in group], [g[3] for g in group], max_bars=args.max_bars,
                                              temp=temp, top_p=top_p, seeds=list(range(i, i + len(group))),
-                                             inadmissibles=np.array(ban, np.int64) if ban else None)
+                                             inadmissibles=np.array(ban, np.int64) if ban else None, top_k=args.top_k, min_p=args.min_p)
         if want:
             score_pieces += scoring.draw_pieces([os.path.basename(g[0]) for g in group], gen, sc[0])
         for (out, key, _, _), ids in zip(group, gen):

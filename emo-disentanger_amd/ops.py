@@ -410,6 +410,12 @@ _GRAMMAR_STEP_LAYOUT = {
     'mask_of': lambda a, t: _is(t, _I32) and t.numel() == a.ld_u and int(t.min()) >= -1 and int(t.max()) < a.n_masks,
     'temp_of': lambda a, t: _is(t, _F32) and t.numel() == a.ld_u,
     'top_p_of': lambda a, t: _is(t, _F32) and t.numel() == a.ld_u,
+    # the optional soft controls, per stream like the four above: shared bias rows (n_biases of them, given in the same call; values finite or
+    # -inf, read back once like mask_of's), the row each stream draws under (-1: none), the rank cap and the floor
+    'tok_bias': lambda a, t: _is(t, _F32) and t.shape == (a.n_biases, a.n_token) and a.n_biases > 0 and not bool((torch.isnan(t) | (t == float('inf'))).any()),
+    'bias_of': lambda a, t: _is(t, _I32) and t.numel() == a.ld_u and int(t.min()) >= -1 and int(t.max()) < a.n_biases,
+    'top_k_of': lambda a, t: _is(t, _I32) and t.numel() == a.ld_u,
+    'min_p_of': lambda a, t: _is(t, _F32) and t.numel() == a.ld_u and not bool(torch.isnan(t).any()),
     # kinds ACC and TXL, classifier-free guidance: per row of the batch; what the three hold together is checked by _check_guidance once they are in
     'guide_cond': lambda a, t: _is(t, _I32) and t.numel() == a.n_rows,
     'guide_uncond': lambda a, t: _is(t, _I32) and t.numel() == a.n_rows,

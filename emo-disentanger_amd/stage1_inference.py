@@ -16,7 +16,7 @@ import torch
 from . import ops, sampling, scoring
 from ._lib import EmoError
 from .gen_loop import GrammarLoop, check_vocab, draw_controls
-from .inference import _EngineBase, check_pairs, guidance_plan, parse_reroll, uniform_table
+from .inference import _EngineBase, _cut_kw, check_pairs, guidance_plan, parse_reroll, uniform_table
 from .sampling import beat_position, event_name, nucleus  # noqa: F401  (`nucleus` is looked up at call time: tests wrap it)
 
 SHARP_NAMES = ('C', 'C#', 'D', 'D#', 'E', 'F', 'F#', 'G', 'G#', 'A', 'A#', 'B')     # pitch-class spelling of convert_key.py:14-15
@@ -222,7 +222,7 @@ def _draw(sheet, logits, pick, idx2event, keyed, key_rule, temp, top_p):
 
 
 def generate_plain_xl_batch(model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
-                            representation='functional', key_determine=None, samplers=None, seeds=None, keep=None):
+                            representation='functional', key_determine=None, samplers=None, seeds=None, keep=None, bias=None, top_k=None, min_p=None):
     """n generate_plain_xl runs in lock-step on ONE TXLMemory, NumPy grammar and sampling per stream.  max_bars, max_events, prompt_bars,
     representation and key_determine may be per-stream lists.  `samplers[i](probs)` defaults to nucleus(probs, p, rng=RandomState(seeds[i]))
     (p = 0.97 on the key draw, top_p otherwise, as generate_plain_xl with its default sampler).  The common primer prefix is one prefill; the
@@ -231,16 +231,22 @@ def generate_plain_xl_batch(model, event2idx, idx2event, primers, max_bars=160, 
     stuck) or, where that run raises, the exception instance (ValueError of the key rule, EmoError past max_gen_len).
     keep (None: every bar is drawn): one entry per primer, None or a per-bar list of None / token ids: the bars that are given, not drawn
     (_LeadSheet._open_bar is the rule; check_keep the refusals).  A kept run is fed one token per step behind the Bar that opened it, and the
-    next draw is made from the logits behind its last Bar.  This is the reference the device loops' keep= is held to."""
+    next draw is made from the logits behind its last Bar.  This is the reference the device loops' keep= is held to.
+    bias / top_k / min_p (gen_loop.draw_controls: None, one for all, or one per primer): the device draw's soft controls on the host.  Stream
+    i's probabilities are taken from float32 `logits + bias` (sampling.biased), the key draw included, and a stream with a cut calls its sampler
+    as samplers[i](probs, top_k=k, min_p=m) (sampling.nucleus applies sampling.soft_cut_count)."""
     n = len(primers)
     assert n > 0
     kw = _per_stream(n, max_bars=max_bars, max_events=max_events, prompt_bars=prompt_bars, representation=representation, key_determine=key_determine)
     keep = None if keep is None else check_keep('generate_plain_xl_batch', keep, n, model.vocab_size, idx2event, [k['prompt_bars'] for k in kw])
     if samplers is None:
         rss = [np.random.RandomState(seeds[i] if seeds is not None else i) for i in range(n)]
-        picks = [(lambda probs, p, rs=rs: nucleus(probs, p, rng=rs)) for rs in rss]
+        picks = [(lambda probs, p, rs=rs, **cut: nucleus(probs, p, rng=rs, **cut)) for rs in rss]
     else:
-        picks = [(lambda probs, p, f=f: f(probs)) for f in samplers]
+        picks = [(lambda probs, p, f=f, **cut: f(probs, **cut)) for f in samplers]
+    soft = draw_controls('generate_plain_xl_batch', n, model.vocab_size, bias=bias, top_k=top_k, min_p=min_p, event2idx=event2idx)
+    # (a stream without a cut keeps the sampler call it had)
+    picks = [(lambda probs, p, f=f, cut=_cut_kw(soft, i): f(probs, p, **cut)) for i, f in enumerate(picks)]
     sheets = [_LeadSheet(event2idx, primers[i], kw[i]['prompt_bars'], kw[i]['max_bars'], kw[i]['max_events'], keep[i] if keep else None)
               for i in range(n)]
     keyed = [k['representation'] in ('functional', 'key') for k in kw]
@@ -271,7 +277,7 @@ def generate_plain_xl_batch(model, event2idx, idx2event, primers, max_bars=160, 
                     if logits_np is None:
                         logits_np = logits.cpu().numpy()
                     try:
-                        took = _draw(s, logits_np[i], picks[i], idx2event, keyed[i], kw[i]['key_determine'] == 'rule', temp, top_p)
+                        took = _draw(s, sampling.biased(logits_np[i], soft.bias_at(i)), picks[i], idx2event, keyed[i], kw[i]['key_determine'] == 'rule', temp, top_p)
                     except ValueError as e:
                         results[i], live[i] = e, False
                         continue
@@ -495,10 +501,10 @@ class LeadSheetLoop(GrammarLoop):
     guided_kinds = (ops.GRAMMAR_TXL,)
 
     def __init__(self, model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
-                 representation='functional', key_determine=None, seed=0, step='chain', scores=False, banned=None, guidance=None, keep=None):
+                 representation='functional', key_determine=None, seed=0, step='chain', scores=False, banned=None, guidance=None, keep=None, soft=None):
         from .model.plain_transformer import TXLMemory
         self._check_step(model, len(primers), step)
-        plens = self._load_jobs(model, event2idx, idx2event, primers, temp, top_p, None, banned, guidance, keep, max_bars=max_bars,
+        plens = self._load_jobs(model, event2idx, idx2event, primers, temp, top_p, None, banned, guidance, keep, soft=soft, max_bars=max_bars,
                                 max_events=max_events, prompt_bars=prompt_bars, representation=representation, key_determine=key_determine)
         n, L0 = self.n, min(plens)
         self.mem = TXLMemory(model, n, model._max_gen_len)
@@ -531,7 +537,7 @@ class LeadSheetLoop(GrammarLoop):
             if why is not None:
                 raise EmoError("step='one_launch' (emo_decode_step[txl]) needs %s; use step='chain'" % why)
 
-    def _load_jobs(self, model, event2idx, idx2event, primers, temp, top_p, feed, banned=None, guidance=None, keep=None, **per_stream):
+    def _load_jobs(self, model, event2idx, idx2event, primers, temp, top_p, feed, banned=None, guidance=None, keep=None, soft=None, **per_stream):
         """n, model, dev and the draw parameters (job_controls: gen_loop.draw_controls of temp / top_p / banned, each one value for all streams
         or one per stream, and of the guidance pairs, checked before anything is allocated; temp / top_p: the launch's scalars); the jobs' tables (_job_tables) on the device as seq / params / state, state[FEED] = `feed`
         (None: the shortest primer's length, the prefix a prefill takes); the running count.  keep (None, or per stream None / a per-bar list of
@@ -541,7 +547,8 @@ class LeadSheetLoop(GrammarLoop):
         assert n > 0
         kw = _per_stream(n, **per_stream)
         keep = self.keep = None if keep is None else check_keep('generate_lead_sheets', keep, n, model.vocab_size, idx2event, [k.get('prompt_bars') for k in kw])
-        ctl = self.job_controls = draw_controls('generate_lead_sheets', n, model.vocab_size, banned, temp, top_p, guidance)
+        ctl = self.job_controls = draw_controls('generate_lead_sheets', n, model.vocab_size, banned, temp, top_p, guidance, event2idx=event2idx,
+                                                **(soft or {}))      # (soft: None, or a dict of draw_controls' bias / top_k / min_p)
         fol = ctl.followers()
         if fol != list(range(n - len(fol), n)):
             raise ValueError('%s: the followers of the guidance pairs come behind every other stream (got %r of %d)' % (type(self).__name__, fol, n))
@@ -683,14 +690,14 @@ class LeadSheetQueue(LeadSheetLoop):
     launches each finished job held a slot; launches: the launches run() queued (a k-step replay ends up to k - 1 launches past the drain)."""
 
     def __init__(self, model, event2idx, idx2event, primers, slots, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
-                 representation='functional', key_determine=None, seed=0, step='chain', scores=False, banned=None, keep=None):
+                 representation='functional', key_determine=None, seed=0, step='chain', scores=False, banned=None, keep=None, soft=None):
         from .model.plain_transformer import TXLMemory
         slots = self.slots = int(slots)
         if slots < 1:
             raise ValueError('slots must be at least 1 (got %d)' % slots)
         self._check_step(model, slots, step)
         # FEED 1 is what an admission sets: the first token goes out with it
-        self._load_jobs(model, event2idx, idx2event, primers, temp, top_p, 1, banned, None, keep, max_bars=max_bars, max_events=max_events,
+        self._load_jobs(model, event2idx, idx2event, primers, temp, top_p, 1, banned, None, keep, soft=soft, max_bars=max_bars, max_events=max_events,
                         prompt_bars=prompt_bars, representation=representation, key_determine=key_determine)
         n, dev = self.n, self.dev
         self.stepper = OneLaunchStep(model, slots) if step == 'one_launch' else None
@@ -726,7 +733,7 @@ class LeadSheetQueue(LeadSheetLoop):
 
 def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
                          representation='functional', key_determine=None, seed=0, use_graph=True, step='chain', best_of=1, best_by='forward',
-                         return_scores=False, slots=None, banned=None, guidance=None, uncond=None, keep=None):
+                         return_scores=False, slots=None, banned=None, guidance=None, uncond=None, keep=None, bias=None, top_k=None, min_p=None):
     """The throughput path of generate_plain_xl_batch: the same arguments and result shape, every draw and the grammar on the device
     (emo_grammar_step), each token step = grammar launch + decode_step, k steps captured once as a hipGraph (EMO_GEN_GRAPH_STEPS,
     default 16) and replayed until every stream has finished.  Draws come from a uniform table seeded with `seed` (like generate_streams),
@@ -754,6 +761,14 @@ def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max
     and no batch waits for its longest member; step='one_launch' then has to hold for S rows.  A job draws from its own column of the uniform
     table, so its ids do not depend on S or on the slot it ran in beyond what the model step's arithmetic does; they are not those of slots =
     None, whose streams share a prefill.  The results, best_of, best_by and return_scores are per job as they are per stream.
+
+    bias / top_k / min_p: the soft controls of the device draw (emo_hip.h: tok_bias / top_k_of / min_p_of), each None, one value for all
+    primers, or one per primer: bias a dict {token id or event name: value} or a full-length array, added to the logits the draw reads
+    (float32; -inf is a ban; inference.event_bias builds one, e.g. {'Bar_None': 4.0} for shorter bars); top_k keeps at most k candidates of
+    top-p's set; min_p drops the candidates below min_p times the best probability.  They hold for the key draw too (which keeps its own
+    1.1 / 0.97), follow a primer through best_of, slots= and a guidance pair, and leave the recorded scores the model's own.  ValueError,
+    before anything is allocated, for a wrong length, an id outside [0, V), an unknown event name, a NaN or +inf bias value, a top_k that is
+    no integer or a min_p that is NaN.
 
     banned: None (no ban), one sequence of token ids (no stream ever DRAWS one of them), or one entry per primer, each a sequence of ids or
     None.  The grammar launch reads a banned token's logit as -inf (emo_hip.h: tok_mask), the key draw included, so the ids are those of the
@@ -815,13 +830,16 @@ def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max
         if slots < 1:
             raise ValueError('slots must be at least 1 (got %d)' % slots)
     # checked per primer, before a loop allocates anything; every candidate of a primer inherits the primer's controls
-    ctl = draw_controls('generate_lead_sheets', n_in, model.vocab_size if banned is not None else None, banned, temp, top_p)
+    ctl = draw_controls('generate_lead_sheets', n_in, model.vocab_size if banned is not None or bias is not None else None, banned, temp, top_p,
+                        bias=bias, top_k=top_k, min_p=min_p, event2idx=event2idx)
     if plan is not None:
         ctl = ctl.with_guidance(plan.scales)
     ctl = ctl.repeat(best_of)                                    # (leaders stay rows [0, n_in * best_of), candidate c of a follower behind them)
     t0 = time.time()
     with scoring.eval_mode(model):
         opts.update(temp=ctl.temp_arg, top_p=ctl.top_p_arg, banned=ctl.bans, seed=seed, step=step, scores=want)
+        if ctl.soft_arg is not None:
+            opts['soft'] = ctl.soft_arg
         if plan is not None:
             opts['guidance'] = ctl.guide_arg
         if keep is not None:
@@ -947,7 +965,13 @@ def parse_args(argv=None):
                     help='instead of new pieces, take this lead sheet (a samp_XX_<emotion> file this command wrote) and draw the bars of --reroll '
                          'again; every other bar is kept.  Written to <FILE stem>_reroll.txt in the output directory (device loop only)')
     ap.add_argument('--reroll', default=None, metavar='A:B[,C:D...]', help='--variation-of: 0-based, half-open ranges of bars to draw again')
+    ap.add_argument('--top-k', dest='top_k', type=int, default=None, metavar='K',
+                    help='draw from at most K candidates of the top-p set (the K most likely; <= 0: off), the key draw included')
+    ap.add_argument('--min-p', dest='min_p', type=float, default=None, metavar='M',
+                    help='drop the candidates whose probability lies below M times the most likely token\'s (<= 0: off)')
     args = ap.parse_args(argv)
+    if args.min_p is not None and args.min_p != args.min_p:
+        ap.error('--min-p takes a number, not NaN')
     if (args.variation_of is None) != (args.reroll is None):
         ap.error('--variation-of FILE and --reroll A:B[,C:D...] go together')
     if args.variation_of is not None and args.exact:
@@ -1027,6 +1051,7 @@ def main(argv=None):
     kw = dict(max_bars=max_bars, max_events=mode['max_events'], temp=mode['temp'], top_p=mode['top_p'], representation=args.representation,
               key_determine=key_determine)
     dev_kw = dict(banned=key_ban(event2idx, args.key)) if args.key is not None else {}
+    soft_kw = dict(top_k=args.top_k, min_p=args.min_p)
     if args.guidance:
         dev_kw.update(guidance=args.guidance, uncond=args.uncond)
     times, score_pieces = [], []
@@ -1043,15 +1068,15 @@ def main(argv=None):
             dev_kw.update(keep=[keep_of[out] for out, _ in group])
             kw.update(max_bars=[bars_in[out] for out, _ in group], prompt_bars=0)
         if args.exact:
-            res, sec = generate_plain_xl_batch(model, event2idx, idx2event, primers, seeds=list(range(i, i + len(group))), **kw)
+            res, sec = generate_plain_xl_batch(model, event2idx, idx2event, primers, seeds=list(range(i, i + len(group))), **kw, **soft_kw)
         elif args.best_of > 1:
             res, sec, picks, *sc = generate_lead_sheets(model, event2idx, idx2event, primers, seed=args.seed + j, step=args.step.replace('-', '_'),
-                                                        best_of=args.best_of, best_by=args.best_by, return_scores=want, slots=args.slots, **kw, **dev_kw)
+                                                        best_of=args.best_of, best_by=args.best_by, return_scores=want, slots=args.slots, **kw, **dev_kw, **soft_kw)
             for (out, _), p in zip(group, picks):
                 print('[info] %s: candidate %d of %d (nll_mean %s)' % (out, p['chosen'], args.best_of, ' '.join('%.4f' % x for x in p['nll_mean'])))
         else:
             res, sec, *sc = generate_lead_sheets(model, event2idx, idx2event, primers, seed=args.seed + j, step=args.step.replace('-', '_'),
-                                                 return_scores=want, slots=args.slots, **kw, **dev_kw)
+                                                 return_scores=want, slots=args.slots, **kw, **dev_kw, **soft_kw)
         times.append(sec)
         if want:
             score_pieces += scoring.draw_pieces([os.path.basename(out) for out, _ in group], res, sc[0])

@@ -695,6 +695,29 @@ typedef struct {
     const int32_t* rows;       /* ACC_WINDOW: int32 [n_rows] or NULL */
     int64_t* win_tok;          /* ACC_WINDOW: int64 [n_rows, window] */
     int64_t* win_seg;          /* ACC_WINDOW: int64 [n_rows, window] */
+    /* --- all kinds (TXL, ACC, ACC_WINDOW, TXL_QUEUE, ACC_QUEUE read all five fields), optional SOFT sampling controls, per stream and indexed
+     * like tok_mask / temp_of / top_p_of below (they stand in front of the queue kinds' fields: the tail of the block stays as it is);
+     * NULL: absent; with these and those four all NULL the launch is exactly the one without them.  Like the ban they
+     * reach the DRAW alone: primer tokens, injected lead-sheet bars, kept bars and track_full are fed as they are, and tok_logp / tok_rank /
+     * tok_entropy (and the host's logp_uncond) stay the model's own, from the unbiased row at temperature 1.
+     * BIAS: the draw of stream r reads the logit of token c as l(c) + tok_bias[bias_of[r], c]: ONE rounded fp32 add, never contracted, so
+     * the id, every state word, seq and segs are bit for bit those of the launch without a bias on a logits row that NumPy's float32 `l + b`
+     * wrote.  Under guidance the bias is added AFTER the three-operation combination, with the LEADER's bias row for both rows of a pair;
+     * the ban is applied last.  (Kind TXL takes every control of a guided draw from the leader's row; kind ACC takes the bias row from
+     * the leader and the ban, temp, top_p, top_k and min_p from the row itself.  The host refuses a pair whose rows differ, so the two
+     * rules give the same draw.)  Values are finite or -INFINITY (-inf behaves as a ban); +inf and NaN are refused by the host.
+     * CUTS: with `last` the candidate count top-p gives (second crossing; single crossing: all; no crossing: top 3), the draw keeps
+     * min(last, k, n_m) candidates of the ranking (probability descending, ties by ascending index: a tie group that straddles k keeps its
+     * lowest indices): k = top_k_of[r], k <= 0 off, k = 1 greedy under that tie rule, k >= n_token no cut; n_m = max(1, #{i : sp[i] >= m *
+     * sp[0]}) over the sorted fp32 probabilities, m = min_p_of[r], the product one rounded fp32 multiply, m <= 0 off, m > 1 leaves the best
+     * token alone.  The f64 renormalisation and the draw run over the final count, and so do the in-launch redraws of ACC / ACC_WINDOW.
+     * The TXL key draw keeps key_temperature / key_top_p and runs under the bias and both cuts, as it runs under the ban. */
+    const float* tok_bias;     /* f32 [n_biases, n_token] or NULL: shared bias rows; needs bias_of and n_biases > 0 */
+    int64_t n_biases;          /* rows of tok_bias */
+    const int32_t* bias_of;    /* int32 [streams] or NULL: the row of tok_bias each stream draws under; a value outside [0, n_biases) = no bias: the
+                                * kernel never reads outside the table (ops.block_set refuses a value outside [-1, n_biases)).  Without tok_bias it is not read */
+    const int32_t* top_k_of;   /* int32 [streams] or NULL: the rank cap k per stream; <= 0 = off */
+    const float* min_p_of;     /* f32 [streams] or NULL: the floor m relative to the best probability per stream; <= 0 = off */
     /* (the queue kinds alone, TXL_QUEUE and ACC_QUEUE; the last of the kind-specific fields: the optional outputs below stay the tail of the block) */
     int32_t* slot_job;         /* queue kinds: int32 [n_rows]: the job of each slot, -1 = free */
     int32_t* queue_head;       /* queue kinds: int32 [1]: the next job to hand out */
