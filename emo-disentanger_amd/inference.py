@@ -20,7 +20,8 @@ import torch
 
 from . import engine, ops, sampling, scoring
 from ._lib import EmoError
-from .gen_loop import GrammarLoop, check_vocab, draw_controls
+from .gen_loop import GrammarLoop, QueueLoop, check_kept_bars, check_vocab, draw_controls, finish_generation, plan_generation
+from .gen_loop import GuidancePlan, check_pairs, guidance_plan, uniform_table  # noqa: F401  (they live there and stay importable from here)
 from .replay import StepReplayer, graph_steps
 
 max_dec_inp_len = 2048
@@ -28,13 +29,6 @@ max_dec_inp_len = 2048
 
 # ------------------------------------------------------------------------------------------------ sampling
 from .sampling import beat_position, event_name, nucleus, temperature  # noqa: E402,F401  (host path with the reference's NumPy semantics)
-
-
-def uniform_table(rows, n, seed, device):
-    """fp32 [rows, n] uniforms of a device generator seeded with `seed`: the draws of the device loops (row = draw number, column = stream)."""
-    gen = torch.Generator(device=device)
-    gen.manual_seed(seed)
-    return torch.rand(rows, n, device=device, generator=gen)
 
 
 def sample_on_device(logits, temp, top_p, u=None, greedy=False):
@@ -963,35 +957,18 @@ def check_keep(who, keep, lead_sheets, V, event2idx):
     PAD_None (the marks the grammar itself writes around a bar)."""
     if keep is None:
         return None
-    keep = list(keep)
-    if len(keep) != len(lead_sheets):
-        raise ValueError('%s: keep has %d entries for %d inputs' % (who, len(keep), len(lead_sheets)))
+    keep = [None if bars is None else list(bars) for bars in keep]
+    for i, (bars, lead) in enumerate(zip(keep, lead_sheets)):
+        if bars is not None and len(bars) > len(lead):
+            raise ValueError('%s: keep[%d] has %d bars, its lead sheet %d' % (who, i, len(bars), len(lead)))
     marks = {event2idx[e]: e for e in ('Track_LeadSheet', 'Track_Full', 'EOS_None', 'PAD_None') if e in event2idx}
-    out = []
-    for i, bars in enumerate(keep):
-        if bars is None:
-            out.append(None)
-            continue
-        bars = list(bars)
-        if len(bars) > len(lead_sheets[i]):
-            raise ValueError('%s: keep[%d] has %d bars, its lead sheet %d' % (who, i, len(bars), len(lead_sheets[i])))
-        row = []
-        for j, bar in enumerate(bars):
-            if bar is None:
-                row.append(None)
-                continue
-            try:
-                ids = [int(t) for t in bar]
-            except TypeError:
-                raise ValueError('%s: keep[%d][%d] is neither None nor a sequence of token ids' % (who, i, j))
-            for t in ids:
-                if not 0 <= t < V:
-                    raise ValueError('%s: keep[%d][%d] holds token id %d outside [0, %d)' % (who, i, j, t, V))
-                if t in marks:
-                    raise ValueError('%s: keep[%d][%d] holds %s, which the grammar writes itself around a bar' % (who, i, j, marks[t]))
-            row.append(ids)
-        out.append(row)
-    return out if any(b is not None for row in out if row is not None for b in row) else None
+
+    def refuse(i, j, ids):
+        for t in ids:
+            if t in marks:
+                raise ValueError('%s: keep[%d][%d] holds %s, which the grammar writes itself around a bar' % (who, i, j, marks[t]))
+
+    return check_kept_bars(who, keep, len(lead_sheets), V, 'inputs', refuse)
 
 
 def pack_keep(keep, lead_sheets):
@@ -1084,93 +1061,6 @@ def tempo_ban(event2idx, tempo, tolerance=20):
     return sorted(i for e, i in event2idx.items() if 'Tempo' in e and 'Conti' not in e and abs(int(e.rsplit('_', 1)[-1]) - tempo) > tolerance)
 
 
-class GuidancePlan:
-    """What generate_accompaniments(guidance=, uncond=) comes to for n inputs: scales (one float per input, 0.0 = unguided), guided (the inputs
-    with a follower, in order: follower j runs behind the leaders as stream n + j), emo_pos (per input, the place of its emotion token in the
-    primer; None where it is unguided), followers (per guided input, its primer with the unconditioned id in that place)."""
-
-    def __init__(self, scales, guided, emo_pos, followers):
-        self.scales, self.guided, self.emo_pos, self.followers = scales, guided, emo_pos, followers
-
-    def rows(self, lead_sheets, primers):
-        """The inputs followed by the followers: a follower takes its leader's lead sheet."""
-        return list(lead_sheets) + [lead_sheets[i] for i in self.guided], list(primers) + self.followers
-
-
-def guidance_plan(who, guidance, uncond, event2idx, idx2event, primers):
-    """guidance (None, one scale >= 0, or one per input with None / 0 for an unguided one) and uncond (the unconditioned token id; None:
-    event2idx['Emotion_None']) of n primers, checked before anything is allocated -> GuidancePlan, or None when no input is guided.  The
-    emotion token of a primer is its first token whose event name starts with 'Emotion_'.  ValueError for a scale that is negative or not
-    finite, a per-input list of the wrong length, a vocabulary without Emotion_None where no uncond was given, a guided primer without an
-    emotion token."""
-    n = len(primers)
-    if guidance is None:
-        return None
-    if isinstance(guidance, numbers.Real) and not isinstance(guidance, bool):
-        scales = [float(guidance)] * n
-    else:
-        try:
-            scales = [0.0 if g is None else float(g) for g in guidance]
-        except (TypeError, ValueError):
-            raise ValueError('%s: guidance must be None, a scale or one scale (or None) per input (got %r)' % (who, guidance))
-        if len(scales) != n:
-            raise ValueError('%s: guidance has %d entries for %d inputs' % (who, len(scales), n))
-    for s in scales:
-        if not (s >= 0 and s != float('inf')):
-            raise ValueError('%s: guidance must be a finite scale >= 0 (got %r)' % (who, s))
-    guided = [i for i in range(n) if scales[i] > 0]
-    if not guided:
-        return None
-    if uncond is None:
-        if 'Emotion_None' not in event2idx:
-            raise ValueError('%s: guidance needs the unconditioned token: the vocabulary has no Emotion_None and no `uncond` was given' % who)
-        uncond = event2idx['Emotion_None']
-    uncond = int(uncond)
-    emo_pos, followers = [None] * n, []
-    for i in guided:
-        at = [k for k, t in enumerate(primers[i]) if (event_name(idx2event, int(t)) or '').startswith('Emotion_')]
-        if not at:
-            raise ValueError('%s: guidance: primer %d has no Emotion_* token to replace' % (who, i))
-        emo_pos[i] = at[0]
-        followers.append([uncond if k == at[0] else int(t) for k, t in enumerate(primers[i])])
-    return GuidancePlan(scales, guided, emo_pos, followers)
-
-
-def check_pairs(results, statuses, scores, controls, emo_pos, who='generate_accompaniments'):
-    """The pair invariant of a guided run, per follower g of `controls` (DrawControls over the rows of `results`) and its leader c: the same
-    status word, both results or both errors, the same length and the same ids except at emo_pos[c] (a result that is no id list, stage 1's
-    None of a stuck stream, is told by its status word alone).  A pair that broke it leaves an EmoError
-    in the LEADER's slot (its scores: None).  Where `scores` is given, a sound pair's leader gets 'logp_uncond': the follower's recorded logp,
-    the unconditioned model's figure for the leader's tokens.  -> (results, scores) without the followers' rows."""
-    out, sc = list(results), None if scores is None else list(scores)
-    fol = controls.followers()
-    for g in fol:
-        c = controls.guide_cond[g]
-        a, b = out[c], out[g]
-        bad = None
-        if statuses[c] != statuses[g]:
-            bad = 'status %d against %d' % (statuses[c], statuses[g])
-        elif isinstance(a, Exception) != isinstance(b, Exception):
-            bad = 'one row failed alone'
-        elif (a is None) != (b is None):
-            bad = 'one row got stuck alone'
-        elif a is not None and not isinstance(a, Exception):
-            if len(a) != len(b):
-                bad = '%d against %d tokens' % (len(a), len(b))
-            else:
-                diff = [k for k, (x, y) in enumerate(zip(a, b)) if x != y and k != emo_pos[c]]
-                if diff:
-                    bad = 'the ids part at token %d' % diff[0]
-        if bad:
-            out[c] = EmoError('%s: stream %d and its unconditioned follower %d left lock-step: %s' % (who, c, g, bad))
-            if sc is not None:
-                sc[c] = None
-        elif sc is not None and sc[c] is not None and sc[g] is not None:
-            sc[c] = dict(sc[c], logp_uncond=sc[g]['logp'])
-    keep = [r for r in range(len(out)) if r not in set(fol)]
-    return [out[r] for r in keep], None if sc is None else [sc[r] for r in keep]
-
-
 def _refuse(model, inadmissibles):
     if inadmissibles is not None:
         raise ValueError('generate_accompaniments: `inadmissibles` is not supported by the device grammar')
@@ -1204,15 +1094,8 @@ class AccompanimentLoop(GrammarLoop):
                  seed=0, n_u=None, persistent=True, redraw=True, scores=False, banned=None, guidance=None, keep=None, soft=None):
         self._load_jobs(model, event2idx, idx2event, lead_sheets, primers, max_events, skip_check, max_bars, temp, top_p, None, banned, guidance, keep, soft)
         n, dev, V = self.n, self.dev, model.n_token
-        # guidance: (guide_cond, guide_uncond, guide_scale) over the n streams (emo_hip.h), the followers behind every other stream.  The other
-        # streams draw from the table the call without followers builds; a follower reads its leader's column, its own is never read
-        fol = self.job_controls.followers()
-        n_lead = n - len(fol)
-        if fol != list(range(n_lead, n)):
-            raise ValueError('AccompanimentLoop: the followers of the guidance pairs come behind every other stream (got %r of %d)' % (fol, n))
-        self.U = uniform_table(int(n_u or 4 * self.W), n_lead, seed, dev)
-        if fol:
-            self.U = torch.cat([self.U, torch.zeros(self.U.shape[0], len(fol), dtype=torch.float32, device=dev)], dim=1).contiguous()
+        # guidance: (guide_cond, guide_uncond, guide_scale) over the n streams (emo_hip.h), the followers behind every other stream
+        self.U = self._uniforms(int(n_u or 4 * self.W), seed)
         self.tok = torch.zeros(n, dtype=torch.int64, device=dev)
         self.segv = torch.ones(n, dtype=torch.int64, device=dev)
         self.logits = torch.empty(n, V, dtype=torch.float32, device=dev)
@@ -1231,8 +1114,9 @@ class AccompanimentLoop(GrammarLoop):
     def _load_jobs(self, model, event2idx, idx2event, lead_sheets, primers, max_events, skip_check, max_bars, temp, top_p, consumed, banned=None,
                    guidance=None, keep=None, soft=None):
         """n, model, dev, W and the draw parameters (job_controls: gen_loop.draw_controls of temp / top_p / banned, each one value for all streams
-        or one per stream, of `soft` (None, or a dict of draw_controls' bias / top_k / min_p) and of the guidance pairs, checked before anything is allocated; temp / top_p: the launch's scalars); the grammar tables, the packed lead sheets and, per stream, its _Stream and its token / segment
-        rows, parameters and state on the device, state[CONSUMED] = `consumed` (None: the shortest prompt's length L0, the prefix a prefill
+        or one per stream, of `soft` (None, or a dict of draw_controls' bias / top_k / min_p) and of the guidance pairs, checked before anything is
+        allocated; temp / top_p: the launch's scalars); the grammar tables, the packed lead sheets and, per stream, its _Stream and its token /
+        segment rows, parameters and state on the device, state[CONSUMED] = `consumed` (None: the shortest prompt's length L0, the prefix a prefill
         takes); the running count.  keep (None, or per stream None / a per-bar list of None / ids: check_keep): the kept bars, packed beside
         the lead sheets (pack_keep -> self.keep_tables, None without any); _Stream has written a kept first bar, or run of first bars, into the
         row already, and a stream whose bars are all kept is DONE at load."""
@@ -1413,7 +1297,7 @@ class AccompanimentLoop(GrammarLoop):
         return out
 
 
-class AccompanimentQueue(AccompanimentLoop):
+class AccompanimentQueue(QueueLoop, AccompanimentLoop):
     """AccompanimentLoop for more jobs than rows: `slots` rows of the model batch (one decode engine of that many rows) work through
     len(lead_sheets) queued jobs.  one_step() = emo_grammar_step (kind ACC_QUEUE) + the restart of the admitted rows' FAVOR+ state (Performer
     only: emo_favor_state_reset on the launch's row_reset flags; a GPT-2 row restarts by being fed position 0) + the engine step: a slot whose
@@ -1428,36 +1312,29 @@ class AccompanimentQueue(AccompanimentLoop):
 
     def __init__(self, model, event2idx, idx2event, lead_sheets, primers, slots, max_events=10000, skip_check=False, max_bars=None, temp=1.2,
                  top_p=0.9, seed=0, n_u=None, persistent=True, redraw=True, scores=False, banned=None, keep=None, soft=None):
-        slots = self.slots = int(slots)
-        if slots < 1:
-            raise ValueError('slots must be at least 1 (got %d)' % slots)
+        slots = self._check_slots(slots)
         # CONSUMED 1 is what an admission sets: the first token goes out with it
         self._load_jobs(model, event2idx, idx2event, lead_sheets, primers, max_events, skip_check, max_bars, temp, top_p, 1, banned, None, keep, soft)
-        n, dev, V = self.n, self.dev, model.n_token
+        dev, V = self.dev, model.n_token
         if model.use_pe and model.pe.pe.shape[0] < self.W:
             raise EmoError('generate_accompaniments(slots=): the positional table has %d rows, fewer than the window of %d tokens'
                            % (model.pe.pe.shape[0], self.W))
         self.bound = self.W
-        self.U = uniform_table(int(n_u or 4 * self.W), n, seed, dev)
+        self.U = self._uniforms(int(n_u or 4 * self.W), seed)
         self.tok = torch.full((slots,), self.pad, dtype=torch.int64, device=dev)
         self.segv = torch.ones(slots, dtype=torch.int64, device=dev)
         self.logits = torch.zeros(slots, V, dtype=torch.float32, device=dev)
-        self.slot_job = torch.full((slots,), -1, dtype=torch.int32, device=dev)
-        self.queue_head = torch.zeros(1, dtype=torch.int32, device=dev)
         self.row_reset = torch.zeros(slots, dtype=torch.int32, device=dev)
-        self.job_steps_dev = torch.zeros(n, dtype=torch.int32, device=dev)
         self.windowed = None
         with torch.no_grad():
             eng = self.eng = self._make_engine(slots, persistent, redraw)
             eng.pos_dev.zero_()
             eng.dev_pos0, eng.pos_auto = 0, False                # position = pos_dev[b], written by the grammar launch
             self.state_table = eng.start_empty() if model.kind == 'performer' else None
-        self._build_block(ops.GRAMMAR_ACC_QUEUE, scores, self.job_controls, n_jobs=n, mem_rows=self.bound, slot_job=self.slot_job, queue_head=self.queue_head,
-                          mem_lens=eng.pos_dev, row_reset=self.row_reset, job_steps=self.job_steps_dev, **self._block_fields(slots))
-        # no job is fed more tokens than the window holds, so the queue is drained before this many launches whatever the slots do: a budget
-        # for the replayer, not a limit that is meant to bind (the per-job limit is the kernel's WINDOW)
-        self.budget = n * self.W + 2
-        self.launches = self.pos = 0
+        # (no job is fed more tokens than the window holds: the per-job limit is the kernel's WINDOW)
+        self._build_block(ops.GRAMMAR_ACC_QUEUE, scores, self.job_controls, mem_lens=eng.pos_dev, row_reset=self.row_reset,
+                          **self._queue_fields(self.bound), **self._block_fields(slots))
+        self.pos = 0
 
     def model_step(self):
         """What follows the grammar launch: the restart of the rows it flagged (Performer), then the engine step on the tokens, segments and
@@ -1471,19 +1348,11 @@ class AccompanimentQueue(AccompanimentLoop):
         self.model_step()
 
     def run(self, use_graph=True, steps_per_graph=None):
-        """Launches until the running count is 0; it is read once per replay (per step without graphs)."""
-        with torch.no_grad():
-            self.launches = self.pos = self._replay(self.launches, self.budget, use_graph, steps_per_graph)
-            torch.cuda.synchronize()
-            if self._live() > 0:
-                raise EmoError('AccompanimentQueue: %d jobs still running after %d launches' % (self._live(), self.launches))
+        self._drain(use_graph, steps_per_graph)
+        self.pos = self.launches
 
     def steps(self):
         return self.launches
-
-    def job_steps(self):
-        """-> per job, the launches it held a slot (0 for a job that was closed before the run)."""
-        return [int(x) for x in self.job_steps_dev.cpu().tolist()]
 
 
 WINDOW_TAG = 0x57494E                  # the windowed phase's uniform table is seeded with (seed, this tag): never the in-window table's seed
@@ -1946,51 +1815,24 @@ def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, m
         if getattr(model, 'use_pe', False) and model.pe.pe.shape[0] < int(max_dec_inp_len):       # (RebaseLoop's refusal, before the first loop runs)
             raise EmoError("generate_accompaniments(window='rebase'): the positional table has %d rows, fewer than the window of %d tokens"
                            % (model.pe.pe.shape[0], int(max_dec_inp_len)))
-    n_in = len(lead_sheets)
     keep = check_keep('generate_accompaniments', keep, lead_sheets, model.n_token, event2idx)
     if keep is not None and window != 'host':
         raise ValueError("generate_accompaniments: keep is not available with window=%r: %s; use window='host'"
                          % (window, 'the windowed launch does not read the kept-bar tables' if window == 'device' else
                             'a re-anchored row drops bars and the kept-bar tables are indexed by the bar'))
-    plan = guidance_plan('generate_accompaniments', guidance, uncond, event2idx, idx2event, primers)
-    if plan is not None:
-        if slots is not None:
-            raise ValueError('generate_accompaniments: guidance runs in the lock-step batch: slots= is not available with it (queue slots are not lock-step)')
-        if window == 'device':
-            raise ValueError("generate_accompaniments: guidance is not available with window='device' (the windowed launch compacts the batch rows): use window='rebase'")
-        lead_sheets, primers = plan.rows(lead_sheets, primers)           # the followers behind the inputs
-        if keep is not None:
-            keep = keep + [keep[i] for i in plan.guided]                 # a follower keeps what its leader keeps: the pair stays in lock-step
-    best_of, by_draws, want, lead_sheets, primers, keep = scoring.best_of_plan(best_of, best_by, return_scores, lead_sheets, primers,
-                                                                               keep if keep is not None else [None] * len(lead_sheets))
-    if all(k is None for k in keep):
-        keep = None
-    if slots is not None:
-        try:
-            slots = int(slots)
-        except (TypeError, ValueError):
-            raise ValueError('slots must be None or a count of at least 1 (got %r)' % (slots,))
-        if slots < 1:
-            raise ValueError('slots must be at least 1 (got %d)' % slots)
-    # checked per input, before a loop allocates anything; every candidate of an input inherits the input's controls
-    ctl = draw_controls('generate_accompaniments', n_in, model.n_token, banned, temp, top_p, bias=bias, top_k=top_k, min_p=min_p, event2idx=event2idx)
-    if plan is not None:
-        ctl = ctl.with_guidance(plan.scales)
-    ctl = ctl.repeat(best_of)                                    # (leaders stay rows [0, n_in * best_of), candidate c of a follower behind them)
+    guide = guidance_plan('generate_accompaniments', guidance, uncond, event2idx, idx2event, primers)
+    if guide is not None and window == 'device':
+        raise ValueError("generate_accompaniments: guidance is not available with window='device' (the windowed launch compacts the batch rows): use window='rebase'")
+    plan = plan_generation('generate_accompaniments', len(lead_sheets), model.n_token, event2idx, keep, guide, dict(lead_sheets=lead_sheets, primers=primers),
+                           best_of, best_by, return_scores, slots, banned, temp, top_p, bias, top_k, min_p)
     t0 = time.time()
-    kw = dict(max_events=max_events, skip_check=skip_check, max_bars=max_bars, temp=ctl.temp_arg, top_p=ctl.top_p_arg, seed=seed,
-              banned=ctl.bans)
-    if ctl.soft_arg is not None:
-        kw['soft'] = ctl.soft_arg
-    if plan is not None:
-        kw['guidance'] = ctl.guide_arg
-    if keep is not None:
-        kw['keep'] = keep
 
     def make(**more):
-        if slots is None:
-            return AccompanimentLoop(model, event2idx, idx2event, lead_sheets, primers, scores=want, **kw, **more)
-        return AccompanimentQueue(model, event2idx, idx2event, lead_sheets, primers, slots, scores=want, **kw, **more)
+        inputs, kw = plan.rows.values(), dict(plan.loop_kw, max_events=max_events, skip_check=skip_check, max_bars=max_bars, seed=seed,
+                                              scores=plan.want_scores, **more)
+        if plan.slots is None:
+            return AccompanimentLoop(model, event2idx, idx2event, *inputs, **kw)
+        return AccompanimentQueue(model, event2idx, idx2event, *inputs, plan.slots, **kw)
 
     with scoring.eval_mode(model):
         loop = make()
@@ -2001,14 +1843,8 @@ def generate_accompaniments(model, event2idx, idx2event, lead_sheets, primers, m
             loop = make(persistent=False, redraw=False)
             loop.run(use_graph=use_graph)
         out = loop.results(event2idx, idx2event, max_events, skip_check, seed, window=window, rebase_keep=rebase_keep, use_graph=use_graph)
-        sc = loop.scores(out) if want else None
-        if plan is not None:
-            out, sc = check_pairs(out, loop.statuses, sc, ctl, [p for p in plan.emo_pos for _ in range(best_of)])
-        picks = None
-        if best_of > 1:
-            nll = scoring.draw_scores_mean(sc) if by_draws else scoring.candidate_scores(model, event2idx, out, loop.bound)
-            picks = scoring.picks_of(out, nll, best_of, sc if return_scores else None)
-    return scoring.generation_result(out, time.time() - t0, sc, picks, return_scores)
+        return finish_generation(out, loop.scores(out) if plan.want_scores else None, loop.statuses if guide is not None else None, plan, guide,
+                                 lambda cands: scoring.candidate_scores(model, event2idx, cands, loop.bound), t0)
 
 
 # ------------------------------------------------------------------------------------------------ command line (reference inference.py:330-485)

@@ -15,8 +15,8 @@ import torch
 
 from . import ops, sampling, scoring
 from ._lib import EmoError
-from .gen_loop import GrammarLoop, check_vocab, draw_controls
-from .inference import _EngineBase, _cut_kw, check_pairs, guidance_plan, parse_reroll, uniform_table
+from .gen_loop import GrammarLoop, QueueLoop, check_kept_bars, check_vocab, draw_controls, finish_generation, guidance_plan, plan_generation
+from .inference import _EngineBase, _cut_kw, parse_reroll
 from .sampling import beat_position, event_name, nucleus  # noqa: F401  (`nucleus` is looked up at call time: tests wrap it)
 
 SHARP_NAMES = ('C', 'C#', 'D', 'D#', 'E', 'F', 'F#', 'G', 'G#', 'A', 'A#', 'B')     # pitch-class spelling of convert_key.py:14-15
@@ -310,39 +310,18 @@ def check_keep(who, keep, n, V, idx2event, prompt_bars=None):
     or one entry per primer: None, or a list indexed by bar number (None, or the bar's ids as ints).  prompt_bars: None, one count, or one per
     primer.  ValueError for a wrong outer length, an id outside [0, V), a kept bar that holds a Bar event ('Bar' in its name), PAD_None or
     EOS_None (the marks the grammar writes or rejects itself), a kept entry under the primer's prompt_bars (a primer's own bars are never kept)."""
-    if keep is None:
-        return None
-    keep = list(keep)
-    if len(keep) != n:
-        raise ValueError('%s: keep has %d entries for %d primers' % (who, len(keep), n))
     pb = list(prompt_bars) if isinstance(prompt_bars, (list, tuple)) else [prompt_bars] * n
-    if len(pb) != n:
+    if keep is not None and len(pb) != n:
         raise ValueError('%s: prompt_bars: %d values for %d primers' % (who, len(pb), n))
-    out = []
-    for i, bars in enumerate(keep):
-        if bars is None:
-            out.append(None)
-            continue
-        row = []
-        for j, bar in enumerate(list(bars)):
-            if bar is None:
-                row.append(None)
-                continue
-            try:
-                ids = [int(t) for t in bar]
-            except (TypeError, ValueError):
-                raise ValueError('%s: keep[%d][%d] is neither None nor a sequence of token ids' % (who, i, j))
-            if j < (pb[i] or 0):
-                raise ValueError('%s: keep[%d][%d] lies under prompt_bars = %d: a primer\'s own bars are never kept' % (who, i, j, pb[i]))
-            for t in ids:
-                if not 0 <= t < V:
-                    raise ValueError('%s: keep[%d][%d] holds token id %d outside [0, %d)' % (who, i, j, t, V))
-                e = event_name(idx2event, t)
-                if e is not None and ('Bar' in e or e in ('PAD_None', 'EOS_None')):
-                    raise ValueError('%s: keep[%d][%d] holds %s, which the grammar writes or rejects itself' % (who, i, j, e))
-            row.append(ids)
-        out.append(row)
-    return out if any(b is not None for row in out if row is not None for b in row) else None
+
+    def refuse(i, j, ids):
+        if j < (pb[i] or 0):
+            raise ValueError('%s: keep[%d][%d] lies under prompt_bars = %d: a primer\'s own bars are never kept' % (who, i, j, pb[i]))
+        for e in (event_name(idx2event, t) for t in ids):
+            if e is not None and ('Bar' in e or e in ('PAD_None', 'EOS_None')):
+                raise ValueError('%s: keep[%d][%d] holds %s, which the grammar writes or rejects itself' % (who, i, j, e))
+
+    return check_kept_bars(who, keep, n, V, 'primers', refuse)
 
 
 def pack_keep(keep, table_of=None):
@@ -509,11 +488,7 @@ class LeadSheetLoop(GrammarLoop):
         n, L0 = self.n, min(plens)
         self.mem = TXLMemory(model, n, model._max_gen_len)
         self.max_len, self.L0 = self.mem.max_len, L0
-        # the other streams draw from the table the call without followers builds; a follower reads its leader's column, its own is never read
-        n_lead = n - len(self.job_controls.followers())
-        self.U = uniform_table(self.max_len - L0 + 1, n_lead, seed, self.dev)      # at most one draw per step, one more at the end
-        if n_lead < n:
-            self.U = torch.cat([self.U, torch.zeros(self.U.shape[0], n - n_lead, dtype=torch.float32, device=self.dev)], dim=1).contiguous()
+        self.U = self._uniforms(self.max_len - L0 + 1, seed)         # at most one draw per step, one more at the end
         # (a valid id in every row before the first grammar step; a copy: with one stream the column is contiguous as it is, and tok_out must not be seq)
         self.tok = self.seq[:, L0 - 1].clone()
         self.logits = torch.empty(n, model.vocab_size, dtype=torch.float32, device=self.dev)
@@ -539,8 +514,9 @@ class LeadSheetLoop(GrammarLoop):
 
     def _load_jobs(self, model, event2idx, idx2event, primers, temp, top_p, feed, banned=None, guidance=None, keep=None, soft=None, **per_stream):
         """n, model, dev and the draw parameters (job_controls: gen_loop.draw_controls of temp / top_p / banned, each one value for all streams
-        or one per stream, and of the guidance pairs, checked before anything is allocated; temp / top_p: the launch's scalars); the jobs' tables (_job_tables) on the device as seq / params / state, state[FEED] = `feed`
-        (None: the shortest primer's length, the prefix a prefill takes); the running count.  keep (None, or per stream None / a per-bar list of
+        or one per stream, and of the guidance pairs, checked before anything is allocated; temp / top_p: the launch's scalars); the jobs' tables
+        (_job_tables) on the device as seq / params / state, state[FEED] = `feed` (None: the shortest primer's length, the prefix a prefill
+        takes); the running count.  keep (None, or per stream None / a per-bar list of
         None / ids: check_keep): the kept bars, packed (pack_keep -> self.keep_tables, None without any; a follower reads its leader's entries)
         with the per-stream count of kept tokens not yet fed, all 0.  -> the primer lengths."""
         n = self.n = len(primers)
@@ -549,9 +525,7 @@ class LeadSheetLoop(GrammarLoop):
         keep = self.keep = None if keep is None else check_keep('generate_lead_sheets', keep, n, model.vocab_size, idx2event, [k.get('prompt_bars') for k in kw])
         ctl = self.job_controls = draw_controls('generate_lead_sheets', n, model.vocab_size, banned, temp, top_p, guidance, event2idx=event2idx,
                                                 **(soft or {}))      # (soft: None, or a dict of draw_controls' bias / top_k / min_p)
-        fol = ctl.followers()
-        if fol != list(range(n - len(fol), n)):
-            raise ValueError('%s: the followers of the guidance pairs come behind every other stream (got %r of %d)' % (type(self).__name__, fol, n))
+        fol = list(range(self._lead_count(), n))                     # (the followers come behind every other stream)
         self.model, self.temp, self.top_p = model, ctl.temp, ctl.top_p
         self.dev = next(model.parameters()).device
         # the mode of a follower's own tag (0 for Emotion_None) would reject every key under the key rule: it has its leader's, the pair rejects together
@@ -680,7 +654,7 @@ def queue_plan(job_steps, slots):
     return launches, sum(steps) / float(launches * slots)
 
 
-class LeadSheetQueue(LeadSheetLoop):
+class LeadSheetQueue(QueueLoop, LeadSheetLoop):
     """LeadSheetLoop for more jobs than rows: `slots` rows of the model batch (one TXLMemory / OneLaunchStep of that many rows) work through
     len(primers) queued jobs.  one_step() = emo_grammar_step (kind TXL_QUEUE) + the model step: a slot whose job ends takes the next job inside
     the grammar launch and restarts its row of the memory (length 0), so the replayed graphs go on and the running count stays the only thing
@@ -692,43 +666,25 @@ class LeadSheetQueue(LeadSheetLoop):
     def __init__(self, model, event2idx, idx2event, primers, slots, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
                  representation='functional', key_determine=None, seed=0, step='chain', scores=False, banned=None, keep=None, soft=None):
         from .model.plain_transformer import TXLMemory
-        slots = self.slots = int(slots)
-        if slots < 1:
-            raise ValueError('slots must be at least 1 (got %d)' % slots)
+        slots = self._check_slots(slots)
         self._check_step(model, slots, step)
         # FEED 1 is what an admission sets: the first token goes out with it
         self._load_jobs(model, event2idx, idx2event, primers, temp, top_p, 1, banned, None, keep, soft=soft, max_bars=max_bars, max_events=max_events,
                         prompt_bars=prompt_bars, representation=representation, key_determine=key_determine)
-        n, dev = self.n, self.dev
         self.stepper = OneLaunchStep(model, slots) if step == 'one_launch' else None
         mem = self.mem = self.stepper.mem if self.stepper is not None else TXLMemory(model, slots, model._max_gen_len)
         self.max_len = mem.max_len
-        self.U = uniform_table(mem.max_len, n, seed, dev)            # a job draws at most once per token of its row
+        self.U = self._uniforms(mem.max_len, seed)                   # a job draws at most once per token of its row
         self.tok = self.seq[0, :1].repeat(slots).contiguous()        # (a valid id in every row: a slot that never gets a job feeds it)
-        self.logits = torch.zeros(slots, model.vocab_size, dtype=torch.float32, device=dev)
-        self.slot_job = torch.full((slots,), -1, dtype=torch.int32, device=dev)
-        self.queue_head = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.job_steps_dev = torch.zeros(n, dtype=torch.int32, device=dev)
-        self._build_block(ops.GRAMMAR_TXL_QUEUE, scores, self.job_controls, n_jobs=n, mem_rows=mem.max_len, slot_job=self.slot_job, queue_head=self.queue_head,
-                          mem_lens=mem.lens, job_steps=self.job_steps_dev, **self._block_fields(slots))
-        # no job can outlast its row of the memory, so the queue is drained before this many launches whatever the slots do: a budget for the
-        # replayer, not a limit that is meant to bind (the per-job limit is the kernel's MEM_FULL)
-        self.budget = n * mem.max_len + 2
-        self.launches = 0
+        self.logits = torch.zeros(slots, model.vocab_size, dtype=torch.float32, device=self.dev)
+        # (no job can outlast its row of the memory: the per-job limit is the kernel's MEM_FULL)
+        self._build_block(ops.GRAMMAR_TXL_QUEUE, scores, self.job_controls, mem_lens=mem.lens, **self._queue_fields(mem.max_len),
+                          **self._block_fields(slots))
 
     def run(self, use_graph=True, steps_per_graph=None):
-        """Launches until the running count is 0; it is read once per replay (per step without graphs)."""
-        with torch.no_grad():
-            self.launches = self._replay(self.launches, self.budget, use_graph, steps_per_graph)
-            torch.cuda.synchronize()
-            if self._live() > 0:
-                raise EmoError('LeadSheetQueue: %d jobs still running after %d launches' % (self._live(), self.launches))
+        self._drain(use_graph, steps_per_graph)
         if self.stepper is not None:
             self.stepper.check_persistent()                          # a launch that gave up must not pass for a result
-
-    def job_steps(self):
-        """-> per job, the launches it held a slot (0 for a job that was closed before the run)."""
-        return [int(x) for x in self.job_steps_dev.cpu().tolist()]
 
 
 def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max_events=2048, temp=1.2, top_p=0.9, prompt_bars=None,
@@ -808,59 +764,27 @@ def generate_lead_sheets(model, event2idx, idx2event, primers, max_bars=160, max
     (check_keep): a wrong outer length, an id outside [0, V), a kept bar that holds a Bar event, PAD_None or EOS_None, an entry under prompt_bars."""
     # a per-primer list among the arguments is repeated like the primers; a value given once holds for every stream
     opts = dict(max_bars=max_bars, max_events=max_events, prompt_bars=prompt_bars, representation=representation, key_determine=key_determine)
-    lists = [k for k, v in opts.items() if isinstance(v, (list, tuple)) and len(v) == len(primers)]
-    n_in = len(primers)
-    keep = None if keep is None else check_keep('generate_lead_sheets', keep, n_in, model.vocab_size, idx2event, prompt_bars)
-    plan = _lead_sheet_guidance(guidance, uncond, event2idx, idx2event, primers, model.vocab_size) if guidance is not None else None
-    if plan is not None:
-        if slots is not None:
-            raise ValueError('generate_lead_sheets: guidance runs in the lock-step batch: slots= is not available with it (queue slots are not lock-step)')
-        for k in lists:                                          # a follower has its leader's options ...
-            opts[k] = plan.rows(opts[k], primers)[0]
-        if keep is not None:
-            keep = keep + [keep[i] for i in plan.guided]         # ... and keeps what its leader keeps: the pair stays in lock-step
-        primers = plan.rows(primers, primers)[1]                 # ... and its leader's primer but for one token (the followers are id lists)
-    best_of, by_draws, want, primers, keep, *repeated = scoring.best_of_plan(best_of, best_by, return_scores, primers,
-                                                                             keep if keep is not None else [None] * len(primers), *(opts[k] for k in lists))
-    opts.update(zip(lists, repeated))
-    if all(k is None for k in keep):
-        keep = None
-    if slots is not None:
-        slots = int(slots)
-        if slots < 1:
-            raise ValueError('slots must be at least 1 (got %d)' % slots)
-    # checked per primer, before a loop allocates anything; every candidate of a primer inherits the primer's controls
-    ctl = draw_controls('generate_lead_sheets', n_in, model.vocab_size if banned is not None or bias is not None else None, banned, temp, top_p,
-                        bias=bias, top_k=top_k, min_p=min_p, event2idx=event2idx)
-    if plan is not None:
-        ctl = ctl.with_guidance(plan.scales)
-    ctl = ctl.repeat(best_of)                                    # (leaders stay rows [0, n_in * best_of), candidate c of a follower behind them)
+    lists = {k: v for k, v in opts.items() if isinstance(v, (list, tuple)) and len(v) == len(primers)}
+    keep = None if keep is None else check_keep('generate_lead_sheets', keep, len(primers), model.vocab_size, idx2event, prompt_bars)
+    guide = _lead_sheet_guidance(guidance, uncond, event2idx, idx2event, primers, model.vocab_size) if guidance is not None else None
+    plan = plan_generation('generate_lead_sheets', len(primers), model.vocab_size if banned is not None or bias is not None else None, event2idx,
+                           keep, guide, dict(lists, primers=primers), best_of, best_by, return_scores, slots, banned, temp, top_p, bias, top_k, min_p)
+    opts.update(plan.rows, **plan.loop_kw, seed=seed, step=step, scores=plan.want_scores)
+    primers = opts.pop('primers')                                # (the followers are id lists)
     t0 = time.time()
     with scoring.eval_mode(model):
-        opts.update(temp=ctl.temp_arg, top_p=ctl.top_p_arg, banned=ctl.bans, seed=seed, step=step, scores=want)
-        if ctl.soft_arg is not None:
-            opts['soft'] = ctl.soft_arg
-        if plan is not None:
-            opts['guidance'] = ctl.guide_arg
-        if keep is not None:
-            opts['keep'] = keep
-        loop = (LeadSheetLoop(model, event2idx, idx2event, primers, **opts) if slots is None else
-                LeadSheetQueue(model, event2idx, idx2event, primers, slots, **opts))
+        loop = (LeadSheetLoop(model, event2idx, idx2event, primers, **opts) if plan.slots is None else
+                LeadSheetQueue(model, event2idx, idx2event, primers, plan.slots, **opts))
         loop.run(use_graph=use_graph)
         out = loop.results()
-        sc = loop.scores() if want else None
-        if plan is not None:
-            out, sc = check_pairs(out, loop.state.cpu().numpy()[:, S_STATUS].tolist(), sc, ctl, [p for p in plan.emo_pos for _ in range(best_of)],
-                                  who='generate_lead_sheets')
-        picks = None
-        if best_of > 1:                                          # (the leaders are the first rows)
-            nll = scoring.draw_scores_mean(sc) if by_draws else scoring.lead_sheet_candidate_scores(model, out, loop.params.cpu().numpy()[:len(out), P_PRIMER_LEN].tolist())
-            picks = scoring.picks_of(out, nll, best_of, sc if return_scores else None)
-    return scoring.generation_result(out, time.time() - t0, sc, picks, return_scores)
+        return finish_generation(out, loop.scores() if plan.want_scores else None,
+                                 loop.state.cpu().numpy()[:, S_STATUS].tolist() if guide is not None else None, plan, guide,
+                                 lambda cands: scoring.lead_sheet_candidate_scores(model, cands, loop.params.cpu().numpy()[:len(cands), P_PRIMER_LEN].tolist()),
+                                 t0)
 
 
 def _lead_sheet_guidance(guidance, uncond, event2idx, idx2event, primers, V):
-    """inference.guidance_plan for generate_lead_sheets, whose primers are event names (None: the reference's default, a lone Bar_None) and
+    """gen_loop.guidance_plan for generate_lead_sheets, whose primers are event names (None: the reference's default, a lone Bar_None) and
     whose `uncond` may be one: -> its GuidancePlan over the primers' ids, or None when no piece is guided.  On top of its refusals, ValueError
     for an `uncond` that is no event of the vocabulary or lies outside [0, V)."""
     if isinstance(uncond, str):

@@ -1,5 +1,7 @@
 """CPU: the best-of tail that generate_lead_sheets and generate_accompaniments share (scoring.picks_of, generation_result, best_of_plan,
-eval_mode), on plain lists, and both generators on fake loop classes: the same flags give the same-shaped tuple."""
+eval_mode), on plain lists, and both generators on fake loop classes: the same flags give the same-shaped tuple.  And what gen_loop gives
+both generators around their loops: the request plan (plan_generation), the result tail (finish_generation) and the walk of the kept-bar
+check (check_kept_bars)."""
 from types import SimpleNamespace
 
 import numpy as np
@@ -124,3 +126,129 @@ def test_both_generators_return_the_same_shaped_tuple_for_the_same_flags(monkeyp
             assert len(got[-1]) == 3 and all(set(sc) == {'logp', 'rank', 'entropy'} for sc in got[-1])
             assert [float(sc['logp'][1]) for sc in got[-1]] == [-1.0 / (i * best_of + chosen + 1) for i in range(3)]
     assert [type(x) for x in one] == [type(x) for x in two]
+
+
+# ------------------------------------------------------------------------------------------------ the request plan and the result tail
+def _guided_plan(**kw):
+    """3 inputs, inputs 1 and 2 guided, on plain lists: per-input entries are tagged by the input they belong to."""
+    from emo_disentanger_amd import gen_loop
+    i2e = {0: 'Emotion_None', 1: 'Emotion_Q1'}
+    primers = [[1, 10], [1, 11], [1, 12]]
+    guide = gen_loop.guidance_plan('t', [None, 2.0, 0.5], None, {'Emotion_None': 0}, i2e, primers)
+    plan = gen_loop.plan_generation('t', 3, 40, None, kw.pop('keep', None), guide, dict(lead_sheets=['L0', 'L1', 'L2'], primers=primers,
+                                                                                        max_events=[10, 20, 30]), **kw)
+    return guide, plan
+
+
+def test_plan_generation_puts_followers_behind_the_leaders_and_repeats_in_candidate_order():
+    keep = [[[5]], None, [None, [6]]]
+    guide, plan = _guided_plan(keep=keep, best_of=2, temp=[1.0, 1.1, 1.2], banned=[None, [7], [8]])
+    order = [0, 0, 1, 1, 2, 2] + [1, 1, 2, 2]                        # leaders, candidate c of input i at i * 2 + c, then the followers alike
+    assert plan.rows['lead_sheets'] == ['L%d' % i for i in order] and plan.rows['max_events'] == [10 * (i + 1) for i in order]
+    assert plan.rows['primers'][:6] == [[1, 10 + i] for i in order[:6]]
+    assert plan.rows['primers'][6:] == [[0, 10 + i] for i in order[6:]]                          # a follower's own primer: the unconditioned token
+    assert plan.keep == [keep[i] for i in order] and plan.loop_kw['keep'] is plan.keep
+    assert list(plan.rows) == ['lead_sheets', 'primers', 'max_events']                           # the order the caller gave: it may pass them positionally
+    ctl = plan.controls
+    assert ctl.n == 10 and (plan.best_of, plan.by_draws, plan.want_scores, plan.slots) == (2, False, False, None)
+    for k in range(4):                                                                           # row n_in * 2 + k is paired with its leader
+        g, c = 6 + k, order[6 + k] * 2 + k % 2
+        assert ctl.guide_cond[g] == ctl.guide_cond[c] == c and ctl.guide_uncond[g] == ctl.guide_uncond[c] == g
+        assert ctl.guide_scale[g] == ctl.guide_scale[c] == [0.0, 2.0, 0.5][order[6 + k]]
+        assert (ctl.bans[g], ctl.temp_at(g)) == (ctl.bans[c], ctl.temp_at(c))
+    assert ctl.guide_cond[:2] == [-1, -1] and ctl.followers() == [6, 7, 8, 9]
+    assert plan.loop_kw['guidance'] == ctl.guide_arg and plan.loop_kw['temp'] == [[1.0, 1.1, 1.2][i] for i in order]
+    assert plan.loop_kw['banned'] == [[None, (7,), (8,)][i] for i in order]
+
+
+def test_plan_generation_leaves_unused_keywords_out_and_refuses_in_one_place():
+    from emo_disentanger_amd import gen_loop
+    rows = dict(primers=[[1], [2]])
+    plan = gen_loop.plan_generation('t', 2, 40, None, None, None, rows, slots='3')
+    assert set(plan.loop_kw) == {'temp', 'top_p', 'banned'} and plan.keep is None and plan.slots == 3
+    assert plan.loop_kw == dict(temp=1.2, top_p=0.9, banned=[None, None]) and plan.rows == rows
+    plan = gen_loop.plan_generation('t', 2, 40, None, [None, [[4]]], None, rows, best_of=2, best_by='draws', top_k=5)
+    assert set(plan.loop_kw) == {'temp', 'top_p', 'banned', 'soft', 'keep'} and (plan.by_draws, plan.want_scores) == (True, True)
+    assert plan.loop_kw['soft'] == dict(bias=None, top_k=[5] * 4, min_p=None) and plan.keep == [None, None, [[4]], [[4]]]
+    guide, plan = _guided_plan()
+    assert set(plan.loop_kw) == {'temp', 'top_p', 'banned', 'guidance'}
+    with pytest.raises(ValueError, match='t: guidance runs in the lock-step batch: slots= is not available with it'):
+        _guided_plan(slots=2)
+    for bad in ('x', [1]):
+        with pytest.raises(ValueError, match='slots must be None or a count of at least 1'):
+            gen_loop.plan_generation('t', 2, 40, None, None, None, rows, slots=bad)
+    with pytest.raises(ValueError, match=r'slots must be at least 1 \(got 0\)'):
+        gen_loop.plan_generation('t', 2, 40, None, None, None, rows, slots=0)
+
+
+def test_both_generators_refuse_a_slots_value_that_is_no_count_alike():
+    from emo_disentanger_amd import inference as inf, stage1_inference as s1
+    for bad in ('x', [2]):
+        with pytest.raises(ValueError, match='slots must be None or a count of at least 1'):
+            s1.generate_lead_sheets(_fake_model(False), {}, {}, [['Emotion_Q1']], slots=bad)
+        with pytest.raises(ValueError, match='slots must be None or a count of at least 1'):
+            inf.generate_accompaniments(_fake_model(False), {}, {}, [[[1]]], [[0]], slots=bad)
+
+
+def test_finish_generation_leaves_a_broken_pair_as_an_error_that_never_wins_a_pick():
+    import time
+    from emo_disentanger_amd import gen_loop
+    from emo_disentanger_amd._lib import EmoError
+    guide, plan = _guided_plan(best_of=2, best_by='forward', return_scores=True)
+    # rows: leaders [0 0 1 1 2 2], followers [1 1 2 2].  Candidate 0 of input 1 parts from its follower at token 2; every other pair holds
+    res = [[1, 3], [1, 4], [1, 5, 9], [1, 6], [1, 7], [1, 8]] + [[0, 5, 2], [0, 6], [0, 7], [0, 8]]
+    sc = [{'logp': np.array([NAN, -0.5 - j])} for j in range(10)]
+    seen = []
+
+    def forward(cands):                                              # the broken candidate would be the likeliest, were it scored
+        seen.append(list(cands))
+        return [NAN if isinstance(c, Exception) else float(j) for j, c in enumerate(cands)]
+
+    got, secs, picks, scores = gen_loop.finish_generation(res, sc, [1] * 10, plan, guide, forward, time.time())
+    assert len(seen) == 1 and len(seen[0]) == 6                      # the followers are gone before the ranking
+    assert isinstance(seen[0][2], EmoError) and 'stream 2 and its unconditioned follower 6 left lock-step: the ids part at token 2' in str(seen[0][2])
+    assert str(seen[0][2]).startswith('t: ')
+    assert [p['chosen'] for p in picks] == [0, 1, 0] and got == [[1, 3], [1, 6], [1, 7]]
+    assert isinstance(picks[1]['candidates'][0], EmoError) and picks[1]['scores'][0] is None
+    assert 'logp_uncond' not in scores[0] and scores[1]['logp_uncond'] is sc[7]['logp'] and secs >= 0.0     # (the follower's row)
+    # ranked by the recorded draws: the error's scores are None, NaN, and never win either
+    guide, plan = _guided_plan(best_of=2, best_by='draws')
+    got, _, picks = gen_loop.finish_generation(res, [dict(s, rank=np.array([-1, 0])) for s in sc], [1] * 10, plan, guide, None, time.time())
+    assert [p['chosen'] for p in picks] == [0, 1, 0] and picks[1]['nll_mean'][0] != picks[1]['nll_mean'][0]
+    # status words that part break a pair whatever the ids say
+    guide, plan = _guided_plan()
+    out, _ = gen_loop.finish_generation([[1, 3], [1, 4], [1, 5], [0, 4], [0, 5]], None, [1, 1, 1, 2, 1], plan, guide, None, time.time())
+    assert out[0] == [1, 3] and isinstance(out[1], EmoError) and 'status 1 against 2' in str(out[1]) and out[2] == [1, 5]
+
+
+def test_each_shared_kept_bar_refusal_raises_once_per_stage_with_the_stages_noun():
+    from emo_disentanger_amd import gen_loop, inference as inf, stage1_inference as s1
+    e2i = {'Track_LeadSheet': 1, 'Track_Full': 2, 'EOS_None': 3, 'PAD_None': 4, 'Bar_None': 5}
+    i2e = {i: e for e, i in e2i.items()}
+    two = lambda keep: inf.check_keep('two', keep, [[[7]], [[8], [9]]], 40, e2i)                 # noqa: E731
+    one = lambda keep, pb=None: s1.check_keep('one', keep, 2, 40, i2e, pb)                      # noqa: E731
+    for keep, text in (([None], 'keep has 1 entries for 2 %s'), ([[7], None], r'keep\[0\]\[0\] is neither None nor a sequence of token ids'),
+                       ([[['x']], None], r'keep\[0\]\[0\] is neither None nor a sequence of token ids'),
+                       ([None, [None, [40]]], r'keep\[1\]\[1\] holds token id 40 outside \[0, 40\)'),
+                       ([None, [[-1]]], r'keep\[1\]\[0\] holds token id -1 outside \[0, 40\)')):
+        with pytest.raises(ValueError, match='two: ' + text.replace('%s', 'inputs')):
+            two(keep)
+        with pytest.raises(ValueError, match='one: ' + text.replace('%s', 'primers')):
+            one(keep)
+    for check in (two, one):                                         # nothing kept is None; what is kept comes back as ints, bar for bar
+        assert check(None) is None and check([None, None]) is None and check([[None], [None, None]]) is None
+        assert check([[np.array([6, 7])], (None, (8,))]) == [[[6, 7]], [None, [8]]]
+    # each stage's own rule, through the walker's refuse(i, j, ids)
+    with pytest.raises(ValueError, match=r'two: keep\[1\]\[0\] holds Track_Full, which the grammar writes itself around a bar'):
+        two([None, [[6, 2]]])
+    with pytest.raises(ValueError, match=r'two: keep\[0\] has 2 bars, its lead sheet 1'):
+        two([[None, None], None])
+    with pytest.raises(ValueError, match=r'one: keep\[1\]\[0\] holds Bar_None, which the grammar writes or rejects itself'):
+        one([None, [[6, 5]]])
+    with pytest.raises(ValueError, match=r"one: keep\[1\]\[0\] lies under prompt_bars = 1: a primer's own bars are never kept"):
+        one([None, [[6]]], [0, 1])
+    with pytest.raises(ValueError, match='one: prompt_bars: 3 values for 2 primers'):
+        one([None, [[6]]], [0, 1, 2])
+    seen = []
+    assert gen_loop.check_kept_bars('w', [[None, [1, 2]], None, [[]]], 3, 9, 'things', lambda i, j, ids: seen.append((i, j, ids))) == [[None, [1, 2]], None, [[]]]
+    assert seen == [(0, 1, [1, 2]), (2, 0, [])]
